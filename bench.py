@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the per-batch joint-CVAE training step on MI355X (BASELINE.json metric: training images/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,9 @@ One "step" = cvae.py:2429-2461 of the reference on one synthetic batch already r
 zero_grad -> evaluate(x, y, with_beta=True) -> total.mean().backward() -> clip_grad_norm_(100) -> Adam, with the
 reparameterisation noise drawn on the device.  Workload = BASELINE.json configs[1] (CIFAR-10 conv CVAE, bs=512
 per GPU, fp32).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline figures.  --full adds what takes runs of its own:
+the roofline probes of the dominant kernels and the CPU baseline of the reference's step.
 """
 import argparse
 import json
@@ -282,6 +285,30 @@ def cpu_baseline(max_seconds=60.0):
             'thread_sweep_bs512': sweep, 'bs512': best, 'bs32': small_best, 'bs32_runs': small}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, net, losses, meas):
+    """--dump-outputs: what a caller of the timed step holds after its last call, one float32 / float64 .npy file per array -
+    the losses it returned (`loss.<key>`), its measures (`measure.<key>`) and the model state it updated in place
+    (`state.<key>`: parameters, BatchNorm running statistics; integer counters as float64)."""
+    import numpy as np
+    arrays = {}
+    for k, v in losses.items():
+        arrays['loss.' + k] = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+    for k, v in (meas.items() if meas is not None else ()):
+        arrays['measure.' + k] = np.asarray(v, dtype=np.float64)
+    for k, v in net.state_dict().items():
+        v = v.detach()
+        arrays['state.' + k] = (v.float() if v.is_floating_point() else v.double()).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def _watchdog(seconds):
     """Abort (exit code 3, stacks dumped) instead of hanging the box if the process makes no progress for `seconds`."""
     import faulthandler
@@ -294,7 +321,11 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline probes of the dominant kernels and the CPU baseline (runs of their own beside the timed steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the losses, measures and model state of the last timed step as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
     ap.add_argument('--batch', type=int, default=None, help='diagnostics only: per-GPU batch (the metric is defined at 512)')
     ap.add_argument('--sync-bn', action='store_true', help='BatchNorm statistics over all ranks (default: per rank)')
     ap.add_argument('--graph', action='store_true',
@@ -308,6 +339,8 @@ def main():
                     help="diagnostics: other BASELINE configs; 'eval' = the label-free evaluation pass (SURVEY.md §8f-1): config 2, "
                          "N=512 images, L=128 latent draws (decoder batch 66 048) per step")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
     eval_mode = a.workload == 'eval'
     a.workload = 2 if eval_mode else int(a.workload)
     # What is timed (round 5): the captured step.  The eager loop needs ~3.0 ms of host time per 3.6 ms step and may run at most one
@@ -374,7 +407,8 @@ def main():
     for i in range(a.warmup):
         _, meas = one_step(i, meas)
     probe = None
-    want_probe = a.workload == 2 and a.dtype == 'f32' and not eval_mode and os.environ.get('JVAE_BENCH_NO_PROBES') != '1'
+    want_probe = (a.full and a.workload == 2 and a.dtype == 'f32' and not eval_mode
+                  and os.environ.get('JVAE_BENCH_NO_PROBES') != '1')
     if want_probe:
         # the dominant kernel (imager.15 forward: ConvT 32->32 5x5 s1 on the 2N x 32 x 32 x 32 decoder activation) timed INSIDE
         # running steps: one HIP-event pair per step around that launch, on the stream it is launched on.  Eager timing: inside the
@@ -397,6 +431,8 @@ def main():
         host_marks[i + 1] = time.time()
     sync()
     dt = time.time() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, net, losses, meas)
     probe_steps = 0
     if probe is not None and a.graph:
         # the instrumented EAGER steps behind the timed replay (same model, same batch, same kernels in the same order)
@@ -472,13 +508,13 @@ def main():
             # target (>= 0.5) is phrased in; most of those FLOPs run on the bf16 pipes (6 bf16 products per fp32 product)
             out['step_throughput_vs_f32_mfma_peak'] = value / world * WORKLOADS[a.workload][1] / (MFMA_F32_PEAK if a.dtype == 'f32' else MFMA_BF16_PEAK)
         # the roofline probes and the CPU baseline belong to the headline config (JVAE_BENCH_NO_PROBES=1: kernel traces of the step alone)
-        if a.workload == 2 and a.dtype == 'f32' and not eval_mode and os.environ.get('JVAE_BENCH_NO_PROBES') != '1':
+        if want_probe:
             out['roofline'] = dominant_kernel_roofline(device, in_step_ms=probe.times_ms() if probe is not None else None,
                                                        where=('%d eager train_step() calls run right after the timed graph-replay region (events cannot be '
                                                               'recorded inside a captured graph)' % probe_steps) if a.graph else 'the timed steps')
             out['roofline_wgrad'] = wgrad_kernel_roofline(device)
             out['roofline_hbm'] = bn_backward_hbm(device)
-        if world == 1 and not a.no_cpu_baseline and a.workload == 2 and a.dtype == 'f32' and not eval_mode:
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == 2 and a.dtype == 'f32' and not eval_mode:
             out['cpu_baseline'] = cpu_baseline()
         print(json.dumps(out))
     if dist is not None:

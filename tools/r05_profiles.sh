@@ -9,8 +9,8 @@ if [ $part = a ]; then
   bash tools/gpu_job.sh
   tail -3 gpurun_out/check/all.log > $O/r05_gpu_suite.txt
   tail -1 gpurun_out/check/smoke.log >> $O/r05_gpu_suite.txt
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_n1.json 2> $O/bench_n1.err
-  python bench.py --gpus 1 --steps 20 --warmup 5 --eager --no-cpu-baseline > $O/r05_bench_eager.json 2>/dev/null
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r05_bench_n1.json 2> $O/bench_n1.err
+  python bench.py --gpus 1 --steps 20 --warmup 5 --eager --full --no-cpu-baseline > $O/r05_bench_eager.json 2>/dev/null
   bash tools/prof_bench.sh r05_bench > $O/r05_bench_step_breakdown.txt 2>&1
   cp $(find gpurun_out/r05_bench -name "*kernel_stats.csv") $O/r05_bench_kernel_stats.csv
   bash tools/prof_noov.sh r05_noov > $O/r05_bench_no_overlap_step_breakdown.txt 2>&1

@@ -48,7 +48,10 @@ int jvae_splitk_fold_f32(const float* part, const float* bias, float* y, int S, 
  * ((Cout,Cin,KH,KW) for Conv2d, (Cin,Cout,KH,KW) for ConvTranspose2d); S stride, P padding,
  * OP output_padding (transposed only).  Replaces nn.Conv2d / nn.ConvTranspose2d built by
  * build_de_conv_layers (module/vae_layers/conv.py:186-196) and their autograd backward.
- * wgrad: accumulate != 0 adds into dw/dbias (autograd .grad accumulation), else overwrites. */
+ * wgrad: accumulate != 0 adds into dw/dbias (autograd .grad accumulation), else overwrites.
+ * ws / ws_bytes: device scratch of at least jvae_conv2d_workspace_bytes(...) bytes (every direction); an entry point given
+ * less than its selected kernel needs returns -3 (JVAE_EWORKSPACE) - the kernel depends on the geometry, the call's arguments
+ * and jvae_conv2d_set_split_bf16 only, never on the workspace size. */
 size_t jvae_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP,
                                    int transposed);
 /* Arithmetic unit of the stride-1 5x5 layers with >= 16 input channels (forward, ConvTranspose2d forward, dgrad):
@@ -145,7 +148,8 @@ int jvae_bn_finalize_f32(const float* x, const float* gamma, const float* beta,
                          const float* ext_stats, int ext_nsplit, const float* ext_pivot,
                          void* ws, size_t ws_bytes, void* stream);
 /* 1 when both the forward and the weight gradient of this geometry can apply in_scale / in_shift / in_relu to the layer
- * input (the implicit 5x5 kernels); the *_aff entry points return -2 otherwise. */
+ * input (the implicit 5x5 kernels; the one for <= 4 output channels with at most 256 input channels); the *_aff entry points
+ * return -2 otherwise. */
 int jvae_conv2d_affine_ok(int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed);
 int jvae_conv2d_fwd_aff_f32(const float* x, const float* w, const float* bias, float* y, float* stats, int* nsplit,
                             const float* in_scale, const float* in_shift, int in_relu,
@@ -246,6 +250,9 @@ int jvae_bn_bwd_sync_b8(const void* dy, const void* x, const float* gamma, const
                         const float* local_sums, const float* global_sums, int world,
                         void* dx, float* dgamma, float* dbeta, int accumulate,
                         int N, int C, long HW, int relu, void* ws, size_t ws_bytes, void* stream);
+/* Deferred BatchNorm(+ReLU) on the B8 layer input (as jvae_conv2d_affine_ok / *_aff_f32): in_scale / in_shift hold
+ * ceil(Cin/8)*8 floats (jvae_bn_finalize_b8), ceil(Cin/8)*8 <= 256.  in_relu = 2 (leaky ReLU) has no bf16 kernel: both
+ * *_aff_b8 entry points return -2 for it before writing anything. */
 int jvae_conv2d_affine_ok_b8(int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed);
 int jvae_conv2d_fwd_aff_b8(const void* x, const float* w, const float* bias, void* y, int y_f32, float* stats, int* nsplit,
                            const float* in_scale, const float* in_shift, int in_relu,

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     u32x4* Xs = reinterpret_cast<u32x4*>(lds_raw);
     u32x4* Ws = Xs + G::XS;
-    __shared__ __attribute__((aligned(16))) float ctab[AFF ? 2 * 256 : 4];   // (scale, shift) of all input channels (<= 256)
+    __shared__ __attribute__((aligned(16))) float ctab[AFF ? 2 * 256 : 4];   // (scale, shift) of all input channels (jvae_conv_route: <= 256)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (AFF)
@@ -354,12 +354,8 @@ int launch_b8(const B8FwdP& p, hipStream_t st) {
     dim3 grid((unsigned)((pixels + G::PIX - 1) / G::PIX), (unsigned)(p.OP / G::WCOLS));
     if (G::OHW < G::PIX) grid.x = (unsigned)((p.N + G::NIMG - 1) / G::NIMG);
     g_b8_splits = (int)grid.x;
-    if (p.aff.sc) {
-        if (p.CBin * 8 > 256) return JVAE_ENOTSUP;
-        hipLaunchKernelGGL((conv5_b8_kernel<S, OW, MT, NT, true>), grid, dim3(256), G::LDS_BYTES, st, p);
-    } else {
-        hipLaunchKernelGGL((conv5_b8_kernel<S, OW, MT, NT, false>), grid, dim3(256), G::LDS_BYTES, st, p);
-    }
+    if (p.aff.sc) hipLaunchKernelGGL((conv5_b8_kernel<S, OW, MT, NT, true>), grid, dim3(256), G::LDS_BYTES, st, p);
+    else hipLaunchKernelGGL((conv5_b8_kernel<S, OW, MT, NT, false>), grid, dim3(256), G::LDS_BYTES, st, p);
     JVAE_LAUNCH_CHECK();
     return 0;
 }

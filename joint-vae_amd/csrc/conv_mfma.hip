@@ -318,21 +318,14 @@ int jvae_conv5_pack(const float* w, float* wp, int C, int O, int swap, int flip,
     return 0;
 }
 
-// ws must hold Cin*25*Cout floats (the packed weights).  swap / flip: see pack_kernel.
 // Upper bound of the number of per-channel partials a stats-producing launch writes (smallest tile: 128 pixels).
 int jvae_conv5_fwd_max_splits(int N, int OW) { return (int)(((long)N * OW * OW + 127) / 128) + 1; }
 
+// The fp32 matrix-core kernel (jvae_conv_route picks it).  ws must hold Cin*25*Cout floats (the packed weights).  swap / flip:
+// see pack_kernel.
 int jvae_conv5_fwd(const float* in, const float* w, int swap, int flip, const float* bias, float* out,
                    int N, int Cin, int H, int W, int Cout, int OW, int S, int P, float* ws, hipStream_t st,
                    float* stats, int* nsplit, const InAff* aff) {
-    if (jvae_conv5_x3_ok(Cin, H, W, Cout, OW, OW, S, P))      // stride-1 layers with >= 16 input channels: conv_x3.hip
-        return jvae_conv5_x3_fwd(in, w, swap, flip, bias, out, N, Cin, H, W, Cout, OW, S, P, ws, st, stats, nsplit, aff);
-    // <= 4 input channels: vector ALUs (conv_smallco.hip) - for the DGRAD role only (no bias, no BatchNorm sums: the image head's
-    // dgrad, 68 -> 56 us).  The first layer's FORWARD gains 3 us there (47 -> 44) and stays on this kernel: another summation order
-    // moves its outputs by 1e-7, which at the small-batch goldens flips single ReLU units further up (b2_n8_vib: one unit of
-    // features.13, global gradient norm 3e-4 off instead of 2e-6; tests/diagnostics/vib_grad_diag.py).
-    if (!aff && jvae_conv5_smallci_ok(Cin, H, W, Cout, OW, S, P, !bias && !stats))
-        return jvae_conv5_smallci(in, w, swap, flip, bias, out, N, Cin, W, Cout, ws, st, stats, nsplit);
     {   // packed weights: the step's cache slot (refreshed once per step, pack_cache.hip) or this call's workspace
         bool fresh = true;
         float* slot = (float*)jvae_pack_cache_get(JVAE_PACK_F32, w, Cin, Cout, swap, flip, &fresh);

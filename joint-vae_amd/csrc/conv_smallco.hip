@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256, 4) void conv5_smallco2_kernel(SmP p) {
     constexpr int CH = ROWS * WP;
     constexpr int XS = CC * CH;
     __shared__ __attribute__((aligned(16))) float Xs[XS];
-    __shared__ float ctab[2 * 256];                // (scale, shift) of the deferred BatchNorm, all input channels (host: Cin <= 256)
+    __shared__ float ctab[2 * 256];                // (scale, shift) of the deferred BatchNorm, all input channels (jvae_conv_route: Cin <= 256)
 
     const int tid = threadIdx.x;
     constexpr int TPI = OH / TH;                   // tiles per image
@@ -284,7 +284,6 @@ bool jvae_conv5_smallco_ok(int Cin, int H, int W, int Cout, int KH, int KW, int 
 int jvae_conv5_smallco(const float* in, const float* w, const float* bias, float* out, int N, int Cin, int W, int Cout,
                        hipStream_t st, const InAff* aff) {
     SmP p{in, w, bias, out, N, Cin, 2, aff ? *aff : InAff{nullptr, nullptr, 0}};
-    if (p.aff.sc && Cin > 256) return JVAE_ENOTSUP;          // coefficient table of the deferred BatchNorm
     if (W == 32) return launch_sm<32>(p, Cout, st);
     if (W == 64) return launch_sm<64>(p, Cout, st);
     return JVAE_ENOTSUP;

@@ -216,12 +216,8 @@ int launch_t2b8(const T2B8P& p, hipStream_t st) {
     dim3 grid(G::HSWS >= G::PIX ? (unsigned)((long)p.N * G::HSWS / G::PIX) : (unsigned)((p.N + G::NIMG - 1) / G::NIMG),
               (unsigned)(p.OP / 32));
     g_t2b8_splits = (int)grid.x;
-    if (p.aff.sc) {
-        if (p.CBin * 8 > 256) return JVAE_ENOTSUP;
-        hipLaunchKernelGGL((convt2_b8_kernel<WS, NW, true>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
-    } else {
-        hipLaunchKernelGGL((convt2_b8_kernel<WS, NW, false>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
-    }
+    if (p.aff.sc) hipLaunchKernelGGL((convt2_b8_kernel<WS, NW, true>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
+    else hipLaunchKernelGGL((convt2_b8_kernel<WS, NW, false>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
     JVAE_LAUNCH_CHECK();
     return 0;
 }

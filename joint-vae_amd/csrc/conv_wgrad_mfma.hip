@@ -277,7 +277,7 @@ inline int pick_cb(int S, int WS, int Cb) {
 
 }  // namespace
 
-// dw (+)= sum over the G slabs (a, b, tap) in a fixed order; shared with the bf16 path (conv_wgrad_b8.hip)
+// dw (+)= sum over the G slabs (a, b, tap) in a fixed order; shared with the split-bf16 and bf16 kernels
 int jvae_wgrad_slab_reduce(const float* slab, float* dw, int G, int Ca, int Cb, int accumulate, int swapflip, hipStream_t st,
                            int tapmajor) {
     const int total = Ca * Cb * 25;
@@ -316,12 +316,11 @@ size_t jvae_conv5_wgrad_ws_floats(int N, int Ca, int Cb, int S, int WS) {
     return f32 > x3 ? f32 : x3;
 }
 
-// dW (+)= ... ; swapflip: the caller passed the role-swapped problem (see wgrad_reduce_kernel).
+// dW (+)= ... on the fp32 matrix cores (jvae_conv_route picks this or conv_wgrad_x3.hip); swapflip: the caller passed the
+// role-swapped problem (see wgrad_reduce_kernel).
 int jvae_conv5_wgrad(const float* ps, const float* q, float* dw, int accumulate, int swapflip,
                      int N, int Ca, int WS, int Cb, int S, int P, float* ws, hipStream_t st,
                      const InAff* aff_p, const InAff* aff_q) {
-    if (jvae_conv5_wgrad_x3_ok(Ca, WS, WS, Cb, WS * S, WS * S, S, P))      // split-bf16 arithmetic (conv_wgrad_x3.hip)
-        return jvae_conv5_wgrad_x3(ps, q, dw, accumulate, swapflip, N, Ca, WS, Cb, S, P, ws, st, aff_p, aff_q);
     const InAff none{nullptr, nullptr, 0};
     WgP p{ps, q, ws, N, Ca, Cb, P, slab_count(N, Ca, Cb, S, WS), aff_p ? *aff_p : none, aff_q ? *aff_q : none};
     int rc = JVAE_ENOTSUP;

@@ -594,10 +594,10 @@ int launch_wgx3(const WgX3P& p, hipStream_t st) {
     if (MODE == 1 || MODE == 3) grid.z = 1;
     const bool aff = p.aff_p.sc || p.aff_q.sc;
     const bool leaky = (p.aff_p.sc && p.aff_p.relu == JVAE_ACT_LEAKY) || (p.aff_q.sc && p.aff_q.relu == JVAE_ACT_LEAKY);
-    // the stride-2 forms keep ONE register set of (scale, shift) for the side that carries a deferred BatchNorm
-    if (S == 2 && p.aff_p.sc && p.aff_q.sc) return JVAE_ENOTSUP;
+    // the stride-2 forms keep ONE register set of (scale, shift) for the side that carries a deferred BatchNorm - only
+    // the layer input carries one (jvae_wgrad_operands).  The bf16 one-plane form (NPL = 1) has ReLU only: jvae_conv_route refuses
+    // leaky ReLU on the bf16 path.
     if constexpr (NPL == 1) {
-        if (leaky) return JVAE_ENOTSUP;            // the bf16 one-plane form has ReLU only (cvae.set_compute_dtype refuses 'leaky')
         static bool attr1 = false;
         if (!attr1) {
             const void* fns[2] = {reinterpret_cast<const void*>(&conv5_wgrad_x3_kernel<S, WS, MODE, 0, true, 1>),

@@ -703,13 +703,9 @@ int launch_x3(const X3P& p, hipStream_t st) {
     X3P q = p;
     q.tpw = 1;
     if (SH && grid.x % 2 == 0 && (long)grid.x * grid.y >= 2048) { q.tpw = 2; grid.x /= 2; }
-    if (q.aff.sc) {
-        if (q.Cin > 256) return JVAE_ENOTSUP;
-        if (q.aff.relu == JVAE_ACT_LEAKY) hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 2, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
-        else hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 1, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
-    } else {
-        hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 0, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
-    }
+    if (q.aff.sc && q.aff.relu == JVAE_ACT_LEAKY) hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 2, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
+    else if (q.aff.sc) hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 1, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
+    else hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 0, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
     JVAE_LAUNCH_CHECK();
     return 0;
 }

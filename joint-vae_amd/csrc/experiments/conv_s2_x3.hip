@@ -1,5 +1,5 @@
 // EXPERIMENT, NOT PART OF THE BUILD (round 5; result and reasons: profiles/r05_conv_s2_x3_ab.txt, profiles/NOTES.md).  To build it: copy this
-// file to csrc/, apply conv_s2_x3_hooks.patch (pack kind JVAE_PACK_S2S, dispatch in jvae_conv5_fwd), make; tools/s2_probe.py measures it.
+// file to csrc/, apply conv_s2_x3_hooks.patch (pack kind JVAE_PACK_S2S, a route entry of jvae_conv_route), make; tools/s2_probe.py measures it.
 //
 // Stride-2 5x5 convolution of the forward type (padding 2: 2H -> H) on the bf16 matrix cores with exact 3-way operand splitting -
 // the polyphase form.  Round 5, built last; conv_t2_x3.hip's machinery (v_mfma_f32_16x16x32_bf16, K = 32 channels of ONE tap,

@@ -43,3 +43,7 @@ struct ConvGeom {
     int Cs, Hs, Ws;   // small side: channels, height, width
     int KH, KW, S, P; // kernel, stride, padding (as in nn.Conv2d / nn.ConvTranspose2d)
 };
+
+// dw (+)= sum over the G weight-gradient slabs (a, b, tap) in a fixed order (conv_wgrad_mfma.hip; every wgrad kernel family)
+int jvae_wgrad_slab_reduce(const float* slab, float* dw, int G, int Ca, int Cb, int accumulate, int swapflip, hipStream_t st,
+                           int tapmajor = 0);

@@ -81,6 +81,46 @@ def test_conv_all_directions(cin, cout, k, s, p, op, tr, H, N):
     assert rel(bd.grad, br.grad) < 2e-5
 
 
+@pytest.mark.parametrize('split', [1, 0])
+def test_conv_entry_points_refuse_a_short_workspace(split):
+    """An fp32 convolution given less workspace than its kernel needs returns JVAE_EWORKSPACE (-3), as the bf16 entry
+    points do, instead of running on another kernel; with the queried size it runs.  The buffer is full-size in both
+    calls, so a missing check could not write past it."""
+    import ctypes
+    from jvae_hip import lib as L, ops
+    lib = L.load()
+    N, cin, cout, H = 8, 32, 64, 16                              # a 5x5 layer of conv32
+    spec = ops.ConvSpec(cin, cout, 5, 1, 2)
+    geom = spec.geom(N, H, H)
+    g = torch.Generator().manual_seed(3)
+    x, gy = torch.randn(N, cin, H, H, generator=g), torch.randn(N, cout, H, H, generator=g)
+    w, b = torch.randn(cout, cin, 5, 5, generator=g) / math.sqrt(cin * 25), torch.randn(cout, generator=g)
+    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    yr = F.conv2d(xr, wr, b, padding=2)
+    yr.backward(gy)
+    xd, wd, bd, gyd = (t.to(DEV) for t in (x, w, b, gy))
+    y, gx, gw = torch.empty_like(gyd), torch.empty_like(xd), torch.empty_like(wd)
+    nb = lib.jvae_conv2d_workspace_bytes(*geom)
+    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    st = L.stream_ptr()
+    calls = {
+        'fwd': lambda n: lib.jvae_conv2d_fwd_f32(L.ptr(xd), L.ptr(wd), L.ptr(bd), L.ptr(y), *geom, L.ptr(ws), n, st),
+        'dgrad': lambda n: lib.jvae_conv2d_dgrad_f32(L.ptr(gyd), L.ptr(wd), L.ptr(gx), *geom, L.ptr(ws), n, st),
+        'wgrad': lambda n: lib.jvae_conv2d_wgrad_f32(L.ptr(xd), L.ptr(gyd), L.ptr(gw), None, 0, *geom, L.ptr(ws), n, st),
+    }
+    old = lib.jvae_conv2d_set_split_bf16(split)
+    try:
+        for name, call in calls.items():
+            assert call(0) == -3, name
+            assert call(ctypes.c_size_t(nb)) == 0, name
+        torch.cuda.synchronize()
+    finally:
+        lib.jvae_conv2d_set_split_bf16(old)
+    assert rel(y, yr) < 2e-5
+    assert rel(gx, xr.grad) < 2e-5
+    assert rel(gw, wr.grad) < 5e-5
+
+
 @pytest.mark.parametrize('N', [64, 37, 512])
 @pytest.mark.parametrize('bias', [True, False])
 def test_small_grid_7x7_head_at_training_batch_sizes(N, bias):

@@ -418,6 +418,44 @@ def test_b8_conv_with_deferred_batchnorm_input(cin, cout, k, s, p, op, tr, H):
     assert rel(gw, wr.grad) < 2e-3
 
 
+def test_b8_conv_refuses_a_leaky_relu_input():
+    """in_relu = 2 (leaky ReLU) has no bf16 kernel: the forward and the weight gradient with a deferred BatchNorm return
+    JVAE_ENOTSUP (-2) on a geometry jvae_conv2d_affine_ok_b8 accepts, before anything is written; plain ReLU runs."""
+    import ctypes
+    from jvae_hip import lib as L, ops, ops_b8
+    lib = L.load()
+    N, cin, cout, H = 5, 32, 64, 16
+    spec = ops.ConvSpec(cin, cout, 5, 1, 2)
+    assert ops_b8.conv_affine_ok(spec, N, H, H)
+    geom = spec.geom(N, H, H)
+    nb = lib.jvae_conv2d_workspace_bytes_b8(*geom)
+    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    xb = ops_b8.pack(torch.randn(N, cin, H, H, device=DEV))
+    gyb = ops_b8.pack(torch.randn(N, cout, H, H, device=DEV))
+    yb = ops_b8.pack(torch.full((N, cout, H, H), 3.0, device=DEV))
+    w = torch.randn(cout, cin, 5, 5, device=DEV) / math.sqrt(cin * 25)
+    coef = torch.ones(2, cin, device=DEV)
+    dw = torch.full((cout, cin, 5, 5), 3.0, device=DEV)
+    y0, dw0 = yb.clone(), dw.clone()
+    st, ns = L.stream_ptr(), ctypes.c_int(7)
+
+    def fwd(relu):
+        return lib.jvae_conv2d_fwd_aff_b8(L.ptr(xb), L.ptr(w), None, L.ptr(yb), 0, None, ctypes.byref(ns), L.ptr(coef[0]),
+                                          L.ptr(coef[1]), relu, *geom, L.ptr(ws), nb, st)
+
+    def wgrad(relu):
+        return lib.jvae_conv2d_wgrad_aff_b8(L.ptr(xb), L.ptr(gyb), L.ptr(dw), None, 0, L.ptr(coef[0]), L.ptr(coef[1]), relu,
+                                            *geom, L.ptr(ws), nb, st)
+
+    assert fwd(2) == -2 and ns.value == 0
+    assert wgrad(2) == -2
+    torch.cuda.synchronize()
+    assert torch.equal(yb, y0) and torch.equal(dw, dw0)
+    assert fwd(1) == 0 and wgrad(1) == 0
+    torch.cuda.synchronize()
+    assert not torch.equal(dw, dw0)
+
+
 @pytest.mark.parametrize('dseed,nseed,strict', [(6, 9, True), (1, 7, False)])
 def test_b8_training_sequence_tracks_fp32(dseed, nseed, strict):
     """BASELINE configs[4] (bf16 mode, 3x64x64 geometry): 24 optimiser steps on the same data with the same noise seed, bf16

@@ -68,6 +68,17 @@ def test_out_shape_entry_point_is_host_only():
     assert ops.ConvSpec(64, 64, 8, 1, 0, 0, transposed=True).out_hw(1, 1) == (8, 8)
 
 
+def test_affine_ok_refuses_smallco_beyond_its_coefficient_table():
+    """The 5x5 kernel for <= 4 output channels (conv_smallco.hip, the conv32 head) holds the deferred BatchNorm's coefficients
+    of at most 256 input channels: the query says no beyond that, so *_aff entry points are never offered a geometry they
+    would refuse.  Host-only."""
+    from jvae_hip import lib
+    q = lib.load().jvae_conv2d_affine_ok
+    assert q(8, 320, 32, 32, 3, 5, 5, 1, 2, 0, 0) == 0
+    assert q(8, 256, 32, 32, 3, 5, 5, 1, 2, 0, 0) == 1
+    assert q(8, 32, 32, 32, 3, 5, 5, 1, 2, 0, 0) == 1          # the conv32 head itself
+
+
 def test_batchnorm_launch_plan_partitions_every_batch_size():
     """The reference keeps the ragged last batch (cvae.py:2245-2249; BatchNorm2d works for any N, conv.py:214-220), so
     every batch size must partition into image ranges that are never negative, never overlap and cover [0, N) exactly -

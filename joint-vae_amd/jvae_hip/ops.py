@@ -3,6 +3,7 @@
 PyTorch is plumbing here (device memory, streams, the autograd tape); every FLOP of the training step is
 executed by the hand-written gfx950 kernels.  Every function raises if its tensors are not on the GPU.
 """
+import contextlib
 import math
 from ctypes import byref, c_int
 
@@ -310,28 +311,109 @@ def conv_wgrad_raw(x, gy, spec, wshape, want_bias, w_slot=None, b_slot=None, aff
     return (None, None) if inplace else (gw, gb)
 
 
+# ------------------------------------------------------------------------------------------- layouts
+FWD, DGRAD, WGRAD = 1, 2, 4          # directions of a convolution (the bits of jvae_conv2d_native_b8)
+
+
+class Layout:
+    """What the convolution and BatchNorm ops below need to know about one activation layout.  This class is fp32 NCHW
+    (F32); ops_b8.B8Layout overrides what differs for the bf16 B8 layout."""
+    sfx = '_f32'                     # suffix of the C entry points
+    ws_sfx = ''                      # suffix of the BatchNorm workspace query
+    acts = BN_ACT                    # activations its kernels apply (in the BatchNorm kernels: the `relu` code)
+
+    def dims(self, x, C):
+        """-> (N, C, P); C is the caller's channel count (a B8 tensor cannot tell it)."""
+        N, C = x.shape[0], x.shape[1]
+        return N, C, x.numel() // max(N * C, 1)
+
+    def coef_width(self, C):
+        return C
+
+    def prep(self, x, what):
+        return _c(_f32(x, what))
+
+    def to_f32(self, t, C):          # plain conversions between the kernels of one op (no autograd node)
+        return t
+
+    def from_f32(self, t):
+        return t
+
+    def native(self, spec, N, H, W):
+        return FWD | DGRAD | WGRAD
+
+    def affine_ok(self, spec, N, H, W):
+        return conv_affine_ok(spec, N, H, W)
+
+    def conv_fwd(self, x, w, b, spec, want_stats, aff, out_f32):
+        """-> (y, stats, nsplit).  out_f32 only matters to a layout other than fp32."""
+        if aff is not None:
+            return conv_fwd_aff_raw(x, w, b, spec, aff, want_stats)
+        if want_stats:
+            return conv_fwd_stats_raw(x, w, b, spec)
+        return conv_fwd_raw(x, w, b, spec), None, 0
+
+    def conv_dgrad(self, gy, w, spec, N, H, W):
+        return conv_dgrad_raw(gy, w, spec, (N, spec.cin, H, W))
+
+    def conv_wgrad(self, *args):
+        return conv_wgrad_raw(*args)
+
+    def bn(self, name, *args, ws=None):
+        """Call the BatchNorm entry point `name` of this layout on the current stream."""
+        name += self.sfx
+        extra = () if ws is None else (L.ptr(ws), ws.numel())
+        L.check(getattr(L.load(), name)(*args, *extra, L.stream_ptr()), name)
+
+    def bn_workspace(self, C, device):
+        return L.workspace(getattr(L.load(), 'jvae_bn_workspace_bytes' + self.ws_sfx)(C), device)
+
+    def bn_fwd(self, *args, ext, ws):
+        """ext = (stats, nsplit, pivot) or nulls.  jvae_bn_fwd_f32 is jvae_bn_fwd_ext_f32 without the sums."""
+        if ext[0] is None:
+            self.bn('jvae_bn_fwd', *args, ws=ws)
+        else:
+            self.bn('jvae_bn_fwd_ext', *args, *ext, ws=ws)
+
+    def coef_args(self, coef):
+        return L.ptr(coef[0]), L.ptr(coef[1])          # jvae_bn_finalize_f32: separate scale and shift rows
+
+    def bn_bwd_sync(self, *args, ws):
+        self.bn('jvae_bn_bwd_sync', *args)              # jvae_bn_bwd_sync_f32 takes no workspace
+
+
+F32 = Layout()
+
+
+def layout_of(t):
+    return _b8.B8 if _b8.is_b8(t) else F32
+
+
 class _Conv(torch.autograd.Function):
-    """nn.Conv2d / nn.ConvTranspose2d (conv.py:186-196)."""
+    """nn.Conv2d / nn.ConvTranspose2d (conv.py:186-196) in the layout of its input.  A direction without a native kernel in
+    that layout runs on the fp32 kernels between two conversions.  out_f32: a B8 input gives an fp32 NCHW output."""
 
     @staticmethod
-    def forward(ctx, x, w, b, spec, dead_bias, stats_out, aff=None):
-        x = _c(_f32(x, 'conv'))
+    def forward(ctx, x, w, b, spec, dead_bias, stats_out, aff, out_f32):
+        lay = layout_of(x)
+        x = lay.prep(x, 'conv')
         if not L.span_depth:               # a convolution called outside forward() / evaluate() (net.imager(z), a raw module call):
             L.pack_cache_end()             # nobody vouches for the weights now - an armed cache (train-mode evaluate() without its
         ctx.w_ref, ctx.b_ref = w, b        # backward yet) may predate a change through .data (ADVICE r4); pack per call
         w = _c(w)
-        ctx.aff = aff
-        if aff is not None:                # x is a pre-BatchNorm tensor: normalise (+ReLU) while staging it
-            y, st, ns = conv_fwd_aff_raw(x, w, b, spec, aff, stats_out is not None)
-            if stats_out is not None:
-                stats_out['stats'], stats_out['nsplit'], stats_out['pivot'] = st, ns, b
-        elif stats_out is not None:        # the caller is a train-mode BatchNorm: let the conv epilogue do its sums
-            y, st, ns = conv_fwd_stats_raw(x, w, b, spec)
-            stats_out['stats'], stats_out['nsplit'], stats_out['pivot'] = st, ns, b
+        native = lay.native(spec, x.shape[0], x.shape[2], x.shape[3])
+        if aff is not None and (native & (FWD | WGRAD)) != FWD | WGRAD:
+            raise L.JvaeHipError('a deferred BatchNorm needs native forward and weight-gradient kernels (conv_affine_ok)')
+        want_stats = stats_out is not None           # the caller is a train-mode BatchNorm: let the conv epilogue do its sums
+        if native & FWD:                   # with aff, x is a pre-BatchNorm tensor: normalise (+ReLU) while staging it
+            y, st, ns = lay.conv_fwd(x, w, b, spec, want_stats, aff, out_f32)
         else:
-            y = conv_fwd_raw(x, w, b, spec)
+            y, st, ns = F32.conv_fwd(lay.to_f32(x, spec.cin), w, b, spec, want_stats, None, False)
+            y = y if out_f32 else lay.from_f32(y)
+        if want_stats:
+            stats_out['stats'], stats_out['nsplit'], stats_out['pivot'] = st, ns, b
         ctx.save_for_backward(x, w)
-        ctx.spec = spec
+        ctx.lay, ctx.native, ctx.spec, ctx.out_f32, ctx.aff = lay, native, spec, out_f32, aff
         ctx.has_bias = b is not None
         ctx.dead_bias = dead_bias
         return y
@@ -339,86 +421,104 @@ class _Conv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        gy = _c(gy)
+        lay, spec = ctx.lay, ctx.spec
+        N, H, W = x.shape[0], x.shape[2], x.shape[3]
+        gys = {F32 if ctx.out_f32 else lay: _c(gy)}      # gy in each layout it is needed in: converted once per layout
+
+        def gy_in(want):
+            if want not in gys:
+                have, g = next(iter(gys.items()))
+                gys[want] = want.from_f32(g) if have is F32 else have.to_f32(g, spec.cout)
+            return gys[want]
         gx = gw = gb = None
         _close_span_after_backward()
         want_b = ctx.has_bias and ctx.needs_input_grad[2] and not ctx.dead_bias
-        w_slot = b_slot = None
+        wgrad = ctx.needs_input_grad[1] or want_b
         on_side = False
-        if ctx.needs_input_grad[1] or want_b:
+        if wgrad:
             w_slot = _grad_slot(ctx.w_ref)
             b_slot = _grad_slot(ctx.b_ref) if want_b else None
             # the first layer of the model (its input needs no gradient) is the END of the backward chain: its weight
             # gradient stays on the main stream, where it runs beside the side stream's last kernels instead of behind them
             on_side = (OVERLAP_WGRAD and ctx.needs_input_grad[0] and w_slot is not None
                        and (b_slot is not None or not want_b))
+        if ctx.needs_input_grad[0]:
+            dl = lay if ctx.native & DGRAD else F32
+            gyd = gy_in(dl)
         if on_side:
             # the weight gradient needs gy and x, not this layer's dgrad: the side stream forks off BEFORE the dgrad is
             # queued.  In a captured graph the dgrad is then the first successor of gy's producer and stays on the
             # launch queue (the runtime moves later successors to other queues: a 10 us hand-over per hop of the chain)
-            main = torch.cuda.current_stream(x.device)
             side = L.side_stream(x.device)
-            side.wait_stream(main)
+            side.wait_stream(torch.cuda.current_stream(x.device))
         if ctx.needs_input_grad[0]:
-            gx = conv_dgrad_raw(gy, w, ctx.spec, x.shape)
-        if ctx.needs_input_grad[1] or want_b:
+            gx = dl.conv_dgrad(gyd, w, spec, N, H, W)
+            gx = gx if dl is lay else lay.from_f32(gx)
+        if wgrad:
+            # on the side stream: in-place into the flat gradient buffer, nothing downstream of this node consumes the
+            # result before the optimiser, so the kernel (and the conversions only it needs) overlaps the rest of backward
+            with torch.cuda.stream(side) if on_side else contextlib.nullcontext():
+                wl = lay if ctx.native & WGRAD else F32
+                xw = x if wl is lay else lay.to_f32(x, spec.cin)
+                gw, gb = wl.conv_wgrad(xw, gy_in(wl), spec, w.shape, want_b, w_slot, b_slot, ctx.aff)
             if on_side:
-                # in-place into the flat gradient buffer: nothing downstream of this node consumes the result before
-                # the optimiser, so the kernel goes to the side stream and overlaps the rest of backward
-                with torch.cuda.stream(side):
-                    conv_wgrad_raw(x, gy, ctx.spec, w.shape, want_b, w_slot, b_slot, ctx.aff)
-                x.record_stream(side)
-                gy.record_stream(side)
-                if ctx.aff is not None:
-                    ctx.aff[0].record_stream(side)
-                    ctx.aff[1].record_stream(side)
+                for t in (x, xw, *gys.values(), *(ctx.aff[:2] if ctx.aff is not None else ())):
+                    t.record_stream(side)
                 _join_after_backward()
-            else:
-                gw, gb = conv_wgrad_raw(x, gy, ctx.spec, w.shape, want_b, w_slot, b_slot, ctx.aff)
         if ctx.dead_bias and ctx.has_bias and ctx.needs_input_grad[2] and _grad_slot(ctx.b_ref) is None:
             gb = torch.zeros_like(ctx.b_ref)          # exact value; makes the bias a regular optimiser citizen
-        return gx, gw, gb, None, None, None, None
+        return gx, gw, gb, None, None, None, None, None
 
 
-def conv2d(x, w, b, spec, dead_bias=False, stats_out=None, aff=None):
+def conv2d(x, w, b, spec, dead_bias=False, stats_out=None, aff=None, out_f32=False):
     """dead_bias: the bias feeds a train-mode BatchNorm, which removes the channel mean: its true gradient is
     exactly zero (what autograd would produce is rounding noise), so the channel reduction is skipped.
-    aff: (scale, shift, relu) of a deferred BatchNorm on x (batchnorm_defer)."""
-    return _Conv.apply(x, w, b, spec, dead_bias, stats_out, aff)
+    aff: (scale, shift, relu) of a deferred BatchNorm on x (batchnorm_defer).  out_f32: see _Conv."""
+    return _Conv.apply(x, w, b, spec, dead_bias, stats_out, aff, out_f32)
 
 
 # ------------------------------------------------------------------------------------------- batch norm
+def _ext_args(ext, training):
+    """(stats, nsplit, pivot) of the producing convolution's BatchNorm sums (conv2d(..., stats_out=ext)), or nulls."""
+    if ext is None or ext.get('stats') is None or not training:
+        return None, 0, None
+    return L.ptr(ext['stats']), int(ext['nsplit']), L.ptr(ext.get('pivot'))
+
+
+def _bn_save(ctx, lay, training, relu, dims, x, gamma, beta, mean, invstd):
+    ctx.lay = lay
+    if training:
+        ctx.save_for_backward(x, gamma, beta, mean, invstd)
+        ctx.relu, ctx.dims = relu, dims
+        ctx.g_ref, ctx.b_ref = gamma, beta
+    else:
+        ctx.dims = None
+
+
+def _bn_param_grads(ctx, C, device):
+    """-> (ggamma, gbeta, inplace): the existing .grad slots when both exist, else new tensors."""
+    sg, sb = _grad_slot(ctx.g_ref), _grad_slot(ctx.b_ref)
+    if sg is not None and sb is not None:
+        return sg, sb, True
+    return torch.empty(C, device=device, dtype=torch.float32), torch.empty(C, device=device, dtype=torch.float32), False
+
+
 class _BatchNormAct(torch.autograd.Function):
-    """nn.BatchNorm2d (train or eval) + optional ReLU (conv.py:214-220)."""
+    """nn.BatchNorm2d (train or eval) + optional ReLU / leaky ReLU (conv.py:214-220) in the layout of its input; statistics
+    and parameters fp32."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, rm, rv, nbt, training, relu, momentum, eps, ext):
-        x = _c(_f32(x, 'batchnorm'))
-        N, C = x.shape[0], x.shape[1]
-        P = x.numel() // max(N * C, 1)
-        lib = L.load()
+    def forward(ctx, x, gamma, beta, rm, rv, nbt, training, relu, momentum, eps, ext, C):
+        lay = layout_of(x)
+        x = lay.prep(x, 'batchnorm')
+        N, C, P = lay.dims(x, C)
         y = torch.empty_like(x)
         mean = torch.empty(C, device=x.device, dtype=torch.float32)
         invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        nb = lib.jvae_bn_workspace_bytes(C)
-        ws = L.workspace(nb, x.device)
-        if ext is not None and ext.get('stats') is not None and training:
-            rc = lib.jvae_bn_fwd_ext_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y),
-                                         L.ptr(mean), L.ptr(invstd), N, C, P, momentum, eps, int(training), int(relu),
-                                         L.ptr(ext['stats']), int(ext['nsplit']), L.ptr(ext.get('pivot')),
-                                         L.ptr(ws), ws.numel(), L.stream_ptr())
-        else:
-            rc = lib.jvae_bn_fwd_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y),
-                                     L.ptr(mean), L.ptr(invstd), N, C, P, momentum, eps, int(training), int(relu),
-                                     L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_fwd_f32')
-        if training:
-            ctx.save_for_backward(x, gamma, beta, mean, invstd)
-            ctx.relu = relu
-            ctx.dims = (N, C, P)
-            ctx.g_ref, ctx.b_ref = gamma, beta
-        else:
-            ctx.dims = None
+        lay.bn_fwd(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y), L.ptr(mean), L.ptr(invstd),
+                   N, C, P, momentum, eps, int(training), int(relu), ext=_ext_args(ext, training),
+                   ws=lay.bn_workspace(C, x.device))
+        _bn_save(ctx, lay, training, relu, (N, C, P), x, gamma, beta, mean, invstd)
         return y
 
     @staticmethod
@@ -428,28 +528,21 @@ class _BatchNormAct(torch.autograd.Function):
         x, gamma, beta, mean, invstd = ctx.saved_tensors
         N, C, P = ctx.dims
         gy = _c(gy)
-        lib = L.load()
         gx = torch.empty_like(x)
-        sg, sb = _grad_slot(ctx.g_ref), _grad_slot(ctx.b_ref)
-        inplace = sg is not None and sb is not None
-        gg = sg if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        gb = sb if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        nb = lib.jvae_bn_workspace_bytes(C)
-        ws = L.workspace(nb, x.device)
-        rc = lib.jvae_bn_bwd_f32(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), L.ptr(gx),
-                                 L.ptr(gg), L.ptr(gb), int(inplace), N, C, P, int(ctx.relu), L.ptr(ws), ws.numel(),
-                                 L.stream_ptr())
-        L.check(rc, 'jvae_bn_bwd_f32')
+        gg, gb, inplace = _bn_param_grads(ctx, C, x.device)
+        ctx.lay.bn('jvae_bn_bwd', L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), L.ptr(gx),
+                   L.ptr(gg), L.ptr(gb), int(inplace), N, C, P, int(ctx.relu), ws=ctx.lay.bn_workspace(C, x.device))
         if inplace:
             gg = gb = None
-        return gx, gg, gb, None, None, None, None, None, None, None, None
+        return gx, gg, gb, None, None, None, None, None, None, None, None, None
 
 
 def batchnorm_act(x, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                  momentum=0.1, eps=1e-5, ext=None):
-    """ext: {'stats', 'nsplit', 'pivot'} filled by conv2d(..., stats_out=ext) for the tensor x."""
+                  momentum=0.1, eps=1e-5, ext=None, C=None):
+    """ext: {'stats', 'nsplit', 'pivot'} filled by conv2d(..., stats_out=ext) for the tensor x.
+    C: the channel count (needed for a B8 tensor)."""
     return _BatchNormAct.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                               momentum, eps, ext)
+                               momentum, eps, ext, C)
 
 
 class _BatchNormDefer(torch.autograd.Function):
@@ -459,73 +552,57 @@ class _BatchNormDefer(torch.autograd.Function):
     gradient the consumer's dgrad returns (which is w.r.t. the normalised activation)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, rm, rv, nbt, training, relu, momentum, eps, ext):
-        x = _c(_f32(x, 'batchnorm'))
-        N, C = x.shape[0], x.shape[1]
-        P = x.numel() // max(N * C, 1)
-        lib = L.load()
+    def forward(ctx, x, gamma, beta, rm, rv, nbt, training, relu, momentum, eps, ext, C):
+        lay = layout_of(x)
+        x = lay.prep(x, 'batchnorm')
+        N, C, P = lay.dims(x, C)
         mean = torch.empty(C, device=x.device, dtype=torch.float32)
         invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        coef = torch.empty((2, C), device=x.device, dtype=torch.float32)
-        ws = L.workspace(lib.jvae_bn_workspace_bytes(C), x.device)
-        use_ext = ext is not None and ext.get('stats') is not None and training
-        rc = lib.jvae_bn_finalize_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt),
-                                      L.ptr(mean), L.ptr(invstd), L.ptr(coef[0]), L.ptr(coef[1]), N, C, P, momentum, eps,
-                                      int(training), L.ptr(ext['stats']) if use_ext else None,
-                                      int(ext['nsplit']) if use_ext else 0, L.ptr(ext.get('pivot')) if use_ext else None,
-                                      L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_finalize_f32')
-        if training:
-            ctx.save_for_backward(x, gamma, beta, mean, invstd)
-            ctx.relu = relu
-            ctx.dims = (N, C, P)
-            ctx.g_ref, ctx.b_ref = gamma, beta
-        else:
-            ctx.dims = None
+        coef = torch.empty((2, lay.coef_width(C)), device=x.device, dtype=torch.float32)
+        lay.bn('jvae_bn_finalize', L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(mean),
+               L.ptr(invstd), *lay.coef_args(coef), N, C, P, momentum, eps, int(training), *_ext_args(ext, training),
+               ws=lay.bn_workspace(C, x.device))
+        _bn_save(ctx, lay, training, relu, (N, C, P), x, gamma, beta, mean, invstd)
         ctx.mark_non_differentiable(coef)
         ctx.set_materialize_grads(False)        # no zero-fill launch for the (never used) gradient of `coef`
         return x.view_as(x), coef
 
     @staticmethod
     def backward(ctx, gy, _gcoef):
-        g = _BatchNormAct.backward(ctx, gy)
-        return g
+        return _BatchNormAct.backward(ctx, gy)
 
 
 def batchnorm_defer(x, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                    momentum=0.1, eps=1e-5, ext=None):
-    """-> (x_alias, (scale, shift, relu)): hand both to conv2d(..., aff=...) of a layer with conv_affine_ok()."""
+                    momentum=0.1, eps=1e-5, ext=None, C=None):
+    """-> (x_alias, (scale, shift, relu)): hand both to conv2d(..., aff=...) of a layer whose layout's conv_affine_ok()
+    holds."""
     xa, coef = _BatchNormDefer.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                                     momentum, eps, ext)
+                                     momentum, eps, ext, C)
     return xa, (coef[0], coef[1], relu)
 
 
 class _SyncBatchNormAct(torch.autograd.Function):
     """Train-mode BatchNorm2d (+ReLU) whose statistics span all data-parallel ranks (what the single-process reference
-    computes on the whole global batch): two (C,2) all-reduces per layer, one in forward, one in backward."""
+    computes on the whole global batch): two (C,2) fp32 all-reduces per layer, one in forward, one in backward."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, rm, rv, nbt, relu, momentum, eps, world, group):
+    def forward(ctx, x, gamma, beta, rm, rv, nbt, relu, momentum, eps, world, group, C):
         import torch.distributed as dist
-        x = _c(_f32(x, 'sync batchnorm'))
-        N, C = x.shape[0], x.shape[1]
-        P = x.numel() // max(N * C, 1)
-        lib = L.load()
-        ws = L.workspace(lib.jvae_bn_workspace_bytes(C), x.device)
+        lay = layout_of(x)
+        x = lay.prep(x, 'sync batchnorm')
+        N, C, P = lay.dims(x, C)
+        ws = lay.bn_workspace(C, x.device)
         pivot = rm.detach().clone()                       # identical on every rank; rm itself is updated by the kernel
         sums = torch.empty((C, 2), device=x.device, dtype=torch.float32)
-        L.check(lib.jvae_bn_sums_f32(L.ptr(x), L.ptr(pivot), L.ptr(sums), N, C, P, L.ptr(ws), ws.numel(), L.stream_ptr()),
-                'jvae_bn_sums_f32')
+        lay.bn('jvae_bn_sums', L.ptr(x), L.ptr(pivot), L.ptr(sums), N, C, P, ws=ws)
         dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
         y = torch.empty_like(x)
         mean = torch.empty(C, device=x.device, dtype=torch.float32)
         invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        rc = lib.jvae_bn_fwd_sync_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y),
-                                      L.ptr(mean), L.ptr(invstd), N, C, P, momentum, eps, int(relu), L.ptr(sums),
-                                      L.ptr(pivot), int(world), L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_fwd_sync_f32')
+        lay.bn('jvae_bn_fwd_sync', L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y),
+               L.ptr(mean), L.ptr(invstd), N, C, P, momentum, eps, int(relu), L.ptr(sums), L.ptr(pivot), int(world), ws=ws)
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
-        ctx.cfg = (N, C, P, relu, int(world), group)
+        ctx.lay, ctx.cfg = lay, (N, C, P, relu, int(world), group)
         ctx.g_ref, ctx.b_ref = gamma, beta
         return y
 
@@ -534,32 +611,27 @@ class _SyncBatchNormAct(torch.autograd.Function):
         import torch.distributed as dist
         x, gamma, beta, mean, invstd = ctx.saved_tensors
         N, C, P, relu, world, group = ctx.cfg
+        lay = ctx.lay
         gy = _c(gy)
-        lib = L.load()
-        ws = L.workspace(lib.jvae_bn_workspace_bytes(C), x.device)
+        ws = lay.bn_workspace(C, x.device)
         local = torch.empty((C, 2), device=x.device, dtype=torch.float32)
-        rc = lib.jvae_bn_bwd_sums_f32(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd),
-                                      L.ptr(local), N, C, P, int(relu), L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_bwd_sums_f32')
+        lay.bn('jvae_bn_bwd_sums', L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), L.ptr(local),
+               N, C, P, int(relu), ws=ws)
         glob = local.clone()
         dist.all_reduce(glob, op=dist.ReduceOp.SUM, group=group)
         gx = torch.empty_like(x)
-        sg, sb = _grad_slot(ctx.g_ref), _grad_slot(ctx.b_ref)
-        inplace = sg is not None and sb is not None
-        gg = sg if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        gb = sb if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        rc = lib.jvae_bn_bwd_sync_f32(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd),
-                                      L.ptr(local), L.ptr(glob), world, L.ptr(gx), L.ptr(gg), L.ptr(gb), int(inplace),
-                                      N, C, P, int(relu), L.stream_ptr())
-        L.check(rc, 'jvae_bn_bwd_sync_f32')
+        gg, gb, inplace = _bn_param_grads(ctx, C, x.device)
+        lay.bn_bwd_sync(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), L.ptr(local),
+                        L.ptr(glob), world, L.ptr(gx), L.ptr(gg), L.ptr(gb), int(inplace), N, C, P, int(relu), ws=ws)
         if inplace:
             gg = gb = None
-        return gx, gg, gb, None, None, None, None, None, None, None, None
+        return gx, gg, gb, None, None, None, None, None, None, None, None, None
 
 
-def sync_batchnorm_act(x, gamma, beta, running_mean, running_var, num_batches_tracked, relu, momentum, eps, world, group=None):
+def sync_batchnorm_act(x, gamma, beta, running_mean, running_var, num_batches_tracked, relu, momentum, eps, world, group=None,
+                       C=None):
     return _SyncBatchNormAct.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, relu, momentum, eps,
-                                   world, group)
+                                   world, group, C)
 
 
 class _Act(torch.autograd.Function):
@@ -1015,3 +1087,6 @@ def draw_augmentation(N, pad, device, generator=None, flip=True, crop=True):
     dy = torch.randint(0, 2 * pad + 1, (N,), device=device, generator=generator, dtype=torch.int32) if crop else None
     dx = torch.randint(0, 2 * pad + 1, (N,), device=device, generator=generator, dtype=torch.int32) if crop else None
     return f, dy, dx
+
+
+from . import ops_b8 as _b8  # noqa: E402  (the B8 layout; it builds on the fp32 wrappers above)

@@ -2,7 +2,7 @@
 
 A B8 tensor is a torch.bfloat16 tensor of shape (N, ceil(C/8), H, W, 8): eight consecutive channels of a pixel are
 contiguous (csrc/conv_b8.hip).  Master weights, gradients of parameters, BatchNorm statistics and all loss math stay
-fp32.  A layer direction without a native bf16 kernel runs through the fp32 kernels between two layout conversions.
+fp32.  The layer ops themselves (convolution, BatchNorm) are those of ops.py; B8 is their description of this layout.
 """
 from ctypes import byref, c_int
 
@@ -10,8 +10,7 @@ import torch
 
 from . import lib as L
 from . import ops as O
-
-FWD, DGRAD, WGRAD = 1, 2, 4
+from .ops import FWD, DGRAD, WGRAD  # noqa: F401
 
 
 def cblocks(C):
@@ -113,7 +112,7 @@ def conv_wgrad_raw(x, gy, spec, wshape, want_bias, w_slot=None, b_slot=None, aff
     return (None, None) if inplace else (gw, gb)
 
 
-# ----------------------------------------------------------------------------------------- autograd layer
+# ----------------------------------------------------------------------------------------- layout
 def is_b8(t):
     return t.dtype == torch.bfloat16 and t.dim() == 5 and t.shape[-1] == 8
 
@@ -147,257 +146,67 @@ def from_b8(xb, C):
     return _Unpack.apply(xb, C)
 
 
-class _ConvB8(torch.autograd.Function):
-    """nn.Conv2d / nn.ConvTranspose2d on a B8 input.  Output: B8, or fp32 NCHW with out_f32 (the last layer of a stack).
-    Directions without a native bf16 kernel take the fp32 kernels between two layout conversions."""
+class B8Layout(O.Layout):
+    """ops.Layout of the B8 layout: its own entry points and workspace query, C passed in, coefficient rows padded to whole
+    channel blocks, native directions from native_mask, ReLU as its only activation."""
+    sfx = ws_sfx = '_b8'
+    acts = {O.IDENT: 0, O.RELU: 1}
 
-    @staticmethod
-    def forward(ctx, x, w, b, spec, dead_bias, stats_out, out_f32, aff=None):
+    def dims(self, x, C):
         N, _, H, W, _ = x.shape
-        mask = native_mask(spec, N, H, W)
-        ctx.w_ref, ctx.b_ref = w, b
-        w = O._c(w)
-        want_stats = stats_out is not None
-        ctx.aff = aff                       # only given where conv_affine_ok(): forward and wgrad are native
-        if mask & FWD and not (out_f32 and spec.transposed and spec.s == 2):
-            y, st, ns = conv_fwd_raw(x, w, b, spec, out_f32=out_f32, want_stats=want_stats, aff=aff)
-        else:
-            x32 = unpack(x, spec.cin)
-            if want_stats:
-                y32, st, ns = O.conv_fwd_stats_raw(x32, w, b, spec)
-            else:
-                y32, st, ns = O.conv_fwd_raw(x32, w, b, spec), None, 0
-            y = y32 if out_f32 else pack(y32)
-        if want_stats:
-            stats_out['stats'], stats_out['nsplit'], stats_out['pivot'] = st, ns, b
-        ctx.save_for_backward(x, w)
-        ctx.spec, ctx.mask, ctx.out_f32 = spec, mask, out_f32
-        ctx.has_bias = b is not None
-        ctx.dead_bias = dead_bias
-        return y
+        return N, C, H * W
 
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        spec, mask = ctx.spec, ctx.mask
-        N, _, H, W, _ = x.shape
-        gy = O._c(gy)
-        cache = {'b8': None if ctx.out_f32 else gy, 'f32': gy if ctx.out_f32 else None}
+    def coef_width(self, C):
+        return cblocks(C) * 8
 
-        def g_b8():
-            if cache['b8'] is None:
-                cache['b8'] = pack(cache['f32'])
-            return cache['b8']
+    def prep(self, x, what):
+        return O._c(x)
 
-        def g_f32():
-            if cache['f32'] is None:
-                cache['f32'] = unpack(cache['b8'], spec.cout)
-            return cache['f32']
+    def to_f32(self, t, C):
+        return unpack(t, C)
 
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            if mask & DGRAD:
-                gx = conv_dgrad_raw(g_b8(), w, spec, N, H, W)
-            else:
-                gx = pack(O.conv_dgrad_raw(g_f32(), w, spec, (N, spec.cin, H, W)))
-        want_b = ctx.has_bias and ctx.needs_input_grad[2] and not ctx.dead_bias
-        if ctx.needs_input_grad[1] or want_b:
-            w_slot = O._grad_slot(ctx.w_ref)
-            b_slot = O._grad_slot(ctx.b_ref) if want_b else None
-            native = bool(mask & WGRAD)
-            if native:
-                gyw = g_b8()
-                run = lambda ws_, bs_: conv_wgrad_raw(x, gyw, spec, w.shape, want_b, ws_, bs_, ctx.aff)
-            else:
-                gyw = g_f32()
-                x32 = unpack(x, spec.cin)
-                run = lambda ws_, bs_: O.conv_wgrad_raw(x32, gyw, spec, w.shape, want_b, ws_, bs_)
-            if O.OVERLAP_WGRAD and w_slot is not None and (b_slot is not None or not want_b):
-                main = torch.cuda.current_stream(x.device)
-                side = L.side_stream(x.device)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    run(w_slot, b_slot)
-                x.record_stream(side)
-                gyw.record_stream(side)
-                if ctx.aff is not None:
-                    ctx.aff[0].record_stream(side)
-                if not native:
-                    x32.record_stream(side)
-                O._join_after_backward()
-            else:
-                gw, gb = run(w_slot, b_slot)
-        if ctx.dead_bias and ctx.has_bias and ctx.needs_input_grad[2] and O._grad_slot(ctx.b_ref) is None:
-            gb = torch.zeros_like(ctx.b_ref)
-        return gx, gw, gb, None, None, None, None, None
+    def from_f32(self, t):
+        return pack(t)
+
+    def native(self, spec, N, H, W):
+        return native_mask(spec, N, H, W)
+
+    def affine_ok(self, spec, N, H, W):
+        return conv_affine_ok(spec, N, H, W)
+
+    def conv_fwd(self, x, w, b, spec, want_stats, aff, out_f32):
+        return conv_fwd_raw(x, w, b, spec, out_f32=out_f32, want_stats=want_stats, aff=aff)
+
+    def conv_dgrad(self, gy, w, spec, N, H, W):
+        return conv_dgrad_raw(gy, w, spec, N, H, W)
+
+    def conv_wgrad(self, *args):
+        return conv_wgrad_raw(*args)
+
+    def bn_fwd(self, *args, ext, ws):
+        self.bn('jvae_bn_fwd', *args, *ext, ws=ws)            # nullable sums
+
+    def coef_args(self, coef):
+        return (L.ptr(coef),)                                  # one (2, CB*8) block
+
+    def bn_bwd_sync(self, *args, ws):
+        self.bn('jvae_bn_bwd_sync', *args, ws=ws)
 
 
-def conv2d(x, w, b, spec, dead_bias=False, stats_out=None, out_f32=False, aff=None):
-    return _ConvB8.apply(x, w, b, spec, dead_bias, stats_out, out_f32, aff)
+B8 = B8Layout()
 
 
-class _BatchNormActB8(torch.autograd.Function):
-    """nn.BatchNorm2d (train or eval) + optional ReLU on a B8 tensor; statistics and parameters fp32."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, rm, rv, nbt, training, relu, momentum, eps, ext, C):
-        x = O._c(x)
-        N, CB, H, W, _ = x.shape
-        HW = H * W
-        lib = L.load()
-        y = torch.empty_like(x)
-        mean = torch.empty(C, device=x.device, dtype=torch.float32)
-        invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        ws = L.workspace(lib.jvae_bn_workspace_bytes_b8(C), x.device)
-        use_ext = ext is not None and ext.get('stats') is not None and training
-        rc = lib.jvae_bn_fwd_b8(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y),
-                                L.ptr(mean), L.ptr(invstd), N, C, HW, momentum, eps, int(training), int(relu),
-                                L.ptr(ext['stats']) if use_ext else None, int(ext['nsplit']) if use_ext else 0,
-                                L.ptr(ext.get('pivot')) if use_ext else None, L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_fwd_b8')
-        if training:
-            ctx.save_for_backward(x, gamma, beta, mean, invstd)
-            ctx.relu = relu
-            ctx.dims = (N, C, HW)
-            ctx.g_ref, ctx.b_ref = gamma, beta
-        else:
-            ctx.dims = None
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        if ctx.dims is None:
-            raise L.JvaeHipError('backward through eval-mode BatchNorm is not part of the training step')
-        x, gamma, beta, mean, invstd = ctx.saved_tensors
-        N, C, HW = ctx.dims
-        gy = O._c(gy)
-        lib = L.load()
-        gx = torch.empty_like(x)
-        sg, sb = O._grad_slot(ctx.g_ref), O._grad_slot(ctx.b_ref)
-        inplace = sg is not None and sb is not None
-        gg = sg if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        gb = sb if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        ws = L.workspace(lib.jvae_bn_workspace_bytes_b8(C), x.device)
-        rc = lib.jvae_bn_bwd_b8(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), L.ptr(gx),
-                                L.ptr(gg), L.ptr(gb), int(inplace), N, C, HW, int(ctx.relu), L.ptr(ws), ws.numel(),
-                                L.stream_ptr())
-        L.check(rc, 'jvae_bn_bwd_b8')
-        if inplace:
-            gg = gb = None
-        return gx, gg, gb, None, None, None, None, None, None, None, None, None
+# the BatchNorm ops of ops.py on a B8 tensor of C channels (same arguments after C)
+def batchnorm_act(x, C, *args, **kw):
+    return O.batchnorm_act(x, *args, C=C, **kw)
 
 
-class _SyncBatchNormActB8(torch.autograd.Function):
-    """Train-mode BatchNorm2d (+ReLU) on a B8 tensor whose statistics span all data-parallel ranks (ops._SyncBatchNormAct
-    for the bf16 layout): two (C,2) fp32 all-reduces per layer, one in forward, one in backward."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, rm, rv, nbt, relu, momentum, eps, world, group, C):
-        import torch.distributed as dist
-        x = O._c(x)
-        N, CB, H, W, _ = x.shape
-        HW = H * W
-        lib = L.load()
-        ws = L.workspace(lib.jvae_bn_workspace_bytes_b8(C), x.device)
-        pivot = rm.detach().clone()                       # identical on every rank; rm itself is updated by the kernel
-        sums = torch.empty((C, 2), device=x.device, dtype=torch.float32)
-        L.check(lib.jvae_bn_sums_b8(L.ptr(x), L.ptr(pivot), L.ptr(sums), N, C, HW, L.ptr(ws), ws.numel(), L.stream_ptr()),
-                'jvae_bn_sums_b8')
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
-        y = torch.empty_like(x)
-        mean = torch.empty(C, device=x.device, dtype=torch.float32)
-        invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        rc = lib.jvae_bn_fwd_sync_b8(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y),
-                                     L.ptr(mean), L.ptr(invstd), N, C, HW, momentum, eps, int(relu), L.ptr(sums),
-                                     L.ptr(pivot), int(world), L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_fwd_sync_b8')
-        ctx.save_for_backward(x, gamma, beta, mean, invstd)
-        ctx.cfg = (N, C, HW, relu, int(world), group)
-        ctx.g_ref, ctx.b_ref = gamma, beta
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        import torch.distributed as dist
-        x, gamma, beta, mean, invstd = ctx.saved_tensors
-        N, C, HW, relu, world, group = ctx.cfg
-        gy = O._c(gy)
-        lib = L.load()
-        ws = L.workspace(lib.jvae_bn_workspace_bytes_b8(C), x.device)
-        local = torch.empty((C, 2), device=x.device, dtype=torch.float32)
-        rc = lib.jvae_bn_bwd_sums_b8(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd),
-                                     L.ptr(local), N, C, HW, int(relu), L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_bwd_sums_b8')
-        glob = local.clone()
-        dist.all_reduce(glob, op=dist.ReduceOp.SUM, group=group)
-        gx = torch.empty_like(x)
-        sg, sb = O._grad_slot(ctx.g_ref), O._grad_slot(ctx.b_ref)
-        inplace = sg is not None and sb is not None
-        gg = sg if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        gb = sb if inplace else torch.empty(C, device=x.device, dtype=torch.float32)
-        rc = lib.jvae_bn_bwd_sync_b8(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd),
-                                     L.ptr(local), L.ptr(glob), world, L.ptr(gx), L.ptr(gg), L.ptr(gb), int(inplace),
-                                     N, C, HW, int(relu), L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_bwd_sync_b8')
-        if inplace:
-            gg = gb = None
-        return gx, gg, gb, None, None, None, None, None, None, None, None, None
+def batchnorm_defer(x, C, *args, **kw):
+    return O.batchnorm_defer(x, *args, C=C, **kw)
 
 
-def sync_batchnorm_act(x, C, gamma, beta, running_mean, running_var, num_batches_tracked, relu, momentum, eps, world, group=None):
-    """Synchronised train-mode BatchNorm(+ReLU) on a B8 tensor (statistics over all data-parallel ranks)."""
-    return _SyncBatchNormActB8.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, relu, momentum, eps,
-                                     world, group, C)
-
-
-class _BatchNormDeferB8(torch.autograd.Function):
-    """BatchNorm(+ReLU) on a B8 tensor deferred into the next bf16 convolution (see ops._BatchNormDefer): forward produces
-    the statistics and the (scale, shift) rows only and returns the input itself; backward is the ordinary one."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, rm, rv, nbt, training, relu, momentum, eps, ext, C):
-        x = O._c(x)
-        N, CB, H, W, _ = x.shape
-        HW = H * W
-        lib = L.load()
-        mean = torch.empty(C, device=x.device, dtype=torch.float32)
-        invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        coef = torch.empty((2, CB * 8), device=x.device, dtype=torch.float32)
-        ws = L.workspace(lib.jvae_bn_workspace_bytes_b8(C), x.device)
-        use_ext = ext is not None and ext.get('stats') is not None and training
-        rc = lib.jvae_bn_finalize_b8(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt),
-                                     L.ptr(mean), L.ptr(invstd), L.ptr(coef), N, C, HW, momentum, eps, int(training),
-                                     L.ptr(ext['stats']) if use_ext else None, int(ext['nsplit']) if use_ext else 0,
-                                     L.ptr(ext.get('pivot')) if use_ext else None, L.ptr(ws), ws.numel(), L.stream_ptr())
-        L.check(rc, 'jvae_bn_finalize_b8')
-        if training:
-            ctx.save_for_backward(x, gamma, beta, mean, invstd)
-            ctx.relu = relu
-            ctx.dims = (N, C, HW)
-            ctx.g_ref, ctx.b_ref = gamma, beta
-        else:
-            ctx.dims = None
-        ctx.mark_non_differentiable(coef)
-        ctx.set_materialize_grads(False)        # no zero-fill launch for the (never used) gradient of `coef`
-        return x.view_as(x), coef
-
-    @staticmethod
-    def backward(ctx, gy, _gcoef):
-        return _BatchNormActB8.backward(ctx, gy)
-
-
-def batchnorm_defer(x, C, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                    momentum=0.1, eps=1e-5, ext=None):
-    """-> (x_alias, (scale, shift, relu)) for conv2d(..., aff=...) of a layer with conv_affine_ok()."""
-    xa, coef = _BatchNormDeferB8.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                                       momentum, eps, ext, C)
-    return xa, (coef[0], coef[1], relu)
-
-
-def batchnorm_act(x, C, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                  momentum=0.1, eps=1e-5, ext=None):
-    return _BatchNormActB8.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, training, relu,
-                                 momentum, eps, ext, C)
+def sync_batchnorm_act(x, C, *args, **kw):
+    return O.sync_batchnorm_act(x, *args, C=C, **kw)
 
 
 class _ReluB8(torch.autograd.Function):

@@ -134,8 +134,8 @@ class HipConv2d(nn.Conv2d):
             self.__dict__['_conv_spec'] = sp
         return sp
 
-    def forward(self, x, dead_bias=False, stats_out=None, aff=None):
-        return ops.conv2d(x, self.weight, self.bias, self._spec(), dead_bias, stats_out, aff)
+    def forward(self, x, dead_bias=False, stats_out=None, aff=None, out_f32=False):
+        return ops.conv2d(x, self.weight, self.bias, self._spec(), dead_bias, stats_out, aff, out_f32)
 
 
 class HipConvTranspose2d(nn.ConvTranspose2d):
@@ -147,12 +147,16 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
             self.__dict__['_conv_spec'] = sp
         return sp
 
-    def forward(self, x, output_size=None, dead_bias=False, stats_out=None, aff=None):
-        return ops.conv2d(x, self.weight, self.bias, self._spec(), dead_bias, stats_out, aff)
+    def forward(self, x, output_size=None, dead_bias=False, stats_out=None, aff=None, out_f32=False):
+        return ops.conv2d(x, self.weight, self.bias, self._spec(), dead_bias, stats_out, aff, out_f32)
+
+
+_CONVS = (HipConv2d, HipConvTranspose2d)
 
 
 class HipBatchNorm2d(nn.BatchNorm2d):
-    """nn.BatchNorm2d state; forward = batch-statistics kernel (+ the following ReLU when fused by the stack)."""
+    """nn.BatchNorm2d state; forward = batch-statistics kernel (+ the following ReLU when fused by the stack), in the
+    layout of its input."""
 
     sync_world = 1          # > 1: statistics over all data-parallel ranks (ClassificationVariationalNetwork.set_sync_batchnorm)
     sync_group = None
@@ -160,20 +164,24 @@ class HipBatchNorm2d(nn.BatchNorm2d):
     def defer(self, x, relu=False, ext=None):
         """Statistics + coefficients only; the consumer convolution applies the normalisation (ops.batchnorm_defer)."""
         return ops.batchnorm_defer(x, self.weight, self.bias, self.running_mean, self.running_var,
-                                   self.num_batches_tracked, self.training, relu, self.momentum, self.eps, ext)
+                                   self.num_batches_tracked, self.training, relu, self.momentum, self.eps, ext,
+                                   C=self.num_features)
 
     def forward(self, x, relu=False, ext=None):
         if self.training and self.sync_world > 1:
-            return ops.sync_batchnorm_act(x, self.weight, self.bias, self.running_mean, self.running_var,
-                                          self.num_batches_tracked, relu, self.momentum, self.eps, self.sync_world,
-                                          self.sync_group)
+            args = (self.weight, self.bias, self.running_mean, self.running_var, self.num_batches_tracked, relu,
+                    self.momentum, self.eps, self.sync_world, self.sync_group)
+            if ops_b8.is_b8(x):           # the bf16 entry (looked up at call time: the data-parallel tests count its calls)
+                return ops_b8.sync_batchnorm_act(x, self.num_features, *args)
+            return ops.sync_batchnorm_act(x, *args)
         return ops.batchnorm_act(x, self.weight, self.bias, self.running_mean, self.running_var,
-                                 self.num_batches_tracked, self.training, relu, self.momentum, self.eps, ext)
+                                 self.num_batches_tracked, self.training, relu, self.momentum, self.eps, ext,
+                                 C=self.num_features)
 
 
 class HipConvStack(nn.Sequential):
-    """nn.Sequential whose forward fuses BatchNorm2d with the activation that follows it and lets the producing
-    convolution's epilogue compute the batch statistics.
+    """nn.Sequential whose forward fuses BatchNorm2d with the activation that follows it, lets the producing
+    convolution's epilogue compute the batch statistics and defers a BatchNorm into the convolution that consumes it.
 
     compute_dtype 'bf16' (config 5 of BASELINE.json; no counterpart in the fp32 reference): activations between the
     layers are bf16 in the B8 layout (jvae_hip/ops_b8.py), convolutions run on the bf16 matrix cores with fp32
@@ -181,121 +189,71 @@ class HipConvStack(nn.Sequential):
     geometry has no bf16 kernel at all (the 3x3 / 4x4 / 7x7 / 8x8 heads) stay on the fp32 kernels."""
 
     compute_dtype = 'fp32'
-    # BatchNorm+ReLU applied by the consuming convolution where its kernels can (fp32 path); JVAE_DEFER_BN=0: A/B switch
+    # BatchNorm+ReLU applied by the consuming convolution where its kernels can; JVAE_DEFER_BN=0: A/B switch
     defer_batchnorm = os.environ.get('JVAE_DEFER_BN', '1') != '0'
 
-    def forward(self, x):
-        if self.compute_dtype == 'bf16':
-            return self._forward_b8(x)
-        mods = list(self)
-        i = 0
-        ext = None
-        aff = None           # (scale, shift, relu) of a BatchNorm deferred into the next convolution
-        while i < len(mods):
-            m = mods[i]
-            if isinstance(m, HipBatchNorm2d) and i + 1 < len(mods) and type(mods[i + 1]) in ACT_OF_MODULE \
-                    and ACT_OF_MODULE[type(mods[i + 1])] in ops.BN_ACT:
-                relu = ops.BN_ACT[ACT_OF_MODULE[type(mods[i + 1])]]      # 0 none, 1 ReLU, 2 leaky ReLU: fused into the BatchNorm kernels
-                nxt = mods[i + 2] if i + 2 < len(mods) else None
-                if self.defer_batchnorm and isinstance(nxt, (HipConv2d, HipConvTranspose2d)) \
-                        and not (m.training and m.sync_world > 1) \
-                        and ops.conv_affine_ok(nxt._spec(), x.shape[0], x.shape[2], x.shape[3]):
-                    # the normalised activation is never materialised: the next convolution (forward and weight
-                    # gradient) applies fmaf(x, scale, shift) + ReLU while it stages its input
-                    x, aff = m.defer(x, relu=relu, ext=ext)
-                else:
-                    x = m(x, relu=relu, ext=ext)
-                ext = None
-                i += 2
-                continue
-            if isinstance(m, (HipConv2d, HipConvTranspose2d)) and i + 1 < len(mods) \
-                    and isinstance(mods[i + 1], HipBatchNorm2d) and mods[i + 1].training:
-                ext = {} if mods[i + 1].sync_world <= 1 else None      # synchronised BN reduces its own sums
-                # BatchNorm removes the channel mean: d(loss)/d(bias) == 0 exactly
-                x = m(x, dead_bias=True, stats_out=ext, aff=aff)
-            elif isinstance(m, (HipConv2d, HipConvTranspose2d)):
-                ext = None
-                x = m(x, aff=aff)
-            else:
-                ext = None
-                x = m(x)
-            aff = None
-            i += 1
-        return x
+    def _layout(self, conv, x):
+        """The layout a convolution consumes: B8 in the bf16 mode where the layer has a native bf16 kernel, else fp32."""
+        if self.compute_dtype == 'bf16' and ops_b8.native_mask(conv._spec(), x.shape[0], x.shape[2], x.shape[3]):
+            return ops_b8.B8
+        return ops.F32
 
-    def _forward_b8(self, x):
+    def forward(self, x):
         mods = list(self)
-        if any(type(m).__name__ == 'HipLeakyReLU' for m in mods):
+        if self.compute_dtype == 'bf16' and any(ACT_OF_MODULE.get(type(m)) == ops.LEAKY for m in mods):
             raise NotImplementedError("the bf16 mode (no counterpart in the reference) has ReLU kernels only: activation='leaky' needs fp32")
-        convs = [k for k, m in enumerate(mods) if isinstance(m, (HipConv2d, HipConvTranspose2d))]
-        i = 0
-        ext = None
-        aff = None           # (scale, shift, relu) of a BatchNorm deferred into the next bf16 convolution
+        last_conv = max((k for k, m in enumerate(mods) if isinstance(m, _CONVS)), default=-1)
         channels = x.shape[1]
+        ext = None           # the producing convolution's BatchNorm sums
+        aff = None           # (scale, shift, relu) of a BatchNorm deferred into the next convolution
+        i = 0
         while i < len(mods):
-            m = mods[i]
-            b8 = ops_b8.is_b8(x)
-            if isinstance(m, (HipConv2d, HipConvTranspose2d)):
+            m, lay = mods[i], ops.layout_of(x)
+            if isinstance(m, _CONVS):
                 spec = m._spec()
-                N = x.shape[0]
-                H, W = (x.shape[2], x.shape[3])
-                native = ops_b8.native_mask(spec, N, H, W) != 0
-                bn_next = i + 1 < len(mods) and isinstance(mods[i + 1], HipBatchNorm2d)
-                fused = bn_next and mods[i + 1].training and mods[i + 1].sync_world <= 1
-                ext = {} if fused else None
-                dead = bn_next and mods[i + 1].training
-                if native:
-                    if not b8:
-                        x = ops_b8.to_b8(x)
-                    # the last convolution of the stack writes fp32 NCHW directly (it feeds the loss / the dense heads)
-                    last = i == convs[-1] and not bn_next and not (spec.transposed and spec.s == 2)
-                    x = ops_b8.conv2d(x, m.weight, m.bias, spec, dead, ext, out_f32=last, aff=aff)
-                else:
-                    if b8:
-                        x = ops_b8.from_b8(x, channels)
-                    x = ops.conv2d(x, m.weight, m.bias, spec, dead, ext)
+                want = self._layout(m, x)
+                if want is not lay:
+                    x = ops_b8.to_b8(x) if want is ops_b8.B8 else ops_b8.from_b8(x, channels)
+                bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], HipBatchNorm2d) else None
+                ext = {} if bn is not None and bn.training and bn.sync_world <= 1 else None   # synchronised BN sums itself
+                # the last convolution of a bf16 stack writes fp32 NCHW directly (it feeds the loss / the dense heads)
+                out_f32 = i == last_conv and bn is None and not (spec.transposed and spec.s == 2)
+                # BatchNorm removes the channel mean: d(loss)/d(bias) == 0 exactly
+                x = m(x, dead_bias=bn is not None and bn.training, stats_out=ext, aff=aff, out_f32=out_f32)
                 aff = None
                 channels = spec.cout
                 i += 1
                 continue
             if isinstance(m, HipBatchNorm2d):
-                relu = False
-                step = 1
-                if i + 1 < len(mods) and type(mods[i + 1]) in ACT_OF_MODULE \
-                        and ACT_OF_MODULE[type(mods[i + 1])] in (ops.RELU, ops.IDENT):
-                    relu = ACT_OF_MODULE[type(mods[i + 1])] == ops.RELU
-                    step = 2
-                nxt = mods[i + step] if i + step < len(mods) else None
-                if b8 and not (m.training and m.sync_world > 1) and self.defer_batchnorm \
-                        and isinstance(nxt, (HipConv2d, HipConvTranspose2d)) \
-                        and ops_b8.conv_affine_ok(nxt._spec(), x.shape[0], x.shape[2], x.shape[3]):
-                    # normalisation + ReLU applied by the next bf16 convolution while it stages this tensor
-                    x, aff = ops_b8.batchnorm_defer(x, channels, m.weight, m.bias, m.running_mean, m.running_var,
-                                                    m.num_batches_tracked, m.training, relu, m.momentum, m.eps, ext)
-                elif b8 and not (m.training and m.sync_world > 1):
-                    x = ops_b8.batchnorm_act(x, channels, m.weight, m.bias, m.running_mean, m.running_var,
-                                             m.num_batches_tracked, m.training, relu, m.momentum, m.eps, ext)
-                elif b8:                  # train mode, statistics over all data-parallel ranks: bf16 kernels of their own
-                    x = ops_b8.sync_batchnorm_act(x, channels, m.weight, m.bias, m.running_mean, m.running_var,
-                                                  m.num_batches_tracked, relu, m.momentum, m.eps, m.sync_world, m.sync_group)
+                relu = lay.acts.get(ACT_OF_MODULE.get(type(mods[i + 1]))) if i + 1 < len(mods) else None
+                if relu is None:
+                    # no activation the BatchNorm kernels of this layout apply follows: a pass of its own, which computes
+                    # its statistics itself
+                    x = m(x)
+                    i += 1
                 else:
-                    x = m(x, relu=relu, ext=ext)
+                    # 0 none, 1 ReLU, 2 leaky ReLU: fused into the BatchNorm kernels
+                    nxt = mods[i + 2] if i + 2 < len(mods) else None
+                    if self.defer_batchnorm and isinstance(nxt, _CONVS) and not (m.training and m.sync_world > 1) \
+                            and self._layout(nxt, x) is lay and lay.affine_ok(nxt._spec(), x.shape[0], x.shape[2], x.shape[3]):
+                        # the normalised activation is never materialised: the next convolution (forward and weight
+                        # gradient) applies fmaf(x, scale, shift) + ReLU while it stages its input
+                        x, aff = m.defer(x, relu=relu, ext=ext)
+                    else:
+                        x = m(x, relu=relu, ext=ext)
+                    i += 2
                 ext = None
-                i += step
                 continue
             ext = None
-            if b8 and type(m) in ACT_OF_MODULE and ACT_OF_MODULE[type(m)] == ops.RELU:
-                x = ops_b8.relu(x)
-            elif b8 and type(m) in ACT_OF_MODULE and ACT_OF_MODULE[type(m)] == ops.IDENT:
-                pass
+            kind = ACT_OF_MODULE.get(type(m))
+            if lay is ops_b8.B8 and kind in lay.acts:
+                x = ops_b8.relu(x) if kind == ops.RELU else x
             else:
-                if b8:
+                if lay is ops_b8.B8:
                     x = ops_b8.from_b8(x, channels)
                 x = m(x)
             i += 1
-        if ops_b8.is_b8(x):
-            x = ops_b8.from_b8(x, channels)
-        return x
+        return x if ops.layout_of(x) is ops.F32 else ops_b8.from_b8(x, channels)
 
 
 def build_de_conv_layers(input_shape, layers_name, batch_norm=False, where='input', activation='relu',

@@ -250,7 +250,7 @@ def _tape(name, t):
 
 # ---- bf16 emulation of the product's mixed-precision mode (BASELINE configs[4]; the reference has no such mode) ----------------
 # BF16_CONV = True makes run_stack() round where the drop-in's bf16 path stores or multiplies bf16 (joint-vae_amd/module/
-# vae_layers/conv.py::_forward_b8, jvae_hip/ops_b8.py): a 5x5 (de)convolution - the geometries with bf16 kernels - multiplies
+# vae_layers/conv.py::HipConvStack, jvae_hip/ops_b8.py): a 5x5 (de)convolution - the geometries with bf16 kernels - multiplies
 # bf16(input) by bf16(weight) with fp32 accumulation and fp32 bias and stores its output in bf16 (the last convolution of a stack
 # that feeds the loss stores fp32); the BatchNorm behind it takes its batch statistics from the fp32 accumulators, normalises
 # the STORED bf16 tensor in fp32 and stores bf16 again; the gradients that travel between those layers are bf16 tensors too

@@ -1174,6 +1174,63 @@ def test_pack_cache_span_closes_without_an_optimizer_step():
     torch.cuda.synchronize()
 
 
+def test_pack_cache_span_protocol_in_the_bf16_mode():
+    """The span protocol of the test above in the bf16 mode on the config-5 geometry, whose 5x5 convolutions run on bf16
+    kernels that read the cache too.  (i) the backward pass closes the span without an optimiser step; (ii) a direct call of
+    the encoder stack between a train-mode evaluate() and its backward is not served from the cache, and the backward gives
+    the same gradients bit for bit; (iii) a weight change through .data made while the cache is armed is seen by a direct
+    call.  The encoder's first convolution runs on a bf16 kernel: nothing on the fp32 kernels disarms the cache before it."""
+    from jvae_hip import lib as L
+    from jvae_hip import ops_b8
+    case = get_case('c5_n4')
+    kw = case['net']
+    net = build(case)
+    net.set_compute_dtype('bf16')
+    x, y, eps = (t.to(DEV) for t in det_inputs(8, kw['input_shape'], kw['num_labels'], 1, kw['latent_dim'], seed=5))
+    net.train_step(x, y, epsilon=eps)                     # parameters settle in the flat buffer
+    net.train_step(x, y, epsilon=eps)
+
+    def served(f):
+        s0 = L.pack_cache_stats()
+        out = f()
+        s1 = L.pack_cache_stats()
+        return out, s1['hits'] - s0['hits'], s1['misses'] - s0['misses']
+
+    conv0 = net.features[0]
+    assert ops_b8.native_mask(conv0._spec(), 8, 64, 64) & ops_b8.FWD
+    xb = ops_b8.pack(x)
+    probe = lambda: ops_b8.conv_fwd_raw(xb, conv0.weight, conv0.bias, conv0._spec())     # a kernel call: never disarms
+
+    def grads(stray):
+        net.optimizer.zero_grad()
+        losses = net.evaluate(x, y, epsilon=eps, with_beta=True)[2]
+        _, hits, misses = served(probe)
+        assert hits + misses >= 1                         # the span is open and serves conv0's weight
+        if stray:
+            _, hits, misses = served(lambda: net.features(x))
+            assert (hits, misses) == (0, 0)
+        losses['total'].mean().backward()
+        torch.cuda.synchronize()
+        _, hits, misses = served(probe)
+        assert (hits, misses) == (0, 0)                   # (i) the backward closed the span
+        return net.optimizer._groups[0].g.clone()
+    g_plain, g_stray = grads(False), grads(True)
+    assert torch.equal(g_plain, g_stray)
+    # (iii) a .data change while the cache is armed
+    with torch.no_grad():
+        before = net.features(x).clone()
+    net.evaluate(x, y, epsilon=eps, with_beta=True)       # train mode, no backward: the cache stays armed
+    conv0.weight.data.neg_()
+    with torch.no_grad():
+        after = net.features(x).clone()
+    L.pack_cache_end()
+    with torch.no_grad():
+        uncached = net.features(x).clone()
+    conv0.weight.data.neg_()
+    assert not torch.equal(before, after) and torch.equal(after, uncached)
+    torch.cuda.synchronize()
+
+
 def test_nonfinite_parameters_end_the_run_before_the_next_backward(capsys):
     """cvae.py:2454-2457: the reference scans every parameter for NaN / Inf between evaluate() and backward() and ends the run
     with `print('GRAD NAN'); sys.exit(1)`.  Here the Adam kernel raises a device flag when an updated parameter is not finite;

@@ -396,6 +396,13 @@ int jvae_pool2d_bwd_f32(const float* dy, const int* idx, float* dx, long planes,
                         int mode, void* stream);
 int jvae_upsample_nearest_fwd_f32(const float* x, float* y, long planes, int H, int W, int scale, void* stream);
 int jvae_upsample_nearest_bwd_f32(const float* dy, float* dx, long planes, int H, int W, int scale, void* stream);
+/* The same four on bf16 B8 tensors (blocks = N*ceil(C/8) channel blocks of (H, W, 8) bf16; padding channels stay zero): per
+ * channel the window order, tie rule and fp32 sums of the fp32 kernels, rounded to bf16 once.  idx: int32 (blocks, OH, OW, 8). */
+int jvae_pool2d_fwd_b8(const void* x, void* y, int* idx, long blocks, int H, int W, int K, int S, int P, int mode, void* stream);
+int jvae_pool2d_bwd_b8(const void* dy, const int* idx, void* dx, long blocks, int H, int W, int K, int S, int P, int mode,
+                       void* stream);
+int jvae_upsample_nearest_fwd_b8(const void* x, void* y, long blocks, int H, int W, int scale, void* stream);
+int jvae_upsample_nearest_bwd_b8(const void* dy, void* dx, long blocks, int H, int W, int scale, void* stream);
 
 /* ---- input pipeline in front of the path: uint8 batch (NHWC if nhwc else NCHW) -> horizontal flip
  * where flip[n] != 0 -> edge padding by `pad` + crop at offsets (dy[n], dx[n]) in [0, 2*pad] -> float32 NCHW / 255.

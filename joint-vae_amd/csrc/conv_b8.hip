@@ -8,9 +8,10 @@
 // registers) is written back as 8-byte half units, 512 contiguous bytes per store instruction.
 //
 // This file: fp32 NCHW <-> B8 converters, the weight re-pack (fp32 master -> bf16 operand layout) and the
-// "forward-type" 5x5 kernel, which serves Conv2d forward (S = 1, 2), ConvTranspose2d stride-1 forward, Conv2d
-// stride-1 dgrad and ConvTranspose2d dgrad exactly as conv_mfma.hip does for fp32 (same weight roles: swap / flip).
-// Accumulation, bias and the BatchNorm partial statistics stay fp32.
+// "forward-type" KxK kernel (K = 5, and K = 3 for the vgg / ivgg / conv32- stacks), which serves Conv2d forward (S = 1, 2),
+// ConvTranspose2d stride-1 forward, Conv2d stride-1 dgrad and ConvTranspose2d dgrad exactly as conv_mfma.hip does for
+// fp32 (same weight roles: swap / flip).  Accumulation, bias and the BatchNorm partial statistics stay fp32.  The entry
+// points keep their conv5_ names (the family's first member) and take K.
 #include "common.h"
 #include "jvae_internal.h"
 #include "conv_b8.h"
@@ -103,13 +104,13 @@ __global__ void b8_channel_fold_kernel(const float* __restrict__ partial, float*
 
 // ---------------------------------------------------------------------------------------------------------------
 // weights: Wp[kb][tap][half][o][ci] = bf16( W[o][c = kb*16 + half*8 + ci][tap] )   (o < OP, zero padding)
-// swap: source is [c][o][tap] (ConvTranspose2d layout / role swap), flip: tap -> 24 - tap
+// swap: source is [c][o][tap] (ConvTranspose2d layout / role swap), flip: tap -> taps - 1 - tap
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void b8_wpack_kernel(const float* __restrict__ w, __bf16* __restrict__ wp,
-                                                       int C, int O, int KB, int OP, int swap, int flip) {
-    const long total = (long)KB * 25 * 2 * OP * 8;
+                                                       int C, int O, int KB, int OP, int swap, int flip, int taps) {
+    const long total = (long)KB * taps * 2 * OP * 8;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
-        jvae_pack_b8_elem(w, wp, i, C, O, swap, flip);
+        jvae_pack_b8_elem(w, wp, i, C, O, swap, flip, taps);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void b8_wpack_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------------------------------
 struct B8FwdP {
     const u32x4* in;     // B8 units (N, CBin, H, W)
-    const u32x4* wp;     // packed weight units (KB, 25, 2, OP)
+    const u32x4* wp;     // packed weight units (KB, K*K, 2, OP)
     const float* bias;   // (CoutReal) or null
     void* out;           // B8 units (N, CBout, OH, OW), or float (N, CoutReal, OH, OW) when out_f32
     int N, CBin, H, W, OP, P, CoutReal, CBout;
@@ -126,28 +127,32 @@ struct B8FwdP {
     InAff aff;           // deferred BatchNorm(+ReLU) of the input (sc == nullptr: none); CBin*8 coefficients
 };
 
-template <int S, int OW, int MT, int NT>
+// K: kernel size (5 or 3); the patch keeps HALO = K - 1 columns left of the interior (the read of tap kw at column
+// c*S + HALO - P + kw stays inside for any P <= HALO)
+template <int K, int S, int OW, int MT, int NT>
 struct B8Geom {
+    static constexpr int TAPS = K * K;
+    static constexpr int HALO = K - 1;
     static constexpr int OH = OW;
     static constexpr int PIX = MT * 128;
     static constexpr int OHW = OH * OW;
     static constexpr int NIMG = PIX >= OHW ? PIX / OHW : 1;
     static constexpr int TH = PIX >= OHW ? OH : PIX / OW;
-    static constexpr int ROWS = (TH - 1) * S + 5;
+    static constexpr int ROWS = (TH - 1) * S + K;
     static constexpr int WIN = OW * S;
-    static constexpr int WP0 = (OW - 1) * S + 9;
-    static constexpr int WP1 = WIN + 4;
+    static constexpr int WP0 = (OW - 1) * S + 2 * HALO + 1;
+    static constexpr int WP1 = WIN + HALO;
     static constexpr int WP = WP0 > WP1 ? WP0 : WP1;          // units per patch row
     static constexpr int CH = ROWS * WP;                       // units per channel block per image
     static constexpr int XS = NIMG * 2 * CH;                   // patch units of one K step (16 channels)
     static constexpr int WCOLS = NT * 32;
-    static constexpr int WS = 25 * 2 * WCOLS;                  // weight units of one K step
+    static constexpr int WS = TAPS * 2 * WCOLS;                // weight units of one K step
     static constexpr int LDS_BYTES = (XS + WS) * 16;
 };
 
-template <int S, int OW, int MT, int NT, bool AFF>
+template <int K, int S, int OW, int MT, int NT, bool AFF>
 __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
-    using G = B8Geom<S, OW, MT, NT>;
+    using G = B8Geom<K, S, OW, MT, NT>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     u32x4* Xs = reinterpret_cast<u32x4*>(lds_raw);
     u32x4* Ws = Xs + G::XS;
@@ -171,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
         const int pix = (wave * MT + mt) * 32 + l31;
         const int im = pix / (G::TH * OW), rem = pix % (G::TH * OW);
         const int r = rem / OW, c = rem % OW;
-        pixoff[mt] = im * (2 * G::CH) + half * G::CH + (r * S) * G::WP + c * S + 4 - p.P;
+        pixoff[mt] = im * (2 * G::CH) + half * G::CH + (r * S) * G::WP + c * S + G::HALO - p.P;
     }
 
     f32x16 acc[NT][MT];
@@ -207,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
             const int u = tid + k * 256;
             const int col = u % G::WCOLS, th = u / G::WCOLS;      // th = tap*2 + half
             u32x4 v = {0u, 0u, 0u, 0u};
-            if (u < G::WS) v = p.wp[((long)kb * 50 + th) * p.OP + o0 + col];
+            if (u < G::WS) v = p.wp[((long)kb * (2 * G::TAPS) + th) * p.OP + o0 + col];
             rw[k] = v;
         }
     };
@@ -225,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
                     const int ir = in_row0 + lr, n = img0 + im, cb = kb * 2 + h;
                     if (ir >= 0 && ir < p.H && n < p.N && cb < p.CBin) v = aff8(v, &ctab[cb * 8], &ctab[256 + cb * 8], p.aff.relu);
                 }
-                Xs[(im * 2 + h) * G::CH + lr * G::WP + 4 + x] = v;
+                Xs[(im * 2 + h) * G::CH + lr * G::WP + G::HALO + x] = v;
             }
         }
 #pragma unroll
@@ -245,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
         // (a 32-cycle bf16 MFMA leaves no slack for an LDS round trip in front of it)
         u32x4 fa[2][NT], fb[2][MT];
         auto frag = [&](int tap, u32x4 (&a)[NT], u32x4 (&b)[MT]) {
-            const int kh = tap / 5, kw = tap % 5;
+            const int kh = tap / K, kw = tap % K;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) a[nt] = Ws[(tap * 2 + half) * G::WCOLS + nt * 32 + l31];
 #pragma unroll
@@ -253,8 +258,8 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
         };
         frag(0, fa[0], fb[0]);
 #pragma unroll
-        for (int tap = 0; tap < 25; ++tap) {
-            if (tap + 1 < 25) frag(tap + 1, fa[(tap + 1) & 1], fb[(tap + 1) & 1]);
+        for (int tap = 0; tap < G::TAPS; ++tap) {
+            if (tap + 1 < G::TAPS) frag(tap + 1, fa[(tap + 1) & 1], fb[(tap + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
@@ -336,16 +341,16 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
 
 thread_local int g_b8_splits = 0;
 
-template <int S, int OW, int MT, int NT>
+template <int K, int S, int OW, int MT, int NT>
 int launch_b8(const B8FwdP& p, hipStream_t st) {
-    using G = B8Geom<S, OW, MT, NT>;
+    using G = B8Geom<K, S, OW, MT, NT>;
     static_assert(G::LDS_BYTES + 2048 <= 80 * 1024, "two workgroups per CU must fit the 160 KB LDS");
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5_b8_kernel<S, OW, MT, NT, false>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5_b8_kernel<K, S, OW, MT, NT, false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5_b8_kernel<S, OW, MT, NT, true>),
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5_b8_kernel<K, S, OW, MT, NT, true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
@@ -354,26 +359,49 @@ int launch_b8(const B8FwdP& p, hipStream_t st) {
     dim3 grid((unsigned)((pixels + G::PIX - 1) / G::PIX), (unsigned)(p.OP / G::WCOLS));
     if (G::OHW < G::PIX) grid.x = (unsigned)((p.N + G::NIMG - 1) / G::NIMG);
     g_b8_splits = (int)grid.x;
-    if (p.aff.sc) hipLaunchKernelGGL((conv5_b8_kernel<S, OW, MT, NT, true>), grid, dim3(256), G::LDS_BYTES, st, p);
-    else hipLaunchKernelGGL((conv5_b8_kernel<S, OW, MT, NT, false>), grid, dim3(256), G::LDS_BYTES, st, p);
+    if (p.aff.sc) hipLaunchKernelGGL((conv5_b8_kernel<K, S, OW, MT, NT, true>), grid, dim3(256), G::LDS_BYTES, st, p);
+    else hipLaunchKernelGGL((conv5_b8_kernel<K, S, OW, MT, NT, false>), grid, dim3(256), G::LDS_BYTES, st, p);
     JVAE_LAUNCH_CHECK();
     return 0;
 }
 
+// the (OW, S) tile plans of both kernel sizes
+template <int K>
+int launch_b8_k(const B8FwdP& p, int OW, int S, hipStream_t st) {
+    if (S == 1) {
+        switch (OW) {
+            case 4: return launch_b8<K, 1, 4, 1, 1>(p, st);      // 4x4 maps (deconv32+): 8 images per workgroup
+            case 8: return launch_b8<K, 1, 8, 2, 1>(p, st);
+            case 16: return launch_b8<K, 1, 16, 4, 1>(p, st);
+            case 32: return launch_b8<K, 1, 32, 4, 1>(p, st);
+            case 64: return launch_b8<K, 1, 64, 4, 1>(p, st);
+        }
+    } else {
+        switch (OW) {
+            case 4: return launch_b8<K, 2, 4, 1, 1>(p, st);
+            case 8: return launch_b8<K, 2, 8, 1, 1>(p, st);
+            case 16: return launch_b8<K, 2, 16, 2, 1>(p, st);
+            case 32: return launch_b8<K, 2, 32, 2, 1>(p, st);
+        }
+    }
+    return JVAE_ENOTSUP;
+}
+
 }  // namespace
 
-bool jvae_conv5_b8_fwd_ok(int Cin, int H, int W, int Cout, int OH, int OW, int S, int P) {
+bool jvae_conv5_b8_fwd_ok(int Cin, int H, int W, int Cout, int OH, int OW, int S, int P, int K) {
+    if (K != 5 && K != 3) return false;
     if (S != 1 && S != 2) return false;
     if (OH != OW || H != W || W != OW * S) return false;
     if (S == 1 && OW != 4 && OW != 8 && OW != 16 && OW != 32 && OW != 64) return false;
     if (S == 2 && OW != 4 && OW != 8 && OW != 16 && OW != 32) return false;
-    if (P < 0 || P > 4) return false;
-    if ((OW - 1) * S + 4 - P >= W + 4) return false;
+    if (P < 0 || P > K - 1) return false;
+    if ((OW - 1) * S + (K - 1) - P >= W + (K - 1)) return false;
     return Cin >= 1 && Cout >= 1;
 }
 
-size_t jvae_conv5_b8_pack_bytes(int Cin, int Cout) {
-    return (size_t)((Cin + 15) / 16) * 25 * 2 * ((Cout + 31) / 32 * 32) * 16;
+size_t jvae_conv5_b8_pack_bytes(int Cin, int Cout, int K) {
+    return (size_t)((Cin + 15) / 16) * K * K * 2 * ((Cout + 31) / 32 * 32) * 16;
 }
 
 int jvae_conv5_b8_max_splits(int N, int OW) { return (int)(((long)N * OW * OW + 127) / 128) + 1; }
@@ -412,46 +440,34 @@ int jvae_b8_channel_sum(const void* t, float* out, int N, int C, long HW, int ac
     return 0;
 }
 
-int jvae_conv5_b8_wpack(const float* w, void* wp, int C, int O, int swap, int flip, hipStream_t st) {
+int jvae_conv5_b8_wpack(const float* w, void* wp, int C, int O, int swap, int flip, hipStream_t st, int K) {
     const int KB = (C + 15) / 16, OP = (O + 31) / 32 * 32;
-    const long total = (long)KB * 25 * 2 * OP * 8;
+    const long total = (long)KB * K * K * 2 * OP * 8;
     const int blocks = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-    hipLaunchKernelGGL(b8_wpack_kernel, dim3(blocks), dim3(256), 0, st, w, (__bf16*)wp, C, O, KB, OP, swap, flip);
+    hipLaunchKernelGGL(b8_wpack_kernel, dim3(blocks), dim3(256), 0, st, w, (__bf16*)wp, C, O, KB, OP, swap, flip, K * K);
     JVAE_LAUNCH_CHECK();
     return 0;
+}
+
+// the bf16 operand of a KxK weight: the step's cache slot (pack_cache.hip) or `ws`; returns the pointer to read, nullptr on a
+// launch error
+const void* jvae_b8_packed(const float* w, void* ws, int C, int O, int swap, int flip, int K, hipStream_t st) {
+    bool fresh = true;
+    void* slot = jvae_pack_cache_get(K == 3 ? JVAE_PACK_B8_3 : JVAE_PACK_B8, w, C, O, swap, flip, &fresh);
+    if (slot) ws = slot;
+    if (!slot || !fresh)
+        if (jvae_conv5_b8_wpack(w, ws, C, O, swap, flip, st, K)) return nullptr;
+    return ws;
 }
 
 // in: B8 (N, ceil(Cin/8), H, W); out: B8 (N, ceil(Cout/8), OW, OW) or fp32 NCHW (out_f32).  ws: packed weights.
 int jvae_conv5_b8_fwd(const void* in, const float* w, int swap, int flip, const float* bias, void* out, int out_f32,
                       int N, int Cin, int H, int W, int Cout, int OW, int S, int P, void* ws, hipStream_t st,
-                      float* stats, int* nsplit, const InAff* aff) {
-    {
-        bool fresh = true;
-        void* slot = jvae_pack_cache_get(JVAE_PACK_B8, w, Cin, Cout, swap, flip, &fresh);
-        if (slot) ws = slot;
-        if (!slot || !fresh) {
-            int rc = jvae_conv5_b8_wpack(w, ws, Cin, Cout, swap, flip, st);
-            if (rc) return rc;
-        }
-    }
-    B8FwdP p{(const u32x4*)in, (const u32x4*)ws, bias, out, N, (Cin + 7) / 8, H, W, (Cout + 31) / 32 * 32, P,
+                      float* stats, int* nsplit, const InAff* aff, int K) {
+    const void* wp = jvae_b8_packed(w, ws, Cin, Cout, swap, flip, K, st);
+    if (!wp) return JVAE_EINVAL;
+    B8FwdP p{(const u32x4*)in, (const u32x4*)wp, bias, out, N, (Cin + 7) / 8, H, W, (Cout + 31) / 32 * 32, P,
              Cout, (Cout + 7) / 8, stats, out_f32, aff ? *aff : InAff{nullptr, nullptr, 0}};
     struct Fin { int* n; ~Fin() { if (n) *n = g_b8_splits; } } fin{nsplit};
-    if (S == 1) {
-        switch (OW) {
-            case 4: return launch_b8<1, 4, 1, 1>(p, st);      // 4x4 maps (deconv32+): 8 images per workgroup
-            case 8: return launch_b8<1, 8, 2, 1>(p, st);
-            case 16: return launch_b8<1, 16, 4, 1>(p, st);
-            case 32: return launch_b8<1, 32, 4, 1>(p, st);
-            case 64: return launch_b8<1, 64, 4, 1>(p, st);
-        }
-    } else {
-        switch (OW) {
-            case 4: return launch_b8<2, 4, 1, 1>(p, st);
-            case 8: return launch_b8<2, 8, 1, 1>(p, st);
-            case 16: return launch_b8<2, 16, 2, 1>(p, st);
-            case 32: return launch_b8<2, 32, 2, 1>(p, st);
-        }
-    }
-    return JVAE_ENOTSUP;
+    return K == 3 ? launch_b8_k<3>(p, OW, S, st) : launch_b8_k<5>(p, OW, S, st);
 }

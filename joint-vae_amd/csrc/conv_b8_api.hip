@@ -8,7 +8,8 @@
 
 namespace {
 
-inline bool is5(const ConvGeom& g) { return g.KH == 5 && g.KW == 5; }
+// the kernel sizes of the bf16 kernel families (the route decides which geometries of them run)
+inline bool has_b8_family(const ConvGeom& g) { return g.KH == g.KW && (g.KH == 5 || (g.KH == 3 && g.P == 1)); }
 inline size_t chsum_ws_bytes(int C) { return (size_t)((C + 7) / 8) * 8 * 64 * 4; }
 inline ConvRoute route(const ConvGeom& g, int transposed, ConvDir dir, CallFlags f = {}) {
     return jvae_conv_route(g, transposed, dir, CONV_B8, f);
@@ -18,10 +19,12 @@ inline ConvRoute route(const ConvGeom& g, int transposed, ConvDir dir, CallFlags
 int run_fwd(const ConvRoute& r, const ConvGeom& g, const void* in, const float* w, const float* bias, void* out, int y_f32,
             void* ws, hipStream_t st, float* stats = nullptr, int* nsplit = nullptr, const InAff* aff = nullptr) {
     const int sw = r.swap ? 1 : 0;
-    if (r.k == CK_T2_B8) return jvae_convt2_b8(in, w, bias, out, g.N, g.Cs, g.Ws, g.Cb, ws, st, stats, nsplit, aff);
+    if (r.k == CK_T2_B8) return jvae_convt2_b8(in, w, bias, out, g.N, g.Cs, g.Ws, g.Cb, ws, st, stats, nsplit, aff, g.KH);
     if (r.swap)
-        return jvae_conv5_b8_fwd(in, w, sw, sw, bias, out, y_f32, g.N, g.Cs, g.Hs, g.Ws, g.Cb, g.Wb, r.S, r.P, ws, st, stats, nsplit, aff);
-    return jvae_conv5_b8_fwd(in, w, sw, sw, bias, out, y_f32, g.N, g.Cb, g.Hb, g.Wb, g.Cs, g.Ws, r.S, r.P, ws, st, stats, nsplit, aff);
+        return jvae_conv5_b8_fwd(in, w, sw, sw, bias, out, y_f32, g.N, g.Cs, g.Hs, g.Ws, g.Cb, g.Wb, r.S, r.P, ws, st, stats, nsplit, aff,
+                                 g.KH);
+    return jvae_conv5_b8_fwd(in, w, sw, sw, bias, out, y_f32, g.N, g.Cb, g.Hb, g.Wb, g.Cs, g.Ws, r.S, r.P, ws, st, stats, nsplit, aff,
+                             g.KH);
 }
 
 int fwd_b8(const void* x, const float* w, const float* bias, void* y, int y_f32, float* stats, int* nsplit, const InAff* aff,
@@ -49,7 +52,7 @@ int wgrad_b8(const void* x, const void* dy, float* dw, float* dbias, int accumul
     if (!ws || ws_bytes < r.ws + (dbias ? chsum_ws_bytes(Cout) : 0)) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (!accumulate) {
-        hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * (size_t)Cin * Cout * 25, st);
+        hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * (size_t)Cin * Cout * KH * KW, st);
         if (e != hipSuccess) return (int)e;
         if (dbias && (e = hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, st)) != hipSuccess) return (int)e;
     }
@@ -60,7 +63,7 @@ int wgrad_b8(const void* x, const void* dy, float* dw, float* dbias, int accumul
     const int Ca = r.swap ? g.Cb : g.Cs, WS = r.swap ? g.Wb : g.Ws, Cb = r.swap ? g.Cs : g.Cb;
     int rc = r.k == CK_WG_B8X
         ? jvae_conv5_wgrad_b8x(ps, q, dw, 1, r.swap, g.N, Ca, WS, Cb, r.S, r.P, (float*)ws, st, aff_p, aff_q)
-        : jvae_conv5_wgrad_b8(ps, q, dw, 1, r.swap, g.N, Ca, WS, Cb, r.S, r.P, (float*)ws, st, aff_p, aff_q);
+        : jvae_conv5_wgrad_b8(ps, q, dw, 1, r.swap, g.N, Ca, WS, Cb, r.S, r.P, (float*)ws, st, aff_p, aff_q, KH);
     if (rc) return rc;
     if (dbias) rc = jvae_b8_channel_sum(dy, dbias, N, Cout, (long)oh * ow, 1, (float*)((char*)ws + r.ws), st);
     return rc;
@@ -97,9 +100,9 @@ size_t jvae_conv2d_workspace_bytes_b8(int N, int Cin, int H, int W, int Cout, in
                                       int transposed) {
     ConvGeom g; int oh, ow;
     if (!jvae_make_geom(N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, &g, &oh, &ow)) return 0;
-    if (!is5(g)) return 0;
+    if (!has_b8_family(g)) return 0;
     // the weight re-pack of either forward-type direction; the weight gradient's slabs + its bias gradient's sum
-    size_t a = jvae_conv5_b8_pack_bytes(g.Cb, g.Cs), b = jvae_conv5_b8_pack_bytes(g.Cs, g.Cb);
+    size_t a = jvae_conv5_b8_pack_bytes(g.Cb, g.Cs, g.KH), b = jvae_conv5_b8_pack_bytes(g.Cs, g.Cb, g.KH);
     if (b > a) a = b;
     const ConvRoute r = route(g, transposed, CONV_WGRAD);
     if (r.k != CK_NONE && (b = r.ws + chsum_ws_bytes(Cout)) > a) a = b;

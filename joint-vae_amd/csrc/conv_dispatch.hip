@@ -1,8 +1,10 @@
 // Kernel selection for one (transposed) convolution, fp32 and bf16: geometry, the route, and the fp32 executors.
 // Direction -> primitive mapping: see the conv_generic.hip header.
 //
-// Fast paths exist for the 5x5 "same-size / half-size" layers that carry >95 % of the FLOPs of conv32 / deconv32; everything
-// else (7x7, 8x8, 3x3, 4x4 heads, odd sizes) takes the unfold + GEMM path in fp32 and has no bf16 kernel.
+// Fast paths exist for the 5x5 "same-size / half-size" layers that carry >95 % of the FLOPs of conv32 / deconv32, in fp32 and
+// bf16.  The bf16 layout also has kernels for the 3x3 padding-1 layers of vgg* / ivgg* / conv32- / deconv32- (the same kernel
+// families at K = 3).  Everything else (7x7, 8x8, 4x4 heads, 3x3 padding-0 heads, odd sizes, and every 3x3 layer in fp32)
+// takes the unfold + GEMM path in fp32 and has no bf16 kernel.
 #include "common.h"
 #include "conv_dispatch.h"
 #include "conv_b8.h"
@@ -11,6 +13,8 @@
 namespace {
 
 inline bool is5(const ConvGeom& g) { return g.KH == 5 && g.KW == 5; }
+// the 3x3 layers with a bf16 kernel: padding 1 ('same' at stride 1, half size at stride 2)
+inline bool is3p1(const ConvGeom& g) { return g.KH == 3 && g.KW == 3 && g.P == 1; }
 inline size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 // Transposed convolution of a 1x1 input with no padding (imager.0 of deconv32: 64 x 1 x 1 -> 64 x 8 x 8): the
@@ -43,7 +47,7 @@ inline bool b8_aff_ok(int Cin, const CallFlags& f) { return (Cin + 7) / 8 * 8 <=
 ConvRoute fwd_route(const ConvGeom& g, int transposed, ConvDir dir, bool b8, const CallFlags& f) {
     const bool small_in = (dir == CONV_FWD) == (transposed != 0);
     const FwdOp o = fwd_op(g, small_in);
-    ConvRoute r{CK_NONE, small_in, small_in ? 1 : g.S, small_in ? 4 - g.P : g.P, 0, 0, false};
+    ConvRoute r{CK_NONE, small_in, small_in ? 1 : g.S, small_in ? g.KH - 1 - g.P : g.P, 0, 0, false};
     if (!b8 && transposed && point_input(g)) {
         r.k = CK_POINT;
         if (!small_in) r.ws = 4 * (size_t)16 * g.N * g.Cs;         // dgrad: K pieces of dx
@@ -56,16 +60,16 @@ ConvRoute fwd_route(const ConvGeom& g, int transposed, ConvDir dir, bool b8, con
     }
     if (small_in && g.S == 2) {     // stride-2 small -> big: the 4-phase kernels
         if (b8 && jvae_convt2_b8_ok(g.Cs, g.Hs, g.Ws, g.Cb, g.Hb, g.Wb, g.KH, g.KW, g.S, g.P) && !f.y_f32) {
-            r = ConvRoute{CK_T2_B8, true, 2, g.P, jvae_conv5_b8_pack_bytes(g.Cs, g.Cb), jvae_conv5_b8_max_splits(g.N, g.Ws),
+            r = ConvRoute{CK_T2_B8, true, 2, g.P, jvae_conv5_b8_pack_bytes(g.Cs, g.Cb, g.KH), jvae_conv5_b8_max_splits(g.N, g.Ws),
                           b8_aff_ok(g.Cs, f)};
         } else if (!b8 && jvae_convt2_ok(g.Cs, g.Hs, g.Ws, g.Cb, g.Hb, g.Wb, g.KH, g.KW, g.S, g.P)) {
             r = ConvRoute{jvae_convt2_x3_ok(g.N, g.Cs, g.Ws, g.Cb) ? CK_T2_X3 : CK_T2, true, 2, g.P,
                           4 * jvae_conv5_pack_floats(g.Cs, g.Cb), jvae_conv5_fwd_max_splits(g.N, g.Ws), true};
         }
-    } else if (is5(g) && (!small_in || g.S == 1)) {      // the implicit 5x5 kernels
-        if (b8 && jvae_conv5_b8_fwd_ok(o.Ci, o.H, o.W, o.Co, o.OH, o.OW, r.S, r.P)) {
+    } else if ((is5(g) || (b8 && is3p1(g))) && (!small_in || g.S == 1)) {      // the implicit 5x5 (and bf16 3x3) kernels
+        if (b8 && jvae_conv5_b8_fwd_ok(o.Ci, o.H, o.W, o.Co, o.OH, o.OW, r.S, r.P, g.KH)) {
             r.k = CK_B8;
-            r.ws = jvae_conv5_b8_pack_bytes(o.Ci, o.Co);
+            r.ws = jvae_conv5_b8_pack_bytes(o.Ci, o.Co, g.KH);
             r.splits = jvae_conv5_b8_max_splits(g.N, o.OW);
             r.aff_ok = b8_aff_ok(o.Ci, f);
         } else if (!b8 && jvae_conv5_fwd_ok(o.Ci, o.H, o.W, o.Co, o.OH, o.OW, r.S, r.P)) {
@@ -91,12 +95,13 @@ ConvRoute wgrad_route(const ConvGeom& g, int transposed, bool b8, const CallFlag
     const int few = b8 ? 8 : 15;
     const bool swap = g.S == 1 && g.Cs <= few && g.Cb > few && g.Hs == g.Hb;
     const WgOp o = wg_op(g, swap);
-    ConvRoute r{CK_NONE, swap, swap ? 1 : g.S, swap ? 4 - g.P : g.P, 0, 0, false};
-    if (is5(g) && b8 && jvae_conv5_wgrad_b8_ok(o.Ca, o.HS, o.WS, o.Cb, o.HB, o.WB, r.S, r.P)) {
-        // the LDS image and read-ahead pipeline of the split-bf16 kernel, one plane (conv_wgrad_x3.hip); the older kernel otherwise
-        const bool x = jvae_conv5_wgrad_b8x_ok(o.Ca, o.WS, o.WS, o.Cb, o.WS * r.S, o.WS * r.S, r.S, r.P);
+    ConvRoute r{CK_NONE, swap, swap ? 1 : g.S, swap ? g.KH - 1 - g.P : g.P, 0, 0, false};
+    if ((is5(g) || is3p1(g)) && b8 && jvae_conv5_wgrad_b8_ok(o.Ca, o.HS, o.WS, o.Cb, o.HB, o.WB, r.S, r.P, g.KH)) {
+        // the LDS image and read-ahead pipeline of the split-bf16 kernel, one plane (conv_wgrad_x3.hip, 5x5 only); the older
+        // kernel otherwise
+        const bool x = is5(g) && jvae_conv5_wgrad_b8x_ok(o.Ca, o.WS, o.WS, o.Cb, o.WS * r.S, o.WS * r.S, r.S, r.P);
         r.k = x ? CK_WG_B8X : CK_WG_B8;
-        r.ws = 4 * jvae_conv5_wgrad_b8_ws_floats(g.N, o.Ca, o.Cb);
+        r.ws = 4 * jvae_conv5_wgrad_b8_ws_floats(g.N, o.Ca, o.Cb, g.KH);
         r.aff_ok = f.aff != 2;
     } else if (is5(g) && !b8 && jvae_conv5_wgrad_ok(o.Ca, o.HS, o.WS, o.Cb, o.HB, o.WB, r.S, r.P)) {
         const bool x = jvae_conv5_wgrad_x3_ok(o.Ca, o.WS, o.WS, o.Cb, o.WS * r.S, o.WS * r.S, r.S, r.P);

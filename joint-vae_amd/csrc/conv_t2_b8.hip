@@ -10,6 +10,11 @@
 // A wave owns 32 consecutive small-grid pixels (MFMA columns) x 32 output channels (rows) and keeps the 4 phases in 4
 // accumulator sets; per 16 input channels it issues 9 patch reads (the 3x3 neighbourhood, one ds_read_b128 each,
 // shared by the phases), 25 weight reads and 25 v_mfma_f32_32x32x16_bf16.
+//
+// K = 3 (ConvTranspose2d(3, stride 2, padding 1, output_padding 1) and the dgrad of Conv2d(3, stride 2, padding 1): the
+// :2++1 / :2 layers of deconv32- / conv32-) is the same decomposition with P = (K - 1) / 2 = 1: tap (kh, kw) belongs to phase
+// (r, q) = ((kh + P) & 1, (kw + P) & 1) and reads the neighbour (r + P - kh) / 2, (q + P - kw) / 2 in {0, 1}, so the
+// phases have 1 / 2 / 2 / 4 taps and 4 of the 9 neighbourhood reads are used.
 #include "common.h"
 #include "jvae_internal.h"
 #include "conv_b8.h"
@@ -24,7 +29,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct T2B8P {
     const u32x4* in;     // small, B8 units (N, CBin, HS, WS)
-    const u32x4* wp;     // packed weight units (KB, 25, 2, OP)
+    const u32x4* wp;     // packed weight units (KB, K*K, 2, OP)
     const float* bias;   // (O) or null
     u32x2* out;          // big, B8 half units (N, CBout, 2HS, 2WS, 2)
     int N, CBin, OP, O, CBout;
@@ -32,8 +37,9 @@ struct T2B8P {
     InAff aff;           // deferred BatchNorm(+ReLU) of the input
 };
 
-template <int WS, int NW>
+template <int K, int WS, int NW>
 struct T2B8Geom {
+    static constexpr int TAPS = K * K;
     static constexpr int HS = WS;
     static constexpr int PIX = NW * 32;                          // small-grid pixels per workgroup
     static constexpr int HSWS = HS * WS;
@@ -43,13 +49,14 @@ struct T2B8Geom {
     static constexpr int WP = WS + 2;                            // one halo column each side
     static constexpr int CH = ROWS * WP;
     static constexpr int XS = NIMG * 2 * CH;                     // units of one K step
-    static constexpr int WSZ = 25 * 2 * 32;
+    static constexpr int WSZ = TAPS * 2 * 32;
     static constexpr int LDS_BYTES = (XS + WSZ) * 16;
 };
 
-template <int WS, int NW, bool AFF>
+template <int K, int WS, int NW, bool AFF>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void convt2_b8_kernel(T2B8P p) {
-    using G = T2B8Geom<WS, NW>;
+    using G = T2B8Geom<K, WS, NW>;
+    constexpr int P = (K - 1) / 2;
     constexpr int NT_ = NW * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     u32x4* Xs = reinterpret_cast<u32x4*>(lds_raw);
@@ -102,7 +109,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void convt2_b8_kernel(T2B
             const int u = tid + k * NT_;
             const int col = u % 32, th = u / 32;
             u32x4 v = {0u, 0u, 0u, 0u};
-            if (u < G::WSZ) v = p.wp[((long)kb * 50 + th) * p.OP + o0 + col];
+            if (u < G::WSZ) v = p.wp[((long)kb * (2 * G::TAPS) + th) * p.OP + o0 + col];
             rw[k] = v;
         }
     };
@@ -143,12 +150,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void convt2_b8_kernel(T2B
         wa[0] = Ws[(0 * 2 + half) * 32 + l31];
         wa[1] = Ws[(1 * 2 + half) * 32 + l31];
 #pragma unroll
-        for (int tap = 0; tap < 25; ++tap) {
-            const int kh = tap / 5, kw = tap % 5;
-            if (tap + 2 < 25) wa[(tap + 2) % 3] = Ws[((tap + 2) * 2 + half) * 32 + l31];
+        for (int tap = 0; tap < G::TAPS; ++tap) {
+            const int kh = tap / K, kw = tap % K;
+            if (tap + 2 < G::TAPS) wa[(tap + 2) % 3] = Ws[((tap + 2) * 2 + half) * 32 + l31];
             __builtin_amdgcn_sched_barrier(0);
-            const int r = kh & 1, q = kw & 1;
-            const int dh = (r + 2 - kh) / 2, dw = (q + 2 - kw) / 2;
+            const int r = (kh + P) & 1, q = (kw + P) & 1;
+            const int dh = (r + P - kh) / 2, dw = (q + P - kw) / 2;
             acc[r][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa[tap % 3]), nb[dh + 1][dw + 1],
                                                                 acc[r][q], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -209,48 +216,46 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void convt2_b8_kernel(T2B
 
 thread_local int g_t2b8_splits = 0;
 
-template <int WS, int NW>
+template <int K, int WS, int NW>
 int launch_t2b8(const T2B8P& p, hipStream_t st) {
-    using G = T2B8Geom<WS, NW>;
+    using G = T2B8Geom<K, WS, NW>;
     static_assert(G::LDS_BYTES <= 64 * 1024, "LDS budget");
     dim3 grid(G::HSWS >= G::PIX ? (unsigned)((long)p.N * G::HSWS / G::PIX) : (unsigned)((p.N + G::NIMG - 1) / G::NIMG),
               (unsigned)(p.OP / 32));
     g_t2b8_splits = (int)grid.x;
-    if (p.aff.sc) hipLaunchKernelGGL((convt2_b8_kernel<WS, NW, true>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
-    else hipLaunchKernelGGL((convt2_b8_kernel<WS, NW, false>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
+    if (p.aff.sc) hipLaunchKernelGGL((convt2_b8_kernel<K, WS, NW, true>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
+    else hipLaunchKernelGGL((convt2_b8_kernel<K, WS, NW, false>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
     JVAE_LAUNCH_CHECK();
     return 0;
+}
+
+template <int K>
+int launch_t2b8_k(const T2B8P& p, int WS, hipStream_t st) {
+    switch (WS) {
+        case 4: return launch_t2b8<K, 4, 4>(p, st);      // 4x4 -> 8x8 (deconv32+): 8 images per workgroup
+        case 8: return launch_t2b8<K, 8, 4>(p, st);
+        case 16: return launch_t2b8<K, 16, 4>(p, st);
+        case 32: return launch_t2b8<K, 32, 4>(p, st);
+    }
+    return JVAE_ENOTSUP;
 }
 
 }  // namespace
 
 bool jvae_convt2_b8_ok(int C, int HS, int WS, int O, int HB, int WB, int KH, int KW, int S, int P) {
-    if (KH != 5 || KW != 5 || S != 2 || P != 2) return false;
+    if (KH != KW || S != 2 || !((KH == 5 && P == 2) || (KH == 3 && P == 1))) return false;
     if (HS != WS || HB != 2 * HS || WB != 2 * WS) return false;
     if (WS != 4 && WS != 8 && WS != 16 && WS != 32) return false;
     return O >= 1 && C >= 1;
 }
 
-// small (N, ceil(C/8), WS, WS, 8) --ConvT 5x5 s2 p2 op1--> big (N, ceil(O/8), 2WS, 2WS, 8); ws: packed weights
+// small (N, ceil(C/8), WS, WS, 8) --ConvT KxK s2 p(K-1)/2 op1--> big (N, ceil(O/8), 2WS, 2WS, 8); ws: packed weights
 int jvae_convt2_b8(const void* in, const float* w, const float* bias, void* out, int N, int C, int WS, int O,
-                   void* ws, hipStream_t st, float* stats, int* nsplit, const InAff* aff) {
-    {
-        bool fresh = true;
-        void* slot = jvae_pack_cache_get(JVAE_PACK_B8, w, C, O, 1, 0, &fresh);
-        if (slot) ws = slot;
-        if (!slot || !fresh) {
-            int rc = jvae_conv5_b8_wpack(w, ws, C, O, 1, 0, st);
-            if (rc) return rc;
-        }
-    }
-    T2B8P p{(const u32x4*)in, (const u32x4*)ws, bias, (u32x2*)out, N, (C + 7) / 8, (O + 31) / 32 * 32, O, (O + 7) / 8, stats,
+                   void* ws, hipStream_t st, float* stats, int* nsplit, const InAff* aff, int K) {
+    const void* wp = jvae_b8_packed(w, ws, C, O, 1, 0, K, st);
+    if (!wp) return JVAE_EINVAL;
+    T2B8P p{(const u32x4*)in, (const u32x4*)wp, bias, (u32x2*)out, N, (C + 7) / 8, (O + 31) / 32 * 32, O, (O + 7) / 8, stats,
             aff ? *aff : InAff{nullptr, nullptr, 0}};
     struct Fin { int* n; ~Fin() { if (n) *n = g_t2b8_splits; } } fin{nsplit};
-    switch (WS) {
-        case 4: return launch_t2b8<4, 4>(p, st);         // 4x4 -> 8x8 (deconv32+): 8 images per workgroup
-        case 8: return launch_t2b8<8, 4>(p, st);
-        case 16: return launch_t2b8<16, 4>(p, st);
-        case 32: return launch_t2b8<32, 4>(p, st);
-    }
-    return JVAE_ENOTSUP;
+    return K == 3 ? launch_t2b8_k<3>(p, WS, st) : launch_t2b8_k<5>(p, WS, st);
 }

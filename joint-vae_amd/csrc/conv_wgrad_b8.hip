@@ -17,6 +17,8 @@
 // The A fragment (2 transposed reads per 16 pixels) is shared by all tiles of a wave; every MFMA needs its own B
 // fragment (2 transposed reads).  Accumulators stay in registers over the whole image loop; each workgroup writes one
 // fp32 slab, reduced in a fixed order by jvae_wgrad_slab_reduce (deterministic; shared with the fp32 path).
+//
+// K = 3 (the 3x3 layers of vgg / ivgg / conv32- / deconv32-) runs the same kernel on 9 taps: MODE 0 has 9 tiles, MODE 1 3.
 #include "common.h"
 #include "jvae_internal.h"
 #include "conv_b8.h"
@@ -31,26 +33,28 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 struct WgB8P {
     const u32x4* ps;     // B8 units (N, CBa, HS, WS)
     const u32x4* q;      // B8 units (N, CBb, HB, WB)
-    float* slab;         // (G, Ca, Cb*25)
+    float* slab;         // (G, Ca, Cb*K*K)
     int N, Ca, Cb, CBa, CBb, P, G;
     InAff aff_p, aff_q;  // deferred BatchNorm(+ReLU) of ps / q (whichever is the layer input); CBa*8 / CBb*8 coefficients
 };
 
-template <int S, int WS, int MODE>
+template <int K, int S, int WS, int MODE>
 struct WgB8Geom {
+    static constexpr int TAPS = K * K;
+    static constexpr int HALO = K - 1;                         // zero columns left of the interior
     static constexpr int HS = WS;
     static constexpr int TPIX = (S == 1 && WS >= 16) ? 128 : 64;
     static constexpr int TH = TPIX / WS;
     static constexpr int TILES = HS * WS / TPIX;
-    static constexpr int ROWS = (TH - 1) * S + 5;
+    static constexpr int ROWS = (TH - 1) * S + K;
     static constexpr int WB = WS * S;
-    static constexpr int WP0 = (WS - 1) * S + 9, WP1 = WB + 4;
+    static constexpr int WP0 = (WS - 1) * S + 2 * HALO + 1, WP1 = WB + HALO;
     static constexpr int WP = WP0 > WP1 ? WP0 : WP1;
     static constexpr int CH = ROWS * WP;                       // units per channel block
     static constexpr int NCBQ = MODE == 0 ? 4 : 1;             // channel blocks of Q staged per item
     static constexpr int QS = NCBQ * CH;
     static constexpr int PS = 4 * TPIX;
-    static constexpr int NTILE = MODE == 0 ? 25 : 7;
+    static constexpr int NTILE = MODE == 0 ? TAPS : (TAPS + 3) / 4;
     static constexpr int NBT = (NTILE + 3) / 4;                // per wave
     static constexpr int LDS_BYTES = (QS + PS) * 16;
 };
@@ -63,9 +67,9 @@ __device__ __forceinline__ bf16x8 tr_pair(const unsigned char* base, int off) {
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <int S, int WS, int MODE, bool AFF>
+template <int K, int S, int WS, int MODE, bool AFF>
 __global__ __launch_bounds__(256, 2) void conv5_wgrad_b8_kernel(WgB8P p) {
-    using G = WgB8Geom<S, WS, MODE>;
+    using G = WgB8Geom<K, S, WS, MODE>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     u32x4* Qs = reinterpret_cast<u32x4*>(lds_raw);
     u32x4* Pt = Qs + G::QS;
@@ -103,8 +107,8 @@ __global__ __launch_bounds__(256, 2) void conv5_wgrad_b8_kernel(WgB8P p) {
         int tap, cbl, sub;
         if (MODE == 0) { tap = tile; cbl = cg * 2 + (pp >> 1); sub = pp & 1; }
         else { tap = tile * 4 + cg * 2 + (pp >> 1); cbl = 0; sub = pp & 1; }
-        if (tap > 24) tap = 24;                                // unused slots: any valid address
-        boff[t] = (cbl * G::CH + lane_pix + (tap / 5) * G::WP + (tap % 5) + 4 - p.P) * 16 + sub * 8;
+        if (tap > G::TAPS - 1) tap = G::TAPS - 1;              // unused slots: any valid address
+        boff[t] = (cbl * G::CH + lane_pix + (tap / K) * G::WP + (tap % K) + G::HALO - p.P) * 16 + sub * 8;
     }
 
     f32x16 acc[G::NBT];
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void conv5_wgrad_b8_kernel(WgB8P p) {
                     const int ir = in_row0 + lr;
                     if (ir >= 0 && ir < HB && cbq0 + c < p.CBb) v = aff8(v, &ctab[c * 8], &ctab[NT8 + c * 8], p.aff_q.relu);
                 }
-                Qs[c * G::CH + lr * G::WP + 4 + x] = v;
+                Qs[c * G::CH + lr * G::WP + G::HALO + x] = v;
             }
         }
 #pragma unroll
@@ -201,8 +205,8 @@ __global__ __launch_bounds__(256, 2) void conv5_wgrad_b8_kernel(WgB8P p) {
         }
     }
 
-    // slab[g][a][b*25 + tap]: lane holds column l31, rows a = (r&3) + 8*(r>>2) + 4*half
-    float* slab = p.slab + (long)blockIdx.x * p.Ca * (p.Cb * 25);
+    // slab[g][a][b*TAPS + tap]: lane holds column l31, rows a = (r&3) + 8*(r>>2) + 4*half
+    float* slab = p.slab + (long)blockIdx.x * p.Ca * (p.Cb * G::TAPS);
 #pragma unroll
     for (int t = 0; t < G::NBT; ++t) {
         const int tile = wave + 4 * t;
@@ -210,24 +214,37 @@ __global__ __launch_bounds__(256, 2) void conv5_wgrad_b8_kernel(WgB8P p) {
         int b, tap;
         if (MODE == 0) { b = cbq0 * 8 + l31; tap = tile; }
         else { b = l31 & 7; tap = tile * 4 + (l31 >> 3); }
-        if (b >= p.Cb || tap > 24) continue;
+        if (b >= p.Cb || tap > G::TAPS - 1) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int a = a0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (a < p.Ca) slab[(long)a * (p.Cb * 25) + b * 25 + tap] = acc[t][r];
+            if (a < p.Ca) slab[(long)a * (p.Cb * G::TAPS) + b * G::TAPS + tap] = acc[t][r];
         }
     }
 }
 
-template <int S, int WS, int MODE>
+template <int K, int S, int WS, int MODE>
 int launch_wgb8(const WgB8P& p, hipStream_t st) {
-    using G = WgB8Geom<S, WS, MODE>;
+    using G = WgB8Geom<K, S, WS, MODE>;
     static_assert(G::LDS_BYTES <= 64 * 1024, "LDS budget");
     dim3 grid(p.G, (p.Ca + 31) / 32, MODE == 0 ? (p.Cb + 31) / 32 : 1);
-    if (p.aff_p.sc || p.aff_q.sc) hipLaunchKernelGGL((conv5_wgrad_b8_kernel<S, WS, MODE, true>), grid, dim3(256), G::LDS_BYTES, st, p);
-    else hipLaunchKernelGGL((conv5_wgrad_b8_kernel<S, WS, MODE, false>), grid, dim3(256), G::LDS_BYTES, st, p);
+    if (p.aff_p.sc || p.aff_q.sc) hipLaunchKernelGGL((conv5_wgrad_b8_kernel<K, S, WS, MODE, true>), grid, dim3(256), G::LDS_BYTES, st, p);
+    else hipLaunchKernelGGL((conv5_wgrad_b8_kernel<K, S, WS, MODE, false>), grid, dim3(256), G::LDS_BYTES, st, p);
     JVAE_LAUNCH_CHECK();
     return 0;
+}
+
+template <int K>
+int launch_wgb8_k(const WgB8P& p, int S, int WS, hipStream_t st) {
+#define WG_CASE(S_, WS_)                                                              \
+    case WS_: return p.Cb <= 8 ? launch_wgb8<K, S_, WS_, 1>(p, st) : launch_wgb8<K, S_, WS_, 0>(p, st);
+    if (S == 1) {
+        switch (WS) { WG_CASE(1, 8) WG_CASE(1, 16) WG_CASE(1, 32) WG_CASE(1, 64) }
+    } else {
+        switch (WS) { WG_CASE(2, 8) WG_CASE(2, 16) WG_CASE(2, 32) }
+    }
+#undef WG_CASE
+    return JVAE_ENOTSUP;
 }
 
 int slab_count(int N, int Ca, int Cb) {
@@ -241,39 +258,33 @@ int slab_count(int N, int Ca, int Cb) {
 
 }  // namespace
 
-bool jvae_conv5_wgrad_b8_ok(int Ca, int HS, int WS, int Cb, int HB, int WB, int S, int P) {
+bool jvae_conv5_wgrad_b8_ok(int Ca, int HS, int WS, int Cb, int HB, int WB, int S, int P, int K) {
+    if (K != 5 && K != 3) return false;
     if (S != 1 && S != 2) return false;
     if (HS != WS || HB != WB || WB != WS * S) return false;
     if (WS != 8 && WS != 16 && WS != 32 && WS != 64) return false;
     if (S == 2 && WS == 64) return false;
-    if (P < 0 || P > 4 || Ca < 1 || Cb < 1) return false;
+    if (P < 0 || P > K - 1 || Ca < 1 || Cb < 1) return false;
     return true;
 }
 
-size_t jvae_conv5_wgrad_b8_ws_floats(int N, int Ca, int Cb) {
-    const size_t a = (size_t)slab_count(N, Ca, Cb) * Ca * Cb * 25;
+size_t jvae_conv5_wgrad_b8_ws_floats(int N, int Ca, int Cb, int K) {
+    const size_t a = (size_t)slab_count(N, Ca, Cb) * Ca * Cb * K * K;
+    if (K != 5) return a;                  // the one-plane kernel (conv_wgrad_x3.hip) is 5x5 only
     const size_t b1 = jvae_conv5_wgrad_b8x_ws_floats(N, Ca, Cb, 1), b2 = jvae_conv5_wgrad_b8x_ws_floats(N, Ca, Cb, 2);
     const size_t b = b1 > b2 ? b1 : b2;
     return a > b ? a : b;
 }
 
-// dW (+)= ...; ps / q: B8 tensors; swapflip: the caller passed the role-swapped problem (dst = (b*Ca + a)*25 + 24 - tap).  The
-// geometries jvae_conv5_wgrad_b8x_ok refuses (jvae_conv_route picks).
+// dW (+)= ...; ps / q: B8 tensors; swapflip: the caller passed the role-swapped problem (dst = (b*Ca + a)*KK + KK-1 - tap).
+// The 5x5 geometries jvae_conv5_wgrad_b8x_ok refuses, and every 3x3 one (jvae_conv_route picks).
 int jvae_conv5_wgrad_b8(const void* ps, const void* q, float* dw, int accumulate, int swapflip,
                         int N, int Ca, int WS, int Cb, int S, int P, float* ws, hipStream_t st,
-                        const InAff* aff_p, const InAff* aff_q) {
+                        const InAff* aff_p, const InAff* aff_q, int K) {
     const InAff none{nullptr, nullptr, 0};
     WgB8P p{(const u32x4*)ps, (const u32x4*)q, ws, N, Ca, Cb, (Ca + 7) / 8, (Cb + 7) / 8, P, slab_count(N, Ca, Cb),
             aff_p ? *aff_p : none, aff_q ? *aff_q : none};
-    int rc = JVAE_ENOTSUP;
-#define WG_CASE(S_, WS_)                                                              \
-    case WS_: rc = Cb <= 8 ? launch_wgb8<S_, WS_, 1>(p, st) : launch_wgb8<S_, WS_, 0>(p, st); break;
-    if (S == 1) {
-        switch (WS) { WG_CASE(1, 8) WG_CASE(1, 16) WG_CASE(1, 32) WG_CASE(1, 64) }
-    } else {
-        switch (WS) { WG_CASE(2, 8) WG_CASE(2, 16) WG_CASE(2, 32) }
-    }
-#undef WG_CASE
+    const int rc = K == 3 ? launch_wgb8_k<3>(p, S, WS, st) : launch_wgb8_k<5>(p, S, WS, st);
     if (rc) return rc;
-    return jvae_wgrad_slab_reduce(ws, dw, p.G, Ca, Cb, accumulate, swapflip, st);
+    return jvae_wgrad_slab_reduce(ws, dw, p.G, Ca, Cb, accumulate, swapflip, st, 0, K * K);
 }

@@ -200,21 +200,23 @@ __global__ __launch_bounds__(256, 2) void conv5_wgrad_kernel(WgP p) {
 }
 
 // dw[dst(i)] (+)= sum_g slab[g][i] in a fixed order (4 interleaved partial sums per output, then LDS).
-// swapflip: slab is (a, b, tap') of the role-swapped problem -> dst = (b*Ca + a)*25 + 24 - tap'.
+// swapflip: slab is (a, b, tap') of the role-swapped problem -> dst = (b*Ca + a)*taps + taps-1 - tap'.
 // tapmajor: the slab is (a, tap, b) instead of (a, b, tap) (conv_wgrad_x3.hip: lanes = channels b, coalesced slab stores).
-__device__ __forceinline__ int wgrad_dst(int i, int Ca, int Cb, int swapflip, int tapmajor) {
+// taps: 25 (5x5) or 9 (the 3x3 bf16 kernels)
+__device__ __forceinline__ int wgrad_dst(int i, int Ca, int Cb, int swapflip, int tapmajor, int taps) {
     if (!swapflip && !tapmajor) return i;
     int tap, b;
-    const int a = i / (25 * Cb);
-    if (tapmajor) { b = i % Cb; tap = (i / Cb) % 25; }
-    else { tap = i % 25; b = (i / 25) % Cb; }
-    return swapflip ? (b * Ca + a) * 25 + 24 - tap : (a * Cb + b) * 25 + tap;
+    const int a = i / (taps * Cb);
+    if (tapmajor) { b = i % Cb; tap = (i / Cb) % taps; }
+    else { tap = i % taps; b = (i / taps) % Cb; }
+    return swapflip ? (b * Ca + a) * taps + taps - 1 - tap : (a * Cb + b) * taps + tap;
 }
 
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ dw,
-                                                           int G, int Ca, int Cb, int accumulate, int swapflip, int tapmajor) {
+                                                           int G, int Ca, int Cb, int accumulate, int swapflip, int tapmajor,
+                                                           int taps) {
     __shared__ float part[4][64];
-    const int total = Ca * Cb * 25;
+    const int total = Ca * Cb * taps;
     const int ix = threadIdx.x & 63, gy = threadIdx.x >> 6;
     const int i = blockIdx.x * 64 + ix;
     float s = 0.f;
@@ -224,16 +226,17 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     __syncthreads();
     if (gy != 0 || i >= total) return;
     s = (part[0][ix] + part[1][ix]) + (part[2][ix] + part[3][ix]);
-    const int dst = wgrad_dst(i, Ca, Cb, swapflip, tapmajor);
+    const int dst = wgrad_dst(i, Ca, Cb, swapflip, tapmajor, taps);
     dw[dst] = accumulate ? dw[dst] + s : s;
 }
 
 // The same fold with 16-byte accesses (Ca*Cb*25 a multiple of 4): 16 outputs-of-4 x 16 slab lanes per workgroup, every
 // thread adds its G/16 slabs in order, the 16 partial sums are folded in a fixed order.
 __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const f32x4* __restrict__ slab, float* __restrict__ dw,
-                                                            int G, int Ca, int Cb, int accumulate, int swapflip, int tapmajor) {
+                                                            int G, int Ca, int Cb, int accumulate, int swapflip, int tapmajor,
+                                                            int taps) {
     __shared__ f32x4 part[16][16];
-    const int total4 = Ca * Cb * 25 / 4;
+    const int total4 = Ca * Cb * taps / 4;
     const int ix = threadIdx.x & 15, gy = threadIdx.x >> 4;
     const int i4 = blockIdx.x * 16 + ix;
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const f32x4* __restr
     s = (t[0] + t[1]) + (t[2] + t[3]);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const int dst = wgrad_dst(i4 * 4 + e, Ca, Cb, swapflip, tapmajor);
+        const int dst = wgrad_dst(i4 * 4 + e, Ca, Cb, swapflip, tapmajor, taps);
         dw[dst] = accumulate ? dw[dst] + s[e] : s[e];
     }
 }
@@ -279,13 +282,14 @@ inline int pick_cb(int S, int WS, int Cb) {
 
 // dw (+)= sum over the G slabs (a, b, tap) in a fixed order; shared with the split-bf16 and bf16 kernels
 int jvae_wgrad_slab_reduce(const float* slab, float* dw, int G, int Ca, int Cb, int accumulate, int swapflip, hipStream_t st,
-                           int tapmajor) {
-    const int total = Ca * Cb * 25;
+                           int tapmajor, int taps) {
+    const int total = Ca * Cb * taps;
     if (total % 4 == 0 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0)
         hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(cdiv(total / 4, 16)), dim3(256), 0, st, (const f32x4*)slab, dw, G, Ca, Cb,
-                           accumulate, swapflip, tapmajor);
+                           accumulate, swapflip, tapmajor, taps);
     else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 64)), dim3(256), 0, st, slab, dw, G, Ca, Cb, accumulate, swapflip, tapmajor);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 64)), dim3(256), 0, st, slab, dw, G, Ca, Cb, accumulate, swapflip,
+                           tapmajor, taps);
     JVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -44,6 +44,7 @@ struct ConvGeom {
     int KH, KW, S, P; // kernel, stride, padding (as in nn.Conv2d / nn.ConvTranspose2d)
 };
 
-// dw (+)= sum over the G weight-gradient slabs (a, b, tap) in a fixed order (conv_wgrad_mfma.hip; every wgrad kernel family)
+// dw (+)= sum over the G weight-gradient slabs (a, b, tap) in a fixed order (conv_wgrad_mfma.hip; every wgrad kernel family);
+// taps = KH*KW of the layer
 int jvae_wgrad_slab_reduce(const float* slab, float* dw, int G, int Ca, int Cb, int accumulate, int swapflip, hipStream_t st,
-                           int tapmajor = 0);
+                           int tapmajor = 0, int taps = 25);

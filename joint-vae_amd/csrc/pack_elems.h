@@ -1,11 +1,13 @@
 // The three weight re-pack mappings of the 5x5 convolution kernels, one definition each: used by the per-layer pack kernels
 // (conv_mfma.hip, conv_x3.hip, conv_b8.hip) and by the batched refresh of the pack cache (pack_cache.hip).
 // Source w: PyTorch layout [o][c][tap] (swap: [c][o][tap] = ConvTranspose2d / role swap); flip: tap -> 24 - tap.
+// JVAE_PACK_B8_3 is the bf16 unit layout of JVAE_PACK_B8 for the 3x3 kernels: 9 taps, flip: tap -> 8 - tap.
 #pragma once
 #include "common.h"
 #include "conv_x3.h"
 
-enum JvaePackKind { JVAE_PACK_F32 = 0, JVAE_PACK_X3 = 1, JVAE_PACK_B8 = 2, JVAE_PACK_X3S = 3, JVAE_PACK_SCI = 4, JVAE_PACK_T2S = 5 };
+enum JvaePackKind { JVAE_PACK_F32 = 0, JVAE_PACK_X3 = 1, JVAE_PACK_B8 = 2, JVAE_PACK_X3S = 3, JVAE_PACK_SCI = 4, JVAE_PACK_T2S = 5,
+                    JVAE_PACK_B8_3 = 7 };
 
 // tap pairs per K step of the 16x16x32 split-bf16 layout: 25 taps = 12 pairs + tap 24 with an all-zero partner, + one all-zero
 // pair so that every staging group of the kernel (2 pairs) is complete
@@ -20,17 +22,18 @@ __host__ __device__ __forceinline__ long jvae_pack_elems(int kind, int C, int O)
     if (kind == JVAE_PACK_SCI) return (long)((O + 7) / 8) * C * 25 * 8;
     if (kind == JVAE_PACK_X3S) return (long)((C + 15) / 16) * JVAE_X3S_PAIRS * 4 * OP * 8;
     if (kind == JVAE_PACK_T2S) return (long)((C + 31) / 32) * 25 * 4 * OP * 8;
-    return (long)((C + 15) / 16) * 25 * 2 * OP * 8;
+    return (long)((C + 15) / 16) * (kind == JVAE_PACK_B8_3 ? 9 : 25) * 2 * OP * 8;
 }
 __host__ __device__ __forceinline__ size_t jvae_pack_bytes(int kind, int C, int O) {
     const long n = jvae_pack_elems(kind, C, O);
     return (size_t)n * ((kind == JVAE_PACK_F32 || kind == JVAE_PACK_SCI) ? 4 : ((kind == JVAE_PACK_X3 || kind == JVAE_PACK_X3S || kind == JVAE_PACK_T2S) ? 6 : 2));
 }
 
-__device__ __forceinline__ float jvae_pack_src(const float* __restrict__ w, int C, int O, int c, int o, int tap, int swap, int flip) {
-    const int st = flip ? 24 - tap : tap;
+__device__ __forceinline__ float jvae_pack_src(const float* __restrict__ w, int C, int O, int c, int o, int tap, int swap, int flip,
+                                               int taps = 25) {
+    const int st = flip ? taps - 1 - tap : tap;
     if (c >= C || o >= O) return 0.f;
-    return swap ? w[((long)c * O + o) * 25 + st] : w[((long)o * C + c) * 25 + st];
+    return swap ? w[((long)c * O + o) * taps + st] : w[((long)o * C + c) * taps + st];
 }
 
 // fp32 operand of conv_mfma.hip / conv_t2_mfma.hip: Wp[c][tap][o] (o < OP, zero for o >= O)
@@ -53,13 +56,14 @@ __device__ __forceinline__ void jvae_pack_sci_elem(const float* __restrict__ w, 
 }
 
 // i -> (kb, tap, half, o, ci) of the 16-byte-unit layouts (8 channels of one (tap, o) per unit)
-__device__ __forceinline__ void jvae_pack_unit_index(long i, int OP, int* kb, int* tap, int* half, int* o, int* ci) {
+__device__ __forceinline__ void jvae_pack_unit_index(long i, int OP, int* kb, int* tap, int* half, int* o, int* ci,
+                                                     int taps = 25) {
     *ci = (int)(i % 8);
     long t = i / 8;
     *o = (int)(t % OP); t /= OP;
     *half = (int)(t % 2); t /= 2;
-    *tap = (int)(t % 25);
-    *kb = (int)(t / 25);
+    *tap = (int)(t % taps);
+    *kb = (int)(t / taps);
 }
 
 // split-bf16 operand of conv_x3.hip / conv_t2_x3.hip:
@@ -125,13 +129,14 @@ __device__ __forceinline__ void jvae_pack_t2s_elem(const float* __restrict__ w, 
         wp[(((((long)kb * 25 + ts) * 3 + pl) * 4 + kq) * OP + o) * 8 + ci] = s[pl];
 }
 
-// bf16 operand of conv_b8.hip / conv_t2_b8.hip: Wp[kb][tap][half][o][ci] = bf16(W[o][c = kb*16 + half*8 + ci][tap])
+// bf16 operand of conv_b8.hip / conv_t2_b8.hip: Wp[kb][tap][half][o][ci] = bf16(W[o][c = kb*16 + half*8 + ci][tap]);
+// taps = 25 (JVAE_PACK_B8) or 9 (JVAE_PACK_B8_3)
 __device__ __forceinline__ void jvae_pack_b8_elem(const float* __restrict__ w, __bf16* __restrict__ wp, long i,
-                                                  int C, int O, int swap, int flip) {
+                                                  int C, int O, int swap, int flip, int taps = 25) {
     const int OP = jvae_pack_op(O);
     int kb, tap, half, o, ci;
-    jvae_pack_unit_index(i, OP, &kb, &tap, &half, &o, &ci);
-    wp[i] = (__bf16)jvae_pack_src(w, C, O, kb * 16 + half * 8 + ci, o, tap, swap, flip);
+    jvae_pack_unit_index(i, OP, &kb, &tap, &half, &o, &ci, taps);
+    wp[i] = (__bf16)jvae_pack_src(w, C, O, kb * 16 + half * 8 + ci, o, tap, swap, flip, taps);
 }
 
 // pack_cache.hip.  Returns the cache slot holding the packed form of (kind, w, C, O, swap, flip), or nullptr when the cache

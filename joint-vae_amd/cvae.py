@@ -382,7 +382,9 @@ class ClassificationVariationalNetwork(nn.Module):
     def set_compute_dtype(self, dtype):
         """'fp32' (the reference's arithmetic; default) or 'bf16' (config 5 of BASELINE.json): bf16 activations between the
         layers of the conv stacks and bf16 matrix-core convolutions from the fp32 master weights; BatchNorm statistics,
-        the dense heads, the latent / loss math, gradients of parameters and Adam stay fp32."""
+        the dense heads, the latent / loss math, gradients of parameters and Adam stay fp32.  Native bf16 layers: 5x5 and 3x3
+        padding-1 convolutions on maps of 4x4 and larger (conv32*, deconv32*, vgg*, ivgg*) and the M / A / U tokens; the
+        others (3x3 padding-0 / 7x7 / 8x8 heads, 3x3 layers on 2x2 / 1x1 maps) run on the fp32 kernels between two conversions."""
         from module.vae_layers.conv import HipConvStack
         if dtype not in ('fp32', 'bf16'):
             raise ValueError(dtype)

@@ -101,6 +101,10 @@ _SIGS = {
     'jvae_pool2d_bwd_f32': (c_int, [P, P, P, c_long] + [c_int] * 6 + [P]),
     'jvae_upsample_nearest_fwd_f32': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
     'jvae_upsample_nearest_bwd_f32': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
+    'jvae_pool2d_fwd_b8': (c_int, [P, P, P, c_long] + [c_int] * 6 + [P]),
+    'jvae_pool2d_bwd_b8': (c_int, [P, P, P, c_long] + [c_int] * 6 + [P]),
+    'jvae_upsample_nearest_fwd_b8': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
+    'jvae_upsample_nearest_bwd_b8': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
 }
 
 

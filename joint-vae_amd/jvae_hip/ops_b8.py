@@ -229,3 +229,81 @@ class _ReluB8(torch.autograd.Function):
 
 def relu(x):
     return _ReluB8.apply(x)
+
+
+# ------------------------------------------------------------------------------- pooling / up-sampling
+def pool2d_fwd_raw(x, K, S, P, mode):
+    """x: B8 -> (y B8, idx int32 (N, CB, OH, OW, 8) for max pooling, else None)."""
+    x = O._c(x)
+    N, CB, H, W, _ = x.shape
+    oh, ow = c_int(0), c_int(0)
+    L.check(L.load().jvae_pool2d_out_shape(H, W, K, S, P, byref(oh), byref(ow)), 'pool2d_out_shape')
+    y = torch.empty((N, CB, oh.value, ow.value, 8), device=x.device, dtype=torch.bfloat16)
+    idx = torch.empty(y.shape, device=x.device, dtype=torch.int32) if mode == O.POOL_MAX else None
+    L.check(L.load().jvae_pool2d_fwd_b8(L.ptr(x), L.ptr(y), L.ptr(idx), N * CB, H, W, K, S, P, mode, L.stream_ptr()),
+            'jvae_pool2d_fwd_b8')
+    return y, idx
+
+
+def pool2d_bwd_raw(gy, idx, H, W, K, S, P, mode):
+    gy = O._c(gy)
+    N, CB = gy.shape[:2]
+    gx = torch.empty((N, CB, H, W, 8), device=gy.device, dtype=torch.bfloat16)
+    L.check(L.load().jvae_pool2d_bwd_b8(L.ptr(gy), L.ptr(idx), L.ptr(gx), N * CB, H, W, K, S, P, mode, L.stream_ptr()),
+            'jvae_pool2d_bwd_b8')
+    return gx
+
+
+def upsample_nearest_fwd_raw(x, scale):
+    x = O._c(x)
+    N, CB, H, W, _ = x.shape
+    y = torch.empty((N, CB, H * scale, W * scale, 8), device=x.device, dtype=torch.bfloat16)
+    L.check(L.load().jvae_upsample_nearest_fwd_b8(L.ptr(x), L.ptr(y), N * CB, H, W, scale, L.stream_ptr()),
+            'jvae_upsample_nearest_fwd_b8')
+    return y
+
+
+def upsample_nearest_bwd_raw(gy, scale):
+    gy = O._c(gy)
+    N, CB, OH, OW, _ = gy.shape
+    gx = torch.empty((N, CB, OH // scale, OW // scale, 8), device=gy.device, dtype=torch.bfloat16)
+    L.check(L.load().jvae_upsample_nearest_bwd_b8(L.ptr(gy), L.ptr(gx), N * CB, OH // scale, OW // scale, scale,
+                                                  L.stream_ptr()), 'jvae_upsample_nearest_bwd_b8')
+    return gx
+
+
+class _Pool2dB8(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, K, S, P, mode):
+        y, idx = pool2d_fwd_raw(x, K, S, P, mode)
+        ctx.save_for_backward(idx)
+        ctx.cfg = (x.shape[2], x.shape[3], K, S, P, mode)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        idx, = ctx.saved_tensors
+        return pool2d_bwd_raw(gy, idx, *ctx.cfg), None, None, None, None
+
+
+class _UpsampleNearestB8(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.scale = scale
+        return upsample_nearest_fwd_raw(x, scale)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return upsample_nearest_bwd_raw(gy, ctx.scale), None
+
+
+def pool2d(x, kernel_size, stride=None, padding=0, mode=O.POOL_MAX):
+    """ops.pool2d on a B8 tensor (same window order / tie rule / fp32 sums, bf16 result)."""
+    return _Pool2dB8.apply(x, int(kernel_size), int(stride or kernel_size), int(padding), mode)
+
+
+def upsample_nearest(x, scale):
+    """ops.upsample_nearest on a B8 tensor."""
+    if int(scale) != scale or scale < 1:
+        raise L.JvaeHipError('nearest up-sampling is built for integer scale factors')
+    return _UpsampleNearestB8.apply(x, int(scale))

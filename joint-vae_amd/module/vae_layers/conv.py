@@ -96,7 +96,8 @@ def conv_layer_name(conv_layer):
 
 
 class HipPool2d(nn.Module):
-    """nn.MaxPool2d / nn.AvgPool2d of the layer DSL (tokens `M` / `A`, reference conv.py:201-206) on the HIP kernels."""
+    """nn.MaxPool2d / nn.AvgPool2d of the layer DSL (tokens `M` / `A`, reference conv.py:201-206) on the HIP kernels, in the
+    layout of its input (fp32, or B8 inside a bf16 stack)."""
 
     def __init__(self, letter, kernel_size, stride=None, padding=0):
         super().__init__()
@@ -104,21 +105,24 @@ class HipPool2d(nn.Module):
         self.kernel_size, self.stride, self.padding = int(kernel_size), int(stride or kernel_size), int(padding)
 
     def forward(self, x):
-        return ops.pool2d(x, self.kernel_size, self.stride, self.padding, ops.POOL_MAX if self.letter == 'M' else ops.POOL_AVG)
+        pool = ops_b8.pool2d if ops_b8.is_b8(x) else ops.pool2d
+        return pool(x, self.kernel_size, self.stride, self.padding, ops.POOL_MAX if self.letter == 'M' else ops.POOL_AVG)
 
     def extra_repr(self):
         return f'{self.letter}: kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}'
 
 
 class HipUpsamplingNearest2d(nn.Module):
-    """nn.UpsamplingNearest2d(scale_factor) of the layer DSL (token `U`, reference conv.py:208-212)."""
+    """nn.UpsamplingNearest2d(scale_factor) of the layer DSL (token `U`, reference conv.py:208-212), in the layout of its
+    input."""
 
     def __init__(self, scale_factor):
         super().__init__()
         self.scale_factor = scale_factor
 
     def forward(self, x):
-        return ops.upsample_nearest(x, self.scale_factor)
+        up = ops_b8.upsample_nearest if ops_b8.is_b8(x) else ops.upsample_nearest
+        return up(x, self.scale_factor)
 
     def extra_repr(self):
         return f'scale_factor={self.scale_factor}'
@@ -185,8 +189,11 @@ class HipConvStack(nn.Sequential):
 
     compute_dtype 'bf16' (config 5 of BASELINE.json; no counterpart in the fp32 reference): activations between the
     layers are bf16 in the B8 layout (jvae_hip/ops_b8.py), convolutions run on the bf16 matrix cores with fp32
-    accumulation from the fp32 master weights; the stack still takes and returns fp32 NCHW tensors.  Layers whose
-    geometry has no bf16 kernel at all (the 3x3 / 4x4 / 7x7 / 8x8 heads) stay on the fp32 kernels."""
+    accumulation from the fp32 master weights; the stack still takes and returns fp32 NCHW tensors.  The 5x5 and the 3x3
+    padding-1 layers (conv32(+/-), deconv32(+/-), vgg*, ivgg*) have bf16 kernels on maps of 4x4 and larger, and pooling /
+    up-sampling tokens run on B8 kernels of their own, so such a stack stays in B8 from its first convolution to its end.
+    Layers whose geometry has no bf16 kernel (3x3 padding-0 / 4x4 / 7x7 / 8x8 heads, 3x3 layers on 2x2 / 1x1 maps) stay
+    on the fp32 kernels between two conversions."""
 
     compute_dtype = 'fp32'
     # BatchNorm+ReLU applied by the consuming convolution where its kernels can; JVAE_DEFER_BN=0: A/B switch
@@ -248,6 +255,8 @@ class HipConvStack(nn.Sequential):
             kind = ACT_OF_MODULE.get(type(m))
             if lay is ops_b8.B8 and kind in lay.acts:
                 x = ops_b8.relu(x) if kind == ops.RELU else x
+            elif lay is ops_b8.B8 and isinstance(m, (HipPool2d, HipUpsamplingNearest2d)):
+                x = m(x)             # B8 kernels of their own
             else:
                 if lay is ops_b8.B8:
                     x = ops_b8.from_b8(x, channels)

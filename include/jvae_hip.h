@@ -411,6 +411,22 @@ int jvae_upsample_nearest_bwd_b8(const void* dy, void* dx, long blocks, int H, i
 int jvae_augment_u8_f32(const unsigned char* in, const unsigned char* flip, const int* dy, const int* dx,
                         float* out, int N, int C, int H, int W, int pad, int nhwc, void* stream);
 
+/* ---- ROC of OOD scores: AUC and the FPR / thresholds at kept TPRs (csrc/roc.hip) -----------------------------------
+ * Replaces utils/roc_curves.py:38-210 (roc_curve, a Python loop over every in-distribution score) as
+ * ood_detection_rates calls it per method and OOD set (cvae.py:1843-1868), for M score rows in one call.
+ * ins (M, n_in), outs (M, n_out): fp32 scores, higher = more in-distribution.  kept_tpr: K doubles, ascending.
+ * two_sided: M int32 on the device, 0 = one-sided test (roc_curves.py:85-88), 1 = 'around-mean' (roc_curves.py:68-72);
+ * the spline modes (a tuple, roc_curves.py:74-83) are not built.
+ * Outputs (fp64): auc (M), kept_fpr / kept_tpr_out / thr_low / thr_up (M, K): what the reference returns, the rates and
+ * thresholds bit for bit (same fp64 expressions over integer counts and exactly widened scores), the AUC summed exactly
+ * over the counts and divided once.  status (M int32): bit 0 = a NaN score was seen, bit 1 = around-mean row with a
+ * non-finite in-score; the other outputs of such a row are meaningless (never out of bounds).
+ * n_in, n_out in [1, 2^24]; M <= 65535; ws 8-byte aligned, jvae_roc_workspace_bytes(...) bytes (0 = invalid sizes). */
+size_t jvae_roc_workspace_bytes(int M, long n_in, long n_out);
+int jvae_roc_curve_f32(const float* ins, const float* outs, const double* kept_tpr, const int* two_sided,
+                       double* auc, double* kept_fpr, double* kept_tpr_out, double* thr_low, double* thr_up, int* status,
+                       int M, long n_in, long n_out, int K, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -912,6 +912,188 @@ class ClassificationVariationalNetwork(nn.Module):
             self.train()
         return acc[methods[0]] if only_one else acc
 
+    OOD_KEPT_TPR = [pc / 100 for pc in range(90, 100)]                        # cvae.py:1736
+    OOD_ROC_EVERY = 100                                                       # batches between two progress ROCs (cvae.py:1843)
+
+    def _ood_methods(self, method):
+        """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
+        line), a name or a list of names; the spline-threshold ('-a-x-y') and ODIN methods raise when asked for by name."""
+        def unbuilt(m):
+            return '-a-' in m or m.startswith('odin')
+        if method == 'all':
+            skipped = [m for m in self.ood_methods if unbuilt(m)]
+            if skipped:
+                logging.warning('ood_detection_rates: methods outside this build are left out: %s', ', '.join(skipped))
+            return [m for m in self.ood_methods if not unbuilt(m)]
+        methods = [method] if isinstance(method, str) else list(method)
+        for m in methods:
+            if unbuilt(m):
+                raise NotImplementedError(f'{m}: spline-threshold (-a-x-y) and ODIN OOD methods are outside this build')
+        return methods
+
+    def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False):
+        """One pass over `dset` for ood_detection_rates: per batch the label-free evaluation (or the batch read back from a full
+        recorder), `batch_dist_measures`, and the score rows written into ONE preallocated (M, n) device buffer - no value comes
+        to the host here.  on_batch(i, num_batch, scores_so_far) is called after each batch.  -> (M, n) fp32 device scores."""
+        device = self.device
+        name = getattr(dset, 'name', 'set')
+        recorded = recorder is not None and len(recorder) >= num_batch
+        recording = recorder is not None and not recorded
+        if recorded:
+            num_batch, batch_size = len(recorder), recorder.batch_size
+        if recording:
+            recorder.reset()
+            recorder.num_batch = num_batch
+        if recorder is not None:
+            recorder.init_seed_for_dataloader()
+        loader = None if recorded else iter(torch.utils.data.DataLoader(dset, batch_size=batch_size, num_workers=0, shuffle=shuffle))
+        buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
+        filled, sums, measures = 0, {}, None
+        with torch.no_grad():
+            for i in range(num_batch):
+                if recorded:
+                    keys = [k for k in recorder.keys() if k in self.loss_components]
+                    losses = recorder.get_batch(i, *keys, force_dict=True)
+                    logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
+                else:
+                    x, y = next(loader)[:2]
+                    x, y = self._device_batch(x.to(device)), y.to(device)
+                    _, logits, losses, measures = self.evaluate(x, batch=i, current_measures=measures)
+                    if recording:
+                        extra = {} if logits is None else {'logits': logits.T}
+                        recorder.append_batch(**losses, y_true=y, **extra)
+                scores = self.batch_dist_measures(logits, losses, methods)
+                n = scores[methods[0]].shape[0]
+                for r, m in enumerate(methods):
+                    buf[r, filled:filled + n] = scores[m]
+                filled += n
+                if keep_test:
+                    for k, v in losses.items():                                      # cvae.py:1671, summed on the device
+                        sums[k] = sums.get(k, 0.) + v.float().mean()
+                if on_batch is not None:
+                    on_batch(i, num_batch, buf[:, :filled])
+        if keep_test:
+            self.test_losses = {k: float(v) / max(num_batch, 1) for k, v in
+                                zip(sums, torch.stack(list(sums.values())).tolist())} if sums else {}
+            if measures:
+                self.test_measures = dict(measures)
+        if recorder is not None:
+            recorder.restore_seed()
+        if recording:
+            for d in sample_dirs:
+                os.makedirs(d, exist_ok=True)
+                recorder.save(os.path.join(d, 'record-{}.pth'.format(name)))
+        return buf[:, :filled].contiguous()
+
+    @staticmethod
+    def _row_mean_std(scores):
+        """fp64 mean and population standard deviation (np.std, ddof = 0) of each score row, on the device -> (M, 2)."""
+        x = scores.double()
+        mean = x.mean(1)
+        return torch.stack([mean, ((x - mean[:, None]).abs() ** 2).mean(1).sqrt()], 1)
+
+    def ood_detection_rates(self, oodsets=None, testset=None, batch_size=100, num_batch='all', method='all', print_result=False,
+                            update_self_ood=True, epoch='last', outputs=None, recorders=None, from_where='all', sample_dirs=[],
+                            sample_recorders=None, log=True):
+        """OOD detection rates of `oodsets` against the in-distribution `testset` per OOD method, with the reference's signature
+        and result dictionary (cvae.py:1455-1911): -> {set: {method: {'epochs', 'n', 'mean', 'std', 'auc', 'tpr', 'fpr',
+        'thresholds'}}}, `self.ood_results[epoch]` updated when `update_self_ood` (with the in-distribution set's
+        {'n', 'epochs', 'mean', 'std:'} entry - the reference's key has that colon), `test_losses` / `test_measures` set from
+        the in-distribution pass, `record-<set>.pth` written into `sample_dirs` through the `LossRecorder`s of `recorders`
+        ({} = make one per set, filled in place), and a full recorder read back instead of evaluating, as in accuracy().
+
+        Underneath, the scores never leave the device: every batch's `batch_dist_measures` rows go into one (M, n) buffer per
+        set, the ROC of all M methods of a set is ONE `ops.roc_curve` call (csrc/roc.hip) made every 100 batches for the
+        progress line and at the last batch, as the reference does with its Python loop (utils/roc_curves.py:38-210), and only
+        its (M, K) results and the fp64 row means / deviations come to the host.  'thresholds' holds the K [low, up] pairs
+        (the reference stores list(dict), i.e. the two key names).  Methods: what `batch_dist_measures` computes, one-sided
+        or with the '-2s' suffix (two-sided around the mean); see `_ood_methods` for the rest.  Named datasets
+        (`testset=None` or a string, `oodsets=None`) and the registry lookup of earlier results (`from_where`) are host
+        plumbing outside this build, as for accuracy(); so are `sample_recorders`."""
+        if testset is None or isinstance(testset, str) or oodsets is None or any(isinstance(o, str) for o in oodsets):
+            raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
+        if sample_recorders:
+            raise NotImplementedError('sample_recorders are outside this build')
+        if not method:
+            return
+        if epoch == 'last':
+            epoch = self.trained
+        methods = self._ood_methods(method)
+        names = [getattr(s, 'name', 'set') for s in [testset] + list(oodsets)]
+        if recorders is not None and not recorders:
+            from jvae_compat.recorders import LossRecorder
+            recorders.update({n: LossRecorder(batch_size) for n in names})
+        recorders = recorders or {}
+        ood_results = {n: {} for n in names[1:]}
+        if not oodsets:
+            return ood_results
+        was_training = self.training
+        self.eval()
+        modes = ['around-mean' if m.endswith('-2s') else False for m in methods]
+
+        def plan(dset):
+            full = int(np.ceil(len(dset) / batch_size))
+            limited = isinstance(num_batch, int) and num_batch < full
+            return (num_batch if limited else full), limited
+
+        sink = outputs if outputs is not None and hasattr(outputs, 'results') else None
+
+        def progress_line(name, row_means, fpr):
+            """on_batch callback of a pass: the progress line of cvae.py:1709-1715,1870-1875, written at the reference's ROC
+            points (every 100 batches and the last one); None without a sink, and the pass then brings nothing to the host."""
+            if sink is None:
+                return None
+            t0 = time.time()
+
+            def on_batch(i, nb, scores):
+                if i % self.OOD_ROC_EVERY and i != nb - 1:
+                    return
+                sink.results(i, nb, 0, 1, metrics=dict(zip(methods, row_means(scores))), fpr=fpr(),
+                             time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, preambule=name)
+            return on_batch
+
+        nb, shuffle = plan(testset)
+        ind = self._score_set(testset, methods, batch_size, nb, shuffle, recorders.get(names[0]), sample_dirs, keep_test=True,
+                              on_batch=progress_line(names[0], lambda s: self._row_mean_std(s)[:, 0].tolist(),
+                                                     lambda: {m: np.nan for m in methods}))
+        if update_self_ood:
+            entry = self.ood_results.setdefault(epoch, {}).setdefault(names[0], {})
+            for m, (mean, std) in zip(methods, self._row_mean_std(ind).tolist()):
+                entry[m] = {'n': ind.shape[1], 'epochs': epoch, 'mean': mean, 'std:': std}
+
+        kept = torch.tensor(self.OOD_KEPT_TPR, dtype=torch.float64, device=ind.device)
+        K = len(self.OOD_KEPT_TPR)
+        for oodset, name in zip(oodsets, names[1:]):
+            last = {}
+
+            def roc(scores):
+                """ONE device ROC for all methods, ONE copy of its (M, 4K + 4) results to the host."""
+                r = ops.roc_curve(ind, scores.contiguous(), kept, modes)
+                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['status'].double()[:, None],
+                                  self._row_mean_std(scores)], 1).cpu().numpy()
+                ops.roc_check_status(host[:, 1 + 4 * K].astype(np.int64))
+                last['host'] = host
+                return host[:, -2].tolist()
+
+            def fpr95():
+                return {m: float(h[1 + 5]) for m, h in zip(methods, last['host'])}      # fpr_at_tpr(..., 0.95): slot 5 of the kept TPRs
+
+            nb, shuffle = plan(oodset)
+            scores = self._score_set(oodset, methods, batch_size, nb, shuffle, recorders.get(name), sample_dirs,
+                                     on_batch=progress_line(name, roc, fpr95))
+            if sink is None:                                  # with a sink the last batch's progress ROC is the final one
+                roc(scores)
+            for m, h in zip(methods, last['host']):
+                fpr, low, up = h[1:1 + K], h[1 + 2 * K:1 + 3 * K], h[1 + 3 * K:1 + 4 * K]
+                ood_results[name][m] = {'epochs': epoch, 'n': scores.shape[1], 'mean': float(h[-2]), 'std': float(h[-1]),
+                                        'auc': float(h[0]), 'tpr': list(self.OOD_KEPT_TPR), 'fpr': [float(f) for f in fpr],
+                                        'thresholds': [[float(a), float(b)] for a, b in zip(low, up)]}
+                if update_self_ood:
+                    self.ood_results.setdefault(epoch, {}).setdefault(name, {})[m] = ood_results[name][m]
+        if was_training:
+            self.train()
+        return ood_results
+
     def _early_reduce_hook(self, grad):
         self.optimizer.reduce_early_bucket()
         return grad
@@ -1108,8 +1290,8 @@ class ClassificationVariationalNetwork(nn.Module):
           epoch -> `validation_accuracy / _measures / _loss`, with `record-<set>.pth` written under `save_dir/samples/{last,
           <epoch>}` (cvae.py:2293-2382); `train_accuracy=True` adds `accuracy(trainset)` -> `train_accuracy`;
         * the hot loop cvae.py:2424-2501 = train_step(); the final test pass of cvae.py:2528-2545.
-        OOD detection rates (`oodsets`, cvae.py:2328-2336,2513-2526: ROC / FPR tooling over the recorders) are out of scope
-        (SURVEY.md §2a): a warning says so once and the phase is skipped.
+        The OOD phase (`oodsets`, cvae.py:2328-2336,2513-2526) is not wired into this loop yet: a warning says so once and the
+        phase is skipped - call `ood_detection_rates()` after training.
 
         data_augmentation: the reference hands the list to its dataset factory, which prepends RandomHorizontalFlip ('flip')
         and RandomCrop(size, padding=size//8 [0 for imagenet sets], padding_mode='edge') ('crop') to the training transforms

@@ -1,0 +1,41 @@
+"""The public names of the reference's `utils/roc_curves.py` on the device ROC (jvae_hip.ops.roc_curve, csrc/roc.hip).
+
+`roc_curve` takes what the reference's takes (array-likes or tensors, on any device: they are moved to the GPU as fp32, the
+precision in which the model produces its scores) and returns numpy values of the same shapes.  What the reference computes
+through a SciPy smoothing spline (`two_sided=(a, b)`), a validation split or reversed scores is not built and raises.
+"""
+import numpy as np
+import torch
+
+from jvae_hip import ops
+
+
+def fpr_at_tpr(fpr, tpr, a, thresholds=None, return_threshold=False):
+    """fpr and tpr in ascending order (utils/roc_curves.py:8-27)."""
+    assert not return_threshold or thresholds is not None
+    i_ = np.where(np.asarray(tpr) >= a)[0].min()
+    fpr_ = np.asarray(fpr)[i_]
+    return (fpr_, thresholds[i_]) if return_threshold else fpr_
+
+
+def tpr_at_fpr(fpr, tpr, a):
+    """utils/roc_curves.py:30-35"""
+    return np.asarray(tpr)[np.where(np.asarray(fpr) <= a)[0]].max()
+
+
+def roc_curve(ins, outs, *kept_tpr, two_sided=False, validation=0, debug=False, ins_are_higher=True, device=None):
+    """-> (auc, kept_fpr, kept_tpr, {'low': ..., 'up': ...}) of utils/roc_curves.py:38-210; ValueError on a NaN score (and on
+    a non-finite in-score with two_sided='around-mean', where the reference fails as well)."""
+    if validation:
+        raise NotImplementedError('roc_curve: a validation split of the in-scores is not built')
+    if not ins_are_higher:
+        raise NotImplementedError('roc_curve: ins_are_higher=False is not built')
+    if isinstance(two_sided, tuple):
+        raise NotImplementedError('roc_curve: the spline thresholds (two_sided=(a, b)) are not built')
+    device = device or ('cuda' if torch.cuda.is_available() else 'cpu')      # off the GPU the op raises JvaeHipError
+    rows = [torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(device=device, dtype=torch.float32).reshape(-1)
+            for v in (ins, outs)]
+    r = ops.roc_curve(rows[0], rows[1], sorted(kept_tpr), 'around-mean' if two_sided == 'around-mean' else False)
+    ops.roc_check_status([int(r['status'].cpu())])
+    host = {k: r[k].cpu().numpy() for k in ('auc', 'fpr', 'tpr', 'low', 'up')}
+    return float(host['auc']), host['fpr'], host['tpr'], {'low': host['low'], 'up': host['up']}

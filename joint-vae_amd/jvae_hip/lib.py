@@ -105,6 +105,8 @@ _SIGS = {
     'jvae_pool2d_bwd_b8': (c_int, [P, P, P, c_long] + [c_int] * 6 + [P]),
     'jvae_upsample_nearest_fwd_b8': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
     'jvae_upsample_nearest_bwd_b8': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
+    'jvae_roc_workspace_bytes': (c_size_t, [c_int, c_long, c_long]),
+    'jvae_roc_curve_f32': (c_int, [P] * 10 + [c_int, c_long, c_long, c_int, P, c_size_t, P]),
 }
 
 

@@ -1059,6 +1059,63 @@ def adam_step_dev(p, g, m, v, hyper, advance, eps, weight_decay, max_norm=0., sq
     L.check(rc, 'jvae_adam_step_dev_f32')
 
 
+# ------------------------------------------------------------------------------------------- ROC of OOD scores
+def roc_curve(ins, outs, kept_tpr, two_sided=False):
+    """AUC and the FPR / thresholds at the kept TPRs of M score rows in one call (utils/roc_curves.py:38-210; csrc/roc.hip).
+    ins (M, n_in) or (n_in,), outs (M, n_out) or (n_out,): fp32 scores on the device, higher = more in-distribution.
+    kept_tpr: ascending floats (list or fp64 device tensor of K).  two_sided: per row (or one value for all rows) False / True
+    = one-sided test, 'around-mean' = two-sided around the mean of the in-scores; int32 device tensor of 0 / 1 accepted.
+    -> dict of DEVICE tensors: 'auc' (M,), 'fpr' / 'tpr' / 'low' / 'up' (M, K) fp64 and 'status' (M,) int32 (bit 0: NaN score,
+    bit 1: non-finite in-score of an around-mean row; `roc_check_status` raises on them).  (n,) inputs drop the M axis.
+    Nothing is synchronised or copied to the host."""
+    lib = L.load()
+    single = ins.dim() == 1
+    ins, outs = _c(_f32(ins, 'roc_curve')), _c(_f32(outs, 'roc_curve'))
+    L.ptr(ins), L.ptr(outs)                                    # off the GPU: JvaeHipError, before anything else is looked at
+    if single:
+        ins, outs = ins[None], outs[None]
+    if ins.dim() != 2 or outs.dim() != 2 or ins.shape[0] != outs.shape[0] or ins.shape[1] < 1 or outs.shape[1] < 1:
+        raise L.JvaeHipError(f'roc_curve: (M, n_in) and (M, n_out) score rows expected, got {tuple(ins.shape)} and {tuple(outs.shape)}')
+    M, n_in, n_out, dev = ins.shape[0], ins.shape[1], outs.shape[1], ins.device
+    if torch.is_tensor(kept_tpr):
+        kept = _c(kept_tpr.to(device=dev, dtype=torch.float64))
+    else:
+        kept = torch.tensor(sorted(float(t) for t in kept_tpr), dtype=torch.float64, device=dev)
+    if torch.is_tensor(two_sided):
+        modes = _c(two_sided.to(device=dev, dtype=torch.int32))
+    else:
+        rows = list(two_sided) if isinstance(two_sided, (list, tuple)) else [two_sided] * M
+        for t in rows:
+            if t not in (False, True, 0, 1, None, 'around-mean'):
+                raise NotImplementedError(f'roc_curve: two_sided={t!r} (the spline thresholds of the reference are not built)')
+        modes = torch.tensor([1 if t == 'around-mean' else 0 for t in rows], dtype=torch.int32, device=dev)
+    if modes.numel() != M:
+        raise L.JvaeHipError(f'roc_curve: {modes.numel()} modes for {M} rows')
+    K = kept.numel()
+    out = torch.empty((4, M, max(K, 1)), dtype=torch.float64, device=dev)
+    auc = torch.empty(M, dtype=torch.float64, device=dev)
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    nbytes = lib.jvae_roc_workspace_bytes(M, n_in, n_out)
+    if not nbytes:
+        raise L.JvaeHipError(f'roc_curve: sizes out of range (M={M}, n_in={n_in}, n_out={n_out})')
+    ws = L.workspace(nbytes, dev)
+    rc = lib.jvae_roc_curve_f32(L.ptr(ins), L.ptr(outs), L.ptr(kept), L.ptr(modes), L.ptr(auc), L.ptr(out[0]), L.ptr(out[1]),
+                                L.ptr(out[2]), L.ptr(out[3]), L.ptr(status), M, n_in, n_out, K, L.ptr(ws), ws.numel(),
+                                L.stream_ptr())
+    L.check(rc, 'jvae_roc_curve_f32')
+    res = {'auc': auc, 'fpr': out[0, :, :K], 'tpr': out[1, :, :K], 'low': out[2, :, :K], 'up': out[3, :, :K], 'status': status}
+    return {k: v[0] for k, v in res.items()} if single else res
+
+
+def roc_check_status(status):
+    """Raise ValueError for the rows `roc_curve` flagged (host values of its 'status' word)."""
+    for m, s in enumerate(status if hasattr(status, '__len__') else [status]):
+        if int(s) & 1:
+            raise ValueError(f'roc_curve: NaN score in row {m}')
+        if int(s) & 2:
+            raise ValueError(f'roc_curve: non-finite in-distribution score in around-mean row {m}')
+
+
 # ------------------------------------------------------------------------------------------- input pipeline
 def augment_batch(images_u8, flip=None, dy=None, dx=None, pad=0, nhwc=True):
     """uint8 batch (N,H,W,C) [or (N,C,H,W) with nhwc=False] -> float32 (N,C,H,W) in [0,1] with the reference's training

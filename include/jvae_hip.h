@@ -136,6 +136,12 @@ int jvae_bn_bwd_f32(const float* dy, const float* x, const float* gamma, const f
                     const float* save_mean, const float* save_invstd,
                     float* dx, float* dgamma, float* dbeta, int accumulate,
                     int N, int C, int P, int relu, void* ws, size_t ws_bytes, void* stream);
+/* Backward of the EVAL-mode BatchNorm (+activation; running statistics are constants): dx = dy * gamma * rsqrt(running_var + eps)
+ * * act'(y), the mask re-derived from x exactly as the forward computes y.  One elementwise pass; no parameter gradients.
+ * Serves the materialised and the deferred form (x = the BatchNorm's input in both). */
+int jvae_bn_eval_bwd_f32(const float* dy, const float* x, const float* gamma, const float* beta,
+                         const float* running_mean, const float* running_var, float* dx,
+                         int N, int C, int P, float eps, int relu, void* stream);
 
 /* Deferred BatchNorm: statistics + per-channel coefficients only (scale, shift: C floats each, y = fmaf(x, scale, shift));
  * the normalisation (+ReLU) itself is applied by the CONSUMING convolution while it stages its input
@@ -426,6 +432,18 @@ size_t jvae_roc_workspace_bytes(int M, long n_in, long n_out);
 int jvae_roc_curve_f32(const float* ins, const float* outs, const double* kept_tpr, const int* two_sided,
                        double* auc, double* kept_fpr, double* kept_tpr_out, double* thr_low, double* thr_up, int* status,
                        int M, long n_in, long n_out, int K, void* ws, size_t ws_bytes, void* stream);
+
+/* ODIN out-of-distribution scores (csrc/odin.hip; reference cvae.py:1645-1663): the two ends of the loop.
+ * Head: logits of F batched forwards, element (f, l, n, c) at f * stride_f + l * stride_l + n * C + c with l = 0 .. L (row 0, the mean
+ * latent, is left out of the mean), temps (F) -> scores (F, N) = max_c softmax_c(mean_{l >= 1} logits / temps[f]); dlogits (same
+ * layout, or NULL) receives d(sum_n scores)/d(logits) = p_max (delta_{c,argmax} - p_c) / (L temps[f]) for l >= 1 and 0 for l = 0.
+ * Ties in the max resolve to the first index.
+ * Perturb: acc (numel) += g (NULL: acc is left as it is), then out (E, numel): out[e][i] = x[i] + eps[e] * sign(acc[i]) with
+ * sign(0) = 0; eps (E) in device memory. */
+int jvae_odin_head_f32(const float* logits, const float* temps, float* scores, float* dlogits,
+                       int F, int L, int N, int C, long stride_f, long stride_l, void* stream);
+int jvae_odin_perturb_f32(float* acc, const float* g, const float* x, const float* eps, float* out, long numel, int E,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -317,6 +317,49 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
+// Eval-mode backward (running statistics are constants): dx = dy * gamma * rsqrt(running_var + eps) * act'(y), one elementwise
+// pass, no reductions, no parameter gradients.  The mask is the forward's own fmaf(x, scale, shift) > 0 (bn_coef), for the
+// materialised and for the deferred form alike.  One block per (channel, image chunk).
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          const float* __restrict__ running_mean,
+                                                          const float* __restrict__ running_var, float* __restrict__ dx,
+                                                          int N, int C, int P, int nchunk, float eps, int relu) {
+    const int c = blockIdx.x, j = blockIdx.y;
+    const float neg = relu == JVAE_ACT_LEAKY ? JVAE_LEAKY_SLOPE : 0.f;
+    const float g_ = gamma ? gamma[c] : 1.f, b_ = beta ? beta[c] : 0.f;
+    float sc, sh;
+    bn_coef(g_, b_, running_mean[c], rsqrtf(running_var[c] + eps), &sc, &sh);
+    const ImageRange ir = image_range(N, nchunk, j);
+    const int nb = ir.nb, ne = ir.ne;
+    if ((P & 3) == 0) {
+        const unsigned cnt = (unsigned)(ne - nb) * (unsigned)(P >> 2);
+        const Plane4Idx pi = plane4_idx(nb, C, c, P);
+#pragma unroll 2
+        for (unsigned i = threadIdx.x; i < cnt; i += 256) {
+            const long off = pi(i);
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + off);
+            f32x4 gv = *reinterpret_cast<const f32x4*>(dy + off);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float g = gv[e];
+                if (relu && !(fmaf(xv[e], sc, sh) > 0.f)) g *= neg;
+                gv[e] = g * sc;
+            }
+            *reinterpret_cast<f32x4*>(dx + off) = gv;
+        }
+    } else {
+        const long cnt = (long)(ne - nb) * P;
+        for (long i = threadIdx.x; i < cnt; i += blockDim.x) {
+            const long n = nb + i / P, q = i % P;
+            const long idx = (n * C + c) * (long)P + q;
+            float g = dy[idx];
+            if (relu && !(fmaf(x[idx], sc, sh) > 0.f)) g *= neg;
+            dx[idx] = g * sc;
+        }
+    }
+}
+
 // sums[c] = sum over splits of partial[c][s] (fp64 accumulation, fixed order)
 __global__ void bn_fold_kernel(const float* __restrict__ partial, float* __restrict__ sums, int C, int nsplit) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -485,6 +528,18 @@ int jvae_bn_bwd_f32(const float* dy, const float* x, const float* gamma, const f
     const int nc = pick_chunk(N, C, P);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(C, nc), dim3(256), 0, st, dy, x, gamma, beta, save_mean, save_invstd,
                        partial, dx, dgamma, dbeta, accumulate, N, C, P, ns, nc, relu, (const float*)nullptr, 1, (order >> 1) & 1);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+int jvae_bn_eval_bwd_f32(const float* dy, const float* x, const float* gamma, const float* beta,
+                         const float* running_mean, const float* running_var, float* dx,
+                         int N, int C, int P, float eps, int relu, void* stream) {
+    if (!dy || !x || !running_mean || !running_var || !dx || N < 0 || C <= 0 || P <= 0) return JVAE_EINVAL;
+    if (N == 0) return 0;
+    const int nc = pick_chunk(N, C, P);
+    hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(C, nc), dim3(256), 0, (hipStream_t)stream, dy, x, gamma, beta, running_mean,
+                       running_var, dx, N, C, P, nc, eps, jvae_act_kind(relu));
     JVAE_LAUNCH_CHECK();
     return 0;
 }

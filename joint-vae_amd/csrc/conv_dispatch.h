@@ -53,6 +53,8 @@ int jvae_convt2(const float* in, const float* wpacked, const float* bias, float*
 bool jvae_conv5_smallco_ok(int Cin, int H, int W, int Cout, int KH, int KW, int S, int P);
 int jvae_conv5_smallco(const float* in, const float* w, const float* bias, float* out, int N, int Cin, int W, int Cout,
                        hipStream_t st, const InAff* aff = nullptr);
+// the data gradient of the mirror layer (Conv2d with <= 4 INPUT channels: the gradient with respect to the input image)
+int jvae_conv5_smallco_dgrad(const float* dy, const float* w, float* dx, int N, int Cy, int W, int Cx, hipStream_t st);
 
 // ... and with <= 4 INPUT channels (forward-type operator, any weight role: the first layer's forward, the head's dgrad)
 bool jvae_conv5_smallci_ok(int Cin, int H, int W, int Cout, int OW, int S, int P, bool dgrad_role);
@@ -85,6 +87,7 @@ enum ConvKernel {
     CK_GENERIC, CK_POINT,                     // unfold + GEMM (conv_generic.hip); the 1x1-input transposed layer as plain GEMMs
     CK_SMALLCO, CK_SMALLCI, CK_FWD5, CK_FWD5_X3, CK_T2, CK_T2_X3, CK_WG5, CK_WG5_X3,     // fp32
     CK_B8, CK_T2_B8, CK_WG_B8, CK_WG_B8X,                                                // bf16
+    CK_SMALLCO_DG,                            // fp32, CONV_DGRAD only: the input-image gradient of a <= 4-input-channel 5x5 layer
 };
 // The per-call facts that change the choice
 struct CallFlags {

@@ -58,6 +58,14 @@ ConvRoute fwd_route(const ConvGeom& g, int transposed, ConvDir dir, bool b8, con
         r.aff_ok = g.Cb <= 256;
         return r;
     }
+    // The gradient with respect to the input IMAGE (features.0 of conv32 / conv32+: dy with 32 channels -> dx with 3): the training step
+    // never asks for it (its input needs no gradient); before this route it took CK_FWD5_X3 - the split-bf16 matrix-core kernel with 3
+    // useful output channels of its 32-wide tile.  The vector-ALU kernel of the image head, weights read swapped and flipped.
+    if (!b8 && dir == CONV_DGRAD && !transposed && g.Hs == g.Hb && g.Ws == g.Wb &&
+        jvae_conv5_smallco_ok(g.Cs, g.Hb, g.Wb, g.Cb, g.KH, g.KW, g.S, g.P)) {
+        r.k = CK_SMALLCO_DG;
+        return r;
+    }
     if (small_in && g.S == 2) {     // stride-2 small -> big: the 4-phase kernels
         if (b8 && jvae_convt2_b8_ok(g.Cs, g.Hs, g.Ws, g.Cb, g.Hb, g.Wb, g.KH, g.KW, g.S, g.P) && !f.y_f32) {
             r = ConvRoute{CK_T2_B8, true, 2, g.P, jvae_conv5_b8_pack_bytes(g.Cs, g.Cb, g.KH), jvae_conv5_b8_max_splits(g.N, g.Ws),
@@ -170,6 +178,7 @@ int jvae_conv_run_fwd(const ConvRoute& r, const ConvGeom& g, const float* in, co
     const int sw = r.swap ? 1 : 0;
     switch (r.k) {
         case CK_SMALLCO: return jvae_conv5_smallco(in, w, bias, out, g.N, g.Cb, g.Wb, g.Cs, st, aff);
+        case CK_SMALLCO_DG: return jvae_conv5_smallco_dgrad(in, w, out, g.N, g.Cs, g.Wb, g.Cb, st);
         case CK_SMALLCI: return jvae_conv5_smallci(in, w, sw, sw, bias, out, g.N, o.Ci, o.W, o.Co, ws, st, stats, nsplit);
         case CK_FWD5_X3:
             return jvae_conv5_x3_fwd(in, w, sw, sw, bias, out, g.N, o.Ci, o.H, o.W, o.Co, o.OW, r.S, r.P, ws, st, stats, nsplit, aff);

@@ -33,7 +33,9 @@ struct SmP {
 // then serves 3 reads per 60 FMAs.  CC = 4 input channels per stage (23 KB): four workgroups per CU, so the 1024 workgroups
 // of the 32 x 32 head (one image each) are all resident at once - the first form ran 768 at a time, a second round for the
 // last third.
-template <int OW, int CO, int CC, bool LEAKY = false>
+// DG: the data gradient of the mirror layer, Conv2d(CO -> Cin channels) - features.0 of conv32 / conv32+, 32 -> 3: `in` is dy, `w` that
+// layer's (Cin, CO, 5, 5) weight read with its two channel indices swapped and its taps flipped; no bias, no deferred BatchNorm.
+template <int OW, int CO, int CC, bool LEAKY = false, bool DG = false>
 __global__ __launch_bounds__(256, 4) void conv5_smallco2_kernel(SmP p) {
     constexpr int OH = OW;
     constexpr int TH = 1024 / OW;                  // rows per workgroup
@@ -119,7 +121,8 @@ __global__ __launch_bounds__(256, 4) void conv5_smallco2_kernel(SmP p) {
 #pragma unroll
                 for (int o = 0; o < CO; ++o)
 #pragma unroll
-                    for (int kw = 0; kw < 5; ++kw) wv[o][kw] = wq[((long)o * p.Cin + ch) * 25 + kh * 5 + kw];
+                    for (int kw = 0; kw < 5; ++kw)
+                        wv[o][kw] = DG ? wq[((long)ch * CO + o) * 25 + (4 - kh) * 5 + (4 - kw)] : wq[((long)o * p.Cin + ch) * 25 + kh * 5 + kw];
 #pragma unroll
                 for (int kw = 0; kw < 5; ++kw)
 #pragma unroll
@@ -258,12 +261,13 @@ __global__ __launch_bounds__(256, 4) void conv5_smallci_kernel(SciP p) {
 }
 
 template <int OW>
-int launch_sm(const SmP& p, int CO, hipStream_t st) {
+int launch_sm(const SmP& p, int CO, hipStream_t st, bool dgrad = false) {
     dim3 grid((unsigned)(p.N * (OW * OW / 1024)));
     const bool leaky = p.aff.sc && p.aff.relu == JVAE_ACT_LEAKY;
 #define SM_CASE(CO_) \
     case CO_: \
-        if (leaky) hipLaunchKernelGGL((conv5_smallco2_kernel<OW, CO_, 4, true>), grid, dim3(256), 0, st, p); \
+        if (dgrad) hipLaunchKernelGGL((conv5_smallco2_kernel<OW, CO_, 4, false, true>), grid, dim3(256), 0, st, p); \
+        else if (leaky) hipLaunchKernelGGL((conv5_smallco2_kernel<OW, CO_, 4, true>), grid, dim3(256), 0, st, p); \
         else hipLaunchKernelGGL((conv5_smallco2_kernel<OW, CO_, 4, false>), grid, dim3(256), 0, st, p); \
         break;
     switch (CO) {
@@ -286,6 +290,15 @@ int jvae_conv5_smallco(const float* in, const float* w, const float* bias, float
     SmP p{in, w, bias, out, N, Cin, 2, aff ? *aff : InAff{nullptr, nullptr, 0}};
     if (W == 32) return launch_sm<32>(p, Cout, st);
     if (W == 64) return launch_sm<64>(p, Cout, st);
+    return JVAE_ENOTSUP;
+}
+
+// Data gradient of Conv2d(Cx -> Cy, 5x5, stride 1, padding 2) with Cx <= 4 (the model's first layer: the gradient with respect to the
+// input image): dy (N, Cy, W, W), w (Cy, Cx, 5, 5) -> dx (N, Cx, W, W); jvae_conv5_smallco_ok(Cy, W, W, Cx, ...) says whether.
+int jvae_conv5_smallco_dgrad(const float* dy, const float* w, float* dx, int N, int Cy, int W, int Cx, hipStream_t st) {
+    SmP p{dy, w, nullptr, dx, N, Cy, 2, InAff{nullptr, nullptr, 0}};
+    if (W == 32) return launch_sm<32>(p, Cx, st, true);
+    if (W == 64) return launch_sm<64>(p, Cx, st, true);
     return JVAE_ENOTSUP;
 }
 

@@ -159,6 +159,18 @@ class ClassificationVariationalNetwork(nn.Module):
                                           'baseline*', 'hyz'],
                                  'vae': [], 'jvae': [], 'xvae': [], 'vib': ['odin*', 'baseline', 'logits', 'hyz']}
 
+    # cvae.py:120-133: the ODIN grid (10 temperatures x 21 perturbation sizes) and what a starred method name expands to; an
+    # instance may override the two lists (its `odin*` rows then follow its own lists)
+    ODIN_TEMPS = [m * 10 ** i for i in (0, 1, 2) for m in (1, 2, 5)] + [1000]
+    ODIN_EPS = [k / 20 * 0.004 for k in range(21)]
+    methods_params = {'softkl': [], 'softzdist': [], 'baseline': [], 'odin': []}
+    for _T in ODIN_TEMPS:
+        for _k in ('softkl', 'softzdist', 'baseline'):
+            methods_params[_k].append('{}-{:.0f}'.format(_k, _T))
+        for _e in ODIN_EPS:
+            methods_params['odin'].append('odin-{:.0f}-{:.4f}'.format(_T, _e))
+    del _T, _k, _e
+
     def __init__(self, input_shape, num_labels, type='cvae', y_is_coded=False, output_distribution='gaussian',
                  job_number=0, features=None, pretrained_features=None, batch_norm=False, dropout=False,
                  encoder=[36], latent_dim=32, prior={}, beta=1., gamma=0., decoder=[36], upsampler=None,
@@ -806,7 +818,9 @@ class ClassificationVariationalNetwork(nn.Module):
             m = name[:-3] if name.endswith('-2s') else name
             m = m.split('-')[0] if '-a-' in m else m
             per_class = self.losses_might_be_computed_for_each_class          # cvae.py:996-1016,1036-1039
-            if m in ('elbo', 'max'):
+            if m.startswith('odin'):
+                v = losses[m]                                                 # cvae.py:1076-1078: computed by odin_scores()
+            elif m in ('elbo', 'max'):
                 v = (-losses['total']).max(0)[0] if (per_class or m == 'max') else -losses['total']
             elif m == 'iws' and not per_class:
                 v = losses['iws']
@@ -832,6 +846,99 @@ class ClassificationVariationalNetwork(nn.Module):
                 raise NotImplementedError(f'{name}: OOD method outside this build')
             out[name] = v.cpu() if to_cpu else v
         return out
+
+    # ------------------------------------------------------------------------------------ ODIN (type 'vib')
+    def _odin_slab_rows(self):
+        """Rows of the perturbed batch that go through `features` at once: no activation passes EVAL_SLAB_ELEMENTS."""
+        env = os.environ.get('JVAE_EVAL_SLAB_ROWS')                 # tests: force many small slabs
+        if env:
+            return max(int(env), 1)
+        widest = max([int(np.prod(self.input_shape))] + [int(np.prod(sh)) for sh in getattr(self.features, 'shapes', [])])
+        return max(self.EVAL_SLAB_ELEMENTS // widest, 1)
+
+    def _odin_logits(self, feats, epsilon):
+        """Encoder features (R, D) -> logits (L+1, R, C): the part of forward() ODIN reads (cvae.py:1649-1651)."""
+        _, _, z, _, _ = self.encoder(feats, None, epsilon=epsilon)
+        if self.classifier_type in ('linear', None):
+            return self.classifier(z)
+        m = self.encoder.prior.mean
+        return ops.linear(z, m, m.pow(2).sum(-1) / 2)
+
+    def odin_scores(self, x, epsilon=None, acc_out=None):
+        """The ODIN out-of-distribution scores of a batch (Liang et al.; cvae.py:1645-1663) for every temperature of
+        `ODIN_TEMPS` and perturbation size of `ODIN_EPS`: {'odin-T-eps': (N,) fp32 device tensor}, in evaluation mode.
+
+            acc = 0
+            for T:   s = max softmax(logits(x)[1:].mean(0) / T);  acc += d(sum s)/dx;  dx = sign(acc)
+                     for eps:  score = max softmax(logits(x + eps * dx)[1:].mean(0) / T)
+
+        Reproduced from the reference as written: (1) the input gradient ACCUMULATES over the temperatures (x.grad is never
+        zeroed there), the sign at temperature k is that of the sum of the gradients of temperatures 1..k; (2) every forward
+        draws its own reparameterisation noise; (3) row 0 of the draws (the mean latent) is left out of the mean and gets no
+        gradient from the score - the gradient reaches mu / log_var through rows 1..L.  The perturbed image is not clamped.
+        One deliberate difference: the reference's backward() also fills every parameter's .grad, which it never uses; here
+        the input gradient alone is computed - no weight-gradient kernel runs and every .grad stays as it was.
+
+        Underneath: per temperature the E perturbed forwards are ONE batch of E*N rows, cut into slabs for the conv stack
+        (`_odin_slab_rows`); the T gradient passes share one `features(x)` forward and differ from the encoder on; the head
+        (csrc/odin.hip) turns the logits of all T*E forwards into scores in one launch; the call is one span of constant
+        weights and brings no value to the host.  `epsilon` (T, 1+E, L+1, N, K) injects the noise: slot [t, 0] is the
+        gradient pass of temperature t, slot [t, 1+e] perturbed forward e.  `acc_out`: a list that receives a copy of the
+        accumulated input gradient after each temperature (tests, diagnostics).  fp32 only."""
+        if getattr(self, 'compute_dtype', 'fp32') != 'fp32':
+            raise NotImplementedError('ODIN scores are built for the fp32 compute mode (set_compute_dtype("fp32"))')
+        if self.classifier_type is None or self.y_is_coded:
+            raise NotImplementedError('ODIN needs a classifier on z of a model without coded labels (type vib)')
+        x = x.detach().reshape(-1, *self.input_shape)
+        dev, N = x.device, x.shape[0]
+        temps, sizes = list(self.ODIN_TEMPS), list(self.ODIN_EPS)
+        T, E, K, C = len(temps), len(sizes), self.latent_dim, self.num_labels
+        if epsilon is not None and tuple(epsilon.shape[:2]) != (T, 1 + E):
+            raise ValueError(f'epsilon: (T, 1 + E, L+1, N, K) = ({T}, {1 + E}, ...) expected, got {tuple(epsilon.shape)}')
+        was_training = self.training
+        self.eval()
+        L = self.latent_sampling
+        frozen = [p for p in self.parameters() if p.requires_grad]
+        for p in frozen:                      # input gradients only: no node of the gradient pass asks for a weight gradient
+            p.requires_grad_(False)
+        _lib.span_hold += 1
+        try:
+            with self._constant_weights(x):
+                t_dev = torch.tensor([float(t) for t in temps for _ in sizes], dtype=torch.float32, device=dev)
+                e_dev = torch.tensor([float(e) for e in sizes], dtype=torch.float32, device=dev)
+                with torch.enable_grad():
+                    xg = x.detach().requires_grad_(True)
+                    feats = self._features_of(xg).reshape(N, -1)        # shared by the T gradient passes
+                acc = torch.zeros_like(x)
+                logits_all = torch.empty((L + 1, T, E * N, C), dtype=torch.float32, device=dev)
+                slab = self._odin_slab_rows()
+                for t in range(T):
+                    with torch.enable_grad():
+                        logits = self._odin_logits(feats, None if epsilon is None else epsilon[t, 0])
+                    with torch.no_grad():
+                        _, dlogits = ops.odin_head(logits.detach().unsqueeze(0), t_dev[t * E:t * E + 1], want_grad=True)
+                    g, = torch.autograd.grad(logits, xg, grad_outputs=dlogits[0], retain_graph=t + 1 < T)
+                    with torch.no_grad():
+                        xp = ops.odin_perturb(acc, g, x, e_dev)         # (E * N, ...): acc += g, x + eps_e * sign(acc)
+                        if acc_out is not None:
+                            acc_out.append(acc.clone())
+                        if self.features:
+                            fp = torch.empty((E * N, feats.shape[1]), dtype=torch.float32, device=dev)
+                            for r0 in range(0, E * N, slab):
+                                fp[r0:r0 + slab] = self.features(xp[r0:r0 + slab]).reshape(-1, feats.shape[1])
+                        else:
+                            fp = xp.reshape(E * N, -1)
+                        noise = None if epsilon is None else epsilon[t, 1:].transpose(0, 1).reshape(L + 1, E * N, K)
+                        logits_all[:, t] = self._odin_logits(fp, noise)
+                with torch.no_grad():
+                    scores = ops.odin_head(logits_all.view(L + 1, T * E, N, C), t_dev, forwards_first=False)      # (T * E, N)
+        finally:
+            _lib.span_hold -= 1
+            for p in frozen:
+                p.requires_grad_(True)
+            if was_training:
+                self.train()
+        return dict(zip(self._odin_names(), scores))
 
     def accuracy(self, testset=None, batch_size=100, num_batch='all', method='all', print_result=False,
                  update_self_testing=True, outputs=None, sample_dirs=[], recorder=None, epoch='last', from_where='all',
@@ -915,20 +1022,38 @@ class ClassificationVariationalNetwork(nn.Module):
     OOD_KEPT_TPR = [pc / 100 for pc in range(90, 100)]                        # cvae.py:1736
     OOD_ROC_EVERY = 100                                                       # batches between two progress ROCs (cvae.py:1843)
 
+    def _odin_names(self):
+        """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
+        return ['odin-{:.0f}-{:.4f}'.format(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
+
     def _ood_methods(self, method):
         """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
-        line), a name or a list of names; the spline-threshold ('-a-x-y') and ODIN methods raise when asked for by name."""
+        line), a name or a list of names.  On a type whose table lists `odin*` (vib), 'all' and 'odin*' expand to the ODIN grid
+        (the plain names first, the expansion behind them, as the reference's develop_starred_methods orders them) and single
+        `odin-T-eps` names are accepted; on every other type an ODIN name raises, and so do the spline-threshold ('-a-x-y')
+        methods everywhere."""
+        has_odin = 'odin*' in self.ood_methods
+
         def unbuilt(m):
-            return '-a-' in m or m.startswith('odin')
+            return '-a-' in m or (m.startswith('odin') and not has_odin)
+
+        def expand(names):
+            plain = [m for m in names if m != 'odin*']
+            return plain + (self._odin_names() if len(plain) < len(names) else [])
         if method == 'all':
             skipped = [m for m in self.ood_methods if unbuilt(m)]
             if skipped:
                 logging.warning('ood_detection_rates: methods outside this build are left out: %s', ', '.join(skipped))
-            return [m for m in self.ood_methods if not unbuilt(m)]
+            return expand([m for m in self.ood_methods if not unbuilt(m)])
         methods = [method] if isinstance(method, str) else list(method)
         for m in methods:
             if unbuilt(m):
                 raise NotImplementedError(f'{m}: spline-threshold (-a-x-y) and ODIN OOD methods are outside this build')
+        methods = expand(methods)
+        grid = set(self._odin_names())
+        for m in methods:
+            if m.startswith('odin') and m not in grid:
+                raise ValueError(f'{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)')
         return methods
 
     def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False):
@@ -949,20 +1074,26 @@ class ClassificationVariationalNetwork(nn.Module):
         loader = None if recorded else iter(torch.utils.data.DataLoader(dset, batch_size=batch_size, num_workers=0, shuffle=shuffle))
         buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
         filled, sums, measures = 0, {}, None
+        odin = any(m.startswith('odin') for m in methods)
         with torch.no_grad():
             for i in range(num_batch):
                 if recorded:
-                    keys = [k for k in recorder.keys() if k in self.loss_components]
+                    keys = [k for k in recorder.keys() if k in self.loss_components or k.startswith('odin')]     # cvae.py:1665-1667
                     losses = recorder.get_batch(i, *keys, force_dict=True)
                     logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
                 else:
                     x, y = next(loader)[:2]
                     x, y = self._device_batch(x.to(device)), y.to(device)
                     _, logits, losses, measures = self.evaluate(x, batch=i, current_measures=measures)
+                    if odin:
+                        # cvae.py:1645-1663: the whole grid per batch (it is what the recorder holds), on the device
+                        losses = dict(losses, **self.odin_scores(x))
                     if recording:
                         extra = {} if logits is None else {'logits': logits.T}
                         recorder.append_batch(**losses, y_true=y, **extra)
                 scores = self.batch_dist_measures(logits, losses, methods)
+                if odin:
+                    losses = {k: v for k, v in losses.items() if not k.startswith('odin')}     # test_losses: the loss components
                 n = scores[methods[0]].shape[0]
                 for r, m in enumerate(methods):
                     buf[r, filled:filled + n] = scores[m]

@@ -72,6 +72,7 @@ _SIGS = {
     'jvae_bn_bwd_sums_f32': (c_int, [P] * 7 + [c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'jvae_bn_bwd_sync_f32': (c_int, [P] * 8 + [c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     'jvae_bn_bwd_f32': (c_int, [P] * 9 + [c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    'jvae_bn_eval_bwd_f32': (c_int, [P] * 7 + [c_int, c_int, c_int, c_float, c_int, P]),
     'jvae_act_fwd_f32': (c_int, [P, P, c_long, c_int, P]),
     'jvae_act_bwd_f32': (c_int, [P, P, P, c_long, c_int, P]),
     'jvae_dict_stats_f32': (c_int, [P, P, c_int, c_int, P]),
@@ -107,6 +108,8 @@ _SIGS = {
     'jvae_upsample_nearest_bwd_b8': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
     'jvae_roc_workspace_bytes': (c_size_t, [c_int, c_long, c_long]),
     'jvae_roc_curve_f32': (c_int, [P] * 10 + [c_int, c_long, c_long, c_int, P, c_size_t, P]),
+    'jvae_odin_head_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, P]),
+    'jvae_odin_perturb_f32': (c_int, [P, P, P, P, P, c_long, c_int, P]),
 }
 
 
@@ -202,6 +205,7 @@ def workspace(nbytes, device):
 PACK_CACHE_BYTES = int(os.environ.get('JVAE_PACK_CACHE_MB', '64')) << 20       # JVAE_PACK_CACHE_MB=0: off (A/B switch)
 _pack_cache = {}
 span_depth = 0        # > 0 while a model-level forward()/evaluate() is running (cvae._constant_weights): see ops._Conv.forward
+span_hold = 0         # > 0 while a span contains backward passes that must not end it (cvae.odin_scores: input gradients only)
 
 
 def pack_cache_begin(weights, device):

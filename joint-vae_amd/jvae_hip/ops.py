@@ -53,7 +53,8 @@ def _close_span_after_backward():
     """The span of constant weights that a train-mode evaluate() / forward() opened (packed weights served from the step's
     cache, lib.pack_cache_begin) ends with the backward pass that needed it: the engine's end-of-backward callback disarms
     the cache, whether or not an optimiser step follows.  Queued by every convolution backward (a host-side flag flip each)."""
-    torch.autograd.Variable._execution_engine.queue_callback(L.pack_cache_end)
+    if not L.span_hold:            # odin_scores: its input-gradient passes sit inside one span, which the call itself closes
+        torch.autograd.Variable._execution_engine.queue_callback(L.pack_cache_end)
 
 
 # ------------------------------------------------------------------------------------------- gemm
@@ -485,14 +486,29 @@ def _ext_args(ext, training):
     return L.ptr(ext['stats']), int(ext['nsplit']), L.ptr(ext.get('pivot'))
 
 
-def _bn_save(ctx, lay, training, relu, dims, x, gamma, beta, mean, invstd):
+def _bn_save(ctx, lay, training, relu, dims, x, gamma, beta, mean, invstd, rm, rv, eps):
     ctx.lay = lay
+    ctx.relu, ctx.dims = relu, dims
+    ctx.eval_eps = None if training else float(eps)
     if training:
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
-        ctx.relu, ctx.dims = relu, dims
         ctx.g_ref, ctx.b_ref = gamma, beta
-    else:
-        ctx.dims = None
+    else:                      # running statistics are constants: backward is one elementwise pass (jvae_bn_eval_bwd_f32)
+        ctx.save_for_backward(x, gamma, beta, rm, rv)
+
+
+def _bn_eval_backward(ctx, gy):
+    """Input gradient of an eval-mode BatchNorm (+activation), materialised or deferred: gy * gamma * rsqrt(running_var + eps)
+    * act'(y).  No parameter gradients (the ODIN gradient pass wants d/dx only)."""
+    if ctx.lay is not F32:
+        raise NotImplementedError('backward through an eval-mode BatchNorm is built for the fp32 layout only')
+    x, gamma, beta, rm, rv = ctx.saved_tensors
+    N, C, P = ctx.dims
+    gy = _c(gy)
+    gx = torch.empty_like(x)
+    L.check(L.load().jvae_bn_eval_bwd_f32(L.ptr(gy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(gx),
+                                          N, C, P, ctx.eval_eps, int(ctx.relu), L.stream_ptr()), 'jvae_bn_eval_bwd_f32')
+    return gx, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _bn_param_grads(ctx, C, device):
@@ -518,13 +534,13 @@ class _BatchNormAct(torch.autograd.Function):
         lay.bn_fwd(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(y), L.ptr(mean), L.ptr(invstd),
                    N, C, P, momentum, eps, int(training), int(relu), ext=_ext_args(ext, training),
                    ws=lay.bn_workspace(C, x.device))
-        _bn_save(ctx, lay, training, relu, (N, C, P), x, gamma, beta, mean, invstd)
+        _bn_save(ctx, lay, training, relu, (N, C, P), x, gamma, beta, mean, invstd, rm, rv, eps)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        if ctx.dims is None:
-            raise L.JvaeHipError('backward through eval-mode BatchNorm is not part of the training step')
+        if ctx.eval_eps is not None:
+            return _bn_eval_backward(ctx, gy)
         x, gamma, beta, mean, invstd = ctx.saved_tensors
         N, C, P = ctx.dims
         gy = _c(gy)
@@ -562,7 +578,7 @@ class _BatchNormDefer(torch.autograd.Function):
         lay.bn('jvae_bn_finalize', L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.ptr(nbt), L.ptr(mean),
                L.ptr(invstd), *lay.coef_args(coef), N, C, P, momentum, eps, int(training), *_ext_args(ext, training),
                ws=lay.bn_workspace(C, x.device))
-        _bn_save(ctx, lay, training, relu, (N, C, P), x, gamma, beta, mean, invstd)
+        _bn_save(ctx, lay, training, relu, (N, C, P), x, gamma, beta, mean, invstd, rm, rv, eps)
         ctx.mark_non_differentiable(coef)
         ctx.set_materialize_grads(False)        # no zero-fill launch for the (never used) gradient of `coef`
         return x.view_as(x), coef
@@ -1114,6 +1130,44 @@ def roc_check_status(status):
             raise ValueError(f'roc_curve: NaN score in row {m}')
         if int(s) & 2:
             raise ValueError(f'roc_curve: non-finite in-distribution score in around-mean row {m}')
+
+
+# ------------------------------------------------------------------------------------------- ODIN (csrc/odin.hip)
+def odin_head(logits, temps, want_grad=False, forwards_first=True):
+    """Scores of F batched forwards: max softmax(mean over the draws l >= 1 of logits / T_f) -> (F, N) [, d(sum scores)/d(logits)].
+    logits (F, L+1, N, C) - or (L+1, F, N, C) with forwards_first=False; temps: (F,) fp32 device tensor."""
+    logits = _c(_f32(logits, 'odin_head'))
+    if logits.dim() != 4:
+        raise L.JvaeHipError(f'odin_head: 4-d logits expected, got {tuple(logits.shape)}')
+    if forwards_first:
+        F, L1, N, C = logits.shape
+        sf, sl = L1 * N * C, N * C
+    else:
+        L1, F, N, C = logits.shape
+        sf, sl = N * C, F * N * C
+    temps = _c(_f32(temps, 'odin_head'))
+    if temps.numel() != F or L1 < 2:
+        raise L.JvaeHipError(f'odin_head: {temps.numel()} temperatures for {F} forwards of {L1 - 1} draws')
+    scores = torch.empty((F, N), device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits) if want_grad else None
+    L.check(L.load().jvae_odin_head_f32(L.ptr(logits), L.ptr(temps), L.ptr(scores), L.ptr(dlogits), F, L1 - 1, N, C, sf, sl,
+                                        L.stream_ptr()), 'jvae_odin_head_f32')
+    return (scores, dlogits) if want_grad else scores
+
+
+def odin_perturb(acc, g, x, eps):
+    """acc += g (in place; g None: acc as it is), then -> (E * N, ...) = x + eps_e * sign(acc) for the E sizes of `eps`
+    ((E,) fp32 device tensor), sign(0) = 0: the operand of the batched perturbed forward."""
+    x = _c(_f32(x, 'odin_perturb'))
+    eps = _c(_f32(eps, 'odin_perturb'))
+    if not acc.is_contiguous() or acc.dtype != torch.float32 or acc.shape != x.shape or (g is not None and g.shape != x.shape):
+        raise L.JvaeHipError('odin_perturb: acc (and g) must be dense fp32 tensors shaped like x')
+    g = None if g is None else _c(_f32(g, 'odin_perturb'))
+    E = eps.numel()
+    out = torch.empty((E * x.shape[0], *x.shape[1:]), device=x.device, dtype=torch.float32)
+    L.check(L.load().jvae_odin_perturb_f32(L.ptr(acc), L.ptr(g), L.ptr(x), L.ptr(eps), L.ptr(out), x.numel(), E,
+                                           L.stream_ptr()), 'jvae_odin_perturb_f32')
+    return out
 
 
 # ------------------------------------------------------------------------------------------- input pipeline

@@ -433,6 +433,26 @@ int jvae_roc_curve_f32(const float* ins, const float* outs, const double* kept_t
                        double* auc, double* kept_fpr, double* kept_tpr_out, double* thr_low, double* thr_up, int* status,
                        int M, long n_in, long n_out, int K, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Misclassification detection: score rows, split by correctness, confusion counts (csrc/misclass.hip) ----------
+ * What surrounds jvae_roc_curve_f32 in misclassification_detection_rates (reference cvae.py:1913-2079).
+ * Scores: src (C, N) fp32 (all-class kl / zdist / iws losses, or the logits as the recorder stores them), C <= 128, read once;
+ * row r of the R requested rows goes to out + rows[r] * out_stride (out_stride >= N), with kinds[r] / temps[r] (device arrays):
+ *   0  max_c softmax_c(-v / T)   1  max_c softmax_c(v / T)   2  max_c (-v)   3  max_c v   4  sum_c p log p, p = softmax_c(v / T)
+ * (batch_dist_measures, cvae.py:1024-1063), fp32 with the max-subtracted softmax; a NaN propagates as in torch.
+ * Split: scores (M, N), mask (N bytes, non-zero = correctly classified) -> out (M * N floats): ins (M, n_correct) followed by
+ * outs (M, N - n_correct), each row in its original order; *n_correct (device int32) receives the count.  One scan of the mask
+ * serves all rows.  ws: 4-byte aligned, jvae_misclass_split_workspace_bytes(N) bytes (0 = invalid N).
+ * Confusion: thr (M, K) fp64 (thr_low of the ROC), K <= 16 -> tp / fp (M, K) int32: the correct / missed samples whose exactly
+ * widened score is >= thr[m][k] (cvae.py:2009-2015).  Integer counts: independent of any order.
+ * N in [1, 2^24], M <= 65535 (the limits of jvae_roc_curve_f32); beyond a bound: -1 (JVAE_EINVAL). */
+int jvae_misclass_scores_f32(const float* src, const int* kinds, const float* temps, const int* rows, float* out,
+                             int R, int C, long N, long out_stride, void* stream);
+size_t jvae_misclass_split_workspace_bytes(long N);
+int jvae_misclass_split_f32(const float* scores, const unsigned char* mask, float* out, int* n_correct, int M, long N,
+                            void* ws, size_t ws_bytes, void* stream);
+int jvae_misclass_confusion_f32(const float* scores, const unsigned char* mask, const double* thr, int* tp, int* fp,
+                                int M, long N, int K, void* stream);
+
 /* ODIN out-of-distribution scores (csrc/odin.hip; reference cvae.py:1645-1663): the two ends of the loop.
  * Head: logits of F batched forwards, element (f, l, n, c) at f * stride_f + l * stride_l + n * C + c with l = 0 .. L (row 0, the mean
  * latent, is left out of the mean), temps (F) -> scores (F, N) = max_c softmax_c(mean_{l >= 1} logits / temps[f]); dlogits (same

@@ -12,8 +12,9 @@ clip -> Adam — executed by hand-written gfx950 HIP kernels (libjvae_hip.so) be
 
 What is NOT rebuilt here (raises NotImplementedError when asked for): (cvae / xvae / vae / vib are complete, jvae: training and labelled evaluation only); resnet
 feature stacks (torchvision); a per-dimension sigma (the reference fails on it too); label-free evaluation of a categorical
-(256-level) decoder - its training / labelled evaluation is built; the misclassification phases of train_model.  Pooling / up-sampling layer tokens, SGD,
-the `y=None` all-class evaluation with its OOD scores and the WIM fine-tuning step are built.
+(256-level) decoder - its training / labelled evaluation is built.  Pooling / up-sampling layer tokens, SGD,
+the `y=None` all-class evaluation with its OOD scores, the WIM fine-tuning step and the evaluation methods accuracy(),
+ood_detection_rates() and misclassification_detection_rates() are built.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -827,12 +828,18 @@ class ClassificationVariationalNetwork(nn.Module):
             elif m == 'iws':
                 top = losses['iws'].max(0)[0]
                 v = (losses['iws'] - top).exp().sum(0).log() + top + math.log(C)
+            elif m == 'softiws':
+                v = losses['iws'].softmax(0).max(0)[0]                        # cvae.py:1024-1028: +iws here, -iws / T below
+            elif m.startswith('softiws-'):
+                v = (-losses['iws'] / float(m[8:])).softmax(0).max(0)[0]
             elif m in ('soft', 'softkl'):
                 v = (-losses['kl']).softmax(0).max(0)[0]
             elif m.startswith('softkl-'):
                 v = (-losses['kl'] / float(m[7:])).softmax(0).max(0)[0]
             elif m in ('zdist', 'kl'):
                 v = (-losses[m]).max(0)[0] if not self.is_vae else -losses[m]
+            elif m.startswith('soft') and '-' in m:                           # cvae.py:1040-1043: soft<loss>-T
+                v = (-losses[m.split('-')[0][4:]] / float(m.split('-')[-1])).softmax(0).max(0)[0]
             elif m == 'mse':
                 v = -losses['cross_x']
             elif m == 'wmse':
@@ -842,6 +849,9 @@ class ClassificationVariationalNetwork(nn.Module):
             elif m.startswith('baseline'):
                 T = float(m.split('-')[-1]) if '-' in m else 1.
                 v = (logits / T).softmax(-1).max(-1)[0]
+            elif m == 'hyz':                                                  # cvae.py:1061-1063: minus the entropy of p(y|z)
+                p_y_z = logits.softmax(-1)
+                v = (p_y_z * p_y_z.log()).sum(-1)
             else:
                 raise NotImplementedError(f'{name}: OOD method outside this build')
             out[name] = v.cpu() if to_cpu else v
@@ -1224,6 +1234,180 @@ class ClassificationVariationalNetwork(nn.Module):
         if was_training:
             self.train()
         return ood_results
+
+    # ------------------------------------------------------------------------------------ misclassification detection
+    def _starred(self, names):
+        """develop_starred_methods (utils/save_load/dictify.py:198-212) on a copy: the plain names in their order, then what
+        each starred name expands to; a starred name without an entry in `methods_params` (softiws*) expands to nothing."""
+        grids = dict(self.methods_params, odin=self._odin_names())
+        plain = [m for m in names if not m.endswith('*')]
+        return plain + [e for m in names if m.endswith('*') for e in grids.get(m[:-1], [])]
+
+    @staticmethod
+    def _misclass_row(m):
+        """-> (recorder key the method reads, (kind, T) of csrc/misclass.hip or None = `batch_dist_measures` computes the row)."""
+        T = float(m.split('-')[-1]) if '-' in m and not m.startswith('odin') else 1.
+        if m == 'iws' or m.startswith('odin'):
+            return m, None
+        if m == 'softiws':
+            return 'iws', ('soft+', 1.)
+        if m in ('soft', 'softkl'):
+            return 'kl', ('soft-', 1.)
+        if m.startswith('soft') and '-' in m:
+            return m.split('-')[0][4:], ('soft-', T)
+        if m in ('kl', 'zdist'):
+            return m, ('max-', 1.)
+        if m == 'max':
+            return 'total', ('max-', 1.)
+        if m == 'logits':
+            return 'logits', ('max+', 1.)
+        if m.startswith('baseline'):
+            return 'logits', ('soft+', T)
+        if m == 'hyz':
+            return 'logits', ('hyz', 1.)
+        raise ValueError(f'{m}: unknown misclassification method')
+
+    def misclassification_detection_rates(self, predict_methods='all', misclass_methods='all', epoch='last', shown_tpr=0.95,
+                                          from_where=('json', 'recorders'), print_result=False, update_self_results=True,
+                                          outputs=None, recorder=None):
+        """How well each misclassification score separates the correctly from the wrongly classified samples of the recorded test
+        set, per prediction method (cvae.py:1913-2079): the ROC of score[correct] against score[missed] - AUC, FPR at the kept
+        TPRs 0.90 .. 0.99 - and the precision tp / (tp + fp) at each kept threshold.  Stored, as the reference stores it, in
+        `self.testing[epoch][predict_method][m] = {'n', 'epochs', 'sampling', 'tpr', 'fpr', 'auc', 'precision'}` (plain floats and
+        lists, `save()` writes them to test.json) and, unlike the reference (which returns None), returned as
+        {predict_method: {m: entry}}.
+
+        The scores come from a `LossRecorder` (the all-class losses, `logits` as (C, N), `y_true`): the one passed as `recorder`,
+        or `saved_dir/samples/<epoch:04d>/record-<training_parameters['set']>.pth` (`epoch='last'`: the largest epoch directory
+        holding that file).  Nothing to do (None, said at debug level) without that file, without 'recorders' in `from_where`, or
+        for a model type without misclassification methods.  The registry lookup of earlier results (`available_results`) is host
+        plumbing outside this build, as for accuracy().  Starred names expand through `methods_params` (`odin*`: this model's
+        grid); `softiws*` has no entry there and expands to nothing, as in the reference.  A name outside the model's table is an
+        error; a method whose loss the recorder does not hold is skipped.
+
+        Underneath, per prediction method: the score rows are computed on the device into ONE (M, N) buffer (csrc/misclass.hip,
+        one launch per source tensor; `batch_dist_measures` for `iws` and the recorded `odin-*` rows), then ONE split by
+        correctness, ONE ROC of all M rows (csrc/roc.hip), ONE confusion count, and ONE copy of the (M, 6K + 2) results to the
+        host; n_correct is the only other value read back.  No (M, N) or (C, N) tensor goes to the host.
+
+        Decided where the reference fails: a prediction method that gets every sample right - or none - is skipped with a
+        warning (the reference dies in roc_curve); a row with a NaN score (`hyz` on a saturated softmax) is skipped with a warning
+        naming it.  The reference's "n already there" guard reads `self.testing[epoch][predict_methods][m]` - the ARGUMENT, a
+        list or 'all', so it never finds anything (cvae.py:2064); here it looks under the prediction method being processed.
+        The P / R / FPR at `shown_tpr` are logged at debug level (and sent to `outputs` with `print_result`); NaN when no kept slot
+        reaches `shown_tpr`.  Nothing stored depends on them."""
+        def nothing(why):
+            logging.debug('misclassification_detection_rates: nothing to do (%s)', why)
+
+        if not self.misclass_methods:
+            return nothing(f'no misclassification methods for type {self.type}')
+        if not (from_where == 'all' or 'recorders' in from_where):
+            return nothing("'recorders' is not in from_where")
+        if recorder is None:
+            from jvae_compat.recorders import LossRecorder
+            fname = 'record-{}.pth'.format(self.training_parameters['set'])
+            root = os.path.join(getattr(self, 'saved_dir', None) or '', 'samples')
+            if epoch == 'last':
+                found = [int(d) for d in (os.listdir(root) if os.path.isdir(root) else [])
+                         if d.isdigit() and os.path.exists(os.path.join(root, d, fname))]
+                if not found:
+                    return nothing(f'no {fname} under {root}')
+                epoch = max(found)
+            path = os.path.join(root, '{:04d}'.format(int(epoch)), fname)
+            if not os.path.exists(path):
+                return nothing(f'no {path}')
+            recorder = LossRecorder.load(path, map_location=self.device)
+        elif epoch == 'last':
+            epoch = self.trained
+        epoch = int(epoch)
+
+        chosen = {}
+        for which, arg, table in (('predict', predict_methods, self.predict_methods), ('miss', misclass_methods, self.misclass_methods)):
+            everything = self._starred(table)
+            names = [arg] if isinstance(arg, str) else list(arg or [])
+            names = everything if names and names[0] in ('all', 'default') else self._starred(names)
+            for m in names:
+                if m not in everything:
+                    raise ValueError(f'{m}: not a {which} method of a {self.type} ({", ".join(table)})')
+            chosen[which] = names
+
+        tensors = {k: recorder[k].to(self.device) for k in recorder.keys()}
+        _lib.ptr(tensors['y_true'])                                          # there is no CPU path
+        logits_cn, y = tensors.pop('logits', None), tensors.pop('y_true')
+        logits = None if logits_cn is None else logits_cn.T
+        sources = dict(tensors, logits=logits_cn)
+        n, K = y.shape[0], len(self.OOD_KEPT_TPR)
+        rows_of = {m: self._misclass_row(m) for m in chosen['miss']}
+        methods = [m for m in chosen['miss'] if sources.get(rows_of[m][0]) is not None]
+        skipped = [m for m in chosen['miss'] if m not in methods]
+        if skipped:
+            logging.debug('misclassification_detection_rates: not in the recorder: %s', ', '.join(skipped))
+        sampling = self._latent_samplings['eval']
+        results = {}
+        if not methods:
+            return results
+
+        def fused(m):
+            src = sources[rows_of[m][0]]
+            return rows_of[m][1] is not None and src.dim() == 2 and src.shape[0] <= ops.MISCLASS_MAX_CLASSES and src.dtype == torch.float32
+
+        # the score rows do not depend on the prediction method: ONE (M, N) buffer, one launch per source tensor
+        scores = torch.empty((len(methods), n), dtype=torch.float32, device=y.device)
+        with torch.no_grad():
+            by_source = {}
+            for r, m in enumerate(methods):
+                if fused(m):
+                    by_source.setdefault(rows_of[m][0], []).append(r)
+            for key, rows in by_source.items():
+                ops.misclass_scores(sources[key], [rows_of[methods[r]][1] for r in rows], out=scores, rows=rows)
+            rest = [m for m in methods if not fused(m)]
+            for m, v in self.batch_dist_measures(logits, tensors, rest).items():
+                scores[methods.index(m)] = v
+            kept = torch.tensor(self.OOD_KEPT_TPR, dtype=torch.float64, device=y.device)
+            sink = outputs if print_result and outputs is not None and hasattr(outputs, 'write') else None
+            for pm in chosen['predict']:
+                correct = self.predict_after_evaluate(logits, tensors, method=pm) == y
+                try:
+                    r = ops.misclass_rates(scores, correct, kept)
+                except ValueError as err:
+                    logging.warning('misclassification_detection_rates: prediction method %s skipped: %s', pm, err)
+                    continue
+                n_correct = r['n_correct']
+                acc = n_correct / n
+                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['tp'].double(), r['fp'].double(),
+                                  r['status'].double()[:, None]], 1).cpu().numpy()
+                logging.debug('Acc. for method %s: (%5.2f) ****', pm, 100 * acc)
+                results[pm] = {}
+                best = (None, 0.)
+                for m, h in zip(methods, host):
+                    if int(h[-1]):
+                        logging.warning('misclassification_detection_rates: %s-%s skipped: NaN score', pm, m)
+                        continue
+                    fpr, tpr = h[1:1 + K], h[1 + K:1 + 2 * K]
+                    tp, fp = h[1 + 4 * K:1 + 5 * K], h[1 + 5 * K:1 + 6 * K]
+                    with np.errstate(invalid='ignore', divide='ignore'):
+                        precision = tp / (tp + fp)                          # 0 / 0 = NaN, as numpy gives the reference
+                    at = np.where(tpr >= shown_tpr)[0]                      # fpr_at_tpr (utils/roc_curves.py:8-27)
+                    p95, r95, f95 = ((precision[at.min()], tp[at.min()] / n_correct, fp[at.min()] / (n - n_correct))
+                                     if len(at) else (np.nan, np.nan, np.nan))
+                    if p95 > best[1]:
+                        best = (m, p95)
+                    line = '{:16}: \tP={:5.2f} ({:+4.1f}) R={:5.2f} FPR={:5.2f}'.format(m, 100 * p95, 100 * (p95 - acc), 100 * r95,
+                                                                                       100 * f95)
+                    logging.debug(line)
+                    if sink is not None:
+                        sink.write(line + '\n')
+                    entry = {'n': n, 'epochs': epoch, 'sampling': sampling, 'tpr': [float(t) for t in tpr],
+                             'fpr': [float(f) for f in fpr], 'auc': float(h[0]), 'precision': [float(p) for p in precision]}
+                    results[pm][m] = entry
+                    n_already = self.testing.get(epoch, {}).get(pm, {}).get(m, {'n': 0})['n']
+                    if update_self_results and n >= n_already:
+                        slot = self.testing.setdefault(epoch, {})
+                        if pm not in slot:
+                            slot[pm] = {'n': n, 'epochs': epoch, 'sampling': sampling, 'accuracy': float(acc)}
+                        slot[pm][m] = entry
+                logging.debug('best method for %s: %s (P=%.2f)', pm, best[0], 100 * best[1])
+        return results
 
     def _early_reduce_hook(self, grad):
         self.optimizer.reduce_early_bucket()

@@ -108,6 +108,10 @@ _SIGS = {
     'jvae_upsample_nearest_bwd_b8': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
     'jvae_roc_workspace_bytes': (c_size_t, [c_int, c_long, c_long]),
     'jvae_roc_curve_f32': (c_int, [P] * 10 + [c_int, c_long, c_long, c_int, P, c_size_t, P]),
+    'jvae_misclass_scores_f32': (c_int, [P] * 5 + [c_int, c_int, c_long, c_long, P]),
+    'jvae_misclass_split_workspace_bytes': (c_size_t, [c_long]),
+    'jvae_misclass_split_f32': (c_int, [P, P, P, P, c_int, c_long, P, c_size_t, P]),
+    'jvae_misclass_confusion_f32': (c_int, [P] * 5 + [c_int, c_long, c_int, P]),
     'jvae_odin_head_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, P]),
     'jvae_odin_perturb_f32': (c_int, [P, P, P, P, P, c_long, c_int, P]),
 }

@@ -1132,6 +1132,105 @@ def roc_check_status(status):
             raise ValueError(f'roc_curve: non-finite in-distribution score in around-mean row {m}')
 
 
+# ------------------------------------------------------------------------------------------- misclassification (csrc/misclass.hip)
+MISCLASS_KINDS = {'soft-': 0, 'soft+': 1, 'max-': 2, 'max+': 3, 'hyz': 4}
+MISCLASS_MAX_CLASSES = 128
+MISCLASS_MAX_KEPT = 16
+
+
+def _mask_u8(mask, N, what):
+    if mask.dim() != 1 or mask.numel() != N:
+        raise L.JvaeHipError(f'{what}: a mask of {N} samples expected, got {tuple(mask.shape)}')
+    return _c(mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8))
+
+
+def misclass_scores(src, specs, out=None, rows=None):
+    """Score rows of one (C, N) fp32 source (all-class losses, or the logits as the recorder stores them) in ONE launch.
+    specs: [(kind, T)] with kind in MISCLASS_KINDS - 'soft-': max_c softmax_c(-v / T), 'soft+': max_c softmax_c(v / T),
+    'max-': max_c(-v), 'max+': max_c v, 'hyz': sum_c p log p with p = softmax_c(v / T) (batch_dist_measures, cvae.py:1024-1063).
+    out (M, N) fp32 with `rows` = the row of each spec: written in place; without: a new (len(specs), N) tensor.  C <= 128."""
+    src = _c(_f32(src, 'misclass_scores'))
+    L.ptr(src)
+    if src.dim() != 2 or not 1 <= src.shape[0] <= MISCLASS_MAX_CLASSES:
+        raise L.JvaeHipError(f'misclass_scores: a (C, N) source with C <= {MISCLASS_MAX_CLASSES} expected, got {tuple(src.shape)}')
+    C, N = src.shape
+    R, dev = len(specs), src.device
+    if out is None:
+        out, rows = torch.empty((R, N), dtype=torch.float32, device=dev), list(range(R))
+    rows = [int(r) for r in rows]
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != N or not out.is_contiguous() or len(rows) != R \
+            or any(not 0 <= r < out.shape[0] for r in rows):
+        raise L.JvaeHipError(f'misclass_scores: a dense (M, {N}) fp32 buffer and {R} rows inside it expected')
+    for kind, T in specs:
+        if kind not in MISCLASS_KINDS or not float(T) > 0:
+            raise L.JvaeHipError(f'misclass_scores: unknown row ({kind!r}, {T!r})')
+    if R and N:
+        kinds = torch.tensor([MISCLASS_KINDS[k] for k, _ in specs], dtype=torch.int32, device=dev)
+        temps = torch.tensor([float(T) for _, T in specs], dtype=torch.float32, device=dev)
+        rows_d = torch.tensor(rows, dtype=torch.int32, device=dev)
+        L.check(L.load().jvae_misclass_scores_f32(L.ptr(src), L.ptr(kinds), L.ptr(temps), L.ptr(rows_d), L.ptr(out), R, C, N, N,
+                                                  L.stream_ptr()), 'jvae_misclass_scores_f32')
+    return out
+
+
+def misclass_split(scores, mask):
+    """(M, N) fp32 score rows and an (N,) mask (non-zero / True = correctly classified) -> ins (M, n_correct), outs
+    (M, N - n_correct), n_correct: both row sets compacted in their original order by ONE scan of the mask (two views of one
+    M * N buffer).  n_correct (a Python int) is the single value read from the device."""
+    lib = L.load()
+    scores = _c(_f32(scores, 'misclass_split'))
+    L.ptr(scores), L.ptr(_c(mask))
+    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise L.JvaeHipError(f'misclass_split: (M, N) score rows expected, got {tuple(scores.shape)}')
+    M, N = scores.shape
+    mask = _mask_u8(mask, N, 'misclass_split')
+    nbytes = lib.jvae_misclass_split_workspace_bytes(N)
+    if not nbytes or M > 65535:
+        raise L.JvaeHipError(f'misclass_split: sizes out of range (M={M}, N={N})')
+    ws = L.workspace(nbytes, scores.device)
+    out = torch.empty(M * N, dtype=torch.float32, device=scores.device)
+    count = torch.empty(1, dtype=torch.int32, device=scores.device)
+    L.check(lib.jvae_misclass_split_f32(L.ptr(scores), L.ptr(mask), L.ptr(out), L.ptr(count), M, N, L.ptr(ws), ws.numel(),
+                                        L.stream_ptr()), 'jvae_misclass_split_f32')
+    nc = int(count.item())
+    return out[:M * nc].view(M, nc), out[M * nc:].view(M, N - nc), nc
+
+
+def misclass_confusion(scores, mask, thr):
+    """tp / fp (M, K) int32 on the device: the correctly / wrongly classified samples whose score is >= thr[m, k] (cvae.py:2009-2015);
+    thr: (M, K) fp64 (the 'low' thresholds of `roc_curve`), K <= 16.  Compared on exactly widened fp32 scores."""
+    scores = _c(_f32(scores, 'misclass_confusion'))
+    L.ptr(scores), L.ptr(_c(mask)), L.ptr(_c(thr))
+    if scores.dim() != 2 or thr.dim() != 2 or thr.shape[0] != scores.shape[0] or thr.dtype != torch.float64 \
+            or not 1 <= thr.shape[1] <= MISCLASS_MAX_KEPT:
+        raise L.JvaeHipError(f'misclass_confusion: (M, N) fp32 scores and (M, K <= {MISCLASS_MAX_KEPT}) fp64 thresholds expected, '
+                             f'got {tuple(scores.shape)} and {tuple(thr.shape)} {thr.dtype}')
+    M, N = scores.shape
+    K = thr.shape[1]
+    mask, thr = _mask_u8(mask, N, 'misclass_confusion'), _c(thr)
+    counts = torch.empty((2, M, K), dtype=torch.int32, device=scores.device)
+    L.check(L.load().jvae_misclass_confusion_f32(L.ptr(scores), L.ptr(mask), L.ptr(thr), L.ptr(counts[0]), L.ptr(counts[1]),
+                                                 M, N, K, L.stream_ptr()), 'jvae_misclass_confusion_f32')
+    return counts[0], counts[1]
+
+
+def misclass_rates(scores, correct_mask, kept_tpr):
+    """The device side of misclassification_detection_rates for M score rows of one prediction method: ONE split, ONE ROC
+    (correct = in, missed = out, one-sided) and ONE confusion call.  -> dict of DEVICE tensors 'auc' (M,), 'fpr' / 'tpr' / 'low' /
+    'up' (M, K) fp64, 'tp' / 'fp' (M, K) int32, 'status' (M,) int32 as `roc_curve` returns it, and 'n_correct' (Python int).
+    ValueError when every sample - or none - is correct: there is no ROC of an empty set."""
+    single = scores.dim() == 1
+    scores = scores[None] if single else scores
+    ins, outs, nc = misclass_split(scores, correct_mask)
+    if nc == 0 or nc == scores.shape[1]:
+        raise ValueError(f'misclass_rates: {nc} of {scores.shape[1]} samples are correct, no ROC of an empty set')
+    res = roc_curve(ins, outs, kept_tpr, False)
+    res['tp'], res['fp'] = misclass_confusion(scores, correct_mask, res['low'])
+    res = {k: v[0] for k, v in res.items()} if single else res
+    res['n_correct'] = nc
+    return res
+
+
 # ------------------------------------------------------------------------------------------- ODIN (csrc/odin.hip)
 def odin_head(logits, temps, want_grad=False, forwards_first=True):
     """Scores of F batched forwards: max softmax(mean over the draws l >= 1 of logits / T_f) -> (F, N) [, d(sum scores)/d(logits)].

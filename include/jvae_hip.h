@@ -421,12 +421,24 @@ int jvae_augment_u8_f32(const unsigned char* in, const unsigned char* flip, cons
  * Replaces utils/roc_curves.py:38-210 (roc_curve, a Python loop over every in-distribution score) as
  * ood_detection_rates calls it per method and OOD set (cvae.py:1843-1868), for M score rows in one call.
  * ins (M, n_in), outs (M, n_out): fp32 scores, higher = more in-distribution.  kept_tpr: K doubles, ascending.
- * two_sided: M int32 on the device, 0 = one-sided test (roc_curves.py:85-88), 1 = 'around-mean' (roc_curves.py:68-72);
- * the spline modes (a tuple, roc_curves.py:74-83) are not built.
+ * two_sided: M int32 mode words on the device, one per row, mixed freely in one call:
+ *   0                               one-sided test (roc_curves.py:85-88)
+ *   1                               'around-mean' (roc_curves.py:68-72)
+ *   2 | f_low << 8 | f_up << 16     strided quantiles, the tuple mode two_sided=(f_low, f_up) of roc_curves.py:74-83, both
+ *                                   factors in [1, 255], bits 24-31 zero: with s the ascending in-scores widened to fp64,
+ *                                   low = [-inf, s[0], s[f_low], s[2 f_low], ..., +inf], up = [-inf, s[0], s[f_up], ..., +inf],
+ *                                   nt = min(len(low), len(up)), iteration `it` uses low[it] and up[len(up) - 1 - it] while
+ *                                   low[it] < up[-1 - it] and it < nt - 1; counts, cursor, kept values and AUC as in the
+ *                                   other modes.  In-scores of +-inf are legal, as in mode 0.
+ *   The reference takes these thresholds from UnivariateSpline(k=3, s=0) through s, evaluated at its own knots: s again up
+ *   to FITPACK's rounding (about 1e-15 relative), which its loop then compares with the scores themselves.  Mode 2 is that
+ *   loop on the noise-free thresholds, bit for bit; the rounding noise is not reproduced.
+ *   Any other word decodes to nothing.  The words live on the device and the call neither copies nor synchronises, so such
+ *   a row is reported through status bit 2 rather than through the return value; it is computed as a mode-0 row.
  * Outputs (fp64): auc (M), kept_fpr / kept_tpr_out / thr_low / thr_up (M, K): what the reference returns, the rates and
  * thresholds bit for bit (same fp64 expressions over integer counts and exactly widened scores), the AUC summed exactly
  * over the counts and divided once.  status (M int32): bit 0 = a NaN score was seen, bit 1 = around-mean row with a
- * non-finite in-score; the other outputs of such a row are meaningless (never out of bounds).
+ * non-finite in-score, bit 2 = malformed mode word; the other outputs of such a row are meaningless (never out of bounds).
  * n_in, n_out in [1, 2^24]; M <= 65535; ws 8-byte aligned, jvae_roc_workspace_bytes(...) bytes (0 = invalid sizes). */
 size_t jvae_roc_workspace_bytes(int M, long n_in, long n_out);
 int jvae_roc_curve_f32(const float* ins, const float* outs, const double* kept_tpr, const int* two_sided,

@@ -2,8 +2,11 @@
 //
 // Reference: utils/roc_curves.py:38-210 (roc_curve: a Python `while` over every in-distribution score taken as a threshold,
 // with inner pointer loops), called per method and per OOD set by ClassificationVariationalNetwork.ood_detection_rates
-// (cvae.py:1843-1868).  The modes kept are the one-sided test (two_sided False / True, roc_curves.py:85-88) and
-// 'around-mean' (roc_curves.py:68-72); the spline modes (roc_curves.py:74-83) are not built.
+// (cvae.py:1843-1868).  The modes are the one-sided test (two_sided False / True, roc_curves.py:85-88), 'around-mean'
+// (roc_curves.py:68-72) and the strided quantiles of the tuple mode (roc_curves.py:74-83): low = [-inf, s[::f_low], inf],
+// up = [-inf, s[::f_up], inf] over the sorted in-scores s THEMSELVES.  The reference takes them from an interpolating cubic
+// spline evaluated at its own knots, i.e. s again up to FITPACK's rounding, and then compares each score with its own noisy
+// image: that noise is not reproduced, the loop on the noise-free thresholds is, bit for bit.
 //
 // The pointer loops are monotone in the iteration index `it`, so every iteration stands alone:
 //   low[it], up[-1 - it]      thresholds (fp64, the reference's own expressions over exactly widened fp32 scores)
@@ -60,8 +63,17 @@ __device__ __forceinline__ float roc_unkey(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
+// Mode word of a row -> 0 one-sided, 1 around-mean, 2 strided quantiles with the factors f_low = bits 8-15 and f_up = bits
+// 16-23, each in [1, 255], of the word 2 | f_low << 8 | f_up << 16; -1: the word decodes to nothing.
+__device__ __forceinline__ int roc_decode(int w, int& f_low, int& f_up) {
+    f_low = (w >> 8) & 255;
+    f_up = (w >> 16) & 255;
+    if (w == 0 || w == 1) return w;
+    return ((w & 255) == 2 && (w >> 24) == 0 && f_low >= 1 && f_up >= 1) ? 2 : -1;
+}
+
 // keys of both row sets (z = 0: ins, 1: outs) + the status word (bit 0: NaN score, bit 1: non-finite in-score of an
-// around-mean row).  atomicOr on an integer flag: the result does not depend on the order.
+// around-mean row, bit 2: malformed mode word).  atomicOr on an integer flag: the result does not depend on the order.
 __global__ __launch_bounds__(256) void roc_keys_kernel(const float* __restrict__ ins, const float* __restrict__ outs,
                                                        const int* __restrict__ modes, uint32_t* __restrict__ kin,
                                                        uint32_t* __restrict__ kout, int* __restrict__ status,
@@ -78,6 +90,8 @@ __global__ __launch_bounds__(256) void roc_keys_kernel(const float* __restrict__
         if (v != v) bad |= 1;
         if (z == 0 && modes[m] == 1 && !isfinite(v)) bad |= 2;
     }
+    int f_low, f_up;
+    if (z == 0 && i == 0 && roc_decode(modes[m], f_low, f_up) < 0) bad |= 4;
     (z ? kout : kin)[(size_t)m * P + i] = key;
     if (bad) atomicOr(&status[m], bad);
 }
@@ -154,20 +168,37 @@ __global__ __launch_bounds__(256) void roc_delta_kernel(const float* __restrict_
 struct RocRow {
     const uint32_t* kin; const uint32_t* kout; const uint64_t* d;
     double c; int mode; long n_in, n_out, nt;
+    long f_low, f_up, n_low, n_up;     // quantile rows: strides and lengths of the two threshold vectors
 };
 __device__ __forceinline__ RocRow roc_row(int m, const uint32_t* kin, const uint32_t* kout, const uint64_t* d, const double* c,
                                           const int* modes, long n_in, long n_out, long Pin, long Pout) {
     RocRow r;
     r.kin = kin + (size_t)m * Pin; r.kout = kout + (size_t)m * Pout; r.d = d + (size_t)m * Pin;
-    r.mode = modes[m] == 1;
-    r.c = r.mode ? c[m] : 0.0;
-    r.n_in = n_in; r.n_out = n_out; r.nt = n_in + 1 + r.mode;
+    int f_low, f_up;
+    const int kind = roc_decode(modes[m], f_low, f_up);
+    r.mode = kind < 0 ? 0 : kind;      // a malformed word is flagged in the status; its row runs as a one-sided one
+    r.c = r.mode == 1 ? c[m] : 0.0;
+    r.n_in = n_in; r.n_out = n_out;
+    r.f_low = f_low; r.f_up = f_up;
+    r.n_low = r.n_up = 0;
+    if (r.mode == 2) {                 // len([-inf, s[::f], inf])
+        r.n_low = (n_in + f_low - 1) / f_low + 2;
+        r.n_up = (n_in + f_up - 1) / f_up + 2;
+        r.nt = r.n_low < r.n_up ? r.n_low : r.n_up;
+    } else {
+        r.nt = n_in + 1 + r.mode;
+    }
     return r;
 }
 
-// all_thresholds['low'][it], all_thresholds['up'][-1 - it] (roc_curves.py:68-72,85-88), 0 <= it < nt
+// all_thresholds['low'][it], all_thresholds['up'][-1 - it] (roc_curves.py:68-72,81-88), 0 <= it < nt
 __device__ __forceinline__ void roc_thresholds(const RocRow& r, long it, double& low, double& up) {
-    if (r.mode) {                      // delta = [0, sort(|ins - c|)..., inf] read from its far end
+    if (r.mode == 2) {                 // it <= nt - 1 <= n_low - 1 and q >= n_up - nt >= 0: every index is inside the row
+        const long q = r.n_up - 1 - it;
+        low = it == 0 ? -(double)INFINITY
+                      : (it == r.n_low - 1 ? (double)INFINITY : (double)roc_unkey(r.kin[(it - 1) * r.f_low]));
+        up = q == 0 ? -(double)INFINITY : (q == r.n_up - 1 ? (double)INFINITY : (double)roc_unkey(r.kin[(q - 1) * r.f_up]));
+    } else if (r.mode) {                      // delta = [0, sort(|ins - c|)..., inf] read from its far end
         const long q = r.n_in + 1 - it;
         const double D = q == 0 ? 0.0 : (q == r.n_in + 1 ? (double)INFINITY : __longlong_as_double((long long)r.d[q - 1]));
         low = -D + r.c;
@@ -245,7 +276,8 @@ __global__ __launch_bounds__(256) void roc_auc_kernel(const int* __restrict__ ne
 
 // The kept-TPR cursor (roc_curves.py:181-189), one thread per row.  The cursor sits on slot j from iteration `start`; it
 // leaves at the first iteration e with tpr < kept[j] (which records nothing) and slot j keeps what iteration e - 1 wrote:
-// its rates and the thresholds of iteration e.  tpr is non-increasing in `it`: one binary search per slot.
+// its rates and the thresholds of iteration e.  tpr is non-increasing in `it` in all three modes (low never falls, up never
+// rises): one binary search per slot.
 __global__ __launch_bounds__(64) void roc_kept_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ kout,
                                                       const uint64_t* __restrict__ d, const double* __restrict__ c,
                                                       const int* __restrict__ modes, const int* __restrict__ negin,

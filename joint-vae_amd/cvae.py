@@ -11,8 +11,8 @@ clip -> Adam — executed by hand-written gfx950 HIP kernels (libjvae_hip.so) be
     .train() / .to() / .save() / .load() / .latent_sampling / .device / .nparams
 
 What is NOT rebuilt here (raises NotImplementedError when asked for): (cvae / xvae / vae / vib are complete, jvae: training and labelled evaluation only); resnet
-feature stacks (torchvision); a per-dimension sigma (the reference fails on it too); label-free evaluation of a categorical
-(256-level) decoder - its training / labelled evaluation is built.  Pooling / up-sampling layer tokens, SGD,
+feature stacks (torchvision); a per-dimension sigma (the reference fails on it too).  A categorical (256-level) decoder,
+its label-free evaluation included, pooling / up-sampling layer tokens, SGD,
 the `y=None` all-class evaluation with its OOD scores, the WIM fine-tuning step and the evaluation methods accuracy(),
 ood_detection_rates() and misclassification_detection_rates() are built.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
@@ -1031,6 +1031,10 @@ class ClassificationVariationalNetwork(nn.Module):
 
     OOD_KEPT_TPR = [pc / 100 for pc in range(90, 100)]                        # cvae.py:1736
     OOD_ROC_EVERY = 100                                                       # batches between two progress ROCs (cvae.py:1843)
+    # The '-a-x-y' methods (cvae.py:1852-1854): two-sided test on every x-th / y-th sorted in-score (ops.roc_curve, mode
+    # ('quantile', x, y)).  Off by default: the reference reads these thresholds off a spline whose rounding noise decides
+    # its kept rates, so the numbers here are close to the reference's, not equal to them.
+    OOD_QUANTILE_METHODS = False
 
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
@@ -1041,11 +1045,11 @@ class ClassificationVariationalNetwork(nn.Module):
         line), a name or a list of names.  On a type whose table lists `odin*` (vib), 'all' and 'odin*' expand to the ODIN grid
         (the plain names first, the expansion behind them, as the reference's develop_starred_methods orders them) and single
         `odin-T-eps` names are accepted; on every other type an ODIN name raises, and so do the spline-threshold ('-a-x-y')
-        methods everywhere."""
+        methods unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
         has_odin = 'odin*' in self.ood_methods
 
         def unbuilt(m):
-            return '-a-' in m or (m.startswith('odin') and not has_odin)
+            return ('-a-' in m and not self.OOD_QUANTILE_METHODS) or (m.startswith('odin') and not has_odin)
 
         def expand(names):
             plain = [m for m in names if m != 'odin*']
@@ -1064,7 +1068,21 @@ class ClassificationVariationalNetwork(nn.Module):
         for m in methods:
             if m.startswith('odin') and m not in grid:
                 raise ValueError(f'{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)')
+            if '-a-' in m:
+                self._roc_mode(m)
         return methods
+
+    @staticmethod
+    def _roc_mode(m):
+        """The `two_sided` value of ops.roc_curve for the method name `m` (cvae.py:1850-1854)."""
+        if m.endswith('-2s'):
+            return 'around-mean'
+        if '-a-' not in m:
+            return False
+        factors = m.split('-a-')[1].split('-')
+        if len(factors) != 2 or not all(f.isdigit() and 1 <= int(f) <= 255 for f in factors):
+            raise ValueError(f'{m}: <score>-a-<x>-<y> with x and y in 1 .. 255 expected')
+        return ('quantile', int(factors[0]), int(factors[1]))
 
     def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False):
         """One pass over `dset` for ood_detection_rates: per batch the label-free evaluation (or the batch read back from a full
@@ -1147,8 +1165,9 @@ class ClassificationVariationalNetwork(nn.Module):
         set, the ROC of all M methods of a set is ONE `ops.roc_curve` call (csrc/roc.hip) made every 100 batches for the
         progress line and at the last batch, as the reference does with its Python loop (utils/roc_curves.py:38-210), and only
         its (M, K) results and the fp64 row means / deviations come to the host.  'thresholds' holds the K [low, up] pairs
-        (the reference stores list(dict), i.e. the two key names).  Methods: what `batch_dist_measures` computes, one-sided
-        or with the '-2s' suffix (two-sided around the mean); see `_ood_methods` for the rest.  Named datasets
+        (the reference stores list(dict), i.e. the two key names).  Methods: what `batch_dist_measures` computes, one-sided,
+        with the '-2s' suffix (two-sided around the mean) or, with `OOD_QUANTILE_METHODS`, the '-a-x-y' suffix (two-sided on
+        in-score quantiles; ValueError below 4 in-distribution samples); see `_ood_methods` for the rest.  Named datasets
         (`testset=None` or a string, `oodsets=None`) and the registry lookup of earlier results (`from_where`) are host
         plumbing outside this build, as for accuracy(); so are `sample_recorders`."""
         if testset is None or isinstance(testset, str) or oodsets is None or any(isinstance(o, str) for o in oodsets):
@@ -1170,7 +1189,7 @@ class ClassificationVariationalNetwork(nn.Module):
             return ood_results
         was_training = self.training
         self.eval()
-        modes = ['around-mean' if m.endswith('-2s') else False for m in methods]
+        modes = [self._roc_mode(m) for m in methods]
 
         def plan(dset):
             full = int(np.ceil(len(dset) / batch_size))
@@ -1197,6 +1216,10 @@ class ClassificationVariationalNetwork(nn.Module):
         ind = self._score_set(testset, methods, batch_size, nb, shuffle, recorders.get(names[0]), sample_dirs, keep_test=True,
                               on_batch=progress_line(names[0], lambda s: self._row_mean_std(s)[:, 0].tolist(),
                                                      lambda: {m: np.nan for m in methods}))
+        for m in methods:
+            if '-a-' in m and ind.shape[1] < 4:
+                raise ValueError(f'{m}: {ind.shape[1]} in-distribution samples, the cubic spline of the reference needs 4 '
+                                 '(utils/roc_curves.py:79)')
         if update_self_ood:
             entry = self.ood_results.setdefault(epoch, {}).setdefault(names[0], {})
             for m, (mean, std) in zip(methods, self._row_mean_std(ind).tolist()):

@@ -2,7 +2,8 @@
 
 `roc_curve` takes what the reference's takes (array-likes or tensors, on any device: they are moved to the GPU as fp32, the
 precision in which the model produces its scores) and returns numpy values of the same shapes.  What the reference computes
-through a SciPy smoothing spline (`two_sided=(a, b)`), a validation split or reversed scores is not built and raises.
+through a SciPy spline (`two_sided=(a, b)`), a validation split or reversed scores raises there; `roc_curve_quantile` is the
+tuple mode on the spline's noise-free values, under a name of its own because its numbers are not the reference's.
 """
 import numpy as np
 import torch
@@ -32,10 +33,26 @@ def roc_curve(ins, outs, *kept_tpr, two_sided=False, validation=0, debug=False, 
         raise NotImplementedError('roc_curve: ins_are_higher=False is not built')
     if isinstance(two_sided, tuple):
         raise NotImplementedError('roc_curve: the spline thresholds (two_sided=(a, b)) are not built')
+    return _one_row(ins, outs, kept_tpr, 'around-mean' if two_sided == 'around-mean' else False, device)
+
+
+def roc_curve_quantile(ins, outs, *kept_tpr, factors=(1, 1), device=None):
+    """What `roc_curve(ins, outs, *kept_tpr, two_sided=factors)` of the reference computes (utils/roc_curves.py:74-83, the
+    '-a-x-y' OOD methods) when its spline through the sorted in-scores returns them unchanged: every factors[0]-th one is a
+    lower threshold, every factors[1]-th one an upper threshold, met from the two ends.  The reference's own numbers carry
+    FITPACK's rounding of that spline on top (DESIGN.md section 7) and differ slightly.  Same return tuple as `roc_curve`;
+    ValueError on a NaN score and for fewer than 4 in-scores, where the reference's cubic fit fails."""
+    n_in = ins.numel() if torch.is_tensor(ins) else np.size(ins)
+    if n_in < 4:
+        raise ValueError(f'roc_curve_quantile: {n_in} in-distribution scores, the cubic spline of the reference needs 4')
+    return _one_row(ins, outs, kept_tpr, ('quantile',) + tuple(factors), device)
+
+
+def _one_row(ins, outs, kept_tpr, mode, device):
     device = device or ('cuda' if torch.cuda.is_available() else 'cpu')      # off the GPU the op raises JvaeHipError
     rows = [torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(device=device, dtype=torch.float32).reshape(-1)
             for v in (ins, outs)]
-    r = ops.roc_curve(rows[0], rows[1], sorted(kept_tpr), 'around-mean' if two_sided == 'around-mean' else False)
+    r = ops.roc_curve(rows[0], rows[1], sorted(kept_tpr), mode)
     ops.roc_check_status([int(r['status'].cpu())])
     host = {k: r[k].cpu().numpy() for k in ('auc', 'fpr', 'tpr', 'low', 'up')}
     return float(host['auc']), host['fpr'], host['tpr'], {'low': host['low'], 'up': host['up']}

@@ -1080,9 +1080,13 @@ def roc_curve(ins, outs, kept_tpr, two_sided=False):
     """AUC and the FPR / thresholds at the kept TPRs of M score rows in one call (utils/roc_curves.py:38-210; csrc/roc.hip).
     ins (M, n_in) or (n_in,), outs (M, n_out) or (n_out,): fp32 scores on the device, higher = more in-distribution.
     kept_tpr: ascending floats (list or fp64 device tensor of K).  two_sided: per row (or one value for all rows) False / True
-    = one-sided test, 'around-mean' = two-sided around the mean of the in-scores; int32 device tensor of 0 / 1 accepted.
+    = one-sided test, 'around-mean' = two-sided around the mean of the in-scores, ('quantile', f_low, f_up) = the reference's
+    two_sided=(f_low, f_up) on the sorted in-scores themselves (every f_low-th as a lower, every f_up-th as an upper threshold,
+    factors in [1, 255]; include/jvae_hip.h says how this differs from the reference's spline); an int32 device tensor of the
+    mode words of include/jvae_hip.h (`roc_mode_word`) is accepted.  A bare tuple such as (4, 1) is read as per-row values.
     -> dict of DEVICE tensors: 'auc' (M,), 'fpr' / 'tpr' / 'low' / 'up' (M, K) fp64 and 'status' (M,) int32 (bit 0: NaN score,
-    bit 1: non-finite in-score of an around-mean row; `roc_check_status` raises on them).  (n,) inputs drop the M axis.
+    bit 1: non-finite in-score of an around-mean row, bit 2: malformed mode word in a tensor; `roc_check_status` raises on
+    them).  (n,) inputs drop the M axis.
     Nothing is synchronised or copied to the host."""
     lib = L.load()
     single = ins.dim() == 1
@@ -1100,11 +1104,9 @@ def roc_curve(ins, outs, kept_tpr, two_sided=False):
     if torch.is_tensor(two_sided):
         modes = _c(two_sided.to(device=dev, dtype=torch.int32))
     else:
-        rows = list(two_sided) if isinstance(two_sided, (list, tuple)) else [two_sided] * M
-        for t in rows:
-            if t not in (False, True, 0, 1, None, 'around-mean'):
-                raise NotImplementedError(f'roc_curve: two_sided={t!r} (the spline thresholds of the reference are not built)')
-        modes = torch.tensor([1 if t == 'around-mean' else 0 for t in rows], dtype=torch.int32, device=dev)
+        for_all = not isinstance(two_sided, (list, tuple)) or two_sided[:1] == ('quantile',)
+        rows = [two_sided] * M if for_all else list(two_sided)
+        modes = torch.tensor([roc_mode_word(t) for t in rows], dtype=torch.int32, device=dev)
     if modes.numel() != M:
         raise L.JvaeHipError(f'roc_curve: {modes.numel()} modes for {M} rows')
     K = kept.numel()
@@ -1123,9 +1125,24 @@ def roc_curve(ins, outs, kept_tpr, two_sided=False):
     return {k: v[0] for k, v in res.items()} if single else res
 
 
+def roc_mode_word(t):
+    """One row's `two_sided` value -> its int32 mode word (include/jvae_hip.h): 0 one-sided, 1 'around-mean',
+    2 | f_low << 8 | f_up << 16 for ('quantile', f_low, f_up)."""
+    if isinstance(t, tuple) and t[:1] == ('quantile',):
+        if len(t) != 3 or any(isinstance(f, bool) or not isinstance(f, int) or not 1 <= f <= 255 for f in t[1:]):
+            raise L.JvaeHipError(f'roc_curve: two_sided={t!r}: two integer factors in [1, 255] expected')
+        return 2 | t[1] << 8 | t[2] << 16
+    if isinstance(t, tuple) or t not in (False, True, 0, 1, None, 'around-mean'):
+        raise NotImplementedError(f'roc_curve: two_sided={t!r} (the spline thresholds of the reference are not built)')
+    return 1 if t == 'around-mean' else 0
+
+
 def roc_check_status(status):
-    """Raise ValueError for the rows `roc_curve` flagged (host values of its 'status' word)."""
+    """Raise for the rows `roc_curve` flagged (host values of its 'status' word): JvaeHipError for a malformed mode word,
+    ValueError for what the scores hold."""
     for m, s in enumerate(status if hasattr(status, '__len__') else [status]):
+        if int(s) & 4:
+            raise L.JvaeHipError(f'roc_curve: malformed mode word in row {m}')
         if int(s) & 1:
             raise ValueError(f'roc_curve: NaN score in row {m}')
         if int(s) & 2:

@@ -66,6 +66,21 @@ int jvae_conv2d_set_split_bf16(int mode);
  * previous setting (A/B switch for tests and benches). */
 int jvae_conv2d_set_split_shape16(int on);
 int jvae_conv2d_out_shape(int H, int W, int KH, int KW, int S, int P, int OP, int transposed, int* OH, int* OW);
+/* Host-only query of the kernel selection (nothing is initialised on the device): the route the entry points take for a call
+ * of direction dir (1 forward, 2 dgrad, 4 wgrad: the bits of jvae_conv2d_native_b8) in layout 0 (fp32 NCHW) or 1 (bf16 B8)
+ * with these call facts: bias / stats given, y_f32 (the bf16 forward's fp32 output), aff_kind 0 / 1 / 2 (in_relu of the *_aff
+ * entry points + 1 when a deferred BatchNorm is applied, 0 without).  Reads the split-bf16 switch like every call.  Outputs
+ * (each may be NULL): *kernel the kernel family (0 = none: that bf16 entry point returns -2; name: jvae_conv2d_kernel_name),
+ * *swap the role swap of the leaf, *ws_bytes the workspace the leaf needs (0: the generic path sizes itself by what it is
+ * given), *splits the BatchNorm partial sums per channel a forward writes at most, *aff_ok whether the leaf applies a
+ * deferred BatchNorm.  -1 for a geometry the entry points refuse. */
+int jvae_conv2d_route(int dir, int layout, int bias, int stats, int y_f32, int aff_kind,
+                      int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
+                      int* kernel, int* swap, size_t* ws_bytes, int* splits, int* aff_ok);
+/* "CK_FWD5_X3", ... for a *kernel of jvae_conv2d_route; NULL beyond the last one */
+const char* jvae_conv2d_kernel_name(int kernel);
+/* N = 0 (an empty batch) is valid on every convolution entry point of both layouts: 0 is returned, no activation is read or
+ * written (their pointers may be NULL), a weight gradient without `accumulate` zeroes dw / dbias and leaves them alone with it. */
 int jvae_conv2d_fwd_f32(const float* x, const float* w, const float* bias, float* y,
                         int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                         void* ws, size_t ws_bytes, void* stream);

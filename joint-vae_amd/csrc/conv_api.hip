@@ -34,7 +34,7 @@ int wgrad_f32(const float* x, const float* dy, float* dw, float* dbias, int accu
               int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
               void* ws, size_t ws_bytes, void* stream) {
     ConvGeom g; int oh, ow;
-    if (!x || !dy || !dw) return JVAE_EINVAL;
+    if (!dw || (N > 0 && (!x || !dy))) return JVAE_EINVAL;
     if (!jvae_make_geom(N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, &g, &oh, &ow)) return JVAE_EINVAL;
     const ConvRoute r = route(g, transposed, CONV_WGRAD, {false, false, false, jvae_aff_kind(aff)});
     if (aff && !affine_ok(g, transposed, CONV_FWD, r)) return JVAE_ENOTSUP;
@@ -71,6 +71,36 @@ size_t jvae_conv2d_workspace_bytes(int N, int Cin, int H, int W, int Cout, int K
     return jvae_conv_ws(g, transposed);
 }
 
+// Host-only: the route the entry points of either layout take for this call (nothing is initialised on the device)
+int jvae_conv2d_route(int dir, int layout, int bias, int stats, int y_f32, int aff_kind,
+                      int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
+                      int* kernel, int* swap, size_t* ws_bytes, int* splits, int* aff_ok) {
+    ConvGeom g; int oh, ow;
+    if (dir != CONV_FWD && dir != CONV_DGRAD && dir != CONV_WGRAD) return JVAE_EINVAL;
+    if ((layout != CONV_F32 && layout != CONV_B8) || aff_kind < 0 || aff_kind > 2) return JVAE_EINVAL;
+    if (!jvae_make_geom(N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, &g, &oh, &ow)) return JVAE_EINVAL;
+    const ConvRoute r = jvae_conv_route(g, transposed, (ConvDir)dir, (ConvLayout)layout,
+                                        {bias != 0, stats != 0, y_f32 != 0, aff_kind});
+    if (kernel) *kernel = (int)r.k;
+    if (swap) *swap = r.swap ? 1 : 0;
+    if (ws_bytes) *ws_bytes = r.ws;
+    if (splits) *splits = r.splits;
+    if (aff_ok) *aff_ok = r.aff_ok ? 1 : 0;
+    return 0;
+}
+
+const char* jvae_conv2d_kernel_name(int kernel) {
+    switch (kernel) {
+#define JVAE_CK_NAME(k) case k: return #k;
+        JVAE_CK_NAME(CK_NONE) JVAE_CK_NAME(CK_GENERIC) JVAE_CK_NAME(CK_POINT) JVAE_CK_NAME(CK_SMALLCO)
+        JVAE_CK_NAME(CK_SMALLCI) JVAE_CK_NAME(CK_FWD5) JVAE_CK_NAME(CK_FWD5_X3) JVAE_CK_NAME(CK_T2) JVAE_CK_NAME(CK_T2_X3)
+        JVAE_CK_NAME(CK_WG5) JVAE_CK_NAME(CK_WG5_X3) JVAE_CK_NAME(CK_B8) JVAE_CK_NAME(CK_T2_B8) JVAE_CK_NAME(CK_WG_B8)
+        JVAE_CK_NAME(CK_WG_B8X) JVAE_CK_NAME(CK_SMALLCO_DG)
+#undef JVAE_CK_NAME
+        default: return nullptr;
+    }
+}
+
 int jvae_conv2d_out_shape(int H, int W, int KH, int KW, int S, int P, int OP, int transposed, int* OH, int* OW) {
     ConvGeom g;
     if (!OH || !OW) return JVAE_EINVAL;
@@ -80,7 +110,7 @@ int jvae_conv2d_out_shape(int H, int W, int KH, int KW, int S, int P, int OP, in
 int jvae_conv2d_fwd_f32(const float* x, const float* w, const float* bias, float* y,
                         int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                         void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !w || !y) return JVAE_EINVAL;
+    if (!w || (N > 0 && (!x || !y))) return JVAE_EINVAL;          // an empty batch has no activations to point at
     return fwd_f32(x, w, bias, y, nullptr, nullptr, nullptr, N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, ws, ws_bytes,
                    stream);
 }
@@ -98,7 +128,7 @@ int jvae_conv2d_stats_splits(int N, int Cin, int H, int W, int Cout, int KH, int
 int jvae_conv2d_fwd_stats_f32(const float* x, const float* w, const float* bias, float* y, float* stats, int* nsplit,
                               int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                               void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !w || !y || !nsplit) return JVAE_EINVAL;
+    if (!w || !nsplit || (N > 0 && (!x || !y))) return JVAE_EINVAL;
     return fwd_f32(x, w, bias, y, stats, nsplit, nullptr, N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, ws, ws_bytes, stream);
 }
 
@@ -114,7 +144,7 @@ int jvae_conv2d_fwd_aff_f32(const float* x, const float* w, const float* bias, f
                             const float* in_scale, const float* in_shift, int in_relu,
                             int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                             void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !w || !y || !in_scale || !in_shift) return JVAE_EINVAL;
+    if (!w || !in_scale || !in_shift || (N > 0 && (!x || !y))) return JVAE_EINVAL;
     if (stats && !nsplit) return JVAE_EINVAL;
     const InAff aff{in_scale, in_shift, in_relu};
     return fwd_f32(x, w, bias, y, stats, nsplit, &aff, N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, ws, ws_bytes, stream);
@@ -133,7 +163,7 @@ int jvae_conv2d_dgrad_f32(const float* dy, const float* w, float* dx,
                           int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                           void* ws, size_t ws_bytes, void* stream) {
     ConvGeom g; int oh, ow;
-    if (!dy || !w || !dx) return JVAE_EINVAL;
+    if (!w || (N > 0 && (!dy || !dx))) return JVAE_EINVAL;
     if (!jvae_make_geom(N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, &g, &oh, &ow)) return JVAE_EINVAL;
     if (N == 0) return 0;
     const ConvRoute r = route(g, transposed, CONV_DGRAD);

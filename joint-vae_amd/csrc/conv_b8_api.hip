@@ -45,11 +45,11 @@ int wgrad_b8(const void* x, const void* dy, float* dw, float* dbias, int accumul
              int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
              void* ws, size_t ws_bytes, void* stream) {
     ConvGeom g; int oh, ow;
-    if (!x || !dy || !dw) return JVAE_EINVAL;
+    if (!dw || (N > 0 && (!x || !dy))) return JVAE_EINVAL;
     if (!jvae_make_geom(N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, &g, &oh, &ow)) return JVAE_EINVAL;
     const ConvRoute r = route(g, transposed, CONV_WGRAD, {false, false, false, jvae_aff_kind(aff)});
     if (r.k == CK_NONE || (aff && !r.aff_ok)) return JVAE_ENOTSUP;
-    if (!ws || ws_bytes < r.ws + (dbias ? chsum_ws_bytes(Cout) : 0)) return JVAE_EWORKSPACE;
+    if (N > 0 && (!ws || ws_bytes < r.ws + (dbias ? chsum_ws_bytes(Cout) : 0))) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (!accumulate) {
         hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * (size_t)Cin * Cout * KH * KW, st);
@@ -120,7 +120,7 @@ int jvae_conv2d_fwd_b8(const void* x, const float* w, const float* bias, void* y
                        int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                        void* ws, size_t ws_bytes, void* stream) {
     if (nsplit) *nsplit = 0;
-    if (!x || !w || !y) return JVAE_EINVAL;
+    if (!w || (N > 0 && (!x || !y))) return JVAE_EINVAL;          // an empty batch has no activations to point at
     return fwd_b8(x, w, bias, y, y_f32, stats, nsplit, nullptr, N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, ws, ws_bytes,
                   stream);
 }
@@ -139,7 +139,7 @@ int jvae_conv2d_fwd_aff_b8(const void* x, const float* w, const float* bias, voi
                            int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                            void* ws, size_t ws_bytes, void* stream) {
     if (nsplit) *nsplit = 0;
-    if (!x || !w || !y || !in_scale || !in_shift) return JVAE_EINVAL;
+    if (!w || !in_scale || !in_shift || (N > 0 && (!x || !y))) return JVAE_EINVAL;
     const InAff aff{in_scale, in_shift, in_relu};
     return fwd_b8(x, w, bias, y, y_f32, stats, nsplit, &aff, N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, ws, ws_bytes,
                   stream);
@@ -150,7 +150,7 @@ int jvae_conv2d_dgrad_b8(const void* dy, const float* w, void* dx,
                          int N, int Cin, int H, int W, int Cout, int KH, int KW, int S, int P, int OP, int transposed,
                          void* ws, size_t ws_bytes, void* stream) {
     ConvGeom g; int oh, ow;
-    if (!dy || !w || !dx) return JVAE_EINVAL;
+    if (!w || (N > 0 && (!dy || !dx))) return JVAE_EINVAL;
     if (!jvae_make_geom(N, Cin, H, W, Cout, KH, KW, S, P, OP, transposed, &g, &oh, &ow)) return JVAE_EINVAL;
     if (N == 0) return 0;
     const ConvRoute r = route(g, transposed, CONV_DGRAD);

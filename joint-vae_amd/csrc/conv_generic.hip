@@ -208,7 +208,7 @@ inline int fwd_slices(const ConvGeom& g) {
     if (!pixel_batched(g)) return 1;
     const long Kd = (long)g.Cb * g.KH * g.KW;
     const long tiles = (long)cdiv(g.N, 64) * cdiv(g.Cs, 64) * g.Hs * g.Ws;
-    if (tiles >= 512 || Kd < 1024) return 1;
+    if (tiles < 1 || tiles >= 512 || Kd < 1024) return 1;          // (tiles = 0: an empty batch)
     // one residency round of FOUR workgroups per CU: the phases of a K step (loads, split + LDS stores, fragment reads + MFMAs) run
     // one after the other inside a workgroup, so it takes several of them per SIMD to keep the matrix pipe fed (round 4, with the
     // coalesced partial-product layout: features.12 of conv32 51.4 -> 50.1 us against the two-per-CU choice of round 3)
@@ -230,11 +230,18 @@ __global__ __launch_bounds__(256) void small_transpose_kernel(const float* __res
 
 inline long col_floats_per_image(const ConvGeom& g) { return (long)g.Cb * g.KH * g.KW * g.Hs * g.Ws; }
 
+// Per-image weight gradient of the larger grids: the per-image products of one chunk of images are stored side by side behind the
+// chunk's unfold buffer and folded onto dW in image order (no float atomics: the same bits from launch to launch).  The chunk is
+// as many images as the workspace holds of both, so a batch is one batched product - the launch it was with atomics - wherever
+// the query's ~1 GiB bound allows.
+inline long wgrad_part_floats(const ConvGeom& g) { return (long)g.Cs * g.Cb * g.KH * g.KW; }
+
 }  // namespace
 
 size_t jvae_conv_generic_ws(const ConvGeom& g) {
     // bounded: at most ~1 GiB of unfold buffer, at least one image
-    const long per = col_floats_per_image(g) * 4;
+    // per image: the unfold buffer and, on the larger grids, the weight gradient's partial product behind it
+    const long per = (col_floats_per_image(g) + (pixel_batched(g) ? 0 : wgrad_part_floats(g))) * 4;
     long imgs = (1L << 30) / (per > 0 ? per : 1);
     if (imgs < 1) imgs = 1;
     if (imgs > g.N) imgs = g.N;
@@ -340,7 +347,7 @@ int jvae_fold_bwd(const ConvGeom& g, const float* ys, const float* w, const floa
 }
 
 // dW[Cs][Kd] (+)= sum_n Ys_n . unfold(Xb)_n^T.  dW must already hold the value to accumulate onto
-// (the caller zeroes it for a plain gradient): partial products are added with float atomics.
+// (the caller zeroes it for a plain gradient): partial products are folded onto it in a fixed order (no float atomics).
 int jvae_fold_wgrad(const ConvGeom& g, const float* xb, const float* ys, float* dw,
                     float* ws, size_t ws_bytes, hipStream_t st) {
     const int Kd = g.Cb * g.KH * g.KW, Ps = g.Hs * g.Ws;
@@ -372,13 +379,30 @@ int jvae_fold_wgrad(const ConvGeom& g, const float* xb, const float* ys, float* 
         }
         return 0;
     }
-    const int chunk = chunk_images(g, ws_bytes);
-    if (chunk < 1) return JVAE_EWORKSPACE;
-    for (int n0 = 0; n0 < g.N; n0 += chunk) {
-        const int ni = (g.N - n0 < chunk) ? g.N - n0 : chunk;
+    // Chunks of as many images as the workspace holds: their per-image products are stored side by side behind the unfold buffer
+    // and folded onto dW in image order (a chunk of one image accumulates straight onto dW).  With room for the unfold buffer
+    // of one image alone: image by image.
+    const long colf = col_floats_per_image(g), partf = wgrad_part_floats(g);
+    long chunk = (long)(ws_bytes / (size_t)(4 * (colf + partf)));
+    if (chunk > g.N) chunk = g.N;
+    if (chunk < 1) {
+        if (chunk_images(g, ws_bytes) < 1) return JVAE_EWORKSPACE;
+        chunk = 1;
+    }
+    float* part = ws + chunk * colf;
+    for (int n0 = 0; n0 < g.N; n0 += (int)chunk) {
+        const int ni = (g.N - n0 < chunk) ? g.N - n0 : (int)chunk;
         { const int rc = launch_unfold(xb, ws, g, n0, ni, false, st); if (rc) return rc; }
-        int rc = jvae_gemm_launch(g.Cs, Kd, Ps, ni, ys + (long)n0 * g.Cs * Ps, Ps, 1, (long)g.Cs * Ps,
-                                  ws, 1, Ps, (long)Kd * Ps, dw, Kd, 1, 0, nullptr, 0, 4, 1, st);
+        const float* a = ys + (long)n0 * g.Cs * Ps;
+        if (ni == 1) {
+            const int rc = jvae_gemm_launch(g.Cs, Kd, Ps, 1, a, Ps, 1, 0, ws, 1, Ps, 0, dw, Kd, 1, 0, nullptr, 0, 1, 1, st);
+            if (rc) return rc;
+            continue;
+        }
+        int rc = jvae_gemm_launch(g.Cs, Kd, Ps, ni, a, Ps, 1, (long)g.Cs * Ps, ws, 1, Ps, (long)Kd * Ps,
+                                  part, Kd, 1, partf, nullptr, 0, 0, 1, st);
+        if (rc) return rc;
+        rc = jvae_splitk_fold(part, nullptr, dw, ni, partf, Kd, 0, 1, st);
         if (rc) return rc;
     }
     return 0;

@@ -23,6 +23,8 @@ _SIGS = {
     'jvae_conv2d_set_split_bf16': (c_int, [c_int]),
     'jvae_conv2d_set_split_shape16': (c_int, [c_int]),
     'jvae_conv2d_out_shape': (c_int, [c_int] * 8 + [POINTER(c_int), POINTER(c_int)]),
+    'jvae_conv2d_route': (c_int, [c_int] * 17 + [POINTER(c_int), POINTER(c_int), POINTER(c_size_t), POINTER(c_int), POINTER(c_int)]),
+    'jvae_conv2d_kernel_name': (c_char_p, [c_int]),
     'jvae_conv2d_fwd_f32': (c_int, [P, P, P, P] + [c_int] * 11 + [P, c_size_t, P]),
     'jvae_conv2d_stats_splits': (c_int, [c_int] * 11),
     'jvae_conv2d_fwd_stats_f32': (c_int, [P, P, P, P, P, POINTER(c_int)] + [c_int] * 11 + [P, c_size_t, P]),

@@ -3,9 +3,10 @@
 PyTorch is plumbing here (device memory, streams, the autograd tape); every FLOP of the training step is
 executed by the hand-written gfx950 kernels.  Every function raises if its tensors are not on the GPU.
 """
+import collections
 import contextlib
 import math
-from ctypes import byref, c_int
+from ctypes import byref, c_int, c_size_t
 
 import torch
 
@@ -234,6 +235,23 @@ def conv_fwd_stats_raw(x, w, b, spec):
 def conv_affine_ok(spec, N, H, W):
     """Can this layer apply a deferred BatchNorm(+ReLU) to its input (forward and weight gradient kernels)?"""
     return bool(_geom_query('jvae_conv2d_affine_ok', spec.geom(N, H, W)))
+
+
+ConvRoute = collections.namedtuple('ConvRoute', 'kernel swap ws splits aff_ok')
+ROUTE_DIR = {'fwd': 1, 'dgrad': 2, 'wgrad': 4}
+ROUTE_LAYOUT = {'f32': 0, 'b8': 1}
+
+
+def conv_route(spec, N, H, W, direction, layout='f32', bias=False, stats=False, y_f32=False, aff=0):
+    """The kernel the entry points of `layout` run for this call ('fwd' / 'dgrad' / 'wgrad'; aff: 0 none, 1 BatchNorm(+ReLU),
+    2 leaky), asked from jvae_conv_route through the host-only query: ConvRoute(kernel='CK_FWD5_X3', swap, ws, splits, aff_ok).
+    Not memoised: the route follows the split-bf16 switch.  JvaeHipError for a geometry the entry points refuse."""
+    lib = L.load()
+    k, sw, ns, ok, ws = c_int(), c_int(), c_int(), c_int(), c_size_t()
+    rc = lib.jvae_conv2d_route(ROUTE_DIR[direction], ROUTE_LAYOUT[layout], int(bias), int(stats), int(y_f32), int(aff),
+                               *spec.geom(N, H, W), byref(k), byref(sw), byref(ws), byref(ns), byref(ok))
+    L.check(rc, 'jvae_conv2d_route')
+    return ConvRoute(lib.jvae_conv2d_kernel_name(k.value).decode(), bool(sw.value), ws.value, ns.value, bool(ok.value))
 
 
 class LaunchProbe:

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases as cc
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
@@ -208,16 +210,23 @@ def test_split_bf16_conv_is_fp32_accurate(cin, cout, tr, H, N, shape16):
     gy = torch.randn(ref.shape, generator=g)
     if tr:
         gref = F.conv2d(gy.double(), w.double(), padding=2)
+        A = F.conv_transpose2d(x.double().abs(), w.double().abs(), b.double().abs(), padding=2)
+        gA = F.conv2d(gy.double().abs(), w.double().abs(), padding=2)
     else:
         gref = F.conv_transpose2d(gy.double(), w.double(), padding=2)
+        A = F.conv2d(x.double().abs(), w.double().abs(), b.double().abs(), padding=2)
+        gA = F.conv_transpose2d(gy.double().abs(), w.double().abs(), padding=2)
     spec = ops.ConvSpec(cin, cout, 5, 1, 2, 0, tr)
     xd, wd, bd, gyd = x.to(DEV), w.to(DEV), b.to(DEV), gy.to(DEV)
-    out = {}
+    out, planes = {}, {}
     old = L.jvae_conv2d_set_split_bf16(1)
     old_shape = L.jvae_conv2d_set_split_shape16(shape16)
     try:
         for mode in (1, 0):
             L.jvae_conv2d_set_split_bf16(mode)
+            kernel = 'CK_FWD5_X3' if mode and 16 <= cin <= 256 else 'CK_FWD5'        # conv_x3.hip serves 16 .. 256 input channels
+            assert ops.conv_route(spec, N, H, H, 'fwd', bias=True).kernel == kernel
+            assert ops.conv_route(spec, N, H, H, 'fwd', bias=True, stats=True).kernel == kernel
             y = ops.conv_fwd_raw(xd, wd, bd, spec)
             ys = ops.conv_fwd_stats_raw(xd, wd, bd, spec)
             dx = ops.conv_dgrad_raw(gyd, wd, spec, xd.shape)
@@ -229,6 +238,7 @@ def test_split_bf16_conv_is_fp32_accurate(cin, cout, tr, H, N, shape16):
                 assert float((part[:, 0] - yc.sum((0, 2, 3))).abs().max() / yc.abs().sum((0, 2, 3)).max()) < 1e-5
                 assert float((part[:, 1] - (yc * yc).sum((0, 2, 3))).abs().max() / (yc * yc).sum((0, 2, 3)).max()) < 1e-5
             out[mode] = (rel(y, ref), rel(dx, gref), y, dx)
+            planes[mode] = (cc.worst_plane(y, ref, A), cc.worst_plane(dx, gref, gA))
     finally:
         L.jvae_conv2d_set_split_bf16(old)
         L.jvae_conv2d_set_split_shape16(old_shape)
@@ -236,6 +246,9 @@ def test_split_bf16_conv_is_fp32_accurate(cin, cout, tr, H, N, shape16):
     assert out[0][0] < 5e-6 and out[0][1] < 5e-6, out[0][:2]          # fp32 MFMA (k-ordered fmaf chain): up to 1.5e-6
     assert out[1][0] < 2 * out[0][0] + 1e-7 and out[1][1] < 2 * out[0][1] + 1e-7, (out[1][:2], out[0][:2])
     assert rel(out[1][2], out[0][2]) < 5e-6 and rel(out[1][3], out[0][3]) < 5e-6
+    # ... and every (image, channel) plane on its own scale (conv_cases.plane_err), at the same bars
+    assert planes[1][0][0] < 3e-6 and planes[1][1][0] < 3e-6, planes[1]
+    assert planes[0][0][0] < 5e-6 and planes[0][1][0] < 5e-6, planes[0]
 
 
 @pytest.mark.parametrize('cin,cout,s,tr,H,N', [(32, 32, 1, True, 32, 6), (32, 64, 1, False, 16, 9), (64, 32, 1, True, 16, 5),
@@ -265,6 +278,8 @@ def test_split_bf16_wgrad_is_fp32_accurate(cin, cout, s, tr, H, N):
         gy = torch.randn(y64.shape, generator=torch.Generator().manual_seed(5)) * \
             torch.exp(torch.randn(N, y64.shape[1], 1, 1, generator=torch.Generator().manual_seed(6)))
         y64.backward(gy.double())
+        absx = x.double().abs() if aff is None else (x.double() * sc.double().view(1, -1, 1, 1)).abs() + sh.double().abs().view(1, -1, 1, 1)
+        A = cc.wgrad64(cc.Spec(cin, cout, 5, s, 2, op, tr), absx, gy.double().abs(), wshape)
         affd = None if aff is None else (sc.to(DEV), sh.to(DEV), True)
         if affd is not None and not ops.conv_affine_ok(spec, N, H, H):
             continue
@@ -273,16 +288,18 @@ def test_split_bf16_wgrad_is_fp32_accurate(cin, cout, s, tr, H, N):
             out = {}
             for mode in (1, 0):
                 L.jvae_conv2d_set_split_bf16(mode)
+                assert ops.conv_route(spec, N, H, H, 'wgrad', aff=int(aff is not None)).kernel == ('CK_WG5_X3' if mode else 'CK_WG5')
                 gw, _ = ops.conv_wgrad_raw(x.to(DEV), gy.to(DEV), spec, wshape, False, aff=affd)
                 gw2, _ = ops.conv_wgrad_raw(x.to(DEV), gy.to(DEV), spec, wshape, False, aff=affd)
                 assert torch.equal(gw, gw2)
-                out[mode] = (rel(gw, w64.grad), gw)
+                out[mode] = (rel(gw, w64.grad), gw, cc.worst_plane(gw, w64.grad, A))
         finally:
             L.jvae_conv2d_set_split_bf16(old)
         assert out[1][0] < 3e-6, (aff is not None, out[1][0], out[0][0])      # split bf16
         assert out[0][0] < 5e-6, (aff is not None, out[0][0])                  # fp32 MFMA (k-ordered fmaf chain)
         assert out[1][0] < 2 * out[0][0] + 2e-7, (out[1][0], out[0][0])
         assert rel(out[1][1], out[0][1]) < 5e-6
+        assert out[1][2][0] < 3e-6 and out[0][2][0] < 5e-6, (out[1][2], out[0][2])      # every filter on its own scale
         res[aff is not None] = (out[1][0], out[0][0])
     print(f'wgrad {cin}->{cout} s{s} tr={tr} H={H}: error vs fp64 split-bf16 / fp32-MFMA: {res}')
 
@@ -779,22 +796,30 @@ def test_split_bf16_stride2_transposed_conv(cin, cout, H, N, tr):
         w = torch.randn(cin, cout, 5, 5, generator=g) / math.sqrt(cin * 25)
         b = torch.randn(cout, generator=g)
         ref = F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2, padding=2, output_padding=1)
+        A = F.conv_transpose2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=2, padding=2, output_padding=1)
         spec = ops.ConvSpec(cin, cout, 5, 2, 2, 1, True)
+        route = lambda: ops.conv_route(spec, N, H, H, 'fwd', bias=True, stats=True)
         run = lambda: ops.conv_fwd_stats_raw(x.to(DEV), w.to(DEV), b.to(DEV), spec)[0]
     else:        # dgrad of the stride-2 convolution: dy (cin = its output channels) -> dx (cout = its input channels)
         w = torch.randn(cin, cout, 5, 5, generator=g) / math.sqrt(cin * 25)
         ref = F.conv_transpose2d(x.double(), w.double(), stride=2, padding=2, output_padding=1)
+        A = F.conv_transpose2d(x.double().abs(), w.double().abs(), stride=2, padding=2, output_padding=1)
         spec = ops.ConvSpec(cout, cin, 5, 2, 2, 0, False)
+        route = lambda: ops.conv_route(spec, N, 2 * H, 2 * H, 'dgrad')
         run = lambda: ops.conv_dgrad_raw(x.to(DEV), w.to(DEV), spec, (N, cout, 2 * H, 2 * H))
     old = L.jvae_conv2d_set_split_bf16(1)
     try:
+        assert route().kernel == 'CK_T2_X3'
         y1 = run()
         L.jvae_conv2d_set_split_bf16(0)
+        assert route().kernel == 'CK_T2'
         y0 = run()
     finally:
         L.jvae_conv2d_set_split_bf16(old)
     assert y1.shape == ref.shape
     assert rel(y1, ref) < 3e-6 and rel(y0, ref) < 5e-6 and rel(y1, y0) < 5e-6
+    p1, p0 = cc.worst_plane(y1, ref, A), cc.worst_plane(y0, ref, A)             # every (image, channel) plane on its own scale
+    assert p1[0] < 3e-6 and p0[0] < 5e-6, (p1, p0)
 
 
 @pytest.mark.parametrize('N,cin,cout,H,s,tr', [(256, 32, 32, 32, 1, True), (256, 64, 32, 16, 1, True), (128, 64, 64, 8, 1, True),

@@ -315,6 +315,21 @@ int jvae_latent_bwd_f32(const float* mu, const float* lv_raw, const float* lv, c
                         float* gmu, float* glv_raw, float* gmeans, float* gT,
                         int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
                         int sampled, int has_forced, void* ws, size_t ws_bytes, void* stream);
+/* The same two calls with the warm-up weight in DEVICE memory: w_dev (1 float; NULL: `w` is used, which is what the two entry
+ * points above do) is read by the kernels instead of the launch argument, so a captured HIP graph of the training step follows
+ * a weight that changes from epoch to epoch.  Same arithmetic on the same fp32 value: bit-identical results. */
+int jvae_latent_fwd_wdev_f32(const float* mu, const float* lv_raw, const float* eps, const long long* y,
+                             const float* means, const float* T, const float* dict,
+                             float* lv, float* z, float* kl, float* zdist, float* var_kl, float* dzdist,
+                             int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
+                             int sampled, int has_forced, float forced_lv, const float* w_dev, void* stream);
+int jvae_latent_bwd_wdev_f32(const float* mu, const float* lv_raw, const float* lv, const float* eps, const long long* y,
+                             const float* means, const float* T,
+                             const float* gz, const float* g_kl, const float* g_zdist, const float* g_vkl,
+                             const float* gmu_direct, const float* glv_direct,
+                             float* gmu, float* glv_raw, float* gmeans, float* gT,
+                             int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
+                             int sampled, int has_forced, const float* w_dev, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- reconstruction term ---------------------------------------------------------------------------
  * wmse[l][n] = mean_D((x_reco[l+1][n] - x[n])^2) / sigma^2   (mse_loss, module/losses.py:8-27, called at
@@ -349,6 +364,14 @@ int jvae_elbo_fwd_f32(const float* wmse_s, const float* kl, const float* ce, con
 int jvae_elbo_bwd_f32(const float* g_wmse, const float* g_cx, const float* g_tot, const float* sigma, int sigma_is_log,
                       float* g_wmse_s, float* g_kl, float* g_ce, float* gsigma, int accumulate_sigma,
                       int L, int N, int D, float beta, float cw, void* ws, size_t ws_bytes, void* stream);
+/* ... with the weight of cross_y in DEVICE memory (cw_dev: 1 float; NULL: `cw`), as for the latent kernels above. */
+int jvae_elbo_fwd_wdev_f32(const float* wmse_s, const float* kl, const float* ce, const float* sigma, int sigma_is_log,
+                           float* wmse, float* cross_x, float* total, float* mse, int L, int N, int D, float beta, float cw,
+                           const float* cw_dev, void* stream);
+int jvae_elbo_bwd_wdev_f32(const float* g_wmse, const float* g_cx, const float* g_tot, const float* sigma, int sigma_is_log,
+                           float* g_wmse_s, float* g_kl, float* g_ce, float* gsigma, int accumulate_sigma,
+                           int L, int N, int D, float beta, float cw, const float* cw_dev, void* ws, size_t ws_bytes,
+                           void* stream);
 
 /* ---- nn.Dropout(p) of the dense trunks (module/vae_layers/layers.py:287-288, cvae.py:297-298), train mode:
  * y[i] = keep(seed, i) ? x[i] / (1 - p) : 0 with a counter-based mask (the backward pass calls it on dy with the same
@@ -376,6 +399,18 @@ int jvae_iws_f32(const float* wmse_s, const float* eps, const float* log_var, co
 int jvae_measures_f32(const float* sumsq_x, long nx, const float* wmse, const float* zdist, const float* var_kl, int N, int Nz,
                       const float* sigma, int sigma_is_log, const float* means, int C, int K, const int* flag,
                       const float* prev, int batch, float* out, void* stream);
+/* The same for a captured training step: the batch index is *counter (device int: read, then incremented by the kernel) and
+ * `run` (16 floats) is both `prev` and `out` - the running means continue from replay to replay with no host value in the
+ * launch.  Zero *counter at the start of an epoch (run is then ignored), or seed both from the last eager batch. */
+int jvae_measures_dev_f32(const float* sumsq_x, long nx, const float* wmse, const float* zdist, const float* var_kl, int N, int Nz,
+                          const float* sigma, int sigma_is_log, const float* means, int C, int K, const int* flag,
+                          float* run, int* counter, void* stream);
+
+/* ---- epoch sums of the batch-mean losses (the `acc += stack(means)` of the training loop, cvae.py:2463-2469) in ONE
+ * launch: acc[r] += mean(rows[r][0 .. lens[r])) for r < nrows <= 16.  rows / lens are HOST arrays (device pointers of the
+ * loss rows - (N,) or (L+1)*N floats each - and their lengths); acc: nrows device floats.  Fixed summation order, no
+ * atomics (fp64 partial sums: each mean is exact to one fp32 rounding). */
+int jvae_loss_sums_f32(const float* const* rows, const long* lens, int nrows, float* acc, void* stream);
 
 /* ---- classification term: per-row cross entropy, target y[r % N] (x_loss, module/losses.py:52-86) -- */
 int jvae_xent_fwd_f32(const float* logits, const long long* y, float* ce, int R, int N, int C, void* stream);

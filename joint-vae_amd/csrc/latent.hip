@@ -32,6 +32,8 @@ struct LatentP {
     int prior, var_dim;
     float tau, alpha;       // tilted: tau; uniform: tau and alpha = log(2 tau) - log(2 Phi(tau) - 1)
     float w;                // warm-up weight on var_kl
+    const float* w_dev;     // when not null: the weight is read from device memory instead (a captured step whose weight changes
+                            // from epoch to epoch; the same arithmetic on the same fp32 value, hence the same bits)
     float sampled;          // 0/1: is_sampled
     float forced_lv;        // used when has_forced
     int has_forced;
@@ -46,6 +48,7 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentP p, float* __res
     const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (n >= p.N) return;
     const int K = p.K;
+    const float w = p.w_dev ? p.w_dev[0] : p.w;
     const long long cls = p.y[n];
     const float* m = p.means + (long)cls * K;
     const long row = (long)n * K;
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentP p, float* __res
         u_nel = wave_sum(u_nel);
         const float vk = u_elogq + K * p.alpha;
         kl_v = fmaxf(u_elogq + u_nel, vk);
-        if (p.w != 1.f) kl_v += (p.w - 1.f) * vk;
+        if (w != 1.f) kl_v += (w - 1.f) * vk;
         vkl_v = 2.f * vk;
     } else if (p.prior == PRIOR_TILTED) {
         const float r = sqrtf(dist) - p.tau;
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentP p, float* __res
         if (p.var_dim == VAR_SCALAR) logdet_p = -2.f * K * __logf(p.T[cls]);
         else logdet_p = wave_sum(logdet_p);
         vkl_v = trace - logdet + logdet_p - (float)K;
-        kl_v = 0.5f * (dist + p.w * vkl_v);
+        kl_v = 0.5f * (dist + w * vkl_v);
     }
     if (lane == 0) {
         kl[n] = kl_v;
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float*
     const bool valid = n_raw < p.N;
     const int n = valid ? n_raw : p.N - 1;     // out-of-range waves shadow the last sample and store nothing
     const int K = p.K;
+    const float w = p.w_dev ? p.w_dev[0] : p.w;
     const long long cls = p.y[n];
     const float* m = p.means + (long)cls * K;
     const long row = (long)n * K;
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float*
     // gradient reaching `distance` and `var_kl` (gaussian) ...
     float g_dist = gd_in, g_var = gv_in;
     bool uni_first = true;          // uniform: which branch of the max() was taken
-    if (p.prior == PRIOR_GAUSS) { g_dist += 0.5f * gk; g_var += 0.5f * p.w * gk; }
+    if (p.prior == PRIOR_GAUSS) { g_dist += 0.5f * gk; g_var += 0.5f * w * gk; }
     else if (p.prior == PRIOR_TILTED) {
         float dist = 0.f;
         for (int k = lane; k < K; k += 64) { const float d = (p.mu[row + k] - m[k]) * p.T[cls]; dist += d * d; }
@@ -211,7 +215,7 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float*
             const float da = (lo > -1.f && lo < 1.f) ? 1.f : 0.f;   // d a_/d (d - span/2)
             const float db = (hi > -1.f && hi < 1.f) ? 1.f : 0.f;
             const float coef = p.alpha - 0.5f * c;
-            const float g_sum_elogq = (uni_first ? gk : 0.f) + (uni_first ? 0.f : gk) + (p.w - 1.f) * gk + 2.f * gv_in;
+            const float g_sum_elogq = (uni_first ? gk : 0.f) + (uni_first ? 0.f : gk) + (w - 1.f) * gk + 2.f * gv_in;
             const float g_nel = uni_first ? gk : 0.f;
             // nel = (c + d^2 + span^2/12)/2 + coef (b_-a_)/span - (b_^3 - a_^3)/(6 span)
             const float dnel_da = -coef / span + a_ * a_ / (2.f * span);
@@ -362,7 +366,7 @@ __global__ __launch_bounds__(256) void uniform_terms_kernel(LatentP p, const flo
 
 bool fill(LatentP* p, const float* mu, const float* lv_raw, const float* eps, const long long* y, const float* means,
           const float* T, const float* dict, int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha,
-          float w, int sampled, int has_forced, float forced_lv) {
+          float w, int sampled, int has_forced, float forced_lv, const float* w_dev = nullptr) {
     if (!mu || !y || !means || N < 0 || K <= 0 || L < 0 || C <= 0) return false;
     if (prior < 0 || prior > 2 || var_dim < 0 || var_dim > 2) return false;
     if (prior != PRIOR_UNIFORM && !T) return false;
@@ -370,7 +374,7 @@ bool fill(LatentP* p, const float* mu, const float* lv_raw, const float* eps, co
     if (!has_forced && !lv_raw) return false;
     p->mu = mu; p->lv_raw = lv_raw; p->eps = eps; p->y = y; p->means = means; p->T = T; p->dict = dict;
     p->N = N; p->K = K; p->L = L; p->C = C; p->prior = prior; p->var_dim = var_dim; p->tau = tau; p->alpha = alpha;
-    p->w = w; p->sampled = sampled ? 1.f : 0.f; p->has_forced = has_forced; p->forced_lv = forced_lv;
+    p->w = w; p->w_dev = w_dev; p->sampled = sampled ? 1.f : 0.f; p->has_forced = has_forced; p->forced_lv = forced_lv;
     return true;
 }
 
@@ -385,13 +389,15 @@ int jvae_dict_stats_f32(const float* means, float* dict, int C, int K, void* str
     return 0;
 }
 
-int jvae_latent_fwd_f32(const float* mu, const float* lv_raw, const float* eps, const long long* y,
-                        const float* means, const float* T, const float* dict,
-                        float* lv, float* z, float* kl, float* zdist, float* var_kl, float* dzdist,
-                        int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
-                        int sampled, int has_forced, float forced_lv, void* stream) {
+// w_dev (may be null): one float in device memory that replaces `w` (jvae_latent_fwd_f32 passes null)
+int jvae_latent_fwd_wdev_f32(const float* mu, const float* lv_raw, const float* eps, const long long* y,
+                             const float* means, const float* T, const float* dict,
+                             float* lv, float* z, float* kl, float* zdist, float* var_kl, float* dzdist,
+                             int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
+                             int sampled, int has_forced, float forced_lv, const float* w_dev, void* stream) {
     LatentP p;
-    if (!fill(&p, mu, lv_raw, eps, y, means, T, dict, N, K, L, C, prior, var_dim, tau, alpha, w, sampled, has_forced, forced_lv))
+    if (!fill(&p, mu, lv_raw, eps, y, means, T, dict, N, K, L, C, prior, var_dim, tau, alpha, w, sampled, has_forced, forced_lv,
+              w_dev))
         return JVAE_EINVAL;
     if (!eps || !lv || !z || !kl || !zdist || !var_kl) return JVAE_EINVAL;
     if (N == 0) return 0;
@@ -400,16 +406,26 @@ int jvae_latent_fwd_f32(const float* mu, const float* lv_raw, const float* eps, 
     return 0;
 }
 
-// ws: 4*N + 2*N*K floats cover every mode (uniform terms, mean contributions, T contributions)
-int jvae_latent_bwd_f32(const float* mu, const float* lv_raw, const float* lv, const float* eps, const long long* y,
-                        const float* means, const float* T,
-                        const float* gz, const float* g_kl, const float* g_zdist, const float* g_vkl,
-                        const float* gmu_direct, const float* glv_direct,
-                        float* gmu, float* glv_raw, float* gmeans, float* gT,
+int jvae_latent_fwd_f32(const float* mu, const float* lv_raw, const float* eps, const long long* y,
+                        const float* means, const float* T, const float* dict,
+                        float* lv, float* z, float* kl, float* zdist, float* var_kl, float* dzdist,
                         int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
-                        int sampled, int has_forced, void* ws, size_t ws_bytes, void* stream) {
+                        int sampled, int has_forced, float forced_lv, void* stream) {
+    return jvae_latent_fwd_wdev_f32(mu, lv_raw, eps, y, means, T, dict, lv, z, kl, zdist, var_kl, dzdist, N, K, L, C, prior,
+                                    var_dim, tau, alpha, w, sampled, has_forced, forced_lv, nullptr, stream);
+}
+
+// ws: 4*N + 2*N*K floats cover every mode (uniform terms, mean contributions, T contributions)
+int jvae_latent_bwd_wdev_f32(const float* mu, const float* lv_raw, const float* lv, const float* eps, const long long* y,
+                             const float* means, const float* T,
+                             const float* gz, const float* g_kl, const float* g_zdist, const float* g_vkl,
+                             const float* gmu_direct, const float* glv_direct,
+                             float* gmu, float* glv_raw, float* gmeans, float* gT,
+                             int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
+                             int sampled, int has_forced, const float* w_dev, void* ws, size_t ws_bytes, void* stream) {
     LatentP p;
-    if (!fill(&p, mu, lv_raw, eps, y, means, T, nullptr, N, K, L, C, prior, var_dim, tau, alpha, w, sampled, has_forced, 0.f))
+    if (!fill(&p, mu, lv_raw, eps, y, means, T, nullptr, N, K, L, C, prior, var_dim, tau, alpha, w, sampled, has_forced, 0.f,
+              w_dev))
         return JVAE_EINVAL;
     if (!lv || !gmu || !glv_raw || (gz && !eps)) return JVAE_EINVAL;
     if (N == 0) return 0;
@@ -453,6 +469,18 @@ int jvae_latent_bwd_f32(const float* mu, const float* lv_raw, const float* lv, c
         JVAE_LAUNCH_CHECK();
     }
     return 0;
+}
+
+int jvae_latent_bwd_f32(const float* mu, const float* lv_raw, const float* lv, const float* eps, const long long* y,
+                        const float* means, const float* T,
+                        const float* gz, const float* g_kl, const float* g_zdist, const float* g_vkl,
+                        const float* gmu_direct, const float* glv_direct,
+                        float* gmu, float* glv_raw, float* gmeans, float* gT,
+                        int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
+                        int sampled, int has_forced, void* ws, size_t ws_bytes, void* stream) {
+    return jvae_latent_bwd_wdev_f32(mu, lv_raw, lv, eps, y, means, T, gz, g_kl, g_zdist, g_vkl, gmu_direct, glv_direct, gmu,
+                                    glv_raw, gmeans, gT, N, K, L, C, prior, var_dim, tau, alpha, w, sampled, has_forced,
+                                    nullptr, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -156,9 +156,11 @@ __global__ __launch_bounds__(256) void elbo_fwd_kernel(const float* __restrict__
                                                        const float* __restrict__ ce, const float* __restrict__ sigma,
                                                        int sigma_mode, float* __restrict__ wmse, float* __restrict__ cross_x,
                                                        float* __restrict__ total, float* __restrict__ mse,
-                                                       int L, int N, float D, float beta, float cw) {
+                                                       int L, int N, float D, float beta, float cw,
+                                                       const float* __restrict__ cw_dev) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
+    if (cw_dev) cw = cw_dev[0];             // the weight of cross_y from device memory (a captured step): same value, same bits
     float s = 0.f;
     for (int l = 0; l < L; ++l) s += wmse_s[(long)l * N + n];
     s /= L;
@@ -188,9 +190,11 @@ __global__ __launch_bounds__(256) void elbo_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ g_tot, const float* __restrict__ sigma,
                                                        int sigma_mode, float* __restrict__ g_wmse_s, float* __restrict__ g_kl,
                                                        float* __restrict__ g_ce, float* __restrict__ gsig_part,
-                                                       int L, int N, float D, float beta, float cw) {
+                                                       int L, int N, float D, float beta, float cw,
+                                                       const float* __restrict__ cw_dev) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
+    if (cw_dev) cw = cw_dev[0];
     const float gt = g_tot ? g_tot[n] : 0.f;
     const float gc = (g_cx ? g_cx[n] : 0.f) + gt;
     float gw;
@@ -217,8 +221,10 @@ __global__ __launch_bounds__(256) void measures_kernel(const float* __restrict__
                                                        const float* __restrict__ var_kl, int N, int Nz,
                                                        const float* __restrict__ sigma, int sigma_is_log,
                                                        const float* __restrict__ means, int C, int K,
-                                                       const int* __restrict__ flag, const float* __restrict__ prev,
-                                                       int batch, float* __restrict__ out) {
+                                                       const int* __restrict__ flag, const float* prev,
+                                                       int batch, float* out, int* __restrict__ counter) {
+    // prev / out carry no __restrict__: the device-counter form (jvae_measures_dev_f32) passes ONE buffer for both - thread 0
+    // reads the four running means of the previous call before it overwrites them (every store below depends on its load)
     __shared__ float red[17];
     const int tid = threadIdx.x;
     // sigma_mode 0 / 1: `wmse` holds wmse, sigma the (log) value; >= 2 (coded / rmse sigma): `wmse` holds the per-sample
@@ -274,6 +280,7 @@ __global__ __launch_bounds__(256) void measures_kernel(const float* __restrict__
         }
     }
     if (tid == 0) {
+        if (counter) batch = counter[0];       // batches seen so far in this epoch, kept on the device (captured step)
         const float mse = a / N * mse_scale;
         out[0] = sg;
         out[1] = sumsq_x[0] / nx;
@@ -297,7 +304,35 @@ __global__ __launch_bounds__(256) void measures_kernel(const float* __restrict__
         out[13] = 10.f * log10f(rxp / rms);
         out[14] = (pzd * nb + out[4]) * inv;
         out[15] = (pvk * nb + out[5]) * inv;
+        if (counter) counter[0] = batch + 1;
     }
+}
+
+// ---- running sums of the step's loss means (train_model's captured step): ONE launch, one block per loss row -------------
+// acc[r] += mean(rows[r][0 .. len[r])).  Each thread sums its stride of the row in fp64, the 256 partial sums are folded by a
+// fixed LDS tree: no atomics, the same bits from run to run (the order differs from torch.mean's; the fp64 partial sums make
+// the mean correct to one fp32 rounding whatever the row's length).
+#define JVAE_LOSS_ROWS_MAX 16
+struct LossRows {
+    const float* p[JVAE_LOSS_ROWS_MAX];
+    long n[JVAE_LOSS_ROWS_MAX];
+};
+
+__global__ __launch_bounds__(256) void loss_sums_kernel(LossRows rows, float* __restrict__ acc) {
+    __shared__ double part[256];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ v = rows.p[r];
+    const long len = rows.n[r];
+    double s = 0.0;
+    for (long i = tid; i < len; i += 256) s += (double)v[i];
+    part[tid] = s;
+    __syncthreads();
+#pragma unroll
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) part[tid] += part[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) acc[r] += (float)(part[0] / (double)len);
 }
 
 inline int ew_grid(long n) {
@@ -468,30 +503,38 @@ int jvae_act_bwd_f32(const float* dy, const float* y, float* dx, long n, int kin
     return 0;
 }
 
-int jvae_elbo_fwd_f32(const float* wmse_s, const float* kl, const float* ce, const float* sigma, int sigma_is_log,
-                      float* wmse, float* cross_x, float* total, float* mse, int L, int N, int D, float beta, float cw,
-                      void* stream) {
+// cw_dev (may be null): one float in device memory that replaces `cw` (jvae_elbo_fwd_f32 passes null)
+int jvae_elbo_fwd_wdev_f32(const float* wmse_s, const float* kl, const float* ce, const float* sigma, int sigma_is_log,
+                           float* wmse, float* cross_x, float* total, float* mse, int L, int N, int D, float beta, float cw,
+                           const float* cw_dev, void* stream) {
     if (!wmse_s || !kl || !sigma || !wmse || !cross_x || !total || L < 1 || N < 0 || D <= 0) return JVAE_EINVAL;
     if (sigma_is_log < 0 || sigma_is_log > 3) return JVAE_EINVAL;
     if (N == 0) return 0;
     hipLaunchKernelGGL(elbo_fwd_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, wmse_s, kl, ce, sigma,
-                       sigma_is_log, wmse, cross_x, total, mse, L, N, (float)D, beta, cw);
+                       sigma_is_log, wmse, cross_x, total, mse, L, N, (float)D, beta, cw, cw_dev);
     JVAE_LAUNCH_CHECK();
     return 0;
 }
 
+int jvae_elbo_fwd_f32(const float* wmse_s, const float* kl, const float* ce, const float* sigma, int sigma_is_log,
+                      float* wmse, float* cross_x, float* total, float* mse, int L, int N, int D, float beta, float cw,
+                      void* stream) {
+    return jvae_elbo_fwd_wdev_f32(wmse_s, kl, ce, sigma, sigma_is_log, wmse, cross_x, total, mse, L, N, D, beta, cw, nullptr, stream);
+}
+
 // gsigma (may be null): modes 0 / 1: 1 float = sum_n (g_cx + g_tot) * D [/ sigma]; mode 2: N floats, ADDED to when
 // accumulate_sigma; mode 3: must be null and `sigma` points to the forward's wmse_s (L,N).  ws: N floats when gsigma != null
-int jvae_elbo_bwd_f32(const float* g_wmse, const float* g_cx, const float* g_tot, const float* sigma, int sigma_is_log,
-                      float* g_wmse_s, float* g_kl, float* g_ce, float* gsigma, int accumulate_sigma,
-                      int L, int N, int D, float beta, float cw, void* ws, size_t ws_bytes, void* stream) {
+int jvae_elbo_bwd_wdev_f32(const float* g_wmse, const float* g_cx, const float* g_tot, const float* sigma, int sigma_is_log,
+                           float* g_wmse_s, float* g_kl, float* g_ce, float* gsigma, int accumulate_sigma,
+                           int L, int N, int D, float beta, float cw, const float* cw_dev, void* ws, size_t ws_bytes,
+                           void* stream) {
     if (!sigma || !g_wmse_s || L < 1 || N < 0 || D <= 0) return JVAE_EINVAL;
     if (sigma_is_log < 0 || sigma_is_log > 3 || (sigma_is_log == SIG_RMSE && gsigma)) return JVAE_EINVAL;
     if (gsigma && (!ws || ws_bytes < sizeof(float) * (size_t)N)) return JVAE_EWORKSPACE;
     if (N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(elbo_bwd_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, g_wmse, g_cx, g_tot, sigma, sigma_is_log,
-                       g_wmse_s, g_kl, g_ce, gsigma ? (float*)ws : nullptr, L, N, (float)D, beta, cw);
+                       g_wmse_s, g_kl, g_ce, gsigma ? (float*)ws : nullptr, L, N, (float)D, beta, cw, cw_dev);
     JVAE_LAUNCH_CHECK();
     if (gsigma && sigma_is_log == SIG_CODED) {
         hipLaunchKernelGGL(rows_fold_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, (const float*)ws, gsigma, 1, N, accumulate_sigma);
@@ -501,6 +544,13 @@ int jvae_elbo_bwd_f32(const float* g_wmse, const float* g_cx, const float* g_tot
         JVAE_LAUNCH_CHECK();
     }
     return 0;
+}
+
+int jvae_elbo_bwd_f32(const float* g_wmse, const float* g_cx, const float* g_tot, const float* sigma, int sigma_is_log,
+                      float* g_wmse_s, float* g_kl, float* g_ce, float* gsigma, int accumulate_sigma,
+                      int L, int N, int D, float beta, float cw, void* ws, size_t ws_bytes, void* stream) {
+    return jvae_elbo_bwd_wdev_f32(g_wmse, g_cx, g_tot, sigma, sigma_is_log, g_wmse_s, g_kl, g_ce, gsigma, accumulate_sigma, L, N, D,
+                                  beta, cw, nullptr, ws, ws_bytes, stream);
 }
 
 // forward (x -> y) and backward (dy -> dx) are the same masked scaling for the same seed
@@ -545,7 +595,38 @@ int jvae_measures_f32(const float* sumsq_x, long nx, const float* wmse, const fl
     if (!sumsq_x || !wmse || !zdist || !var_kl || !sigma || !out || N <= 0 || Nz <= 0 || nx <= 0) return JVAE_EINVAL;
     if (means && (C <= 0 || K <= 0 || C > 1024)) return JVAE_EINVAL;
     hipLaunchKernelGGL(measures_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sumsq_x, (float)nx, wmse, zdist, var_kl,
-                       N, Nz, sigma, sigma_is_log, means, C, K, flag, prev, batch, out);
+                       N, Nz, sigma, sigma_is_log, means, C, K, flag, prev, batch, out, (int*)nullptr);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same measures for a captured step: the batch index is read from *counter (device int, incremented by the kernel) and
+// `run` (16 floats) is both the previous call's result and this call's: the running means continue from replay to replay
+// without a host value in the launch.  The caller zeroes *counter at the start of an epoch (the content of `run` is ignored
+// at batch 0) or seeds both from the last eager batch.
+int jvae_measures_dev_f32(const float* sumsq_x, long nx, const float* wmse, const float* zdist, const float* var_kl, int N, int Nz,
+                          const float* sigma, int sigma_is_log, const float* means, int C, int K, const int* flag,
+                          float* run, int* counter, void* stream) {
+    if (!sumsq_x || !wmse || !zdist || !var_kl || !sigma || !run || !counter || N <= 0 || Nz <= 0 || nx <= 0) return JVAE_EINVAL;
+    if (means && (C <= 0 || K <= 0 || C > 1024)) return JVAE_EINVAL;
+    hipLaunchKernelGGL(measures_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sumsq_x, (float)nx, wmse, zdist, var_kl,
+                       N, Nz, sigma, sigma_is_log, means, C, K, flag, (const float*)run, 0, run, counter);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// acc[r] += mean(rows[r][0 .. lens[r])) for r < nrows <= 16, in ONE launch.  `rows` / `lens`: HOST arrays (device pointers of
+// the rows, their lengths > 0); acc: nrows floats on the device.  Deterministic (see loss_sums_kernel).
+int jvae_loss_sums_f32(const float* const* rows, const long* lens, int nrows, float* acc, void* stream) {
+    if (nrows < 0 || nrows > JVAE_LOSS_ROWS_MAX || (nrows > 0 && (!rows || !lens || !acc))) return JVAE_EINVAL;
+    if (nrows == 0) return 0;
+    LossRows t;
+    for (int r = 0; r < JVAE_LOSS_ROWS_MAX; ++r) {
+        t.p[r] = r < nrows ? rows[r] : nullptr;
+        t.n[r] = r < nrows ? lens[r] : 0;
+        if (r < nrows && (!rows[r] || lens[r] <= 0)) return JVAE_EINVAL;
+    }
+    hipLaunchKernelGGL(loss_sums_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, t, acc);
     JVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -172,6 +172,20 @@ class ClassificationVariationalNetwork(nn.Module):
             methods_params['odin'].append('odin-{:.0f}-{:.4f}'.format(_T, _e))
     del _T, _k, _e
 
+    # train_model(): run every full-size batch of the train phase as a replay of ONE captured HIP graph (zero_grad ... Adam,
+    # the epoch's loss sums and running measures included) instead of the eager train_step().  Opt-in; an instance may set
+    # it.  What stays eager, and the late NaN exit: INTEGRATION.md ("The captured training loop").
+    TRAIN_CAPTURED = False
+    # full-size eager batches in front of every capture (allocations, the optimiser's flat buffers, lazy initialisations):
+    # they are real batches of the epoch run through train_step() - a capture costs no extra optimiser step
+    CAPTURE_WARMUP_BATCHES = 2
+    # test hook: when set, train_model() calls it after every batch, on both paths, as hook(epoch, i, x, y, eps, losses) with
+    # the loop's own tensors (captured path: the graph's buffers, overwritten by the next replay - clone what you keep;
+    # eps: the (L, N, K) noise encode() returned).  It exists so that tests can replay the very batches of a run through
+    # train_step(); it is not part of the reference's interface.
+    _train_batch_hook = None
+    _captures_built = 0             # how many captured steps this model has built (capture_train_step)
+
     def __init__(self, input_shape, num_labels, type='cvae', y_is_coded=False, output_distribution='gaussian',
                  job_number=0, features=None, pretrained_features=None, batch_norm=False, dropout=False,
                  encoder=[36], latent_dim=32, prior={}, beta=1., gamma=0., decoder=[36], upsampler=None,
@@ -592,7 +606,8 @@ class ClassificationVariationalNetwork(nn.Module):
         if y is None or self.is_vib:
             if self.is_vib:
                 return self._evaluate_vib(x, y, batch, current_measures, with_beta, kl_var_weighting, gamma_weighting,
-                                          z_output, epsilon, kw.get('_raw_measures'))
+                                          z_output, epsilon, kw.get('_raw_measures'), kw.get('_dev_weights'),
+                                          kw.get('_dev_state'))
             return self._evaluate_all_classes(x, batch, current_measures, with_beta, z_output, epsilon)
         if x.dim() != self.input_dim + 1:
             x = x.reshape(-1, *self.input_shape)
@@ -607,6 +622,14 @@ class ClassificationVariationalNetwork(nn.Module):
             else:
                 cross_y_weight = gamma_weighting * self.gamma
 
+        # captured step of train_model(): the two warm-up weights as device scalars ([kl_var_weighting, cross_y weight]; the
+        # host values above only decide WHETHER cross_y is in the loss) and the running measures / batch counter on the device
+        dev_weights, dev_state = kw.get('_dev_weights'), kw.get('_dev_state')
+        cw = cross_y_weight
+        if dev_weights is not None:
+            kl_var_weighting = dev_weights[0:1]
+            cw = dev_weights[1:2] if cross_y_weight else cross_y_weight
+
         feats = self._features_of(x).reshape(N, -1)
         y1h = onehot_encoding(y, self.num_labels).float() if self.y_is_coded else None
         try:
@@ -614,6 +637,7 @@ class ClassificationVariationalNetwork(nn.Module):
         except ValueError as err:
             self._dump_after_encoder_error(err, x, y)
             raise
+        self._last_epsilon = eps
         if self.training and self.optimizer._world > 1 and z.requires_grad and not getattr(self, '_graph_capture', False) \
                 and not getattr(self.optimizer, '_external_reduce', False):
             # data-parallel: the decoder's gradients are final once d(loss)/dz exists -> start their all-reduce there
@@ -638,11 +662,12 @@ class ClassificationVariationalNetwork(nn.Module):
             cross_x = ce_x.mean(0)
             total = cross_x + (self.beta if with_beta else 1.) * terms['kl']
             if cross_y_weight:
-                total = total + cross_y_weight * ce
+                total = total + cw * ce
         else:
             wmse_s = ops.recon_wmse(x_reco, x, s, s_kind, snapshot=bool(self.training and self.sigma.decay))     # (L, N)
             wmse, cross_x, total, mse = ops.elbo(wmse_s, terms['kl'], ce if cross_y_weight else None, s, s_kind, D,
-                                                 self.beta if with_beta else 1., float(cross_y_weight or 0.), with_mse=True)
+                                                 self.beta if with_beta else 1.,
+                                                 cw if torch.is_tensor(cw) else float(cross_y_weight or 0.), with_mse=True)
         losses = {'kl': terms['kl'], 'zdist': terms['distance'], 'var_kl': terms['var_kl']}
         dictionary = self.encoder.prior.mean if self.encoder.prior.conditional else None
         if dictionary is not None:
@@ -655,7 +680,8 @@ class ClassificationVariationalNetwork(nn.Module):
 
         prev = current_measures._dev if isinstance(current_measures, Measures) else self._upload_measures(
             current_measures, x.device) if (current_measures and batch) else None
-        packed = self._pack_measures(x, wmse, terms, dictionary, prev, batch, mse=mse, sigma_rms=sigma_rms, sigma_t=s)
+        packed = self._pack_measures(x, wmse, terms, dictionary, prev, batch, mse=mse, sigma_rms=sigma_rms, sigma_t=s,
+                                     dev_state=dev_state)
         if self.training:
             if self.sigma.decay and not self.sigma.learned:                  # the decay rule computes with the rmse now
                 from jvae_hip import lib as _lib
@@ -675,7 +701,7 @@ class ClassificationVariationalNetwork(nn.Module):
 
     # ------------------------------------------------------------------------------------ type 'vib'
     def _evaluate_vib(self, x, y, batch, current_measures, with_beta, kl_var_weighting, gamma_weighting, z_output, epsilon,
-                      raw_measures=False):
+                      raw_measures=False, dev_weights=None, dev_state=None):
         """evaluate() of a model WITHOUT decoder (type 'vib': cvae.py:189,201,490-505,891-896): the loss is the classifier's
         cross entropy on z plus beta x the KL to the single prior; the returned `reconstruction` is x itself.  With labels:
         every loss (N,); without (the evaluation path): cross_y and total are (C, N) - one row per candidate class
@@ -685,6 +711,9 @@ class ClassificationVariationalNetwork(nn.Module):
             y = None if y is None else y.reshape(-1)
         N = x.shape[0]
         cross_y_weight = gamma_weighting * self.gamma                                   # cvae.py:557-563: always in the loss
+        cw = cross_y_weight
+        if dev_weights is not None:              # captured step of train_model(): the weights as device scalars (see _evaluate)
+            kl_var_weighting, cw = dev_weights[0:1], dev_weights[1]
         with torch.set_grad_enabled(torch.is_grad_enabled() and y is not None):
             feats = self._features_of(x).reshape(N, -1)
             dummy = y if y is not None else torch.zeros(N, dtype=torch.int64, device=x.device)
@@ -693,13 +722,14 @@ class ClassificationVariationalNetwork(nn.Module):
             except ValueError as err:
                 self._dump_after_encoder_error(err, x, y)
                 raise
+            self._last_epsilon = eps
             _, logits = self._decode(z)
             ce = x_loss(y, logits, batch_mean=False)                                     # (N,) or (C, N); all L+1 rows
             beta = self.beta if with_beta else 1.
             losses = {'kl': terms['kl'], 'zdist': terms['distance'], 'var_kl': terms['var_kl']}
             total = beta * terms['kl']
             if cross_y_weight:
-                total = total + cross_y_weight * ce                                     # broadcasts to (C, N) without labels
+                total = total + cw * ce                                                 # broadcasts to (C, N) without labels
             elif y is None:
                 total = total.unsqueeze(0).expand_as(ce)
             losses['total'] = total
@@ -708,7 +738,7 @@ class ClassificationVariationalNetwork(nn.Module):
             current_measures, x.device) if (current_measures and batch) else None
         with torch.no_grad():
             packed = self._pack_measures_raw(x, torch.zeros(N, device=x.device), terms, None, prev, batch, self.sigma.detach(),
-                                             int(self.sigma.is_log))
+                                             int(self.sigma.is_log), dev_state=dev_state)
         keys = ('sigma', 'zdist', 'var_kl')
         measures = (packed, False) if raw_measures else Measures(packed, False, _grad_nan_exit, only=keys)
         out = (x, _mean_over_draws(logits), losses, measures)
@@ -1460,7 +1490,7 @@ class ClassificationVariationalNetwork(nn.Module):
         sg.update(v=per_sample.detach())
         return per_sample.reshape(N), ops.SIGMA_CODED, rms
 
-    def _pack_measures(self, x, wmse, terms, dictionary, prev, batch, mse=None, sigma_rms=None, sigma_t=None):
+    def _pack_measures(self, x, wmse, terms, dictionary, prev, batch, mse=None, sigma_rms=None, sigma_t=None, dev_state=None):
         """Every scalar evaluate() reports, computed by one kernel into one 16-float device buffer."""
         if sigma_rms is not None:
             if self.sigma.coded:
@@ -1468,11 +1498,11 @@ class ClassificationVariationalNetwork(nn.Module):
                 # that - the only use of `mse` with a coded sigma - is mean(wmse) * mean(sigma^2), reproduced here
                 with torch.no_grad():
                     mse = (wmse.detach().mean() * (2 * sigma_t.detach()).exp().mean()).expand(wmse.numel()).contiguous()
-            return self._pack_measures_raw(x, mse.detach(), terms, dictionary, prev, batch, sigma_rms, 2)
+            return self._pack_measures_raw(x, mse.detach(), terms, dictionary, prev, batch, sigma_rms, 2, dev_state=dev_state)
         return self._pack_measures_raw(x, wmse.detach(), terms, dictionary, prev, batch, self.sigma.detach(),
-                                       int(self.sigma.is_log))
+                                       int(self.sigma.is_log), dev_state=dev_state)
 
-    def _pack_measures_raw(self, x, wmse, terms, dictionary, prev, batch, sigma_t, sigma_kind):
+    def _pack_measures_raw(self, x, wmse, terms, dictionary, prev, batch, sigma_t, sigma_kind, dev_state=None):
         from jvae_hip import lib as _lib
         with torch.no_grad():
             if getattr(self, '_scratch', None) is None or self._scratch.device != x.device:
@@ -1482,8 +1512,9 @@ class ClassificationVariationalNetwork(nn.Module):
             side.wait_stream(main)
             args = (x, wmse, terms['distance'].detach(), terms['var_kl'].detach(), sigma_t)
             with torch.cuda.stream(side):
+                run, counter = dev_state if dev_state is not None else (None, None)      # captured step: see ops.measures
                 packed = ops.measures(*args, sigma_kind, None if dictionary is None else dictionary.detach(),
-                                      self.optimizer.nonfinite_flag(), self._scratch, prev, batch)
+                                      self.optimizer.nonfinite_flag(), self._scratch, prev, batch, run=run, counter=counter)
             for t in args:
                 t.record_stream(side)
             return packed
@@ -1603,6 +1634,242 @@ class ClassificationVariationalNetwork(nn.Module):
         step.graph = graph
         step.constants = (self._mean_grad,)             # the captured graph reads it: alive as long as the step is
         return step
+
+    # ---- the captured step of train_model() (TRAIN_CAPTURED) ----------------------------------------------------------
+    def _capture_buffers(self, device):
+        """The device words a captured step shares with the loop, in ONE 40-float block so that one copy reads them all back:
+        [0:16] the measures (running means included), [16:32] the epoch sums of the batch-mean losses, [32] the optimiser's
+        non-finite flag (an int32 in place); next to it the batch counter (int32) and the two warm-up weights."""
+        b = getattr(self, '_capt_bufs', None)
+        if b is None or b['state'].device != device:
+            state = torch.zeros(40, device=device, dtype=torch.float32)
+            b = self._capt_bufs = {'state': state, 'run': state[0:16], 'sums': state[16:32],
+                                   'flag': state.view(torch.int32)[32:33],
+                                   'counter': torch.zeros(1, device=device, dtype=torch.int32),
+                                   'weights': torch.ones(2, device=device, dtype=torch.float32)}
+        opt = self.optimizer
+        if opt._flag is None or opt._flag.data_ptr() != b['flag'].data_ptr():
+            if opt._flag is not None and opt._flag.device == device:
+                b['flag'].copy_(opt._flag)           # the update kernels raise the flag inside the block from now on
+            else:
+                b['flag'].zero_()
+            opt._flag = b['flag']
+        return b
+
+    def _capture_key(self, x, y, cross_y_on):
+        """What a captured step is valid for: the batch's shape, the set of trainable parameters and where they (and the
+        optimiser's device words) live, the number of latent draws, whether cross_y is part of the loss.  The learning rate
+        and the warm-up weights are NOT in it: they are device words the replay reads."""
+        opt = self.optimizer
+        return (tuple(x.shape), str(x.dtype), tuple(y.shape), str(x.device), self.latent_sampling, bool(cross_y_on),
+                getattr(self, 'compute_dtype', 'fp32'),
+                tuple((id(p), p.data_ptr()) for p in self.parameters() if p.requires_grad),
+                tuple((g.p.data_ptr(), getattr(g, 'hyper', None) is not None and g.hyper.data_ptr()) for g in opt._groups),
+                None if opt._flag is None else opt._flag.data_ptr())
+
+    def _cross_y_on(self, gamma_weighting):
+        if not self.y_is_decoded:
+            return False
+        return bool(gamma_weighting * self.gamma)
+
+    def capture_train_step(self, x, y, kl_var_weighting=1., gamma_weighting=1.):
+        """The captured step train_model() replays (TRAIN_CAPTURED): sibling of graph_train_step() that is fit for a loop.
+        * NO optimiser step is taken here: the caller has run its eager warm-up (CAPTURE_WARMUP_BATCHES real batches through
+          train_step(), with optimizer.enable_device_hyper(True)); capture executes nothing and the host step count is rolled
+          back.
+        * kl_var_weighting and the cross_y weight (gamma_weighting * gamma) are read by the latent and ELBO kernels from a
+          device buffer (`step.set_weights()`); the values given here only seed it.
+        * the running measures continue from replay to replay: the batch index is a device counter the measures kernel
+          increments (`step.seed_measures(prev, batch)` / `step.reset_epoch()`).
+        * the step's last launch adds the mean of every loss row to the running sums (ops.loss_sums).
+        * `step.epsilon`: the (L, N, K) noise of the replay that has just run; `step.losses`: the graph's loss rows.
+        step(x, y) copies the batch in, replays and returns `step.losses`.  Single process only."""
+        if getattr(self.optimizer, '_world', 1) > 1:
+            raise NotImplementedError('capture_train_step() is single-process: data-parallel models use graph_train_step()')
+        if self.optimizer.kind != 'adam':
+            raise NotImplementedError('capture_train_step() needs the device-side hyper-parameters of the Adam kernel')
+        if not getattr(self.optimizer, '_device_hyper', False) or not self.optimizer._groups \
+                or any(getattr(g, 'hyper', None) is None for g in self.optimizer._groups):
+            raise RuntimeError('capture_train_step(): run the eager warm-up steps with optimizer.enable_device_hyper(True) first')
+        dev = x.device
+        bufs = self._capture_buffers(dev)
+        net, opt = self, self.optimizer
+        sx, sy = x.clone(), y.clone()
+        keys = []
+
+        def body():
+            opt.zero_grad()
+            _, _, losses, _ = net.evaluate(sx, sy, batch=0, with_beta=True, kl_var_weighting=kl_var_weighting,
+                                           gamma_weighting=gamma_weighting, _raw_measures=True,
+                                           _dev_weights=bufs['weights'], _dev_state=(bufs['run'], bufs['counter']))
+            net._mean_backward(losses['total'])         # (its constant was created by the eager warm-up, not captured)
+            opt.clip(net.parameters())
+            opt.step()
+            keys.extend(losses)
+            ops.loss_sums([losses[k] for k in keys], bufs['sums'])      # the step's last launch
+            return losses
+
+        was_training = self.training
+        self.train()
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(graph):
+                losses = body()
+        finally:
+            self.train(was_training)
+        for g in opt._groups:                           # the capture pass advanced the host counter without executing
+            g.step -= 1
+        self._captures_built = self._captures_built + 1
+
+        def step(xb, yb):
+            sx.copy_(xb, non_blocking=True)
+            sy.copy_(yb, non_blocking=True)
+            graph.replay()
+            opt.note_replayed_step()
+            return losses
+
+        def set_weights(kl_w, gamma_w):
+            cw = gamma_w * net.gamma if net.y_is_decoded else 0.
+            bufs['weights'].copy_(torch.tensor([float(kl_w), float(cw or 0.)], dtype=torch.float32))
+
+        def seed_measures(prev, batch):
+            """Continue after `batch` eager batches whose last measures buffer (16 device floats) is `prev`."""
+            bufs['run'].copy_(prev)
+            bufs['counter'].fill_(int(batch))
+
+        def reset_epoch():
+            bufs['counter'].zero_()
+            bufs['sums'].zero_()
+
+        set_weights(kl_var_weighting, gamma_weighting)
+        step.graph, step.losses, step.keys, step.epsilon = graph, losses, keys, self._last_epsilon
+        step.buffers, step.x, step.y = bufs, sx, sy
+        step.set_weights, step.seed_measures, step.reset_epoch = set_weights, seed_measures, reset_epoch
+        step.has_dictionary = self.encoder.prior.conditional
+        # what the graph reads besides the model: alive as long as the step is
+        step.constants = (self._mean_grad, [g.hyper for g in opt._groups], opt._sqnorm, getattr(self, '_scratch', None))
+        step.key = self._capture_key(x, y, self._cross_y_on(gamma_weighting))
+        return step
+
+    def _read_captured_state(self, bufs):
+        """THE read-back of the captured loop: measures, loss sums and the non-finite flag in one copy (it synchronises).
+        A NaN / Inf parameter ends the run here, as _grad_nan_exit() does on the eager path."""
+        h = bufs['state'].tolist()
+        if h[32] != 0 or h[9] != 0:
+            _grad_nan_exit()
+        return h
+
+    def _measures_from_host(self, h, has_dictionary):
+        m = {'sigma': h[0], 'xpow': h[10], 'mse': h[11], 'rmse': h[12], 'dB': h[13], 'zdist': h[14], 'var_kl': h[15]}
+        if has_dictionary:
+            m.update({'ld-norm': h[6], 'imut-zy': h[7], 'd-mind': h[8]})
+        if self.is_vib:
+            m = {k: m[k] for k in ('sigma', 'zdist', 'var_kl')}
+        return m
+
+    def _train_epoch_eager(self, batches, epoch, epochs, batch_size, w_kl, w_gamma, outputs, report_every):
+        """The train phase of one epoch, one train_step() per batch (cvae.py:2424-2501): -> (mean_loss, measures dict)."""
+        per_epoch = len(batches)
+        hook = self._train_batch_hook
+        t0 = time.time()
+        measures, nb = None, 0
+        keys, acc = None, None          # running sums of the batch means of every loss: ONE device vector
+        shown = {}
+        for i, (x, y) in enumerate(batches):
+            losses, measures = self.train_step(x, y, batch=i, current_measures=measures,
+                                               kl_var_weighting=w_kl, gamma_weighting=w_gamma)
+            if hook is not None:
+                hook(epoch, i, x, y, self._last_epsilon, losses)
+            if keys is None:
+                keys = list(losses)
+                acc = torch.zeros(len(keys), device=x.device)
+            # one small kernel per batch (stack of means) instead of the reference's .item() per loss (cvae.py:2463-2469)
+            acc += torch.stack([losses[k].detach().mean() for k in keys])
+            nb = i + 1
+            if outputs is not None and hasattr(outputs, 'results'):
+                if i % report_every == 0 or i + 1 == per_epoch:
+                    host = (acc / nb).tolist()                    # the only read-back of the loop: every k batches
+                    shown = dict(zip(keys, host))
+                outputs.results(i, per_epoch, epoch + 1, epochs, preambule='train',
+                                losses={k: shown.get(k, float('nan')) for k in self.loss_components},
+                                metrics={k: measures[k] for k in self.metrics} if (i % report_every == 0 or i + 1 == per_epoch)
+                                else {k: float('nan') for k in self.metrics},
+                                accuracy={k: np.nan for k in self.predict_methods},
+                                time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, end_of_epoch='\n')
+        mean_loss = dict(zip(keys or [], (acc / max(nb, 1)).tolist() if acc is not None else []))
+        return mean_loss, dict(measures or {})
+
+    def _train_epoch_captured(self, batches, epoch, epochs, batch_size, w_kl, w_gamma, outputs, report_every):
+        """The train phase of one epoch with TRAIN_CAPTURED: -> (mean_loss, measures dict).  Full-size batches are replays of
+        the captured step; the first CAPTURE_WARMUP_BATCHES of an epoch that has to (re-)capture and the ragged last batch
+        go through train_step().  One read-back every `report_every` batches and at the last one; no other host
+        synchronisation."""
+        opt = self.optimizer
+        per_epoch = len(batches)
+        hook = self._train_batch_hook
+        if not getattr(opt, '_device_hyper', False):
+            opt.enable_device_hyper(True)
+        step = getattr(self, '_captured_step', None)
+        bufs, keys, t0 = None, None, time.time()
+        shown, metrics_host, warm, h, checked = {}, {}, 0, None, False
+        has_dict = self.encoder.prior.conditional
+        measures = None
+        for i, (x, y) in enumerate(batches):
+            if bufs is None:
+                bufs = self._capture_buffers(x.device)
+                bufs['sums'].zero_()
+                bufs['counter'].zero_()
+            full = x.shape[0] == batch_size
+            if full and step is not None and not checked \
+                    and step.key != self._capture_key(x, y, self._cross_y_on(w_gamma)):
+                step = self._captured_step = None      # thawed prior means, .to(), a re-flattened optimiser, another batch shape
+            checked = checked or full                  # once per epoch: nothing in the loop changes the key
+            if full and step is None and warm >= self.CAPTURE_WARMUP_BATCHES:
+                measures = None                        # no live eager autograd graph may reach into the capture
+                step = self._captured_step = self.capture_train_step(x, y, w_kl, w_gamma)
+            if full and step is not None:
+                if i == 0 or warm:
+                    step.set_weights(w_kl, w_gamma)    # once per epoch
+                    warm = 0
+                losses = step(x, y)
+                eps = step.epsilon
+                keys = step.keys
+            else:
+                if i and measures is None:             # eager after replays (the ragged batch): continue their running means
+                    measures = Measures(bufs['run'].clone(), has_dict, _grad_nan_exit, from_main=True)
+                losses, measures = self.train_step(x, y, batch=i, current_measures=measures,
+                                                   kl_var_weighting=w_kl, gamma_weighting=w_gamma)
+                eps = self._last_epsilon
+                keys = list(losses)
+                ops.loss_sums([losses[k] for k in keys], bufs['sums'])
+                torch.cuda.current_stream(x.device).wait_stream(_lib.side_stream(x.device))
+                bufs['run'].copy_(measures._dev)       # the block always holds the latest measures, whichever path ran
+                bufs['counter'].fill_(i + 1)
+                if full:
+                    warm += 1
+                else:
+                    measures = None
+            if hook is not None:
+                hook(epoch, i, x, y, eps, losses)
+            del losses
+            nb = i + 1
+            if i % report_every == 0 or nb == per_epoch:
+                h = self._read_captured_state(bufs)
+                shown = {k: v / nb for k, v in zip(keys, h[16:])}
+                metrics_host = self._measures_from_host(h, has_dict)
+            if outputs is not None and hasattr(outputs, 'results'):
+                fresh = i % report_every == 0 or nb == per_epoch
+                outputs.results(i, per_epoch, epoch + 1, epochs, preambule='train',
+                                losses={k: shown.get(k, float('nan')) for k in self.loss_components},
+                                metrics={k: metrics_host[k] if fresh else float('nan') for k in self.metrics},
+                                accuracy={k: np.nan for k in self.predict_methods},
+                                time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, end_of_epoch='\n')
+        if h is None:
+            return {}, {}
+        if not self.is_vib:
+            self.training_parameters['sigma'] = self.sigma.host_params(h[0])
+        return dict(shown), dict(metrics_host)
 
     def train_model(self, trainset=None, transformer=None, data_augmentation=None, optimizer=None, epochs=50,
                     batch_size=100, test_batch_size=100, validation=4096, device=None, testset=None, oodsets=None,
@@ -1786,35 +2053,18 @@ class ClassificationVariationalNetwork(nn.Module):
             self.train()
             w_kl = max(0., min(1., (epoch + 1 - warmup[0]) / (warmup[1] + 1)))
             w_gamma = max(0., min(1., (epoch + 1 - warmup_gamma[0]) / (warmup_gamma[1] + 1)))
-            t0 = time.time()
-            measures, nb = None, 0
-            keys, acc = None, None          # running sums of the batch means of every loss: ONE device vector
-            shown = {}
-            for i, (x, y) in enumerate(batches):
-                losses, measures = self.train_step(x, y, batch=i, current_measures=measures,
-                                                   kl_var_weighting=w_kl, gamma_weighting=w_gamma)
-                if keys is None:
-                    keys = list(losses)
-                    acc = torch.zeros(len(keys), device=x.device)
-                # one small kernel per batch (stack of means) instead of the reference's .item() per loss (cvae.py:2463-2469)
-                acc += torch.stack([losses[k].detach().mean() for k in keys])
-                nb = i + 1
-                if outputs is not None and hasattr(outputs, 'results'):
-                    if i % report_every == 0 or i + 1 == per_epoch:
-                        host = (acc / nb).tolist()                    # the only read-back of the loop: every k batches
-                        shown = dict(zip(keys, host))
-                    outputs.results(i, per_epoch, epoch + 1, epochs, preambule='train',
-                                    losses={k: shown.get(k, float('nan')) for k in self.loss_components},
-                                    metrics={k: measures[k] for k in self.metrics} if (i % report_every == 0 or i + 1 == per_epoch)
-                                    else {k: float('nan') for k in self.metrics},
-                                    accuracy={k: np.nan for k in self.predict_methods},
-                                    time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, end_of_epoch='\n')
+            captured = bool(self.TRAIN_CAPTURED)
+            if captured and (optimizer._world > 1 or optimizer.kind != 'adam' or optimizer is not self.optimizer):
+                logging.info('TRAIN_CAPTURED: %s - this epoch runs the eager train_step()',
+                             'data-parallel model' if optimizer._world > 1 else 'the captured step needs the built-in Adam')
+                captured = False
+            run_epoch = self._train_epoch_captured if captured else self._train_epoch_eager
+            mean_loss, measures = run_epoch(batches, epoch, epochs, batch_size, w_kl, w_gamma, outputs, report_every)
             self.eval()
-            mean_loss = dict(zip(keys or [], (acc / max(nb, 1)).tolist() if acc is not None else []))
             if train_accuracy:
                 history_checkpoint['train_accuracy'] = train_accuracy
             history_checkpoint['train_loss'] = mean_loss
-            history_checkpoint['train_measures'] = dict(measures or {})
+            history_checkpoint['train_measures'] = measures
             self.train_history['epochs'] += 1
             history_checkpoint['lr'] = self.optimizer.lr
             self.trained += 1

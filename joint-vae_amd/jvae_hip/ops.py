@@ -5,6 +5,7 @@ executed by the hand-written gfx950 kernels.  Every function raises if its tenso
 """
 import collections
 import contextlib
+import ctypes
 import math
 from ctypes import byref, c_int, c_size_t
 
@@ -798,6 +799,12 @@ PRIOR_KIND = {'gaussian': 0, 'tilted': 1, 'uniform': 2}
 VAR_KIND = {'scalar': 0, 'diag': 1, 'full': 2}
 
 
+def _device_scalar(t, what):
+    if not t.is_cuda or t.dtype != torch.float32 or t.numel() != 1 or t.requires_grad:
+        raise L.JvaeHipError(what + ' as a tensor must be ONE fp32 value on the GPU without gradient')
+    return t.detach()
+
+
 class _Latent(torch.autograd.Function):
     """clip + reparameterise + KL terms; see csrc/latent.hip for the reference anchors."""
 
@@ -824,12 +831,19 @@ class _Latent(torch.autograd.Function):
         forced = cfg.get('forced_lv')
         args = (N, K, Ls, C, cfg['prior'], cfg['var_dim'], cfg['tau'], cfg['alpha'], cfg['w'], int(cfg['sampled']),
                 int(forced is not None))
-        rc = lib.jvae_latent_fwd_f32(L.ptr(mu), L.ptr(lv_raw), L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T), L.ptr(dict_),
-                                     L.ptr(lv), L.ptr(z), L.ptr(kl), L.ptr(zd), L.ptr(vkl), L.ptr(dzd),
-                                     *args, float(forced or 0.), L.stream_ptr())
+        w_dev = cfg.get('w_dev')             # the weight as a device scalar (captured step): the *_wdev entry points
+        if w_dev is None:
+            rc = lib.jvae_latent_fwd_f32(L.ptr(mu), L.ptr(lv_raw), L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T), L.ptr(dict_),
+                                         L.ptr(lv), L.ptr(z), L.ptr(kl), L.ptr(zd), L.ptr(vkl), L.ptr(dzd),
+                                         *args, float(forced or 0.), L.stream_ptr())
+        else:
+            rc = lib.jvae_latent_fwd_wdev_f32(L.ptr(mu), L.ptr(lv_raw), L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T),
+                                              L.ptr(dict_), L.ptr(lv), L.ptr(z), L.ptr(kl), L.ptr(zd), L.ptr(vkl), L.ptr(dzd),
+                                              *args, float(forced or 0.), L.ptr(w_dev), L.stream_ptr())
         L.check(rc, 'jvae_latent_fwd_f32')
         ctx.save_for_backward(mu, lv_raw, lv, eps, y, means, T)
         ctx.args = args
+        ctx.w_dev = w_dev
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(dzd)
         return lv, z, kl, zd, vkl, dzd
@@ -851,20 +865,26 @@ class _Latent(torch.autograd.Function):
 
         def opt(t):
             return None if t is None else _c(t)
-        rc = lib.jvae_latent_bwd_f32(L.ptr(mu), L.ptr(lv_raw), L.ptr(lv), L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T),
-                                     L.ptr(opt(g_z)), L.ptr(opt(g_kl)), L.ptr(opt(g_zd)), L.ptr(opt(g_vkl)),
-                                     None, L.ptr(opt(g_lv)),
-                                     L.ptr(gmu), L.ptr(glv), L.ptr(gmeans), L.ptr(gT),
-                                     *ctx.args, L.ptr(ws), ws.numel(), L.stream_ptr())
+        ptrs = (L.ptr(mu), L.ptr(lv_raw), L.ptr(lv), L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T),
+                L.ptr(opt(g_z)), L.ptr(opt(g_kl)), L.ptr(opt(g_zd)), L.ptr(opt(g_vkl)), None, L.ptr(opt(g_lv)),
+                L.ptr(gmu), L.ptr(glv), L.ptr(gmeans), L.ptr(gT))
+        if ctx.w_dev is None:
+            rc = lib.jvae_latent_bwd_f32(*ptrs, *ctx.args, L.ptr(ws), ws.numel(), L.stream_ptr())
+        else:
+            rc = lib.jvae_latent_bwd_wdev_f32(*ptrs, *ctx.args, L.ptr(ctx.w_dev), L.ptr(ws), ws.numel(), L.stream_ptr())
         L.check(rc, 'jvae_latent_bwd_f32')
         return gmu, glv, None, None, gmeans, gT, None
 
 
 def latent(mu, lv_raw, eps, y, means, T, *, prior='gaussian', var_dim='scalar', tau=0., alpha=0., w=1.,
            sampled=True, forced_lv=None):
-    """-> (log_var (N,K), z (L+1,N,K), kl, zdist, var_kl, dzdist (N,))"""
+    """-> (log_var (N,K), z (L+1,N,K), kl, zdist, var_kl, dzdist (N,)).  `w`: a float, or a 1-element fp32 DEVICE tensor that
+    the kernels read at run time (a captured step whose warm-up weight changes between replays; bit-identical to the float)."""
+    w_dev = None
+    if torch.is_tensor(w):
+        w_dev, w = _device_scalar(w, 'w'), 1.
     cfg = dict(prior=PRIOR_KIND[prior], var_dim=VAR_KIND[var_dim], tau=float(tau), alpha=float(alpha), w=float(w),
-               sampled=bool(sampled), forced_lv=forced_lv)
+               sampled=bool(sampled), forced_lv=forced_lv, w_dev=w_dev)
     return _Latent.apply(mu, lv_raw, eps, y, means, T, cfg)
 
 
@@ -961,17 +981,21 @@ class _Elbo(torch.autograd.Function):
     """wmse_s (L,N), kl (N,), ce (N,)|None, sigma -> (wmse, cross_x, total, mse) (cvae.py:662-670,773-791,887-902)."""
 
     @staticmethod
-    def forward(ctx, wmse_s, kl, ce, sigma, mode, D, beta, cw):
+    def forward(ctx, wmse_s, kl, ce, sigma, mode, D, beta, cw, cw_dev=None):
         wmse_s, kl, sigma = _c(wmse_s), _c(kl), _c(sigma)
         ce = None if ce is None else _c(ce)
         mode = int(mode)
         Ls, N = wmse_s.shape
         _check_sigma(sigma, mode, N)
         wmse, cx, tot, mse = (torch.empty(N, device=kl.device, dtype=torch.float32) for _ in range(4))
-        rc = L.load().jvae_elbo_fwd_f32(L.ptr(wmse_s), L.ptr(kl), L.ptr(ce), L.ptr(sigma), mode, L.ptr(wmse),
-                                        L.ptr(cx), L.ptr(tot), L.ptr(mse), Ls, N, int(D), float(beta), float(cw),
-                                        L.stream_ptr())
+        args = (L.ptr(wmse_s), L.ptr(kl), L.ptr(ce), L.ptr(sigma), mode, L.ptr(wmse), L.ptr(cx), L.ptr(tot), L.ptr(mse),
+                Ls, N, int(D), float(beta), float(cw))
+        if cw_dev is None:
+            rc = L.load().jvae_elbo_fwd_f32(*args, L.stream_ptr())
+        else:
+            rc = L.load().jvae_elbo_fwd_wdev_f32(*args, L.ptr(cw_dev), L.stream_ptr())
         L.check(rc, 'jvae_elbo_fwd_f32')
+        ctx.cw_dev = cw_dev
         ctx.save_for_backward(wmse_s if mode == SIGMA_RMSE else sigma)
         ctx.cfg = (mode, Ls, N, int(D), float(beta), float(cw), ce is not None)
         ctx.set_materialize_grads(False)
@@ -991,15 +1015,22 @@ class _Elbo(torch.autograd.Function):
 
         def opt(t):
             return None if t is None else _c(t)
-        rc = L.load().jvae_elbo_bwd_f32(L.ptr(opt(g_wmse)), L.ptr(opt(g_cx)), L.ptr(opt(g_tot)), L.ptr(sigma), mode,
-                                        L.ptr(g_ws), L.ptr(g_kl), L.ptr(g_ce), L.ptr(gs), 0, Ls, N, D, beta, cw,
-                                        L.ptr(ws), ws.numel(), L.stream_ptr())
+        args = (L.ptr(opt(g_wmse)), L.ptr(opt(g_cx)), L.ptr(opt(g_tot)), L.ptr(sigma), mode,
+                L.ptr(g_ws), L.ptr(g_kl), L.ptr(g_ce), L.ptr(gs), 0, Ls, N, D, beta, cw)
+        if ctx.cw_dev is None:
+            rc = L.load().jvae_elbo_bwd_f32(*args, L.ptr(ws), ws.numel(), L.stream_ptr())
+        else:
+            rc = L.load().jvae_elbo_bwd_wdev_f32(*args, L.ptr(ctx.cw_dev), L.ptr(ws), ws.numel(), L.stream_ptr())
         L.check(rc, 'jvae_elbo_bwd_f32')
-        return g_ws, g_kl, g_ce, gs, None, None, None, None
+        return g_ws, g_kl, g_ce, gs, None, None, None, None, None
 
 
 def elbo(wmse_s, kl, ce, sigma, sigma_is_log, D, beta, cw, with_mse=False):
-    wmse, cx, tot, mse = _Elbo.apply(wmse_s, kl, ce, sigma, int(sigma_is_log), D, beta, cw)
+    """`cw` (the weight of cross_y in `total`): a float, or a 1-element fp32 DEVICE tensor read by the kernels at run time."""
+    cw_dev = None
+    if torch.is_tensor(cw):
+        cw_dev, cw = _device_scalar(cw, 'cw'), 0.
+    wmse, cx, tot, mse = _Elbo.apply(wmse_s, kl, ce, sigma, int(sigma_is_log), D, beta, cw, cw_dev)
     return (wmse, cx, tot, mse) if with_mse else (wmse, cx, tot)
 
 
@@ -1017,19 +1048,52 @@ def iws(wmse_s, eps, log_var, log_pz, sigma, sigma_is_log, D):
     return out if conditional else out[0]
 
 
-def measures(x, wmse, zdist, var_kl, sigma, sigma_is_log, means, flag, scratch, prev=None, batch=0):
+def measures(x, wmse, zdist, var_kl, sigma, sigma_is_log, means, flag, scratch, prev=None, batch=0, run=None, counter=None):
     """-> device tensor of 16 floats (layout in csrc/loss.hip measures_kernel); `scratch`: 1-float device tensor;
-    `prev`: the tensor returned for the previous batch (running means are continued on the device)."""
+    `prev`: the tensor returned for the previous batch (running means are continued on the device).
+    run (16 fp32) + counter (1 int32), both on the device: the captured-step form - the batch index is *counter (incremented
+    by the kernel), `run` is the previous result and receives this one (returned); prev / batch are not used."""
     lib = L.load()
     x = _c(x)
     sqnorm_accum(x, scratch, True)
-    out = torch.empty(16, device=x.device, dtype=torch.float32)
     C, K = (means.shape if means is not None else (0, 0))
+    if run is not None:
+        if run.dtype != torch.float32 or run.numel() != 16 or counter is None or counter.dtype != torch.int32 or counter.numel() != 1:
+            raise L.JvaeHipError('measures: run must hold 16 fp32 values and counter one int32')
+        rc = lib.jvae_measures_dev_f32(L.ptr(scratch), x.numel(), L.ptr(_c(wmse)), L.ptr(_c(zdist)), L.ptr(_c(var_kl)), wmse.numel(),
+                                       zdist.numel(), L.ptr(_c(sigma)), int(sigma_is_log),
+                                       L.ptr(None if means is None else _c(means)), C, K, L.ptr(flag), L.ptr(run), L.ptr(counter),
+                                       L.stream_ptr())
+        L.check(rc, 'jvae_measures_dev_f32')
+        return run
+    out = torch.empty(16, device=x.device, dtype=torch.float32)
     rc = lib.jvae_measures_f32(L.ptr(scratch), x.numel(), L.ptr(_c(wmse)), L.ptr(_c(zdist)), L.ptr(_c(var_kl)), wmse.numel(), zdist.numel(),
                                L.ptr(_c(sigma)), int(sigma_is_log), L.ptr(None if means is None else _c(means)), C, K,
                                L.ptr(flag), L.ptr(prev), int(batch), L.ptr(out), L.stream_ptr())
     L.check(rc, 'jvae_measures_f32')
     return out
+
+
+LOSS_ROWS_MAX = 16
+
+
+def loss_sums(rows, acc):
+    """acc[r] += mean(rows[r]) for every r, in ONE launch (csrc/loss.hip loss_sums_kernel): `rows` - up to 16 fp32 device
+    tensors of any shapes (the loss rows of a step, (N,) or (L+1, N)); `acc` - fp32 device vector of at least len(rows)
+    entries, updated in place.  Fixed summation order: repeatable bit for bit."""
+    n = len(rows)
+    if n > LOSS_ROWS_MAX:
+        raise L.JvaeHipError('loss_sums takes at most {} rows, got {}'.format(LOSS_ROWS_MAX, n))
+    if acc.dtype != torch.float32 or acc.numel() < n:
+        raise L.JvaeHipError('loss_sums: acc must be fp32 with one entry per row')
+    rows = [_c(_f32(r.detach(), 'loss_sums')) for r in rows]
+    if any(r.numel() == 0 for r in rows):
+        raise L.JvaeHipError('loss_sums: empty row')
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[L.ptr(r) for r in rows])
+    lens = (ctypes.c_long * max(n, 1))(*[r.numel() for r in rows])
+    rc = L.load().jvae_loss_sums_f32(ptrs, lens, n, L.ptr(acc), L.stream_ptr())
+    L.check(rc, 'jvae_loss_sums_f32')
+    return acc
 
 
 class _Xent(torch.autograd.Function):

@@ -23,9 +23,11 @@
 //    per CU (77 KB each);
 //  * accumulators, bias, BatchNorm partial sums and the coalesced NCHW epilogue are those of the fp32 kernel.
 // Default since round 4 (maps up to 32 wide): the 16x16x32 form (template argument SH) - K = 2 consecutive taps x 16 channels per
-// MFMA, weights staged per group of two tap pairs, a wave-uniform channel block per staging item (the deferred BatchNorm's
-// coefficients are scalar operands), straight-line weight groups with their read-ahead, two tiles per workgroup on the large
-// launches: see the comments at computeSH, lstoreX and the tile loop, and DESIGN.md section 4.
+// MFMA, a wave-uniform channel block per staging item (the deferred BatchNorm's coefficients are scalar operands), two tiles per
+// workgroup on the large launches.  Since round 6 its weights are NOT staged in LDS: they are packed in fragment order, every wave
+// loads its six 16-byte units of a tap pair from global memory (L1 / L2) straight into the fragment registers, one pair ahead,
+// and the 13 pairs of a K step run without a barrier - one LDS barrier pair per K step is left, around the patch restage
+// (77 KB -> 59 KB of LDS per workgroup).  See the comments at pairStep, lstoreX and the tile loop, and DESIGN.md section 4.
 #include <stdlib.h>
 #include "common.h"
 #include "jvae_internal.h"
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(256) void x3s_wpack_kernel(const float* __restrict_
 
 struct X3P {
     const float* in;     // (N, Cin, H, W) fp32
-    const u32x4* wp;     // packed split weights (KB*5, 30, OP) units
+    const u32x4* wp;     // packed split weights: (KB*5, 30, OP) units | 16x16x32 form: (KB*14 pairs, 3 planes, 4 lane groups, OP)
     const float* bias;   // (CoutReal) or null
     float* out;          // (N, CoutReal, OH, OW) fp32
     int N, Cin, H, W, OP, P, CoutReal;
@@ -110,10 +112,9 @@ struct X3Geom {
     static constexpr int WP = WP0 > WP1 ? WP0 : WP1;           // units per patch row
     static constexpr int CH = ROWS * WP;                       // units per 8-channel block per image
     static constexpr int XS = NIMG * 2 * CH;                   // patch units of one plane (16 channels)
-    static constexpr int WGS = SH ? 2 * 3 * 4 * 32             // weight units of one group: 2 pairs x 3 planes x 4 lane groups
-                                  : 3 * 5 * 2 * 32;            // ... of one kernel row (3 planes x 5 taps x 2 halves)
-    static constexpr int GPK = SH ? 7 : 5;                     // weight groups per K step
-    static constexpr int WROWS = SH ? JVAE_X3S_PAIRS * 12 : 150;   // 32-unit rows of packed weights per K step and 32 channels
+    static constexpr int WGS = SH ? 0                          // the 16x16x32 form stages no weights (fragments come from global memory)
+                                  : 3 * 5 * 2 * 32;            // weight units of one kernel row (3 planes x 5 taps x 2 halves)
+    static constexpr int GPK = SH ? 7 : 5;                     // groups per K step: 6 x 2 tap pairs + 1 | kernel rows (staged weight groups)
     static constexpr int NPT = SH ? PIX / 64 : MT;             // pixel tiles per wave (16 pixels each in the SH form, else 32)
     static constexpr int LDS_BYTES = (3 * XS + 2 * WGS) * 16;
 };
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
     using G = X3Geom<S, OW, MT, SH>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     u32x4* Xs = reinterpret_cast<u32x4*>(lds_raw);            // [3 planes][XS]
-    u32x4* Ws = Xs + 3 * G::XS;                                // [2 buffers][WGS]
+    u32x4* Ws = Xs + 3 * G::XS;                                // [2 buffers][WGS] (32x32x16 form only)
     __shared__ float bias_s[32];                              // this workgroup's 32 bias values: fetched while the first patch
                                                               // loads are in flight (a global load in the epilogue is an exposed
                                                               // round trip per workgroup: 36 us of the 32-wide layer)
@@ -140,8 +141,8 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
     // of ONE image - which share their halo rows - used to sit on different XCDs and every halo row came from HBM again
     // (profiles/r02_x3_fwd_pmc.json: 188 MB read for 134 MB of input).  Workgroup w = (xcd, k) takes tile xcd * (tiles / 8) + k:
     // neighbouring tiles run on the same XCD at about the same time, the halo is an L2 hit.
-    // Two tiles per workgroup (16x16x32 form, p.tpw = 2; round 4), so that the second tile's first patch and
-    // first weight groups are loaded under the last weight groups of the first one and its prologue (entry, address set-up, zero
+    // Two tiles per workgroup (16x16x32 form, p.tpw = 2; round 4), so that the second tile's first patch is loaded
+    // under the last tap pair of the first one and its prologue (entry, address set-up, zero
     // fill, the round trip of the first loads: 3 500 of a tile's 63 000 cycles) is paid once.
     // Its tiles are w and w + gridDim.x, NOT 2w and 2w + 1: the workgroups that run side by side then hold neighbouring tiles in both
     // passes and share their halo rows in L2 (with consecutive tiles per workgroup the PMC passes read 172 MB instead of 136).
@@ -152,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
     int row0 = (G::OHW >= G::PIX) ? (bx % TILES_PER_IMG) * G::TH : 0;
     const int o0 = blockIdx.y * 32;
     const int KB = (p.Cin + 15) / 16;
-    const int NG = KB * G::GPK;                                // weight groups: (K step, kernel row | group of 2 tap pairs)
+    const int NG = KB * G::GPK;                                // groups: (K step, kernel row | group of 2 tap pairs)
 
     if (tid < 32) bias_s[tid] = (p.bias && o0 + tid < p.CoutReal) ? p.bias[o0 + tid] : 0.f;
     // pixel tiles of this wave: MT groups of 32 pixels (32x32x16: the pixel on lane & 31, channel block `half`), or 2*MT tiles of 16
@@ -196,17 +197,17 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
     // them from LDS inside the per-lane `live` branch: 16 dependent ds_read_b32 per item, 3 600 + 2 400 of a workgroup's 74 000
     // cycles (tools/x3_stamps.py with AFF=0 / 1).
     constexpr int PERH = G::NIMG * G::ROWS * W2;               // items per 8-channel block and K step
-    constexpr int XU = (PERH + 127) / 128, WU = (G::WGS + 255) / 256;
+    constexpr int XU = (PERH + 127) / 128, WU = (G::WGS + 255) / 256, WUA = WU ? WU : 1;      // (WU = 0 in the 16x16x32 form)
     const int hq = __builtin_amdgcn_readfirstlane(tid >> 7);   // this wave's channel block (scalar)
     f32x2 rx[XU][8];
-    u32x4 rw[WU];
+    u32x4 rw[WUA];
 
     // Loads are unconditional (out-of-range items read a valid stand-in address and are zeroed when they are stored to
     // LDS): with branches around them the compiler cannot count outstanding loads and falls back to vmcnt(0).  Their
     // addresses are computed once: per K step / weight group only a uniform stride is added.
     const float* xsrc[XU];
     const float* xsrcN[XU];                                    // ... of the workgroup's next tile
-    const u32x4* wsrc[WU];
+    const u32x4* wsrc[WUA];
     const long cstride = (long)p.H * p.W;
     auto tile_src = [&](int timg0, int tin_row0, const float* (&dst)[XU]) {
 #pragma unroll
@@ -345,75 +346,83 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
       }
     };
 
-    // 16x16x32 form.  One group = 2 tap pairs (the last group of a K step: 1); per pair the wave issues 6 products x NPT pixel
-    // tiles x 2 channel tiles; the pair is worked through in halves of 2 pixel tiles (24 MFMAs), the fragments of the next half
-    // are read ahead.  Lane group kq reads tap 2*pair + (kq >> 1): the second tap of a pair lies one unit to the right, or - when
-    // the pair crosses a kernel row (taps 4|5, 14|15) - one row down and four units to the left; tap 25 does not exist (its
-    // weights are zero): those lanes re-read tap 24 so that no value from outside the receptive field enters a 0 * x.
-    // npair (1 for the last group of a K step) is a COMPILE-TIME constant (round 4): as a run-time value it put the read-ahead
-    // of the next half behind a branch, and at the join the compiler's s_waitcnt had to assume the path WITHOUT the new reads -
-    // lgkmcnt(2) / (0) right behind twelve fresh ds_read_b128, i.e. the read-ahead was waited for before the MFMAs it was meant
-    // to hide under (one exposed LDS round trip per pair).
-    // pre(): the staging of the next weight group, issued BEHIND the group's first fragment reads (their LDS round trip runs under
-    // its ~500 cycles of address arithmetic, waits for the weight loads and LDS stores) and in front of the first MFMA.
-    auto computeSH = [&](int buf, int gi, auto npair_c, auto&& pre) {
-        constexpr int TPH = NPT >= 2 ? 2 : 1;                    // pixel tiles per half
-        constexpr int NH = SH ? NPT / TPH : 1;                   // halves per pair
-        const u32x4* Wb = Ws + buf * G::WGS + kq * 32 + l15;
-        constexpr int npair = decltype(npair_c)::value;
-        u32x4 fa[2][3][2], fb[2][3][TPH];
-        auto tapoff = [&](int t) {                               // LDS unit offset of tap t relative to the lane's pixel
+    // 16x16x32 form.  The 13 tap pairs of a K step (12 pairs + tap 24 with an all-zero partner) run as ONE free sequence (round 6):
+    // the patch image is read-only during a K step and the weight fragments do not pass through LDS, so nothing inside a K step
+    // needs a barrier - the one barrier pair left sits around lstoreX at the K-step change.  Per pair the wave issues 6 products x
+    // NPT pixel tiles x 2 channel tiles; the pair is worked through in halves of 2 pixel tiles (24 MFMAs), the patch fragments of
+    // the next half are read ahead.  Lane group kq reads tap 2*pair + (kq >> 1): the second tap of a pair lies one unit to the
+    // right, or - when the pair crosses a kernel row (taps 4|5, 14|15) - one row down and four units to the left; tap 25 does not
+    // exist (its weights are zero): those lanes re-read tap 24 so that no value from outside the receptive field enters a 0 * x.
+    // Weight fragments: the packed buffer is in fragment order ([K step][pair][plane][kq][o] 16-byte units, pack_elems.h
+    // JVAE_PACK_X3S), so the lane's operand of (pair, plane, channel tile) is ONE unit at
+    //     uniform base (a buffer descriptor + a scalar offset: K step, pair, plane, channel tile) + a 32-bit lane offset (kq, o:
+    //     the same register for every load)
+    // and is loaded from global memory (L1 / L2: the 8 waves of a CU walk the same 77 KB per K step in loose lock step) straight
+    // into fa, one pair ahead as the LDS reads were, into the buffer the pair before has left.  The loads are
+    // unconditional and every pair is straight-line code, so the compiler's s_waitcnt vmcnt(N) is counted: a pair waits for its
+    // own six loads (issued in front of the previous pair's last 24 MFMAs; nothing else is in flight behind them).  The pair
+    // count of a step and the buffer a pair reads are COMPILE-TIME constants (round 4: as run-time values they put the read-ahead
+    // behind a branch, and at the join the s_waitcnt had to assume the path without the new reads).
+    constexpr int TPH = NPT >= 2 ? 2 : 1;                        // pixel tiles per half
+    constexpr int NH = SH ? NPT / TPH : 1;                       // halves per pair
+    [[maybe_unused]] u32x4 fa[2][3][2], fb[2][3][TPH];
+    const unsigned wlane = (unsigned)(kq * p.OP + l15) * 16u;    // byte offset of the lane's unit inside a (pair, plane, channel tile)
+    const int wplane = 4 * p.OP * 16;                            // bytes of one plane of a pair (4 lane groups x OP channels)
+    // buffer descriptor of this workgroup's 32-channel column of the packed weights: base and the per-load stream offset are scalar
+    // operands, the lane offset is one 32-bit register, reads beyond the packed form would return zeros instead of faulting
+    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<u32x4*>(p.wp + o0), 0, KB * JVAE_X3S_PAIRS * 3 * wplane - o0 * 16, 0x00020000);
+    [[maybe_unused]] auto fragA = [&](int pi, u32x4 (&a)[3][2]) {     // pi = K step * JVAE_X3S_PAIRS + pair (uniform)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+                a[pl][ct] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, (pi * 3 + pl) * wplane + ct * 256, 0));
+    };
+    [[maybe_unused]] auto fragB = [&](int off, int hp, u32x4 (&b)[3][TPH]) {
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int j = 0; j < TPH; ++j) b[pl][j] = Xs[pl * G::XS + pixoff[(hp * TPH + j) % NPT] + off];
+    };
+    [[maybe_unused]] auto offs = [&](int pair) {                 // LDS unit offset of THIS lane's tap of a pair (tap 25: tap 24 again)
+        auto tapoff = [&](int t) {                               // ... of tap t relative to the lane's pixel
             const int kh = t / 5, kw = t - 5 * kh;
             return kh * G::WP + kw;
         };
-        auto offs = [&](int pq) {                                // ... of THIS lane's tap of pair pq (tap 25: tap 24 again)
-            const int ta = 4 * gi + 2 * pq;
-            const int oa = tapoff(ta), ob = ta == 24 ? oa : tapoff(ta + 1);
-            return (kq >> 1) ? ob : oa;
-        };
-        auto fragA = [&](int pq, u32x4 (&a)[3][2]) {
+        const int ta = 2 * pair;
+        const int oa = tapoff(ta), ob = ta == 24 ? oa : tapoff(ta + 1);
+        return (kq >> 1) ? ob : oa;
+    };
+    // One tap pair with its weight fragments in fa[slot] and its first half's patch fragments in fb[...] (both issued earlier).
+    // ahead: issue the NEXT pair's weight fragments (stream index pin) in front of this pair's MFMAs and its first patch fragments
+    // (offset offn) in front of the last half's; false for the last pair of a K step (the patch changes behind it).
+    // hook(): issued behind the read-ahead of the pair's last half and in front of that half's MFMAs (the next patch's global loads).
+    [[maybe_unused]] auto pairStep = [&](auto slot_c, auto ahead_c, int off, int offn, int pin, auto&& hook) {
+        constexpr int slot = decltype(slot_c)::value;
+        constexpr bool ahead = decltype(ahead_c)::value;
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
+        for (int hp = 0; hp < NH; ++hp) {
+            const int cur = (slot * NH + hp) & 1;
+            if (ahead && hp + 1 == NH) fragA(pin, fa[slot ^ 1]);
+            if (hp + 1 < NH) fragB(off, hp + 1, fb[cur ^ 1]);
+            else if (ahead) fragB(offn, 0, fb[cur ^ 1]);
+            if (hp + 1 == NH) { __builtin_amdgcn_sched_barrier(0); hook(); }
+            __builtin_amdgcn_sched_barrier(0);
+            constexpr int WPL[6] = {0, 0, 2, 1, 1, 0}, XPL[6] = {2, 1, 0, 0, 1, 0};
 #pragma unroll
-                for (int ct = 0; ct < 2; ++ct) a[pl][ct] = Wb[((pq * 3 + pl) * 4) * 32 + ct * 16];
-        };
-        auto fragB = [&](int off, int hp, u32x4 (&b)[3][TPH]) {
+            for (int t = 0; t < 6; ++t)
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
+                for (int j = 0; j < TPH; ++j)
 #pragma unroll
-                for (int j = 0; j < TPH; ++j) b[pl][j] = Xs[pl * G::XS + pixoff[(hp * TPH + j) % NPT] + off];
-        };
-        int off = offs(0);
-        fragA(0, fa[0]);
-        fragB(off, 0, fb[0]);
-#pragma unroll
-        for (int pq = 0; pq < 2; ++pq) {
-            if (pq < npair) {
-                const int offn = pq + 1 < npair ? offs(pq + 1) : off;
-#pragma unroll
-                for (int hp = 0; hp < NH; ++hp) {
-                    const int cur = (pq * NH + hp) & 1;
-                    if (hp + 1 < NH) fragB(off, hp + 1, fb[cur ^ 1]);
-                    else if (pq + 1 < npair) { fragA(pq + 1, fa[(pq + 1) & 1]); fragB(offn, 0, fb[cur ^ 1]); }
-                    if (pq == 0 && hp == 0) { __builtin_amdgcn_sched_barrier(0); pre(); }
-                    __builtin_amdgcn_sched_barrier(0);
-                    constexpr int WPL[6] = {0, 0, 2, 1, 1, 0}, XPL[6] = {2, 1, 0, 0, 1, 0};
-#pragma unroll
-                    for (int t = 0; t < 6; ++t)
-#pragma unroll
-                        for (int j = 0; j < TPH; ++j)
-#pragma unroll
-                            for (int ct = 0; ct < 2; ++ct) {
-                                if constexpr (SH) {
-                                    f32x4& d = (t & 1) ? acc[hp * TPH + j][ct] : acs[hp * TPH + j][ct];
-                                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[pq & 1][WPL[t]][ct]),
-                                                                                __builtin_bit_cast(bf16x8, fb[cur][XPL[t]][j]), d, 0, 0, 0);
-                                }
-                            }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                off = offn;
-            }
+                    for (int ct = 0; ct < 2; ++ct) {
+                        if constexpr (SH) {
+                            f32x4& d = (t & 1) ? acc[hp * TPH + j][ct] : acs[hp * TPH + j][ct];
+                            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[slot][WPL[t]][ct]),
+                                                                        __builtin_bit_cast(bf16x8, fb[cur][XPL[t]][j]), d, 0, 0, 0);
+                        }
+                    }
+            __builtin_amdgcn_sched_barrier(0);
         }
     };
 
@@ -499,7 +508,7 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
 
     X3_STAMP(1);                                   // 0 = kernel entry (below the declarations), 1 = zero fill issued
     gloadX(0);
-    gloadW(0);
+    if constexpr (!SH) gloadW(0);
     // The halo COLUMNS (4 units left of the image row, WP - 4 - WIN right of it) are zeroed once and never written again;
     // every other cell - out-of-image rows, missing images and channels included - is rewritten by lstoreX at every K step.
     // Issued behind the first global loads (they fly meanwhile).  Round 4: the whole 46 KB image used to be cleared, in front
@@ -515,28 +524,24 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
     __syncthreads();                               // halo zero fill complete (it overlaps nothing lstoreX writes, but orders bias_s)
     X3_STAMP(2);
     lstoreX(0);
-    lstoreW(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (NG > 1) gloadW(1);
+    if constexpr (SH) {
+        fragA(0, fa[0]);                           // the first pair's weight fragments
+    } else {
+        lstoreW(0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (NG > 1) gloadW(1);
+    }
     lds_barrier();
     X3_STAMP(3);
     if constexpr (SH) {
-        // 16x16x32 form: K steps outside, the GPK - 1 two-pair groups of a K step inside, its one-pair group with the K-step change
-        // behind them - so that the registers of the next patch (rx: loaded at the start of the one-pair group, split and stored
-        // behind it) are live in that tail only and not across the two-pair code, which needs the room for its read-ahead
-        typedef std::integral_constant<int, 1> one_pair;
-        typedef std::integral_constant<int, 2> two_pairs;
-        int g = 0, gbase = 0;                          // group inside the tile; groups of the workgroup's earlier tiles
+        // 16x16x32 form: K steps outside; the six two-pair groups of a K step inside (a loop: the pair -> buffer mapping repeats
+        // every two pairs), its 13th pair with the K-step change behind them - so that the registers of the next patch (rx: loaded
+        // in front of the 13th pair's last MFMAs, split and stored behind them) are live in that tail only and not across the two-pair
+        // code, which needs the room for its read-ahead
+        typedef std::integral_constant<int, 0> slot0;
+        typedef std::integral_constant<int, 1> slot1;
+        int g = 0;                                     // group inside the tile (stamps)
         bool has_next = false;
-        auto stageW = [&] {
-            // buffer (gg+1)&1 was last read in group gg-1: every wave is past it.  The store (which waits for the loads of
-            // rw) must stay ahead of the next loads: the scheduler would otherwise issue them first and wait for all.  The group
-            // sequence runs on into the workgroup's next tile (whose weight groups are the same ones again).
-            const int gg = gbase + g;
-            if (g + 1 < NG || has_next) lstoreW((gg + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (g + 2 < NG || has_next) gloadW(g + 2 < NG ? g + 2 : g + 2 - NG);
-        };
         for (int ti = 0; ti < TPW; ++ti) {
             has_next = ti + 1 < TPW;
             if (has_next) {                                // the next tile's coordinates and patch addresses
@@ -547,29 +552,38 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
             }
             g = 0;
             for (int kb = 0; kb < KB; ++kb) {
-                // invariant: patch of K step kb in Xs, weight group g in buffer (gbase+g)&1, rw = the next weight group (in flight)
-                for (int kh = 0; kh < G::GPK - 1; ++kh, ++g) {
+                // invariant: patch of K step kb in Xs, the weight fragments of its pair 0 on their way into fa[0] (issued behind lstoreX)
+                const int pi0 = kb * JVAE_X3S_PAIRS;
+                int off = offs(0);
+                fragB(off, 0, fb[0]);
+                for (int gi = 0; gi < G::GPK - 1; ++gi, ++g) {
                     if (g < 14) X3_STAMP(8 + 4 * g);           // group start
-                    computeSH((gbase + g) & 1, kh, two_pairs{}, [&] {
-                        stageW();
-                        if (g < 14) X3_STAMP(9 + 4 * g);       // first fragment reads issued, weights stored, next loads issued
+                    const int off1 = offs(2 * gi + 1);
+                    pairStep(slot0{}, std::true_type{}, off, off1, pi0 + 2 * gi + 1, [&] {
+                        if (g < 14) X3_STAMP(9 + 4 * g);       // read-ahead issued
                     });
+                    off = offs(2 * gi + 2);
+                    pairStep(slot1{}, std::true_type{}, off1, off, pi0 + 2 * gi + 2, [] {});
                     if (g < 14) X3_STAMP(10 + 4 * g);          // MFMAs issued
-                    lds_barrier();
-                    if (g < 14) X3_STAMP(11 + 4 * g);          // barrier passed
+                    if (g < 14) X3_STAMP(11 + 4 * g);          // (no barrier)
                 }
                 const bool nextk = kb + 1 < KB;
                 if (g < 14) X3_STAMP(8 + 4 * g);
-                computeSH((gbase + g) & 1, G::GPK - 1, one_pair{}, [&] {
-                    stageW();
-                    if (nextk || has_next) gloadX(nextk ? kb + 1 : 0, !nextk);     // (the next tile's first patch behind the last K step)
+                // The next patch's loads (the next tile's first patch behind the last K step) go out in front of this pair's LAST half:
+                // by then its weight fragments have all been waited for, so nothing in front of lstoreX waits on the vector-memory
+                // counter again.  In front of the first half, the branch around them would join ahead of MFMAs that still wait
+                // for fa[0], and that wait has to assume the path without the loads behind it: vmcnt(0), the patch's round trip.
+                // (Hoisting the condition around the whole pair - two copies of it - cost 180 bytes of scratch.)
+                pairStep(slot0{}, std::false_type{}, off, off, 0, [&] {
+                    if (nextk || has_next) gloadX(nextk ? kb + 1 : 0, !nextk);
                     if (g < 14) X3_STAMP(9 + 4 * g);
                 });
                 if (g < 14) X3_STAMP(10 + 4 * g);
-                lds_barrier();
+                lds_barrier();                                 // every wave is past the patch
                 if (g < 14) X3_STAMP(11 + 4 * g);
                 if (nextk) {                                   // K step change: the patch is fully consumed
                     lstoreX(kb + 1);
+                    fragA(pi0 + JVAE_X3S_PAIRS, fa[0]);        // behind the split (its registers are the kernel's peak), under the barrier
                     lds_barrier();
                     X3_STAMP(4);                               // (first) K step change done
                 }
@@ -577,7 +591,6 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
             }
             epilogueSH();                                      // (its LDS use is red_s; the stores drain under what follows)
             if (has_next) {                                    // enter the next tile: its first patch sits in rx
-                gbase += NG;
                 bx += gridDim.x;
                 img0 = (G::OHW >= G::PIX) ? bx / TILES_PER_IMG : bx * G::NIMG;
                 row0 = (G::OHW >= G::PIX) ? (bx % TILES_PER_IMG) * G::TH : 0;
@@ -585,6 +598,7 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
 #pragma unroll
                 for (int k = 0; k < XU; ++k) xsrc[k] = xsrcN[k];
                 lstoreX(0);
+                fragA(0, fa[0]);                               // the weight stream starts again
                 lds_barrier();
             }
         }
@@ -593,7 +607,8 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
         for (int g = 0; g < NG; ++g) {
             // invariant: patch of K step kb in Xs, weight group g in buffer g&1, rw = weight group g+1 (in flight)
             const bool more = g + 1 < NG, last_row = kh == G::GPK - 1;
-            if (more) lstoreW((g + 1) & 1);                // (order: see stageW above)
+            if (more) lstoreW((g + 1) & 1);                // (the store, which waits for rw, ahead of the next loads: the scheduler
+                                                           // would otherwise issue them first and wait for all)
             __builtin_amdgcn_sched_barrier(0);
             if (g + 2 < NG) gloadW(g + 2);
             if (kh == G::GPK - 2 && kb + 1 < KB) gloadX(kb + 1);
@@ -699,7 +714,7 @@ int launch_x3(const X3P& p, hipStream_t st) {
     if (G::OHW < G::PIX) grid.x = (unsigned)((p.N + G::NIMG - 1) / G::NIMG);
     g_x3_splits = (int)grid.x;                                 // BatchNorm partial sums: one per TILE
     // Two tiles per workgroup (16x16x32 form, stride 1) when that still leaves two residency rounds of 512 workgroups:
-    // the second tile's prologue hides under the first one's last weight groups.
+    // the second tile's prologue hides under the first one's last tap pairs.
     X3P q = p;
     q.tpw = 1;
     if (SH && grid.x % 2 == 0 && (long)grid.x * grid.y >= 2048) { q.tpw = 2; grid.x /= 2; }

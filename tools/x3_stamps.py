@@ -43,7 +43,7 @@ for sh in (1,):          # the stamped epilogue is the 16x16x32 form's
     print(f'  first split/stores + barrier         {m(2, 3):8.0f}   (prologue total {m(0, 3):.0f})')
     st = np.array([[float((d[:, 8 + 4 * g + k + 1] - d[:, 8 + 4 * g + k]).mean()) for k in range(3)] for g in range(NG)])
     tail = np.array([float((d[:, (8 + 4 * (g + 1)) if g + 1 < NG else 5] - d[:, 11 + 4 * g]).mean()) for g in range(NG)])
-    print(f'  per group (mean over {NG}): store W + issue loads {st[:, 0].mean():6.0f} | fragment reads + MFMAs {st[:, 1].mean():6.0f} | barrier wait {st[:, 2].mean():6.0f} | after barrier (K-step change) {tail.mean():6.0f}')
+    print(f'  per group (mean over {NG}): read-ahead issue {st[:, 0].mean():6.0f} | fragment waits + MFMAs {st[:, 1].mean():6.0f} | barrier wait {st[:, 2].mean():6.0f} | after barrier (K-step change) {tail.mean():6.0f}')
     for g in range(NG):
         print(f'    group {g:2d}: {st[g, 0]:6.0f} {st[g, 1]:6.0f} {st[g, 2]:6.0f} {tail[g]:6.0f}')
     print(f'  main loop total                      {m(3, 5):8.0f}   (ideal MFMA issue: {NG and (13 if sh else 25) * 2 * 6 * (8 if sh else 2) * (16 if sh else 32)} cycles)')

@@ -16,6 +16,7 @@
 #include "jvae_internal.h"
 #include "conv_b8.h"
 #include "pack_elems.h"
+#include "conv_stats.h"
 
 namespace {
 
@@ -287,19 +288,14 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
                 sv[r] = s1;
                 sv[16 + r] = s2;
             }
-            // lane l31 receives the half-wave total of sv[l31]
+            // lane l31 receives the half-wave total of sv[l31].  (Not stats_stage32 of conv_stats.h: through it these kernels
+            // took up to 4 more VGPRs - 198 -> 202 for <5,1,32,4,1> - so the stage step stays as it was; profiles/NOTES.md)
             const float tot = half_wave_reduce32(sv);
             const int r = l31 & 15, ch = nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
             red[(wave * G::WCOLS + ch) * 2 + (l31 >> 4)] = tot;
         }
         __syncthreads();
-        if (tid < G::WCOLS && o0 + tid < p.CoutReal) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { s1 += red[(w * G::WCOLS + tid) * 2]; s2 += red[(w * G::WCOLS + tid) * 2 + 1]; }
-            float* dst = p.stats + ((long)(o0 + tid) * gridDim.x + blockIdx.x) * 2;
-            dst[0] = s1; dst[1] = s2;
-        }
+        stats_fold<4, G::WCOLS>(red, p.stats, tid, o0, p.CoutReal, gridDim.x, blockIdx.x);
     }
 
     // ---- epilogue: lane holds pixel l31 of each 32-pixel group, rows (channels) (r&3) + 8*(r>>2) + 4*half
@@ -339,10 +335,8 @@ __global__ __launch_bounds__(256, 2) void conv5_b8_kernel(B8FwdP p) {
     }
 }
 
-thread_local int g_b8_splits = 0;
-
 template <int K, int S, int OW, int MT, int NT>
-int launch_b8(const B8FwdP& p, hipStream_t st) {
+int launch_b8(const B8FwdP& p, hipStream_t st, int* nsplit) {
     using G = B8Geom<K, S, OW, MT, NT>;
     static_assert(G::LDS_BYTES + 2048 <= 80 * 1024, "two workgroups per CU must fit the 160 KB LDS");
     static bool attr_set = false;
@@ -358,30 +352,30 @@ int launch_b8(const B8FwdP& p, hipStream_t st) {
     const long pixels = (long)p.N * G::OHW;
     dim3 grid((unsigned)((pixels + G::PIX - 1) / G::PIX), (unsigned)(p.OP / G::WCOLS));
     if (G::OHW < G::PIX) grid.x = (unsigned)((p.N + G::NIMG - 1) / G::NIMG);
-    g_b8_splits = (int)grid.x;
     if (p.aff.sc) hipLaunchKernelGGL((conv5_b8_kernel<K, S, OW, MT, NT, true>), grid, dim3(256), G::LDS_BYTES, st, p);
     else hipLaunchKernelGGL((conv5_b8_kernel<K, S, OW, MT, NT, false>), grid, dim3(256), G::LDS_BYTES, st, p);
     JVAE_LAUNCH_CHECK();
+    if (nsplit) *nsplit = (int)grid.x;
     return 0;
 }
 
 // the (OW, S) tile plans of both kernel sizes
 template <int K>
-int launch_b8_k(const B8FwdP& p, int OW, int S, hipStream_t st) {
+int launch_b8_k(const B8FwdP& p, int OW, int S, hipStream_t st, int* nsplit) {
     if (S == 1) {
         switch (OW) {
-            case 4: return launch_b8<K, 1, 4, 1, 1>(p, st);      // 4x4 maps (deconv32+): 8 images per workgroup
-            case 8: return launch_b8<K, 1, 8, 2, 1>(p, st);
-            case 16: return launch_b8<K, 1, 16, 4, 1>(p, st);
-            case 32: return launch_b8<K, 1, 32, 4, 1>(p, st);
-            case 64: return launch_b8<K, 1, 64, 4, 1>(p, st);
+            case 4: return launch_b8<K, 1, 4, 1, 1>(p, st, nsplit);      // 4x4 maps (deconv32+): 8 images per workgroup
+            case 8: return launch_b8<K, 1, 8, 2, 1>(p, st, nsplit);
+            case 16: return launch_b8<K, 1, 16, 4, 1>(p, st, nsplit);
+            case 32: return launch_b8<K, 1, 32, 4, 1>(p, st, nsplit);
+            case 64: return launch_b8<K, 1, 64, 4, 1>(p, st, nsplit);
         }
     } else {
         switch (OW) {
-            case 4: return launch_b8<K, 2, 4, 1, 1>(p, st);
-            case 8: return launch_b8<K, 2, 8, 1, 1>(p, st);
-            case 16: return launch_b8<K, 2, 16, 2, 1>(p, st);
-            case 32: return launch_b8<K, 2, 32, 2, 1>(p, st);
+            case 4: return launch_b8<K, 2, 4, 1, 1>(p, st, nsplit);
+            case 8: return launch_b8<K, 2, 8, 1, 1>(p, st, nsplit);
+            case 16: return launch_b8<K, 2, 16, 2, 1>(p, st, nsplit);
+            case 32: return launch_b8<K, 2, 32, 2, 1>(p, st, nsplit);
         }
     }
     return JVAE_ENOTSUP;
@@ -452,12 +446,8 @@ int jvae_conv5_b8_wpack(const float* w, void* wp, int C, int O, int swap, int fl
 // the bf16 operand of a KxK weight: the step's cache slot (pack_cache.hip) or `ws`; returns the pointer to read, nullptr on a
 // launch error
 const void* jvae_b8_packed(const float* w, void* ws, int C, int O, int swap, int flip, int K, hipStream_t st) {
-    bool fresh = true;
-    void* slot = jvae_pack_cache_get(K == 3 ? JVAE_PACK_B8_3 : JVAE_PACK_B8, w, C, O, swap, flip, &fresh);
-    if (slot) ws = slot;
-    if (!slot || !fresh)
-        if (jvae_conv5_b8_wpack(w, ws, C, O, swap, flip, st, K)) return nullptr;
-    return ws;
+    return jvae_packed(K == 3 ? JVAE_PACK_B8_3 : JVAE_PACK_B8, w, C, O, swap, flip, ws,
+                       [&](void* dst) { return jvae_conv5_b8_wpack(w, dst, C, O, swap, flip, st, K); });
 }
 
 // in: B8 (N, ceil(Cin/8), H, W); out: B8 (N, ceil(Cout/8), OW, OW) or fp32 NCHW (out_f32).  ws: packed weights.
@@ -468,6 +458,5 @@ int jvae_conv5_b8_fwd(const void* in, const float* w, int swap, int flip, const 
     if (!wp) return JVAE_EINVAL;
     B8FwdP p{(const u32x4*)in, (const u32x4*)wp, bias, out, N, (Cin + 7) / 8, H, W, (Cout + 31) / 32 * 32, P,
              Cout, (Cout + 7) / 8, stats, out_f32, aff ? *aff : InAff{nullptr, nullptr, 0}};
-    struct Fin { int* n; ~Fin() { if (n) *n = g_b8_splits; } } fin{nsplit};
-    return K == 3 ? launch_b8_k<3>(p, OW, S, st) : launch_b8_k<5>(p, OW, S, st);
+    return K == 3 ? launch_b8_k<3>(p, OW, S, st, nsplit) : launch_b8_k<5>(p, OW, S, st, nsplit);
 }

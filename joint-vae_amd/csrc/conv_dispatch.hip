@@ -127,11 +127,8 @@ ConvRoute wgrad_route(const ConvGeom& g, int transposed, bool b8, const CallFlag
 
 // fp32 operand of the 4-phase kernel: the step's cache slot (pack_cache.hip) or the call's workspace; nullptr: launch error
 inline const float* packed_f32(const float* w, float* ws, int C, int O, int swap, int flip, hipStream_t st) {
-    bool fresh = true;
-    float* slot = (float*)jvae_pack_cache_get(JVAE_PACK_F32, w, C, O, swap, flip, &fresh);
-    if (slot && fresh) return slot;
-    float* dst = slot ? slot : ws;
-    return jvae_conv5_pack(w, dst, C, O, swap, flip, st) == 0 ? dst : nullptr;
+    return (const float*)jvae_packed(JVAE_PACK_F32, w, C, O, swap, flip, ws,
+                                     [&](void* dst) { return jvae_conv5_pack(w, (float*)dst, C, O, swap, flip, st); });
 }
 
 }  // namespace

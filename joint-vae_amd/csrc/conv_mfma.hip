@@ -24,6 +24,7 @@
 #include "jvae_internal.h"
 #include "conv_dispatch.h"
 #include "pack_elems.h"
+#include "conv_stats.h"
 
 namespace {
 
@@ -200,19 +201,10 @@ __global__ __launch_bounds__(256, 2) void conv5_fwd_kernel(FwdP p) {
                 sv[r] = s1;
                 sv[16 + r] = s2;
             }
-            // lane l31 receives the half-wave total of sv[l31]
-            const float tot = half_wave_reduce32(sv);
-            const int r = l31 & 15, ch = nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            red[(wave * G::WCOLS + ch) * 2 + (l31 >> 4)] = tot;
+            stats_stage32<G::WCOLS>(sv, red, wave, nt * 32, l31, half);
         }
         __syncthreads();
-        if (tid < G::WCOLS && o0 + tid < p.CoutReal) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { s1 += red[(w * G::WCOLS + tid) * 2]; s2 += red[(w * G::WCOLS + tid) * 2 + 1]; }
-            float* dst = p.stats + ((long)(o0 + tid) * gridDim.x + blockIdx.x) * 2;
-            dst[0] = s1; dst[1] = s2;
-        }
+        stats_fold<4, G::WCOLS>(red, p.stats, tid, o0, p.CoutReal, gridDim.x, blockIdx.x);
     }
 
     // ---- epilogue: D[i = channel][j = pixel]; lane holds pixel j = l31, rows i = (r&3) + 8*(r>>2) + 4*half
@@ -257,36 +249,34 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ w, 
         jvae_pack_f32_elem(w, wp, i, C, O, swap, flip);
 }
 
-thread_local int g_last_splits = 0;     // grid.x of the last forward-type launch (host side, per call: read right after launching)
-
 template <int S, int OW, int MT, int NT, int CC>
-int launch_fwd(const FwdP& p, hipStream_t st) {
-    // two instantiations: the deferred-BatchNorm input transform costs registers only where it is used
+int launch_fwd(const FwdP& p, hipStream_t st, int* nsplit) {
+    // three instantiations: the deferred-BatchNorm input transform costs registers only where it is used
     using G = FwdGeom<S, OW, MT, NT, CC>;
     static_assert((G::XS + G::WS) * 4 <= 160 * 1024, "LDS budget");
     const long pixels = (long)p.N * G::OHW;
     dim3 grid((unsigned)((pixels + G::PIX - 1) / G::PIX), (unsigned)(p.Cout / G::WCOLS));
     if (G::OHW < G::PIX) grid.x = (unsigned)((p.N + G::NIMG - 1) / G::NIMG);
-    g_last_splits = (int)grid.x;
-    if (p.aff.sc && p.aff.relu == JVAE_ACT_LEAKY) hipLaunchKernelGGL((conv5_fwd_kernel<S, OW, MT, NT, CC, 2>), grid, dim3(256), 0, st, p);
-    else if (p.aff.sc) hipLaunchKernelGGL((conv5_fwd_kernel<S, OW, MT, NT, CC, 1>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv5_fwd_kernel<S, OW, MT, NT, CC, 0>), grid, dim3(256), 0, st, p);
+    jvae_with_aff(jvae_aff_inst(p.aff), [&](auto A) {
+        hipLaunchKernelGGL((conv5_fwd_kernel<S, OW, MT, NT, CC, decltype(A)::value>), grid, dim3(256), 0, st, p);
+    });
     JVAE_LAUNCH_CHECK();
+    if (nsplit) *nsplit = (int)grid.x;      // BatchNorm partial sums: one per tile
     return 0;
 }
 
 // Tile choice: the largest tile that still gives the chip >= ~3 workgroups per CU (256 CUs); small feature maps
 // (8x8, 16x16 at batch 512) fall back to 256- or 128-pixel tiles x 32 channels.
 template <int S, int OW>
-int launch_fwd_ow(const FwdP& p, hipStream_t st) {
+int launch_fwd_ow(const FwdP& p, hipStream_t st, int* nsplit) {
     const long pixels = (long)p.N * OW * OW;
     auto wgs = [&](int mt, int nt) { return ((pixels + mt * 128 - 1) / (mt * 128)) * (p.Cout / (nt * 32)); };
     constexpr long ENOUGH = 768;
-    if (p.Cin <= 4) return launch_fwd<S, OW, 4, 1, 4>(p, st);      // 3-channel inputs: one chunk of 2 channel pairs
-    if (p.Cout % 64 == 0 && wgs(2, 2) >= ENOUGH) return launch_fwd<S, OW, 2, 2, (S == 1 ? 8 : 4)>(p, st);
-    if (wgs(4, 1) >= ENOUGH) return launch_fwd<S, OW, 4, 1, (S == 1 ? 8 : 4)>(p, st);
-    if (wgs(2, 1) >= ENOUGH) return launch_fwd<S, OW, 2, 1, (S == 1 ? 8 : 4)>(p, st);
-    return launch_fwd<S, OW, 1, 1, (S == 1 ? 8 : 4)>(p, st);
+    if (p.Cin <= 4) return launch_fwd<S, OW, 4, 1, 4>(p, st, nsplit);      // 3-channel inputs: one chunk of 2 channel pairs
+    if (p.Cout % 64 == 0 && wgs(2, 2) >= ENOUGH) return launch_fwd<S, OW, 2, 2, (S == 1 ? 8 : 4)>(p, st, nsplit);
+    if (wgs(4, 1) >= ENOUGH) return launch_fwd<S, OW, 4, 1, (S == 1 ? 8 : 4)>(p, st, nsplit);
+    if (wgs(2, 1) >= ENOUGH) return launch_fwd<S, OW, 2, 1, (S == 1 ? 8 : 4)>(p, st, nsplit);
+    return launch_fwd<S, OW, 1, 1, (S == 1 ? 8 : 4)>(p, st, nsplit);
 }
 
 }  // namespace
@@ -326,30 +316,25 @@ int jvae_conv5_fwd_max_splits(int N, int OW) { return (int)(((long)N * OW * OW +
 int jvae_conv5_fwd(const float* in, const float* w, int swap, int flip, const float* bias, float* out,
                    int N, int Cin, int H, int W, int Cout, int OW, int S, int P, float* ws, hipStream_t st,
                    float* stats, int* nsplit, const InAff* aff) {
-    {   // packed weights: the step's cache slot (refreshed once per step, pack_cache.hip) or this call's workspace
-        bool fresh = true;
-        float* slot = (float*)jvae_pack_cache_get(JVAE_PACK_F32, w, Cin, Cout, swap, flip, &fresh);
-        if (slot) ws = slot;
-        if (!slot || !fresh) {
-            int rc = jvae_conv5_pack(w, ws, Cin, Cout, swap, flip, st);
-            if (rc) return rc;
-        }
-    }
+    // packed weights: the step's cache slot (refreshed once per step, pack_cache.hip) or this call's workspace
+    int rc = 0;
+    ws = (float*)jvae_packed(JVAE_PACK_F32, w, Cin, Cout, swap, flip, ws,
+                             [&](void* dst) { return jvae_conv5_pack(w, (float*)dst, Cin, Cout, swap, flip, st); }, &rc);
+    if (!ws) return rc ? rc : JVAE_EINVAL;
     FwdP p{in, ws, bias, out, N, Cin, H, W, (Cout + 31) / 32 * 32, P, Cout, stats, aff ? *aff : InAff{nullptr, nullptr, 0}};
-    struct Fin { int* n; ~Fin() { if (n) *n = g_last_splits; } } fin{nsplit};
     if (S == 1) {
         switch (OW) {
-            case 8: return launch_fwd_ow<1, 8>(p, st);
-            case 16: return launch_fwd_ow<1, 16>(p, st);
-            case 32: return launch_fwd_ow<1, 32>(p, st);
-            case 64: return launch_fwd_ow<1, 64>(p, st);
+            case 8: return launch_fwd_ow<1, 8>(p, st, nsplit);
+            case 16: return launch_fwd_ow<1, 16>(p, st, nsplit);
+            case 32: return launch_fwd_ow<1, 32>(p, st, nsplit);
+            case 64: return launch_fwd_ow<1, 64>(p, st, nsplit);
         }
     } else {
         switch (OW) {
-            case 8: return launch_fwd_ow<2, 8>(p, st);
-            case 16: return launch_fwd_ow<2, 16>(p, st);
-            case 32: return launch_fwd_ow<2, 32>(p, st);
-            case 64: return launch_fwd_ow<2, 64>(p, st);
+            case 8: return launch_fwd_ow<2, 8>(p, st, nsplit);
+            case 16: return launch_fwd_ow<2, 16>(p, st, nsplit);
+            case 32: return launch_fwd_ow<2, 32>(p, st, nsplit);
+            case 64: return launch_fwd_ow<2, 64>(p, st, nsplit);
         }
     }
     return JVAE_ENOTSUP;

@@ -312,16 +312,15 @@ bool jvae_conv5_smallci_ok(int Cin, int H, int W, int Cout, int OW, int S, int P
 
 int jvae_conv5_smallci(const float* in, const float* w, int swap, int flip, const float* bias, float* out,
                        int N, int Cin, int W, int Cout, float* ws, hipStream_t st, float* stats, int* nsplit) {
-    {   // packed weights: the step's cache slot (refreshed once per step, pack_cache.hip) or this call's workspace
-        bool fresh = true;
-        float* slot = (float*)jvae_pack_cache_get(JVAE_PACK_SCI, w, Cin, Cout, swap, flip, &fresh);
-        if (slot) ws = slot;
-        if (!slot || !fresh) {
-            const long total = jvae_pack_elems(JVAE_PACK_SCI, Cin, Cout);
-            hipLaunchKernelGGL(sci_wpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, ws, Cin, Cout, total, swap, flip);
-            JVAE_LAUNCH_CHECK();
-        }
-    }
+    // packed weights: the step's cache slot (refreshed once per step, pack_cache.hip) or this call's workspace
+    int rc = 0;
+    ws = (float*)jvae_packed(JVAE_PACK_SCI, w, Cin, Cout, swap, flip, ws, [&](void* dst) {
+        const long total = jvae_pack_elems(JVAE_PACK_SCI, Cin, Cout);
+        hipLaunchKernelGGL(sci_wpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, (float*)dst, Cin, Cout, total, swap, flip);
+        JVAE_LAUNCH_CHECK();
+        return 0;
+    }, &rc);
+    if (!ws) return rc ? rc : JVAE_EINVAL;
     SciP p{in, ws, bias, out, stats, N, Cout};
     dim3 grid((unsigned)(N * (W * W / 1024)), (unsigned)((Cout + 15) / 16));      // 2 channel groups of 8 per workgroup
     if (nsplit) *nsplit = stats ? (int)grid.x : 0;

@@ -19,6 +19,7 @@
 #include "jvae_internal.h"
 #include "conv_b8.h"
 #include "pack_elems.h"
+#include "conv_stats.h"
 
 namespace {
 
@@ -176,19 +177,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void convt2_b8_kernel(T2B
             sv[e] = s1;
             sv[16 + e] = s2;
         }
-        {   // lane l31 receives the half-wave total of sv[l31]
-            const float tot = half_wave_reduce32(sv);
-            const int e = l31 & 15, ch = (e & 3) + 8 * (e >> 2) + 4 * half;
-            red[(wave * 32 + ch) * 2 + (l31 >> 4)] = tot;
-        }
+        stats_stage32<32>(sv, red, wave, 0, l31, half);
         __syncthreads();
-        if (tid < 32 && o0 + tid < p.O) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) { s1 += red[(w * 32 + tid) * 2]; s2 += red[(w * 32 + tid) * 2 + 1]; }
-            float* dst = p.stats + ((long)(o0 + tid) * gridDim.x + blockIdx.x) * 2;
-            dst[0] = s1; dst[1] = s2;
-        }
+        stats_fold<NW, 32>(red, p.stats, tid, o0, p.O, gridDim.x, blockIdx.x);
     }
     const int n = img0 + im;
     if (n >= p.N) return;
@@ -214,28 +205,26 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void convt2_b8_kernel(T2B
     }
 }
 
-thread_local int g_t2b8_splits = 0;
-
 template <int K, int WS, int NW>
-int launch_t2b8(const T2B8P& p, hipStream_t st) {
+int launch_t2b8(const T2B8P& p, hipStream_t st, int* nsplit) {
     using G = T2B8Geom<K, WS, NW>;
     static_assert(G::LDS_BYTES <= 64 * 1024, "LDS budget");
     dim3 grid(G::HSWS >= G::PIX ? (unsigned)((long)p.N * G::HSWS / G::PIX) : (unsigned)((p.N + G::NIMG - 1) / G::NIMG),
               (unsigned)(p.OP / 32));
-    g_t2b8_splits = (int)grid.x;
     if (p.aff.sc) hipLaunchKernelGGL((convt2_b8_kernel<K, WS, NW, true>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
     else hipLaunchKernelGGL((convt2_b8_kernel<K, WS, NW, false>), grid, dim3(NW * 64), G::LDS_BYTES, st, p);
     JVAE_LAUNCH_CHECK();
+    if (nsplit) *nsplit = (int)grid.x;
     return 0;
 }
 
 template <int K>
-int launch_t2b8_k(const T2B8P& p, int WS, hipStream_t st) {
+int launch_t2b8_k(const T2B8P& p, int WS, hipStream_t st, int* nsplit) {
     switch (WS) {
-        case 4: return launch_t2b8<K, 4, 4>(p, st);      // 4x4 -> 8x8 (deconv32+): 8 images per workgroup
-        case 8: return launch_t2b8<K, 8, 4>(p, st);
-        case 16: return launch_t2b8<K, 16, 4>(p, st);
-        case 32: return launch_t2b8<K, 32, 4>(p, st);
+        case 4: return launch_t2b8<K, 4, 4>(p, st, nsplit);      // 4x4 -> 8x8 (deconv32+): 8 images per workgroup
+        case 8: return launch_t2b8<K, 8, 4>(p, st, nsplit);
+        case 16: return launch_t2b8<K, 16, 4>(p, st, nsplit);
+        case 32: return launch_t2b8<K, 32, 4>(p, st, nsplit);
     }
     return JVAE_ENOTSUP;
 }
@@ -256,6 +245,5 @@ int jvae_convt2_b8(const void* in, const float* w, const float* bias, void* out,
     if (!wp) return JVAE_EINVAL;
     T2B8P p{(const u32x4*)in, (const u32x4*)wp, bias, (u32x2*)out, N, (C + 7) / 8, (O + 31) / 32 * 32, O, (O + 7) / 8, stats,
             aff ? *aff : InAff{nullptr, nullptr, 0}};
-    struct Fin { int* n; ~Fin() { if (n) *n = g_t2b8_splits; } } fin{nsplit};
-    return K == 3 ? launch_t2b8_k<3>(p, WS, st) : launch_t2b8_k<5>(p, WS, st);
+    return K == 3 ? launch_t2b8_k<3>(p, WS, st, nsplit) : launch_t2b8_k<5>(p, WS, st, nsplit);
 }

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "jvae_internal.h"
 #include "conv_dispatch.h"
+#include "conv_stats.h"
 
 namespace {
 
@@ -185,19 +186,10 @@ __global__ __launch_bounds__(256, NT == 1 ? 4 : 2) void convt2_kernel(T2P p) {
                 sv[e] = s1;
                 sv[16 + e] = s2;
             }
-            // lane l31 receives the half-wave total of sv[l31]
-            const float tot = half_wave_reduce32(sv);
-            const int e = l31 & 15, ch = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-            red[(wave * G::WCOLS + ch) * 2 + (l31 >> 4)] = tot;
+            stats_stage32<G::WCOLS>(sv, red, wave, t * 32, l31, half);
         }
         __syncthreads();
-        if (tid < G::WCOLS) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { s1 += red[(w * G::WCOLS + tid) * 2]; s2 += red[(w * G::WCOLS + tid) * 2 + 1]; }
-            float* dst = p.stats + ((long)(o0 + tid) * gridDim.x + blockIdx.x) * 2;
-            dst[0] = s1; dst[1] = s2;
-        }
+        stats_fold<4, G::WCOLS>(red, p.stats, tid, o0, p.O, gridDim.x, blockIdx.x);      // (O % 32 == 0: the guard never bites)
     }
     const int n = img0 + im;
     if (n >= p.N) return;
@@ -217,19 +209,18 @@ __global__ __launch_bounds__(256, NT == 1 ? 4 : 2) void convt2_kernel(T2P p) {
         }
 }
 
-static thread_local int g_t2_splits = 0;
-
-template <int WS, int NT>
-int launch_t2(const T2P& p, hipStream_t st) {
-    using G = T2Geom<WS, NT, 4>;
+// NT = 1 only: NT = 2 needs 128 accumulator registers (1 wave/SIMD), so every wave takes one 32-channel tile instead
+template <int WS>
+int launch_t2(const T2P& p, hipStream_t st, int* nsplit) {
+    using G = T2Geom<WS, 1, 4>;
     static_assert((G::XS + G::WSZ) * 4 <= 64 * 1024, "static LDS budget");
     dim3 grid(G::HSWS >= G::PIX ? (unsigned)((long)p.N * G::HSWS / G::PIX) : (unsigned)((p.N + G::NIMG - 1) / G::NIMG),
               (unsigned)(p.O / G::WCOLS));
-    g_t2_splits = (int)grid.x;
-    if (p.aff.sc && p.aff.relu == JVAE_ACT_LEAKY) hipLaunchKernelGGL((convt2_kernel<WS, NT, 4, 2>), grid, dim3(256), 0, st, p);
-    else if (p.aff.sc) hipLaunchKernelGGL((convt2_kernel<WS, NT, 4, 1>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((convt2_kernel<WS, NT, 4, 0>), grid, dim3(256), 0, st, p);
+    jvae_with_aff(jvae_aff_inst(p.aff), [&](auto A) {
+        hipLaunchKernelGGL((convt2_kernel<WS, 1, 4, decltype(A)::value>), grid, dim3(256), 0, st, p);
+    });
     JVAE_LAUNCH_CHECK();
+    if (nsplit) *nsplit = (int)grid.x;
     return 0;
 }
 
@@ -246,12 +237,10 @@ bool jvae_convt2_ok(int C, int HS, int WS, int O, int HB, int WB, int KH, int KW
 int jvae_convt2(const float* in, const float* wpacked, const float* bias, float* out, int N, int C, int WS, int O,
                 hipStream_t st, float* stats, int* nsplit, const InAff* aff) {
     T2P p{in, wpacked, bias, out, N, C, O, stats, aff ? *aff : InAff{nullptr, nullptr, 0}};
-    struct Fin { int* n; ~Fin() { if (n) *n = g_t2_splits; } } fin{nsplit};
-    const bool two = false;      // NT = 2 needs 128 accumulator registers (1 wave/SIMD): one 32-channel tile per wave instead
     switch (WS) {
-        case 8: return two ? launch_t2<8, 2>(p, st) : launch_t2<8, 1>(p, st);
-        case 16: return two ? launch_t2<16, 2>(p, st) : launch_t2<16, 1>(p, st);
-        case 32: return two ? launch_t2<32, 2>(p, st) : launch_t2<32, 1>(p, st);
+        case 8: return launch_t2<8>(p, st, nsplit);
+        case 16: return launch_t2<16>(p, st, nsplit);
+        case 32: return launch_t2<32>(p, st, nsplit);
     }
     return JVAE_ENOTSUP;
 }

@@ -14,6 +14,7 @@
 #include "conv_dispatch.h"
 #include "conv_x3.h"
 #include "pack_elems.h"
+#include "conv_stats.h"
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
@@ -23,8 +24,6 @@ namespace {
 typedef x3_bf16x8 bf16x8;
 typedef x3_u32x4 u32x4;
 typedef x3_f32x2 f32x2;
-
-static thread_local int g_t2x3_splits = 0;
 
 struct T2X3P {
     const float* in;     // small (N, C, HS, WS) fp32
@@ -404,46 +403,24 @@ __global__ __launch_bounds__(256, 2) void convt2s_x3_kernel(T2X3P p) {
                         make_float2(acc[r * 2][pt][ct][e], acc[r * 2 + 1][pt][ct][e]);
     }
     if (p.stats) {                                             // ... reduced after the stores have been issued (they drain meanwhile)
-        {   // lane l15 of every 16-lane row receives the row total of sv[l15]
-            const float tot = row_reduce16(sv);
-            const int j = l15 & 7, ch = (j >> 2) * 16 + kq * 4 + (j & 3);
-            red_s[(wave * 32 + ch) * 2 + (l15 >> 3)] = tot;
-        }
+        stats_stage16(sv, red_s, wave, l15, kq);
         lds_barrier();                                         // LDS only: the output stores keep draining
-        if (tid < 32) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { s1 += red_s[(w * 32 + tid) * 2]; s2 += red_s[(w * 32 + tid) * 2 + 1]; }
-            float* dst = p.stats + ((long)(o0 + tid) * gridDim.x + bx) * 2;      // slot of the TILE
-            dst[0] = s1; dst[1] = s2;
-        }
+        stats_fold<4, 32>(red_s, p.stats, tid, o0, p.O, gridDim.x, bx);      // (O % 32 == 0: the guard never bites)
     }
 }
 
 template <int WS>
-int launch_t2s(const T2X3P& p, hipStream_t st) {
+int launch_t2s(const T2X3P& p, hipStream_t st, int* nsplit) {
     using G = T2SGeom<WS>;
     static_assert(G::LDS_BYTES + 2048 <= 80 * 1024, "two workgroups per CU");
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2s_x3_kernel<WS, 0>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2s_x3_kernel<WS, 1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convt2s_x3_kernel<WS, 2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    auto kernel = [](auto A) { return &convt2s_x3_kernel<WS, decltype(A)::value>; };
+    if (const int rc = jvae_aff_lds_attr(attr_set, G::LDS_BYTES, kernel)) return rc;
     dim3 grid(G::HSWS >= G::PIX ? (unsigned)((long)p.N * G::HSWS / G::PIX) : (unsigned)((p.N + G::NIMG - 1) / G::NIMG),
               (unsigned)(p.O / 32));
-    g_t2x3_splits = (int)grid.x;
-    if (!p.aff.sc) hipLaunchKernelGGL((convt2s_x3_kernel<WS, 0>), grid, dim3(256), G::LDS_BYTES, st, p);
-    else if (p.aff.relu == JVAE_ACT_LEAKY) hipLaunchKernelGGL((convt2s_x3_kernel<WS, 2>), grid, dim3(256), G::LDS_BYTES, st, p);
-    else hipLaunchKernelGGL((convt2s_x3_kernel<WS, 1>), grid, dim3(256), G::LDS_BYTES, st, p);
+    jvae_with_aff(jvae_aff_inst(p.aff), [&](auto A) { hipLaunchKernelGGL(kernel(A), grid, dim3(256), G::LDS_BYTES, st, p); });
     JVAE_LAUNCH_CHECK();
+    if (nsplit) *nsplit = (int)grid.x;
     return 0;
 }
 
@@ -466,23 +443,20 @@ bool jvae_convt2_x3_ok(int N, int C, int WS, int O) {
 // w: the layer's weight read as [c][o][tap] (ConvTranspose2d layout / Conv2d dgrad); ws: jvae_conv5_x3_pack_bytes(C, O)
 int jvae_convt2_x3(const float* in, const float* w, const float* bias, float* out, int N, int C, int WS, int O, float* ws,
                    hipStream_t st, float* stats, int* nsplit, const InAff* aff) {
-    {
-        bool fresh = true;
-        float* slot = (float*)jvae_pack_cache_get(JVAE_PACK_T2S, w, C, O, 1, 0, &fresh);
-        if (slot) ws = slot;
-        if (!slot || !fresh) {
-            const long total = jvae_pack_elems(JVAE_PACK_T2S, C, O);
-            const int blocks = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-            hipLaunchKernelGGL(t2s_wpack_kernel, dim3(blocks), dim3(256), 0, st, w, (__bf16*)ws, C, O, total, 1, 0);
-            JVAE_LAUNCH_CHECK();
-        }
-    }
+    int rc = 0;
+    ws = (float*)jvae_packed(JVAE_PACK_T2S, w, C, O, 1, 0, ws, [&](void* dst) {
+        const long total = jvae_pack_elems(JVAE_PACK_T2S, C, O);
+        const int blocks = (int)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
+        hipLaunchKernelGGL(t2s_wpack_kernel, dim3(blocks), dim3(256), 0, st, w, (__bf16*)dst, C, O, total, 1, 0);
+        JVAE_LAUNCH_CHECK();
+        return 0;
+    }, &rc);
+    if (!ws) return rc ? rc : JVAE_EINVAL;
     T2X3P p{in, (const u32x4*)ws, bias, out, N, C, O, stats, aff ? *aff : InAff{nullptr, nullptr, 0}};
-    struct Fin { int* n; ~Fin() { if (n) *n = g_t2x3_splits; } } fin{nsplit};
     switch (WS) {
-        case 8: return launch_t2s<8>(p, st);
-        case 16: return launch_t2s<16>(p, st);
-        case 32: return launch_t2s<32>(p, st);
+        case 8: return launch_t2s<8>(p, st, nsplit);
+        case 16: return launch_t2s<16>(p, st, nsplit);
+        case 32: return launch_t2s<32>(p, st, nsplit);
     }
     return JVAE_ENOTSUP;
 }

@@ -261,11 +261,11 @@ int launch_wg(const WgP& p, hipStream_t st) {
     using G = WgGeom<S, WS, CB>;
     static_assert((G::QS + G::PSZ) * 4 + 8 * (CB + 32) <= 64 * 1024, "static LDS budget");
     dim3 grid(p.G, (p.Ca + 31) / 32, (p.Cb + CB - 1) / CB);
-    // two instantiations: the deferred-BatchNorm transform costs registers / LDS only where it is used
-    const bool leaky = (p.aff_p.sc && p.aff_p.relu == JVAE_ACT_LEAKY) || (p.aff_q.sc && p.aff_q.relu == JVAE_ACT_LEAKY);
-    if (leaky) hipLaunchKernelGGL((conv5_wgrad_kernel<S, WS, CB, PF, 2>), grid, dim3(256), 0, st, p);
-    else if (p.aff_p.sc || p.aff_q.sc) hipLaunchKernelGGL((conv5_wgrad_kernel<S, WS, CB, PF, 1>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv5_wgrad_kernel<S, WS, CB, PF, 0>), grid, dim3(256), 0, st, p);
+    // three instantiations: the deferred-BatchNorm transform costs registers / LDS only where it is used (leaky on either side: 2)
+    const int ip = jvae_aff_inst(p.aff_p), iq = jvae_aff_inst(p.aff_q);
+    jvae_with_aff(ip > iq ? ip : iq, [&](auto A) {
+        hipLaunchKernelGGL((conv5_wgrad_kernel<S, WS, CB, PF, decltype(A)::value>), grid, dim3(256), 0, st, p);
+    });
     JVAE_LAUNCH_CHECK();
     return 0;
 }

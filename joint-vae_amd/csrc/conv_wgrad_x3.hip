@@ -616,19 +616,9 @@ int launch_wgx3(const WgX3P& p, hipStream_t st) {
     // (the 32x32x16 MFMA shape of this kernel and its JVAE_WGRAD_SH16 switch left the tree in round 5: the 16x16x32 shape has been
     // the default since round 2 and the other was never part of a test)
     static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[3] = {reinterpret_cast<const void*>(&conv5_wgrad_x3_kernel<S, WS, MODE, 0, true>),
-                              reinterpret_cast<const void*>(&conv5_wgrad_x3_kernel<S, WS, MODE, 1, true>),
-                              reinterpret_cast<const void*>(&conv5_wgrad_x3_kernel<S, WS, MODE, 2, true>)};
-        for (const void* f : fns) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-            if (e != hipSuccess) return (int)e;
-        }
-        attr_set = true;
-    }
-    if (leaky) hipLaunchKernelGGL((conv5_wgrad_x3_kernel<S, WS, MODE, 2, true>), grid, dim3(256), G::LDS_BYTES, st, p);
-    else if (aff) hipLaunchKernelGGL((conv5_wgrad_x3_kernel<S, WS, MODE, 1, true>), grid, dim3(256), G::LDS_BYTES, st, p);
-    else hipLaunchKernelGGL((conv5_wgrad_x3_kernel<S, WS, MODE, 0, true>), grid, dim3(256), G::LDS_BYTES, st, p);
+    auto kernel = [](auto A) { return &conv5_wgrad_x3_kernel<S, WS, MODE, decltype(A)::value, true>; };
+    if (const int rc = jvae_aff_lds_attr(attr_set, G::LDS_BYTES, kernel)) return rc;
+    jvae_with_aff(leaky ? 2 : (aff ? 1 : 0), [&](auto A) { hipLaunchKernelGGL(kernel(A), grid, dim3(256), G::LDS_BYTES, st, p); });
     JVAE_LAUNCH_CHECK();
     return 0;
     }

@@ -35,6 +35,7 @@
 #include "conv_x3.h"
 #include <type_traits>
 #include "pack_elems.h"
+#include "conv_stats.h"
 
 namespace {
 
@@ -483,19 +484,9 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
                     sv[ct * 4 + r] = s1;
                     sv[8 + ct * 4 + r] = s2;
                 }
-            {   // lane l15 of every 16-lane row receives the row total of sv[l15]
-                const float tot = row_reduce16(sv);
-                const int j = l15 & 7, ch = (j >> 2) * 16 + kq * 4 + (j & 3);
-                red[(wave * 32 + ch) * 2 + (l15 >> 3)] = tot;
-            }
+            stats_stage16(sv, red, wave, l15, kq);
             lds_barrier();                                        // LDS only: the output stores keep draining
-            if (tid < 32 && o0 + tid < p.CoutReal) {
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) { s1 += red[(w * 32 + tid) * 2]; s2 += red[(w * 32 + tid) * 2 + 1]; }
-                float* dst = p.stats + ((long)(o0 + tid) * ntiles + bx) * 2;
-                dst[0] = s1; dst[1] = s2;
-            }
+            stats_fold<4, 32>(red, p.stats, tid, o0, p.CoutReal, ntiles, bx);
         }
 #pragma unroll
         for (int b = 0; b < NPT; ++b)
@@ -673,55 +664,32 @@ __global__ __launch_bounds__(256, 2) void conv5_x3_kernel(X3P p) {
             sv[r] = s1;
             sv[16 + r] = s2;
         }
-        {   // lane l31 receives the half-wave total of sv[l31]
-            const float tot = half_wave_reduce32(sv);
-            const int r = l31 & 15, ch = (r & 3) + 8 * (r >> 2) + 4 * half;
-            red[(wave * 32 + ch) * 2 + (l31 >> 4)] = tot;
-        }
+        stats_stage32<32>(sv, red, wave, 0, l31, half);
         lds_barrier();                                        // LDS only: the output stores keep draining
-        if (tid < 32 && o0 + tid < p.CoutReal) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { s1 += red[(w * 32 + tid) * 2]; s2 += red[(w * 32 + tid) * 2 + 1]; }
-            float* dst = p.stats + ((long)(o0 + tid) * gridDim.x + bx) * 2;         // slot of the TILE: order independent of the mapping
-            dst[0] = s1; dst[1] = s2;
-        }
+        stats_fold<4, 32>(red, p.stats, tid, o0, p.CoutReal, gridDim.x, bx);
     }
     }
 }
 
-thread_local int g_x3_splits = 0;
-
 template <int S, int OW, int MT, bool SH = false>
-int launch_x3(const X3P& p, hipStream_t st) {
+int launch_x3(const X3P& p, hipStream_t st, int* nsplit) {
     using G = X3Geom<S, OW, MT, SH>;
     static_assert(S == 1 && G::LDS_BYTES + 2048 <= 80 * 1024, "two workgroups per CU");
     static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5_x3_kernel<S, OW, MT, 0, SH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5_x3_kernel<S, OW, MT, 1, SH>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv5_x3_kernel<S, OW, MT, 2, SH>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    auto kernel = [](auto A) { return &conv5_x3_kernel<S, OW, MT, decltype(A)::value, SH>; };
+    if (const int rc = jvae_aff_lds_attr(attr_set, G::LDS_BYTES, kernel)) return rc;
     const long pixels = (long)p.N * G::OHW;
     dim3 grid((unsigned)((pixels + G::PIX - 1) / G::PIX), (unsigned)(p.OP / 32));
     if (G::OHW < G::PIX) grid.x = (unsigned)((p.N + G::NIMG - 1) / G::NIMG);
-    g_x3_splits = (int)grid.x;                                 // BatchNorm partial sums: one per TILE
+    const int tiles = (int)grid.x;                             // BatchNorm partial sums: one per TILE
     // Two tiles per workgroup (16x16x32 form, stride 1) when that still leaves two residency rounds of 512 workgroups:
     // the second tile's prologue hides under the first one's last tap pairs.
     X3P q = p;
     q.tpw = 1;
     if (SH && grid.x % 2 == 0 && (long)grid.x * grid.y >= 2048) { q.tpw = 2; grid.x /= 2; }
-    if (q.aff.sc && q.aff.relu == JVAE_ACT_LEAKY) hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 2, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
-    else if (q.aff.sc) hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 1, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
-    else hipLaunchKernelGGL((conv5_x3_kernel<S, OW, MT, 0, SH>), grid, dim3(256), G::LDS_BYTES, st, q);
+    jvae_with_aff(jvae_aff_inst(q.aff), [&](auto A) { hipLaunchKernelGGL(kernel(A), grid, dim3(256), G::LDS_BYTES, st, q); });
     JVAE_LAUNCH_CHECK();
+    if (nsplit) *nsplit = tiles;
     return 0;
 }
 
@@ -798,34 +766,29 @@ int jvae_conv5_x3_fwd(const float* in, const float* w, int swap, int flip, const
                       float* stats, int* nsplit, const InAff* aff) {
     const int OP = (Cout + 31) / 32 * 32;
     const bool sh = OW <= 32 && x3_sh16();                  // 64-wide maps (config 5 in fp32) keep the 32x32x16 form
-    {   // split weights: the step's cache slot (refreshed once per step, pack_cache.hip) or this call's workspace
-        bool fresh = true;
-        const int kind = sh ? JVAE_PACK_X3S : JVAE_PACK_X3;
-        float* slot = (float*)jvae_pack_cache_get(kind, w, Cin, Cout, swap, flip, &fresh);
-        if (slot) ws = slot;
-        if (!slot || !fresh) {
-            const int rc = sh ? x3s_wpack(w, ws, Cin, Cout, swap, flip, st) : jvae_conv5_x3_wpack(w, ws, Cin, Cout, swap, flip, st);
-            if (rc) return rc;
-        }
-    }
+    // split weights: the step's cache slot (refreshed once per step, pack_cache.hip) or this call's workspace
+    int rc = 0;
+    ws = (float*)jvae_packed(sh ? JVAE_PACK_X3S : JVAE_PACK_X3, w, Cin, Cout, swap, flip, ws, [&](void* dst) {
+        return (sh ? x3s_wpack : jvae_conv5_x3_wpack)(w, (float*)dst, Cin, Cout, swap, flip, st);
+    }, &rc);
+    if (!ws) return rc ? rc : JVAE_EINVAL;
     X3P p{in, (const u32x4*)ws, bias, out, N, Cin, H, W, OP, P, Cout, stats, aff ? *aff : InAff{nullptr, nullptr, 0}, 1};
 #ifdef JVAE_X3_STAMPS
     p.dbg = g_x3_dbg;
 #endif
-    struct Fin { int* n; ~Fin() { if (n) *n = g_x3_splits; } } fin{nsplit};
     if (S != 1) return JVAE_ENOTSUP;
     if (sh) {
         switch (OW) {
-            case 8: return launch_x3<1, 8, 1, true>(p, st);
-            case 16: return launch_x3<1, 16, 2, true>(p, st);
-            case 32: return launch_x3<1, 32, 2, true>(p, st);
+            case 8: return launch_x3<1, 8, 1, true>(p, st, nsplit);
+            case 16: return launch_x3<1, 16, 2, true>(p, st, nsplit);
+            case 32: return launch_x3<1, 32, 2, true>(p, st, nsplit);
         }
     }
     switch (OW) {
-        case 8: return launch_x3<1, 8, 1>(p, st);
-        case 16: return launch_x3<1, 16, 2>(p, st);
-        case 32: return launch_x3<1, 32, 2>(p, st);
-        case 64: return launch_x3<1, 64, 1>(p, st);
+        case 8: return launch_x3<1, 8, 1>(p, st, nsplit);
+        case 16: return launch_x3<1, 16, 2>(p, st, nsplit);
+        case 32: return launch_x3<1, 32, 2>(p, st, nsplit);
+        case 64: return launch_x3<1, 64, 1>(p, st, nsplit);
     }
     return JVAE_ENOTSUP;
 }

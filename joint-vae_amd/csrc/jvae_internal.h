@@ -1,6 +1,8 @@
 // Internal (non-ABI) declarations shared between the translation units of libjvae_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
+#include "common.h"
 
 // C[b](m,n) (+)= sum_k A[b](m,k) B[b](k,n); element strides in floats.  flags: 1 accumulate, 2 ReLU.
 // splitk > 1 adds partial products with float atomics: C must then hold the value to accumulate onto
@@ -34,6 +36,29 @@ int jvae_gemm_launch_part(int M, int N, int K, int batch,
 // This is the BatchNorm(+ReLU) that produced the layer input, deferred into the consumer so that the normalised
 // activation is never written to / re-read from HBM (sc == nullptr: identity).
 struct InAff { const float* sc; const float* sh; int relu; };
+
+// The kernels that stage such an input come in three instantiations, AFF = 0 plain input, 1 deferred BatchNorm (+ReLU by flag),
+// 2 ... + leaky ReLU.  jvae_with_aff calls f(std::integral_constant<int, AFF>{}) for the one a launch needs.
+inline int jvae_aff_inst(const InAff& a) { return !a.sc ? 0 : (a.relu == JVAE_ACT_LEAKY ? 2 : 1); }
+template <class F>
+inline void jvae_with_aff(int inst, F&& f) {
+    if (inst == 2) f(std::integral_constant<int, 2>{});
+    else if (inst == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+// Once per launcher (`done`: a static of the caller): the dynamic-LDS size on kernel(AFF) of all three.  0 or the hipError_t.
+template <class K>
+inline int jvae_aff_lds_attr(bool& done, int bytes, K&& kernel) {
+    for (int inst = 0; inst < 3 && !done; ++inst) {
+        hipError_t e = hipSuccess;
+        jvae_with_aff(inst, [&](auto A) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel(A)), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        });
+        if (e != hipSuccess) return (int)e;
+    }
+    done = true;
+    return 0;
+}
 
 // Geometry of one (transposed) convolution.  "big" side = the tensor that is unfolded (conv input /
 // transposed-conv output), "small" side = the tensor on the folded grid (conv output / transposed-conv input).

@@ -143,3 +143,17 @@ __device__ __forceinline__ void jvae_pack_b8_elem(const float* __restrict__ w, _
 // is off / disarmed / full (the caller then packs into its own workspace, as without a cache).  *fresh = false: the slot is
 // new - the caller must launch the pack into it on `st` now; later steps find it refreshed by jvae_pack_cache_begin.
 void* jvae_pack_cache_get(int kind, const float* w, int C, int O, int swap, int flip, bool* fresh);
+
+// The packed operand a kernel reads: the step's cache slot when it is fresh; else pack(dst) (-> 0, or a launch error) fills the
+// stale or new slot, or - without a slot - the call's workspace `ws`.  Returns the pointer to read, nullptr on a launch error
+// (*rc, when given, then holds the pack's return value).
+template <class Pack>
+inline void* jvae_packed(int kind, const float* w, int C, int O, int swap, int flip, void* ws, Pack&& pack, int* rc = nullptr) {
+    bool fresh = true;
+    void* slot = jvae_pack_cache_get(kind, w, C, O, swap, flip, &fresh);
+    if (slot && fresh) return slot;
+    void* dst = slot ? slot : ws;
+    const int e = pack(dst);
+    if (rc) *rc = e;
+    return e == 0 ? dst : nullptr;
+}

@@ -500,7 +500,12 @@ int jvae_roc_curve_f32(const float* ins, const float* outs, const double* kept_t
  * Scores: src (C, N) fp32 (all-class kl / zdist / iws losses, or the logits as the recorder stores them), C <= 128, read once;
  * row r of the R requested rows goes to out + rows[r] * out_stride (out_stride >= N), with kinds[r] / temps[r] (device arrays):
  *   0  max_c softmax_c(-v / T)   1  max_c softmax_c(v / T)   2  max_c (-v)   3  max_c v   4  sum_c p log p, p = softmax_c(v / T)
- * (batch_dist_measures, cvae.py:1024-1063), fp32 with the max-subtracted softmax; a NaN propagates as in torch.
+ * and, with l = -v, d = l - max_c l, e = exp d and temps[r] an additive constant (any finite value):
+ *   5  log sum_c e + max_c l + temps[r]   6  kind 5 on l = +v   7  log mean_c e + max_c l   8  unbiased std_c l (C = 1: NaN)
+ *   9  (std_c e / mean_c e)^2, unbiased   10  max_c l - median_c l (lower middle element)
+ *   11  sum_c(d e) / (C mean_c e) - log mean_c e   12  -v   13  v   (12, 13: row 0 of the source, meant for C = 1)
+ * (batch_dist_measures, cvae.py:985-1068), fp32 with the max-subtracted softmax; a NaN propagates as in torch; any other kind
+ * above 4 gives a NaN row.
  * Split: scores (M, N), mask (N bytes, non-zero = correctly classified) -> out (M * N floats): ins (M, n_correct) followed by
  * outs (M, N - n_correct), each row in its original order; *n_correct (device int32) receives the count.  One scan of the mask
  * serves all rows.  ws: 4-byte aligned, jvae_misclass_split_workspace_bytes(N) bytes (0 = invalid N).

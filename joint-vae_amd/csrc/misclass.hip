@@ -7,6 +7,12 @@
 //                kind 2  max_c (-v)                   kl, zdist, max
 //                kind 3  max_c v                      logits
 //                kind 4  sum_c p log p, p = softmax v hyz
+//              and the rest of the class-axis table (cvae.py:985-1068), which the OOD pass asks for; l = -v, d = l - max_c l,
+//              e = exp d, T = an additive constant:
+//                kind 5  log sum_c e + max_c l + T    sum (T = 0)          kind 6  the same on l = +v: iws (T = log C)
+//                kind 7  log mean_c e + max_c l       mean                 kind 8  std_c l, unbiased       std
+//                kind 9  (std_c e / mean_c e)^2       nstd                 kind 10 max_c l - median_c l    mag
+//                kind 11 sum_c(d e) / (C mean_c e) - log mean_c e  IYx     kind 12 / 13  -v / v of a (1, N) source: mse, wmse, elbo
 //              A workgroup stages a (C, 64) tile of the source in LDS once; one lane per sample then loops over the classes
 //              for every row, so the source is read from HBM once whatever the number of temperatures.  fp32 throughout, the
 //              max-subtracted softmax torch uses: exp(x - max) / sum, whose largest term is 1 / sum.
@@ -31,6 +37,80 @@ constexpr long MISC_MAX_N = 1L << 24;  // as jvae_roc_curve_f32: counts stay in 
 // torch.max keeps a NaN (fmaxf would drop it)
 __device__ __forceinline__ float misc_max(float best, float x) { return (x > best || x != x) ? x : best; }
 
+// Kahan sum: the class-axis rows below add up to 128 terms per lane in sequence and are held to the error of torch's tree sums
+struct MiscSum {
+    float s = 0.f, c = 0.f;
+    __device__ __forceinline__ void add(float x) {
+        const float y = x - c, t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+
+// kinds 5 .. 13 of one sample: col[c * MISC_TILE] = v_c, l = -v (lse+: l = v), d = l - lmax, e = exp d.  The order of operations
+// is the reference's (cvae.py:985-1068); `add` is the constant of the lse rows.  An unknown kind gives NaN.
+__device__ float misc_axis_row(const float* col, int C, int kind, float add) {
+    if (kind == 12) return -col[0];
+    if (kind == 13) return col[0];
+    const float sign = kind == 6 ? 1.f : -1.f;
+    const float n = (float)C;
+    float lmax = -INFINITY;
+    for (int c = 0; c < C; ++c) lmax = misc_max(lmax, sign * col[c * MISC_TILE]);
+    if (kind == 10) {                  // lmax - the lower middle element, found by its rank; a NaN is in lmax already
+        const int k = (C - 1) / 2;
+        float med = lmax;
+        for (int i = 0; i < C; ++i) {
+            const float x = -col[i * MISC_TILE];
+            int lt = 0, eq = 0;
+            for (int j = 0; j < C; ++j) {
+                const float y = -col[j * MISC_TILE];
+                lt += y < x;
+                eq += y == x;
+            }
+            if (lt <= k && k < lt + eq) med = x;
+        }
+        return lmax - med;
+    }
+    if (kind == 8) {                   // torch.std (ddof = 1) of l - lmax, which is that of l: two passes, 0 / 0 = NaN for C = 1
+        MiscSum m, q;                  // l - lmax as hi + lo, exactly (TwoSum): at an ELBO's spread its rounding would be the error
+        float lo_sum = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float l = -col[c * MISC_TILE], hi = l - lmax, b = hi - l;
+            m.add(hi);
+            lo_sum += (l - (hi - b)) + (-lmax - b);
+        }
+        const float mean = (m.s + lo_sum) / n;
+        for (int c = 0; c < C; ++c) {
+            const float l = -col[c * MISC_TILE], hi = l - lmax, b = hi - l;
+            const float t = (hi - mean) + ((l - (hi - b)) + (-lmax - b));
+            q.add(t * t);
+        }
+        return sqrtf(q.s / (float)(C - 1));
+    }
+    if (kind < 5 || kind > 11) return NAN;
+    MiscSum e;
+    for (int c = 0; c < C; ++c) e.add(expf(sign * col[c * MISC_TILE] - lmax));
+    if (kind == 5 || kind == 6) return logf(e.s) + lmax + add;
+    const float mean = e.s / n;
+    if (kind == 7) return logf(mean) + lmax;
+    if (kind == 9) {
+        MiscSum q;
+        for (int c = 0; c < C; ++c) {
+            const float t = expf(-col[c * MISC_TILE] - lmax) - mean;
+            q.add(t * t);
+        }
+        const float r = expf(logf(sqrtf(q.s / (float)(C - 1))) - logf(mean));
+        return r * r;
+    }
+    const float m = logf(mean);        // kind 11
+    MiscSum w;
+    for (int c = 0; c < C; ++c) {
+        const float d = -col[c * MISC_TILE] - lmax;
+        w.add(d * expf(d));
+    }
+    return w.s / (n * expf(m)) - m;
+}
+
 __global__ __launch_bounds__(MISC_TILE) void misclass_scores_kernel(const float* __restrict__ src, const int* __restrict__ kinds,
                                                                     const float* __restrict__ temps,
                                                                     const int* __restrict__ rows, float* __restrict__ out,
@@ -44,7 +124,9 @@ __global__ __launch_bounds__(MISC_TILE) void misclass_scores_kernel(const float*
         const int kind = kinds[r];
         const float T = temps[r];
         float res;
-        if (kind == 2 || kind == 3) {
+        if (kind >= 5) {
+            res = misc_axis_row(s + lane, C, kind, T);
+        } else if (kind == 2 || kind == 3) {
             float best = -INFINITY;
             for (int c = 0; c < C; ++c) {
                 const float v = s[c * MISC_TILE + lane];

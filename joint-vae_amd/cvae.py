@@ -7,7 +7,7 @@ clip -> Adam — executed by hand-written gfx950 HIP kernels (libjvae_hip.so) be
     ClassificationVariationalNetwork(input_shape, num_labels, type, ..., sigma, optimizer, ...)   cvae.py:135-167
     .forward(x, y=None, x_features=None, z_output=True, sampling_epsilon_norm_out=False, sigma_out=False)  :426-521
     .evaluate(x, y, batch, current_measures, with_beta, kl_var_weighting, gamma_weighting, z_output)       :523-917
-    .train_model(...)   (hot loop :2424-2479; test / OOD phases are out of scope)                            :2081-2547
+    .train_model(...)   (hot loop :2424-2479, test phase; the OOD phase is an opt-in: TRAIN_OOD_PHASE)       :2081-2547
     .train() / .to() / .save() / .load() / .latent_sampling / .device / .nparams
 
 What is NOT rebuilt here (raises NotImplementedError when asked for): (cvae / xvae / vae / vib are complete, jvae: training and labelled evaluation only); resnet
@@ -176,6 +176,9 @@ class ClassificationVariationalNetwork(nn.Module):
     # the epoch's loss sums and running measures included) instead of the eager train_step().  Opt-in; an instance may set
     # it.  What stays eager, and the late NaN exit: INTEGRATION.md ("The captured training loop").
     TRAIN_CAPTURED = False
+    # train_model(): run the reference's OOD phase (ood_detection_rates on `oodsets` every `ood_detection_every` epochs and once
+    # after the loop, cvae.py:2309-2336,2513-2526).  Opt-in; an instance may set it.  Off: one warning, the phase is skipped.
+    TRAIN_OOD_PHASE = False
     # full-size eager batches in front of every capture (allocations, the optimiser's flat buffers, lazy initialisations):
     # they are real batches of the epoch run through train_step() - a capture costs no extra optimiser step
     CAPTURE_WARMUP_BATCHES = 2
@@ -840,14 +843,54 @@ class ClassificationVariationalNetwork(nn.Module):
         _, logits, losses, _ = self.evaluate(x)
         return self.predict_after_evaluate(logits, losses, method=method or 'default')
 
-    def batch_dist_measures(self, logits, losses, methods, to_cpu=False):
-        """OOD scores per sample (higher = more in-distribution) for the cvae methods (cvae.py:972-1085); the
-        '-2s' / '-a-x-y' suffixes only name the thresholding done downstream."""
+    CLASS_AXIS_METHODS = ('sum', 'mean', 'std', 'nstd', 'mag', 'IYx')         # cvae.py:1020-1068, all from -losses['total']
+    # Rows (by the start of their name) that ood_detection_rates leaves on the torch expressions although a kernel row exists:
+    # existing ROC checks hold their thresholds to the bits of exactly these expressions, and a softmax or log-sum-exp summed in
+    # another order moves a last bit (measured on the MI355X: up to 2 fp32 ulp between the kernel's softmax rows and torch's).
+    SCORE_SET_TORCH_ROWS = ('iws', 'elbo', 'soft', 'baseline', 'hyz')
+
+    @staticmethod
+    def _base_method(name):
+        """The score a method name stands for: the '-2s' / '-a-x-y' suffixes only name the thresholding done downstream."""
+        m = name[:-3] if name.endswith('-2s') else name
+        return m.split('-')[0] if '-a-' in m else m
+
+    def _fused_row(self, m):
+        """-> (the loss `m` reads, its (kind, T) of ops.misclass_scores) or (m, None) where only the torch expression exists."""
+        per_class = self.losses_might_be_computed_for_each_class
+        if m == 'elbo':
+            return 'total', ('max-', 1.) if per_class else ('neg', 0.)
+        if m == 'iws':                                                        # cvae.py:1013-1019: log C unless is_jvae
+            return 'iws', ('lse+', 0. if self.is_jvae else math.log(self.num_labels)) if per_class else ('id', 0.)
+        if m in ('zdist', 'kl') and self.is_vae:
+            return m, ('neg', 0.)
+        if m in ('mse', 'wmse'):
+            return {'mse': 'cross_x', 'wmse': 'wmse'}[m], ('neg', 0.)
+        try:
+            return self._misclass_row(m)
+        except ValueError:
+            return m, None
+
+    def batch_dist_measures(self, logits, losses, methods, to_cpu=False, out=None, rows=None, col=0):
+        """OOD scores per sample (higher = more in-distribution) for the reference's methods (cvae.py:972-1085), the class-axis
+        scores `sum`, `mean`, `std`, `nstd`, `mag`, `IYx` of the all-class total loss among them; the '-2s' / '-a-x-y' suffixes
+        only name the thresholding done downstream.  -> {method: (N,) scores}.
+
+        Plain call: the reference's torch expressions.  With `out` (a dense (M, n) fp32 device buffer), `rows` (the row of each
+        method, default 0 .. len(methods) - 1) and `col` (first column): the scores are WRITTEN into out[row, col:col + N] and
+        the returned tensors are those views.  Every row with a kernel form goes through `ops.misclass_scores`
+        (csrc/misclass.hip), ONE launch per source tensor (`total`, `iws`, `kl`, `zdist`, `logits`, `cross_x`, `wmse`), grouped
+        as misclassification_detection_rates groups them; the torch expression is kept for a source with more than
+        ops.MISCLASS_MAX_CLASSES classes or that is not fp32, and for the recorded `odin-*` rows.  Against the plain call the
+        pure max / negation rows (`max`, `elbo`, `kl`, `zdist`, `logits`, `mse`, `wmse`, a single-prior `iws`) and `mag` are
+        bit-identical; the softmax and log-sum-exp rows agree within the fp32 error of either
+        (tests/test_13_ood_phase_gpu.py)."""
+        if out is not None:
+            return self._dist_measures_into(logits, losses, list(methods), out, rows, col, to_cpu)
         C = self.num_labels
         out = {}
         for name in methods:
-            m = name[:-3] if name.endswith('-2s') else name
-            m = m.split('-')[0] if '-a-' in m else m
+            m = self._base_method(name)
             per_class = self.losses_might_be_computed_for_each_class          # cvae.py:996-1016,1036-1039
             if m.startswith('odin'):
                 v = losses[m]                                                 # cvae.py:1076-1078: computed by odin_scores()
@@ -857,7 +900,9 @@ class ClassificationVariationalNetwork(nn.Module):
                 v = losses['iws']
             elif m == 'iws':
                 top = losses['iws'].max(0)[0]
-                v = (losses['iws'] - top).exp().sum(0).log() + top + math.log(C)
+                v = (losses['iws'] - top).exp().sum(0).log() + top
+                if not self.is_jvae:
+                    v = v + math.log(C)
             elif m == 'softiws':
                 v = losses['iws'].softmax(0).max(0)[0]                        # cvae.py:1024-1028: +iws here, -iws / T below
             elif m.startswith('softiws-'):
@@ -882,10 +927,57 @@ class ClassificationVariationalNetwork(nn.Module):
             elif m == 'hyz':                                                  # cvae.py:1061-1063: minus the entropy of p(y|z)
                 p_y_z = logits.softmax(-1)
                 v = (p_y_z * p_y_z.log()).sum(-1)
+            elif m in self.CLASS_AXIS_METHODS:                                # cvae.py:985-988,1020-1021,1052-1068
+                logp = -losses['total']
+                top = logp.max(0)[0]
+                d = logp - top
+                if m == 'sum':
+                    v = d.exp().sum(0).log() + top
+                elif m == 'mean':
+                    v = d.exp().mean(0).log() + top
+                elif m == 'std':
+                    v = logp.std(0)
+                elif m == 'nstd':
+                    v = (d.exp().std(0).log() - d.exp().mean(0).log()).exp().pow(2)
+                elif m == 'mag':
+                    v = top - logp.median(0)[0]
+                else:
+                    d_x = d.exp().mean(0).log()
+                    v = (d * d.exp()).sum(0) / (C * d_x.exp()) - d_x
             else:
                 raise NotImplementedError(f'{name}: OOD method outside this build')
             out[name] = v.cpu() if to_cpu else v
         return out
+
+    def _dist_measures_into(self, logits, losses, methods, out, rows, col, to_cpu):
+        """batch_dist_measures(out=...): kernel rows by source tensor, the remaining rows by the torch expressions."""
+        rows = list(range(len(methods))) if rows is None else [int(r) for r in rows]
+        if len(rows) != len(methods):
+            raise ValueError(f'batch_dist_measures: {len(methods)} methods and {len(rows)} rows')
+        sources = dict(losses)
+        if logits is not None and logits.dim() == 2:
+            sources['logits'] = logits.T                                      # (C, N), as the recorder stores them
+        by_source, rest, n = {}, [], None
+        for name, r in zip(methods, rows):
+            key, spec = self._fused_row(self._base_method(name))
+            src = sources.get(key)
+            flat = spec is not None and spec[0] in ('neg', 'id')
+            if spec is not None and torch.is_tensor(src) and src.dtype == torch.float32 and (
+                    src.dim() == 1 if flat else src.dim() == 2 and src.shape[0] <= ops.MISCLASS_MAX_CLASSES):
+                by_source.setdefault(key, []).append((r, spec))
+                n = src.shape[-1]
+            else:
+                rest.append((name, r))
+        for key, items in by_source.items():
+            src = sources[key]
+            ops.misclass_scores(src[None] if src.dim() == 1 else src, [spec for _, spec in items], out=out,
+                                rows=[r for r, _ in items], col=col)
+        plain = self.batch_dist_measures(logits, losses, [name for name, _ in rest])
+        for name, r in rest:
+            n = plain[name].shape[0]
+            out[r, col:col + n] = plain[name]
+        res = {name: out[r, col:col + n] for name, r in zip(methods, rows)}
+        return {k: v.cpu() for k, v in res.items()} if to_cpu else res
 
     # ------------------------------------------------------------------------------------ ODIN (type 'vib')
     def _odin_slab_rows(self):
@@ -1116,8 +1208,8 @@ class ClassificationVariationalNetwork(nn.Module):
 
     def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False):
         """One pass over `dset` for ood_detection_rates: per batch the label-free evaluation (or the batch read back from a full
-        recorder), `batch_dist_measures`, and the score rows written into ONE preallocated (M, n) device buffer - no value comes
-        to the host here.  on_batch(i, num_batch, scores_so_far) is called after each batch.  -> (M, n) fp32 device scores."""
+        recorder), then `batch_dist_measures(out=...)`: the score rows go straight into ONE preallocated (M, n) device buffer, one
+        kernel launch per source tensor (the `SCORE_SET_TORCH_ROWS` by their torch expressions) - no value comes to the host here.  on_batch(i, num_batch, scores_so_far) is called after each batch.  -> (M, n) fp32 device scores."""
         device = self.device
         name = getattr(dset, 'name', 'set')
         recorded = recorder is not None and len(recorder) >= num_batch
@@ -1133,6 +1225,8 @@ class ClassificationVariationalNetwork(nn.Module):
         buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
         filled, sums, measures = 0, {}, None
         odin = any(m.startswith('odin') for m in methods)
+        by_torch = [r for r, m in enumerate(methods) if self._base_method(m).startswith(tuple(self.SCORE_SET_TORCH_ROWS))]
+        fused = [r for r in range(len(methods)) if r not in by_torch]
         with torch.no_grad():
             for i in range(num_batch):
                 if recorded:
@@ -1149,12 +1243,13 @@ class ClassificationVariationalNetwork(nn.Module):
                     if recording:
                         extra = {} if logits is None else {'logits': logits.T}
                         recorder.append_batch(**losses, y_true=y, **extra)
-                scores = self.batch_dist_measures(logits, losses, methods)
+                n = self.batch_dist_measures(logits, losses, [methods[r] for r in fused], out=buf, rows=fused,
+                                             col=filled)[methods[fused[0]]].shape[0] if fused else 0
+                for m, v in self.batch_dist_measures(logits, losses, [methods[r] for r in by_torch]).items():
+                    n = v.shape[0]
+                    buf[methods.index(m), filled:filled + n] = v
                 if odin:
                     losses = {k: v for k, v in losses.items() if not k.startswith('odin')}     # test_losses: the loss components
-                n = scores[methods[0]].shape[0]
-                for r, m in enumerate(methods):
-                    buf[r, filled:filled + n] = scores[m]
                 filled += n
                 if keep_test:
                     for k, v in losses.items():                                      # cvae.py:1671, summed on the device
@@ -1191,8 +1286,11 @@ class ClassificationVariationalNetwork(nn.Module):
         the in-distribution pass, `record-<set>.pth` written into `sample_dirs` through the `LossRecorder`s of `recorders`
         ({} = make one per set, filled in place), and a full recorder read back instead of evaluating, as in accuracy().
 
-        Underneath, the scores never leave the device: every batch's `batch_dist_measures` rows go into one (M, n) buffer per
-        set, the ROC of all M methods of a set is ONE `ops.roc_curve` call (csrc/roc.hip) made every 100 batches for the
+        train_model() makes this call in its test phase when `TRAIN_OOD_PHASE` is set.
+
+        Underneath, the scores never leave the device: every batch's `batch_dist_measures(out=...)` rows are written into one
+        (M, n) buffer per set by csrc/misclass.hip, one launch per source tensor (`SCORE_SET_TORCH_ROWS` - `iws`, `elbo` and
+        the softmax rows - by their torch expressions, whose bits the ROC thresholds are held to), the ROC of all M methods of a set is ONE `ops.roc_curve` call (csrc/roc.hip) made every 100 batches for the
         progress line and at the last batch, as the reference does with its Python loop (utils/roc_curves.py:38-210), and only
         its (M, K) results and the fp64 row means / deviations come to the host.  'thresholds' holds the K [low, up] pairs
         (the reference stores list(dict), i.e. the two key names).  Methods: what `batch_dist_measures` computes, one-sided,
@@ -1318,6 +1416,8 @@ class ClassificationVariationalNetwork(nn.Module):
             return 'logits', ('soft+', T)
         if m == 'hyz':
             return 'logits', ('hyz', 1.)
+        if m in ('sum', 'mean', 'std', 'nstd', 'mag', 'IYx'):               # the class-axis scores of the all-class total loss
+            return 'total', ('lse-' if m == 'sum' else m, 0.)
         raise ValueError(f'{m}: unknown misclassification method')
 
     def misclassification_detection_rates(self, predict_methods='all', misclass_methods='all', epoch='last', shown_tpr=0.95,
@@ -1895,8 +1995,16 @@ class ClassificationVariationalNetwork(nn.Module):
           epoch -> `validation_accuracy / _measures / _loss`, with `record-<set>.pth` written under `save_dir/samples/{last,
           <epoch>}` (cvae.py:2293-2382); `train_accuracy=True` adds `accuracy(trainset)` -> `train_accuracy`;
         * the hot loop cvae.py:2424-2501 = train_step(); the final test pass of cvae.py:2528-2545.
-        The OOD phase (`oodsets`, cvae.py:2328-2336,2513-2526) is not wired into this loop yet: a warning says so once and the
-        phase is skipped - call `ood_detection_rates()` after training.
+        The OOD phase (`oodsets`, cvae.py:2309-2336,2513-2526) is an opt-in, `TRAIN_OOD_PHASE` (class attribute, settable per
+        instance).  Off (the default): a warning says so once and the phase is skipped - call `ood_detection_rates()` after
+        training.  On: every `ood_detection_every` epochs and at epoch == epochs the test phase starts with
+        `ood_detection_rates(oodsets, testset, batch_size=test_batch_size, num_batch='all', recorders=..., sample_dirs=...)`
+        over this model's `ood_methods` (rows outside the build are left out, said in that function's one log line) ->
+        `ood_results[epoch]` (`ood.json` in `save()`), `record-<set>.pth` / `record-<oodset>.pth` under `save_dir/samples/{last,
+        <epoch>}` (the directories are then made on OOD epochs too); the `accuracy(testset)` of the same epoch reads the test
+        set's full recorder back instead of evaluating again.  The same call runs once more after the loop, before the final
+        accuracy pass, unless a signal above 1 came in.  OOD sets given by name raise NotImplementedError, as elsewhere;
+        `sample_recorders` stay outside this build.
 
         data_augmentation: the reference hands the list to its dataset factory, which prepends RandomHorizontalFlip ('flip')
         and RandomCrop(size, padding=size//8 [0 for imagenet sets], padding_mode='edge') ('crop') to the training transforms
@@ -1980,7 +2088,13 @@ class ClassificationVariationalNetwork(nn.Module):
         from jvae_compat.recorders import LossRecorder
         sets = [set_name] + (['validation'] if validation else [])
         recorders = {s: LossRecorder(test_batch_size) for s in sets}      # tensors allocated by the first recorded batch
-        if oodsets:
+        ood_phase = bool(self.TRAIN_OOD_PHASE) and bool(oodsets)
+        if ood_phase:
+            if testset is None or isinstance(testset, str) or any(isinstance(o, str) for o in oodsets):
+                raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
+            for o in oodsets:                                             # cvae.py:2226-2232: one recorder per OOD set
+                recorders[getattr(o, 'name', 'set')] = LossRecorder(test_batch_size)
+        elif oodsets:
             logging.warning('OOD detection rates (%s) are outside this build (SURVEY.md 2a): phase skipped; the recorders of '
                             'accuracy() hold the losses the reference computes them from',
                             ','.join(str(getattr(s, 'name', s)) for s in oodsets))
@@ -2006,7 +2120,8 @@ class ClassificationVariationalNetwork(nn.Module):
                 recorders[s].reset()
             # ---- test phase (cvae.py:2302-2382)
             full_test = bool((epoch - done_epochs) and epoch % full_test_every == 0) or epoch == epochs
-            if (full_test or not epoch) and save_dir:
+            ood_detection = ood_phase and (bool((epoch - done_epochs) and epoch % ood_detection_every == 0) or epoch == epochs)
+            if (full_test or not epoch or ood_detection) and save_dir:
                 sample_dirs = [os.path.join(save_dir, 'samples', d) for d in ('last', '{:04d}'.format(epoch))]
                 for d in sample_dirs:
                     os.makedirs(d, exist_ok=True)
@@ -2014,6 +2129,9 @@ class ClassificationVariationalNetwork(nn.Module):
                 sample_dirs = []
             with torch.no_grad():
                 self.test_losses, self.test_measures = {}, {}
+                if ood_detection:                # cvae.py:2328-2336; the accuracy pass below then reads the test recorder back
+                    self.ood_detection_rates(oodsets=oodsets, testset=testset, batch_size=test_batch_size, num_batch='all',
+                                             outputs=outputs, recorders=recorders, sample_dirs=sample_dirs, print_result='*')
                 if full_test and testset is not None:
                     test_accuracy = self.accuracy(testset, batch_size=test_batch_size, num_batch='all', method=acc_methods,
                                                   outputs=outputs, sample_dirs=sample_dirs, update_self_testing=full_test,
@@ -2084,6 +2202,10 @@ class ClassificationVariationalNetwork(nn.Module):
             sample_dirs = [os.path.join(save_dir, 'samples', d) for d in ('last', '{:04d}'.format(epoch + 1))]
             for d in sample_dirs:
                 os.makedirs(d, exist_ok=True)
+        if ood_phase and not signalled(1):       # cvae.py:2513-2526
+            with torch.no_grad():
+                self.ood_detection_rates(oodsets=oodsets, testset=testset, batch_size=test_batch_size, num_batch='all',
+                                         outputs=outputs, recorders=recorders, sample_dirs=sample_dirs, print_result='*')
         if testset is not None and not signalled(1):
             with torch.no_grad():
                 self.accuracy(testset, batch_size=test_batch_size, method=acc_methods, recorder=recorders[set_name],

@@ -1232,7 +1232,8 @@ def roc_check_status(status):
 
 
 # ------------------------------------------------------------------------------------------- misclassification (csrc/misclass.hip)
-MISCLASS_KINDS = {'soft-': 0, 'soft+': 1, 'max-': 2, 'max+': 3, 'hyz': 4}
+MISCLASS_KINDS = {'soft-': 0, 'soft+': 1, 'max-': 2, 'max+': 3, 'hyz': 4, 'lse-': 5, 'lse+': 6, 'mean': 7, 'std': 8, 'nstd': 9,
+                  'mag': 10, 'IYx': 11, 'neg': 12, 'id': 13}
 MISCLASS_MAX_CLASSES = 128
 MISCLASS_MAX_KEPT = 16
 
@@ -1243,11 +1244,19 @@ def _mask_u8(mask, N, what):
     return _c(mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8))
 
 
-def misclass_scores(src, specs, out=None, rows=None):
+_misclass_specs = {}         # (kinds, constants, rows, device) -> their three device arrays: a pass repeats one launch per batch
+
+
+def misclass_scores(src, specs, out=None, rows=None, col=0):
     """Score rows of one (C, N) fp32 source (all-class losses, or the logits as the recorder stores them) in ONE launch.
     specs: [(kind, T)] with kind in MISCLASS_KINDS - 'soft-': max_c softmax_c(-v / T), 'soft+': max_c softmax_c(v / T),
     'max-': max_c(-v), 'max+': max_c v, 'hyz': sum_c p log p with p = softmax_c(v / T) (batch_dist_measures, cvae.py:1024-1063).
-    out (M, N) fp32 with `rows` = the row of each spec: written in place; without: a new (len(specs), N) tensor.  C <= 128."""
+    The class-axis rows of cvae.py:985-1068, with l = -v, d = l - max_c l, e = exp d; their T is not a temperature - 'lse-':
+    log sum_c e + max_c l + T (`sum`: T = 0), 'lse+': the same on l = v (all-class `iws`: T = log C), 'mean': log mean_c e +
+    max_c l, 'std': torch.std of l over the classes (C = 1: NaN), 'nstd': (std_c e / mean_c e)^2, 'mag': max_c l - torch.median
+    of l, 'IYx': sum_c(d e) / (C mean_c e) - log mean_c e; the other new kinds ignore T.  'neg' / 'id': -v / v of a (1, N) source.
+    out (M, n >= col + N) fp32 with `rows` = the row of each spec: columns col .. col + N of those rows are written in place;
+    without: a new (len(specs), N) tensor.  C <= 128."""
     src = _c(_f32(src, 'misclass_scores'))
     L.ptr(src)
     if src.dim() != 2 or not 1 <= src.shape[0] <= MISCLASS_MAX_CLASSES:
@@ -1256,19 +1265,27 @@ def misclass_scores(src, specs, out=None, rows=None):
     R, dev = len(specs), src.device
     if out is None:
         out, rows = torch.empty((R, N), dtype=torch.float32, device=dev), list(range(R))
-    rows = [int(r) for r in rows]
-    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != N or not out.is_contiguous() or len(rows) != R \
-            or any(not 0 <= r < out.shape[0] for r in rows):
-        raise L.JvaeHipError(f'misclass_scores: a dense (M, {N}) fp32 buffer and {R} rows inside it expected')
+    rows, col = [int(r) for r in rows], int(col)
+    if out.dtype != torch.float32 or out.dim() != 2 or not 0 <= col <= out.shape[1] - N or not out.is_contiguous() \
+            or len(rows) != R or any(not 0 <= r < out.shape[0] for r in rows):
+        raise L.JvaeHipError(f'misclass_scores: a dense (M, >= {col} + {N}) fp32 buffer and {R} rows inside it expected')
     for kind, T in specs:
-        if kind not in MISCLASS_KINDS or not float(T) > 0:
+        if kind not in MISCLASS_KINDS or not (float(T) > 0 if MISCLASS_KINDS[kind] < 5 else math.isfinite(float(T))):
             raise L.JvaeHipError(f'misclass_scores: unknown row ({kind!r}, {T!r})')
+        if kind in ('neg', 'id') and C != 1:
+            raise L.JvaeHipError(f'misclass_scores: {kind!r} is a row of a (1, N) source, got {tuple(src.shape)}')
     if R and N:
-        kinds = torch.tensor([MISCLASS_KINDS[k] for k, _ in specs], dtype=torch.int32, device=dev)
-        temps = torch.tensor([float(T) for _, T in specs], dtype=torch.float32, device=dev)
-        rows_d = torch.tensor(rows, dtype=torch.int32, device=dev)
-        L.check(L.load().jvae_misclass_scores_f32(L.ptr(src), L.ptr(kinds), L.ptr(temps), L.ptr(rows_d), L.ptr(out), R, C, N, N,
-                                                  L.stream_ptr()), 'jvae_misclass_scores_f32')
+        key = (tuple(MISCLASS_KINDS[k] for k, _ in specs), tuple(float(T) for _, T in specs), tuple(rows), dev)
+        if key not in _misclass_specs:
+            if len(_misclass_specs) >= 256:
+                _misclass_specs.clear()
+            _misclass_specs[key] = (torch.tensor(key[0], dtype=torch.int32, device=dev),
+                                    torch.tensor(key[1], dtype=torch.float32, device=dev),
+                                    torch.tensor(key[2], dtype=torch.int32, device=dev))
+        kinds, temps, rows_d = _misclass_specs[key]
+        L.ptr(out)
+        L.check(L.load().jvae_misclass_scores_f32(L.ptr(src), L.ptr(kinds), L.ptr(temps), L.ptr(rows_d), out.data_ptr() + 4 * col,
+                                                  R, C, N, out.shape[1], L.stream_ptr()), 'jvae_misclass_scores_f32')
     return out
 
 

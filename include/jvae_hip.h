@@ -532,6 +532,25 @@ int jvae_odin_head_f32(const float* logits, const float* temps, float* scores, f
 int jvae_odin_perturb_f32(float* acc, const float* g, const float* x, const float* eps, float* out, long numel, int E,
                           void* stream);
 
+/* ---- WIM score rows: the scores of a model fine-tuned with an alternate prior (csrc/wim.hip) -------------------------
+ * Replaces the torch expressions of WIMJob.batch_dist_measures (reference ft/wim.py:132-201): about ten small launches per
+ * method and batch become ONE launch for every row of a batch.
+ * srcs / alts / factors: HOST arrays of S <= 4 entries - srcs[s] a (C, N) fp32 device tensor (the all-class kl, zdist, iws or
+ * total losses), factors[s] its factor f (-1, -1/2, +1; -1 on `total` stands for elbo), alts[s] the (N,) fp32 loss of the same
+ * name under the alternate prior, or NULL.  y_est: (N,) int64 estimated labels on the device.  specs: HOST array of R <= 16
+ * triples (source index, kind, out row); row r goes to out + row * out_stride (out_stride >= N, rows distinct).  With
+ * x = f * v, y = y_est[n], a = alts[s][n]:
+ *   0  Y       x[y]                    `k~`          1  SOFT_Y  softmax_c(x)[y]             `softk~`
+ *   2  LSE_AT  logsumexp_c(x) - f a    `k@`          3  Y_AT    x[y] - f a                  `k~@`
+ * Kinds 0 and 3 are the torch expressions bit for bit for the factors above (f v is exact); kinds 1 and 2 are the max-shifted
+ * fp32 forms.  A source is read at most twice whatever the number of its rows; no atomics, one writer per output element.
+ * A label outside [0, C) is never used as an index: kinds 0, 1, 3 of that sample are NaN and *status (device int32, owned and
+ * cleared by the caller) is set to 1 (bit 0).  Non-finite losses give unspecified values, never an access out of bounds.
+ * Neither allocates nor synchronises.  1 <= C <= 128, else -2 (JVAE_ENOTSUP); any other malformed argument (a kind 2 / 3 row
+ * of a source without alternate, a repeated out row, S, R or N out of range): -1 (JVAE_EINVAL). */
+int jvae_wim_scores_f32(const float* const* srcs, const float* const* alts, const float* factors, int S, const long long* y_est,
+                        const int* specs, int R, float* out, long out_stride, int C, long N, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -754,7 +754,20 @@ class ClassificationVariationalNetwork(nn.Module):
         """evaluate(x) without labels (cvae.py:548-600, 793-873): every class is tried as the prior component.
         Losses kl / zdist / var_kl / total / iws [/ cross_y] are (C, N); wmse / cross_x / dzdist stay (N,).
         The heavy parts (conv stacks on (L+1)N latents, BatchNorm, latent / KL kernel on C*N rows, reconstruction,
-        Mahalanobis distances of the L*C*N sampled latents, the importance-weight assembly) run on the HIP kernels."""
+        Mahalanobis distances of the L*C*N sampled latents, the importance-weight assembly) run on the HIP kernels.
+
+        Two halves: what does not depend on the prior (`_all_classes_forward`: features, encoder, the epsilon draw, decoder,
+        reconstruction terms) and the tail that does (`_all_classes_tail`: KL, distances, log p(z|y), importance weights, total).
+        A fine-tuned model with two priors (jvae_compat/wim.py) runs the first half once and the tail once per prior."""
+        fwd = self._all_classes_forward(x, epsilon)
+        losses, measures = self._all_classes_tail(fwd, self.encoder.prior, self.num_labels, batch, current_measures, with_beta)
+        out = (fwd['x_reco'], _mean_over_draws(fwd['logits']), losses, measures)
+        if z_output:
+            out += (fwd['mu'], fwd['log_var'], fwd['z'])
+        return out
+
+    def _all_classes_forward(self, x, epsilon):
+        """The prior-independent half of the label-free evaluation -> the tensors `_all_classes_tail` reads."""
         if self.y_is_coded or self.is_jvae:
             # The reference cannot do it either: cvae.py:593-600 builds the (C, N) label grid and forward() (cvae.py:451)
             # then calls y.view(N) on it - "RuntimeError: shape '[N]' is invalid for input of size C*N" for conv and MLP
@@ -763,10 +776,9 @@ class ClassificationVariationalNetwork(nn.Module):
                                       'reference fails on it: cvae.py:451): pass y')
         if x.dim() != self.input_dim + 1:
             x = x.reshape(-1, *self.input_shape)
-        N, C, K = x.shape[0], self.num_labels, self.latent_dim
+        N = x.shape[0]
         L = self.latent_sampling
         D = int(np.prod(self.input_shape))
-        pr = self.encoder.prior
         with torch.no_grad():
             feats = self._features_of(x).reshape(N, -1)
             dummy = torch.zeros(N, dtype=torch.int64, device=x.device)
@@ -775,6 +787,7 @@ class ClassificationVariationalNetwork(nn.Module):
             x_reco = x_.view(L + 1, N, *self._reco_shape())
             s, s_kind, sigma_rms = self._sigma_operand(sigma_coded, N)
             categorical = self.output_distribution == 'categorical'
+            s_report = s
             if categorical:
                 # cvae.py:654-660,672-676: log p(x|z_l) = -(256-level pixel cross entropy); the kernels below take it as the
                 # equivalent "weighted mse" of a unit-sigma gaussian: -D/2 (w + log 2 pi) = -ce  <=>  w = 2 ce / D - log 2 pi
@@ -783,25 +796,37 @@ class ClassificationVariationalNetwork(nn.Module):
                 levels = x_reco[1:].argmax(-ndim - 1).float() / 255
                 wmse_cat = mse_loss(levels, x, ndim=ndim, batch_mean=False).mean(0)
                 wmse_s = 2. * ce_x / D - LOG2PI
-                s_report, s, s_kind = s, torch.ones(1, device=x.device), ops.SIGMA_VALUE
+                s, s_kind = torch.ones(1, device=x.device), ops.SIGMA_VALUE
             else:
                 wmse_s = ops.recon_wmse(x_reco, x, s, s_kind)                             # (L, N)
-            y_all = torch.arange(C, device=x.device).unsqueeze(1).expand(C, N)
-            kd = pr.kl(mu, log_var, y=y_all if pr.conditional else None)                  # (C, N) each
             zero_kl = torch.zeros(N, device=x.device)
             wmse, cross_x, _, mse = ops.elbo(wmse_s, zero_kl, None, s, s_kind, D, 1., 0., with_mse=True)
             if categorical:
                 wmse, mse = wmse_cat, None             # what the reference reports: the arg-max image's mean-square error
+            cross_y = x_loss(None, logits, batch_mean=False) if self.y_is_decoded else None       # (C, N)
+        return dict(x=x, N=N, L=L, D=D, dummy=dummy, mu=mu, log_var=log_var, z=z, eps=eps, x_reco=x_reco, logits=logits, s=s,
+                    s_kind=s_kind, s_report=s_report, sigma_rms=sigma_rms, wmse_s=wmse_s, wmse=wmse, cross_x=cross_x, mse=mse,
+                    cross_y=cross_y)
+
+    def _all_classes_tail(self, fwd, pr, C, batch, current_measures, with_beta, with_measures=True):
+        """The prior-dependent half: the losses of `fwd` under the prior `pr` with `C` candidate classes (one per component of a
+        conditional prior) -> (losses, measures); measures None without `with_measures`."""
+        x, N, L, D = fwd['x'], fwd['N'], fwd['L'], fwd['D']
+        K = self.latent_dim
+        mu, log_var, z, cross_x, s, s_kind = fwd['mu'], fwd['log_var'], fwd['z'], fwd['cross_x'], fwd['s'], fwd['s_kind']
+        with torch.no_grad():
+            y_all = torch.arange(C, device=x.device).unsqueeze(1).expand(C, N)
+            kd = pr.kl(mu, log_var, y=y_all if pr.conditional else None)                  # (C, N) each
             losses = {'kl': kd['kl'], 'zdist': kd['distance'], 'var_kl': kd['var_kl']}
             dictionary = pr.mean if pr.conditional else None
             terms = {'distance': kd['distance'].reshape(-1), 'var_kl': kd['var_kl'].reshape(-1)}
             if dictionary is not None:
-                _, _, _, _, _, dz = ops.latent(mu, log_var, torch.zeros((1, N, K), device=x.device), dummy,
+                _, _, _, _, _, dz = ops.latent(mu, log_var, torch.zeros((1, N, K), device=x.device), fwd['dummy'],
                                                dictionary, pr._var_parameter, var_dim=pr.var_dim, sampled=False)
                 losses['dzdist'] = dz
-            losses['wmse'], losses['cross_x'] = wmse, cross_x
+            losses['wmse'], losses['cross_x'] = fwd['wmse'], cross_x
             if self.y_is_decoded:
-                losses['cross_y'] = x_loss(None, logits, batch_mean=False)                # (C, N)
+                losses['cross_y'] = fwd['cross_y']                                        # (C, N)
             beta = self.beta if with_beta else 1.
             # one prior component per class: (C, N); a single prior (type 'vae'): (N,)
             losses['total'] = (cross_x.unsqueeze(0) if pr.conditional else cross_x) + beta * kd['kl']
@@ -816,15 +841,13 @@ class ClassificationVariationalNetwork(nn.Module):
             else:
                 log_pz = pr.log_density(z_s, None)                                        # (L, N)
             # rows + max / mean-exp fold over the L samples in one kernel pair (jvae_iws_f32)
-            losses['iws'] = ops.iws(wmse_s, eps, log_var, log_pz, s, s_kind, D)
+            losses['iws'] = ops.iws(fwd['wmse_s'], fwd['eps'], log_var, log_pz, s, s_kind, D)
+            if not with_measures:
+                return losses, None
             prev = current_measures._dev if isinstance(current_measures, Measures) else None
-            packed = self._pack_measures(x, wmse, terms, dictionary, prev, batch, mse=mse, sigma_rms=sigma_rms,
-                                         sigma_t=s_report if categorical else s)
-        measures = Measures(packed, dictionary is not None, _grad_nan_exit)
-        out = (x_reco, _mean_over_draws(logits), losses, measures)
-        if z_output:
-            out += (mu, log_var, z)
-        return out
+            packed = self._pack_measures(x, fwd['wmse'], terms, dictionary, prev, batch, mse=fwd['mse'],
+                                         sigma_rms=fwd['sigma_rms'], sigma_t=fwd['s_report'])
+        return losses, Measures(packed, dictionary is not None, _grad_nan_exit)
 
     def predict_after_evaluate(self, logits, losses, method='default'):
         """Class prediction from the all-class losses (cvae.py:938-970)."""
@@ -1206,6 +1229,17 @@ class ClassificationVariationalNetwork(nn.Module):
             raise ValueError(f'{m}: <score>-a-<x>-<y> with x and y in 1 .. 255 expected')
         return ('quantile', int(factors[0]), int(factors[1]))
 
+    def _score_row_by_torch(self, m):
+        """Whether the scoring pass leaves the row of method `m` on its torch expression (`SCORE_SET_TORCH_ROWS`)."""
+        return self._base_method(m).startswith(tuple(self.SCORE_SET_TORCH_ROWS))
+
+    def _evaluate_for_scores(self, x, batch, measures):
+        """One batch of the scoring pass: `x` as the data loader yields it -> (x on the device, logits, losses, measures).  A
+        subclass whose items carry more than the image (jvae_compat/wim.py: (x, y_est) pairs) overrides this."""
+        x = self._device_batch(x.to(self.device))
+        _, logits, losses, measures = self.evaluate(x, batch=batch, current_measures=measures)
+        return x, logits, losses, measures
+
     def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False):
         """One pass over `dset` for ood_detection_rates: per batch the label-free evaluation (or the batch read back from a full
         recorder), then `batch_dist_measures(out=...)`: the score rows go straight into ONE preallocated (M, n) device buffer, one
@@ -1225,7 +1259,7 @@ class ClassificationVariationalNetwork(nn.Module):
         buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
         filled, sums, measures = 0, {}, None
         odin = any(m.startswith('odin') for m in methods)
-        by_torch = [r for r, m in enumerate(methods) if self._base_method(m).startswith(tuple(self.SCORE_SET_TORCH_ROWS))]
+        by_torch = [r for r, m in enumerate(methods) if self._score_row_by_torch(m)]
         fused = [r for r in range(len(methods)) if r not in by_torch]
         with torch.no_grad():
             for i in range(num_batch):
@@ -1235,8 +1269,8 @@ class ClassificationVariationalNetwork(nn.Module):
                     logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
                 else:
                     x, y = next(loader)[:2]
-                    x, y = self._device_batch(x.to(device)), y.to(device)
-                    _, logits, losses, measures = self.evaluate(x, batch=i, current_measures=measures)
+                    x, logits, losses, measures = self._evaluate_for_scores(x, i, measures)
+                    y = y.to(device)
                     if odin:
                         # cvae.py:1645-1663: the whole grid per batch (it is what the recorder holds), on the device
                         losses = dict(losses, **self.odin_scores(x))

@@ -122,6 +122,7 @@ _SIGS = {
     'jvae_misclass_confusion_f32': (c_int, [P] * 5 + [c_int, c_long, c_int, P]),
     'jvae_odin_head_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, P]),
     'jvae_odin_perturb_f32': (c_int, [P, P, P, P, P, c_long, c_int, P]),
+    'jvae_wim_scores_f32': (c_int, [P, P, P, c_int, P, P, c_int, P, c_long, c_int, c_long, P, P]),
 }
 
 

@@ -1289,6 +1289,85 @@ def misclass_scores(src, specs, out=None, rows=None, col=0):
     return out
 
 
+# ------------------------------------------------------------------------------------------- WIM score rows (csrc/wim.hip)
+WIM_KINDS = {'Y': 0, 'SOFT_Y': 1, 'LSE_AT': 2, 'Y_AT': 3}
+WIM_MAX_SOURCES = 4
+_wim_status = {}             # device index -> the int32 status word `wim_scores` uses when the caller passes none
+
+
+def wim_status(device):
+    """The per-device status word of `wim_scores` calls made without one of their own (created cleared, on first use)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _wim_status:
+        _wim_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _wim_status[idx]
+
+
+def wim_scores(sources, y_est, specs, out=None, rows=None, col=0, status=None):
+    """Every WIM score row of a batch in ONE launch (ft/wim.py:132-201).  sources: up to 4 triples (src, f, alt) - src a (C, N)
+    fp32 all-class loss, f its factor (-1 kl, -1/2 zdist, +1 iws, -1 on `total` for elbo), alt the (N,) fp32 loss under the
+    alternate prior or None; y_est (N,) int64; specs: [(source index, kind)] with kind in WIM_KINDS and x = f * src -
+    'Y': x[y_est], 'SOFT_Y': softmax_c(x)[y_est], 'LSE_AT': logsumexp_c(x) - f * alt, 'Y_AT': x[y_est] - f * alt.
+    out / rows / col as for `misclass_scores`: columns col .. col + N of the given rows of a dense (M, n) fp32 buffer are written
+    in place; without `out` a new (len(specs), N) tensor.  status: an int32 device word the kernel sets to 1 when a label is
+    outside [0, C) (those samples' 'Y', 'SOFT_Y', 'Y_AT' values are NaN); default `wim_status(device)`; `wim_check_status`
+    raises on it.  Nothing is synchronised.  C outside 1 .. MISCLASS_MAX_CLASSES: JvaeHipError (unsupported configuration)."""
+    S, R = len(sources), len(specs)
+    if not 1 <= S <= WIM_MAX_SOURCES:
+        raise L.JvaeHipError(f'wim_scores: 1 .. {WIM_MAX_SOURCES} sources expected, got {S}')
+    srcs = [_c(_f32(s, 'wim_scores')) for s, _, _ in sources]
+    for s in srcs:
+        L.ptr(s)
+    if any(s.dim() != 2 or s.shape != srcs[0].shape for s in srcs):
+        raise L.JvaeHipError(f'wim_scores: (C, N) sources of one shape expected, got {[tuple(s.shape) for s in srcs]}')
+    C, N = srcs[0].shape
+    dev = srcs[0].device
+    alts = [None if a is None else _c(_f32(a, 'wim_scores')) for _, _, a in sources]
+    if any(a is not None and (tuple(a.shape) != (N,) or a.device != dev) for a in alts):
+        raise L.JvaeHipError(f'wim_scores: ({N},) alternate losses on {dev} expected')
+    if y_est.dtype != torch.int64 or tuple(y_est.shape) != (N,) or y_est.device != dev:
+        raise L.JvaeHipError(f'wim_scores: ({N},) int64 labels on {dev} expected, got {tuple(y_est.shape)} {y_est.dtype}')
+    y_est = _c(y_est)
+    if out is None:
+        out, rows = torch.empty((R, N), dtype=torch.float32, device=dev), list(range(R))
+    rows, col = [int(r) for r in rows], int(col)
+    if out.dtype != torch.float32 or out.dim() != 2 or not 0 <= col <= out.shape[1] - N or not out.is_contiguous() \
+            or out.device != dev or len(rows) != R or len(set(rows)) != R or any(not 0 <= r < out.shape[0] for r in rows):
+        raise L.JvaeHipError(f'wim_scores: a dense (M, >= {col} + {N}) fp32 buffer and {R} distinct rows inside it expected')
+    flat = []
+    for (s, kind), r in zip(specs, rows):
+        if kind not in WIM_KINDS or not 0 <= int(s) < S or (kind in ('LSE_AT', 'Y_AT') and alts[int(s)] is None):
+            raise L.JvaeHipError(f'wim_scores: unknown row ({s!r}, {kind!r}) or no alternate loss for it')
+        flat += [int(s), WIM_KINDS[kind], r]
+    if status is None:
+        status = wim_status(dev)
+    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise L.JvaeHipError('wim_scores: an int32 status word on the device of the sources expected')
+    src_p = (ctypes.c_void_p * S)(*[s.data_ptr() for s in srcs])
+    alt_p = (ctypes.c_void_p * S)(*[None if a is None else a.data_ptr() for a in alts])
+    fac = (ctypes.c_float * S)(*[float(f) for _, f, _ in sources])
+    spec = (ctypes.c_int * max(len(flat), 1))(*flat)
+    L.check(L.load().jvae_wim_scores_f32(src_p, alt_p, fac, S, L.ptr(y_est), spec, R, out.data_ptr() + 4 * col, out.shape[1], C, N,
+                                         L.ptr(status), L.stream_ptr()), 'jvae_wim_scores_f32')
+    return out
+
+
+def wim_check_status(status=None):
+    """Raise JvaeHipError when a `wim_scores` launch met an estimated label outside [0, C).  status: the word given to
+    `wim_scores` (a device tensor: read here - this is the synchronisation - and cleared), a host value, or None for the
+    per-device default words."""
+    if status is None:
+        words = list(_wim_status.values())
+    else:
+        words = [status]
+    for w in words:
+        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
+        if torch.is_tensor(w) and v:
+            w.zero_()
+        if v & 1:
+            raise L.JvaeHipError('wim_scores: an estimated label outside [0, C) was met (its score rows are NaN)')
+
+
 def misclass_split(scores, mask):
     """(M, N) fp32 score rows and an (N,) mask (non-zero / True = correctly classified) -> ins (M, n_correct), outs
     (M, N - n_correct), n_correct: both row sets compacted in their original order by ONE scan of the mask (two views of one

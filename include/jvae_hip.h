@@ -330,6 +330,32 @@ int jvae_latent_bwd_wdev_f32(const float* mu, const float* lv_raw, const float* 
                              float* gmu, float* glv_raw, float* gmeans, float* gT,
                              int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha, float w,
                              int sampled, int has_forced, const float* w_dev, void* ws, size_t ws_bytes, void* stream);
+/* The latent kernel over ONE batch measured against TWO priors (the WIM fine-tuning step: labelled samples against the
+ * class-conditional prior, mixture samples against the alternate one).  Sample n < split takes prior A (means_a (C_a,K), T_a,
+ * prior_a, var_dim_a, tau_a, alpha_a) with class y[n]; sample n >= split takes prior B with class y[n].  `dict` belongs to
+ * the A part; dzdist[n] = 0 for n >= split.  One launch, one wavefront per sample, the choice of prior wave-uniform; each
+ * sample runs the per-sample body of the single-prior kernels, so its results are theirs bit for bit.  0 <= split <= N;
+ * split = N / split = 0 is the single-prior kernel under A / B on the whole batch.  A label outside [0, C_a) resp. [0, C_b) is
+ * never used as an index: every output of that sample is NaN.
+ * Backward: both priors are frozen - gmeans and gT must be NULL (else -1); gmu and glv_raw only.  No workspace is needed
+ * (ws may be NULL): nothing is folded per class, the uniform prior's two forward sums are recomputed in the wave.
+ * Neither call allocates, synchronises or uses atomics. */
+int jvae_latent_mixed_fwd_f32(const float* mu, const float* lv_raw, const float* eps, const long long* y,
+                              const float* means_a, const float* T_a, const float* dict, const float* means_b, const float* T_b,
+                              float* lv, float* z, float* kl, float* zdist, float* var_kl, float* dzdist,
+                              int N, int K, int L, int split,
+                              int C_a, int prior_a, int var_dim_a, float tau_a, float alpha_a,
+                              int C_b, int prior_b, int var_dim_b, float tau_b, float alpha_b,
+                              float w, int sampled, int has_forced, float forced_lv, void* stream);
+int jvae_latent_mixed_bwd_f32(const float* mu, const float* lv_raw, const float* lv, const float* eps, const long long* y,
+                              const float* means_a, const float* T_a, const float* means_b, const float* T_b,
+                              const float* gz, const float* g_kl, const float* g_zdist, const float* g_vkl,
+                              const float* gmu_direct, const float* glv_direct,
+                              float* gmu, float* glv_raw, float* gmeans, float* gT,
+                              int N, int K, int L, int split,
+                              int C_a, int prior_a, int var_dim_a, float tau_a, float alpha_a,
+                              int C_b, int prior_b, int var_dim_b, float tau_b, float alpha_b,
+                              float w, int sampled, int has_forced, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- reconstruction term ---------------------------------------------------------------------------
  * wmse[l][n] = mean_D((x_reco[l+1][n] - x[n])^2) / sigma^2   (mse_loss, module/losses.py:8-27, called at
@@ -550,6 +576,14 @@ int jvae_odin_perturb_f32(float* acc, const float* g, const float* x, const floa
  * of a source without alternate, a repeated out row, S, R or N out of range): -1 (JVAE_EINVAL). */
 int jvae_wim_scores_f32(const float* const* srcs, const float* const* alts, const float* factors, int S, const long long* y_est,
                         const int* specs, int R, float* out, long out_stride, int C, long N, int* status, void* stream);
+/* Running tally of the losses the fine-tuning loop prints (reference ft/job.py:401-417 reads a masked .mean().item() per
+ * group and batch: one host synchronisation per batch).  values (R, N) fp32 rows, group (N,) int32 in [0, G) - a value outside
+ * it (negative: "skip") leaves the sample out.  sums (R, G) fp64 and counts (G,) int64 are DEVICE accumulators the caller
+ * owns and clears: sums[r][g] += sum of values[r][n] over group[n] == g, counts[g] += their number.  One workgroup, each
+ * sum taken in fp64 in a fixed order (a strided walk per thread, then a tree over the threads): the same bits run to run;
+ * no atomics, no allocation, no synchronisation.  1 <= R, 1 <= G, 0 <= N, R * G <= 4096, else -1. */
+int jvae_group_tally_f32(const float* values, const int* group, double* sums, long long* counts, int R, int N, int G,
+                         void* stream);
 
 #ifdef __cplusplus
 }

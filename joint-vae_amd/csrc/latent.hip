@@ -2,6 +2,10 @@
 // class-conditional prior, forward and backward.  One wavefront per sample; lanes stride the latent
 // dimension K; per-sample reductions are wave shuffles (no LDS, no atomics in forward).
 //
+// The per-sample work lives in __device__ bodies (latent_fwd_sample, latent_bwd_sample, uniform_terms_sample) that the
+// single-prior kernels and the two-prior ones (latent_mixed_*: one batch, rows before `split` against prior A, the rest
+// against prior B - the WIM fine-tuning step) both call: one copy of the formulas, the same bits per sample.
+//
 // Reference path replaced:
 //   Encoder.forward clip            module/vae_layers/layers.py:388-394
 //   Sampling.forward                module/vae_layers/layers.py:230-244   (eps is an INPUT here: the caller draws it)
@@ -41,15 +45,14 @@ struct LatentP {
 
 __device__ __forceinline__ float hardtanh1(float v) { return fminf(1.f, fmaxf(-1.f, v)); }
 
-__global__ __launch_bounds__(256) void latent_fwd_kernel(LatentP p, float* __restrict__ lv_out, float* __restrict__ z,
-                                                         float* __restrict__ kl, float* __restrict__ zdist,
-                                                         float* __restrict__ var_kl, float* __restrict__ dzdist) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (n >= p.N) return;
+// The forward of ONE sample by one wave (sample n < p.N, class cls in [0, p.C)): shared by the single-prior kernel and the
+// two-prior one, which differ only in where `p` and `cls` come from.
+__device__ __forceinline__ void latent_fwd_sample(const LatentP& p, const int n, const long long cls, const int lane,
+                                                  float* __restrict__ lv_out, float* __restrict__ z,
+                                                  float* __restrict__ kl, float* __restrict__ zdist,
+                                                  float* __restrict__ var_kl, float* __restrict__ dzdist) {
     const int K = p.K;
     const float w = p.w_dev ? p.w_dev[0] : p.w;
-    const long long cls = p.y[n];
     const float* m = p.means + (long)cls * K;
     const long row = (long)n * K;
     float dist = 0.f, trace = 0.f, logdet = 0.f, logdet_p = 0.f, dz = 0.f;
@@ -125,6 +128,58 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentP p, float* __res
     }
 }
 
+__global__ __launch_bounds__(256) void latent_fwd_kernel(LatentP p, float* __restrict__ lv_out, float* __restrict__ z,
+                                                         float* __restrict__ kl, float* __restrict__ zdist,
+                                                         float* __restrict__ var_kl, float* __restrict__ dzdist) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (n >= p.N) return;
+    latent_fwd_sample(p, n, p.y[n], lane, lv_out, z, kl, zdist, var_kl, dzdist);
+}
+
+// The second prior of the two-prior kernels: what replaces the fields of the same names in LatentP for samples n >= split
+struct PriorB {
+    const float* means;
+    const float* T;
+    int C, prior, var_dim;
+    float tau, alpha;
+};
+
+// `a` with prior B (and without dictionary) when sample n belongs to the second part
+__device__ __forceinline__ LatentP prior_of_sample(const LatentP& a, const PriorB& b, const int n, const int split) {
+    LatentP p = a;
+    if (n >= split) {
+        p.means = b.means; p.T = b.T; p.C = b.C; p.prior = b.prior; p.var_dim = b.var_dim; p.tau = b.tau; p.alpha = b.alpha;
+        p.dict = nullptr;
+    }
+    return p;
+}
+
+// Two priors in one launch: the wave's sample index is made scalar, so the choice of prior is wave-uniform.  A label outside
+// the chosen prior's classes is never an index: NaN in every output of the sample.
+__global__ __launch_bounds__(256) void latent_mixed_fwd_kernel(LatentP a, PriorB b, int split, float* __restrict__ lv_out,
+                                                               float* __restrict__ z, float* __restrict__ kl,
+                                                               float* __restrict__ zdist, float* __restrict__ var_kl,
+                                                               float* __restrict__ dzdist) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (n >= a.N) return;
+    const LatentP p = prior_of_sample(a, b, n, split);
+    const long long cls = p.y[n];
+    if (cls < 0 || cls >= (long long)p.C) {
+        for (int k = lane; k < p.K; k += 64) {
+            lv_out[(long)n * p.K + k] = NAN;
+            for (int l = 0; l <= p.L; ++l) z[((long)l * p.N + n) * p.K + k] = NAN;
+        }
+        if (lane == 0) {
+            kl[n] = NAN; zdist[n] = NAN; var_kl[n] = NAN;
+            if (dzdist) dzdist[n] = p.dict ? NAN : 0.f;
+        }
+        return;
+    }
+    latent_fwd_sample(p, n, cls, lane, lv_out, z, kl, zdist, var_kl, dzdist);
+}
+
 // Backward.  Upstream: gz (L+1,N,K) [may be null], g_kl, g_zdist, g_vkl (N,) [each may be null],
 // gmu_direct / glv_direct (N,K) [may be null: gradients reaching mu / clipped log_var from other consumers].
 // Outputs: gmu, glv_raw (N,K); gd_scratch (N,K) = per-sample contribution to the gradient of its class mean (reduced in a
@@ -134,23 +189,22 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentP p, float* __res
 // which gT_full_kernel rebuilds the rank-one terms per class in sample order.
 // Full variance: d and wd of the wave's sample are staged in LDS (2 K floats per wave) so that the per-sample cost is
 // O(K^2) (it was O(K^3): every lane recomputed every wd_i).
-__global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float* __restrict__ lv,   // clipped
-                                                         const float* __restrict__ gz, const float* __restrict__ g_kl,
-                                                         const float* __restrict__ g_zdist, const float* __restrict__ g_vkl,
-                                                         const float* __restrict__ gmu_direct,
-                                                         const float* __restrict__ glv_direct,
-                                                         const float* __restrict__ kl_fwd_terms,   // uniform: (N,2) = (elogq+nel, vk)
-                                                         float* __restrict__ gmu, float* __restrict__ glv_raw,
-                                                         float* gd_scratch, float* gt_scratch, float* gpair) {
-    extern __shared__ float lds_dw[];          // full variance only: per wave d[K] then wd[K]
-    const int lane = threadIdx.x & 63;
-    const int wv = threadIdx.x >> 6;
-    const int n_raw = blockIdx.x * (blockDim.x >> 6) + wv;
-    const bool valid = n_raw < p.N;
-    const int n = valid ? n_raw : p.N - 1;     // out-of-range waves shadow the last sample and store nothing
+//
+// latent_bwd_sample is the backward of ONE sample by one wave, shared by the single-prior kernel and the two-prior one.
+// `valid` false: the wave shadows sample n (it only takes the barriers) and stores nothing.  `uni_first` (uniform prior):
+// which branch of the forward's max() was taken.  `block_full`: some wave of the workgroup has a full-variance prior, so
+// EVERY wave of it takes the two barriers of the LDS staging (block-uniform; the single-prior kernel passes `full` itself).
+__device__ __forceinline__ void latent_bwd_sample(const LatentP& p, const int n, const bool valid, const long long cls,
+                                                  const int lane, const int wv, const bool block_full, const bool uni_first,
+                                                  float* lds_dw, const float* __restrict__ lv,
+                                                  const float* __restrict__ gz, const float* __restrict__ g_kl,
+                                                  const float* __restrict__ g_zdist, const float* __restrict__ g_vkl,
+                                                  const float* __restrict__ gmu_direct,
+                                                  const float* __restrict__ glv_direct,
+                                                  float* __restrict__ gmu, float* __restrict__ glv_raw,
+                                                  float* gd_scratch, float* gt_scratch, float* gpair) {
     const int K = p.K;
     const float w = p.w_dev ? p.w_dev[0] : p.w;
-    const long long cls = p.y[n];
     const float* m = p.means + (long)cls * K;
     const long row = (long)n * K;
     const float gk = g_kl ? g_kl[n] : 0.f;
@@ -159,7 +213,6 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float*
 
     // gradient reaching `distance` and `var_kl` (gaussian) ...
     float g_dist = gd_in, g_var = gv_in;
-    bool uni_first = true;          // uniform: which branch of the max() was taken
     if (p.prior == PRIOR_GAUSS) { g_dist += 0.5f * gk; g_var += 0.5f * w * gk; }
     else if (p.prior == PRIOR_TILTED) {
         float dist = 0.f;
@@ -168,26 +221,25 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float*
         const float r = sqrtf(dist);
         g_dist += gk * 0.5f * (1.f - p.tau / r);     // d/dD 0.5 (sqrt D - tau)^2
         g_var = 0.f;
-    } else {
-        uni_first = kl_fwd_terms[2 * n] >= kl_fwd_terms[2 * n + 1];
     }
 
     const bool full = p.prior != PRIOR_UNIFORM && p.var_dim == VAR_FULL;
     float* d_s = lds_dw + (size_t)wv * 2 * K;
     float* wd_s = d_s + K;
-    if (full) {                                // uniform over the block: every wave takes the barriers
-        const float* Tc = p.T + (long)cls * K * K;
+    if (full)
         for (int k = lane; k < K; k += 64) d_s[k] = p.mu[row + k] - m[k];
-        __syncthreads();
+    if (block_full) __syncthreads();           // uniform over the block: every wave takes the barriers
+    if (full) {
+        const float* Tc = p.T + (long)cls * K * K;
         for (int k = lane; k < K; k += 64) {   // wd_k = sum_{j<=k} T_kj d_j  (the forward's summation order)
             float wd = 0.f;
             for (int j = 0; j <= k; ++j) wd += Tc[(long)k * K + j] * d_s[j];
             wd_s[k] = wd;
             if (valid && gt_scratch) gt_scratch[row + k] = wd;
         }
-        __syncthreads();
-        if (valid && gpair && lane == 0) { gpair[2 * n] = g_dist; gpair[2 * n + 1] = g_var; }
     }
+    if (block_full) __syncthreads();
+    if (full && valid && gpair && lane == 0) { gpair[2 * n] = g_dist; gpair[2 * n + 1] = g_var; }
     if (!valid) return;
 
     for (int k = lane; k < K; k += 64) {
@@ -255,6 +307,26 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float*
         const bool pass = p.has_forced ? false : (raw >= -20.f && raw <= 20.f);
         glv_raw[row + k] = pass ? g_lv : 0.f;
     }
+}
+
+__global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float* __restrict__ lv,   // clipped
+                                                         const float* __restrict__ gz, const float* __restrict__ g_kl,
+                                                         const float* __restrict__ g_zdist, const float* __restrict__ g_vkl,
+                                                         const float* __restrict__ gmu_direct,
+                                                         const float* __restrict__ glv_direct,
+                                                         const float* __restrict__ kl_fwd_terms,   // uniform: (N,2) = (elogq+nel, vk)
+                                                         float* __restrict__ gmu, float* __restrict__ glv_raw,
+                                                         float* gd_scratch, float* gt_scratch, float* gpair) {
+    extern __shared__ float lds_dw[];          // full variance only: per wave d[K] then wd[K]
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int n_raw = blockIdx.x * (blockDim.x >> 6) + wv;
+    const bool valid = n_raw < p.N;
+    const int n = valid ? n_raw : p.N - 1;     // out-of-range waves shadow the last sample and store nothing
+    const bool uni_first = p.prior == PRIOR_UNIFORM ? kl_fwd_terms[2 * n] >= kl_fwd_terms[2 * n + 1] : true;
+    const bool full = p.prior != PRIOR_UNIFORM && p.var_dim == VAR_FULL;
+    latent_bwd_sample(p, n, valid, p.y[n], lane, wv, full, uni_first, lds_dw, lv, gz, g_kl, g_zdist, g_vkl, gmu_direct,
+                      glv_direct, gmu, glv_raw, gd_scratch, gt_scratch, gpair);
 }
 
 // Full variance: gT[c][i][k] += sum over the samples n of class c, IN SAMPLE ORDER, of
@@ -339,12 +411,10 @@ __global__ __launch_bounds__(1024) void dict_stats_kernel(const float* __restric
 }
 
 // forward-only helper for the uniform prior's backward: terms[n] = (sum elogq + sum nel, vk)
-__global__ __launch_bounds__(256) void uniform_terms_kernel(LatentP p, const float* __restrict__ lv, float* __restrict__ terms) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (n >= p.N) return;
+__device__ __forceinline__ void uniform_terms_sample(const LatentP& p, const int n, const long long cls, const int lane,
+                                                     const float* __restrict__ lv, float& first, float& second) {
     const int K = p.K;
-    const float* m = p.means + (long)p.y[n] * K;
+    const float* m = p.means + (long)cls * K;
     float se = 0.f, sn = 0.f;
     for (int k = lane; k < K; k += 64) {
         const float c = 1.8378770664093453f;
@@ -361,7 +431,50 @@ __global__ __launch_bounds__(256) void uniform_terms_kernel(LatentP p, const flo
     }
     se = wave_sum(se);
     sn = wave_sum(sn);
-    if (lane == 0) { terms[2 * n] = se + sn; terms[2 * n + 1] = se + K * p.alpha; }
+    first = se + sn;
+    second = se + K * p.alpha;
+}
+
+__global__ __launch_bounds__(256) void uniform_terms_kernel(LatentP p, const float* __restrict__ lv, float* __restrict__ terms) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (n >= p.N) return;
+    float first, second;
+    uniform_terms_sample(p, n, p.y[n], lane, lv, first, second);
+    if (lane == 0) { terms[2 * n] = first; terms[2 * n + 1] = second; }
+}
+
+// Two priors in one launch (both frozen: no per-class contributions are written).  The uniform prior's two forward sums are
+// taken in the wave by the body of uniform_terms_kernel instead of being read back from a workspace: the same fp32 values.
+// A sample whose label is outside its prior's classes takes the barriers as a shadow and gets NaN gradients.
+__global__ __launch_bounds__(256) void latent_mixed_bwd_kernel(LatentP a, PriorB b, int split, int block_full,
+                                                               const float* __restrict__ lv,
+                                                               const float* __restrict__ gz, const float* __restrict__ g_kl,
+                                                               const float* __restrict__ g_zdist,
+                                                               const float* __restrict__ g_vkl,
+                                                               const float* __restrict__ gmu_direct,
+                                                               const float* __restrict__ glv_direct,
+                                                               float* __restrict__ gmu, float* __restrict__ glv_raw) {
+    extern __shared__ float lds_dw[];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_raw = blockIdx.x * (blockDim.x >> 6) + wv;
+    const bool in_range = n_raw < a.N;
+    const int n = in_range ? n_raw : a.N - 1;
+    const LatentP p = prior_of_sample(a, b, n, split);
+    const long long y = p.y[n];
+    const bool good = y >= 0 && y < (long long)p.C;
+    const long long cls = good ? y : 0;
+    bool uni_first = true;
+    if (p.prior == PRIOR_UNIFORM) {
+        float first, second;
+        uniform_terms_sample(p, n, cls, lane, lv, first, second);
+        uni_first = first >= second;
+    }
+    latent_bwd_sample(p, n, in_range && good, cls, lane, wv, block_full != 0, uni_first, lds_dw, lv, gz, g_kl, g_zdist, g_vkl,
+                      gmu_direct, glv_direct, gmu, glv_raw, nullptr, nullptr, nullptr);
+    if (in_range && !good)
+        for (int k = lane; k < p.K; k += 64) { gmu[(long)n * p.K + k] = NAN; glv_raw[(long)n * p.K + k] = NAN; }
 }
 
 bool fill(LatentP* p, const float* mu, const float* lv_raw, const float* eps, const long long* y, const float* means,
@@ -481,6 +594,59 @@ int jvae_latent_bwd_f32(const float* mu, const float* lv_raw, const float* lv, c
     return jvae_latent_bwd_wdev_f32(mu, lv_raw, lv, eps, y, means, T, gz, g_kl, g_zdist, g_vkl, gmu_direct, glv_direct, gmu,
                                     glv_raw, gmeans, gT, N, K, L, C, prior, var_dim, tau, alpha, w, sampled, has_forced,
                                     nullptr, ws, ws_bytes, stream);
+}
+
+// Two priors, one launch.  `fill` vets each prior's description as the single-prior entry points do.
+int jvae_latent_mixed_fwd_f32(const float* mu, const float* lv_raw, const float* eps, const long long* y,
+                              const float* means_a, const float* T_a, const float* dict, const float* means_b, const float* T_b,
+                              float* lv, float* z, float* kl, float* zdist, float* var_kl, float* dzdist,
+                              int N, int K, int L, int split,
+                              int C_a, int prior_a, int var_dim_a, float tau_a, float alpha_a,
+                              int C_b, int prior_b, int var_dim_b, float tau_b, float alpha_b,
+                              float w, int sampled, int has_forced, float forced_lv, void* stream) {
+    LatentP a, vet;
+    if (!fill(&a, mu, lv_raw, eps, y, means_a, T_a, dict, N, K, L, C_a, prior_a, var_dim_a, tau_a, alpha_a, w, sampled,
+              has_forced, forced_lv) ||
+        !fill(&vet, mu, lv_raw, eps, y, means_b, T_b, nullptr, N, K, L, C_b, prior_b, var_dim_b, tau_b, alpha_b, w, sampled,
+              has_forced, forced_lv))
+        return JVAE_EINVAL;
+    if (!eps || !lv || !z || !kl || !zdist || !var_kl || split < 0 || split > N) return JVAE_EINVAL;
+    if (N == 0) return 0;
+    const PriorB b = {means_b, T_b, C_b, prior_b, var_dim_b, tau_b, alpha_b};
+    hipLaunchKernelGGL(latent_mixed_fwd_kernel, dim3(cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, a, b, split, lv, z, kl,
+                       zdist, var_kl, dzdist);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+int jvae_latent_mixed_bwd_f32(const float* mu, const float* lv_raw, const float* lv, const float* eps, const long long* y,
+                              const float* means_a, const float* T_a, const float* means_b, const float* T_b,
+                              const float* gz, const float* g_kl, const float* g_zdist, const float* g_vkl,
+                              const float* gmu_direct, const float* glv_direct,
+                              float* gmu, float* glv_raw, float* gmeans, float* gT,
+                              int N, int K, int L, int split,
+                              int C_a, int prior_a, int var_dim_a, float tau_a, float alpha_a,
+                              int C_b, int prior_b, int var_dim_b, float tau_b, float alpha_b,
+                              float w, int sampled, int has_forced, void* ws, size_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;                  // nothing is folded per class: no workspace
+    LatentP a, vet;
+    if (gmeans || gT) return JVAE_EINVAL;      // both priors are frozen
+    if (!fill(&a, mu, lv_raw, eps, y, means_a, T_a, nullptr, N, K, L, C_a, prior_a, var_dim_a, tau_a, alpha_a, w, sampled,
+              has_forced, 0.f) ||
+        !fill(&vet, mu, lv_raw, eps, y, means_b, T_b, nullptr, N, K, L, C_b, prior_b, var_dim_b, tau_b, alpha_b, w, sampled,
+              has_forced, 0.f))
+        return JVAE_EINVAL;
+    if (!lv || !gmu || !glv_raw || (gz && !eps) || split < 0 || split > N) return JVAE_EINVAL;
+    if (N == 0) return 0;
+    const PriorB b = {means_b, T_b, C_b, prior_b, var_dim_b, tau_b, alpha_b};
+    const bool full_a = prior_a != PRIOR_UNIFORM && var_dim_a == VAR_FULL, full_b = prior_b != PRIOR_UNIFORM && var_dim_b == VAR_FULL;
+    const int block_full = (full_a && split > 0) || (full_b && split < N);
+    const size_t lds = block_full ? sizeof(float) * 4 * 2 * (size_t)K : 0;
+    if (lds > 64 * 1024) return JVAE_ENOTSUP;
+    hipLaunchKernelGGL(latent_mixed_bwd_kernel, dim3(cdiv(N, 4)), dim3(256), lds, (hipStream_t)stream, a, b, split, block_full,
+                       lv, gz, g_kl, g_zdist, g_vkl, gmu_direct, glv_direct, gmu, glv_raw);
+    JVAE_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // extern "C"

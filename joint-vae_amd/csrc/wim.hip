@@ -84,9 +84,57 @@ __global__ __launch_bounds__(WIM_BLOCK) void wim_scores_kernel(WimArgs a, const 
     }
 }
 
+// Running tally of the fine-tuning loop's printed losses: ONE workgroup adds this batch's per-group sums of every row and the
+// per-group counts to the caller's device accumulators.  For each (row, group) pair a thread sums, in fp64 and in index order,
+// the samples tid, tid + 256, ... of that group; the 256 partial sums are folded by a tree over LDS.  A fixed order throughout:
+// the same bits run to run; one writer per accumulator, no atomics.
+constexpr int TALLY_BLOCK = 256;
+
+__device__ __forceinline__ double tally_fold(double v, double* red) {
+    const int tid = threadIdx.x;
+    __syncthreads();                       // the previous fold's result has been read by thread 0
+    red[tid] = v;
+    __syncthreads();
+    for (int s = TALLY_BLOCK / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(TALLY_BLOCK) void group_tally_kernel(const float* __restrict__ values, const int* __restrict__ group,
+                                                                  double* __restrict__ sums, long long* __restrict__ counts,
+                                                                  int R, int N, int G) {
+    __shared__ double red[TALLY_BLOCK];
+    const int tid = threadIdx.x;
+    for (int g = 0; g < G; ++g) {
+        double cnt = 0.;                   // exact in fp64 far beyond any batch size
+        for (int n = tid; n < N; n += TALLY_BLOCK) cnt += group[n] == g ? 1. : 0.;
+        const double c = tally_fold(cnt, red);
+        if (tid == 0) counts[g] += (long long)c;
+        for (int r = 0; r < R; ++r) {
+            double acc = 0.;
+            for (int n = tid; n < N; n += TALLY_BLOCK)
+                if (group[n] == g) acc += (double)values[(size_t)r * N + n];
+            const double t = tally_fold(acc, red);
+            if (tid == 0) sums[(size_t)r * G + g] += t;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int jvae_group_tally_f32(const float* values, const int* group, double* sums, long long* counts, int R, int N, int G,
+                         void* stream) {
+    if (!sums || !counts || R < 1 || G < 1 || N < 0 || (long)R * G > 4096) return JVAE_EINVAL;
+    if (N == 0) return 0;
+    if (!values || !group) return JVAE_EINVAL;
+    group_tally_kernel<<<1, TALLY_BLOCK, 0, (hipStream_t)stream>>>(values, group, sums, counts, R, N, G);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
 
 int jvae_wim_scores_f32(const float* const* srcs, const float* const* alts, const float* factors, int S, const long long* y_est,
                         const int* specs, int R, float* out, long out_stride, int C, long N, int* status, void* stream) {

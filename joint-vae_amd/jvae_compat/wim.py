@@ -10,20 +10,32 @@ evaluation under BOTH priors and the scores read from it (`k~`, `softk~`, `k@`, 
   * every WIM score row of a batch comes from ONE launch of csrc/wim.hip (`ops.wim_scores`) instead of about ten small torch
     launches per method.
 
+  * `finetune()` is the reference's fine-tuning loop (ft/job.py:170-478) over data-set objects, and `finetune_step()` its step
+    in ONE pass: `finetune_batch()` evaluates the labelled batch under the original prior and the mixture batch under the
+    alternate one, two passes through the network; every BatchNorm being on its running statistics, the two batches differ
+    only in the prior of their KL, so they are concatenated and `ops.latent_mixed` (csrc/latent.hip) measures each part against
+    its prior in one launch (`WIM_FUSED_STEP`).  Same per-sample losses bit for bit; measured on config 2
+    (tools/wim_finetune_bench.py, profiles/wim_finetune_bench.json, median of 20 steps): 4.01 ms against 6.89 ms at 64 + 64
+    images, 6.52 ms against 8.01 ms at 512 + 512.  The printed losses are tallied per group on the device (`ops.group_tally`).
+
 Data sets yield `((x, y_est), y)` items, as the reference's `EstimatedLabelsDataset` does (`EstimatedLabelsDataset` below).
-The `finetune()` loop itself (mixture / moving sets of named data sets), POSCOD and job arrays stay in the reference's `ft/`
-package: see DESIGN.md.
+Seeded sub-sampling and padding of the moving set, sample recorders, POSCOD and job arrays stay in the reference's `ft/`
+package: see DESIGN.md section 7d.
 """
 import json
 import logging
 import os
+import time
 from contextlib import contextmanager
 
 import torch
 
 from cvae import ClassificationVariationalNetwork, _mean_over_draws
+from jvae_compat.ft_datasets import MovingSet, finetune_schedule
+from jvae_compat.recorders import LossRecorder
 from jvae_hip import ops
 from module.priors import build_prior
+from module.vae_layers.layers import draw_epsilon
 
 
 class EstimatedLabelsDataset(torch.utils.data.Dataset):
@@ -60,6 +72,12 @@ class WIMJob(ClassificationVariationalNetwork):
     # evaluate_on_both_priors(): one pass through features / encoder / decoder and the prior-dependent tail once per prior
     # (True), or two full evaluations as the reference runs them (False).  Same bits for every loss with the same epsilon.
     WIM_SHARED_PASS = True
+
+    # finetune_step(): the two halves of a fine-tuning step in ONE pass over the concatenated batch with a two-prior latent
+    # kernel (True, where `_fused_step_applies()`), or always the two evaluations of finetune_batch() (False).  The same
+    # per-sample losses bit for bit; the gradients are the same per-sample terms summed in another order.
+    WIM_FUSED_STEP = True
+    last_finetune_route = None          # 'fused' / 'two_pass': what the last finetune_step() ran
 
     # the factor of each score family on its loss (ft/wim.py:145); `elbo` is -total
     WIM_FACTORS = {'kl': -1., 'zdist': -0.5, 'iws': 1., 'elbo': 1.}
@@ -337,24 +355,199 @@ class WIMJob(ClassificationVariationalNetwork):
         return res
 
     # ------------------------------------------------------------------------------------ fine-tuning step
-    def finetune_batch(self, epoch, batch, x_in, y_in, x_mix, alpha=0.1):
+    def finetune_batch(self, epoch, batch, x_in, y_in, x_mix, alpha=0.1, epsilon=None):
         """One WIM step's loss (ft/wim.py:215-259): the labelled batch under the original prior plus alpha x the mixture batch
         under the alternate prior, every sample of it with label 0 -> (L to back-propagate, in losses, mix losses).  Leaves the
-        alternate prior in place, as the reference does."""
+        alternate prior in place, as the reference does.  `epsilon` (L+1, N_in + N_mix, K), optional: the noise of both halves."""
+        eps_in, eps_mix = (None, None) if epsilon is None else (epsilon[:, :len(x_in)], epsilon[:, len(x_in):])
         self._evaluate_on_both_priors = False
         self.original_prior = True
         self.train()
         with self.no_estimated_labels():
-            _, _, in_loss, _ = self.evaluate(x_in, y_in, batch=batch, with_beta=True)
+            _, _, in_loss, _ = self.evaluate(x_in, y_in, batch=batch, with_beta=True, epsilon=eps_in)
         L = in_loss['total'].mean()
         self.alternate_prior = True
         y_mix = torch.zeros(len(x_mix), device=x_mix.device, dtype=torch.int64)
         self.train()
         with self.no_estimated_labels():
-            _, _, mix_loss, _ = self.evaluate(x_mix, y_mix, batch=batch, with_beta=True)
+            _, _, mix_loss, _ = self.evaluate(x_mix, y_mix, batch=batch, with_beta=True, epsilon=eps_mix)
         L = L + alpha * mix_loss['total'].mean()
         self._evaluate_on_both_priors = True
         return L, in_loss, mix_loss
+
+    def _fused_step_applies(self):
+        """Host decision of finetune_step(): may the two halves of a step share one pass?  No sample's result may depend on
+        its batch (every BatchNorm on running statistics, no active dropout, a sigma that does not follow the batch rmse), the
+        prior may reach the loss through the latent kernel only (cvae, labels not coded, no classifier term), fp32 compute."""
+        from module.vae_layers.layers import HipDropout
+        if not (self.WIM_FUSED_STEP and self.is_cvae and not self.y_is_coded and not self.y_is_decoded):
+            return False
+        if getattr(self, 'compute_dtype', 'fp32') != 'fp32' or self.sigma.kind not in ('fixed', 'learned'):
+            return False
+        if self._alternate_prior is None or not self._original_prior.conditional:
+            return False
+        for m in self.modules():
+            if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training:
+                return False
+            if isinstance(m, HipDropout) and m.p and m.training:
+                return False
+        return True
+
+    @contextmanager
+    def _mixed_prior(self, split):
+        """Inside: the encoder measures rows [split, N) of its batch against the alternate prior (the original one is in place
+        for the rows before) - the seam of finetune_step() in Encoder.encode."""
+        self.encoder.mixed_prior = (self._alternate_prior, int(split))
+        try:
+            yield
+        finally:
+            self.encoder.mixed_prior = None
+
+    def finetune_step(self, epoch, batch, x_in, y_in, x_mix, alpha=0.1, epsilon=None):
+        """finetune_batch() in ONE pass through the network: cat(x_in, x_mix) is evaluated once, the latent kernel measures
+        the first len(x_in) rows against the original prior and the others against the alternate one (`ops.latent_mixed`), and
+        the per-sample losses are sliced at the seam -> (L, in losses, mix losses), the same keys and the same state left behind
+        as finetune_batch().  Without `epsilon` the noise is drawn as finetune_batch() draws it (the in part, then the mix part),
+        so the two forms see the same noise under one torch seed.  Applies when `_fused_step_applies()`; else, and with
+        `WIM_FUSED_STEP = False`, this IS finetune_batch().  `last_finetune_route` tells which ran: 'fused' or 'two_pass'."""
+        self._evaluate_on_both_priors = False
+        self.original_prior = True
+        self.train()
+        if not self._fused_step_applies():
+            self.last_finetune_route = 'two_pass'
+            return self.finetune_batch(epoch, batch, x_in, y_in, x_mix, alpha=alpha, epsilon=epsilon)
+        self.last_finetune_route = 'fused'
+        split, n_mix = len(x_in), len(x_mix)
+        x = torch.cat((x_in, x_mix))
+        y = torch.cat((y_in.reshape(-1), torch.zeros(n_mix, device=y_in.device, dtype=torch.int64)))
+        if epsilon is None:
+            shape = (self.encoder.sampling_size, self.latent_dim, self.encoder.sampling.distribution)
+            epsilon = torch.cat([draw_epsilon(shape[0], (n, shape[1]), x.device, shape[2]) for n in (split, n_mix)], 1)
+        with self.no_estimated_labels(), self._mixed_prior(split):
+            _, _, losses, _ = self.evaluate(x, y, batch=batch, with_beta=True, epsilon=epsilon)
+        in_loss = {k: v[..., :split] for k, v in losses.items()}
+        mix_loss = {k: v[..., split:] for k, v in losses.items() if k != 'dzdist'}
+        L = in_loss['total'].mean() + alpha * mix_loss['total'].mean()
+        self.alternate_prior = True
+        self._evaluate_on_both_priors = True
+        return L, in_loss, mix_loss
+
+    # ------------------------------------------------------------------------------------ fine-tuning loop
+    TALLY_GROUPS = ('ind', 'ood', 'in')          # groups of the printed losses: moving set's two classes, then the labelled batch
+
+    def finetune(self, trainset, ind_set, ood_sets, *, train_size=100000, epochs=None, batch_size=None, test_batch_size=8192,
+                 optimizer=None, outputs=None, alpha=0.1, report_every=10, testset_name=None, on_batch=None):
+        """The WIM fine-tuning loop (ft/job.py:170-478) over data-set objects: `trainset` yields the labelled (x, y) batches,
+        `ind_set` and the sets of `ood_sets` (name -> data set) make the `MovingSet` the alternate prior pulls on.
+
+          before   ood_detection_rates under the original prior, recorders filled per set, then `ood_results` cleared;
+          epochs   ceil(train_size / len(moving set)) of them (`finetune_schedule`); per batch zero_grad, finetune_step(),
+                   backward, optimizer.step() and then optimizer.clip() - the reference's order; the printed losses
+                   (`printed_loss`) are tallied per group on the device (`ops.group_tally`) and read back every
+                   `report_every` batches and at the last one, for outputs.results(losses={'ind_zdist', 'ood_zdist',
+                   'in_zdist'});
+          after    y_est = argmin over the classes of the recorded kl, per set, and ood_detection_rates under both priors.
+
+        The scoring passes re-seed torch for their recorders; the generator states found at the call are put back before the
+        first epoch, so `torch.manual_seed(s)` in front of finetune() fixes the loaders' order and the noise of the epochs.
+        `on_batch(epoch, batch, in_loss, mix_loss, tags)` is called after each step with that step's loss dictionaries.
+        `trained` is left as found, as in the reference.  Named data sets raise NotImplementedError; see DESIGN.md for what
+        else of the reference's loop is outside this build."""
+        named = [s for s in (trainset, ind_set) if isinstance(s, str) or s is None]
+        if named or not isinstance(ood_sets, dict) or any(isinstance(s, str) for s in ood_sets.values()):
+            raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets '
+                                      '(ood_sets: a dict of name -> Dataset)')
+        optimizer = self.optimizer if optimizer is None else optimizer
+        batch_size = int(batch_size or self.training_parameters['batch_size'])
+        testset_name = testset_name or getattr(ind_set, 'name', None) or self.training_parameters.get('set') or 'ind'
+        device = self.device
+        moving_set = MovingSet(ind_set, ood_sets)
+        if not hasattr(self, 'ft_params'):
+            self.ft_params = {}
+        self.ft_params.update(sets=list(ood_sets), train_size=train_size, moving_size=len(moving_set), mix=moving_set.mix[1],
+                              padding=0, padding_sets=[], mix_padding=0, alpha=alpha)
+        test_batch_size = min(self.max_batch_sizes['test'], test_batch_size)
+        logging.info('Moving set of length %d, with mixture %s', len(moving_set),
+                     ', '.join('{}:{:.1%}'.format(n, m) for n, m in zip(moving_set.classes, moving_set.mix)))
+
+        # ---- before tuning: the original prior's rates, and the recorders the estimated labels are read from
+        rng = (torch.get_rng_state(), torch.cuda.get_rng_state(device) if device.type == 'cuda' else None)
+        self.eval()
+        self.original_prior = True
+        self._evaluate_on_both_priors = False
+        recorders = {n: LossRecorder(test_batch_size) for n in list(ood_sets) + [testset_name]}
+        ood_ = moving_set.extract_subdataset('ood')
+        with self.no_estimated_labels(), torch.no_grad():
+            self.ood_detection_rates(batch_size=test_batch_size,
+                                     testset=moving_set.extract_subdataset('ind', new_name=testset_name),
+                                     oodsets=[ood_.extract_subdataset(n, new_name=n) for n in ood_sets],
+                                     outputs=outputs, recorders=recorders, print_result='*')
+            self.ood_results = {}
+        torch.set_rng_state(rng[0])
+        if rng[1] is not None:
+            torch.cuda.set_rng_state(rng[1], device)
+
+        # ---- the epochs
+        train_loader = torch.utils.data.DataLoader(trainset, batch_size=batch_size, shuffle=True, num_workers=0)
+        moving_loader = torch.utils.data.DataLoader(moving_set, drop_last=True, batch_size=batch_size, shuffle=True, num_workers=0)
+        self.ft_params['train_size'], schedule = finetune_schedule(train_size, len(moving_set), batch_size, epochs)
+        epochs = len(schedule)
+        logging.info('Epochs: %d of %s batches of size %d', epochs, schedule, batch_size)
+        printed = [k for k in self.printed_loss]
+        G = len(self.TALLY_GROUPS)
+        sums = torch.zeros((len(printed), G), dtype=torch.float64, device=device)
+        counts = torch.zeros(G, dtype=torch.int64, device=device)
+        sink = outputs if outputs is not None and hasattr(outputs, 'results') else None
+        for epoch, per_epoch in enumerate(schedule):
+            self.eval()
+            sums.zero_()
+            counts.zero_()
+            t0 = time.time()
+            shown = {f'{g}_{k}': float('nan') for g in self.TALLY_GROUPS for k in printed}
+            train_iter, moving_iter = iter(train_loader), iter(moving_loader)
+            for batch in range(per_epoch):
+                x_u, tags = next(moving_iter)
+                try:
+                    x_a, y_a = next(train_iter)[:2]
+                except StopIteration:
+                    train_iter = iter(train_loader)
+                    x_a, y_a = next(train_iter)[:2]
+                optimizer.zero_grad()
+                L, in_loss, mix_loss = self.finetune_step(epoch, batch, x_a.to(device), y_a.to(device), x_u.to(device), alpha=alpha)
+                L.backward()
+                optimizer.step()
+                optimizer.clip(self.parameters())          # after the step, as the reference has it (ft/job.py:397-399)
+                # the printed losses: this batch's rows [mix | in] and their groups, one launch, nothing read back
+                group = torch.cat((tags.to(torch.int32), torch.full((len(x_a),), G - 1, dtype=torch.int32))).to(device)
+                rows = torch.stack([torch.cat((mix_loss[k].detach(), in_loss[k].detach())) for k in printed])
+                ops.group_tally(rows, group, sums, counts)
+                if on_batch is not None:
+                    on_batch(epoch, batch, in_loss, mix_loss, tags)
+                if batch % report_every == 0 or batch + 1 == per_epoch:
+                    host = (sums / counts).tolist()          # the only read-back of the loop; an empty group shows nan
+                    shown = {f'{g}_{k}': host[r][j] for r, k in enumerate(printed) for j, g in enumerate(self.TALLY_GROUPS)}
+                if sink is not None:
+                    sink.results(batch, per_epoch, epoch + 1, epochs, preambule='finetune', losses=dict(shown),
+                                 batch_size=2 * batch_size, time_per_i=(time.time() - t0) / (batch + 1), end_of_epoch='\n')
+
+        # ---- after tuning: estimated labels from the recorded kl, rates under both priors
+        logging.info('Computing ood fprs')
+        self.eval()
+        self.original_prior = True
+        self._evaluate_on_both_priors = False
+
+        def with_estimated(dset):
+            kl = recorders[dset.name]['kl']
+            y_est = kl.argmin(0) if kl.dim() > 1 else torch.zeros(kl.shape[-1], dtype=torch.int64)
+            return EstimatedLabelsDataset(dset, y_est[:len(dset)])
+
+        testset = with_estimated(moving_set.extract_subdataset('ind', new_name=testset_name))
+        oodsets = [with_estimated(ood_.extract_subdataset(n, new_name=n)) for n in ood_sets]
+        with torch.no_grad():
+            res = self.ood_detection_rates(batch_size=test_batch_size, testset=testset, oodsets=oodsets, num_batch='all',
+                                           outputs=outputs, recorders={}, print_result='*')
+        logging.info('misclassification_detection_rates with the `~` scores is outside this build: skipped')
+        return res
 
     # ------------------------------------------------------------------------------------ persistence
     def save(self, *a, except_state=True, **kw):

@@ -82,6 +82,10 @@ _SIGS = {
     'jvae_latent_bwd_f32': (c_int, [P] * 17 + [c_int] * 6 + [c_float] * 3 + [c_int, c_int, P, c_size_t, P]),
     'jvae_latent_fwd_wdev_f32': (c_int, [P] * 13 + [c_int] * 6 + [c_float] * 3 + [c_int, c_int, c_float, P, P]),
     'jvae_latent_bwd_wdev_f32': (c_int, [P] * 17 + [c_int] * 6 + [c_float] * 3 + [c_int, c_int, P, P, c_size_t, P]),
+    'jvae_latent_mixed_fwd_f32': (c_int, [P] * 15 + [c_int] * 4 + ([c_int] * 3 + [c_float] * 2) * 2
+                                  + [c_float, c_int, c_int, c_float, P]),
+    'jvae_latent_mixed_bwd_f32': (c_int, [P] * 19 + [c_int] * 4 + ([c_int] * 3 + [c_float] * 2) * 2
+                                  + [c_float, c_int, c_int, P, c_size_t, P]),
     'jvae_recon_fwd_f32': (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, P]),
     'jvae_recon_bwd_f32': (c_int, [P, P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'jvae_mse_rows_fwd_f32': (c_int, [P, P, P, c_int, c_int, c_int, P]),
@@ -123,6 +127,7 @@ _SIGS = {
     'jvae_odin_head_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, P]),
     'jvae_odin_perturb_f32': (c_int, [P, P, P, P, P, c_long, c_int, P]),
     'jvae_wim_scores_f32': (c_int, [P, P, P, c_int, P, P, c_int, P, c_long, c_int, c_long, P, P]),
+    'jvae_group_tally_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
 }
 
 

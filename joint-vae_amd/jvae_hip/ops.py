@@ -888,6 +888,85 @@ def latent(mu, lv_raw, eps, y, means, T, *, prior='gaussian', var_dim='scalar', 
     return _Latent.apply(mu, lv_raw, eps, y, means, T, cfg)
 
 
+class _LatentMixed(torch.autograd.Function):
+    """`_Latent` over one batch measured against two frozen priors: rows [0, split) against A, the rest against B."""
+
+    @staticmethod
+    def forward(ctx, mu, lv_raw, eps, y, means_a, T_a, means_b, T_b, cfg):
+        lib = L.load()
+        mu = _c(_f32(mu, 'latent_mixed'))
+        lv_raw, eps, y = _c(lv_raw), _c(eps), _c(y)
+        means_a, T_a, means_b, T_b = _c(means_a), _c(T_a), _c(means_b), _c(T_b)
+        if y.dtype != torch.int64:
+            raise L.JvaeHipError('class labels must be int64')
+        N, K = mu.shape
+        Ls = eps.shape[0] - 1
+        dev = mu.device
+        dict_ = torch.empty(K + 1, device=dev, dtype=torch.float32)
+        L.check(lib.jvae_dict_stats_f32(L.ptr(means_a), L.ptr(dict_), means_a.shape[0], K, L.stream_ptr()), 'dict_stats')
+        lv = torch.empty_like(mu)
+        z = torch.empty((Ls + 1, N, K), device=dev, dtype=torch.float32)
+        kl, zd, vkl, dzd = (torch.empty(N, device=dev, dtype=torch.float32) for _ in range(4))
+        forced = cfg.get('forced_lv')
+        args = (N, K, Ls, cfg['split'], means_a.shape[0], *cfg['a'], means_b.shape[0], *cfg['b'], cfg['w'], int(cfg['sampled']),
+                int(forced is not None))
+        rc = lib.jvae_latent_mixed_fwd_f32(L.ptr(mu), L.ptr(lv_raw), L.ptr(eps), L.ptr(y), L.ptr(means_a), L.ptr(T_a),
+                                           L.ptr(dict_), L.ptr(means_b), L.ptr(T_b), L.ptr(lv), L.ptr(z), L.ptr(kl), L.ptr(zd),
+                                           L.ptr(vkl), L.ptr(dzd), *args, float(forced or 0.), L.stream_ptr())
+        L.check(rc, 'jvae_latent_mixed_fwd_f32')
+        ctx.save_for_backward(mu, lv_raw, lv, eps, y, means_a, T_a, means_b, T_b)
+        ctx.args = args
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(dzd)
+        return lv, z, kl, zd, vkl, dzd
+
+    @staticmethod
+    def backward(ctx, g_lv, g_z, g_kl, g_zd, g_vkl, _g_dzd):
+        mu, lv_raw, lv, eps, y, means_a, T_a, means_b, T_b = ctx.saved_tensors
+        lib = L.load()
+        gmu = torch.empty_like(mu)
+        glv = torch.empty_like(mu)
+        # both priors are frozen: a prior that asks for its gradient is handed to the kernel's own refusal (JVAE_EINVAL)
+        gmeans = torch.zeros_like(means_a) if ctx.needs_input_grad[4] or ctx.needs_input_grad[6] else None
+        gT = torch.zeros_like(T_a) if ctx.needs_input_grad[5] or ctx.needs_input_grad[7] else None
+
+        def opt(t):
+            return None if t is None else _c(t)
+        rc = lib.jvae_latent_mixed_bwd_f32(L.ptr(mu), L.ptr(lv_raw), L.ptr(lv), L.ptr(eps), L.ptr(y), L.ptr(means_a), L.ptr(T_a),
+                                           L.ptr(means_b), L.ptr(T_b), L.ptr(opt(g_z)), L.ptr(opt(g_kl)), L.ptr(opt(g_zd)),
+                                           L.ptr(opt(g_vkl)), None, L.ptr(opt(g_lv)), L.ptr(gmu), L.ptr(glv), L.ptr(gmeans),
+                                           L.ptr(gT), *ctx.args, None, 0, L.stream_ptr())
+        L.check(rc, 'jvae_latent_mixed_bwd_f32')
+        return gmu, glv, None, None, None, None, None, None, None
+
+
+def latent_prior(means, T, *, prior='gaussian', var_dim='scalar', tau=0., alpha=0.):
+    """One prior of `latent_mixed`: means (C, K), the whitening factor T in the layout of `var_dim`, and its kind."""
+    return dict(means=means, T=T, kind=(PRIOR_KIND[prior], VAR_KIND[var_dim], float(tau), float(alpha)))
+
+
+def latent_mixed(mu, lv_raw, eps, y, prior_a, prior_b, split, *, w=1., sampled=True, forced_lv=None):
+    """`latent` for a batch whose rows [0, split) are measured against `prior_a` and whose rows [split, N) against `prior_b`
+    (two `latent_prior` descriptions), in ONE launch; every sample's values are the single-prior kernel's, bit for bit.  The
+    dictionary term belongs to the A part: dzdist is 0 from `split` on.  Both priors are frozen: the backward gives the
+    gradients of mu and lv_raw only and raises if a prior's tensors require one.  Labels given on the HOST are checked against
+    [0, C_A) resp. [0, C_B) here (JvaeHipError, the kernel's "invalid argument"); labels on the device are checked by the
+    kernel, which never indexes with a bad one: that sample's outputs are NaN."""
+    N, split = mu.shape[0], int(split)
+    if not 0 <= split <= N:
+        raise L.JvaeHipError(f'latent_mixed: split {split} outside [0, {N}]')
+    if torch.is_tensor(w):
+        raise L.JvaeHipError('latent_mixed: the warm-up weight is a host value here')
+    if not y.is_cuda:
+        C = torch.full((N,), prior_b['means'].shape[0], dtype=torch.int64)
+        C[:split] = prior_a['means'].shape[0]
+        if y.dtype != torch.int64 or tuple(y.shape) != (N,) or bool(((y < 0) | (y >= C)).any()):
+            L.check(-1, 'latent_mixed: a label outside the classes of its prior')
+        y = y.to(mu.device)
+    cfg = dict(split=split, a=prior_a['kind'], b=prior_b['kind'], w=float(w), sampled=bool(sampled), forced_lv=forced_lv)
+    return _LatentMixed.apply(mu, lv_raw, eps, y, prior_a['means'], prior_a['T'], prior_b['means'], prior_b['T'], cfg)
+
+
 # ------------------------------------------------------------------------------------------- losses
 SIGMA_VALUE, SIGMA_LOG, SIGMA_CODED, SIGMA_RMSE = 0, 1, 2, 3      # kinds of sigma the loss kernels know (csrc/loss.hip)
 
@@ -1366,6 +1445,23 @@ def wim_check_status(status=None):
             w.zero_()
         if v & 1:
             raise L.JvaeHipError('wim_scores: an estimated label outside [0, C) was met (its score rows are NaN)')
+
+
+def group_tally(values, group, sums, counts):
+    """sums (R, G) fp64 and counts (G,) int64, device accumulators of the caller, take this batch's per-group sums of the rows
+    `values` (R, N) fp32 and the group sizes; group (N,) int32 in [0, G), anything else (negative: skip) leaves the sample out.
+    One launch, fp64 sums in a fixed order, nothing synchronised (the fine-tuning loop's printed losses, ft/job.py:401-417)."""
+    values = _c(_f32(values, 'group_tally'))
+    if values.dim() != 2 or sums.dim() != 2 or counts.dim() != 1 or sums.shape[0] != values.shape[0] \
+            or sums.shape[1] != counts.shape[0] or sums.dtype != torch.float64 or counts.dtype != torch.int64 \
+            or group.dtype != torch.int32 or tuple(group.shape) != (values.shape[1],) \
+            or any(t.device != values.device for t in (group, sums, counts)):
+        raise L.JvaeHipError('group_tally: values (R, N) fp32, group (N,) int32, sums (R, G) fp64 and counts (G,) int64 on one '
+                             'device expected')
+    R, N = values.shape
+    L.check(L.load().jvae_group_tally_f32(L.ptr(values), L.ptr(_c(group)), L.ptr(sums), L.ptr(counts), R, N, counts.shape[0],
+                                          L.stream_ptr()), 'jvae_group_tally_f32')
+    return sums, counts
 
 
 def misclass_split(scores, mask):

@@ -301,6 +301,8 @@ class Encoder(nn.Module):
         prior['dim'] = latent_dim
         self.prior = build_prior(**prior)
         logging.debug('Built %s', self.prior)
+        # (second prior, split) while one batch is measured against two priors (WIMJob._mixed_prior), else None
+        self.mixed_prior = None
 
     @property
     def sampling_size(self):
@@ -349,10 +351,24 @@ class Encoder(nn.Module):
         lab, means, T = pr._kernel_operands(labels if pr.conditional else None, n, mu.device)
         forced = math.log(self.forced_variance) if self.forced_variance else None
         raw2 = mu2 if lv_raw is None else lv_raw.reshape(-1, K)
-        lv, z, kl, dist, vkl, dzd = ops.latent(mu2, raw2, epsilon.reshape(epsilon.shape[0], n, K), lab, means, T,
-                                               prior=pr.distribution, var_dim=pr.var_dim, tau=pr._tau,
-                                               alpha=pr._alpha_k, w=kl_var_weighting,
-                                               sampled=bool(self.sampling.is_sampled), forced_lv=forced)
+        if self.mixed_prior is None:
+            lv, z, kl, dist, vkl, dzd = ops.latent(mu2, raw2, epsilon.reshape(epsilon.shape[0], n, K), lab, means, T,
+                                                   prior=pr.distribution, var_dim=pr.var_dim, tau=pr._tau,
+                                                   alpha=pr._alpha_k, w=kl_var_weighting,
+                                                   sampled=bool(self.sampling.is_sampled), forced_lv=forced)
+        else:
+            # rows [split, n) are measured against a second, frozen prior in the same launch (WIMJob.finetune_step); the
+            # caller's labels are that prior's classes there (0 for a single prior)
+            other, split = self.mixed_prior
+            if not pr.conditional:
+                raise NotImplementedError('a mixed prior needs the class-conditional prior in place')
+            _, means_b, T_b = other._kernel_operands(labels if other.conditional else None, n, mu.device)
+            describe = ops.latent_prior
+            lv, z, kl, dist, vkl, dzd = ops.latent_mixed(
+                mu2, raw2, epsilon.reshape(epsilon.shape[0], n, K), lab,
+                describe(means, T, prior=pr.distribution, var_dim=pr.var_dim, tau=pr._tau, alpha=pr._alpha_k),
+                describe(means_b, T_b, prior=other.distribution, var_dim=other.var_dim, tau=other._tau, alpha=other._alpha_k),
+                split, w=kl_var_weighting, sampled=bool(self.sampling.is_sampled), forced_lv=forced)
         sigma = self.sigma(u) if self.sigma_output_dim else None
         terms = {'kl': kl.reshape(batch), 'distance': dist.reshape(batch), 'var_kl': vkl.reshape(batch),
                  'dzdist': dzd.reshape(batch)}

@@ -585,6 +585,36 @@ int jvae_wim_scores_f32(const float* const* srcs, const float* const* alts, cons
 int jvae_group_tally_f32(const float* values, const int* group, double* sums, long long* counts, int R, int N, int G,
                          void* stream);
 
+/* ---- Image generation: prior draws and the image grid (csrc/sample.hip) -------------------------------------------
+ * The two ends of the reference's module/sample.py::sample(): noise -> latent draws of the prior, decoded rows -> the grid of
+ * images, its cells and its 8-bit form.  Neither entry point allocates or synchronises; no atomics, one writer per output
+ * element, the same bits run to run.
+ * Draws: eps (R, K) fp32 noise, y (R,) int64 labels on the device or NULL (component 0 for every row), means (C, K), T the
+ * whitening factor in the layout of GaussianPrior._var_parameter ((C,), (C, K) or (C, K, K): only the lower triangle is read;
+ * NULL allowed in mode 0), t a temperature -> z (R, K) dense:
+ *   0  UNIT    z = means[y] + t eps                 (module/sample.py:129-132: the prior's variance is ignored)
+ *   1  SCALAR  z = means[y] + (t eps) / T[y]        2  DIAG  z = means[y] + (t eps) / T[y, k]
+ *   3  FULL    z = means[y] + u, tril(T[y]) u = t eps        (the inverse of whiten(), module/priors.py:228-233)
+ * Modes 0 - 2: each product, quotient and sum is rounded on its own, in that order - the fp32 torch expressions bit for bit
+ * (t = 1, mode 0: the reference's z + mean).  Mode 3: one forward substitution per row in fp32 by one 64-lane wave; the order
+ * of every sum depends on K alone, not on R or the launch.  A label outside [0, C) is never used as an index: its row is NaN
+ * and *status (device int32, owned and cleared by the caller) is set to 1 (bit 0), as for jvae_wim_scores_f32.
+ * 1 <= K <= 1024, 1 <= C, 0 <= R; any malformed argument: -1 (JVAE_EINVAL).
+ * Grid: x_in (N, D, H, W) or NULL, decoded rows x_out (Rr, N, D, H, W), specs a DEVICE int32 array of Ncol triples
+ * (kind, a, b) owned by the caller, specs_host the same values in host memory (checked there):
+ *   0  INPUT    x_in[row]        1  DRAW  x_out[a, row]        2  AVERAGE  (sum_{l = a .. b} x_out[l, row]) / (b - a + 1)
+ * (the sum in ascending l in fp32, then one division) -> cell (row, column) of grid_f32 (D, N H, Ncol W) and / or of
+ * grid_u8 (N H, Ncol W, D), channel last (either may be NULL, not both).  The 8-bit value is
+ * floor(min(max(v * 255 + 0.5, 0), 255)), product and sum rounded separately (torchvision's save_image:
+ * mul(255).add_(0.5).clamp_(0, 255).to(uint8)); NaN gives 0.  INPUT and DRAW cells are copies.  16-byte accesses when W is a
+ * multiple of 4 and the tensors are 16-byte aligned (grid_u8: 4-byte), a scalar path otherwise.
+ * grid_u8 with D > 4: -2 (JVAE_ENOTSUP; any D for grid_f32 alone).  1 <= Ncol <= 1024; a kind-0 column without x_in, a kind
+ * outside 0 .. 2, a or b of a kind-1 / kind-2 column outside [0, Rr), b < a in kind 2: -1 (JVAE_EINVAL). */
+int jvae_prior_sample_f32(const float* eps, const long long* y, const float* means, const float* T, float* z, int* status,
+                          long R, int K, int C, float t, int mode, void* stream);
+int jvae_image_grid_f32(const float* x_in, const float* x_out, const int* specs, const int* specs_host, int Ncol, float* grid_f32,
+                        unsigned char* grid_u8, int N, int D, int H, int W, int Rr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ What is NOT rebuilt here (raises NotImplementedError when asked for): (cvae / xv
 feature stacks (torchvision); a per-dimension sigma (the reference fails on it too).  A categorical (256-level) decoder,
 its label-free evaluation included, pooling / up-sampling layer tokens, SGD,
 the `y=None` all-class evaluation with its OOD scores, the WIM fine-tuning step and the evaluation methods accuracy(),
-ood_detection_rates() and misclassification_detection_rates() are built.
+ood_detection_rates() and misclassification_detection_rates() are built, and so is generate():
+images decoded from draws of the prior (module/sample.py builds the reference's grids of them).
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -528,6 +529,51 @@ class ClassificationVariationalNetwork(nn.Module):
             m = self.encoder.prior.mean
             logits = ops.linear(z, m, m.pow(2).sum(-1) / 2)
         return x_, logits
+
+    def generate(self, y=None, L=1, epsilon=None, temperature=1., prior_variance=False, prior=None, z_output=False):
+        """Images decoded from draws of the prior: z ~ p(z | y), x = imager(decoder(z)) -> (L, N, *input_shape) fp32 on the
+        device (what the prior branch of the reference's module/sample.py:124-139 computes by hand).
+
+        y (N,) labels: one draw set per label; default one per class for a class-conditional prior, and N = num_labels
+        unconditioned items for a single prior (its y, if given, only sets N).  epsilon (L, N, K) injects the unit noise.
+        prior_variance=False is the reference's draw, mean[y] + temperature * epsilon; True draws with the prior's own
+        variance (GaussianPrior.sample).  prior: another prior than self.encoder.prior (the alternate one of a WIMJob).
+        z_output=True returns (x, z).
+
+        Runs under no_grad with the whole model in eval mode (running-statistics BatchNorm: decoded rows are independent), so
+        the L * N rows go through the decoder in slabs of `_eval_slab_rows()` like the label-free evaluation; the training flag
+        is restored.  fp32 compute mode only (bf16: NotImplementedError, as odin_scores)."""
+        if not self.x_is_generated:
+            raise ValueError('You try to generate images with a net which is {}'.format(self.type))     # module/sample.py:158-160
+        if getattr(self, 'compute_dtype', 'fp32') != 'fp32':
+            raise NotImplementedError('generate() is built for the fp32 compute mode (set_compute_dtype("fp32"))')
+        pr = self.encoder.prior if prior is None else prior
+        dev = self.device
+        if y is None:
+            n = epsilon.shape[1] if epsilon is not None and not pr.conditional else self.num_labels
+            y = torch.arange(n, device=dev)
+        y = y.reshape(-1).to(dev)
+        N, K = y.shape[0], self.latent_dim
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                z = pr.sample(y=y if pr.conditional else None, n=N, L=L, epsilon=epsilon, temperature=temperature,
+                              with_variance=prior_variance)
+                rows, slab = z.shape[0] * N, self._eval_slab_rows()
+                zf = z.reshape(rows, K)
+                with self._constant_weights(zf):
+                    if rows <= slab:
+                        x_ = self._decode_rows(zf)
+                    else:
+                        x_ = torch.empty((rows, *self._reco_shape()), device=dev, dtype=torch.float32)
+                        for r0 in range(0, rows, slab):
+                            x_[r0:r0 + slab].copy_(self._decode_rows(zf[r0:r0 + slab]).view(-1, *self._reco_shape()))
+        finally:
+            if was_training:
+                self.train()
+        x_ = x_.view(z.shape[0], N, *self._reco_shape())
+        return (x_, z) if z_output else x_
 
     def forward_from_features(self, x_features, y, x, z_output=True, sampling_epsilon_norm_out=False,
                               sigma_out=False, epsilon=None):

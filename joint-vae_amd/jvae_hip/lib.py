@@ -128,6 +128,8 @@ _SIGS = {
     'jvae_odin_perturb_f32': (c_int, [P, P, P, P, P, c_long, c_int, P]),
     'jvae_wim_scores_f32': (c_int, [P, P, P, c_int, P, P, c_int, P, c_long, c_int, c_long, P, P]),
     'jvae_group_tally_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    'jvae_prior_sample_f32': (c_int, [P] * 6 + [c_long, c_int, c_int, c_float, c_int, P]),
+    'jvae_image_grid_f32': (c_int, [P, P, P, P, c_int, P, P] + [c_int] * 5 + [P]),
 }
 
 

@@ -1464,6 +1464,99 @@ def group_tally(values, group, sums, counts):
     return sums, counts
 
 
+# ------------------------------------------------------------------------- image generation (csrc/sample.hip)
+SAMPLE_MODES = {'unit': 0, 'scalar': 1, 'diag': 2, 'full': 3}
+GRID_KINDS = {'input': 0, 'draw': 1, 'average': 2}
+GRID_MAX_COLUMNS = 1024
+
+
+def prior_sample(eps, y, means, T, mode='unit', temperature=1., out=None, status=None):
+    """Latent draws of a Gaussian prior from noise, ONE launch: eps (..., K) fp32, y (...) int64 labels or None (component 0),
+    means (C, K), T the whitening factor ((C,), (C, K) or (C, K, K) by mode; unused by 'unit') -> z of eps's shape:
+    'unit' means[y] + t eps (the reference's draw, module/sample.py:129-132) | 'scalar' / 'diag' means[y] + (t eps) / T[y(, k)]
+    | 'full' means[y] + tril(T[y])^-1 (t eps).  The first three are the fp32 torch expressions bit for bit.  out: a dense fp32
+    tensor of eps's shape to write into.  status as for `wim_scores`: bit 0 is set when a label is outside [0, C) (that row is
+    NaN); default `wim_status(device)`, read and raised on by `wim_check_status`.  Nothing is synchronised."""
+    if mode not in SAMPLE_MODES:
+        raise L.JvaeHipError(f'prior_sample: mode {mode!r} unknown (one of {sorted(SAMPLE_MODES)})')
+    eps = _c(_f32(eps, 'prior_sample'))
+    means = _c(_f32(means, 'prior_sample'))
+    L.ptr(eps)
+    dev = eps.device
+    if means.dim() != 2 or eps.dim() < 1 or eps.shape[-1] != means.shape[1] or means.device != dev:
+        raise L.JvaeHipError(f'prior_sample: eps (..., K) and means (C, K) on one device expected, got {tuple(eps.shape)}, '
+                             f'{tuple(means.shape)}')
+    C, K = means.shape
+    R = eps.numel() // K
+    if mode != 'unit':
+        T = _c(_f32(T, 'prior_sample'))
+        want = {'scalar': (C,), 'diag': (C, K), 'full': (C, K, K)}[mode]
+        if tuple(T.shape) != want or T.device != dev:
+            raise L.JvaeHipError(f'prior_sample: a {want} factor on {dev} expected for mode {mode!r}, got {tuple(T.shape)}')
+    else:
+        T = None
+    if y is not None:
+        if y.dtype != torch.int64 or y.numel() != R or y.device != dev:
+            raise L.JvaeHipError(f'prior_sample: {R} int64 labels on {dev} expected, got {tuple(y.shape)} {y.dtype}')
+        y = _c(y)
+    if out is None:
+        out = torch.empty_like(eps)
+    elif out.dtype != torch.float32 or out.shape != eps.shape or not out.is_contiguous() or out.device != dev:
+        raise L.JvaeHipError(f'prior_sample: a dense fp32 output of shape {tuple(eps.shape)} on {dev} expected')
+    if status is None:
+        status = wim_status(dev)
+    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise L.JvaeHipError('prior_sample: an int32 status word on the device of the noise expected')
+    L.check(L.load().jvae_prior_sample_f32(L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T), L.ptr(out), L.ptr(status), R, K, C,
+                                           float(temperature), SAMPLE_MODES[mode], L.stream_ptr()), 'jvae_prior_sample_f32')
+    return out
+
+
+def grid_columns(columns, device):
+    """The column specs of `image_grid` in both forms the kernel takes: [('input',) | ('draw', a) | ('average', a, b)] ->
+    (host ctypes array, (Ncol, 3) int32 device tensor).  Build once for a layout that is launched repeatedly."""
+    flat = []
+    for col in columns:
+        kind = col[0]
+        if kind not in GRID_KINDS or len(col) != {'input': 1, 'draw': 2, 'average': 3}[kind]:
+            raise L.JvaeHipError(f'image_grid: column {col!r} is not (input,), (draw, a) or (average, a, b)')
+        a = int(col[1]) if len(col) > 1 else 0
+        flat += [GRID_KINDS[kind], a, int(col[2]) if len(col) > 2 else a]
+    if not 1 <= len(columns) <= GRID_MAX_COLUMNS:
+        raise L.JvaeHipError(f'image_grid: 1 .. {GRID_MAX_COLUMNS} columns expected, got {len(columns)}')
+    host = (ctypes.c_int * len(flat))(*flat)
+    return host, torch.tensor(flat, dtype=torch.int32, device=device).view(-1, 3)
+
+
+def image_grid(x_in, x_out, columns, f32=True, u8=True):
+    """The grid of images of module/sample.py in ONE launch.  x_in (N, D, H, W) or None, x_out (Rr, N, D, H, W) decoded rows,
+    columns: a list [('input',) | ('draw', a) | ('average', a, b)] (x_in[n] | x_out[a, n] | the mean of x_out[a .. b, n], b
+    included) or the pair `grid_columns` made of one -> (grid_f32 (D, N H, Ncol W) or None, grid_u8 (N H, Ncol W, D) uint8,
+    channel last, or None): cell (n, c) is rows n H .. (n + 1) H, columns c W .. (c + 1) W.  The 8-bit value is
+    floor(clamp(v * 255 + 0.5, 0, 255)) (torchvision's save_image), NaN -> 0; it needs D <= 4."""
+    x_out = _c(_f32(x_out, 'image_grid'))
+    L.ptr(x_out)
+    dev = x_out.device
+    if x_out.dim() != 5:
+        raise L.JvaeHipError(f'image_grid: decoded rows (Rr, N, D, H, W) expected, got {tuple(x_out.shape)}')
+    Rr, N, D, H, W = x_out.shape
+    if x_in is not None:
+        x_in = _c(_f32(x_in, 'image_grid'))
+        if tuple(x_in.shape) != (N, D, H, W) or x_in.device != dev:
+            raise L.JvaeHipError(f'image_grid: inputs {(N, D, H, W)} on {dev} expected, got {tuple(x_in.shape)}')
+    host, specs = columns if isinstance(columns, tuple) and torch.is_tensor(columns[1]) else grid_columns(columns, dev)
+    Ncol = specs.shape[0]
+    if specs.dtype != torch.int32 or specs.device != dev or len(host) != 3 * Ncol:
+        raise L.JvaeHipError('image_grid: column specs as made by grid_columns on the device of the rows expected')
+    if not (f32 or u8):
+        raise L.JvaeHipError('image_grid: nothing to write')
+    gf = torch.empty((D, N * H, Ncol * W), dtype=torch.float32, device=dev) if f32 else None
+    gu = torch.empty((N * H, Ncol * W, D), dtype=torch.uint8, device=dev) if u8 else None      # D > 4: the entry point refuses
+    L.check(L.load().jvae_image_grid_f32(L.ptr(x_in), L.ptr(x_out), L.ptr(_c(specs)), host, Ncol, L.ptr(gf), L.ptr(gu), N, D, H, W,
+                                         Rr, L.stream_ptr()), 'jvae_image_grid_f32')
+    return gf, gu
+
+
 def misclass_split(scores, mask):
     """(M, N) fp32 score rows and an (N,) mask (non-zero / True = correctly classified) -> ins (M, n_correct), outs
     (M, N - n_correct), n_correct: both row sets compacted in their original order by ONE scan of the mask (two views of one

@@ -251,6 +251,35 @@ class GaussianPrior(nn.Module):
             log_det = log_det.index_select(0, y.reshape(-1)).view(u.shape)
         return -math.log(2 * math.pi) * self.dim / 2 - u / 2 - log_det / 2
 
+    def sample(self, y=None, n=None, L=1, epsilon=None, temperature=1., with_variance=True):
+        """L draws per item from p(z | y) -> (L, N, K) fp32 on the prior's device, through ONE launch of ops.prior_sample.
+        A conditional prior takes y (N,) int64 labels, a non-conditional one the number of items n.  epsilon (L, N, K):
+        the unit noise (drawn with torch.randn on the device when not given); temperature scales it.  with_variance=False
+        ignores the prior's variance: mean[y] + temperature * epsilon, what the reference's sample() draws
+        (module/sample.py:129-132); True applies the inverse of `whiten`: mean[y] + T_y^-1 (temperature * epsilon).
+        A label outside [0, C) gives a NaN row and sets bit 0 of ops.wim_status(device) (ops.wim_check_status raises on it)."""
+        dev = self.mean.device
+        if self.conditional:
+            if y is None:
+                raise ValueError('a conditional prior samples given labels: pass y')
+            y = y.reshape(-1).to(device=dev, dtype=torch.int64)
+            n = y.shape[0]
+        elif n is None:
+            if epsilon is None:
+                raise ValueError('a non-conditional prior needs the number of items n (or epsilon)')
+            n = epsilon.shape[1]
+        if epsilon is None:
+            epsilon = torch.randn(L, n, self.dim, device=dev)
+        elif tuple(epsilon.shape[1:]) != (n, self.dim):
+            raise ValueError('epsilon: (L, {}, {}) expected, got {}'.format(n, self.dim, tuple(epsilon.shape)))
+        L = epsilon.shape[0]
+        if self.conditional:
+            labels, means, T = y.unsqueeze(0).expand(L, n).reshape(-1), self.mean, self._var_parameter
+        else:
+            labels, means, T = None, self.mean.reshape(1, self.dim), self._var_parameter.unsqueeze(0)
+        return ops.prior_sample(epsilon.to(device=dev, dtype=torch.float32), labels, means.detach(), T.detach(),
+                                mode=self.var_dim if with_variance else 'unit', temperature=temperature)
+
     def __repr__(self):
         pre = 'conditional ' if self.conditional else ''
         var = ('learned ' if self.learned_var else '') + self.var_dim + ' variance'
@@ -294,6 +323,12 @@ class TiltedGaussianPrior(GaussianPrior):
     def log_density(self, z, y=None):
         return super().log_density(z, y) - z.norm(dim=-1)
 
+    def sample(self, *a, with_variance=True, **kw):
+        if with_variance:
+            raise NotImplementedError('the tilted density is not Gaussian: only with_variance=False (mean + noise, the '
+                                      'reference\'s draw) is built')
+        return super().sample(*a, with_variance=False, **kw)
+
     def __repr__(self):
         m = ' with {} {}means'.format(self.num_priors, 'learned ' if self.learned_means else '') \
             if self.num_priors > 1 else ''
@@ -333,6 +368,12 @@ class UniformWithGaussianTailPrior(GaussianPrior):
         inside = -self._alpha * torch.ones_like(z)
         tail = -c / 2 - z.square() / 2
         return torch.where(z.abs() > self.tau, tail, inside).sum(-1)
+
+    def sample(self, *a, with_variance=True, **kw):
+        if with_variance:
+            raise NotImplementedError('the uniform-with-tails density is not Gaussian: only with_variance=False (mean + noise, '
+                                      'the reference\'s draw) is built')
+        return super().sample(*a, with_variance=False, **kw)
 
     def __repr__(self):
         m = ' with {} {}means'.format(self.num_priors, 'learned ' if self.learned_means else '') \

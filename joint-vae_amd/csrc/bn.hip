@@ -8,37 +8,13 @@
 // Numerics: per-channel sums are taken on data shifted by the channel's first element (robust against
 // |mean| >> std), per-block partials are combined in fp64 by a one-block finalize kernel.
 #include <stdlib.h>
-#include "common.h"
+#include "bn_core.h"
 #include "jvae_internal.h"
 
 namespace {
 
-constexpr int MAX_SPLIT = 64;
-
-// y = fmaf(x, scale, shift): one definition so that backward re-derives the forward's ReLU mask bit-exactly
-__device__ __forceinline__ void bn_coef(float g, float b, float mean, float invstd, float* sc, float* sh) {
-    *sc = g * invstd;
-    *sh = b - mean * (g * invstd);
-}
-
-// float offset of the i-th float4 of channel c inside the images [nb, ne): 32-bit arithmetic, a shift when the plane size is a
-// power of two.  (The loops used 64-bit i / P4 and i % P4 per 16 bytes: ~100 vector instructions per load, which is what made
-// these HBM-bound kernels crawl beside the matrix-core kernels of the other stream - they compete for the same issue slots.)
-struct Plane4Idx {
-    unsigned p4; int sh; long stride, base;
-    __device__ __forceinline__ long operator()(unsigned i) const {
-        const unsigned n = sh >= 0 ? i >> sh : i / p4;
-        return base + (long)n * stride + (long)(i - n * p4) * 4;
-    }
-};
-__device__ __forceinline__ Plane4Idx plane4_idx(int nb, int C, int c, int P) {
-    Plane4Idx u;
-    u.p4 = (unsigned)(P >> 2);
-    u.sh = (u.p4 & (u.p4 - 1)) == 0 ? __ffs((int)u.p4) - 1 : -1;
-    u.stride = (long)C * P;
-    u.base = ((long)nb * C + c) * P;
-    return u;
-}
+constexpr int MAX_SPLIT_F32 = 64;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // partial[c][s] = (sum(x-p), sum((x-p)^2)) over the images of split s;  p = x[0][c][0]
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, float* __restrict__ partial,
@@ -47,25 +23,8 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     const int c = blockIdx.x, s = blockIdx.y;
     const float pivot = pv ? pv[c] : x[(long)c * P];
     const ImageRange ir = image_range(N, nsplit, s);   // trailing parts may be empty, never negative
-    const int nb = ir.nb, ne = ir.ne;
     float s1 = 0.f, s2 = 0.f;
-    if ((P & 3) == 0) {
-        const unsigned cnt = (unsigned)(ne - nb) * (unsigned)(P >> 2);
-        const Plane4Idx pi = plane4_idx(nb, C, c, P);
-#pragma unroll 2
-        for (unsigned i = threadIdx.x; i < cnt; i += 256) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(x + pi(i));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = v[j] - pivot; s1 += d; s2 += d * d; }
-        }
-    } else {
-        const long cnt = (long)(ne - nb) * P;
-        for (long i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const long n = nb + i / P, q = i % P;
-            const float d = x[(n * C + c) * (long)P + q] - pivot;
-            s1 += d; s2 += d * d;
-        }
-    }
+    bn_plane_walk(x, nullptr, nullptr, ir.nb, ir.ne, C, c, P, [&](float v, float) { const float d = v - pivot; s1 += d; s2 += d * d; });
     s1 = block_sum(s1, red);
     s2 = block_sum(s2, red);
     if (threadIdx.x == 0) {
@@ -86,40 +45,18 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     __shared__ float cs[2];
     __shared__ double dred[2][4];
     const int c = blockIdx.x, j = blockIdx.y;
-    double s1 = 0., s2 = 0.;
-    if (training) {                              // fold the channel's partial sums with the whole block (fp64)
-        for (int s = threadIdx.x; s < nsplit; s += blockDim.x) {
-            s1 += (double)partial[((long)c * nsplit + s) * 2 + 0];
-            s2 += (double)partial[((long)c * nsplit + s) * 2 + 1];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
-        if ((threadIdx.x & 63) == 0) { dred[0][threadIdx.x >> 6] = s1; dred[1][threadIdx.x >> 6] = s2; }
-        __syncthreads();
-    }
+    BnSums t = {0., 0.};
+    if (training) t = bn_fold<BN_FOLD_BLOCK_SEQ>(partial, c, nsplit, dred);     // the whole block folds the channel's partial sums
     if (threadIdx.x == 0) {
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
         float mean, invstd;
         if (training) {
-            s1 = dred[0][0] + dred[0][1] + dred[0][2] + dred[0][3];
-            s2 = dred[1][0] + dred[1][1] + dred[1][2] + dred[1][3];
             const double n = (double)N * P * count_mult;          // count_mult = ranks of a synchronised BatchNorm
-            const double dm = s1 / n;
-            double var = s2 / n - dm * dm;
-            if (var < 0.) var = 0.;
             const double pv = ext_pivot ? (pivot ? (double)pivot[c] : 0.) : (double)x[(long)c * P];
-            mean = (float)(pv + dm);
-            invstd = (float)(1.0 / sqrt(var + (double)eps));
-            if (j == 0) {
-                save_mean[c] = mean;
-                save_invstd[c] = invstd;
-                if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-                if (running_var) {
-                    const float unbiased = (float)(n > 1. ? var * n / (n - 1.) : var);
-                    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-                }
-                if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
-            }
+            const BnMoments m = bn_moments(t.s1, t.s2, n, pv, eps);
+            if (j == 0) bn_publish(m, n, c, momentum, save_mean, save_invstd, running_mean, running_var, num_batches_tracked);
+            mean = m.mean;
+            invstd = m.invstd;
         } else {
             mean = running_mean[c];
             invstd = rsqrtf(running_var[c] + eps);
@@ -129,27 +66,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     __syncthreads();
     const float sc = cs[0], sh = cs[1];
     const ImageRange ir = image_range(N, nchunk, j);   // trailing parts may be empty, never negative
-    const int nb = ir.nb, ne = ir.ne;
-    if ((P & 3) == 0) {
-        const unsigned cnt = (unsigned)(ne - nb) * (unsigned)(P >> 2);
-        const Plane4Idx pi = plane4_idx(nb, C, c, P);
-#pragma unroll 2
-        for (unsigned i = threadIdx.x; i < cnt; i += 256) {
-            const long off = pi(i);
-            f32x4 v = *reinterpret_cast<const f32x4*>(x + off);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float t = fmaf(v[e], sc, sh); v[e] = jvae_act(t, relu); }
-            *reinterpret_cast<f32x4*>(y + off) = v;
-        }
-    } else {
-        const long cnt = (long)(ne - nb) * P;
-        for (long i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const long n = nb + i / P, q = i % P;
-            const long off = (n * C + c) * (long)P + q;
-            const float t = fmaf(x[off], sc, sh);
-            y[off] = jvae_act(t, relu);
-        }
-    }
+    bn_plane_walk(x, nullptr, y, ir.nb, ir.ne, C, c, P, [&](float v, float) { return jvae_act(fmaf(v, sc, sh), relu); });
 }
 
 // One block per channel: folds the partial sums (fp64, fixed order), publishes mean / invstd, updates the running
@@ -167,34 +84,13 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
     float mean, invstd;
     if (training) {
-        double s1 = 0., s2 = 0.;
-        for (int s = l; s < nsplit; s += 256) {
-            s1 += (double)partial[((long)c * nsplit + s) * 2 + 0];
-            s2 += (double)partial[((long)c * nsplit + s) * 2 + 1];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
-        if ((l & 63) == 0) { dred[0][l >> 6] = s1; dred[1][l >> 6] = s2; }
-        __syncthreads();
-        s1 = (dred[0][0] + dred[0][1]) + (dred[0][2] + dred[0][3]);
-        s2 = (dred[1][0] + dred[1][1]) + (dred[1][2] + dred[1][3]);
+        const BnSums t = bn_fold<BN_FOLD_BLOCK_PAIR>(partial, c, nsplit, dred);
         const double n = (double)N * P;
-        const double dm = s1 / n;
-        double var = s2 / n - dm * dm;
-        if (var < 0.) var = 0.;
         const double pv = ext_pivot ? (pivot ? (double)pivot[c] : 0.) : (double)x[(long)c * P];
-        mean = (float)(pv + dm);
-        invstd = (float)(1.0 / sqrt(var + (double)eps));
-        if (l == 0) {
-            save_mean[c] = mean;
-            save_invstd[c] = invstd;
-            if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-            if (running_var) {
-                const float unbiased = (float)(n > 1. ? var * n / (n - 1.) : var);
-                running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-            }
-            if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
-        }
+        const BnMoments m = bn_moments(t.s1, t.s2, n, pv, eps);
+        if (l == 0) bn_publish(m, n, c, momentum, save_mean, save_invstd, running_mean, running_var, num_batches_tracked);
+        mean = m.mean;
+        invstd = m.invstd;
     } else {
         mean = running_mean[c];
         invstd = rsqrtf(running_var[c] + eps);
@@ -216,34 +112,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
     float sc, sh;
     bn_coef(g_, b_, mu, is, &sc, &sh);
     const ImageRange ir = image_range(N, nsplit, s);   // trailing parts may be empty, never negative
-    const int nb = ir.nb, ne = ir.ne;
-    float s1 = 0.f, s2 = 0.f;
-    if ((P & 3) == 0) {
-        const unsigned cnt = (unsigned)(ne - nb) * (unsigned)(P >> 2);
-        const Plane4Idx pi = plane4_idx(nb, C, c, P);
-#pragma unroll 2
-        for (unsigned i = threadIdx.x; i < cnt; i += 256) {
-            const long off = pi(i);
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + off);
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(dy + off);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float g = gv[e];
-                if (relu && !(fmaf(xv[e], sc, sh) > 0.f)) g *= neg;
-                s1 += g; s2 += g * ((xv[e] - mu) * is);
-            }
-        }
-    } else {
-        const long cnt = (long)(ne - nb) * P;
-        for (long i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const long n = nb + i / P, q = i % P;
-            const long idx = (n * C + c) * (long)P + q;
-            const float xv = x[idx];
-            float g = dy[idx];
-            if (relu && !(fmaf(xv, sc, sh) > 0.f)) g *= neg;
-            s1 += g; s2 += g * ((xv - mu) * is);
-        }
-    }
+    // (s1, s2) as one two-lane sum: its second lane takes the ROUNDED product - inside a vector add the product cannot contract
+    // into an FMA, whatever the vectoriser makes of the loop - and the pair costs one packed add
+    f32x2 acc = 0.f;
+    bn_plane_walk(x, dy, nullptr, ir.nb, ir.ne, C, c, P, [&](float xv, float g) {
+        if (relu && !(fmaf(xv, sc, sh) > 0.f)) g *= neg;
+        acc += f32x2{g, g * ((xv - mu) * is)};
+    });
+    float s1 = acc[0], s2 = acc[1];
     s1 = block_sum(s1, red);
     s2 = block_sum(s2, red);
     if (threadIdx.x == 0) {
@@ -265,18 +141,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     const int c = blockIdx.x, j = rev ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.y;
     const float neg = relu == JVAE_ACT_LEAKY ? JVAE_LEAKY_SLOPE : 0.f;
     if (threadIdx.x == 0) {
-        double s1 = 0., s2 = 0.;
-        for (int s = 0; s < nsplit; ++s) {
-            s1 += (double)partial[((long)c * nsplit + s) * 2 + 0];
-            s2 += (double)partial[((long)c * nsplit + s) * 2 + 1];
-        }
+        const BnSums t = bn_fold<BN_FOLD_THREAD>(partial, c, nsplit);
         const double M = (double)N * P * count_mult;
         // synchronised BatchNorm: the means over ALL ranks come from gsums; dgamma / dbeta stay the LOCAL sums
-        ms[0] = (float)((gsums ? (double)gsums[2 * c] : s1) / M);
-        ms[1] = (float)((gsums ? (double)gsums[2 * c + 1] : s2) / M);
+        ms[0] = (float)((gsums ? (double)gsums[2 * c] : t.s1) / M);
+        ms[1] = (float)((gsums ? (double)gsums[2 * c + 1] : t.s2) / M);
         if (j == 0) {
-            if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s1;
-            if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s2;
+            if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)t.s1;
+            if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)t.s2;
         }
     }
     __syncthreads();
@@ -287,34 +159,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     bn_coef(g_, b_, mu, is, &sc, &sh);
     const float k = g_ * is;
     const ImageRange ir = image_range(N, nchunk, j);   // trailing parts may be empty, never negative
-    const int nb = ir.nb, ne = ir.ne;
-    if ((P & 3) == 0) {
-        const unsigned cnt = (unsigned)(ne - nb) * (unsigned)(P >> 2);
-        const Plane4Idx pi = plane4_idx(nb, C, c, P);
-#pragma unroll 2
-        for (unsigned i = threadIdx.x; i < cnt; i += 256) {
-            const long off = pi(i);
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + off);
-            f32x4 gv = *reinterpret_cast<const f32x4*>(dy + off);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float g = gv[e];
-                if (relu && !(fmaf(xv[e], sc, sh) > 0.f)) g *= neg;
-                gv[e] = k * (g - m1 - ((xv[e] - mu) * is) * m2);
-            }
-            *reinterpret_cast<f32x4*>(dx + off) = gv;
-        }
-    } else {
-        const long cnt = (long)(ne - nb) * P;
-        for (long i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const long n = nb + i / P, q = i % P;
-            const long idx = (n * C + c) * (long)P + q;
-            const float xv = x[idx];
-            float g = dy[idx];
-            if (relu && !(fmaf(xv, sc, sh) > 0.f)) g *= neg;
-            dx[idx] = k * (g - m1 - ((xv - mu) * is) * m2);
-        }
-    }
+    bn_plane_walk(x, dy, dx, ir.nb, ir.ne, C, c, P, [&](float xv, float g) {
+        if (relu && !(fmaf(xv, sc, sh) > 0.f)) g *= neg;
+        return k * (g - m1 - ((xv - mu) * is) * m2);
+    });
 }
 
 // Eval-mode backward (running statistics are constants): dx = dy * gamma * rsqrt(running_var + eps) * act'(y), one elementwise
@@ -331,46 +179,19 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float* __restric
     float sc, sh;
     bn_coef(g_, b_, running_mean[c], rsqrtf(running_var[c] + eps), &sc, &sh);
     const ImageRange ir = image_range(N, nchunk, j);
-    const int nb = ir.nb, ne = ir.ne;
-    if ((P & 3) == 0) {
-        const unsigned cnt = (unsigned)(ne - nb) * (unsigned)(P >> 2);
-        const Plane4Idx pi = plane4_idx(nb, C, c, P);
-#pragma unroll 2
-        for (unsigned i = threadIdx.x; i < cnt; i += 256) {
-            const long off = pi(i);
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + off);
-            f32x4 gv = *reinterpret_cast<const f32x4*>(dy + off);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float g = gv[e];
-                if (relu && !(fmaf(xv[e], sc, sh) > 0.f)) g *= neg;
-                gv[e] = g * sc;
-            }
-            *reinterpret_cast<f32x4*>(dx + off) = gv;
-        }
-    } else {
-        const long cnt = (long)(ne - nb) * P;
-        for (long i = threadIdx.x; i < cnt; i += blockDim.x) {
-            const long n = nb + i / P, q = i % P;
-            const long idx = (n * C + c) * (long)P + q;
-            float g = dy[idx];
-            if (relu && !(fmaf(x[idx], sc, sh) > 0.f)) g *= neg;
-            dx[idx] = g * sc;
-        }
-    }
+    bn_plane_walk(x, dy, dx, ir.nb, ir.ne, C, c, P, [&](float xv, float g) {
+        if (relu && !(fmaf(xv, sc, sh) > 0.f)) g *= neg;
+        return g * sc;
+    });
 }
 
 // sums[c] = sum over splits of partial[c][s] (fp64 accumulation, fixed order)
 __global__ void bn_fold_kernel(const float* __restrict__ partial, float* __restrict__ sums, int C, int nsplit) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double s1 = 0., s2 = 0.;
-    for (int s = 0; s < nsplit; ++s) {
-        s1 += (double)partial[((long)c * nsplit + s) * 2 + 0];
-        s2 += (double)partial[((long)c * nsplit + s) * 2 + 1];
-    }
-    sums[2 * c] = (float)s1;
-    sums[2 * c + 1] = (float)s2;
+    const BnSums t = bn_fold<BN_FOLD_THREAD>(partial, c, nsplit);
+    sums[2 * c] = (float)t.s1;
+    sums[2 * c + 1] = (float)t.s2;
 }
 
 inline int pick_split(int N, int C, int P) {
@@ -379,7 +200,7 @@ inline int pick_split(int N, int C, int P) {
     if (s < 1) s = 1;
     int cap = (2048 + C - 1) / C;          // ~2048 blocks in flight is plenty
     if (s > cap) s = cap;
-    if (s > MAX_SPLIT) s = MAX_SPLIT;
+    if (s > MAX_SPLIT_F32) s = MAX_SPLIT_F32;
     if (s > N) s = N;
     return s < 1 ? 1 : s;
 }
@@ -415,8 +236,8 @@ int jvae_image_range(int N, int parts, int j, int* nb, int* ne) {
     return 0;
 }
 
-// workspace: 2*C*MAX_SPLIT partials + 2*C coefficients
-size_t jvae_bn_workspace_bytes(int C) { return sizeof(float) * ((size_t)2 * C * MAX_SPLIT + (size_t)2 * C); }
+// workspace: 2*C*MAX_SPLIT_F32 partials + 2*C coefficients
+size_t jvae_bn_workspace_bytes(int C) { return sizeof(float) * ((size_t)2 * C * MAX_SPLIT_F32 + (size_t)2 * C); }
 
 static int bn_fwd_impl(const float* x, const float* gamma, const float* beta,
                        float* running_mean, float* running_var, long long* num_batches_tracked,
@@ -425,28 +246,17 @@ static int bn_fwd_impl(const float* x, const float* gamma, const float* beta,
                        const float* ext_stats, int ext_nsplit, const float* ext_pivot, int count_mult,
                        void* ws, size_t ws_bytes, void* stream) {
     if (!x || !y || N < 0 || C <= 0 || P <= 0) return JVAE_EINVAL;
-    if (ws_bytes < jvae_bn_workspace_bytes(C) || !ws) return JVAE_EWORKSPACE;
-    if (N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const float* partial = (const float*)ws;
-    int ns = 1;
-    const bool ext = training && ext_stats && ext_nsplit > 0;
-    if (ext) {
-        partial = ext_stats;
-        ns = ext_nsplit;
-        if (!save_mean || !save_invstd) return JVAE_EINVAL;
-    } else if (training) {
-        if (!save_mean || !save_invstd) return JVAE_EINVAL;
-        ns = pick_split(N, C, P);
+    BnStatsSrc src;
+    const int rc = bn_stats_source(ws, ws_bytes, jvae_bn_workspace_bytes(C), N, training, ext_stats, ext_nsplit, save_mean, save_invstd,
+                                   running_mean, running_var, pick_split(N, C, P), [&](int ns) {
         hipLaunchKernelGGL(bn_stats_kernel, dim3(C, ns), dim3(256), 0, st, x, (float*)ws, N, C, P, ns, (const float*)nullptr);
-        JVAE_LAUNCH_CHECK();
-    } else if (!running_mean || !running_var) {
-        return JVAE_EINVAL;
-    }
+    }, &src);
+    if (rc != 0 || N == 0) return rc;
     const int nc = pick_chunk(N, C, P);
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(C, nc), dim3(256), 0, st, x, partial, gamma, beta, running_mean, running_var,
-                       num_batches_tracked, save_mean, save_invstd, y, N, C, P, ns, nc, momentum, eps, training, jvae_act_kind(relu),
-                       ext ? 1 : 0, ext_pivot, count_mult > 0 ? count_mult : 1);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(C, nc), dim3(256), 0, st, x, src.partial, gamma, beta, running_mean, running_var,
+                       num_batches_tracked, save_mean, save_invstd, y, N, C, P, src.nsplit, nc, momentum, eps, training,
+                       jvae_act_kind(relu), src.ext, ext_pivot, count_mult > 0 ? count_mult : 1);
     JVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -483,25 +293,16 @@ int jvae_bn_finalize_f32(const float* x, const float* gamma, const float* beta,
                          const float* ext_stats, int ext_nsplit, const float* ext_pivot,
                          void* ws, size_t ws_bytes, void* stream) {
     if (!x || !scale || !shift || N <= 0 || C <= 0 || P <= 0) return JVAE_EINVAL;
-    if (ws_bytes < jvae_bn_workspace_bytes(C) || !ws) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const float* partial = (const float*)ws;
-    int ns = 1;
-    const bool ext = training && ext_stats && ext_nsplit > 0;
-    if (training && (!save_mean || !save_invstd)) return JVAE_EINVAL;
-    if (ext) {
-        partial = ext_stats;
-        ns = ext_nsplit;
-    } else if (training) {
-        ns = pick_split(N, C, P);
+    BnStatsSrc src;
+    const int rc = bn_stats_source(ws, ws_bytes, jvae_bn_workspace_bytes(C), N, training, ext_stats, ext_nsplit, save_mean, save_invstd,
+                                   running_mean, running_var, pick_split(N, C, P), [&](int ns) {
         hipLaunchKernelGGL(bn_stats_kernel, dim3(C, ns), dim3(256), 0, st, x, (float*)ws, N, C, P, ns, (const float*)nullptr);
-        JVAE_LAUNCH_CHECK();
-    } else if (!running_mean || !running_var) {
-        return JVAE_EINVAL;
-    }
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, x, partial, gamma, beta, running_mean, running_var,
-                       num_batches_tracked, save_mean, save_invstd, scale, shift, N, C, P, ns, momentum, eps, training,
-                       ext ? 1 : 0, ext_pivot);
+    }, &src);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, x, src.partial, gamma, beta, running_mean, running_var,
+                       num_batches_tracked, save_mean, save_invstd, scale, shift, N, C, P, src.nsplit, momentum, eps, training,
+                       src.ext, ext_pivot);
     JVAE_LAUNCH_CHECK();
     return 0;
 }

@@ -3,13 +3,13 @@
 // activation tensors are bf16.  HBM-bound: each pass streams the tensor once in 16-byte units (8 channels of a pixel),
 // a block owns one channel block (8 channels) x a chunk of images.
 // Reference: nn.BatchNorm2d + ReLU after every (de)conv (module/vae_layers/conv.py:214-220).
-#include "common.h"
+#include "bn_core.h"
 #include "jvae_internal.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int MAX_SPLIT = 512;     // partial sums per channel (few channel blocks -> many image splits to fill the chip)
+constexpr int MAX_SPLIT_B8 = 512;     // partial sums per channel (few channel blocks -> many image splits to fill the chip)
 
 // unit offset of flat index i (image-major inside this block's image range) without 64-bit division
 struct UnitIdx {
@@ -27,11 +27,6 @@ __device__ __forceinline__ UnitIdx unit_idx(int nb, int CB, int cb, long HW) {
     u.stride = (long)CB * HW;
     u.base = ((long)nb * CB + cb) * HW;
     return u;
-}
-
-__device__ __forceinline__ void bn_coef(float g, float b, float mean, float invstd, float* sc, float* sh) {
-    *sc = g * invstd;
-    *sh = b - mean * (g * invstd);
 }
 
 // reduce 8 per-thread values over the block (256 threads): result[ci] valid in thread 0
@@ -93,31 +88,12 @@ __global__ __launch_bounds__(64) void bn8_finalize_kernel(const bf16x8* __restri
     if (c < C) {
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
         if (training) {
-            double s1 = 0., s2 = 0.;
-            for (int s = l; s < nsplit; s += 64) {
-                s1 += (double)partial[((long)c * nsplit + s) * 2 + 0];
-                s2 += (double)partial[((long)c * nsplit + s) * 2 + 1];
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+            const BnSums t = bn_fold<BN_FOLD_WAVE>(partial, c, nsplit);
             const double n = (double)N * HW;
-            const double dm = s1 / n;
-            double var = s2 / n - dm * dm;
-            if (var < 0.) var = 0.;
             const double pv = ext_pivot ? (pivot ? (double)pivot[c] : 0.) : (double)(float)x[(long)(c >> 3) * HW][c & 7];
-            const float mean = (float)(pv + dm);
-            const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-            if (l == 0) {
-                save_mean[c] = mean;
-                save_invstd[c] = invstd;
-                if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-                if (running_var) {
-                    const float unbiased = (float)(n > 1. ? var * n / (n - 1.) : var);
-                    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
-                }
-                if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
-            }
-            bn_coef(g, b, mean, invstd, &sc, &sh);
+            const BnMoments m = bn_moments(t.s1, t.s2, n, pv, eps);
+            if (l == 0) bn_publish(m, n, c, momentum, save_mean, save_invstd, running_mean, running_var, num_batches_tracked);
+            bn_coef(g, b, m.mean, m.invstd, &sc, &sh);
         } else {
             bn_coef(g, b, running_mean[c], rsqrtf(running_var[c] + eps), &sc, &sh);
         }
@@ -201,21 +177,14 @@ __global__ __launch_bounds__(64) void bn8_bwd_finalize_kernel(const float* __res
                                                               float* dgamma, float* dbeta, int accumulate,
                                                               int N, int C, int C8, long HW, int nsplit) {
     const int c = blockIdx.x, l = threadIdx.x;
-    double s1 = 0., s2 = 0.;
-    if (c < C)
-        for (int s = l; s < nsplit; s += 64) {
-            s1 += (double)partial[((long)c * nsplit + s) * 2 + 0];
-            s2 += (double)partial[((long)c * nsplit + s) * 2 + 1];
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+    const BnSums t = bn_fold<BN_FOLD_WAVE>(partial, c, c < C ? nsplit : 0);    // padding channels: no partials, sums 0
     if (l == 0) {
         const double M = (double)N * HW;
-        coef[c] = (float)(s1 / M);
-        coef[C8 + c] = (float)(s2 / M);
+        coef[c] = (float)(t.s1 / M);
+        coef[C8 + c] = (float)(t.s2 / M);
         if (c < C) {
-            if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s1;
-            if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s2;
+            if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)t.s1;
+            if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)t.s2;
         }
     }
 }
@@ -262,14 +231,8 @@ __global__ __launch_bounds__(256) void bn8_bwd_apply_kernel(const bf16x8* __rest
 // sums[c] = fold of partial[c][0..nsplit) (fp64, fixed order): the (C,2) block the ranks all-reduce
 __global__ __launch_bounds__(64) void bn8_fold_kernel(const float* __restrict__ partial, float* __restrict__ sums, int nsplit) {
     const int c = blockIdx.x, l = threadIdx.x;
-    double s1 = 0., s2 = 0.;
-    for (int s = l; s < nsplit; s += 64) {
-        s1 += (double)partial[((long)c * nsplit + s) * 2 + 0];
-        s2 += (double)partial[((long)c * nsplit + s) * 2 + 1];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
-    if (l == 0) { sums[2 * c] = (float)s1; sums[2 * c + 1] = (float)s2; }
+    const BnSums t = bn_fold<BN_FOLD_WAVE>(partial, c, nsplit);
+    if (l == 0) { sums[2 * c] = (float)t.s1; sums[2 * c + 1] = (float)t.s2; }
 }
 
 // synchronised backward: means of (g, g*xhat) over ALL ranks from the all-reduced sums; dgamma / dbeta stay the local sums
@@ -312,7 +275,7 @@ inline int pick_split(int N, int CB, long HW) {
     if (s < 1) s = 1;
     long cap = (2048 + CB - 1) / CB;
     if (s > cap) s = cap;
-    if (s > MAX_SPLIT) s = MAX_SPLIT;
+    if (s > MAX_SPLIT_B8) s = MAX_SPLIT_B8;
     if (s > N) s = N;
     return (int)(s < 1 ? 1 : s);
 }
@@ -338,8 +301,30 @@ int jvae_bn_plan_b8(int N, int C, long HW, int* nsplit, int* nchunk) {
     return 0;
 }
 
-// partial sums (2 * C8 * MAX_SPLIT floats) followed by 2 * C8 per-channel coefficients
-size_t jvae_bn_workspace_bytes_b8(int C) { return sizeof(float) * ((size_t)2 * ((C + 7) / 8 * 8) * (MAX_SPLIT + 1)); }
+// partial sums (2 * C8 * MAX_SPLIT_B8 floats) followed by 2 * C8 per-channel coefficients
+size_t jvae_bn_workspace_bytes_b8(int C) { return sizeof(float) * ((size_t)2 * ((C + 7) / 8 * 8) * (MAX_SPLIT_B8 + 1)); }
+
+// The finalize path of both forward entry points (argument checks of x / N / C / HW are the callers'): statistics from
+// ext_stats, from the statistics kernel or from the running statistics, then one bn8_finalize_kernel launch writes `coef`.
+static int bn8_finalize(const void* x, const float* gamma, const float* beta,
+                        float* running_mean, float* running_var, long long* num_batches_tracked,
+                        float* save_mean, float* save_invstd, float* coef,
+                        int N, int C, long HW, float momentum, float eps, int training,
+                        const float* ext_stats, int ext_nsplit, const float* ext_pivot,
+                        void* ws, size_t ws_bytes, hipStream_t st) {
+    const int CB = (C + 7) / 8;
+    BnStatsSrc src;
+    const int rc = bn_stats_source(ws, ws_bytes, jvae_bn_workspace_bytes_b8(C), N, training, ext_stats, ext_nsplit, save_mean, save_invstd,
+                                   running_mean, running_var, pick_split(N, CB, HW), [&](int ns) {
+        hipLaunchKernelGGL(bn8_stats_kernel, dim3(CB, ns), dim3(256), 0, st, (const bf16x8*)x, (float*)ws, N, C, CB, HW, ns, (const float*)nullptr);
+    }, &src);
+    if (rc != 0 || N == 0) return rc;
+    hipLaunchKernelGGL(bn8_finalize_kernel, dim3(CB * 8), dim3(64), 0, st, (const bf16x8*)x, src.partial, gamma, beta,
+                       running_mean, running_var, num_batches_tracked, save_mean, save_invstd, coef, N, C, CB * 8, HW, src.nsplit,
+                       momentum, eps, training, src.ext, ext_pivot);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
 
 // x, y: B8 (N, ceil(C/8), HW, 8).  Workspace: jvae_bn_workspace_bytes_b8(C).  ext_stats as in jvae_bn_fwd_ext_f32
 // (ext_nsplit == 0: the statistics kernel runs here).
@@ -350,29 +335,12 @@ int jvae_bn_fwd_b8(const void* x, const float* gamma, const float* beta,
                    const float* ext_stats, int ext_nsplit, const float* ext_pivot,
                    void* ws, size_t ws_bytes, void* stream) {
     if (!x || !y || N < 0 || C <= 0 || HW <= 0) return JVAE_EINVAL;
-    if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
-    if (N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int CB = (C + 7) / 8;
-    const float* partial = (const float*)ws;
-    int ns = 1;
-    const bool ext = training && ext_stats && ext_nsplit > 0;
-    if (training && (!save_mean || !save_invstd)) return JVAE_EINVAL;
-    if (ext) {
-        partial = ext_stats;
-        ns = ext_nsplit;
-    } else if (training) {
-        ns = pick_split(N, CB, HW);
-        hipLaunchKernelGGL(bn8_stats_kernel, dim3(CB, ns), dim3(256), 0, st, (const bf16x8*)x, (float*)ws, N, C, CB, HW, ns, (const float*)nullptr);
-        JVAE_LAUNCH_CHECK();
-    } else if (!running_mean || !running_var) {
-        return JVAE_EINVAL;
-    }
-    float* coef = (float*)ws + (size_t)2 * CB * 8 * MAX_SPLIT;
-    hipLaunchKernelGGL(bn8_finalize_kernel, dim3(CB * 8), dim3(64), 0, st, (const bf16x8*)x, partial, gamma, beta,
-                       running_mean, running_var, num_batches_tracked, save_mean, save_invstd, coef, N, C, CB * 8, HW, ns,
-                       momentum, eps, training, ext ? 1 : 0, ext_pivot);
-    JVAE_LAUNCH_CHECK();
+    float* coef = ws ? (float*)ws + (size_t)2 * CB * 8 * MAX_SPLIT_B8 : nullptr;      // no workspace: bn8_finalize refuses
+    const int rc = bn8_finalize(x, gamma, beta, running_mean, running_var, num_batches_tracked, save_mean, save_invstd, coef,
+                                N, C, HW, momentum, eps, training, ext_stats, ext_nsplit, ext_pivot, ws, ws_bytes, st);
+    if (rc != 0 || N == 0) return rc;
     const int nc = pick_chunk(N, CB, HW);
     hipLaunchKernelGGL(bn8_apply_kernel, dim3(CB, nc), dim3(256), 0, st, (const bf16x8*)x, (const float*)coef, (bf16x8*)y,
                        N, CB, HW, nc, relu);
@@ -389,28 +357,8 @@ int jvae_bn_finalize_b8(const void* x, const float* gamma, const float* beta,
                         const float* ext_stats, int ext_nsplit, const float* ext_pivot,
                         void* ws, size_t ws_bytes, void* stream) {
     if (!x || !coef || N <= 0 || C <= 0 || HW <= 0) return JVAE_EINVAL;
-    if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int CB = (C + 7) / 8;
-    const float* partial = (const float*)ws;
-    int ns = 1;
-    const bool ext = training && ext_stats && ext_nsplit > 0;
-    if (training && (!save_mean || !save_invstd)) return JVAE_EINVAL;
-    if (ext) {
-        partial = ext_stats;
-        ns = ext_nsplit;
-    } else if (training) {
-        ns = pick_split(N, CB, HW);
-        hipLaunchKernelGGL(bn8_stats_kernel, dim3(CB, ns), dim3(256), 0, st, (const bf16x8*)x, (float*)ws, N, C, CB, HW, ns, (const float*)nullptr);
-        JVAE_LAUNCH_CHECK();
-    } else if (!running_mean || !running_var) {
-        return JVAE_EINVAL;
-    }
-    hipLaunchKernelGGL(bn8_finalize_kernel, dim3(CB * 8), dim3(64), 0, st, (const bf16x8*)x, partial, gamma, beta,
-                       running_mean, running_var, num_batches_tracked, save_mean, save_invstd, coef, N, C, CB * 8, HW, ns,
-                       momentum, eps, training, ext ? 1 : 0, ext_pivot);
-    JVAE_LAUNCH_CHECK();
-    return 0;
+    return bn8_finalize(x, gamma, beta, running_mean, running_var, num_batches_tracked, save_mean, save_invstd, coef,
+                        N, C, HW, momentum, eps, training, ext_stats, ext_nsplit, ext_pivot, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int jvae_bn_bwd_b8(const void* dy, const void* x, const float* gamma, const float* beta,
@@ -427,7 +375,7 @@ int jvae_bn_bwd_b8(const void* dy, const void* x, const float* gamma, const floa
     hipLaunchKernelGGL(bn8_bwd_reduce_kernel, dim3(CB, ns), dim3(256), 0, st, (const bf16x8*)dy, (const bf16x8*)x, gamma, beta,
                        save_mean, save_invstd, partial, N, C, CB, HW, ns, relu);
     JVAE_LAUNCH_CHECK();
-    float* coef = partial + (size_t)2 * CB * 8 * MAX_SPLIT;
+    float* coef = partial + (size_t)2 * CB * 8 * MAX_SPLIT_B8;
     hipLaunchKernelGGL(bn8_bwd_finalize_kernel, dim3(CB * 8), dim3(64), 0, st, (const float*)partial, coef, dgamma, dbeta,
                        accumulate, N, C, CB * 8, HW, ns);
     JVAE_LAUNCH_CHECK();
@@ -438,7 +386,6 @@ int jvae_bn_bwd_b8(const void* dy, const void* x, const float* gamma, const floa
     return 0;
 }
 
-// ReLU on B8 tensors of `units` 16-byte units (backward takes the forward OUTPUT)
 // ---- synchronised BatchNorm on B8 tensors (data-parallel ranks share the batch statistics) ----------------
 // Same protocol as the fp32 entry points (bn.hip): the host all-reduces the (C,2) sums between the two calls of each
 // direction.  Statistics fp32, activations bf16.
@@ -470,7 +417,7 @@ int jvae_bn_fwd_sync_b8(const void* x, const float* gamma, const float* beta,
     if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int CB = (C + 7) / 8;
-    float* coef = (float*)ws + (size_t)2 * CB * 8 * MAX_SPLIT;
+    float* coef = (float*)ws + (size_t)2 * CB * 8 * MAX_SPLIT_B8;
     // one "split" holding the global sums, N*world images behind them
     hipLaunchKernelGGL(bn8_finalize_kernel, dim3(CB * 8), dim3(64), 0, st, (const bf16x8*)x, global_sums, gamma, beta,
                        running_mean, running_var, num_batches_tracked, save_mean, save_invstd, coef, N * world, C, CB * 8, HW, 1,
@@ -512,7 +459,7 @@ int jvae_bn_bwd_sync_b8(const void* dy, const void* x, const float* gamma, const
     if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int CB = (C + 7) / 8;
-    float* coef = (float*)ws + (size_t)2 * CB * 8 * MAX_SPLIT;
+    float* coef = (float*)ws + (size_t)2 * CB * 8 * MAX_SPLIT_B8;
     hipLaunchKernelGGL(bn8_bwd_sync_coef_kernel, dim3(cdiv(CB * 8, 64)), dim3(64), 0, st, local_sums, global_sums, coef, dgamma, dbeta,
                        accumulate, (double)N * (double)HW * world, C, CB * 8);
     JVAE_LAUNCH_CHECK();
@@ -523,6 +470,7 @@ int jvae_bn_bwd_sync_b8(const void* dy, const void* x, const float* gamma, const
     return 0;
 }
 
+// ReLU on B8 tensors of `units` 16-byte units (backward takes the forward OUTPUT)
 int jvae_relu_fwd_b8(const void* x, void* y, long units, void* stream) {
     if (!x || !y || units < 0) return JVAE_EINVAL;
     if (units == 0) return 0;

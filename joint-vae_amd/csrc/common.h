@@ -184,8 +184,8 @@ __device__ __forceinline__ float jvae_act(float t, int kind) {
     return kind == JVAE_ACT_RELU ? fmaxf(t, 0.f) : (kind == JVAE_ACT_LEAKY ? fmaxf(t, JVAE_LEAKY_SLOPE * t) : t);
 }
 
-// a = [relu](v*s + t) on a float4 (deferred BatchNorm of a convolution input; the same fmaf as bn_coef / bn_apply_kernel,
-// so the ReLU mask BatchNorm-backward recomputes is the one applied here)
+// a = [relu](v*s + t) on a float4 (deferred BatchNorm of a convolution input; s, t are bn_coef's scale / shift (bn_core.h, its one
+// definition) and the fmaf is bn_apply_kernel's, so the ReLU mask BatchNorm-backward recomputes is the one applied here)
 __device__ __forceinline__ f32x4 aff4(f32x4 v, float s, float t, int relu) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) { const float x = fmaf(v[j], s, t); v[j] = relu ? fmaxf(x, 0.f) : x; }

@@ -347,6 +347,77 @@ def test_batchnorm_train(N, C, P, relu):
     assert rel(ye, act(yer)) < 1e-5
 
 
+@pytest.mark.parametrize('ext_nsplit', [1, 64, 200])
+@pytest.mark.parametrize('entry', ['jvae_bn_fwd_ext_f32', 'jvae_bn_finalize_f32', 'jvae_bn_finalize_b8'])
+def test_batchnorm_folds_external_partials(entry, ext_nsplit):
+    """The forward entry points on statistics handed over by a convolution: (C, ext_nsplit, 2) tile partials, up to 200 per
+    channel - more than one wave's worth, so every wave of the 256-thread folds (csrc/bn_core.h) carries non-zero sums.
+    The partials are the (sum, sum of squares) of random tile data whose tile sizes add up to N * P, so s2/n >= (s1/n)^2 holds
+    and the var < 0 clamp hides nothing.  Reference: the same formulas in fp64 (torch) from the fp32 partials.
+    Bound: one fp32 ulp, |a - b| <= 2^-23 |b|.  mean, invstd and the unbiased variance are computed in fp64 and rounded once
+    (<= 2^-24 relative); what the kernels then do in fp32 adds ONE more rounding of <= 2^-24 for the inputs chosen here:
+    scale = fl(gamma * invstd); the running statistics start at 0, so they are fl(momentum * mean) and
+    fl(momentum * unbiased) with momentum the fp32 value of 0.1; shift = fl(beta - mean * scale) with |beta| >= 30 while
+    |mean * scale| < 5, so |shift| > 4 |mean * scale| and the at most four roundings inside the product (mean, invstd, scale,
+    the product itself where it is not fused: 4 * 2^-24 |mean * scale|) stay below the one 2^-24 |shift| that is left beside
+    the final rounding.  (The blend with non-zero running statistics is fp32 arithmetic of more roundings;
+    test_batchnorm_train checks it.)"""
+    from jvae_hip import lib as L, ops_b8
+    N, C, P, eps = 25, 5, 56, 1e-5
+    n = N * P
+    g = torch.Generator().manual_seed(ext_nsplit)
+    tiles = torch.tensor_split(torch.randn(C, n, generator=g, dtype=torch.float64) * 1.5 + 0.3, ext_nsplit, dim=1)
+    assert sum(t.shape[1] for t in tiles) == n
+    partial = torch.stack([torch.stack([t.sum(1), (t * t).sum(1)], 1) for t in tiles], 1).float()      # (C, ext_nsplit, 2)
+    pivot = torch.randn(C, generator=g)
+    x = torch.randn(N, C, 7, 8, generator=g)
+    gamma = torch.rand(C, generator=g) + 0.5
+    beta = (30 + torch.rand(C, generator=g)) * torch.tensor([1., -1., 1., -1., -1.])
+    m32 = torch.tensor(0.1, dtype=torch.float32).double()
+    s = partial.double().sum(1)
+    dm = s[:, 0] / n
+    var = s[:, 1] / n - dm * dm
+    assert float(var.min()) > 1.
+    ref = {'mean': pivot.double() + dm, 'invstd': 1. / torch.sqrt(var + eps)}
+    ref['rm'], ref['rv'] = m32 * ref['mean'], m32 * (var * n / (n - 1.))
+    ref['scale'] = gamma.double() * ref['invstd']
+    ref['shift'] = beta.double() - ref['mean'] * ref['scale']
+    assert float((ref['mean'] * ref['scale']).abs().max()) < 5.
+
+    dev = torch.device(DEV)
+    gd, bd, pd, sd = (t.to(dev) for t in (gamma, beta, pivot, partial))
+    out = {k: torch.zeros(C, device=dev) for k in ('rm', 'rv', 'mean', 'invstd')}
+    nbt = torch.zeros((), dtype=torch.int64, device=dev)
+    lib = L.load()
+    b8 = entry.endswith('_b8')
+    nbytes = (lib.jvae_bn_workspace_bytes_b8 if b8 else lib.jvae_bn_workspace_bytes)(C)
+    ws = L.workspace(nbytes, dev)
+    xd = ops_b8.pack(x.to(dev)) if b8 else x.to(dev)
+    head = (L.ptr(xd), L.ptr(gd), L.ptr(bd), L.ptr(out['rm']), L.ptr(out['rv']), L.ptr(nbt))
+    tail = (L.ptr(sd), ext_nsplit, L.ptr(pd), L.ptr(ws), nbytes, L.stream_ptr())
+    if entry == 'jvae_bn_fwd_ext_f32':
+        y = torch.empty_like(xd)
+        rc = lib.jvae_bn_fwd_ext_f32(*head, L.ptr(y), L.ptr(out['mean']), L.ptr(out['invstd']), N, C, P, 0.1, eps, 1, 2, *tail)
+    elif b8:
+        coef = torch.full((2, 8), float('nan'), device=dev)
+        rc = lib.jvae_bn_finalize_b8(*head, L.ptr(out['mean']), L.ptr(out['invstd']), L.ptr(coef), N, C, P, 0.1, eps, 1, *tail)
+        out['scale'], out['shift'] = coef[0, :C], coef[1, :C]
+    else:
+        out['scale'], out['shift'] = torch.empty(C, device=dev), torch.empty(C, device=dev)
+        rc = lib.jvae_bn_finalize_f32(*head, L.ptr(out['mean']), L.ptr(out['invstd']), L.ptr(out['scale']), L.ptr(out['shift']),
+                                      N, C, P, 0.1, eps, 1, *tail)
+    L.check(rc, entry)
+    assert int(nbt) == 1
+    ulps = {k: float(((v.double().cpu() - ref[k]).abs() / ref[k].abs()).max()) * 2. ** 23 for k, v in out.items()}
+    print(f'{entry} ext_nsplit={ext_nsplit}: error in units of 2^-23 relative: {ulps}')
+    assert all(u <= 1. for u in ulps.values()), ulps
+    if b8:
+        assert bool((coef[:, C:] == 0).all())                      # padding channels
+    if entry == 'jvae_bn_fwd_ext_f32':
+        yr = F.leaky_relu(x.double().view(N, C, P) * ref['scale'][:, None] + ref['shift'][:, None])
+        assert rel(y.view(N, C, P), yr) < 1e-5
+
+
 @pytest.mark.parametrize('N,C,P', [(49, 32, 1024), (98, 64, 256), (5, 3, 1023)])
 def test_channel_sum_ragged_partitions(N, C, P):
     from jvae_hip import ops

@@ -615,6 +615,44 @@ int jvae_prior_sample_f32(const float* eps, const long long* y, const float* mea
 int jvae_image_grid_f32(const float* x_in, const float* x_out, const int* specs, const int* specs_host, int Ncol, float* grid_f32,
                         unsigned char* grid_u8, int N, int D, int H, int W, int Rr, void* stream);
 
+/* ---- Model ensembles: class posteriors of latent draws, pairwise latent mutual information, score aggregation
+ * (csrc/aggregate.hip; reference module/aggregation.py, module/cascad.py, results/aggregation.py:321-374) -------------
+ * None of the entry points allocates or synchronises; no atomics, one writer per output element, the order of every sum is
+ * fixed by the shape: the same bits run to run.  temps: a HOST array of nT <= 16 temperatures; a NaN entry is a temperature of
+ * the reference's NAN_TEMPS (None, -1, 0): its slot takes the logits unchanged.
+ * Class posteriors: z (R, K) rows (the draws z[1:] of a model, R = L N), means (C, K), T the whitening factor in the layout
+ * of GaussianPrior._var_parameter (var_dim 0 scalar (C,), 1 diag (C, K), 2 full (C, K, K): only the lower triangle is read),
+ * log_det (C,) = log|Sigma_c| ->
+ *   logp (C, R)      = (-(K / 2) log 2 pi - u / 2) - log_det[c] / 2,  u = |T_c (z_r - m_c)|^2 as jvae_latent_fwd_f32's zdist
+ *   P    (nT, C, R)  = softmax_c(logp / temps[t]), max-shifted
+ * (either may be NULL, not both; P needs nT >= 1).  Each row of z is read once whatever C and nT.  The quadratic form, logp and
+ * the soft-max are taken in fp64 and rounded once: P is the soft-max of the unrounded logp.
+ * 1 <= K <= 1024, 1 <= C <= 128, 0 <= R <= 2^30, else -1 (JVAE_EINVAL).
+ * Latent mutual information: P0 (nT, C, L0, N), P1 (nT, C, L1, N) ->
+ *   Im (nT, N),  Im[t, n] = 1 / (L0 L1) sum_{a < L0, b < L1} log sum_c P0[t, c, a, n] P1[t, c, b, n]
+ * the class sum in fp32 (ascending c, fused multiply-adds), the logs added in fp64 in a fixed order, one division.  A draw
+ * pair whose class sum is exactly 0 gives -inf, and so does its sample.  ws: device scratch of at least
+ * jvae_latent_mi_workspace_bytes(nT, L0, N) bytes, 8-byte aligned (-3, JVAE_EWORKSPACE, when smaller).
+ * 1 <= nT <= 16, 1 <= C <= 128, 1 <= L0, L1, else -1.
+ * Score aggregation: srcs / factors HOST arrays of E <= 8 entries - srcs[e] a (C, N) fp32 device tensor x_e (mode 3: an (N,)
+ * int64 tensor of predicted classes), factors[e] its factor f_e:
+ *   0  MEAN       a = m + log((sum_e exp(f x_e - m)) / E), m = max_e f x_e       (log_mean_exp; iws, f = 1)
+ *   1  JOINT      a = f_0 sum_e x_e, ascending e                                  (joint_posterior; zdist, f = -1/2)
+ *   2  MEAN_SOFT  post[t] = (sum_e softmax_c(f x_e / T_t)) / E; NaN T_t: (sum_e f x_e) / E     (`mean~`; kl, f = -1; no a)
+ *   3  VOTE       a = count_c / E; post[t] = a for every t
+ * post (nT, C, N): softmax_c(a / T_t), or a for a NaN T_t; a (C, N); amax (N,) fp32 / argmax (N,) int64: maximum over c and
+ * its lowest index of slot `slot` of post (-1: of a), a NaN kept.  Every output may be NULL, not all.  A vote outside [0, C)
+ * is never used as an index: its sample is NaN in a / post and *status (device int32, owned and cleared by the caller; needed
+ * in mode 3) is set to 1 (bit 0), as for jvae_wim_scores_f32.
+ * 1 <= E <= 8, 1 <= C <= 128, 0 <= nT <= 16, -1 <= slot < nT, an unknown mode, a or slot -1 in mode 2: -1. */
+int jvae_class_posterior_f32(const float* z, const float* means, const float* T, const float* log_det, const float* temps, int nT,
+                             float* logp, float* P, long R, int K, int C, int var_dim, void* stream);
+size_t jvae_latent_mi_workspace_bytes(int nT, int L0, long N);
+int jvae_latent_mi_f32(const float* P0, const float* P1, float* Im, int nT, int C, int L0, int L1, long N, void* ws, size_t ws_bytes,
+                       void* stream);
+int jvae_aggregate_scores_f32(const void* const* srcs, const float* factors, int E, int mode, const float* temps, int nT, float* post,
+                              float* a, float* amax, long long* argmax, int slot, int C, long N, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,10 @@ _SIGS = {
     'jvae_group_tally_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
     'jvae_prior_sample_f32': (c_int, [P] * 6 + [c_long, c_int, c_int, c_float, c_int, P]),
     'jvae_image_grid_f32': (c_int, [P, P, P, P, c_int, P, P] + [c_int] * 5 + [P]),
+    'jvae_class_posterior_f32': (c_int, [P] * 5 + [c_int, P, P, c_long, c_int, c_int, c_int, P]),
+    'jvae_latent_mi_workspace_bytes': (c_size_t, [c_int, c_int, c_long]),
+    'jvae_latent_mi_f32': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_long, P, c_size_t, P]),
+    'jvae_aggregate_scores_f32': (c_int, [P, P, c_int, c_int, P, c_int, P, P, P, P, c_int, c_int, c_long, P, P]),
 }
 
 

@@ -1432,9 +1432,9 @@ def wim_scores(sources, y_est, specs, out=None, rows=None, col=0, status=None):
 
 
 def wim_check_status(status=None):
-    """Raise JvaeHipError when a `wim_scores` launch met an estimated label outside [0, C).  status: the word given to
-    `wim_scores` (a device tensor: read here - this is the synchronisation - and cleared), a host value, or None for the
-    per-device default words."""
+    """Raise JvaeHipError when a launch that takes a status word (`wim_scores`, `prior_sample`, `aggregate_scores` on votes) met
+    a label outside [0, C).  status: the word given to the op (a device tensor: read here - this is the synchronisation - and
+    cleared), a host value, or None for the per-device default words."""
     if status is None:
         words = list(_wim_status.values())
     else:
@@ -1444,7 +1444,8 @@ def wim_check_status(status=None):
         if torch.is_tensor(w) and v:
             w.zero_()
         if v & 1:
-            raise L.JvaeHipError('wim_scores: an estimated label outside [0, C) was met (its score rows are NaN)')
+            raise L.JvaeHipError('a label outside [0, C) was met by wim_scores, prior_sample or aggregate_scores (the rows of '
+                                 'that sample are NaN)')
 
 
 def group_tally(values, group, sums, counts):
@@ -1555,6 +1556,154 @@ def image_grid(x_in, x_out, columns, f32=True, u8=True):
     L.check(L.load().jvae_image_grid_f32(L.ptr(x_in), L.ptr(x_out), L.ptr(_c(specs)), host, Ncol, L.ptr(gf), L.ptr(gu), N, D, H, W,
                                          Rr, L.stream_ptr()), 'jvae_image_grid_f32')
     return gf, gu
+
+
+# ------------------------------------------------------------------------- model ensembles (csrc/aggregate.hip)
+AGG_MODES = {'mean': 0, 'joint': 1, 'mean_soft': 2, 'vote': 3}
+AGG_MAX_SOURCES = 8
+AGG_MAX_TEMPS = 16
+AGG_MAX_K = 1024
+AGG_NAN_TEMPS = (None, -1, 0)          # the reference's NAN_TEMPS: such a temperature passes the logits through
+
+
+def _temps_array(temps, what, least=0):
+    """Temperatures -> the host float array the entry points take (NaN for a temperature of AGG_NAN_TEMPS)."""
+    temps = list(temps)
+    if not least <= len(temps) <= AGG_MAX_TEMPS:
+        raise L.JvaeHipError(f'{what}: {least} .. {AGG_MAX_TEMPS} temperatures expected, got {len(temps)}')
+    vals = [float('nan') if any(t is n or (t is not None and n is not None and t == n) for n in AGG_NAN_TEMPS) else float(t)
+            for t in temps]
+    return (ctypes.c_float * max(len(vals), 1))(*vals)
+
+
+def class_posterior(z, means, T, log_det, var_dim='scalar', temps=(1,), logp=True, post=True):
+    """log p(z | c) of latent draws for EVERY class of a conditional Gaussian prior, and its soft-max over the classes, in ONE
+    launch: z (..., K) fp32 (each row is read once), means (C, K), T the whitening factor ((C,), (C, K) or (C, K, K) by
+    var_dim, the layout of GaussianPrior._var_parameter), log_det (C,) = log|Sigma_c| (GaussianPrior.log_det_per_class()) ->
+    (logp (C, ...) or None, P (nT, C, ...) or None): logp = (-(K / 2) log 2 pi - u / 2) - log_det[c] / 2 with u the quadratic
+    form of GaussianPrior.mahala, P[t] = softmax_c(logp / temps[t]) (a temperature of AGG_NAN_TEMPS: logp itself).  No tensor of
+    C * rows * K elements is made.  C <= MISCLASS_MAX_CLASSES, K <= AGG_MAX_K.  Nothing is synchronised."""
+    if var_dim not in VAR_KIND:
+        raise L.JvaeHipError(f'class_posterior: var_dim {var_dim!r} unknown (one of {sorted(VAR_KIND)})')
+    z, means = _c(_f32(z, 'class_posterior')), _c(_f32(means, 'class_posterior'))
+    T, log_det = _c(_f32(T, 'class_posterior')), _c(_f32(log_det, 'class_posterior'))
+    L.ptr(z)
+    dev = z.device
+    if means.dim() != 2 or z.dim() < 1 or z.shape[-1] != means.shape[1]:
+        raise L.JvaeHipError(f'class_posterior: z (..., K) and means (C, K) expected, got {tuple(z.shape)}, {tuple(means.shape)}')
+    C, K = means.shape
+    want = {'scalar': (C,), 'diag': (C, K), 'full': (C, K, K)}[var_dim]
+    if tuple(T.shape) != want or tuple(log_det.shape) != (C,) or any(t.device != dev for t in (means, T, log_det)):
+        raise L.JvaeHipError(f'class_posterior: a {want} factor and ({C},) log-determinants on {dev} expected for var_dim '
+                             f'{var_dim!r}, got {tuple(T.shape)}, {tuple(log_det.shape)}')
+    if not 1 <= C <= MISCLASS_MAX_CLASSES or not 1 <= K <= AGG_MAX_K:
+        raise L.JvaeHipError(f'class_posterior: 1 <= C <= {MISCLASS_MAX_CLASSES} and 1 <= K <= {AGG_MAX_K} expected, got C = {C}, '
+                             f'K = {K}')
+    if not (logp or post):
+        raise L.JvaeHipError('class_posterior: nothing to write')
+    tarr = _temps_array(temps if post else (), 'class_posterior', 1 if post else 0)
+    nT = len(list(temps)) if post else 0
+    lead = tuple(z.shape[:-1])
+    R = z.numel() // K
+    lp = torch.empty((C,) + lead, dtype=torch.float32, device=dev) if logp else None
+    P = torch.empty((nT, C) + lead, dtype=torch.float32, device=dev) if post else None
+    L.check(L.load().jvae_class_posterior_f32(L.ptr(z), L.ptr(means), L.ptr(T), L.ptr(log_det), tarr, nT, L.ptr(lp), L.ptr(P), R, K,
+                                              C, VAR_KIND[var_dim], L.stream_ptr()), 'jvae_class_posterior_f32')
+    return lp, P
+
+
+def latent_mutual_info(P0, P1):
+    """Pairwise latent mutual information of two models' class posteriors: P0 (nT, C, L0, N), P1 (nT, C, L1, N) fp32 ->
+    Im (nT, N), Im[t, n] = 1 / (L0 L1) sum_{a, b} log sum_c P0[t, c, a, n] P1[t, c, b, n] (reference
+    module/aggregation.py::compute_latent_mutual_info without its (C, L1, L0, N) tensors).  The logs are added in fp64 in a
+    fixed order; a pair of draws with no class in common (class sum exactly 0) makes its sample -inf.  The only allocation
+    beside Im is nT * ceil(L0 / 4) * N fp64 partial sums.  Nothing is synchronised."""
+    P0, P1 = _c(_f32(P0, 'latent_mutual_info')), _c(_f32(P1, 'latent_mutual_info'))
+    L.ptr(P0)
+    L.ptr(P1)
+    if P0.dim() != 4 or P1.dim() != 4 or P0.shape[:2] != P1.shape[:2] or P0.shape[3] != P1.shape[3] or P0.device != P1.device:
+        raise L.JvaeHipError(f'latent_mutual_info: (nT, C, L0, N) and (nT, C, L1, N) on one device expected, got '
+                             f'{tuple(P0.shape)}, {tuple(P1.shape)}')
+    nT, C, L0, N = P0.shape
+    L1 = P1.shape[2]
+    if not 1 <= nT <= AGG_MAX_TEMPS or not 1 <= C <= MISCLASS_MAX_CLASSES or L0 < 1 or L1 < 1:
+        raise L.JvaeHipError(f'latent_mutual_info: 1 <= nT <= {AGG_MAX_TEMPS}, 1 <= C <= {MISCLASS_MAX_CLASSES} and at least one '
+                             f'draw per model expected, got {tuple(P0.shape)}, {tuple(P1.shape)}')
+    lib = L.load()
+    Im = torch.empty((nT, N), dtype=torch.float32, device=P0.device)
+    nbytes = lib.jvae_latent_mi_workspace_bytes(nT, L0, N)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=P0.device)
+    L.check(lib.jvae_latent_mi_f32(L.ptr(P0), L.ptr(P1), L.ptr(Im), nT, C, L0, L1, N, L.ptr(ws), ws.numel() * 8, L.stream_ptr()),
+            'jvae_latent_mi_f32')
+    return Im
+
+
+def aggregate_scores(sources, mode, factors=None, temps=(), post=True, a=False, amax=False, argmax=False, slot=None,
+                     num_classes=None, status=None):
+    """The ensemble rows of several models' recorded scores in ONE launch (reference results/aggregation.py:321-374).
+    sources: 1 .. 8 (C, N) fp32 tensors x_e - for mode 'vote' (N,) int64 predicted classes and `num_classes` = C;
+    factors: one float per source (or one for all; default 1).  mode, with a the (C, N) aggregated row:
+    'mean': a = log_mean_exp_e(f x_e) | 'joint': a = f sum_e x_e (ascending e) | 'mean_soft': no a, post[t] = mean_e
+    softmax_c(f x_e / T_t) ((sum_e f x_e) / E for a temperature of AGG_NAN_TEMPS) | 'vote': a = count_c / E.
+    -> (post, a, amax, argmax), None where not asked for: post (nT, C, N) = softmax_c(a / T_t), a itself for a temperature of
+    AGG_NAN_TEMPS and for votes; amax (N,) fp32 and argmax (N,) int64 of slot `slot` of post (None: of a) - equal maxima give
+    the lowest class, a NaN is kept.  status as for `wim_scores`: bit 0 is set when a vote is outside [0, C) (that sample is
+    NaN); default `wim_status(device)`, read and raised on by `wim_check_status`.  Nothing is synchronised."""
+    if mode not in AGG_MODES:
+        raise L.JvaeHipError(f'aggregate_scores: mode {mode!r} unknown (one of {sorted(AGG_MODES)})')
+    sources = list(sources)
+    E = len(sources)
+    if not 1 <= E <= AGG_MAX_SOURCES:
+        raise L.JvaeHipError(f'aggregate_scores: 1 .. {AGG_MAX_SOURCES} sources expected, got {E}')
+    vote = mode == 'vote'
+    for s in sources:
+        if not s.is_cuda:
+            L.ptr(s)                   # raises: no CPU fallback
+    dev = sources[0].device
+    if vote:
+        if num_classes is None:
+            raise L.JvaeHipError('aggregate_scores: votes need num_classes')
+        if any(s.dtype != torch.int64 or s.dim() != 1 or s.shape != sources[0].shape or s.device != dev for s in sources):
+            raise L.JvaeHipError(f'aggregate_scores: (N,) int64 votes of one length on {dev} expected, got '
+                                 f'{[(tuple(s.shape), s.dtype) for s in sources]}')
+        C, N = int(num_classes), sources[0].shape[0]
+    else:
+        if any(s.dim() != 2 or s.shape != sources[0].shape or s.device != dev for s in sources):
+            raise L.JvaeHipError(f'aggregate_scores: (C, N) sources of one shape on {dev} expected, got '
+                                 f'{[tuple(s.shape) for s in sources]}')
+        sources = [_f32(s, 'aggregate_scores') for s in sources]
+        C, N = sources[0].shape
+    sources = [_c(s) for s in sources]
+    if not 1 <= C <= MISCLASS_MAX_CLASSES:
+        raise L.JvaeHipError(f'aggregate_scores: 1 <= C <= {MISCLASS_MAX_CLASSES} expected, got {C}')
+    if factors is None:
+        factors = [1.] * E
+    elif not isinstance(factors, (list, tuple)):
+        factors = [float(factors)] * E
+    if len(factors) != E or (mode == 'joint' and any(float(f) != float(factors[0]) for f in factors)):
+        raise L.JvaeHipError(f'aggregate_scores: {E} factors expected (one value for mode joint), got {factors!r}')
+    temps = list(temps)
+    tarr = _temps_array(temps, 'aggregate_scores', 1 if post else 0)
+    nT = len(temps)
+    if slot is None:
+        slot = -1
+    if not -1 <= int(slot) < nT or not (post or a or amax or argmax) or (mode == 'mean_soft' and (a or ((amax or argmax) and slot < 0))):
+        raise L.JvaeHipError(f'aggregate_scores: nothing to write, slot {slot} outside the {nT} temperatures, or the aggregated '
+                             'row of mode mean_soft (it has none) asked for')
+    if status is None:
+        status = wim_status(dev)
+    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise L.JvaeHipError('aggregate_scores: an int32 status word on the device of the sources expected')
+    o_post = torch.empty((nT, C, N), dtype=torch.float32, device=dev) if post else None
+    o_a = torch.empty((C, N), dtype=torch.float32, device=dev) if a else None
+    o_max = torch.empty((N,), dtype=torch.float32, device=dev) if amax else None
+    o_arg = torch.empty((N,), dtype=torch.int64, device=dev) if argmax else None
+    src_p = (ctypes.c_void_p * E)(*[s.data_ptr() for s in sources])
+    fac = (ctypes.c_float * E)(*[float(f) for f in factors])
+    L.check(L.load().jvae_aggregate_scores_f32(src_p, fac, E, AGG_MODES[mode], tarr, nT, L.ptr(o_post), L.ptr(o_a), L.ptr(o_max),
+                                               L.ptr(o_arg), int(slot), C, N, L.ptr(status), L.stream_ptr()),
+            'jvae_aggregate_scores_f32')
+    return o_post, o_a, o_max, o_arg
 
 
 def misclass_split(scores, mask):

@@ -653,6 +653,28 @@ int jvae_latent_mi_f32(const float* P0, const float* P1, float* Im, int nT, int 
 int jvae_aggregate_scores_f32(const void* const* srcs, const float* factors, int E, int mode, const float* temps, int nT, float* post,
                               float* a, float* amax, long long* argmax, int slot, int C, long N, int* status, void* stream);
 
+/* ---- Chained models: stage-pair mean squared errors, sequential Bayesian update (csrc/cascad.hip; reference
+ * module/cascad.py) ----------------------------------------------------------------------------------------------------
+ * Neither entry point allocates or synchronises; no atomics, the order of every sum is fixed by the shape: the same bits run
+ * to run.
+ * Stage-pair MSE: x (N, D) fp32 is stage 0, stages a HOST array of M device pointers R_1 .. R_M, each (L, N, D) fp32 and
+ * contiguous (any 4-byte aligned base: the views x_reco[1:] are taken as they are) ->
+ *   mse (M (M + 1) / 2, N),  row p = i (i - 1) / 2 + j for 1 <= i <= M, 0 <= j < i (the reference's `for i: for j < i`):
+ *   mse[p, n] = 1 / (L D) sum_{l, d} (R_i[l, n, d] - R_j[l, n, d])^2,  R_0[l] = x
+ * in ONE pass: every stage element is loaded once, x once per (n, d); differences, squares and sums in fp64, one division,
+ * one rounding.  16-byte loads where D % 4 == 0 and every base is 16-byte aligned, 4-byte loads otherwise - the same bits
+ * either way.  ws: device scratch of at least jvae_cascade_mse_workspace_bytes(M, N, D) bytes, 8-byte aligned (-3,
+ * JVAE_EWORKSPACE, when smaller).  1 <= M <= 8, 1 <= L, 0 <= N, 1 <= D <= 65535 * 256, N * ceil(D / 256) < 2^24 (the threads of
+ * the launch stay below 2^32), else -1 (JVAE_EINVAL).
+ * Sequential update: p (M, C, N) -> posterior (M, C, N) (another buffer than p), per sample
+ *   prior_0 = 1 / C;  posterior[i] = p[i] prior / sum_c p[i] prior;  prior = posterior[i]
+ * products and class sums in fp64, ascending c.  A stage whose class sum is 0 makes that sample NaN from that stage on.
+ * 1 <= M <= 8, 1 <= C <= 128, 0 <= N <= 2^30, else -1. */
+size_t jvae_cascade_mse_workspace_bytes(int M, long N, long D);
+int jvae_cascade_mse_f32(const float* x, const void* const* stages, int M, float* mse, int L, long N, long D, void* ws,
+                         size_t ws_bytes, void* stream);
+int jvae_iterate_prior_f32(const float* p, float* posterior, int M, int C, long N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,9 @@ _SIGS = {
     'jvae_latent_mi_workspace_bytes': (c_size_t, [c_int, c_int, c_long]),
     'jvae_latent_mi_f32': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_long, P, c_size_t, P]),
     'jvae_aggregate_scores_f32': (c_int, [P, P, c_int, c_int, P, c_int, P, P, P, P, c_int, c_int, c_long, P, P]),
+    'jvae_cascade_mse_workspace_bytes': (c_size_t, [c_int, c_long, c_long]),
+    'jvae_cascade_mse_f32': (c_int, [P, P, c_int, P, c_int, c_long, c_long, P, c_size_t, P]),
+    'jvae_iterate_prior_f32': (c_int, [P, P, c_int, c_int, c_long, P]),
 }
 
 

@@ -1706,6 +1706,63 @@ def aggregate_scores(sources, mode, factors=None, temps=(), post=True, a=False, 
     return o_post, o_a, o_max, o_arg
 
 
+# ------------------------------------------------------------------------- chained models (csrc/cascad.hip)
+CASCADE_MAX_MODELS = 8
+
+
+def cascade_mse(x, stages):
+    """The mean squared errors of EVERY pair of stages of a cascade in ONE pass (reference module/cascad.py::evaluate, which
+    forms them pair by pair): x (N, ...) fp32 is stage 0, stages 1 .. 8 tensors R_1 .. R_M of one shape (L, N, ...) - the sampled
+    reconstructions x_reco[1:] of the models, taken as the views they are: contiguous, any 4-byte aligned base, never copied ->
+    mse (M (M + 1) / 2, N), row p = i (i - 1) / 2 + j for 1 <= i <= M, 0 <= j < i (`for i: for j < i`):
+    mse[p, n] = mean over l and the image axes of (R_i[l, n] - R_j[l, n])^2, R_0[l] = x.  Every stage element is loaded once;
+    differences, squares and sums in fp64 in an order (L, D) fixes.  The only allocation beside mse is
+    ceil(D / 256) * M (M + 1) / 2 * N fp64 partial sums.  Nothing is synchronised."""
+    stages = list(stages)
+    M = len(stages)
+    if not 1 <= M <= CASCADE_MAX_MODELS:
+        raise L.JvaeHipError(f'cascade_mse: 1 .. {CASCADE_MAX_MODELS} stages expected, got {M}')
+    for t in [x] + stages:
+        _f32(t, 'cascade_mse')
+        L.ptr(t)                       # raises on a CPU or a strided tensor: no CPU fallback, no hidden copy
+    if x.dim() < 1 or any(s.dim() != x.dim() + 1 or s.shape != stages[0].shape or s.device != x.device for s in stages) \
+            or tuple(stages[0].shape[1:]) != tuple(x.shape):
+        raise L.JvaeHipError(f'cascade_mse: x (N, ...) and stages of one shape (L, N, ...) on one device expected, got '
+                             f'{tuple(x.shape)} and {[tuple(s.shape) for s in stages]}')
+    Ls, N = stages[0].shape[0], x.shape[0]
+    D = math.prod(x.shape[1:])
+    if Ls < 1 or D < 1:
+        raise L.JvaeHipError(f'cascade_mse: at least one draw and one element per sample expected, got {tuple(stages[0].shape)}')
+    lib = L.load()
+    mse = torch.empty((M * (M + 1) // 2, N), dtype=torch.float32, device=x.device)
+    if N == 0:                         # an empty batch has no storage to point at
+        return mse
+    nbytes = lib.jvae_cascade_mse_workspace_bytes(M, N, D)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=x.device)
+    src_p = (ctypes.c_void_p * M)(*[s.data_ptr() for s in stages])
+    L.check(lib.jvae_cascade_mse_f32(L.ptr(x), src_p, M, L.ptr(mse), Ls, N, D, L.ptr(ws), ws.numel() * 8, L.stream_ptr()),
+            'jvae_cascade_mse_f32')
+    return mse
+
+
+def iterate_prior(p):
+    """The sequential Bayesian update of module/cascad.py::iterate_with_prior in one launch: p (M, C, N) fp32, the class
+    likelihoods of M <= 8 chained models -> posterior (M, C, N): prior_0 = 1 / C, posterior[i] = p[i] prior / sum_c p[i] prior,
+    prior = posterior[i].  A stage whose class sum is 0 makes that sample NaN from that stage on (0 / 0, as in the reference).
+    C <= MISCLASS_MAX_CLASSES.  Nothing is synchronised."""
+    p = _c(_f32(p, 'iterate_prior'))
+    L.ptr(p)
+    if p.dim() != 3:
+        raise L.JvaeHipError(f'iterate_prior: (M, C, N) expected, got {tuple(p.shape)}')
+    M, C, N = p.shape
+    if not 1 <= M <= CASCADE_MAX_MODELS or not 1 <= C <= MISCLASS_MAX_CLASSES:
+        raise L.JvaeHipError(f'iterate_prior: 1 <= M <= {CASCADE_MAX_MODELS} and 1 <= C <= {MISCLASS_MAX_CLASSES} expected, got '
+                             f'M = {M}, C = {C}')
+    post = torch.empty_like(p)
+    L.check(L.load().jvae_iterate_prior_f32(L.ptr(p), L.ptr(post), M, C, N, L.stream_ptr()), 'jvae_iterate_prior_f32')
+    return post
+
+
 def misclass_split(scores, mask):
     """(M, N) fp32 score rows and an (N,) mask (non-zero / True = correctly classified) -> ins (M, n_correct), outs
     (M, N - n_correct), n_correct: both row sets compacted in their original order by ONE scan of the mask (two views of one

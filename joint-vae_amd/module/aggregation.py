@@ -29,8 +29,8 @@ Deliberate differences:
     NotImplementedError by name (their log_density stays on the existing path).
   * At most 128 classes, 8 models and 16 temperatures per call (the kernels' limits): beyond them JvaeHipError.
 
-Not rebuilt, they stay in the reference: the command-line block of module/aggregation.py, module/cascad.py (CascadModels)
-and the command-line, pandas and TeX parts of results/aggregation.py - host-side bookkeeping around these functions.
+Not rebuilt, they stay in the reference: the command-line block of module/aggregation.py and the command-line, pandas and
+TeX parts of results/aggregation.py - host-side bookkeeping around these functions.
 """
 import torch
 

@@ -25,7 +25,7 @@
 //      MEAN_SOFT  post[t] = (sum_e softmax_c(f x_e / T_t)) / E; NaN temperature: (sum_e f x_e) / E     `mean~`, on kl with f = -1
 //      VOTE       the sources are (N,) int64 predictions, a = count_c / E
 //    post[t] = softmax_c(a / T_t), a itself for a NaN temperature (VOTE: a for every t); amax / argmax of one slot (-1: a),
-//    equal maxima to the lowest class, a NaN kept (wim_max).  The soft-max slots are written as x = a / T first and rewritten
+//    equal maxima to the lowest class, a NaN kept (nan_max).  The soft-max slots are written as x = a / T first and rewritten
 //    in place by the thread that wrote them.  A vote outside [0, C) is never used as an index: the sample's row is NaN and the
 //    status word is set to 1.
 // No atomics anywhere: one writer per output element, every sum in an order the shape fixes - the same bits run to run.
@@ -53,15 +53,6 @@ struct Temps { float v[AG_MAX_T]; int n; };       // by value in the kernel argu
 
 // torch.max keeps a NaN; the FIRST NaN / maximum wins (torch.argmax)
 __device__ __forceinline__ bool ag_better(float x, float best) { return best == best && (x > best || x != x); }
-
-struct Kahan {
-    float s = 0.f, c = 0.f;
-    __device__ __forceinline__ void add(float x) {
-        const float y = x - c, t = s + y;
-        c = (t - s) - y;
-        s = t;
-    }
-};
 
 // ------------------------------------------------------------------------------------------------- 1. class posteriors
 // fp64 throughout: the fp32 operands are exact in it, so logp carries one rounding (its own, on the way out) and P none of logp's

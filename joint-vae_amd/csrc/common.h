@@ -149,6 +149,19 @@ __device__ __forceinline__ float half_wave_reduce32(const float (&v)[32]) {
     return row_reduce16(a);
 }
 
+// torch.max keeps a NaN (fmaxf would drop it)
+__device__ __forceinline__ float nan_max(float best, float x) { return (x > best || x != x) ? x : best; }
+
+// Kahan sum: the score rows add up to 128 terms per lane in sequence and are held to the error of torch's tree sums
+struct Kahan {
+    float s = 0.f, c = 0.f;
+    __device__ __forceinline__ void add(float x) {
+        const float y = x - c, t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

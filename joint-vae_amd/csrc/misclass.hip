@@ -34,19 +34,6 @@ constexpr int MISC_SCAN = 1024;        // samples per block of the mask scan
 constexpr int MISC_CONF_PER = 8;       // samples per thread of the confusion kernel
 constexpr long MISC_MAX_N = 1L << 24;  // as jvae_roc_curve_f32: counts stay in int32
 
-// torch.max keeps a NaN (fmaxf would drop it)
-__device__ __forceinline__ float misc_max(float best, float x) { return (x > best || x != x) ? x : best; }
-
-// Kahan sum: the class-axis rows below add up to 128 terms per lane in sequence and are held to the error of torch's tree sums
-struct MiscSum {
-    float s = 0.f, c = 0.f;
-    __device__ __forceinline__ void add(float x) {
-        const float y = x - c, t = s + y;
-        c = (t - s) - y;
-        s = t;
-    }
-};
-
 // kinds 5 .. 13 of one sample: col[c * MISC_TILE] = v_c, l = -v (lse+: l = v), d = l - lmax, e = exp d.  The order of operations
 // is the reference's (cvae.py:985-1068); `add` is the constant of the lse rows.  An unknown kind gives NaN.
 __device__ float misc_axis_row(const float* col, int C, int kind, float add) {
@@ -55,7 +42,7 @@ __device__ float misc_axis_row(const float* col, int C, int kind, float add) {
     const float sign = kind == 6 ? 1.f : -1.f;
     const float n = (float)C;
     float lmax = -INFINITY;
-    for (int c = 0; c < C; ++c) lmax = misc_max(lmax, sign * col[c * MISC_TILE]);
+    for (int c = 0; c < C; ++c) lmax = nan_max(lmax, sign * col[c * MISC_TILE]);
     if (kind == 10) {                  // lmax - the lower middle element, found by its rank; a NaN is in lmax already
         const int k = (C - 1) / 2;
         float med = lmax;
@@ -72,7 +59,7 @@ __device__ float misc_axis_row(const float* col, int C, int kind, float add) {
         return lmax - med;
     }
     if (kind == 8) {                   // torch.std (ddof = 1) of l - lmax, which is that of l: two passes, 0 / 0 = NaN for C = 1
-        MiscSum m, q;                  // l - lmax as hi + lo, exactly (TwoSum): at an ELBO's spread its rounding would be the error
+        Kahan m, q;                  // l - lmax as hi + lo, exactly (TwoSum): at an ELBO's spread its rounding would be the error
         float lo_sum = 0.f;
         for (int c = 0; c < C; ++c) {
             const float l = -col[c * MISC_TILE], hi = l - lmax, b = hi - l;
@@ -88,13 +75,13 @@ __device__ float misc_axis_row(const float* col, int C, int kind, float add) {
         return sqrtf(q.s / (float)(C - 1));
     }
     if (kind < 5 || kind > 11) return NAN;
-    MiscSum e;
+    Kahan e;
     for (int c = 0; c < C; ++c) e.add(expf(sign * col[c * MISC_TILE] - lmax));
     if (kind == 5 || kind == 6) return logf(e.s) + lmax + add;
     const float mean = e.s / n;
     if (kind == 7) return logf(mean) + lmax;
     if (kind == 9) {
-        MiscSum q;
+        Kahan q;
         for (int c = 0; c < C; ++c) {
             const float t = expf(-col[c * MISC_TILE] - lmax) - mean;
             q.add(t * t);
@@ -103,7 +90,7 @@ __device__ float misc_axis_row(const float* col, int C, int kind, float add) {
         return r * r;
     }
     const float m = logf(mean);        // kind 11
-    MiscSum w;
+    Kahan w;
     for (int c = 0; c < C; ++c) {
         const float d = -col[c * MISC_TILE] - lmax;
         w.add(d * expf(d));
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(MISC_TILE) void misclass_scores_kernel(const float*
             float best = -INFINITY;
             for (int c = 0; c < C; ++c) {
                 const float v = s[c * MISC_TILE + lane];
-                best = misc_max(best, kind == 2 ? -v : v);
+                best = nan_max(best, kind == 2 ? -v : v);
             }
             res = best;
         } else {
@@ -138,7 +125,7 @@ __global__ __launch_bounds__(MISC_TILE) void misclass_scores_kernel(const float*
             float best = -INFINITY;
             for (int c = 0; c < C; ++c) {
                 const float v = s[c * MISC_TILE + lane];
-                best = misc_max(best, (neg ? -v : v) / T);
+                best = nan_max(best, (neg ? -v : v) / T);
             }
             float sum = 0.f;
             for (int c = 0; c < C; ++c) {

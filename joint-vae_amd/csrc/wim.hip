@@ -34,9 +34,6 @@ struct WimArgs {                       // by value in the kernel arguments: noth
     int R;
 };
 
-// torch.max keeps a NaN (fmaxf would drop it)
-__device__ __forceinline__ float wim_max(float best, float x) { return (x > best || x != x) ? x : best; }
-
 __global__ __launch_bounds__(WIM_BLOCK) void wim_scores_kernel(WimArgs a, const long long* __restrict__ y_est,
                                                                float* __restrict__ out, int* __restrict__ status, int C, long N,
                                                                long out_stride) {
@@ -61,7 +58,7 @@ __global__ __launch_bounds__(WIM_BLOCK) void wim_scores_kernel(WimArgs a, const 
     float top = -INFINITY, sum = 0.f;
     if (walk) {
 #pragma unroll 4
-        for (int c = 0; c < C; ++c) top = wim_max(top, f * src[(size_t)c * N + n]);
+        for (int c = 0; c < C; ++c) top = nan_max(top, f * src[(size_t)c * N + n]);
         float comp = 0.f;              // Kahan
 #pragma unroll 4
         for (int c = 0; c < C; ++c) {

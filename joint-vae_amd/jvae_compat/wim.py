@@ -79,9 +79,6 @@ class WIMJob(ClassificationVariationalNetwork):
     WIM_FUSED_STEP = True
     last_finetune_route = None          # 'fused' / 'two_pass': what the last finetune_step() ran
 
-    # the factor of each score family on its loss (ft/wim.py:145); `elbo` is -total
-    WIM_FACTORS = {'kl': -1., 'zdist': -0.5, 'iws': 1., 'elbo': 1.}
-
     def __init__(self, *a, alternate_prior=None, **kw):
         super().__init__(*a, **kw)
         self.update_loss_components()
@@ -247,93 +244,14 @@ class WIMJob(ClassificationVariationalNetwork):
         return o
 
     # ------------------------------------------------------------------------------------ scores
-    @classmethod
-    def _wim_row(cls, m):
-        """Method name -> (family, kind of ops.wim_scores): 'zdist~' -> ('zdist', 'Y'), 'softkl~' -> ('kl', 'SOFT_Y'),
-        'elbo@' -> ('elbo', 'LSE_AT'), 'iws~@' -> ('iws', 'Y_AT')."""
-        if m.endswith('~@'):
-            k, kind = m[:-2], 'Y_AT'
-        elif m.endswith('@'):
-            k, kind = m[:-1], 'LSE_AT'
-        elif m.startswith('soft'):
-            k, kind = m[4:-1], 'SOFT_Y'
-        else:
-            k, kind = m[:-1], 'Y'
-        if k not in cls.WIM_FACTORS:
-            raise NotImplementedError(f'{m}: WIM score outside this build')
-        return k, kind
-
-    def _wim_rows_torch(self, losses, rows_of):
-        """The torch expressions of ft/wim.py:145-192 for the (family, kind) pairs of `rows_of` -> {(family, kind): (N,)}."""
-        y = losses['y_est_already'].unsqueeze(0)
-        out = {}
-        for k, kind in rows_of:
-            f = self.WIM_FACTORS[k]
-            v = -losses['total'] if k == 'elbo' else losses[k]
-            if kind in ('LSE_AT', 'Y_AT'):
-                alt = -losses['total@'] if k == 'elbo' else losses[k + '@']
-            if kind == 'Y':
-                r = f * v.gather(0, y).squeeze(0)
-            elif kind == 'SOFT_Y':
-                r = (v * f).softmax(0).gather(0, y).squeeze(0)
-            elif kind == 'LSE_AT':
-                r = (v * f).logsumexp(0) - f * alt
-            else:
-                r = f * v.gather(0, y).squeeze(0) - f * alt
-            out[k, kind] = r
-        return out
-
-    def batch_dist_measures(self, logits, losses, methods, to_cpu=False, out=None, rows=None, col=0):
-        """The base class's scores for names without a trailing `~` / `@`; the WIM names (ft/wim.py:132-201) from ONE
-        `ops.wim_scores` launch over the sources kl, zdist, iws and total (f = -1 on total stands for elbo), written into
-        out[row, col:col + N] when `out` is given, else into a fresh (R, N) buffer.  The torch expressions remain for more
-        than ops.MISCLASS_MAX_CLASSES classes or a source that is not fp32 on the device.  `losses` is left as found."""
-        methods = list(methods)
-        rows = list(range(len(methods))) if rows is None else [int(r) for r in rows]
-        if len(rows) != len(methods):
-            raise ValueError(f'batch_dist_measures: {len(methods)} methods and {len(rows)} rows')
-        wim = [(m, r) for m, r in zip(methods, rows) if m[-1] in '~@']
-        plain = [(m, r) for m, r in zip(methods, rows) if m[-1] not in '~@']
-        if out is not None and plain:
-            res = super().batch_dist_measures(logits, losses, [m for m, _ in plain], to_cpu=to_cpu, out=out,
-                                              rows=[r for _, r in plain], col=col)
-        else:
-            res = super().batch_dist_measures(logits, losses, [m for m, _ in plain], to_cpu=to_cpu)
-        if not wim:
-            return res
+    def _wim_status_word(self, name, device):
+        """What score_rows.write_rows asks before the `~` / `@` rows of a batch (ft/wim.py:132-201; ONE `ops.wim_scores` launch
+        over the sources kl, zdist, iws and total): the word that launch flags a label outside [0, C) in."""
         if not self.is_cvae:
             raise NotImplementedError('the `~` / `@` scores need the class-conditional model (type cvae)')
-        specs = [self._wim_row(m) for m, _ in wim]
-        families = list(dict.fromkeys(k for k, _ in specs))
-        src = {k: losses['total' if k == 'elbo' else k] for k in families}
-        y_est = losses['y_est_already']
-        C, N = src[families[0]].shape
-        fused = C <= ops.MISCLASS_MAX_CLASSES and y_est.is_cuda and y_est.dtype == torch.int64 and all(
-            v.dtype == torch.float32 and v.is_cuda and v.dim() == 2 for v in src.values())
-        if fused:
-            at = {k for k, kind in specs if kind.endswith('AT')}
-            sources = [(src[k], -1. if k == 'elbo' else self.WIM_FACTORS[k],
-                        losses[('total' if k == 'elbo' else k) + '@'].float() if k in at else None) for k in families]
-            if self._wim_status is None or self._wim_status.device != y_est.device:
-                self._wim_status = torch.zeros(1, dtype=torch.int32, device=y_est.device)
-            buf, where = (out, [r for _, r in wim]) if out is not None else (None, None)
-            buf = ops.wim_scores(sources, y_est, [(families.index(k), kind) for k, kind in specs], out=buf, rows=where, col=col,
-                                 status=self._wim_status)
-            where = where if out is not None else list(range(len(wim)))
-            got = {m: buf[r, col:col + N] if out is not None else buf[r] for (m, _), r in zip(wim, where)}
-        else:
-            by_torch = self._wim_rows_torch(losses, specs)
-            got = {}
-            for (m, r), spec in zip(wim, specs):
-                got[m] = by_torch[spec]
-                if out is not None:
-                    out[r, col:col + N] = got[m]
-                    got[m] = out[r, col:col + N]
-        res.update({m: v.cpu() if to_cpu else v for m, v in got.items()})
-        return {m: res[m] for m in methods}
-
-    def _score_row_by_torch(self, m):
-        return m[-1] not in '~@' and super()._score_row_by_torch(m)
+        if self._wim_status is None or self._wim_status.device != device:
+            self._wim_status = torch.zeros(1, dtype=torch.int32, device=device)
+        return self._wim_status
 
     def _evaluate_for_scores(self, x, batch, measures):
         """Scoring pass of ood_detection_rates: with estimated labels on, the loader's item is the pair (x, y_est) and the

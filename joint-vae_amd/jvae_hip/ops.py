@@ -1323,6 +1323,18 @@ def _mask_u8(mask, N, what):
     return _c(mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8))
 
 
+def _rows_into(out, rows, col, R, N, dev, what):
+    """The `out` / `rows` / `col` arguments of the score-row ops, checked -> (out, rows, col): a new (R, N) buffer without `out`,
+    else columns col .. col + N of R distinct rows of a dense fp32 (M, n) buffer on `dev`."""
+    if out is None:
+        out, rows = torch.empty((R, N), dtype=torch.float32, device=dev), range(R)
+    rows, col = [int(r) for r in rows], int(col)
+    if out.dtype != torch.float32 or out.dim() != 2 or not 0 <= col <= out.shape[1] - N or not out.is_contiguous() \
+            or out.device != dev or len(rows) != R or len(set(rows)) != R or any(not 0 <= r < out.shape[0] for r in rows):
+        raise L.JvaeHipError(f'{what}: a dense (M, >= {col} + {N}) fp32 buffer and {R} distinct rows inside it expected')
+    return out, rows, col
+
+
 _misclass_specs = {}         # (kinds, constants, rows, device) -> their three device arrays: a pass repeats one launch per batch
 
 
@@ -1334,20 +1346,15 @@ def misclass_scores(src, specs, out=None, rows=None, col=0):
     log sum_c e + max_c l + T (`sum`: T = 0), 'lse+': the same on l = v (all-class `iws`: T = log C), 'mean': log mean_c e +
     max_c l, 'std': torch.std of l over the classes (C = 1: NaN), 'nstd': (std_c e / mean_c e)^2, 'mag': max_c l - torch.median
     of l, 'IYx': sum_c(d e) / (C mean_c e) - log mean_c e; the other new kinds ignore T.  'neg' / 'id': -v / v of a (1, N) source.
-    out (M, n >= col + N) fp32 with `rows` = the row of each spec: columns col .. col + N of those rows are written in place;
-    without: a new (len(specs), N) tensor.  C <= 128."""
+    out (M, n >= col + N) fp32 on the source's device with `rows` = the row of each spec, all distinct: columns col .. col + N of
+    those rows are written in place; without: a new (len(specs), N) tensor.  C <= 128."""
     src = _c(_f32(src, 'misclass_scores'))
     L.ptr(src)
     if src.dim() != 2 or not 1 <= src.shape[0] <= MISCLASS_MAX_CLASSES:
         raise L.JvaeHipError(f'misclass_scores: a (C, N) source with C <= {MISCLASS_MAX_CLASSES} expected, got {tuple(src.shape)}')
     C, N = src.shape
     R, dev = len(specs), src.device
-    if out is None:
-        out, rows = torch.empty((R, N), dtype=torch.float32, device=dev), list(range(R))
-    rows, col = [int(r) for r in rows], int(col)
-    if out.dtype != torch.float32 or out.dim() != 2 or not 0 <= col <= out.shape[1] - N or not out.is_contiguous() \
-            or len(rows) != R or any(not 0 <= r < out.shape[0] for r in rows):
-        raise L.JvaeHipError(f'misclass_scores: a dense (M, >= {col} + {N}) fp32 buffer and {R} rows inside it expected')
+    out, rows, col = _rows_into(out, rows, col, R, N, dev, 'misclass_scores')
     for kind, T in specs:
         if kind not in MISCLASS_KINDS or not (float(T) > 0 if MISCLASS_KINDS[kind] < 5 else math.isfinite(float(T))):
             raise L.JvaeHipError(f'misclass_scores: unknown row ({kind!r}, {T!r})')
@@ -1407,12 +1414,7 @@ def wim_scores(sources, y_est, specs, out=None, rows=None, col=0, status=None):
     if y_est.dtype != torch.int64 or tuple(y_est.shape) != (N,) or y_est.device != dev:
         raise L.JvaeHipError(f'wim_scores: ({N},) int64 labels on {dev} expected, got {tuple(y_est.shape)} {y_est.dtype}')
     y_est = _c(y_est)
-    if out is None:
-        out, rows = torch.empty((R, N), dtype=torch.float32, device=dev), list(range(R))
-    rows, col = [int(r) for r in rows], int(col)
-    if out.dtype != torch.float32 or out.dim() != 2 or not 0 <= col <= out.shape[1] - N or not out.is_contiguous() \
-            or out.device != dev or len(rows) != R or len(set(rows)) != R or any(not 0 <= r < out.shape[0] for r in rows):
-        raise L.JvaeHipError(f'wim_scores: a dense (M, >= {col} + {N}) fp32 buffer and {R} distinct rows inside it expected')
+    out, rows, col = _rows_into(out, rows, col, R, N, dev, 'wim_scores')
     flat = []
     for (s, kind), r in zip(specs, rows):
         if kind not in WIM_KINDS or not 0 <= int(s) < S or (kind in ('LSE_AT', 'Y_AT') and alts[int(s)] is None):

@@ -1,0 +1,484 @@
+"""The scoring and detection methods of the model (reference cvae.py:972-1085,1187-2079) as a mixin of
+ClassificationVariationalNetwork: per-sample OOD scores, accuracy, OOD and misclassification detection rates.  What a method name
+means, and the one writer of score rows, are in module/score_rows.py; the model itself (evaluate, predict_after_evaluate,
+odin_scores, the tables of method names) is in cvae.py."""
+import logging
+import os
+import time
+
+import numpy as np
+import torch
+
+from jvae_hip import ops
+from jvae_hip import lib as _lib
+from module import score_rows
+
+
+class ScoringMixin:
+    # Rows (by the start of their name) that ood_detection_rates leaves on the torch expressions although a kernel row exists:
+    # existing ROC checks hold their thresholds to the bits of exactly these expressions, and a softmax or log-sum-exp summed in
+    # another order moves a last bit (measured on the MI355X: up to 2 fp32 ulp between the kernel's softmax rows and torch's).
+    SCORE_SET_TORCH_ROWS = ('iws', 'elbo', 'soft', 'baseline', 'hyz')
+    MISCLASS_TORCH_ROWS = ('iws', 'odin')     # what misclassification_detection_rates leaves on torch: `iws`, the recorded `odin-*`
+    _wim_status_word = None                   # jvae_compat.wim.WIMJob: (name, device) -> the status word of its `~` / `@` rows
+
+    def batch_dist_measures(self, logits, losses, methods, to_cpu=False, out=None, rows=None, col=0):
+        """OOD scores per sample (higher = more in-distribution) for the reference's methods (cvae.py:972-1085), the class-axis
+        scores `sum`, `mean`, `std`, `nstd`, `mag`, `IYx` of the all-class total loss among them; the '-2s' / '-a-x-y' suffixes
+        only name the thresholding done downstream.  -> {method: (N,) scores}.
+
+        Plain call: the reference's torch expressions.  With `out` (a dense (M, n) fp32 device buffer), `rows` (the row of each
+        method, default 0 .. len(methods) - 1) and `col` (first column): the scores are WRITTEN into out[row, col:col + N] and
+        the returned tensors are those views.  Every row with a kernel form goes through `ops.misclass_scores`
+        (csrc/misclass.hip), ONE launch per source tensor (`total`, `iws`, `kl`, `zdist`, `logits`, `cross_x`, `wmse`), grouped
+        as misclassification_detection_rates groups them; the torch expression is kept for a source with more than
+        ops.MISCLASS_MAX_CLASSES classes or that is not fp32, and for the recorded `odin-*` rows.  Against the plain call the
+        pure max / negation rows (`max`, `elbo`, `kl`, `zdist`, `logits`, `mse`, `wmse`, a single-prior `iws`) and `mag` are
+        bit-identical; the softmax and log-sum-exp rows agree within the fp32 error of either
+        (tests/test_13_ood_phase_gpu.py).  What each name means: module/score_rows.py."""
+        methods = list(methods)
+        records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
+        rows = list(range(len(methods))) if rows is None else [int(r) for r in rows]
+        if len(rows) != len(methods):
+            raise ValueError(f'batch_dist_measures: {len(methods)} methods and {len(rows)} rows')
+        got = score_rows.write_rows(records, rows, logits, losses, out, col, torch_rows=('',) if out is None else (),
+                                    wim_status=self._wim_status_word)
+        return {m: v.cpu() if to_cpu else v for m, v in zip(methods, got)}
+
+    def accuracy(self, testset=None, batch_size=100, num_batch='all', method='all', print_result=False,
+                 update_self_testing=True, outputs=None, sample_dirs=[], recorder=None, epoch='last', from_where='all',
+                 epoch_tolerance=0, log=True):
+        """Classification accuracy of `testset` (any map-style dataset of (x, label)) per prediction method, with the
+        reference's signature and bookkeeping (cvae.py:1187-1452): every batch goes through the label-free evaluation
+        (all-class losses, `iws`: SURVEY.md §8f-1); with a `LossRecorder` the per-sample losses, `logits.T` and the labels are
+        recorded batch by batch and written as `record-<set>.pth` into `sample_dirs` (the files test.py / results/ of the
+        reference read, §8f-3) - or, if the recorder already holds the batches, the losses are RECOVERED from it instead of
+        being computed.  Named torchvision datasets and the registry lookup of earlier results (`from_where`) are host-side
+        plumbing outside this build: pass the dataset."""
+        if testset is None or isinstance(testset, str):
+            raise NotImplementedError('named torchvision datasets are outside this build: pass a torch.utils.data.Dataset')
+        name = getattr(testset, 'name', 'testset')
+        only_one = isinstance(method, str) and method != 'all'
+        methods = list(self.predict_methods) if method == 'all' else ([method] if only_one else list(method))
+        full = int(np.ceil(len(testset) / batch_size))
+        shuffle = not (num_batch == 'all' or num_batch >= full)
+        num_batch = full if not shuffle else int(num_batch)
+        if epoch == 'last':
+            epoch = self.trained
+        recorded = recorder is not None and len(recorder) >= num_batch
+        recording = recorder is not None and not recorded
+        if recorded:
+            num_batch, batch_size = len(recorder), recorder.batch_size
+        if recording:
+            recorder.reset()
+            recorder.num_batch = num_batch
+        if recorder is not None:
+            recorder.init_seed_for_dataloader()
+        device = self.device
+        was_training = self.training
+        self.eval()
+        loader = iter(torch.utils.data.DataLoader(testset, batch_size=batch_size, num_workers=0, shuffle=shuffle))
+        errors = torch.zeros(len(methods), device=device)
+        sums, n, measures, t0 = {}, 0, None, time.time()
+        with torch.no_grad():
+            for i in range(num_batch):
+                if recorded:
+                    keys = [k for k in recorder.keys() if k in self.loss_components]
+                    losses = recorder.get_batch(i, *keys, force_dict=True)
+                    logits = recorder.get_batch(i, 'logits').T
+                    y = recorder.get_batch(i, 'y_true')
+                else:
+                    x, y = next(loader)[:2]
+                    x, y = self._device_batch(x.to(device)), y.to(device)      # raw uint8 images: ToTensor on the device
+                    _, logits, losses, measures = self.evaluate(x, batch=i, current_measures=measures)
+                preds = [self.predict_after_evaluate(logits, losses, method=m) for m in methods]
+                if recording:
+                    recorder.append_batch(**losses, y_true=y, logits=logits.T)
+                errors += torch.stack([(p != y).sum() for p in preds]).float()
+                for k, v in losses.items():                     # loss of the TRUE class where a loss is per class (C, N)
+                    v = v.gather(0, y.unsqueeze(0))[0] if v.dim() == 2 else v
+                    sums[k] = sums.get(k, 0.) + v.float().mean()
+                n += y.numel()
+                if print_result and outputs is not None and hasattr(outputs, 'results'):
+                    acc_now = (1 - errors / n).tolist()
+                    outputs.results(i, num_batch, 0, 0, losses={k: float(sums[k]) / (i + 1) for k in self.loss_components if k in sums},
+                                    metrics={k: (measures or {}).get(k, np.nan) for k in self.metrics},
+                                    accuracy=dict(zip(methods, acc_now)), time_per_i=(time.time() - t0) / (i + 1),
+                                    batch_size=batch_size, preambule=print_result)
+        acc = dict(zip(methods, (1 - errors / max(n, 1)).tolist()))
+        self.test_losses = {k: float(v) / max(num_batch, 1) for k, v in sums.items()}
+        if measures:
+            self.test_measures = dict(measures)
+        if recorder is not None:
+            recorder.restore_seed()
+        if recording:
+            for d in sample_dirs:
+                os.makedirs(d, exist_ok=True)
+                recorder.save(os.path.join(d, 'record-{}.pth'.format(name)))
+        if update_self_testing:
+            for m in methods:
+                if n > self.testing.get(epoch, {}).get(m, {'n': 0})['n']:
+                    self.testing.setdefault(epoch, {})[m] = {'n': n, 'epochs': epoch,
+                                                             'sampling': self._latent_samplings['eval'], 'accuracy': acc[m]}
+        if was_training:
+            self.train()
+        return acc[methods[0]] if only_one else acc
+
+    OOD_KEPT_TPR = [pc / 100 for pc in range(90, 100)]                        # cvae.py:1736
+    OOD_ROC_EVERY = 100                                                       # batches between two progress ROCs (cvae.py:1843)
+    # The '-a-x-y' methods (cvae.py:1852-1854): two-sided test on every x-th / y-th sorted in-score (ops.roc_curve, mode
+    # ('quantile', x, y)).  Off by default: the reference reads these thresholds off a spline whose rounding noise decides
+    # its kept rates, so the numbers here are close to the reference's, not equal to them.
+    OOD_QUANTILE_METHODS = False
+
+    def _odin_names(self):
+        """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
+        return ['odin-{:.0f}-{:.4f}'.format(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
+
+    def _ood_methods(self, method):
+        """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
+        line), a name or a list of names.  On a type whose table lists `odin*` (vib), 'all' and 'odin*' expand to the ODIN grid
+        (the plain names first, the expansion behind them, as the reference's develop_starred_methods orders them) and single
+        `odin-T-eps` names are accepted; on every other type an ODIN name raises, and so do the spline-threshold ('-a-x-y')
+        methods unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
+        has_odin = 'odin*' in self.ood_methods
+
+        def unbuilt(m):
+            return ('-a-' in m and not self.OOD_QUANTILE_METHODS) or (m.startswith('odin') and not has_odin)
+
+        def expand(names):
+            plain = [m for m in names if m != 'odin*']
+            return plain + (self._odin_names() if len(plain) < len(names) else [])
+        if method == 'all':
+            skipped = [m for m in self.ood_methods if unbuilt(m)]
+            if skipped:
+                logging.warning('ood_detection_rates: methods outside this build are left out: %s', ', '.join(skipped))
+            return expand([m for m in self.ood_methods if not unbuilt(m)])
+        methods = [method] if isinstance(method, str) else list(method)
+        for m in methods:
+            if unbuilt(m):
+                raise NotImplementedError(f'{m}: spline-threshold (-a-x-y) and ODIN OOD methods are outside this build')
+        methods = expand(methods)
+        grid = set(self._odin_names())
+        for m in methods:
+            if m.startswith('odin') and m not in grid:
+                raise ValueError(f'{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)')
+            if '-a-' in m:
+                score_rows.roc_mode(m)
+        return methods
+
+    def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False):
+        """One pass over `dset` for ood_detection_rates: per batch the label-free evaluation (or the batch read back from a full
+        recorder), then `score_rows.write_rows`: the score rows go straight into ONE preallocated (M, n) device buffer, one
+        kernel launch per source tensor (the `SCORE_SET_TORCH_ROWS` by their torch expressions) - no value comes to the host
+        here.  on_batch(i, num_batch, scores_so_far) is called after each batch.  -> (M, n) fp32 device scores."""
+        device = self.device
+        name = getattr(dset, 'name', 'set')
+        recorded = recorder is not None and len(recorder) >= num_batch
+        recording = recorder is not None and not recorded
+        if recorded:
+            num_batch, batch_size = len(recorder), recorder.batch_size
+        if recording:
+            recorder.reset()
+            recorder.num_batch = num_batch
+        if recorder is not None:
+            recorder.init_seed_for_dataloader()
+        loader = None if recorded else iter(torch.utils.data.DataLoader(dset, batch_size=batch_size, num_workers=0, shuffle=shuffle))
+        buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
+        filled, sums, measures = 0, {}, None
+        odin = any(m.startswith('odin') for m in methods)
+        records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
+        with torch.no_grad():
+            for i in range(num_batch):
+                if recorded:
+                    keys = [k for k in recorder.keys() if k in self.loss_components or k.startswith('odin')]     # cvae.py:1665-1667
+                    losses = recorder.get_batch(i, *keys, force_dict=True)
+                    logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
+                else:
+                    x, y = next(loader)[:2]
+                    x, logits, losses, measures = self._evaluate_for_scores(x, i, measures)
+                    y = y.to(device)
+                    if odin:
+                        # cvae.py:1645-1663: the whole grid per batch (it is what the recorder holds), on the device
+                        losses = dict(losses, **self.odin_scores(x))
+                    if recording:
+                        extra = {} if logits is None else {'logits': logits.T}
+                        recorder.append_batch(**losses, y_true=y, **extra)
+                n = score_rows.write_rows(records, range(len(records)), logits, losses, buf, filled, self.SCORE_SET_TORCH_ROWS,
+                                          self._wim_status_word)[0].shape[0]
+                if odin:
+                    losses = {k: v for k, v in losses.items() if not k.startswith('odin')}     # test_losses: the loss components
+                filled += n
+                if keep_test:
+                    for k, v in losses.items():                                      # cvae.py:1671, summed on the device
+                        sums[k] = sums.get(k, 0.) + v.float().mean()
+                if on_batch is not None:
+                    on_batch(i, num_batch, buf[:, :filled])
+        if keep_test:
+            self.test_losses = {k: float(v) / max(num_batch, 1) for k, v in
+                                zip(sums, torch.stack(list(sums.values())).tolist())} if sums else {}
+            if measures:
+                self.test_measures = dict(measures)
+        if recorder is not None:
+            recorder.restore_seed()
+        if recording:
+            for d in sample_dirs:
+                os.makedirs(d, exist_ok=True)
+                recorder.save(os.path.join(d, 'record-{}.pth'.format(name)))
+        return buf[:, :filled].contiguous()
+
+    @staticmethod
+    def _row_mean_std(scores):
+        """fp64 mean and population standard deviation (np.std, ddof = 0) of each score row, on the device -> (M, 2)."""
+        x = scores.double()
+        mean = x.mean(1)
+        return torch.stack([mean, ((x - mean[:, None]).abs() ** 2).mean(1).sqrt()], 1)
+
+    def ood_detection_rates(self, oodsets=None, testset=None, batch_size=100, num_batch='all', method='all', print_result=False,
+                            update_self_ood=True, epoch='last', outputs=None, recorders=None, from_where='all', sample_dirs=[],
+                            sample_recorders=None, log=True):
+        """OOD detection rates of `oodsets` against the in-distribution `testset` per OOD method, with the reference's signature
+        and result dictionary (cvae.py:1455-1911): -> {set: {method: {'epochs', 'n', 'mean', 'std', 'auc', 'tpr', 'fpr',
+        'thresholds'}}}, `self.ood_results[epoch]` updated when `update_self_ood` (with the in-distribution set's
+        {'n', 'epochs', 'mean', 'std:'} entry - the reference's key has that colon), `test_losses` / `test_measures` set from
+        the in-distribution pass, `record-<set>.pth` written into `sample_dirs` through the `LossRecorder`s of `recorders`
+        ({} = make one per set, filled in place), and a full recorder read back instead of evaluating, as in accuracy().
+
+        train_model() makes this call in its test phase when `TRAIN_OOD_PHASE` is set.
+
+        Underneath, the scores never leave the device: every batch's `batch_dist_measures(out=...)` rows are written into one
+        (M, n) buffer per set by csrc/misclass.hip, one launch per source tensor (`SCORE_SET_TORCH_ROWS` - `iws`, `elbo` and
+        the softmax rows - by their torch expressions, whose bits the ROC thresholds are held to), the ROC of all M methods of a set is ONE `ops.roc_curve` call (csrc/roc.hip) made every 100 batches for the
+        progress line and at the last batch, as the reference does with its Python loop (utils/roc_curves.py:38-210), and only
+        its (M, K) results and the fp64 row means / deviations come to the host.  'thresholds' holds the K [low, up] pairs
+        (the reference stores list(dict), i.e. the two key names).  Methods: what `batch_dist_measures` computes, one-sided,
+        with the '-2s' suffix (two-sided around the mean) or, with `OOD_QUANTILE_METHODS`, the '-a-x-y' suffix (two-sided on
+        in-score quantiles; ValueError below 4 in-distribution samples); see `_ood_methods` for the rest.  Named datasets
+        (`testset=None` or a string, `oodsets=None`) and the registry lookup of earlier results (`from_where`) are host
+        plumbing outside this build, as for accuracy(); so are `sample_recorders`."""
+        if testset is None or isinstance(testset, str) or oodsets is None or any(isinstance(o, str) for o in oodsets):
+            raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
+        if sample_recorders:
+            raise NotImplementedError('sample_recorders are outside this build')
+        if not method:
+            return
+        if epoch == 'last':
+            epoch = self.trained
+        methods = self._ood_methods(method)
+        names = [getattr(s, 'name', 'set') for s in [testset] + list(oodsets)]
+        if recorders is not None and not recorders:
+            from jvae_compat.recorders import LossRecorder
+            recorders.update({n: LossRecorder(batch_size) for n in names})
+        recorders = recorders or {}
+        ood_results = {n: {} for n in names[1:]}
+        if not oodsets:
+            return ood_results
+        was_training = self.training
+        self.eval()
+        modes = [score_rows.roc_mode(m) for m in methods]
+
+        def plan(dset):
+            full = int(np.ceil(len(dset) / batch_size))
+            limited = isinstance(num_batch, int) and num_batch < full
+            return (num_batch if limited else full), limited
+
+        sink = outputs if outputs is not None and hasattr(outputs, 'results') else None
+
+        def progress_line(name, row_means, fpr):
+            """on_batch callback of a pass: the progress line of cvae.py:1709-1715,1870-1875, written at the reference's ROC
+            points (every 100 batches and the last one); None without a sink, and the pass then brings nothing to the host."""
+            if sink is None:
+                return None
+            t0 = time.time()
+
+            def on_batch(i, nb, scores):
+                if i % self.OOD_ROC_EVERY and i != nb - 1:
+                    return
+                sink.results(i, nb, 0, 1, metrics=dict(zip(methods, row_means(scores))), fpr=fpr(),
+                             time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, preambule=name)
+            return on_batch
+
+        nb, shuffle = plan(testset)
+        ind = self._score_set(testset, methods, batch_size, nb, shuffle, recorders.get(names[0]), sample_dirs, keep_test=True,
+                              on_batch=progress_line(names[0], lambda s: self._row_mean_std(s)[:, 0].tolist(),
+                                                     lambda: {m: np.nan for m in methods}))
+        for m in methods:
+            if '-a-' in m and ind.shape[1] < 4:
+                raise ValueError(f'{m}: {ind.shape[1]} in-distribution samples, the cubic spline of the reference needs 4 '
+                                 '(utils/roc_curves.py:79)')
+        if update_self_ood:
+            entry = self.ood_results.setdefault(epoch, {}).setdefault(names[0], {})
+            for m, (mean, std) in zip(methods, self._row_mean_std(ind).tolist()):
+                entry[m] = {'n': ind.shape[1], 'epochs': epoch, 'mean': mean, 'std:': std}
+
+        kept = torch.tensor(self.OOD_KEPT_TPR, dtype=torch.float64, device=ind.device)
+        K = len(self.OOD_KEPT_TPR)
+        for oodset, name in zip(oodsets, names[1:]):
+            last = {}
+
+            def roc(scores):
+                """ONE device ROC for all methods, ONE copy of its (M, 4K + 4) results to the host."""
+                r = ops.roc_curve(ind, scores.contiguous(), kept, modes)
+                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['status'].double()[:, None],
+                                  self._row_mean_std(scores)], 1).cpu().numpy()
+                ops.roc_check_status(host[:, 1 + 4 * K].astype(np.int64))
+                last['host'] = host
+                return host[:, -2].tolist()
+
+            def fpr95():
+                return {m: float(h[1 + 5]) for m, h in zip(methods, last['host'])}      # fpr_at_tpr(..., 0.95): slot 5 of the kept TPRs
+
+            nb, shuffle = plan(oodset)
+            scores = self._score_set(oodset, methods, batch_size, nb, shuffle, recorders.get(name), sample_dirs,
+                                     on_batch=progress_line(name, roc, fpr95))
+            if sink is None:                                  # with a sink the last batch's progress ROC is the final one
+                roc(scores)
+            for m, h in zip(methods, last['host']):
+                fpr, low, up = h[1:1 + K], h[1 + 2 * K:1 + 3 * K], h[1 + 3 * K:1 + 4 * K]
+                ood_results[name][m] = {'epochs': epoch, 'n': scores.shape[1], 'mean': float(h[-2]), 'std': float(h[-1]),
+                                        'auc': float(h[0]), 'tpr': list(self.OOD_KEPT_TPR), 'fpr': [float(f) for f in fpr],
+                                        'thresholds': [[float(a), float(b)] for a, b in zip(low, up)]}
+                if update_self_ood:
+                    self.ood_results.setdefault(epoch, {}).setdefault(name, {})[m] = ood_results[name][m]
+        if was_training:
+            self.train()
+        return ood_results
+
+    # ------------------------------------------------------------------------------------ misclassification detection
+    def _starred(self, names):
+        """develop_starred_methods (utils/save_load/dictify.py:198-212) on a copy: the plain names in their order, then what
+        each starred name expands to; a starred name without an entry in `methods_params` (softiws*) expands to nothing."""
+        grids = dict(self.methods_params, odin=self._odin_names())
+        plain = [m for m in names if not m.endswith('*')]
+        return plain + [e for m in names if m.endswith('*') for e in grids.get(m[:-1], [])]
+
+    def misclassification_detection_rates(self, predict_methods='all', misclass_methods='all', epoch='last', shown_tpr=0.95,
+                                          from_where=('json', 'recorders'), print_result=False, update_self_results=True,
+                                          outputs=None, recorder=None):
+        """How well each misclassification score separates the correctly from the wrongly classified samples of the recorded test
+        set, per prediction method (cvae.py:1913-2079): the ROC of score[correct] against score[missed] - AUC, FPR at the kept
+        TPRs 0.90 .. 0.99 - and the precision tp / (tp + fp) at each kept threshold.  Stored, as the reference stores it, in
+        `self.testing[epoch][predict_method][m] = {'n', 'epochs', 'sampling', 'tpr', 'fpr', 'auc', 'precision'}` (plain floats and
+        lists, `save()` writes them to test.json) and, unlike the reference (which returns None), returned as
+        {predict_method: {m: entry}}.
+
+        The scores come from a `LossRecorder` (the all-class losses, `logits` as (C, N), `y_true`): the one passed as `recorder`,
+        or `saved_dir/samples/<epoch:04d>/record-<training_parameters['set']>.pth` (`epoch='last'`: the largest epoch directory
+        holding that file).  Nothing to do (None, said at debug level) without that file, without 'recorders' in `from_where`, or
+        for a model type without misclassification methods.  The registry lookup of earlier results (`available_results`) is host
+        plumbing outside this build, as for accuracy().  Starred names expand through `methods_params` (`odin*`: this model's
+        grid); `softiws*` has no entry there and expands to nothing, as in the reference.  A name outside the model's table is an
+        error; a method whose loss the recorder does not hold is skipped.
+
+        Underneath, per prediction method: the score rows are computed on the device into ONE (M, N) buffer (csrc/misclass.hip,
+        one launch per source tensor; `batch_dist_measures` for `iws` and the recorded `odin-*` rows), then ONE split by
+        correctness, ONE ROC of all M rows (csrc/roc.hip), ONE confusion count, and ONE copy of the (M, 6K + 2) results to the
+        host; n_correct is the only other value read back.  No (M, N) or (C, N) tensor goes to the host.
+
+        Decided where the reference fails: a prediction method that gets every sample right - or none - is skipped with a
+        warning (the reference dies in roc_curve); a row with a NaN score (`hyz` on a saturated softmax) is skipped with a warning
+        naming it.  The reference's "n already there" guard reads `self.testing[epoch][predict_methods][m]` - the ARGUMENT, a
+        list or 'all', so it never finds anything (cvae.py:2064); here it looks under the prediction method being processed.
+        The P / R / FPR at `shown_tpr` are logged at debug level (and sent to `outputs` with `print_result`); NaN when no kept slot
+        reaches `shown_tpr`.  Nothing stored depends on them."""
+        def nothing(why):
+            logging.debug('misclassification_detection_rates: nothing to do (%s)', why)
+
+        if not self.misclass_methods:
+            return nothing(f'no misclassification methods for type {self.type}')
+        if not (from_where == 'all' or 'recorders' in from_where):
+            return nothing("'recorders' is not in from_where")
+        if recorder is None:
+            from jvae_compat.recorders import LossRecorder
+            fname = 'record-{}.pth'.format(self.training_parameters['set'])
+            root = os.path.join(getattr(self, 'saved_dir', None) or '', 'samples')
+            if epoch == 'last':
+                found = [int(d) for d in (os.listdir(root) if os.path.isdir(root) else [])
+                         if d.isdigit() and os.path.exists(os.path.join(root, d, fname))]
+                if not found:
+                    return nothing(f'no {fname} under {root}')
+                epoch = max(found)
+            path = os.path.join(root, '{:04d}'.format(int(epoch)), fname)
+            if not os.path.exists(path):
+                return nothing(f'no {path}')
+            recorder = LossRecorder.load(path, map_location=self.device)
+        elif epoch == 'last':
+            epoch = self.trained
+        epoch = int(epoch)
+
+        chosen = {}
+        for which, arg, table in (('predict', predict_methods, self.predict_methods), ('miss', misclass_methods, self.misclass_methods)):
+            everything = self._starred(table)
+            names = [arg] if isinstance(arg, str) else list(arg or [])
+            names = everything if names and names[0] in ('all', 'default') else self._starred(names)
+            for m in names:
+                if m not in everything:
+                    raise ValueError(f'{m}: not a {which} method of a {self.type} ({", ".join(table)})')
+            chosen[which] = names
+
+        tensors = {k: recorder[k].to(self.device) for k in recorder.keys()}
+        _lib.ptr(tensors['y_true'])                                          # there is no CPU path
+        logits_cn, y = tensors.pop('logits', None), tensors.pop('y_true')
+        logits = None if logits_cn is None else logits_cn.T
+        sources = dict(tensors, logits=logits)
+        n, K = y.shape[0], len(self.OOD_KEPT_TPR)
+        rows_of = {m: score_rows.parse(m, score_rows.traits_of(self), misclass=True) for m in chosen['miss']}
+        methods = [m for m in chosen['miss'] if sources.get(rows_of[m].source) is not None]
+        skipped = [m for m in chosen['miss'] if m not in methods]
+        if skipped:
+            logging.debug('misclassification_detection_rates: not in the recorder: %s', ', '.join(skipped))
+        sampling = self._latent_samplings['eval']
+        results = {}
+        if not methods:
+            return results
+
+        # the score rows do not depend on the prediction method: ONE (M, N) buffer, one launch per source tensor
+        scores = torch.empty((len(methods), n), dtype=torch.float32, device=y.device)
+        with torch.no_grad():
+            score_rows.write_rows([rows_of[m] for m in methods], range(len(methods)), logits, tensors, scores,
+                                  torch_rows=self.MISCLASS_TORCH_ROWS)
+            kept = torch.tensor(self.OOD_KEPT_TPR, dtype=torch.float64, device=y.device)
+            sink = outputs if print_result and outputs is not None and hasattr(outputs, 'write') else None
+            for pm in chosen['predict']:
+                correct = self.predict_after_evaluate(logits, tensors, method=pm) == y
+                try:
+                    r = ops.misclass_rates(scores, correct, kept)
+                except ValueError as err:
+                    logging.warning('misclassification_detection_rates: prediction method %s skipped: %s', pm, err)
+                    continue
+                n_correct = r['n_correct']
+                acc = n_correct / n
+                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['tp'].double(), r['fp'].double(),
+                                  r['status'].double()[:, None]], 1).cpu().numpy()
+                logging.debug('Acc. for method %s: (%5.2f) ****', pm, 100 * acc)
+                results[pm] = {}
+                best = (None, 0.)
+                for m, h in zip(methods, host):
+                    if int(h[-1]):
+                        logging.warning('misclassification_detection_rates: %s-%s skipped: NaN score', pm, m)
+                        continue
+                    fpr, tpr = h[1:1 + K], h[1 + K:1 + 2 * K]
+                    tp, fp = h[1 + 4 * K:1 + 5 * K], h[1 + 5 * K:1 + 6 * K]
+                    with np.errstate(invalid='ignore', divide='ignore'):
+                        precision = tp / (tp + fp)                          # 0 / 0 = NaN, as numpy gives the reference
+                    at = np.where(tpr >= shown_tpr)[0]                      # fpr_at_tpr (utils/roc_curves.py:8-27)
+                    p95, r95, f95 = ((precision[at.min()], tp[at.min()] / n_correct, fp[at.min()] / (n - n_correct))
+                                     if len(at) else (np.nan, np.nan, np.nan))
+                    if p95 > best[1]:
+                        best = (m, p95)
+                    line = '{:16}: \tP={:5.2f} ({:+4.1f}) R={:5.2f} FPR={:5.2f}'.format(m, 100 * p95, 100 * (p95 - acc), 100 * r95,
+                                                                                       100 * f95)
+                    logging.debug(line)
+                    if sink is not None:
+                        sink.write(line + '\n')
+                    entry = {'n': n, 'epochs': epoch, 'sampling': sampling, 'tpr': [float(t) for t in tpr],
+                             'fpr': [float(f) for f in fpr], 'auc': float(h[0]), 'precision': [float(p) for p in precision]}
+                    results[pm][m] = entry
+                    n_already = self.testing.get(epoch, {}).get(pm, {}).get(m, {'n': 0})['n']
+                    if update_self_results and n >= n_already:
+                        slot = self.testing.setdefault(epoch, {})
+                        if pm not in slot:
+                            slot[pm] = {'n': n, 'epochs': epoch, 'sampling': sampling, 'accuracy': float(acc)}
+                        slot[pm][m] = entry
+                logging.debug('best method for %s: %s (P=%.2f)', pm, best[0], 100 * best[1])
+        return results

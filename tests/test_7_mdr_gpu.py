@@ -119,13 +119,14 @@ def test_confusion_counts_of_plain_thresholds():
 # ---------------------------------------------------------------------------------------------- 2. + 3. score rows
 def fused_rows(c):
     """Every fused method of a golden case through ops.misclass_scores, one launch per source tensor -> {method: fp32 row}."""
-    from cvae import ClassificationVariationalNetwork as Net
     from jvae_hip import ops
+    from module import score_rows
+    traits = score_rows.Traits(losses_might_be_computed_for_each_class=True, is_vae=False, is_jvae=False, num_labels=10)
     by_source = {}
     for m in c['methods']:
-        key, spec = Net._misclass_row(m)
-        if spec is not None:
-            by_source.setdefault(key, []).append((m, spec))
+        row = score_rows.parse(m, traits, misclass=True)       # none of these rows depends on the model type
+        if m != 'iws' and row.kind is not None:                 # the misclassification pass keeps `iws` on its torch row
+            by_source.setdefault(row.source, []).append((m, (row.kind, row.const)))
     out = {}
     for key, rows in by_source.items():
         got = ops.misclass_scores(dev(c['recorder'][key]), [spec for _, spec in rows]).cpu().numpy()
@@ -165,6 +166,7 @@ def device_recorder_tensors(c):
 
 def test_batch_dist_measures_new_branches_and_old_ones_bit_for_bit():
     from jvae_hip import ops
+    from module import score_rows
     c = load_case(GOLDEN, 'cvae_1500')
     net = cvae_net()
     logits, losses, _ = device_recorder_tensors(c)
@@ -177,7 +179,8 @@ def test_batch_dist_measures_new_branches_and_old_ones_bit_for_bit():
     exact = fp64_rows(rec, list(new))
     soft_bar, hyz_bar = 4 * max(c['referr'][f] for f in ('softkl', 'softzdist', 'baseline')), 4 * c['referr']['hyz']
     for m, (key, kind, T) in new.items():
-        assert net._misclass_row(m) == (key, (kind, T))
+        row = score_rows.parse(m, score_rows.traits_of(net), misclass=True)
+        assert (row.source, (row.kind, row.const)) == (key, (kind, T))
         fused = ops.misclass_scores(dev(rec[key]), [(kind, T)])[0].cpu().numpy().astype(np.float64)
         torch_row = got[m].cpu().numpy().astype(np.float64)
         bar = hyz_bar if m == 'hyz' else soft_bar

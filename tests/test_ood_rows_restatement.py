@@ -112,19 +112,30 @@ def test_row_tables():
     from jvae_hip import ops
     assert ops.MISCLASS_KINDS == {'soft-': 0, 'soft+': 1, 'max-': 2, 'max+': 3, 'hyz': 4, 'lse-': 5, 'lse+': 6, 'mean': 7,
                                   'std': 8, 'nstd': 9, 'mag': 10, 'IYx': 11, 'neg': 12, 'id': 13}
-    assert Net._misclass_row('sum') == ('total', ('lse-', 0.))
-    for m in ('mean', 'std', 'nstd', 'mag', 'IYx'):
-        assert Net._misclass_row(m) == ('total', (m, 0.))
-    assert Net._misclass_row('iws') == ('iws', None)           # the misclassification table keeps its torch row
-    with pytest.raises(ValueError):
-        Net._misclass_row('softmax')
+    from module import score_rows
+
+    def fused_row(net, m, **kw):
+        row = score_rows.parse(m, score_rows.traits_of(net), **kw)
+        return row.source, None if row.kind is None else (row.kind, row.const)
     net = cpu_cvae()
-    assert net._fused_row('iws') == ('iws', ('lse+', math.log(net.num_labels)))
-    assert net._fused_row('elbo') == ('total', ('max-', 1.)) and net._fused_row('zdist') == ('zdist', ('max-', 1.))
-    assert net._fused_row('mse') == ('cross_x', ('neg', 0.)) and net._fused_row('wmse') == ('wmse', ('neg', 0.))
-    assert net._fused_row('odin-1-0.0040') == ('odin-1-0.0040', None) and net._fused_row('fisher_rao') == ('fisher_rao', None)
-    assert Net._base_method('iws-2s') == 'iws' and Net._base_method('elbo-a-4-1') == 'elbo' and Net._base_method('softkl-10') == 'softkl-10'
+    assert fused_row(net, 'sum', misclass=True) == ('total', ('lse-', 0.))
+    for m in ('mean', 'std', 'nstd', 'mag', 'IYx'):
+        assert fused_row(net, m, misclass=True) == ('total', (m, 0.))
+    # the misclassification pass keeps `iws` on its torch row: no launch is tried (there is no CPU path), the row is torch's
+    iws, row = {'iws': make_source(10, 5, 1., 0)}, score_rows.parse('iws', score_rows.traits_of(net), misclass=True)
+    kept, = score_rows.write_rows([row], [0], None, iws, torch.zeros(1, 5), torch_rows=Net.MISCLASS_TORCH_ROWS)
+    assert row.source == 'iws' and kept.numpy().tobytes() == row.torch_row(iws).numpy().tobytes()
+    with pytest.raises(ValueError):
+        score_rows.parse('softmax', score_rows.traits_of(net), misclass=True)
+    assert fused_row(net, 'iws') == ('iws', ('lse+', math.log(net.num_labels)))
+    assert fused_row(net, 'elbo') == ('total', ('max-', 1.)) and fused_row(net, 'zdist') == ('zdist', ('max-', 1.))
+    assert fused_row(net, 'mse') == ('cross_x', ('neg', 0.)) and fused_row(net, 'wmse') == ('wmse', ('neg', 0.))
+    assert fused_row(net, 'odin-1-0.0040') == ('odin-1-0.0040', None)
+    with pytest.raises(NotImplementedError):
+        score_rows.parse('fisher_rao', score_rows.traits_of(net))
+    base = {m: score_rows.parse(m, score_rows.traits_of(net)).base for m in ('iws-2s', 'elbo-a-4-1', 'softkl-10')}
+    assert base == {'iws-2s': 'iws', 'elbo-a-4-1': 'elbo', 'softkl-10': 'softkl-10'}
     vae = Net(**dict(get_case('ea2_n8_vae_L3')['net']))
-    assert vae._fused_row('iws') == ('iws', ('id', 0.)) and vae._fused_row('elbo') == ('total', ('neg', 0.))
-    assert vae._fused_row('zdist') == ('zdist', ('neg', 0.))
+    assert fused_row(vae, 'iws') == ('iws', ('id', 0.)) and fused_row(vae, 'elbo') == ('total', ('neg', 0.))
+    assert fused_row(vae, 'zdist') == ('zdist', ('neg', 0.))
     assert Net.TRAIN_OOD_PHASE is False and set(Net.SCORE_SET_TORCH_ROWS) >= {'iws', 'elbo'}

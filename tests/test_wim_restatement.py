@@ -123,10 +123,15 @@ def test_fallback_expressions_reproduce_the_reference_rows(name):
 def test_method_names_and_tables():
     from jvae_compat.wim import WIMJob
     job = tiny_job()
-    assert WIMJob._wim_row('zdist~') == ('zdist', 'Y') and WIMJob._wim_row('softkl~') == ('kl', 'SOFT_Y')
-    assert WIMJob._wim_row('elbo@') == ('elbo', 'LSE_AT') and WIMJob._wim_row('iws~@') == ('iws', 'Y_AT')
+    from module import score_rows
+
+    def wim_row(m):                                         # elbo reads `total`; the factor is the family's (ft/wim.py:145)
+        row = score_rows.parse(m, score_rows.traits_of(job))
+        return row.source, row.kind, row.const
+    assert wim_row('zdist~') == ('zdist', 'Y', -.5) and wim_row('softkl~') == ('kl', 'SOFT_Y', -1.)
+    assert wim_row('elbo@') == ('total', 'LSE_AT', 1.) and wim_row('iws~@') == ('iws', 'Y_AT', 1.)
     with pytest.raises(NotImplementedError):
-        WIMJob._wim_row('mse~')
+        wim_row('mse~')
     assert job.ood_methods == ['zdist', 'zdist~', 'zdist@', 'zdist~@', 'elbo', 'elbo~', 'elbo@', 'elbo~@']
     assert job.misclass_methods == ['softzdist~', 'zdist~'] and job.predict_methods == ['already']
     base = type(job).__mro__[1].loss_components_per_type['cvae']

@@ -6,7 +6,7 @@ draws of `bench.py --workload eval`:
                 evaluate(x) calls with the prior swapped in between (WIM_SHARED_PASS = False: what the reference does, and what
                 a base model can be driven to do by hand);
   score_rows    the 12 OOD rows {kl, zdist, iws, elbo} x {~, @, ~@} of one batch from ONE `ops.wim_scores` launch against the
-                torch expressions of ft/wim.py:145-192 (`WIMJob._wim_rows_torch`), on the losses of that evaluation.
+                torch expressions of ft/wim.py:145-192 (`Row.torch_row` of module/score_rows.py), on the losses of that evaluation.
 
     python tools/wim_bench.py [--calls 20] [--warmup 5] [--n 512] [--L 128] [--out profiles/wim_bench.json]
 
@@ -50,6 +50,7 @@ def main():
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     from jvae_compat.wim import WIMJob
+    from module import score_rows
     from oracle.cases import WIM_CASES, full_config
     from oracle.det_init import load_det_state
     dev = 'cuda:0'
@@ -75,13 +76,13 @@ def main():
     one, two = timed(both(True), a.calls, a.warmup), timed(both(False), a.calls, a.warmup)
     out['both_priors'] = {'shared_pass': one, 'two_passes': two, 'two_over_shared': two['ms_median'] / one['ms_median']}
     losses = kept['out'][2]
-    methods = [k + s for k in job.WIM_FACTORS for s in ('~', '@', '~@')]
-    specs = [job._wim_row(m) for m in methods]
+    methods = [k + s for k in ('kl', 'zdist', 'iws', 'elbo') for s in ('~', '@', '~@')]
+    records = [score_rows.parse(m, score_rows.traits_of(job)) for m in methods]
     buf = torch.empty((len(methods), a.n), dtype=torch.float32, device=dev)
     fused = timed(lambda: job.batch_dist_measures(None, losses, methods, out=buf), a.calls, a.warmup)
-    by_torch = timed(lambda: job._wim_rows_torch(losses, specs), a.calls, a.warmup)
-    ref = job._wim_rows_torch(losses, specs)
-    worst = max(float((buf[i] - ref[s]).abs().max() / ref[s].abs().max().clamp_min(1e-30)) for i, s in enumerate(specs))
+    by_torch = timed(lambda: [r.torch_row(losses) for r in records], a.calls, a.warmup)
+    ref = [r.torch_row(losses) for r in records]
+    worst = max(float((row - want).abs().max() / want.abs().max().clamp_min(1e-30)) for row, want in zip(buf, ref))
     out['score_rows'] = {'rows': len(methods), 'wim_scores_one_launch': fused, 'torch_expressions': by_torch,
                          'torch_over_fused': by_torch['ms_median'] / fused['ms_median'], 'max_relative_difference': worst}
     line = json.dumps(out)

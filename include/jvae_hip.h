@@ -675,6 +675,37 @@ int jvae_cascade_mse_f32(const float* x, const void* const* stages, int M, float
                          size_t ws_bytes, void* stream);
 int jvae_iterate_prior_f32(const float* p, float* posterior, int M, int C, long N, void* stream);
 
+/* ---- Latent-space inspection: per-group posterior moments, nearest centroid, histogram (csrc/inspect.hip; reference
+ * module/sample.py::zsample, ft/inspection.py, utils/inspection.py) ----------------------------------------------------
+ * None of the entry points allocates or synchronises.  No floating-point atomics: every float result is the same bits run to
+ * run and does not depend on the number of CUs; the exact counts are added with integer atomics.
+ * Moments: mu, log_var (N, K) fp32, group (N,) int32 in [0, G) or NULL (every sample in group 0, G = 1) - a value outside
+ * [0, G) leaves the sample out, as in jvae_group_tally_f32.  sums (G, 4, K) fp64 and counts (G,) int64 are DEVICE accumulators
+ * the caller owns and clears:
+ *   sums[g, 0..3, k] += sum over group[n] == g of mu, mu^2, v, v^2,  v = expf(log_var[n, k]) widened to fp64
+ *   counts[g]        += the number of such n
+ * Rows are summed in slabs of 256 (inside a slab: four interleaved runs, folded as (0 + 1) + (2 + 3)), the slabs in ascending
+ * order: the order hangs on N alone.  ws: device scratch of at least jvae_latent_moments_workspace_bytes(N, K, G) bytes, 8-byte
+ * aligned (-3, JVAE_EWORKSPACE, when smaller).  1 <= K <= 65536, 1 <= G <= 65536, 0 <= N <= 2^24, else -2 (JVAE_ENOTSUP).
+ * Nearest centroid: mu (N, K), centroids (C, K) -> y_nearest (N,) int64 = argmin_c |mu_n - m_c|^2, d2 (N,) fp32 the winner's
+ * squared distance.  Differences, squares and sums in fp64, one rounding; the comparison is made on the fp64 sums, ties go to
+ * the lowest index and a NaN distance comes before every number (torch.argmin).  1 <= K <= 65536, 1 <= C <= 65536,
+ * 0 <= N <= 2^30, else -2.
+ * Histogram: values (n,) fp32, edges (B + 1,) fp64 ascending ON THE DEVICE, group (n,) int32 in [0, G) or NULL ->
+ *   counts[g, b] += #{i: group[i] == g, edges[b] <= values[i] < edges[b + 1]}, the last bin closed on the right
+ * (np.histogram's rule).  counts (G, B) int64 is the caller's accumulator.  Values outside [edges[0], edges[B]] are not counted;
+ * neither are NaN and +-inf, whose number is added to *nonfinite (device int64, owned and cleared by the caller).  The bin is
+ * found by bisection of the edges in fp64; edges that do not ascend give unspecified counts, never an access out of bounds.
+ * B <= 4096 and G B <= 4096: edges and private counters in LDS.  G B <= 2^26, else -2.
+ * Any other malformed argument: -1 (JVAE_EINVAL). */
+size_t jvae_latent_moments_workspace_bytes(int N, int K, int G);
+int jvae_latent_moments_f32(const float* mu, const float* log_var, const int* group, double* sums, long long* counts, int N, int K,
+                            int G, void* ws, size_t ws_bytes, void* stream);
+int jvae_nearest_centroid_f32(const float* mu, const float* centroids, long long* y_nearest, float* d2, long N, int K, int C,
+                              void* stream);
+int jvae_histogram_f32(const float* values, const double* edges, const int* group, long long* counts, long long* nonfinite, long n,
+                       int B, int G, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

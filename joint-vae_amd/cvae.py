@@ -16,6 +16,8 @@ its label-free evaluation included, pooling / up-sampling layer tokens, SGD,
 the `y=None` all-class evaluation with its OOD scores, the WIM fine-tuning step and the evaluation methods accuracy(),
 ood_detection_rates() and misclassification_detection_rates() are built (module/scoring.py), and so is generate():
 images decoded from draws of the prior (module/sample.py builds the reference's grids of them).
+latent_posterior(x, y) is the encode-only pass (mu, log_var bit for bit evaluate()'s, nothing decoded) under module.sample.zsample();
+the sample recorders of ood_detection_rates() write the reference's samples-<set>.pth.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -1006,12 +1008,42 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                 self.train()
         return dict(zip(self._odin_names(), scores))
 
-    def _evaluate_for_scores(self, x, batch, measures):
-        """One batch of the scoring pass: `x` as the data loader yields it -> (x on the device, logits, losses, measures).  A
-        subclass whose items carry more than the image (jvae_compat/wim.py: (x, y_est) pairs) overrides this."""
+    def latent_posterior(self, x, y=None):
+        """The encoder's posterior of a batch and nothing else -> (mu, log_var), each (N, K): the feature stack, the two heads of
+        the encoder, then the +-20 clip of the log-variance (or the forced variance) as the latent kernel applies it.  No noise is
+        drawn, nothing is decoded and no prior is consulted beyond the operand the kernel wants: bit for bit the mu, log_var of
+        evaluate(x, y, z_output=True) on the same batch, without the (L + 1) N decoded images and the C-class tail that call
+        spends on them (reference module/sample.py::zsample keeps these two tensors of a whole evaluate()).  Models with coded
+        labels need y.  Runs under no_grad in both compute dtypes; put the model in eval mode first, as for evaluate()."""
+        if y is None and self.y_is_coded:
+            raise NotImplementedError('latent_posterior(x) without labels is not possible for models with coded labels (their '
+                                      'encoder reads y): pass y')
+        if x.dim() != self.input_dim + 1:
+            x = x.reshape(-1, *self.input_shape)
+            y = None if y is None else y.reshape(-1)
+        N = x.shape[0]
+        enc = self.encoder
+        with torch.no_grad(), self._constant_weights(x):
+            feats = self._features_of(x).reshape(N, -1)
+            y1h = onehot_encoding(y, self.num_labels).float() if self.y_is_coded else None
+            _, mu, lv_raw = enc.heads(feats, y1h)
+            K = mu.shape[-1]
+            pr = enc.prior
+            dummy = torch.zeros(N, dtype=torch.int64, device=x.device)
+            lab, means, T = pr._kernel_operands(dummy if pr.conditional else None, N, mu.device)
+            forced = math.log(enc.forced_variance) if enc.forced_variance else None
+            log_var = ops.latent(mu, mu if lv_raw is None else lv_raw, torch.zeros((1, N, K), device=x.device), lab, means, T,
+                                 prior=pr.distribution, var_dim=pr.var_dim, tau=pr._tau, alpha=pr._alpha_k, sampled=False,
+                                 forced_lv=forced)[0]
+        return mu, log_var
+
+    def _evaluate_for_scores(self, x, batch, measures, with_mu=False):
+        """One batch of the scoring pass: `x` as the data loader yields it -> (x on the device, logits, losses, measures[, mu]).
+        `with_mu`: the posterior means of the same pass, for the sample recorders.  A subclass whose items carry more than the
+        image (jvae_compat/wim.py: (x, y_est) pairs) overrides this."""
         x = self._device_batch(x.to(self.device))
-        _, logits, losses, measures = self.evaluate(x, batch=batch, current_measures=measures)
-        return x, logits, losses, measures
+        out = self.evaluate(x, batch=batch, current_measures=measures, z_output=with_mu)
+        return (x,) + tuple(out[1:4]) + ((out[4],) if with_mu else ())
 
     def _early_reduce_hook(self, grad):
         self.optimizer.reduce_early_bucket()

@@ -253,16 +253,16 @@ class WIMJob(ClassificationVariationalNetwork):
             self._wim_status = torch.zeros(1, dtype=torch.int32, device=device)
         return self._wim_status
 
-    def _evaluate_for_scores(self, x, batch, measures):
+    def _evaluate_for_scores(self, x, batch, measures, with_mu=False):
         """Scoring pass of ood_detection_rates: with estimated labels on, the loader's item is the pair (x, y_est) and the
-        evaluation runs under both priors."""
+        evaluation runs under both priors.  `with_mu`: the posterior means of that same pass come back as a fifth item."""
         if not self._with_estimated_labels:
-            return super()._evaluate_for_scores(x, batch, measures)
+            return super()._evaluate_for_scores(x, batch, measures, with_mu=with_mu)
         x, y_est = x
         x = self._device_batch(x.to(self.device))
         with self.evaluate_on_both_priors():
-            _, logits, losses, measures = self.evaluate((x, y_est.to(self.device)), batch=batch, current_measures=measures)
-        return x, logits, losses, measures
+            out = self.evaluate((x, y_est.to(self.device)), batch=batch, current_measures=measures, z_output=with_mu)
+        return (x,) + tuple(out[1:4]) + ((out[4],) if with_mu else ())
 
     def ood_detection_rates(self, *a, **kw):
         """The base class's method over `((x, y_est), y)` items; a label outside [0, C) met by the score kernel raises here,
@@ -354,7 +354,8 @@ class WIMJob(ClassificationVariationalNetwork):
     TALLY_GROUPS = ('ind', 'ood', 'in')          # groups of the printed losses: moving set's two classes, then the labelled batch
 
     def finetune(self, trainset, ind_set, ood_sets, *, train_size=100000, epochs=None, batch_size=None, test_batch_size=8192,
-                 optimizer=None, outputs=None, alpha=0.1, report_every=10, testset_name=None, on_batch=None):
+                 optimizer=None, outputs=None, alpha=0.1, report_every=10, testset_name=None, on_batch=None,
+                 sample_recorders=None):
         """The WIM fine-tuning loop (ft/job.py:170-478) over data-set objects: `trainset` yields the labelled (x, y) batches,
         `ind_set` and the sets of `ood_sets` (name -> data set) make the `MovingSet` the alternate prior pulls on.
 
@@ -370,7 +371,13 @@ class WIMJob(ClassificationVariationalNetwork):
         first epoch, so `torch.manual_seed(s)` in front of finetune() fixes the loaders' order and the noise of the epochs.
         `on_batch(epoch, batch, in_loss, mix_loss, tags)` is called after each step with that step's loss dictionaries.
         `trained` is left as found, as in the reference.  Named data sets raise NotImplementedError; see DESIGN.md for what
-        else of the reference's loop is outside this build."""
+        else of the reference's loop is outside this build.
+
+        `sample_recorders` ({set name: SampleRecorder}, see `make_sample_recorders`): the latent records of the reference's
+        `--inspection` switch (ft/job.py:282-300, 451-470).  They are filled by the scoring pass before tuning and, with `saved_dir`
+        set, written as `saved_dir/samples/<trained:04d>/init/samples-<set>.pth`; then reset(), filled again by the pass after
+        tuning and written into `saved_dir/samples/<trained:04d>`.  Without `saved_dir` no file is written and the recorders
+        hold the records of the pass after tuning.  They change nothing else: the same launches of the loop, the same parameters."""
         named = [s for s in (trainset, ind_set) if isinstance(s, str) or s is None]
         if named or not isinstance(ood_sets, dict) or any(isinstance(s, str) for s in ood_sets.values()):
             raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets '
@@ -388,6 +395,12 @@ class WIMJob(ClassificationVariationalNetwork):
         logging.info('Moving set of length %d, with mixture %s', len(moving_set),
                      ', '.join('{}:{:.1%}'.format(n, m) for n, m in zip(moving_set.classes, moving_set.mix)))
 
+        def sample_dirs(*sub):
+            saved = getattr(self, 'saved_dir', None)
+            if not sample_recorders or not saved:
+                return []
+            return [os.path.join(saved, 'samples', '{:04d}'.format(self.trained), *sub)]
+
         # ---- before tuning: the original prior's rates, and the recorders the estimated labels are read from
         rng = (torch.get_rng_state(), torch.cuda.get_rng_state(device) if device.type == 'cuda' else None)
         self.eval()
@@ -399,8 +412,11 @@ class WIMJob(ClassificationVariationalNetwork):
             self.ood_detection_rates(batch_size=test_batch_size,
                                      testset=moving_set.extract_subdataset('ind', new_name=testset_name),
                                      oodsets=[ood_.extract_subdataset(n, new_name=n) for n in ood_sets],
-                                     outputs=outputs, recorders=recorders, print_result='*')
+                                     outputs=outputs, recorders=recorders, print_result='*',
+                                     sample_recorders=sample_recorders, sample_dirs=sample_dirs('init'))
             self.ood_results = {}
+        for r in (sample_recorders or {}).values():
+            r.reset()
         torch.set_rng_state(rng[0])
         if rng[1] is not None:
             torch.cuda.set_rng_state(rng[1], device)
@@ -463,9 +479,28 @@ class WIMJob(ClassificationVariationalNetwork):
         oodsets = [with_estimated(ood_.extract_subdataset(n, new_name=n)) for n in ood_sets]
         with torch.no_grad():
             res = self.ood_detection_rates(batch_size=test_batch_size, testset=testset, oodsets=oodsets, num_batch='all',
-                                           outputs=outputs, recorders={}, print_result='*')
+                                           outputs=outputs, recorders={}, print_result='*',
+                                           sample_recorders=sample_recorders, sample_dirs=sample_dirs())
         logging.info('misclassification_detection_rates with the `~` scores is outside this build: skipped')
         return res
+
+    def make_sample_recorders(self, names, batch_size):
+        """The sample recorders of the reference's `--inspection` switch (ft/__main__.py:208-221), one per name: `mu` and `y`,
+        plus `y_nearest` for a cvae, `batch_size` slots to begin with, with the auxiliary tensors `centroids` (the original
+        prior's means) and `alternate` (the first mean of the alternate prior)."""
+        from jvae_compat.recorders import SampleRecorder
+        fakes = dict(mu=torch.zeros(batch_size, self.latent_dim, device=self.device),
+                     y=torch.zeros(batch_size, dtype=torch.int64, device=self.device))
+        if self.is_cvae:
+            fakes['y_nearest'] = fakes['y']
+        if self._alternate_prior is None:
+            raise AttributeError('this model has no alternate prior yet (set_alternate_prior)')
+        out = {}
+        for n in names:
+            out[n] = r = SampleRecorder(batch_size, **fakes)
+            r.add_auxiliary(centroids=self._original_prior.mean.detach().clone(),
+                            alternate=self._alternate_prior.mean[0].detach().clone())
+        return out
 
     # ------------------------------------------------------------------------------------ persistence
     def save(self, *a, except_state=True, **kw):

@@ -137,6 +137,10 @@ _SIGS = {
     'jvae_cascade_mse_workspace_bytes': (c_size_t, [c_int, c_long, c_long]),
     'jvae_cascade_mse_f32': (c_int, [P, P, c_int, P, c_int, c_long, c_long, P, c_size_t, P]),
     'jvae_iterate_prior_f32': (c_int, [P, P, c_int, c_int, c_long, P]),
+    'jvae_latent_moments_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'jvae_latent_moments_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
+    'jvae_nearest_centroid_f32': (c_int, [P, P, P, P, c_long, c_int, c_int, P]),
+    'jvae_histogram_f32': (c_int, [P, P, P, P, P, c_long, c_int, c_int, P]),
 }
 
 

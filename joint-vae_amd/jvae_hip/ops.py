@@ -1765,6 +1765,110 @@ def iterate_prior(p):
     return post
 
 
+# ------------------------------------------------------------------------- latent-space inspection (csrc/inspect.hip)
+def latent_moments(mu, log_var, group, sums, counts):
+    """sums (G, 4, K) fp64 and counts (G,) int64, device accumulators of the caller, take this batch's per-group, per-dimension
+    sums of mu, mu^2, v and v^2 (v = exp(log_var) in fp32, widened) of the posterior mu, log_var (N, K) fp32 and the group sizes;
+    group (N,) int32 in [0, G) - anything else leaves the sample out - or None (G = 1).  Two launches (slabs of 256 rows, then their
+    fold in ascending order), no floating-point atomics: the same bits run to run whatever the device.  Nothing is
+    synchronised (reference module/sample.py::zsample with the class mask it forgets to apply)."""
+    mu, log_var = _c(_f32(mu, 'latent_moments')), _c(_f32(log_var, 'latent_moments'))
+    L.ptr(mu), L.ptr(log_var)
+    if mu.dim() != 2 or log_var.shape != mu.shape or sums.dim() != 3 or counts.dim() != 1 \
+            or tuple(sums.shape) != (counts.shape[0], 4, mu.shape[1]) or sums.dtype != torch.float64 \
+            or counts.dtype != torch.int64 or not sums.is_contiguous() or not counts.is_contiguous() \
+            or (group is None and counts.shape[0] != 1) \
+            or (group is not None and (group.dtype != torch.int32 or tuple(group.shape) != (mu.shape[0],))) \
+            or any(t.device != mu.device for t in (log_var, sums, counts) + (() if group is None else (group,))):
+        raise L.JvaeHipError('latent_moments: mu and log_var (N, K) fp32, group (N,) int32 (None: one group), sums (G, 4, K) fp64 '
+                             'and counts (G,) int64, dense and on one device, expected')
+    N, K = mu.shape
+    G = counts.shape[0]
+    if N == 0:
+        return sums, counts
+    lib = L.load()
+    nbytes = lib.jvae_latent_moments_workspace_bytes(N, K, G)
+    ws = L.workspace(nbytes + 8, mu.device)
+    off = (-ws.data_ptr()) % 8
+    L.check(lib.jvae_latent_moments_f32(L.ptr(mu), L.ptr(log_var), None if group is None else L.ptr(_c(group)), L.ptr(sums),
+                                        L.ptr(counts), N, K, G, ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()),
+            'jvae_latent_moments_f32')
+    return sums, counts
+
+
+def nearest_centroid(mu, centroids):
+    """mu (N, K), centroids (C, K) fp32 -> (y_nearest (N,) int64, d2 (N,) fp32): the centroid with the smallest squared distance
+    to each row and that distance (reference ft/inspection.py::estimate_y, which goes through an (N, C, K) temporary).  The
+    distances are summed and compared in fp64; ties go to the lowest index, as torch.argmin.  One launch, nothing synchronised."""
+    mu, centroids = _c(_f32(mu, 'nearest_centroid')), _c(_f32(centroids, 'nearest_centroid'))
+    L.ptr(mu), L.ptr(centroids)
+    if mu.dim() != 2 or centroids.dim() != 2 or centroids.shape[1] != mu.shape[1] or centroids.shape[0] < 1 or mu.shape[1] < 1 \
+            or centroids.device != mu.device:
+        raise L.JvaeHipError(f'nearest_centroid: mu (N, K) and centroids (C, K) on one device expected, got {tuple(mu.shape)} and '
+                             f'{tuple(centroids.shape)}')
+    N, K = mu.shape
+    y = torch.empty(N, dtype=torch.int64, device=mu.device)
+    d2 = torch.empty(N, dtype=torch.float32, device=mu.device)
+    if N:
+        L.check(L.load().jvae_nearest_centroid_f32(L.ptr(mu), L.ptr(centroids), L.ptr(y), L.ptr(d2), N, K, centroids.shape[0],
+                                                   L.stream_ptr()), 'jvae_nearest_centroid_f32')
+    return y, d2
+
+
+_hist_nonfinite = {}
+
+
+def histogram(values, edges, group=None, counts=None, G=None, check=False):
+    """Counts of `values` (n,) fp32 in the bins of `edges` (B + 1 ascending numbers: a numpy array or a sequence, checked and
+    uploaded as fp64; or an fp64 device tensor, taken as it is) -> counts (G, B) int64, added to when given.  Bin b holds
+    edges[b] <= x < edges[b + 1], the last bin is closed on the right, values outside [edges[0], edges[B]] are not counted:
+    np.histogram's rule, so that with edges = np.histogram_bin_edges(np.empty(0, np.float32), bins=B, range=(lo, hi)) the counts
+    are np.histogram(values, bins=B, range=(lo, hi))'s.  group (n,) int32 in [0, G) - anything else leaves the value out - or
+    None (G = 1); G is taken from `counts`, or given.  NaN and +-inf are not counted; their number goes to a device word that
+    `check=True` reads (a synchronisation) and turns into ValueError.  One launch; exact integer counts."""
+    values = _c(_f32(values, 'histogram')).reshape(-1)
+    L.ptr(values)
+    dev = values.device
+    if not torch.is_tensor(edges):
+        import numpy as np
+        e = np.asarray(edges, dtype=np.float64).reshape(-1)
+        if e.size < 2 or not np.all(np.isfinite(e)) or np.any(np.diff(e) < 0):
+            raise ValueError('histogram: at least two finite, ascending edges expected')
+        edges = torch.from_numpy(e).to(dev)
+    if edges.dtype != torch.float64 or edges.dim() != 1 or edges.shape[0] < 2 or edges.device != dev:
+        raise L.JvaeHipError('histogram: edges (B + 1,) fp64 on the device of the values expected')
+    B = edges.shape[0] - 1
+    if counts is None:
+        G = 1 if G is None else int(G)
+        if G < 1:
+            raise L.JvaeHipError('histogram: at least one group expected')
+        counts = torch.zeros((G, B), dtype=torch.int64, device=dev)
+    if counts.dtype != torch.int64 or counts.dim() != 2 or counts.shape[1] != B or counts.device != dev or not counts.is_contiguous() \
+            or (G is not None and counts.shape[0] != G) or (group is None and counts.shape[0] != 1) \
+            or (group is not None and (group.dtype != torch.int32 or tuple(group.shape) != (values.shape[0],) or group.device != dev)):
+        raise L.JvaeHipError('histogram: counts (G, B) int64 and group (n,) int32 (None: G = 1) on the device of the values expected')
+    key = (dev.index if dev.index is not None else torch.cuda.current_device())
+    word = _hist_nonfinite.get(key)
+    if word is None:
+        _hist_nonfinite[key] = word = torch.zeros(1, dtype=torch.int64, device=dev)
+    L.check(L.load().jvae_histogram_f32(L.ptr(values), L.ptr(_c(edges)), None if group is None else L.ptr(_c(group)), L.ptr(counts),
+                                        L.ptr(word), values.shape[0], B, counts.shape[0], L.stream_ptr()), 'jvae_histogram_f32')
+    if check:
+        histogram_check(dev)
+    return counts
+
+
+def histogram_check(device=None):
+    """Read (and clear) the non-finite word(s) of `histogram`: ValueError when a NaN or an infinity was met since the last check."""
+    for key, word in _hist_nonfinite.items():
+        if device is not None and device.index not in (None, key):
+            continue
+        bad = int(word[0])
+        if bad:
+            word.zero_()
+            raise ValueError(f'histogram: {bad} non-finite value(s) were met (they are in no bin)')
+
+
 def misclass_split(scores, mask):
     """(M, N) fp32 score rows and an (N,) mask (non-zero / True = correctly classified) -> ins (M, n_correct), outs
     (M, N - n_correct), n_correct: both row sets compacted in their original order by ONE scan of the mask (two views of one

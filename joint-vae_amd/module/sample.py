@@ -11,8 +11,14 @@ floor(clamp(255 v + 0.5, 0, 255))), written with the standard library alone (zli
 neither torchvision nor PIL is needed).  The prior branch draws and decodes through `net.generate()`, the `x` branch runs the
 label-free `net.evaluate(x[:N], None, z_output=True)` once.  `save=False` returns the list without touching the disk.
 
-Not rebuilt here, they stay in the reference: the command-line block, `zsample()` and `comparison()` (host-side plotting and
-dataset plumbing around evaluate(), nothing for a kernel to do).
+`zsample()` writes the per-dimension statistics of the posterior (`hist_var_z.dat`, `mu_z_var_z.dat`, and one pair per class)
+through the encode-only pass `net.latent_posterior()` - no image is decoded - and ONE `ops.latent_moments` launch pair per batch
+into fp64 device accumulators grouped by label; the only read-back is at the end.  Unlike the reference, whose per-class
+files repeat the all-sample statistics (it builds the class mask and never applies it), the per-class files hold the
+statistics of that class's samples.  `comparison()` returns the reference's (div, y_pred) dictionaries; every pair's mean
+squared difference of the mean reconstructions comes from one `ops.cascade_mse` call.
+
+Not rebuilt here, it stays in the reference: the command-line block.
 """
 import logging
 import os
@@ -142,3 +148,86 @@ def sample(net, x=None, y=None, root=os.path.join(DEFAULT_RESULTS_DIR, '%j', 'sa
                 f.write(image['tex'])
 
     return list_of_images
+
+
+def zsample(x, net, y=None, batch_size=128, root=os.path.join(DEFAULT_RESULTS_DIR, '%j', 'samples'), bins=10, directory='test'):
+    r"""Statistics of the posterior q(z|x) over a set (reference module/sample.py:176-233): per latent dimension the mean of
+    mu^2, the mean variance, their sum, the mean of mu and the unbiased std of the variance (`mu_z_var_z.dat`, rows sorted by the
+    first column, descending) and the histogram of the K mean variances over (0, max) (`hist_var_z.dat`); with `y`, the same
+    two files per class c (`hist_var_z<c>.dat`, `mu_z_var_z<c>.dat`) over that class's samples - no file for a class
+    without samples, `nan` in std_var_z for a class with one.  N is cut to a multiple of `batch_size`.
+
+    Per batch: `net.latent_posterior` (features and the two encoder heads: nothing is decoded), then `ops.latent_moments`
+    with group = y into (C + 1, 4, K) fp64 accumulators on the device (the last group takes labels outside [0, C)); they are
+    read once, at the end, and the all-sample statistics are the sum of the groups.  -> {'dir', 'sums' (C + 1, 4, K),
+    'counts' (C + 1,)} (the reference returns None)."""
+    from jvae_compat import inspection
+    N = len(x)
+    N -= N % batch_size
+    assert net.type != 'cvae' or y is not None
+    device = net.device
+    K = net.latent_dim
+    C = net.num_labels if y is not None else 0
+    sums = torch.zeros((C + 1, 4, K), dtype=torch.float64, device=device)
+    counts = torch.zeros(C + 1, dtype=torch.int64, device=device)
+    logging.debug('Computes mu_z var_z for {} samples'.format(N))
+    for start in range(0, N, batch_size):
+        xb = x[start:start + batch_size].to(device)
+        yb = None if y is None else y[start:start + batch_size].to(device)
+        mu, log_var = net.latent_posterior(xb, yb if net.y_is_coded else None)
+        group = None
+        if yb is not None:
+            group = torch.where((yb >= 0) & (yb < C), yb, torch.full_like(yb, C)).to(torch.int32)
+        ops.latent_moments(mu.reshape(-1, K), log_var.reshape(-1, K), group, sums, counts)
+    sums, counts = sums.cpu().numpy(), counts.cpu().numpy()              # the only read-back
+
+    dir_path = os.path.join(job_to_str(net.job_number, root), directory)
+    os.makedirs(dir_path, exist_ok=True)
+
+    def write(tag, s, n):
+        stats = inspection.per_dim_statistics(s, n)
+        with open(os.path.join(dir_path, f'hist_var_z{tag}.dat'), 'w') as f:
+            f.write(inspection.hist_text(*inspection.per_dim_hist(stats['mu_var_z'], bins=bins)))
+        with open(os.path.join(dir_path, f'mu_z_var_z{tag}.dat'), 'w') as f:
+            f.write(inspection.scatter_text(stats))
+
+    if counts.sum():
+        write('', sums.sum(0), counts.sum())
+    for c in range(C):
+        if counts[c]:
+            write(c, sums[c], counts[c])
+    return {'dir': dir_path, 'sums': sums, 'counts': counts}
+
+
+def comparison(x, *nets, batch_size=128, root=os.path.join(DEFAULT_RESULTS_DIR, '%j', 'samples'), directory='ood'):
+    r"""Comparison of different nets on the same inputs (reference module/sample.py:236-274) -> (div, y_pred):
+    div[j][jj], for the job numbers jj > j, is the (N,) mean squared difference between the mean reconstructions of the two
+    nets, y_pred[j] (N,) the classes net j predicts; N = len(x) cut to a multiple of the batch size, which is bounded by
+    every net's max_batch_sizes['test'].  All pairs come from ONE `ops.cascade_mse` call with the mean reconstructions as
+    one-draw stages (its rows against x itself are ignored).  Both dictionaries hold host tensors, as in the reference."""
+    root = root.replace('%j', '-'.join(str(n.job_number) for n in nets))
+    for n in nets:
+        batch_size = min(n.max_batch_sizes['test'], batch_size)
+    logging.info('Batch size for comparison: %s', batch_size)
+    N = x.shape[0] // batch_size * batch_size
+    jobs = [n.job_number for n in nets]
+    x_, y_pred = {}, {}
+    for n in nets:
+        reco, pred = [], []
+        for start in range(0, N, batch_size):
+            with torch.no_grad():
+                x__, logits, losses, _ = n.evaluate(x[start:start + batch_size].to(n.device))
+                pred.append(n.predict_after_evaluate(logits, losses))
+                reco.append(x__[0])
+        x_[n.job_number] = torch.cat(reco).unsqueeze(0).contiguous() if reco else None
+        y_pred[n.job_number] = torch.cat(pred).cpu() if pred else torch.zeros(0, dtype=torch.int64)
+    div = {j: {jj: torch.zeros(0) for jj in jobs if jj > j} for j in jobs}
+    if N:
+        x0 = x[:N].to(nets[0].device).contiguous()
+        mse = ops.cascade_mse(x0, [x_[j].to(x0.device) for j in jobs]).cpu()
+        for a, j in enumerate(jobs):
+            for b, jj in enumerate(jobs):
+                if jj > j:
+                    hi, lo = max(a, b) + 1, min(a, b) + 1          # stages of the two nets; stage 0 is x
+                    div[j][jj] = mse[hi * (hi - 1) // 2 + lo]
+    return div, y_pred

@@ -167,11 +167,17 @@ class ScoringMixin:
                 score_rows.roc_mode(m)
         return methods
 
-    def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False):
+    def _score_set(self, dset, methods, batch_size, num_batch, shuffle, recorder, sample_dirs, on_batch=None, keep_test=False,
+                   sample_recorder=None):
         """One pass over `dset` for ood_detection_rates: per batch the label-free evaluation (or the batch read back from a full
         recorder), then `score_rows.write_rows`: the score rows go straight into ONE preallocated (M, n) device buffer, one
         kernel launch per source tensor (the `SCORE_SET_TORCH_ROWS` by their torch expressions) - no value comes to the host
-        here.  on_batch(i, num_batch, scores_so_far) is called after each batch.  -> (M, n) fp32 device scores."""
+        here.  on_batch(i, num_batch, scores_so_far) is called after each batch.  -> (M, n) fp32 device scores.
+
+        `sample_recorder` (a jvae_compat.recorders.SampleRecorder, or None): every EVALUATED batch appends, of the keys the recorder
+        holds, `mu` (the posterior means of the same pass: no second one), `y` (the loader's labels) and `y_nearest` (argmin over
+        the classes of this batch's zdist); a set read back from a full LossRecorder appends nothing (cvae.py:1634-1642,1793-1795).
+        It is saved as samples-<set>.pth beside the loss record."""
         device = self.device
         name = getattr(dset, 'name', 'set')
         recorded = recorder is not None and len(recorder) >= num_batch
@@ -196,8 +202,13 @@ class ScoringMixin:
                     logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
                 else:
                     x, y = next(loader)[:2]
-                    x, logits, losses, measures = self._evaluate_for_scores(x, i, measures)
+                    if sample_recorder is None:
+                        x, logits, losses, measures = self._evaluate_for_scores(x, i, measures)
+                    else:
+                        x, logits, losses, measures, mu = self._evaluate_for_scores(x, i, measures, with_mu=True)
                     y = y.to(device)
+                    if sample_recorder is not None:
+                        sample_recorder.append_batch(**self._sample_record(sample_recorder, mu, y, losses))
                     if odin:
                         # cvae.py:1645-1663: the whole grid per batch (it is what the recorder holds), on the device
                         losses = dict(losses, **self.odin_scores(x))
@@ -225,7 +236,30 @@ class ScoringMixin:
             for d in sample_dirs:
                 os.makedirs(d, exist_ok=True)
                 recorder.save(os.path.join(d, 'record-{}.pth'.format(name)))
+        if sample_recorder is not None:
+            for d in sample_dirs:
+                os.makedirs(d, exist_ok=True)
+                sample_recorder.save(os.path.join(d, 'samples-{}.pth'.format(name)))
         return buf[:, :filled].contiguous()
+
+    @staticmethod
+    def _sample_record(recorder, mu, y, losses):
+        """What one evaluated batch appends to a sample recorder: the keys it holds among mu, y, y_nearest."""
+        keys = set(recorder.keys()) if len(recorder.keys()) else {'mu', 'y'}
+        unknown = keys - {'mu', 'y', 'y_nearest'}
+        if unknown:
+            raise KeyError('sample recorders hold mu, y and y_nearest, not ' + ', '.join(sorted(unknown)))
+        out = {}
+        if 'mu' in keys:
+            out['mu'] = mu
+        if 'y' in keys:
+            out['y'] = y
+        if 'y_nearest' in keys:
+            zdist = losses['zdist']
+            if zdist.dim() < 2:
+                raise ValueError('y_nearest needs a zdist with a class axis (a class-conditional prior evaluated without labels)')
+            out['y_nearest'] = zdist.argmin(0)
+        return out
 
     @staticmethod
     def _row_mean_std(scores):
@@ -255,11 +289,15 @@ class ScoringMixin:
         with the '-2s' suffix (two-sided around the mean) or, with `OOD_QUANTILE_METHODS`, the '-a-x-y' suffix (two-sided on
         in-score quantiles; ValueError below 4 in-distribution samples); see `_ood_methods` for the rest.  Named datasets
         (`testset=None` or a string, `oodsets=None`) and the registry lookup of earlier results (`from_where`) are host
-        plumbing outside this build, as for accuracy(); so are `sample_recorders`."""
+        plumbing outside this build, as for accuracy().
+
+        `sample_recorders` ({set name: SampleRecorder}): a set named there has the posterior means `mu`, the labels `y` and the
+        nearest class `y_nearest` of every evaluated batch appended (the keys the recorder holds; `_score_set`) and
+        `samples-<set>.pth` written into every `sample_dirs` entry.  The OOD sets get `y` and `y_nearest` as well when their
+        recorder holds them - the reference leaves zeros there (cvae.py:1793-1795 appends `mu` alone) and its ft/inspection.py
+        recomputes `y_nearest` from `mu`.  Empty or None: nothing changes, the same launches and the same results."""
         if testset is None or isinstance(testset, str) or oodsets is None or any(isinstance(o, str) for o in oodsets):
             raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
-        if sample_recorders:
-            raise NotImplementedError('sample_recorders are outside this build')
         if not method:
             return
         if epoch == 'last':
@@ -270,6 +308,7 @@ class ScoringMixin:
             from jvae_compat.recorders import LossRecorder
             recorders.update({n: LossRecorder(batch_size) for n in names})
         recorders = recorders or {}
+        sample_recorders = sample_recorders or {}
         ood_results = {n: {} for n in names[1:]}
         if not oodsets:
             return ood_results
@@ -300,7 +339,7 @@ class ScoringMixin:
 
         nb, shuffle = plan(testset)
         ind = self._score_set(testset, methods, batch_size, nb, shuffle, recorders.get(names[0]), sample_dirs, keep_test=True,
-                              on_batch=progress_line(names[0], lambda s: self._row_mean_std(s)[:, 0].tolist(),
+                              sample_recorder=sample_recorders.get(names[0]), on_batch=progress_line(names[0], lambda s: self._row_mean_std(s)[:, 0].tolist(),
                                                      lambda: {m: np.nan for m in methods}))
         for m in methods:
             if '-a-' in m and ind.shape[1] < 4:
@@ -330,7 +369,7 @@ class ScoringMixin:
 
             nb, shuffle = plan(oodset)
             scores = self._score_set(oodset, methods, batch_size, nb, shuffle, recorders.get(name), sample_dirs,
-                                     on_batch=progress_line(name, roc, fpr95))
+                                     sample_recorder=sample_recorders.get(name), on_batch=progress_line(name, roc, fpr95))
             if sink is None:                                  # with a sink the last batch's progress ROC is the final one
                 roc(scores)
             for m, h in zip(methods, last['host']):

@@ -493,6 +493,31 @@ int jvae_upsample_nearest_bwd_b8(const void* dy, void* dx, long blocks, int H, i
 int jvae_augment_u8_f32(const unsigned char* in, const unsigned char* flip, const int* dy, const int* dx,
                         float* out, int N, int C, int H, int W, int pad, int nhwc, void* stream);
 
+/* ---- device-resident image sets (csrc/imageset.hip, jvae_compat/torch_load.py): sample indices -> float32 NCHW batch + labels
+ * in ONE launch.  data: the whole set's raw uint8 images on the device, (n, Hs, Ws, Cs) or (n, Cs, Hs, Ws), Cs 1 or 3; idx: N
+ * int64 indices on the device, any order, repeats allowed, every one in [0, n) - the CALLER checks them, there is no trap in the
+ * kernel; y[i] = lut[targets[idx[i]]] (lut NULL: identity; the caller checks the targets against the table's length).
+ * desc: jvae_imageset_desc_words ints in HOST memory, the static chain of the set in the order of utils/torch_load.py:347-426:
+ *   [0] nhwc  [1] Hs  [2] Ws  [3] Cs
+ *   [4] A     quarter-turn/flip element, k + 4 f: k counter-clockwise quarter turns, then a horizontal flip when f
+ *   [5] resize (0 / 1)  [6] Hr  [7] Wr  [8] kh  [9] kv: PIL's 8-bit bilinear resampling, horizontal then vertical pass, the
+ *       intermediate rounded and clipped to uint8: clip8((2^21 + sum k v) >> 22), int32 sums; coef_h (Wr, kh) / coef_v (Hr, kv)
+ *       int32 22-bit fixed-point weights and bounds_h (Wr, 2) / bounds_v (Hr, 2) int32 (first source index, count <= ksize), all
+ *       on the device and checked by the caller against the extents after A; kh or kv above 8: -2 (JVAE_ENOTSUP)
+ *   [10] p0   zero padding on all four sides
+ *   [11] B    second quarter-turn/flip element
+ *   [12] g2c  one source channel repeated to 3 (Cs = 1)
+ *   [13] pa   edge padding of the random part: flip[i] (uint8), then crop at (dy[i], dx[i]) in [0, 2 pa] (int32) of the padded
+ *             image, exactly as jvae_augment_u8_f32; flip NULL: none, dy and dx NULL (both or neither): the centred crop
+ *   [14] post 0 none, 1 zero padding 2, 2 centre crop at offsets [15] oy, [16] ox
+ *   [17] C  [18] H  [19] W  the output extents; they must be what the chain gives, else -1 (JVAE_EINVAL)
+ * then (float)v / 255.0f; padded zeros are 0.0f.  x: float32 (N, C, H, W), y: int64 (N,).  Neither allocates nor synchronises. */
+int jvae_imageset_desc_words(void);
+int jvae_imageset_batch_u8_f32(const unsigned char* data, const long long* idx, const long long* targets, const long long* lut,
+                               const int* desc, const int* coef_h, const int* bounds_h, const int* coef_v, const int* bounds_v,
+                               const unsigned char* flip, const int* dy, const int* dx, float* x, long long* y, long n, int N,
+                               void* stream);
+
 /* ---- ROC of OOD scores: AUC and the FPR / thresholds at kept TPRs (csrc/roc.hip) -----------------------------------
  * Replaces utils/roc_curves.py:38-210 (roc_curve, a Python loop over every in-distribution score) as
  * ood_detection_rates calls it per method and OOD set (cvae.py:1843-1868), for M score rows in one call.

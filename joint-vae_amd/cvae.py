@@ -18,6 +18,9 @@ ood_detection_rates() and misclassification_detection_rates() are built (module/
 images decoded from draws of the prior (module/sample.py builds the reference's grids of them).
 latent_posterior(x, y) is the encode-only pass (mu, log_var bit for bit evaluate()'s, nothing decoded) under module.sample.zsample();
 the sample recorders of ood_detection_rates() write the reference's samples-<set>.pth.
+Named data sets ('cifar10-3', 'mnist32r', 'svhn', ...: jvae_compat/torch_load.py, device-resident sets whose batches are one
+launch of csrc/imageset.hip) are an opt-in, `DATA_ROOT` (class attribute, settable per instance: the torchvision-style directory
+of the raw files); None, the default, keeps every refusal of a name as it was.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -1464,8 +1467,9 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         `trainset` is a map-style dataset of (image, int label) - what utils/torch_load.get_dataset() returns (train.py:236-243
         hands it over with `.name`, `.transformer` and, for the torchvision sets, the raw images in `.data` / `.targets`), or any
         torch Dataset: float tensors in [0,1] shaped like `input_shape`, or RAW uint8 images ((H,W,C) or (C,H,W)), which are
-        converted - and augmented - on the device.  Named datasets (a string) are the reference's torchvision plumbing and
-        outside this build.
+        converted - and augmented - on the device.  A name (a string; None on resume: the recorded set) is opened from
+        `DATA_ROOT` as a device-resident set when that attribute is set (jvae_compat/torch_load.py; the test split too when no
+        `testset` is given, cvae.py:2160-2162), and refused when it is None, the default.
 
         What the reference does and this does too (same order):
         * `training_parameters` gets `epochs`, and - for an untrained net only - `set` (trainset.name), `transformer`
@@ -1486,7 +1490,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         `ood_results[epoch]` (`ood.json` in `save()`), `record-<set>.pth` / `record-<oodset>.pth` under `save_dir/samples/{last,
         <epoch>}` (the directories are then made on OOD epochs too); the `accuracy(testset)` of the same epoch reads the test
         set's full recorder back instead of evaluating again.  The same call runs once more after the loop, before the final
-        accuracy pass, unless a signal above 1 came in.  OOD sets given by name raise NotImplementedError, as elsewhere;
+        accuracy pass, unless a signal above 1 came in.  OOD sets given by name raise NotImplementedError unless `DATA_ROOT` is set, as elsewhere;
         `sample_recorders` stay outside this build.
 
         data_augmentation: the reference hands the list to its dataset factory, which prepends RandomHorizontalFlip ('flip')
@@ -1501,8 +1505,13 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         losses the reference prints (cvae.py:2463-2479), refreshed from the device every `report_every` batches (extra
         keyword) so that the loop does not synchronise per batch.  The batch size is clamped to `max_batch_sizes['train']`."""
         if isinstance(trainset, str):
-            raise NotImplementedError('named torchvision datasets are host-side plumbing outside this build: '
-                                      'pass a torch.utils.data.Dataset')
+            if self.DATA_ROOT is None:
+                raise NotImplementedError('named torchvision datasets are host-side plumbing outside this build: '
+                                          'pass a torch.utils.data.Dataset')
+            opened = self._open_named(trainset, 'train', transformer or 'default')      # cvae.py:2160-2162
+            if testset is None:
+                testset = self._open_named(trainset, 'test', opened.transformer)
+            trainset = opened
         if epochs:
             self.training_parameters['epochs'] = epochs
         set_name = None
@@ -1530,8 +1539,12 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             self.training_parameters['set'] = set_name        # a resumed job whose record lacks the key (written before round 5)
         set_name = str(self.training_parameters['set'])
         if trainset is None:
-            raise NotImplementedError('re-opening the recorded set {!r} by name is torchvision plumbing outside this build: '
-                                      'pass the dataset (train.py:224-226 does)'.format(set_name))
+            if self.DATA_ROOT is None:
+                raise NotImplementedError('re-opening the recorded set {!r} by name is torchvision plumbing outside this build: '
+                                          'pass the dataset (train.py:224-226 does)'.format(set_name))
+            trainset = self._open_named(set_name, 'train')
+            if testset is None:
+                testset = self._open_named(set_name, 'test')
         data_augmentation = list(self.training_parameters.get('data_augmentation') or [])
         full_test_every = self.training_parameters.get('full_test_every', 10)
         unknown = [t for t in data_augmentation if t not in ('flip', 'crop')]
@@ -1574,7 +1587,9 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         ood_phase = bool(self.TRAIN_OOD_PHASE) and bool(oodsets)
         if ood_phase:
             if testset is None or isinstance(testset, str) or any(isinstance(o, str) for o in oodsets):
-                raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
+                if self.DATA_ROOT is None:
+                    raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
+                testset, oodsets = self._open_named_sets(testset, oodsets)
             for o in oodsets:                                             # cvae.py:2226-2232: one recorder per OOD set
                 recorders[getattr(o, 'name', 'set')] = LossRecorder(test_batch_size)
         elif oodsets:
@@ -1722,6 +1737,11 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             def __iter__(self):
                 for item in self.loader:
                     yield self.convert(item)
+        from jvae_compat import torch_load
+        resident = torch_load.device_loader(trainset, batch_size, True, data_augmentation,
+                                            getattr(self, 'augmentation_generator', None))
+        if resident is not None:                 # a device-resident set: gathered, transformed and augmented in one launch
+            return Batches(resident, lambda b: (b[0].to(device), b[1].to(device)))
         probe = trainset[0][0] if len(trainset) else None
         is_raw = torch.is_tensor(probe) and probe.dtype == torch.uint8
         if is_raw or not data_augmentation or probe is None:

@@ -370,7 +370,8 @@ class WIMJob(ClassificationVariationalNetwork):
         The scoring passes re-seed torch for their recorders; the generator states found at the call are put back before the
         first epoch, so `torch.manual_seed(s)` in front of finetune() fixes the loaders' order and the noise of the epochs.
         `on_batch(epoch, batch, in_loss, mix_loss, tags)` is called after each step with that step's loss dictionaries.
-        `trained` is left as found, as in the reference.  Named data sets raise NotImplementedError; see DESIGN.md for what
+        `trained` is left as found, as in the reference.  Named data sets (names, or None for the recorded set) are opened from
+        `DATA_ROOT` when it is set and raise NotImplementedError when it is None; see DESIGN.md for what
         else of the reference's loop is outside this build.
 
         `sample_recorders` ({set name: SampleRecorder}, see `make_sample_recorders`): the latent records of the reference's
@@ -380,8 +381,17 @@ class WIMJob(ClassificationVariationalNetwork):
         hold the records of the pass after tuning.  They change nothing else: the same launches of the loop, the same parameters."""
         named = [s for s in (trainset, ind_set) if isinstance(s, str) or s is None]
         if named or not isinstance(ood_sets, dict) or any(isinstance(s, str) for s in ood_sets.values()):
-            raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets '
-                                      '(ood_sets: a dict of name -> Dataset)')
+            if self.DATA_ROOT is None:
+                raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets '
+                                          '(ood_sets: a dict of name -> Dataset)')
+            if trainset is None or isinstance(trainset, str):
+                trainset = self._open_named(trainset, 'train')
+            if ind_set is None or isinstance(ind_set, str):
+                ind_set = self._open_named(ind_set)
+            if not isinstance(ood_sets, dict):   # names (ft/job.py hands over a list of them)
+                ood_sets = {str(getattr(s, 'name', s)): s for s in ood_sets}
+            ood_sets = {n: self._open_named(s, transformer=ind_set.transformer) if isinstance(s, str) else s
+                        for n, s in ood_sets.items()}
         optimizer = self.optimizer if optimizer is None else optimizer
         batch_size = int(batch_size or self.training_parameters['batch_size'])
         testset_name = testset_name or getattr(ind_set, 'name', None) or self.training_parameters.get('set') or 'ind'

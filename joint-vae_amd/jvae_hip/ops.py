@@ -1995,4 +1995,89 @@ def draw_augmentation(N, pad, device, generator=None, flip=True, crop=True):
     return f, dy, dx
 
 
+
+# ------------------------------------------------------------------------------------------- device-resident image sets
+class ImagesetDesc:
+    """Static transform chain of a device-resident image set (csrc/imageset.hip; the slots of include/jvae_hip.h), checked on
+    the host ONCE so that no launch can read outside an image: extents through every stage, the resize tables against the
+    extents they index.  `source` = (Hs, Ws, Cs); A, B = quarter-turn/flip elements k + 4 f; resize = None or (Hr, Wr, coef_h,
+    bounds_h, coef_v, bounds_v) with the int32 CPU tables of jvae_compat.torch_load.pil_bilinear_tables; post = None | 'pad' |
+    ('crop', th, tw).  `.shape` is the (C, H, W) of the batches; `.with_pa(pa)` is the same chain with the random crop's padding."""
+
+    def __init__(self, source, nhwc, A=0, resize=None, p0=0, B=0, g2c=False, pa=0, post=None, device=None):
+        Hs, Ws, Cs = (int(v) for v in source)
+        if Cs not in (1, 3) or Hs < 1 or Ws < 1 or not 0 <= A < 8 or not 0 <= B < 8 or p0 < 0 or pa < 0 or (g2c and Cs != 1):
+            raise ValueError(f'imageset chain: source {source}, A={A}, B={B}, p0={p0}, pa={pa}, g2c={g2c}')
+        H, W = (Ws, Hs) if A & 1 else (Hs, Ws)
+        self.tables = (None,) * 4
+        rs = [0, 0, 0, 0, 0]
+        if resize is not None:
+            Hr, Wr, ch, bh, cv, bv = resize
+            for name, coef, bnd, out, size in (('horizontal', ch, bh, Wr, W), ('vertical', cv, bv, Hr, H)):
+                coef, bnd = torch.as_tensor(coef), torch.as_tensor(bnd)
+                ok = (coef.dtype == bnd.dtype == torch.int32 and coef.dim() == 2 and tuple(bnd.shape) == (out, 2)
+                      and coef.shape[0] == out and int(bnd.min()) >= 0 and int(bnd[:, 1].max()) <= coef.shape[1]
+                      and int((bnd[:, 0] + bnd[:, 1]).max()) <= size and int(coef.min()) >= 0)
+                if not ok:
+                    raise ValueError(f'imageset chain: the {name} resize tables do not fit {size} -> {out}')
+            rs = [1, int(Hr), int(Wr), int(ch.shape[1]), int(cv.shape[1])]
+            self.tables = tuple(_c(torch.as_tensor(t).to(device)) for t in (ch, bh, cv, bv))
+            H, W = int(Hr), int(Wr)
+        H, W = H + 2 * p0, W + 2 * p0
+        if B & 1:
+            H, W = W, H
+        oy = ox = 0
+        if post == 'pad':
+            kind, H, W = 1, H + 4, W + 4
+        elif post:
+            _, th, tw = post
+            if th > H or tw > W:
+                raise ValueError(f'imageset chain: centre crop to ({th}, {tw}) of a ({H}, {W}) image')
+            kind, oy, ox, H, W = 2, int(round((H - th) / 2.)), int(round((W - tw) / 2.)), int(th), int(tw)
+        else:
+            kind = 0
+        self.shape = (3 if g2c else Cs, H, W)
+        self.source, self.nhwc, self.pa = (Hs, Ws, Cs), bool(nhwc), int(pa)
+        self._args = dict(source=source, nhwc=nhwc, A=A, resize=resize, p0=p0, B=B, g2c=g2c, post=post, device=device)
+        words = [int(bool(nhwc)), Hs, Ws, Cs, int(A)] + rs + [int(p0), int(B), int(bool(g2c)), int(pa), kind, oy, ox, *self.shape]
+        assert len(words) == L.load().jvae_imageset_desc_words()
+        self.words = (ctypes.c_int * len(words))(*words)
+        self._pads = {self.pa: self}
+
+    def with_pa(self, pa):
+        d = self._pads.get(int(pa))
+        if d is None:
+            self._pads[int(pa)] = d = ImagesetDesc(pa=int(pa), **self._args)
+            d._pads = self._pads
+        return d
+
+
+def imageset_batch(data, idx, desc, targets, lut=None, flip=None, dy=None, dx=None):
+    """-> (x float32 (N, C, H, W), y int64 (N,)): images data[idx] of a device-resident uint8 set through the static chain
+    `desc` (an ImagesetDesc) and, where given, the random flip / crop decisions of `draw_augmentation`; y = lut[targets[idx]]
+    (lut None: identity).  `idx`: int64 on the device, every entry in [0, len(data)) - checked by the caller
+    (DeviceImageSet.batch does it on the host before the upload), the kernel has no trap.  Does not synchronise."""
+    if data.dtype != torch.uint8 or data.dim() != 4 or idx.dtype != torch.int64 or targets.dtype != torch.int64 or (
+            lut is not None and lut.dtype != torch.int64):
+        raise L.JvaeHipError('imageset_batch: data uint8 (n, ., ., .), idx / targets / lut int64')
+    Hs, Ws, Cs = desc.source
+    if tuple(data.shape[1:]) != ((Hs, Ws, Cs) if desc.nhwc else (Cs, Hs, Ws)) or targets.numel() != data.shape[0]:
+        raise L.JvaeHipError(f'imageset_batch: data {tuple(data.shape)} / {targets.numel()} targets against the chain of {desc.source}')
+    data, idx, targets = _c(data), _c(idx), _c(targets)
+    N = idx.numel()
+    x = torch.empty((N, *desc.shape), device=data.device, dtype=torch.float32)
+    y = torch.empty((N,), device=data.device, dtype=torch.int64)
+    f = None if flip is None else _c(flip.to(torch.uint8))
+    a = None if dy is None else _c(dy.to(torch.int32))
+    b = None if dx is None else _c(dx.to(torch.int32))
+    for t in (f, a, b):
+        if t is not None and t.numel() != N:
+            raise L.JvaeHipError('imageset_batch: one flip / dy / dx decision per index')
+    rc = L.load().jvae_imageset_batch_u8_f32(L.ptr(data), L.ptr(idx), L.ptr(targets), L.ptr(None if lut is None else _c(lut)),
+                                             desc.words, *(L.ptr(t) for t in desc.tables), L.ptr(f), L.ptr(a), L.ptr(b),
+                                             L.ptr(x), L.ptr(y), data.shape[0], N, L.stream_ptr())
+    L.check(rc, 'jvae_imageset_batch_u8_f32')
+    return x, y
+
+
 from . import ops_b8 as _b8  # noqa: E402  (the B8 layout; it builds on the fp32 wrappers above)

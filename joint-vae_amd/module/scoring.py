@@ -45,6 +45,43 @@ class ScoringMixin:
                                     wim_status=self._wim_status_word)
         return {m: v.cpu() if to_cpu else v for m, v in zip(methods, got)}
 
+    # Named data sets ('cifar10-3', 'mnist32r', ...; jvae_compat/torch_load.py) are an opt-in: the torchvision-style directory
+    # their raw files are read from.  None (the default): a name, or a set left out, raises NotImplementedError as it always did.
+    DATA_ROOT = None
+
+    def _open_named(self, name=None, split='test', transformer=None, data_augmentation=()):
+        """One split of the named set (None: the recorded training set, with its recorded transformer) from `DATA_ROOT`, on the
+        model's device (cvae.py:1208-1212,1473-1477)."""
+        from jvae_compat import torch_load
+        if transformer is None:
+            transformer = self.training_parameters.get('transformer')
+        if transformer is None:
+            transformer = 'default'
+        return torch_load.open_named(name or self.training_parameters['set'], transformer, self.DATA_ROOT, self.device, split,
+                                     data_augmentation)
+
+    def _open_named_sets(self, testset, oodsets):
+        """ood_detection_rates' sets by name: the test set as in accuracy(); `oodsets=None` = the same-size siblings of the test
+        set that can be opened (cvae.py:1486-1488), a name in the list = that set (FileNotFoundError when it is not there)."""
+        from jvae_compat import torch_load
+        if testset is None or isinstance(testset, str):
+            testset = self._open_named(testset)
+        if oodsets is None:
+            oodsets = torch_load.open_siblings(testset, self.DATA_ROOT, self.device)
+        else:
+            transformer = getattr(testset, 'transformer', None)
+            oodsets = [self._open_named(o, transformer=transformer) if isinstance(o, str) else o for o in oodsets]
+        return testset, oodsets
+
+    def _batch_source(self, dset, batch_size, shuffle):
+        """The batches of an evaluation pass: device batches straight from a device-resident set (jvae_compat.torch_load
+        .device_loader: float32, on the device, same sample order and generator use), else the DataLoader of cvae.py:1245."""
+        from jvae_compat import torch_load
+        batches = torch_load.device_loader(dset, batch_size, shuffle)
+        if batches is not None:
+            return batches
+        return torch.utils.data.DataLoader(dset, batch_size=batch_size, num_workers=0, shuffle=shuffle)
+
     def accuracy(self, testset=None, batch_size=100, num_batch='all', method='all', print_result=False,
                  update_self_testing=True, outputs=None, sample_dirs=[], recorder=None, epoch='last', from_where='all',
                  epoch_tolerance=0, log=True):
@@ -53,10 +90,13 @@ class ScoringMixin:
         (all-class losses, `iws`: SURVEY.md §8f-1); with a `LossRecorder` the per-sample losses, `logits.T` and the labels are
         recorded batch by batch and written as `record-<set>.pth` into `sample_dirs` (the files test.py / results/ of the
         reference read, §8f-3) - or, if the recorder already holds the batches, the losses are RECOVERED from it instead of
-        being computed.  Named torchvision datasets and the registry lookup of earlier results (`from_where`) are host-side
-        plumbing outside this build: pass the dataset."""
+        being computed.  `testset=None` (the recorded training set's test split) or a name is resolved from `DATA_ROOT` when that
+        is set (jvae_compat/torch_load.py), else refused; a device-resident set is read through `device_loader`, one launch per
+        batch.  The registry lookup of earlier results (`from_where`) is host-side plumbing outside this build."""
         if testset is None or isinstance(testset, str):
-            raise NotImplementedError('named torchvision datasets are outside this build: pass a torch.utils.data.Dataset')
+            if self.DATA_ROOT is None:
+                raise NotImplementedError('named torchvision datasets are outside this build: pass a torch.utils.data.Dataset')
+            testset = self._open_named(testset)
         name = getattr(testset, 'name', 'testset')
         only_one = isinstance(method, str) and method != 'all'
         methods = list(self.predict_methods) if method == 'all' else ([method] if only_one else list(method))
@@ -77,7 +117,7 @@ class ScoringMixin:
         device = self.device
         was_training = self.training
         self.eval()
-        loader = iter(torch.utils.data.DataLoader(testset, batch_size=batch_size, num_workers=0, shuffle=shuffle))
+        loader = iter(self._batch_source(testset, batch_size, shuffle))
         errors = torch.zeros(len(methods), device=device)
         sums, n, measures, t0 = {}, 0, None, time.time()
         with torch.no_grad():
@@ -189,7 +229,7 @@ class ScoringMixin:
             recorder.num_batch = num_batch
         if recorder is not None:
             recorder.init_seed_for_dataloader()
-        loader = None if recorded else iter(torch.utils.data.DataLoader(dset, batch_size=batch_size, num_workers=0, shuffle=shuffle))
+        loader = None if recorded else iter(self._batch_source(dset, batch_size, shuffle))
         buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
         filled, sums, measures = 0, {}, None
         odin = any(m.startswith('odin') for m in methods)
@@ -288,8 +328,9 @@ class ScoringMixin:
         (the reference stores list(dict), i.e. the two key names).  Methods: what `batch_dist_measures` computes, one-sided,
         with the '-2s' suffix (two-sided around the mean) or, with `OOD_QUANTILE_METHODS`, the '-a-x-y' suffix (two-sided on
         in-score quantiles; ValueError below 4 in-distribution samples); see `_ood_methods` for the rest.  Named datasets
-        (`testset=None` or a string, `oodsets=None`) and the registry lookup of earlier results (`from_where`) are host
-        plumbing outside this build, as for accuracy().
+        (`testset=None` or a string, `oodsets=None` = the same-size siblings of the test set that can be opened, or names) are
+        resolved from `DATA_ROOT` when that is set, else refused, as for accuracy(); the registry lookup of earlier results
+        (`from_where`) is host plumbing outside this build.
 
         `sample_recorders` ({set name: SampleRecorder}): a set named there has the posterior means `mu`, the labels `y` and the
         nearest class `y_nearest` of every evaluated batch appended (the keys the recorder holds; `_score_set`) and
@@ -297,7 +338,9 @@ class ScoringMixin:
         recorder holds them - the reference leaves zeros there (cvae.py:1793-1795 appends `mu` alone) and its ft/inspection.py
         recomputes `y_nearest` from `mu`.  Empty or None: nothing changes, the same launches and the same results."""
         if testset is None or isinstance(testset, str) or oodsets is None or any(isinstance(o, str) for o in oodsets):
-            raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
+            if self.DATA_ROOT is None:
+                raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
+            testset, oodsets = self._open_named_sets(testset, oodsets)
         if not method:
             return
         if epoch == 'last':

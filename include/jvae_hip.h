@@ -518,6 +518,26 @@ int jvae_imageset_batch_u8_f32(const unsigned char* data, const long long* idx, 
                                const unsigned char* flip, const int* dy, const int* dx, float* x, long long* y, long n, int N,
                                void* stream);
 
+/* ---- mixed batches (the moving sets of jvae_compat/ft_datasets.py): N images taken from SEVERAL resident sets, and from the
+ * synthetic const / uniform sets, in ONE launch.  One record per leaf (jvae_imageset_mix_leaf_bytes bytes each), the same
+ * array in host memory (checked here, before the launch) and on the device (read by the kernel):
+ *   int kind (0 image set, 1 const, 2 uniform); int border (synthetic leaves: zero border of 2, the 'pad' transformer);
+ *   seven device pointers: data, targets, lut (or NULL), coef_h, bounds_h, coef_v, bounds_v (NULL without a resize);
+ *   the leaf's jvae_imageset_desc_words descriptor words, [13] pa = 0 (a mixed batch has no random part); a synthetic leaf
+ *   sets only [17..19].  Every leaf must end in the same (C, H, W), else -1 (JVAE_EINVAL).
+ * leaf (int32), index, tag (int64): per item of the resolved set, on the device, the number of its leaf, the sample inside
+ * that leaf and its class position; pos: N int64 positions into these arrays, on the device.  The CALLER checks pos against
+ * the arrays' length, leaf against n_leaves and index against the leaf's length: there is no trap in the kernel.
+ * x[i] = image index[pos[i]] of leaf leaf[pos[i]] through that leaf's chain (the resize is chosen per image), tagout[i] =
+ * tag[pos[i]], y[i] = lut[targets[index[pos[i]]]] of the leaf (0 for a synthetic leaf).  Synthetic leaves take their values
+ * from u, float32 on the device drawn by the caller: u_dims 2 = (N, C), const leaves only, x[i, c, :, :] = u[i, c];
+ * u_dims 4 = (N, C, H, W), x[i] = u[i] for a uniform leaf and u[i, c, 0, 0] for a const one; NULL when there is no synthetic
+ * leaf.  vec: consecutive x per thread, 1 or 4 (W a multiple of it), 0 = the default.  Neither allocates nor synchronises. */
+int jvae_imageset_mix_leaf_bytes(void);
+int jvae_imageset_mixed_u8_f32(const void* leaves_host, const void* leaves_dev, int n_leaves, const int* leaf,
+                               const long long* index, const long long* tag, const long long* pos, const float* u, int u_dims,
+                               float* x, long long* tagout, long long* y, int N, int vec, void* stream);
+
 /* ---- ROC of OOD scores: AUC and the FPR / thresholds at kept TPRs (csrc/roc.hip) -----------------------------------
  * Replaces utils/roc_curves.py:38-210 (roc_curve, a Python loop over every in-distribution score) as
  * ood_detection_rates calls it per method and OOD set (cvae.py:1843-1868), for M score rows in one call.

@@ -2,6 +2,8 @@
 torchvision): `get_dataset('cifar10-3')` reads the raw files torchvision leaves on disk, keeps the uint8 images and labels
 on the GPU and hands out `DeviceImageSet`s whose batches come from ONE kernel launch (`ops.imageset_batch`,
 csrc/imageset.hip) - gather by sample index, the set's static transform chain, the random flip / crop when asked, /255.
+`mixed_loader` does the same for a moving set of jvae_compat/ft_datasets.py, whose batches mix several resident sets:
+`ops.imageset_mixed_batch`, one launch per batch as well.
 
 The static chain has eight fixed slots, in the reference's order (utils/torch_load.py:347-426):
     A (quarter turns / flip) -> resize (PIL 8-bit bilinear) -> zero padding -> B (quarter turns / flip) -> g2c
@@ -530,16 +532,78 @@ class DeviceBatches:
 
 
 def device_loader(dset, batch_size, shuffle, data_augmentation=(), generator=None):
-    """DeviceBatches over `dset` if it is a DeviceImageSet or a chain of torch Subsets over one (the seeded random_split of
-    train_model), else None: the caller keeps its DataLoader."""
+    """DeviceBatches over `dset` if it is a DeviceImageSet behind any chain of torch Subsets (the seeded random_split of
+    train_model), `SubSampledDataset`s over one set and `NamedView`s (the sub-sets the fine-tuning loop scores), the indices
+    composed on the host; else None: the caller keeps its DataLoader."""
+    from jvae_compat.ft_datasets import NamedView, SubSampledDataset
     base, indices = dset, None
-    while isinstance(base, torch.utils.data.Subset):
-        idx = torch.as_tensor(base.indices, dtype=torch.int64)
+    while True:
+        if isinstance(base, torch.utils.data.Subset):
+            idx, base = torch.as_tensor(base.indices, dtype=torch.int64), base.dataset
+        elif isinstance(base, NamedView):
+            base = base.dataset
+            continue
+        elif isinstance(base, SubSampledDataset):
+            leaves, _, index, _ = base.resolve()
+            if len(leaves) != 1 or hasattr(base._source, 'resolve'):     # over a mixture the items are (x, tag), not (x, y)
+                return None
+            idx, base = torch.tensor(index), leaves[0]
+        else:
+            break
         indices = idx if indices is None else idx[indices]
-        base = base.dataset
     if not isinstance(base, DeviceImageSet):
         return None
     return DeviceBatches(base, indices, batch_size, shuffle, data_augmentation, generator)
+
+
+class MixedBatches:
+    """Re-iterable of the (x, tag) device batches of a resolved moving set (`SubSampledDataset` / `MixtureDataset` of
+    jvae_compat.ft_datasets) whose leaves are all resident on one device: ONE launch per batch (`ops.imageset_mixed_batch`)
+    whatever the number of sets, layouts and chains in it, plus one torch.rand when a synthetic leaf is in the set.  The index
+    batches come from a DataLoader over the bare positions, as in `DeviceBatches`.  The table on the device is built again when
+    the set was shrunk, barred or moved since the last epoch."""
+
+    def __init__(self, moving_set, device, batch_size, shuffle, drop_last):
+        self.moving_set, self.device, self.table = moving_set, device, None
+        self.loader = torch.utils.data.DataLoader(_Indices(len(moving_set)), batch_size=batch_size, shuffle=shuffle,
+                                                  drop_last=drop_last, num_workers=0)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        resolved = self.moving_set.resolve()
+        if self.table is None or not self.table.matches(*resolved):
+            self.table = ops.ImagesetMixTable(*resolved, self.device)
+            if self.table.n_items != self.loader.dataset.n:
+                raise RuntimeError('{}: {} items, the loader was made for {}'.format(
+                    getattr(self.moving_set, 'name', 'moving set'), self.table.n_items, self.loader.dataset.n))
+        table = self.table
+        C, H, W = table.shape
+        for idx in self.loader:
+            n = idx.numel()
+            if n and (int(idx.min()) < 0 or int(idx.max()) >= table.n_items):
+                raise IndexError('position out of range for the {} items of the moving set'.format(table.n_items))
+            u = None
+            if table.u_dims:
+                u = torch.rand((n, C) if table.u_dims == 2 else (n, C, H, W), device=self.device)
+            x, tag, _ = ops.imageset_mixed_batch(table, idx.to(self.device), u)
+            yield x, tag
+
+
+def mixed_loader(moving_set, batch_size, shuffle, drop_last):
+    """MixedBatches over `moving_set` when it resolves (`resolve()`) to DeviceImageSets / SyntheticImageSets that are all on one
+    device, else None: the caller keeps its DataLoader.  Sample order and use of the global generator are those of a DataLoader
+    over the set itself; the images are too unless a synthetic leaf is in the set (its noise is drawn per batch, not per item)."""
+    if not hasattr(moving_set, 'resolve'):
+        return None
+    leaves = moving_set.resolve()[0]
+    if not leaves or not all(isinstance(l, DeviceImageSet) for l in leaves):
+        return None
+    devices = {l.device for l in leaves}
+    if len(devices) != 1 or next(iter(devices)).type == 'cpu':
+        return None
+    return MixedBatches(moving_set, next(iter(devices)), batch_size, shuffle, drop_last)
 
 
 def open_named(name, transformer, root, device, split='test', data_augmentation=()):

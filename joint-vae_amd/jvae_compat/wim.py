@@ -19,8 +19,9 @@ evaluation under BOTH priors and the scores read from it (`k~`, `softk~`, `k@`, 
     images, 6.52 ms against 8.01 ms at 512 + 512.  The printed losses are tallied per group on the device (`ops.group_tally`).
 
 Data sets yield `((x, y_est), y)` items, as the reference's `EstimatedLabelsDataset` does (`EstimatedLabelsDataset` below).
-Seeded sub-sampling and padding of the moving set, sample recorders, POSCOD and job arrays stay in the reference's `ft/`
-package: see DESIGN.md section 7d.
+`finetune(moving_size=...)` builds the reference's seeded, padded moving set (jvae_compat/ft_datasets.py) and reads its mixed
+batches with one launch each (`torch_load.mixed_loader`).  The `_generalize` switch, POSCOD and job arrays
+stay in the reference's `ft/` package: see DESIGN.md section 7d.
 """
 import json
 import logging
@@ -31,7 +32,7 @@ from contextlib import contextmanager
 import torch
 
 from cvae import ClassificationVariationalNetwork, _mean_over_draws
-from jvae_compat.ft_datasets import MovingSet, finetune_schedule
+from jvae_compat.ft_datasets import MovingSet, create_moving_set, finetune_schedule
 from jvae_compat.recorders import LossRecorder
 from jvae_hip import ops
 from module.priors import build_prior
@@ -355,7 +356,8 @@ class WIMJob(ClassificationVariationalNetwork):
 
     def finetune(self, trainset, ind_set, ood_sets, *, train_size=100000, epochs=None, batch_size=None, test_batch_size=8192,
                  optimizer=None, outputs=None, alpha=0.1, report_every=10, testset_name=None, on_batch=None,
-                 sample_recorders=None):
+                 sample_recorders=None, moving_size=None, ood_mix=0.5, padding=0., padding_sets=None, mix_padding=0., seed=0,
+                 task=0):
         """The WIM fine-tuning loop (ft/job.py:170-478) over data-set objects: `trainset` yields the labelled (x, y) batches,
         `ind_set` and the sets of `ood_sets` (name -> data set) make the `MovingSet` the alternate prior pulls on.
 
@@ -373,6 +375,17 @@ class WIMJob(ClassificationVariationalNetwork):
         `trained` is left as found, as in the reference.  Named data sets (names, or None for the recorded set) are opened from
         `DATA_ROOT` when it is set and raise NotImplementedError when it is None; see DESIGN.md for what
         else of the reference's loop is outside this build.
+
+        `moving_size` given: the moving set is the reference's seeded one, `create_moving_set(ind_set, ood_sets, padding_sets,
+        moving_size, ood_mix, padding, mix_padding, seed, task)` (jvae_compat/ft_datasets.py) with classes 'ood', 'ind', 'pad'
+        (padding > 0) and 'padmix' (mix_padding > 0).  `padding_sets`: a dict name -> data set or name, or a list of them (names
+        are opened from `DATA_ROOT`; 'uniform' / 'const' = that sibling of the model's set); empty with padding > 0 = the
+        `uniform*` and `const*` siblings of the model's set, as in ft/job.py:225-231.  `ft_params`
+        records moving_size - reduced to len(moving set) // (1 + padding + mix_padding) when that is smaller (ft/job.py:264-267)
+        - padding, padding_sets, mix_padding and mix = the share of class 'ood'.  A sample's tally group is 'ind' for class
+        'ind' and 'ood' for every other class (ft/job.py:374-375).  When every set of the moving set is resident on the device
+        its batches come from `torch_load.mixed_loader`, one launch per batch, else from a DataLoader: the same batches either
+        way (`tags` is then on the device).  `moving_size=None` is the plain `MovingSet` of everything, in order.
 
         `sample_recorders` ({set name: SampleRecorder}, see `make_sample_recorders`): the latent records of the reference's
         `--inspection` switch (ft/job.py:282-300, 451-470).  They are filled by the scoring pass before tuning and, with `saved_dir`
@@ -396,11 +409,25 @@ class WIMJob(ClassificationVariationalNetwork):
         batch_size = int(batch_size or self.training_parameters['batch_size'])
         testset_name = testset_name or getattr(ind_set, 'name', None) or self.training_parameters.get('set') or 'ind'
         device = self.device
-        moving_set = MovingSet(ind_set, ood_sets)
+        if moving_size is None:
+            moving_set, group_of_tag = MovingSet(ind_set, ood_sets), None
+        else:
+            padding_sets = self._padding_sets(padding_sets, padding, ind_set)
+            moving_set = create_moving_set(ind_set, ood_sets, padding_sets, moving_size, ood_mix, padding=padding,
+                                           mix_padding=mix_padding, seed=seed, task=task)
+            group_of_tag = torch.tensor([0 if c == 'ind' else 1 for c in moving_set.classes], dtype=torch.int32, device=device)
         if not hasattr(self, 'ft_params'):
             self.ft_params = {}
-        self.ft_params.update(sets=list(ood_sets), train_size=train_size, moving_size=len(moving_set), mix=moving_set.mix[1],
-                              padding=0, padding_sets=[], mix_padding=0, alpha=alpha)
+        if moving_size is None:
+            self.ft_params.update(sets=list(ood_sets), train_size=train_size, moving_size=len(moving_set), mix=moving_set.mix[1],
+                                  padding=0, padding_sets=[], mix_padding=0, alpha=alpha)
+        else:
+            actual = int(len(moving_set) // (1 + padding + mix_padding))
+            if actual < moving_size:
+                logging.warning('Moving size reduced to %d (instead of %d)', actual, moving_size)
+            self.ft_params.update(sets=list(ood_sets), train_size=train_size, moving_size=min(actual, int(moving_size)),
+                                  mix=moving_set.mix[moving_set.classes.index('ood')], padding=padding,
+                                  padding_sets=list(padding_sets), mix_padding=mix_padding, alpha=alpha)
         test_batch_size = min(self.max_batch_sizes['test'], test_batch_size)
         logging.info('Moving set of length %d, with mixture %s', len(moving_set),
                      ', '.join('{}:{:.1%}'.format(n, m) for n, m in zip(moving_set.classes, moving_set.mix)))
@@ -433,7 +460,12 @@ class WIMJob(ClassificationVariationalNetwork):
 
         # ---- the epochs
         train_loader = torch.utils.data.DataLoader(trainset, batch_size=batch_size, shuffle=True, num_workers=0)
-        moving_loader = torch.utils.data.DataLoader(moving_set, drop_last=True, batch_size=batch_size, shuffle=True, num_workers=0)
+        moving_loader = None
+        if moving_size is not None:
+            from jvae_compat import torch_load
+            moving_loader = torch_load.mixed_loader(moving_set, batch_size, True, True)
+        if moving_loader is None:
+            moving_loader = torch.utils.data.DataLoader(moving_set, drop_last=True, batch_size=batch_size, shuffle=True, num_workers=0)
         self.ft_params['train_size'], schedule = finetune_schedule(train_size, len(moving_set), batch_size, epochs)
         epochs = len(schedule)
         logging.info('Epochs: %d of %s batches of size %d', epochs, schedule, batch_size)
@@ -462,7 +494,11 @@ class WIMJob(ClassificationVariationalNetwork):
                 optimizer.step()
                 optimizer.clip(self.parameters())          # after the step, as the reference has it (ft/job.py:397-399)
                 # the printed losses: this batch's rows [mix | in] and their groups, one launch, nothing read back
-                group = torch.cat((tags.to(torch.int32), torch.full((len(x_a),), G - 1, dtype=torch.int32))).to(device)
+                if group_of_tag is None:
+                    group = torch.cat((tags.to(torch.int32), torch.full((len(x_a),), G - 1, dtype=torch.int32))).to(device)
+                else:                                      # class -> tally group, one small lookup on the device
+                    group = torch.cat((group_of_tag[tags.to(device)],
+                                       torch.full((len(x_a),), G - 1, dtype=torch.int32, device=device)))
                 rows = torch.stack([torch.cat((mix_loss[k].detach(), in_loss[k].detach())) for k in printed])
                 ops.group_tally(rows, group, sums, counts)
                 if on_batch is not None:
@@ -493,6 +529,34 @@ class WIMJob(ClassificationVariationalNetwork):
                                            sample_recorders=sample_recorders, sample_dirs=sample_dirs())
         logging.info('misclassification_detection_rates with the `~` scores is outside this build: skipped')
         return res
+
+    def _padding_sets(self, padding_sets, padding, ind_set):
+        """The padding sets of a moving set as a dict name -> data set.  Given: a dict name -> data set or name, or a list of
+        data sets and names; a name is opened from `DATA_ROOT`, and the short names 'uniform' / 'const' stand for the uniform* /
+        const* sibling of the model's set; none given = ['uniform', 'const'] (ft/job.py:225-231).  No padding, no sets."""
+        if not padding:
+            return {}
+        if not padding_sets:
+            padding_sets = ['uniform', 'const']
+        if not isinstance(padding_sets, dict):
+            padding_sets = {str(getattr(p, 'name', p)): p for p in padding_sets}
+        if not any(isinstance(p, str) for p in padding_sets.values()):
+            return dict(padding_sets)
+        if self.DATA_ROOT is None:
+            raise NotImplementedError('named torchvision datasets are outside this build: pass padding_sets as a dict of '
+                                      'name -> Dataset')
+        from jvae_compat import torch_load
+        set_name = self.training_parameters.get('set') or getattr(ind_set, 'name', None)
+        transformer = getattr(ind_set, 'transformer', None)
+        opened = {}
+        for name, p in padding_sets.items():
+            if p in ('uniform', 'const'):
+                found = [n for n in (torch_load.get_same_size_by_name(set_name) if set_name else []) if n.startswith(p)]
+                if not found:
+                    raise ValueError('no {}* sibling of {} to pad the moving set with'.format(p, set_name))
+                name = p = found[0]
+            opened[name] = self._open_named(p, transformer=transformer) if isinstance(p, str) else p
+        return opened
 
     def make_sample_recorders(self, names, batch_size):
         """The sample recorders of the reference's `--inspection` switch (ft/__main__.py:208-221), one per name: `mu` and `y`,

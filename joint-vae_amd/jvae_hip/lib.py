@@ -105,6 +105,8 @@ _SIGS = {
     'jvae_augment_u8_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'jvae_imageset_desc_words': (c_int, []),
     'jvae_imageset_batch_u8_f32': (c_int, [P] * 4 + [POINTER(c_int)] + [P] * 9 + [c_long, c_int, P]),
+    'jvae_imageset_mix_leaf_bytes': (c_int, []),
+    'jvae_imageset_mixed_u8_f32': (c_int, [P, P, c_int] + [P] * 5 + [c_int] + [P] * 3 + [c_int, c_int, P]),
     'jvae_sqnorm_workspace_bytes': (c_size_t, []),
     'jvae_sqnorm_accum_f32': (c_int, [P, c_long, P, c_int, P, c_size_t, P]),
     'jvae_clip_scale_f32': (c_int, [P, c_long, P, c_float, P]),

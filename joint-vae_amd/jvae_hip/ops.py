@@ -9,6 +9,7 @@ import ctypes
 import math
 from ctypes import byref, c_int, c_size_t
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -2078,6 +2079,141 @@ def imageset_batch(data, idx, desc, targets, lut=None, flip=None, dy=None, dx=No
                                              L.ptr(x), L.ptr(y), data.shape[0], N, L.stream_ptr())
     L.check(rc, 'jvae_imageset_batch_u8_f32')
     return x, y
+
+
+
+class _MixLeaf(ctypes.Structure):
+    """One leaf record of csrc/imageset.hip (struct MixLeaf)."""
+    _fields_ = [('kind', ctypes.c_int), ('border', ctypes.c_int)] + [
+        (n, ctypes.c_void_p) for n in ('data', 'targets', 'lut', 'coef_h', 'bounds_h', 'coef_v', 'bounds_v')] + [('desc', ctypes.c_int * 20)]
+
+
+class ImagesetMixTable:
+    """What one launch of `imageset_mixed_batch` needs of a resolved moving set (jvae_compat.ft_datasets: `resolve()`), built
+    once and kept on `device`: a record per leaf - kind (image set / const / uniform), the pointers of the leaf's `data`,
+    `targets`, `lut` and resize tables, its 20 descriptor words - and the per-item arrays `leaf`, `index`, `tag`.  A leaf is a
+    device-resident image set (`.data`, `.targets`, `.lut`, `.desc`) or a synthetic one (`.data` None, `.kind` 'const' /
+    'uniform', `.image_shape`, `.transformer`).  Everything a launch could read outside of is checked here, on the host:
+    leaf numbers, every sample index against its leaf's length, tags; ValueError when the leaves' chains do not all end in the
+    same (C, H, W), a leaf carries its own data_augmentation (a mixed batch has no random flip / crop) or holds a tensor that
+    is not contiguous.  The table keeps every
+    tensor whose pointer it stored; `matches()` tells whether it still describes the set (else: build another)."""
+
+    KINDS = {'const': 1, 'uniform': 2}
+
+    def __init__(self, leaves, leaf, index, tag, device):
+        device = torch.device(device)
+        leaves = list(leaves)
+        if not leaves:
+            raise ValueError('mixed image set: no leaf')
+        shapes, kinds = [], []
+        for l in leaves:
+            if tuple(getattr(l, 'data_augmentation', ())):
+                raise ValueError('mixed image set: {} carries its own data_augmentation {}; a mixed batch has no random flip / '
+                                 'crop'.format(getattr(l, 'name', 'leaf'), list(l.data_augmentation)))
+            if l.data is None:
+                kind = self.KINDS.get(getattr(l, 'kind', None))
+                if kind is None:
+                    raise ValueError('mixed image set: {} is neither resident nor const / uniform'.format(getattr(l, 'name', 'leaf')))
+                C, H, W = l.image_shape
+                pad = 4 if l.transformer == 'pad' else 0
+                shapes.append((C, H + pad, W + pad))
+            else:
+                kind = 0
+                shapes.append(tuple(l.desc.shape))
+            kinds.append(kind)
+        if len(set(shapes)) != 1:
+            raise ValueError('mixed image set: the leaves do not end in one shape: ' + ', '.join(
+                '{} {}'.format(getattr(l, 'name', 'leaf'), s) for l, s in zip(leaves, shapes)))
+        self.shape, self.kinds = shapes[0], tuple(kinds)
+        self.u_dims = 4 if 2 in kinds else (2 if 1 in kinds else 0)
+        leaf_np, index_np, tag_np = (np.ascontiguousarray(a, np.int64).reshape(-1) for a in (leaf, index, tag))
+        n = len(leaf_np)
+        if not (len(index_np) == len(tag_np) == n):
+            raise ValueError('mixed image set: leaf, index and tag of one length')
+        if n and (leaf_np.min() < 0 or leaf_np.max() >= len(leaves) or tag_np.min() < 0):
+            raise IndexError('mixed image set: a leaf number outside the {} leaves, or a negative tag'.format(len(leaves)))
+        lengths = np.asarray([len(l) for l in leaves], np.int64)
+        if n and (index_np.min() < 0 or bool((index_np >= lengths[leaf_np]).any())):
+            bad = int(np.flatnonzero((index_np < 0) | (index_np >= lengths[leaf_np]))[0])
+            raise IndexError('mixed image set: item {} is sample {} of the {} of {}'.format(
+                bad, int(index_np[bad]), int(lengths[leaf_np[bad]]), getattr(leaves[leaf_np[bad]], 'name', 'leaf')))
+        self.n_items, self.device = n, device
+        self._source = (leaves, leaf, index, tag)
+        keep, records = [], (_MixLeaf * len(leaves))()
+        for rec, l, kind in zip(records, leaves, kinds):
+            rec.kind, rec.border = kind, int(kind != 0 and l.transformer == 'pad')
+            words = [0] * 17 + list(self.shape)
+            if kind == 0:
+                desc = l.desc.with_pa(0)
+                tensors = [l.data, l.targets, l.lut, *desc.tables]
+                if not all(t is None or t.is_contiguous() for t in tensors):      # the table stores pointers, never a copy
+                    raise ValueError('mixed image set: {} holds a tensor that is not contiguous'.format(getattr(l, 'name', 'leaf')))
+                Hs, Ws, Cs = desc.source
+                if (l.data.dtype != torch.uint8 or tuple(l.data.shape[1:]) != ((Hs, Ws, Cs) if desc.nhwc else (Cs, Hs, Ws))
+                        or l.targets.dtype != torch.int64 or l.targets.numel() != l.data.shape[0]
+                        or (l.lut is not None and l.lut.dtype != torch.int64)):
+                    raise ValueError('mixed image set: {}: data {} / {} targets against the chain of {}'.format(
+                        getattr(l, 'name', 'leaf'), tuple(l.data.shape), l.targets.numel(), desc.source))
+                for t in tensors:
+                    if t is not None and t.device != device:
+                        raise ValueError('mixed image set: {} is on {}, the table on {}'.format(getattr(l, 'name', 'leaf'), t.device, device))
+                for name, t in zip(('data', 'targets', 'lut', 'coef_h', 'bounds_h', 'coef_v', 'bounds_v'), tensors):
+                    setattr(rec, name, L.ptr(t))
+                keep += [t for t in tensors if t is not None]
+                words = list(desc.words)
+            rec.desc[:] = words
+        assert ctypes.sizeof(_MixLeaf) == L.load().jvae_imageset_mix_leaf_bytes()
+        self.records = records
+        raw = np.frombuffer(bytes(records), np.uint8).copy()
+        self.records_dev = torch.from_numpy(raw).to(device)
+        self.leaf = torch.from_numpy(leaf_np.astype(np.int32)).to(device)
+        self.index = torch.tensor(index_np).to(device)
+        self.tag = torch.tensor(tag_np).to(device)
+        self._keep = keep
+        self._pointers = [t.data_ptr() for t in keep]
+
+    def matches(self, leaves, leaf, index, tag):
+        """Whether the table was built from these very arrays and every leaf's tensors are where they were."""
+        mine = self._source
+        if len(leaves) != len(mine[0]) or any(a is not b for a, b in zip(leaves, mine[0])):
+            return False
+        if leaf is not mine[1] or index is not mine[2] or tag is not mine[3]:
+            return False
+        now = []
+        for l, kind in zip(leaves, self.kinds):
+            if kind == 0:
+                now += [t for t in (l.data, l.targets, l.lut, *l.desc.with_pa(0).tables) if t is not None]
+        return len(now) == len(self._keep) and all(t.device == self.device and t.is_contiguous() and t.data_ptr() == p
+                                                   for t, p in zip(now, self._pointers))
+
+
+def imageset_mixed_batch(table, pos, u=None, vec=0):
+    """-> (x float32 (N, C, H, W), tag int64 (N,), y int64 (N,)): the items `pos` (int64 on the device, every entry in
+    [0, table.n_items) - checked by the caller on the host before the upload, the kernel has no trap) of a resolved moving set,
+    each through the chain of its own leaf, in ONE launch.  `u`: what the synthetic leaves show, float32 drawn by the caller -
+    (N, C) when only const leaves occur, (N, C, H, W) when a uniform leaf occurs, None without synthetic leaves.  `vec`:
+    consecutive x per thread (1 | 4), 0 = the default.  Does not synchronise."""
+    if pos.dtype != torch.int64 or pos.device != table.device:
+        raise L.JvaeHipError('imageset_mixed_batch: pos int64 on the device of the table')
+    pos = _c(pos.reshape(-1))
+    N = pos.numel()
+    C, H, W = table.shape
+    if table.u_dims:
+        want = (N, C) if table.u_dims == 2 else (N, C, H, W)
+        if u is None or u.dtype != torch.float32 or tuple(u.shape) != want or u.device != table.device:
+            raise L.JvaeHipError(f'imageset_mixed_batch: u float32 {want} on the device for the synthetic leaves')
+        u = _c(u)
+    elif u is not None:
+        raise L.JvaeHipError('imageset_mixed_batch: u given, but the set has no synthetic leaf')
+    x = torch.empty((N, C, H, W), device=table.device, dtype=torch.float32)
+    tag = torch.empty((N,), device=table.device, dtype=torch.int64)
+    y = torch.empty((N,), device=table.device, dtype=torch.int64)
+    rc = L.load().jvae_imageset_mixed_u8_f32(ctypes.addressof(table.records), L.ptr(table.records_dev), len(table.kinds),
+                                             L.ptr(table.leaf), L.ptr(table.index), L.ptr(table.tag), L.ptr(pos), L.ptr(u),
+                                             table.u_dims, L.ptr(x), L.ptr(tag), L.ptr(y), N, int(vec), L.stream_ptr())
+    L.check(rc, 'jvae_imageset_mixed_u8_f32')
+    return x, tag, y
 
 
 from . import ops_b8 as _b8  # noqa: E402  (the B8 layout; it builds on the fp32 wrappers above)

@@ -566,6 +566,38 @@ int jvae_roc_curve_f32(const float* ins, const float* outs, const double* kept_t
                        double* auc, double* kept_fpr, double* kept_tpr_out, double* thr_low, double* thr_up, int* status,
                        int M, long n_in, long n_out, int K, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- SCOD: selective classification with OOD data, score rows and risk curves (csrc/scod.hip) ----------------------
+ * Replaces tests/scod.py of the reference (scoring_r, scoring_g, scoring, scrisk and the figures of its command-line block).
+ * Scores: M <= 32 variants of ONE recorded set of N samples in one launch, row m of out (row stride out_stride >= N) =
+ * r + weights[m] * g.  r_src / r_aux / g_src / g_alt: HOST arrays of M device pointers (NULL where the kind reads nothing),
+ * kinds: HOST array of M pairs (r kind, g kind), weights: HOST array of M floats, y_est: (N,) int64 labels on the device.
+ *   r kind  0  0.                             1  0.5 * r_src[y]   (r_src (C, N): zdist for `dist`, pre-zdist for `predist`)
+ *           2  0.5 * r_src[y] - r_aux         (`logmsp`: r_src = zdist, r_aux (N,) = logsumexp_c(-0.5 zdist), computed by torch)
+ *           3  1 - r_src                      (r_src (N,): a recorded `odin-*` row)
+ *   g kind  0  0.     1  0.5 * (g_src[y] - g_alt)  (`elbo`)     2  -(g_src[y] - g_alt)  (`iws`)     3  g_src[y] - g_alt
+ *           (g_src (C, N) the all-class loss, g_alt (N,) its `@` partner under the alternate prior; a 2-D partner: its row 0)
+ *   kind -1 on one side: the row is the OTHER side alone (r, or the unweighted g), nothing is added.
+ * Every product, difference and sum is rounded on its own: the reference's fp32 torch expressions bit for bit.  A label
+ * outside [0, C) is never used as an index: that sample is NaN and *status (device int32, owned and cleared by the caller)
+ * is set to 1, as for jvae_wim_scores_f32.  Neither allocates nor synchronises.  Malformed arguments: -1 (JVAE_EINVAL).
+ * Curves: scores (M, n) fp32, the HIGHer the more likely to reject; y_true (n,) int64, the class of an in-distribution sample
+ * and a negative value for an OOD one; y_est (n,) int64; n_in = the number of in-distribution samples (known to the host:
+ * nothing is read back), 1 <= n_in < n <= 2^24, M <= 65535.  Each row is sorted ascending, stable by position, and scanned:
+ *   curves (3, M, n) fp32 or NULL: tpr = in_cum / n_in, selective_risk = wrong_cum / in_cum (0 / 0 -> 0), fpr = ood_cum / n_ood
+ *     - correctly rounded fp32 quotients of integers below 2^24, what scrisk returns bit for bit on tie-free scores;
+ *   figures (M, 5) fp64 or NULL: fpr95, sr95 (the minimum of fpr and of selective_risk over tpr >= 0.95f), then the trapezoid
+ *     areas AuROC (fpr, tpr), AuST (tpr, selective_risk), AuSCODT (tpr, 0.5 sr + 0.5 fpr formed in fp32), summed in fp64 over
+ *     the fp32 curve values in a fixed order.
+ * status (M int32, cleared by the call): bit 0 = a NaN score was seen, bit 1 = y_true does not hold n_in non-negative
+ * entries; the outputs of such a row are meaningless (never out of bounds).  No float atomics; the same bits run to run.
+ * ws 16-byte aligned, jvae_scod_workspace_bytes(M, n) bytes (0 = invalid sizes). */
+int jvae_scod_scores_f32(const float* const* r_src, const float* const* r_aux, const float* const* g_src,
+                         const float* const* g_alt, const int* kinds, const float* weights, const long long* y_est,
+                         float* out, long out_stride, int M, int C, long N, int* status, void* stream);
+size_t jvae_scod_workspace_bytes(int M, long n);
+int jvae_scod_curve_f32(const float* scores, const long long* y_true, const long long* y_est, float* curves, double* figures,
+                        int* status, int M, long n, long n_in, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Misclassification detection: score rows, split by correctness, confusion counts (csrc/misclass.hip) ----------
  * What surrounds jvae_roc_curve_f32 in misclassification_detection_rates (reference cvae.py:1913-2079).
  * Scores: src (C, N) fp32 (all-class kl / zdist / iws losses, or the logits as the recorder stores them), C <= 128, read once;

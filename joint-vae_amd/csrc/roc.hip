@@ -22,17 +22,9 @@
 // Rows are padded to a power of two (>= one tile) with the largest key, which sorts behind every real score.
 #include "common.h"
 #include "jvae_internal.h"
+#include "roc_sort.h"                  // ROC_TILE, roc_pad, roc_key / roc_unkey, the bitonic passes, roc_sort_rows, ROC_MAX_N
 
 namespace {
-
-constexpr int ROC_TILE = 2048;         // keys per workgroup of the LDS passes (16 KiB of uint64)
-constexpr int ROC_TILE_THREADS = 1024; // one compare-exchange per thread and pass
-
-__host__ __device__ inline long roc_pad(long n) {
-    long p = ROC_TILE;
-    while (p < n) p <<= 1;
-    return p;
-}
 
 struct RocWs {                         // carve-up of the caller's workspace (all offsets multiples of 256 bytes)
     size_t kin, kout, d, negin, negout, acc, c, V, total;
@@ -52,15 +44,6 @@ inline RocWs roc_ws(int M, long n_in, long n_out) {
     w.V = o;      o += roc_align(sizeof(int) * M);
     w.total = o;
     return w;
-}
-
-// fp32 -> uint32 with the order of the floats (-inf < ... < -0 < +0 < ... < +inf), and back
-__device__ __forceinline__ uint32_t roc_key(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float roc_unkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
 // Mode word of a row -> 0 one-sided, 1 around-mean, 2 strided quantiles with the factors f_low = bits 8-15 and f_up = bits
@@ -94,46 +77,6 @@ __global__ __launch_bounds__(256) void roc_keys_kernel(const float* __restrict__
     if (z == 0 && i == 0 && roc_decode(modes[m], f_low, f_up) < 0) bad |= 4;
     (z ? kout : kin)[(size_t)m * P + i] = key;
     if (bad) atomicOr(&status[m], bad);
-}
-
-// Compare-exchange passes of the bitonic network that fit one tile.  k == 0: the whole local sort (k = 2 ... ROC_TILE);
-// k > ROC_TILE: the tail j = ROC_TILE/2 ... 1 of merge stage k.  Element g sorts ascending where (g & k) == 0.
-template <typename KT>
-__global__ __launch_bounds__(ROC_TILE_THREADS) void roc_bitonic_tile_kernel(KT* __restrict__ keys, long P,
-                                                                            const int* __restrict__ modes, long k) {
-    if (modes && modes[blockIdx.y] != 1) return;
-    __shared__ KT s[ROC_TILE];
-    const int t = threadIdx.x;
-    const long base = (long)blockIdx.x * ROC_TILE;
-    KT* row = keys + (size_t)blockIdx.y * P + base;
-    s[t] = row[t];
-    s[t + ROC_TILE_THREADS] = row[t + ROC_TILE_THREADS];
-    __syncthreads();
-    for (long kk = k ? k : 2; kk <= (k ? k : (long)ROC_TILE); kk <<= 1) {
-        for (int j = (int)(kk < ROC_TILE ? kk : ROC_TILE) >> 1; j > 0; j >>= 1) {
-            const int i = 2 * t - (t & (j - 1));
-            const bool up = ((base + i) & kk) == 0;
-            const KT a = s[i], b = s[i + j];
-            if ((a > b) == up) { s[i] = b; s[i + j] = a; }
-            __syncthreads();
-        }
-    }
-    row[t] = s[t];
-    row[t + ROC_TILE_THREADS] = s[t + ROC_TILE_THREADS];
-}
-
-// One pass (k, j) with j >= ROC_TILE: partners are in different tiles
-template <typename KT>
-__global__ __launch_bounds__(256) void roc_bitonic_step_kernel(KT* __restrict__ keys, long P, const int* __restrict__ modes,
-                                                               long k, long j) {
-    if (modes && modes[blockIdx.y] != 1) return;
-    const long g = (long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= (P >> 1)) return;
-    const long i = 2 * g - (g & (j - 1));
-    KT* row = keys + (size_t)blockIdx.y * P;
-    const bool up = (i & k) == 0;
-    const KT a = row[i], b = row[i + j];
-    if ((a > b) == up) { row[i] = b; row[i + j] = a; }
 }
 
 // c = mean(ins) in fp64 (roc_curves.py:69): strided partial sums, then a fixed tree
@@ -321,24 +264,6 @@ __global__ __launch_bounds__(64) void roc_kept_kernel(const uint32_t* __restrict
     }
     auc[m] = (double)(long long)acc[m] / (2.0 * (double)n_in * (double)n_out);
 }
-
-template <typename KT>
-int roc_sort_rows(KT* keys, long P, int M, const int* modes, hipStream_t st) {
-    const dim3 tiles((unsigned)(P / ROC_TILE), (unsigned)M), pairs((unsigned)cdiv(P >> 1, 256), (unsigned)M);
-    roc_bitonic_tile_kernel<KT><<<tiles, ROC_TILE_THREADS, 0, st>>>(keys, P, modes, 0);
-    JVAE_LAUNCH_CHECK();
-    for (long k = 2L * ROC_TILE; k <= P; k <<= 1) {
-        for (long j = k >> 1; j >= ROC_TILE; j >>= 1) {
-            roc_bitonic_step_kernel<KT><<<pairs, 256, 0, st>>>(keys, P, modes, k, j);
-            JVAE_LAUNCH_CHECK();
-        }
-        roc_bitonic_tile_kernel<KT><<<tiles, ROC_TILE_THREADS, 0, st>>>(keys, P, modes, k);
-        JVAE_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
-constexpr long ROC_MAX_N = 1L << 24;   // counts stay in int32 and M rows of padded keys in a 32-bit grid
 
 }  // namespace
 

@@ -1311,6 +1311,145 @@ def roc_check_status(status):
             raise ValueError(f'roc_curve: non-finite in-distribution score in around-mean row {m}')
 
 
+# ------------------------------------------------------------------------------------------- SCOD risk curves (csrc/scod.hip)
+SCOD_R_KINDS = {None: -1, 'zero': 0, 'half_y': 1, 'logmsp': 2, 'odin': 3}
+SCOD_G_KINDS = {None: -1, 'zero': 0, 'half': 1, 'neg': 2, 'plain': 3}
+SCOD_MAX_ROWS = 32           # variants per launch (more are dealt to further launches)
+SCOD_MAX_N = 1 << 24         # ROC_MAX_N of csrc/roc_sort.h: counts are exact in fp32 below it
+SCOD_FIGURES = ('fpr95', 'sr95', 'auroc', 'aust', 'auscodt')
+
+
+def scod_scores(specs, y_est, C, N, out=None, col=0, status=None):
+    """The SCOD score rows r + weight * g of M variants of one recorded set in ONE launch per 32 variants (tests/scod.py:60-144 of
+    the reference; csrc/scod.hip).  specs: M tuples (r_kind, r_src, r_aux, g_kind, g_src, g_alt, weight) - r_kind in
+    SCOD_R_KINDS: 'zero' 0., 'half_y' 0.5 * r_src[y_est] (r_src (C, N)), 'logmsp' 0.5 * r_src[y_est] - r_aux (r_aux (N,), the
+    class-axis logsumexp(-0.5 r_src) the caller took with torch), 'odin' 1 - r_src (r_src (N,)); g_kind in SCOD_G_KINDS: 'zero'
+    0., 'half' / 'neg' / 'plain': 0.5 / -1 / 1 times (g_src[y_est] - g_alt), g_src (C, N), g_alt (N,) or (R, N) (its row 0);
+    a kind None: the row is the other side alone.  Tensors a kind does not read may be None.  y_est (N,) int64 or None when no
+    kind gathers.  out: a dense (>= M, >= col + N) fp32 device buffer whose rows 0 .. M - 1 are written at columns col .. col + N;
+    without: a new (M, N) tensor.  Each operation is rounded on its own (the torch expressions bit for bit).  status as for
+    `wim_scores`: set to 1 when a label is outside [0, C) (that sample is NaN); `wim_check_status` raises on it."""
+    M = len(specs)
+    dev = None
+    rows = []
+    for rk, r_src, r_aux, gk, g_src, g_alt, weight in specs:
+        if rk not in SCOD_R_KINDS or gk not in SCOD_G_KINDS or (rk is None and gk is None):
+            raise L.JvaeHipError(f'scod_scores: unknown variant ({rk!r}, {gk!r})')
+        need = {'r_src': (r_src, SCOD_R_KINDS[rk] > 0, (N,) if rk == 'odin' else (C, N)), 'r_aux': (r_aux, rk == 'logmsp', (N,)),
+                'g_src': (g_src, SCOD_G_KINDS[gk] > 0, (C, N)), 'g_alt': (g_alt, SCOD_G_KINDS[gk] > 0, (N,))}
+        ptrs = []
+        for name, (t, used, shape) in need.items():
+            if not used:
+                ptrs.append(None)
+                continue
+            if t is None:
+                raise L.JvaeHipError(f'scod_scores: ({rk!r}, {gk!r}) needs {name}')
+            if name == 'g_alt' and t.dim() == 2:
+                t = t[0]
+            t = _c(_f32(t, 'scod_scores'))
+            L.ptr(t)
+            if tuple(t.shape) != shape or (dev is not None and t.device != dev):
+                raise L.JvaeHipError(f'scod_scores: {name} of shape {shape} on one device expected, got {tuple(t.shape)} on {t.device}')
+            dev = t.device
+            ptrs.append(t)
+        rows.append((ptrs, SCOD_R_KINDS[rk], SCOD_G_KINDS[gk], float(weight)))
+    gathers = any(rk in (1, 2) or gk > 0 for _, rk, gk, _ in rows)
+    if y_est is not None:
+        L.ptr(y_est)
+        dev = dev or y_est.device
+        if y_est.dtype != torch.int64 or tuple(y_est.shape) != (N,) or y_est.device != dev:
+            raise L.JvaeHipError(f'scod_scores: ({N},) int64 labels on {dev} expected, got {tuple(y_est.shape)} {y_est.dtype}')
+        y_est = _c(y_est)
+    elif gathers:
+        raise L.JvaeHipError('scod_scores: the variants gather at the estimated labels: y_est expected')
+    if dev is None:
+        dev = out.device if out is not None else torch.device('cuda', torch.cuda.current_device())
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    col = int(col)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < M or not 0 <= col <= out.shape[1] - N \
+            or not out.is_contiguous() or out.device != dev:
+        raise L.JvaeHipError(f'scod_scores: a dense (>= {M}, >= {col} + {N}) fp32 buffer on {dev} expected')
+    L.ptr(out)
+    if status is None:
+        status = wim_status(dev)
+    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise L.JvaeHipError('scod_scores: an int32 status word on the device of the sources expected')
+    lib = L.load()
+    for m0 in range(0, M, SCOD_MAX_ROWS):
+        part = rows[m0:m0 + SCOD_MAX_ROWS]
+        n = len(part)
+        arrays = [(ctypes.c_void_p * n)(*[None if p[j] is None else p[j].data_ptr() for p, _, _, _ in part]) for j in range(4)]
+        kinds = (ctypes.c_int * (2 * n))(*[k for _, rk, gk, _ in part for k in (rk, gk)])
+        weights = (ctypes.c_float * n)(*[w for _, _, _, w in part])
+        L.check(lib.jvae_scod_scores_f32(*arrays, kinds, weights, L.ptr(y_est), out.data_ptr() + 4 * (m0 * out.shape[1] + col),
+                                         out.shape[1], n, int(C), int(N), L.ptr(status), L.stream_ptr()), 'jvae_scod_scores_f32')
+    return out[:M, col:col + N]
+
+
+def scod_curve(scores, y_true, y_est, curves=True, figures=True, n_in=None):
+    """The SCOD risk curves of M score rows in one call (scrisk and the figures of the reference's tests/scod.py; csrc/scod.hip).
+    scores (M, n) or (n,) fp32 on the device, the HIGHer the more likely to reject; y_true (n,) int64: the class of an
+    in-distribution sample, negative for an OOD one; y_est (n,) int64.  Each row is sorted ascending (stable by position) and
+    scanned.  -> dict of DEVICE tensors: with `curves` 'tpr', 'selective_risk', 'fpr' (M, n) fp32 - the reference's, bit for bit
+    on tie-free scores; with `figures` 'figures' (M, 5) fp64 in the order of SCOD_FIGURES: the minimum of fpr / selective_risk
+    over tpr >= 0.95 and the trapezoid areas AuROC, AuST, AuSCODT, summed in fp64 in a fixed order; 'status' (M,) int32, bit 0:
+    NaN score, bit 1: `n_in` is not the number of non-negative y_true (`scod_check_status` raises on them).  (n,) scores drop
+    the M axis.  n_in: the number of in-distribution samples when the caller knows it - nothing is then read back or
+    synchronised; None: counted here, which reads one value back.  An empty in or OOD side (the reference returns NaN curves),
+    n > SCOD_MAX_N, scores that are not fp32 or not on the device: JvaeHipError before any launch."""
+    lib = L.load()
+    single = scores.dim() == 1
+    _f32(scores, 'scod_curve')
+    for t in (scores, y_true, y_est):                          # off the GPU: JvaeHipError, before anything else is looked at
+        if not t.is_cuda:
+            raise L.JvaeHipError(f'scod_curve: tensors resident on the GPU expected (no CPU fallback); got device {t.device}')
+    if single:
+        scores = scores[None]
+    if scores.dim() != 2 or scores.shape[0] < 1:
+        raise L.JvaeHipError(f'scod_curve: (M, n) score rows expected, got {tuple(scores.shape)}')
+    M, n = scores.shape
+    dev = scores.device
+    for name, y in (('y_true', y_true), ('y_est', y_est)):
+        if y.dtype != torch.int64 or tuple(y.shape) != (n,) or y.device != dev:
+            raise L.JvaeHipError(f'scod_curve: {name}: ({n},) int64 on {dev} expected, got {tuple(y.shape)} {y.dtype} on {y.device}')
+    if not (curves or figures):
+        raise L.JvaeHipError('scod_curve: nothing asked for')
+    if n > SCOD_MAX_N or M > 65535:
+        raise L.JvaeHipError(f'scod_curve: sizes out of range (M={M}, n={n}, at most {SCOD_MAX_N} samples)')
+    if n_in is None:
+        n_in = int((y_true >= 0).sum())
+    n_in = int(n_in)
+    if n_in < 1 or n_in >= n:
+        raise L.JvaeHipError(f'scod_curve: {n_in} in-distribution and {n - n_in} OOD samples: neither side may be empty')
+    scores, y_true, y_est = _c(scores), _c(y_true), _c(y_est)
+    out = torch.empty((3, M, n), dtype=torch.float32, device=dev) if curves else None
+    fig = torch.empty((M, len(SCOD_FIGURES)), dtype=torch.float64, device=dev) if figures else None
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    nbytes = lib.jvae_scod_workspace_bytes(M, n)
+    if not nbytes:
+        raise L.JvaeHipError(f'scod_curve: sizes out of range (M={M}, n={n})')
+    ws = L.workspace(nbytes, dev)
+    rc = lib.jvae_scod_curve_f32(L.ptr(scores), L.ptr(y_true), L.ptr(y_est), L.ptr(out), L.ptr(fig), L.ptr(status), M, n, n_in,
+                                 L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, 'jvae_scod_curve_f32')
+    res = {'status': status}
+    if curves:
+        res.update(tpr=out[0], selective_risk=out[1], fpr=out[2])
+    if figures:
+        res['figures'] = fig
+    return {k: v[0] for k, v in res.items()} if single else res
+
+
+def scod_check_status(status):
+    """Raise for the rows `scod_curve` flagged (host values of its 'status' word: a tensor, a list or one value)."""
+    for m, s in enumerate(torch.as_tensor(status).reshape(-1).tolist()):
+        if int(s) & 1:
+            raise ValueError(f'scod_curve: NaN score in row {m}')
+        if int(s) & 2:
+            raise L.JvaeHipError(f'scod_curve: n_in is not the number of in-distribution samples of y_true (row {m})')
+
+
 # ------------------------------------------------------------------------------------------- misclassification (csrc/misclass.hip)
 MISCLASS_KINDS = {'soft-': 0, 'soft+': 1, 'max-': 2, 'max+': 3, 'hyz': 4, 'lse-': 5, 'lse+': 6, 'mean': 7, 'std': 8, 'nstd': 9,
                   'mag': 10, 'IYx': 11, 'neg': 12, 'id': 13}

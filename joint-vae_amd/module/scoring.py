@@ -434,6 +434,14 @@ class ScoringMixin:
         plain = [m for m in names if not m.endswith('*')]
         return plain + [e for m in names if m.endswith('*') for e in grids.get(m[:-1], [])]
 
+    def scod_rates(self, sample_dir=None, epoch='last', **kw):
+        """SCOD figures of this saved job - selective classification in the presence of OOD data (reference tests/scod.py):
+        {'fpr95', 'sr95', 'auroc', 'aust', 'auscodt'} from the `record-*.pth` files of `sample_dir` (default: the job's sample
+        directory of `epoch`), with the job's training set as the in-distribution set and its type ('wim' for a WIMJob) as the
+        model type.  Keywords (`r`, `g`, `weight`, lists of them, `curves`) and everything else: jvae_compat.scod.scod_rates."""
+        from jvae_compat import scod
+        return scod.job_scod_rates(self, sample_dir=sample_dir, epoch=epoch, **kw)
+
     def misclassification_detection_rates(self, predict_methods='all', misclass_methods='all', epoch='last', shown_tpr=0.95,
                                           from_where=('json', 'recorders'), print_result=False, update_self_results=True,
                                           outputs=None, recorder=None):

@@ -43,6 +43,31 @@ int jvae_gemm_f32(int M, int N, int K, int batch,
 int jvae_splitk_fold_f32(const float* part, const float* bias, float* y, int S, long MN, int N, int relu, int accumulate,
                          void* stream);
 
+/* Independent products in ONE launch (two when the group holds both kernel families, see csrc/gemm.hip).  A descriptor is the
+ * argument list of jvae_gemm_f32; want_splits > 0 asks instead for the deterministic split-K form: K is cut into at most
+ * want_splits pieces whose partial products are STORED sCsplit elements apart (no bias, flags and splitk unused), and the number of
+ * pieces made is written to *splits (required then; fold them with jvae_splitk_fold_f32).  Every product runs the kernel, the
+ * tiles and the K slices that it gets when launched alone: the results are the same bits.  The products must not depend on each
+ * other.  n == 0: nothing is done.  n > 8: -2.  A descriptor that jvae_gemm_f32 refuses, or two descriptors whose outputs
+ * overlap (judged by the address ranges they span): -1, and nothing is launched. */
+typedef struct JvaeGemmDesc {
+    int M, N, K, batch;
+    const float* A; long sAm, sAk, sAb;
+    const float* B; long sBk, sBn, sBb;
+    float* C; long sCm, sCn, sCb;
+    const float* bias; int bias_mode, flags, splitk;
+    int want_splits; long sCsplit; int* splits;
+} JvaeGemmDesc;
+int jvae_gemm_group_f32(const JvaeGemmDesc* descs, int n, void* stream);
+
+/* Up to 8 folds (the arguments of jvae_splitk_fold_f32 each) in one launch; every element is folded by the same expression in
+ * the same slice order.  n == 0: nothing; n > 8: -2; a descriptor that jvae_splitk_fold_f32 refuses or overlapping outputs: -1. */
+typedef struct JvaeFoldDesc {
+    const float* part; const float* bias; float* y;
+    int S; long MN; int N, relu, accumulate;
+} JvaeFoldDesc;
+int jvae_splitk_fold_group_f32(const JvaeFoldDesc* descs, int n, void* stream);
+
 /* ---- (transposed) convolution ---------------------------------------------------------------------
  * x: (N,Cin,H,W) layer input; y: (N,Cout,OH,OW) layer output; w in the PyTorch layout of the layer kind
  * ((Cout,Cin,KH,KW) for Conv2d, (Cin,Cout,KH,KW) for ConvTranspose2d); S stride, P padding,

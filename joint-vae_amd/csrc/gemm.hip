@@ -9,8 +9,11 @@
 //
 // Serves: Linear layers fwd/dgrad/wgrad (reference: nn.Linear in layers.py:283-296, cvae.py:291-326),
 // the 1x1 -> kxk first transposed conv of the upsampler, and the generic (im2col) convolution path.
+// Independent products that cannot fill the chip alone (the two latent heads, a linear layer's dgrad and weight gradient) share
+// ONE launch through jvae_gemm_group_f32: the same plan, bodies and bits per product as alone.
 #include <stdlib.h>
 #include "common.h"
+#include "jvae_hip.h"
 #include "conv_x3.h"
 #include "jvae_internal.h"
 #include "conv_dispatch.h"
@@ -52,20 +55,32 @@ __device__ __forceinline__ f32x4 load4(const float* p, long stride, int i0, int 
 
 // AK: A is contiguous along k (row-major MxK); otherwise thread groups run along m.
 // BN_: B is contiguous along n (row-major KxN); otherwise along k.
+//
+// The body of one block tile is a __device__ function of the tile indices (bx, by, bz) and the grid (gx, gy, gz) they belong to,
+// so that the stand-alone kernel (the hardware's own block index) and the grouped kernel (a flat index cut into records,
+// gemm_group_tile_kernel) run the same code on the same operands in the same K order.
+template <int BM, int BN>
+struct TileLds {
+    static constexpr int LDA = BM + 4, LDB = BN + 4;
+    static constexpr int BYTES = BK * (LDA + LDB) * (int)sizeof(float);
+};
+
 template <int BM, int BN, bool AK, bool BNC>
-__global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
-    constexpr int LDA = BM + 4, LDB = BN + 4;
+__device__ __forceinline__ void gemm_tile_body(const GemmP& p, float* __restrict__ lds, unsigned bx, unsigned by, unsigned bz,
+                                               unsigned gx, unsigned gy, unsigned gz) {
+    constexpr int LDA = TileLds<BM, BN>::LDA, LDB = TileLds<BM, BN>::LDB;
     constexpr int WM = BM / 2, WN = BN / 2;          // wave tile
     constexpr int TM = WM / 32, TN = WN / 32;        // 32x32 MFMA tiles per wave
     constexpr int GA = BM * BK / 4 / 256;            // float4 groups per thread (A)
     constexpr int GB = BN * BK / 4 / 256;
-    __shared__ float As[BK * LDA];
-    __shared__ float Bs[BK * LDB];
+    float* As = lds;                                 // [BK][LDA]
+    float* Bs = lds + BK * LDA;                      // [BK][LDB]
+    (void)gx; (void)gy; (void)gz;                    // (no tile remap in this kernel)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int batch = blockIdx.z / p.splitk, split = blockIdx.z % p.splitk;
+    const int m0 = by * BM, n0 = bx * BN;
+    const int batch = bz / p.splitk, split = bz % p.splitk;
     const int kbeg = split * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);
     const float* A = p.A + (long)batch * p.sAb;
@@ -192,16 +207,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
         }
 }
 
-template <int BM, int BN>
-int launch_tile(const GemmP& p, int batch, hipStream_t st) {
-    dim3 grid(cdiv(p.N, BN), cdiv(p.M, BM), batch * p.splitk), block(256);
-    const bool ak = (p.sAk == 1), bnc = (p.sBn == 1);
-    if (ak && bnc)       hipLaunchKernelGGL((gemm_kernel<BM, BN, true, true>), grid, block, 0, st, p);
-    else if (ak && !bnc) hipLaunchKernelGGL((gemm_kernel<BM, BN, true, false>), grid, block, 0, st, p);
-    else if (!ak && bnc) hipLaunchKernelGGL((gemm_kernel<BM, BN, false, true>), grid, block, 0, st, p);
-    else                 hipLaunchKernelGGL((gemm_kernel<BM, BN, false, false>), grid, block, 0, st, p);
-    JVAE_LAUNCH_CHECK();
-    return 0;
+template <int BM, int BN, bool AK, bool BNC>
+__global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
+    __shared__ float lds[TileLds<BM, BN>::BYTES / sizeof(float)];
+    gemm_tile_body<BM, BN, AK, BNC>(p, lds, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -245,13 +254,14 @@ struct GxImg {
 // step - these products are bound neither by load latency nor by the operand split but by the L2 / Infinity-Cache traffic of
 // 64 x 64 tiles ((64 + 64) K operand elements per 64 * 64 * K multiplications: the 7x7 head's forward moves 205 MB for 32 MB of
 // distinct data).  (The one-stage form takes what the 16-byte loads cannot.)
-template <bool AK, bool BNC, int DEPTH = 1>
-__global__ __launch_bounds__(256, 4) void gemm_x3_kernel(GemmP p) {
+// (the body is a __device__ function of the tile indices and their grid, as gemm_tile_body: the grouped kernel runs it too)
+template <bool AK, bool BNC, int DEPTH>
+__device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __restrict__ gx_lds, unsigned bx, unsigned by, unsigned bz,
+                                             unsigned gx, unsigned gy, unsigned gz) {
     using IA = GxImg<AK>;
     using IB = GxImg<!BNC>;
     constexpr int BM = 64, BN = 64, G4 = BM * BKX / 4 / 256;   // float4 groups per thread and operand
     constexpr int KQX = BKX / 4;                               // float4 groups along k
-    extern __shared__ __attribute__((aligned(16))) unsigned char gx_lds[];
     unsigned char* As = gx_lds;                                 // [3 planes][IA::BYTES]
     unsigned char* Bs = gx_lds + 3 * IA::BYTES;                 // [3 planes][IB::BYTES]
 
@@ -262,10 +272,9 @@ __global__ __launch_bounds__(256, 4) void gemm_x3_kernel(GemmP p) {
     // XCD-aware tile order: consecutive workgroup ids go round-robin to the 8 XCDs, so the tiles of
     // one (batch, K slice) - which share their A rows and B columns - used to be spread over all eight L2s.  Workgroup
     // w = (xcd, k) takes tile xcd * (tiles / 8) + k of the (z, y, x) order: one XCD works through whole (batch, K slice) planes.
-    unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     if (p.xcd) {
-        const unsigned lin = (unsigned)xcd_tile(bx + gridDim.x * (by + gridDim.y * bz), gridDim.x * gridDim.y * gridDim.z);
-        bx = lin % gridDim.x; by = (lin / gridDim.x) % gridDim.y; bz = lin / (gridDim.x * gridDim.y);
+        const unsigned lin = (unsigned)xcd_tile(bx + gx * (by + gy * bz), gx * gy * gz);
+        bx = lin % gx; by = (lin / gx) % gy; bz = lin / (gx * gy);
     }
     const int m0 = by * BM, n0 = bx * BN;
     const int batch = bz / p.splitk, split = bz % p.splitk;
@@ -444,44 +453,309 @@ __global__ __launch_bounds__(256, 4) void gemm_x3_kernel(GemmP p) {
     }
 }
 
-template <bool AK, bool BNC, int DEPTH>
-int launch_x3_variant(const GemmP& p, int batch, hipStream_t st) {
-    constexpr int LDS = 3 * (GxImg<AK>::BYTES + GxImg<!BNC>::BYTES);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_x3_kernel<AK, BNC, DEPTH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    dim3 grid(cdiv(p.N, 64), cdiv(p.M, 64), batch * p.splitk), block(256);
-    hipLaunchKernelGGL((gemm_x3_kernel<AK, BNC, DEPTH>), grid, block, LDS, st, p);
-    JVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-template <bool AK, bool BNC>
-int launch_x3_ab(const GemmP& p, int batch, hipStream_t st) {
-    // deep prefetch: 16-byte loads on both operands, K range a multiple of 4 (kchunk is a multiple of 32)
-    const bool deep = p.vecA && p.vecB && p.K % 4 == 0
-                      && (AK || p.M % 4 == 0) && (!BNC || p.N % 4 == 0);
-    if (deep) return launch_x3_variant<AK, BNC, 3>(p, batch, st);
-    return launch_x3_variant<AK, BNC, 1>(p, batch, st);
-}
-
-int launch_x3(const GemmP& p0, int batch, hipStream_t st) {
-    GemmP p = p0;
-    p.xcd = 1;                                                 // XCD-aware tile order
-    const bool ak = (p.sAk == 1), bnc = (p.sBn == 1);
-    if (ak && bnc) return launch_x3_ab<true, true>(p, batch, st);
-    if (ak) return launch_x3_ab<true, false>(p, batch, st);
-    if (bnc) return launch_x3_ab<false, true>(p, batch, st);
-    return launch_x3_ab<false, false>(p, batch, st);
+template <bool AK, bool BNC, int DEPTH = 1>
+__global__ __launch_bounds__(256, 4) void gemm_x3_kernel(GemmP p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gx_lds[];
+    gemm_x3_body<AK, BNC, DEPTH>(p, gx_lds, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z);
 }
 
 inline bool gemm_x3_on(int K) {                               // jvae_conv2d_set_split(0): the fp32 matrix-core kernel
     return K >= 64 && jvae_conv5_x3_enabled();
 }
+
+// ---- plan: what one product runs - its GemmP, the kernel variant and the grid.  The single-product entries and the grouped entry
+// take it from gemm_plan() alone, so a product cannot get another kernel, tile or K slicing because it shares a launch.
+//   variant 0 ... 7   gemm_kernel<BM, BN, AK, BNC>:      (BM == 128 ? 4 : 0) + 2 * AK + BNC        __launch_bounds__(256)
+//   variant 8 ... 15  gemm_x3_kernel<AK, BNC, DEPTH>:    8 + 4 * AK + 2 * BNC + (DEPTH == 3)       __launch_bounds__(256, 4)
+constexpr int VAR_X3 = 8;
+struct GemmPlan {
+    GemmP p;
+    int variant;
+    unsigned gx, gy, gz;     // the grid of the stand-alone launch = the virtual grid of the record in a group
+    int lds;                 // dynamic LDS bytes (the x3 variants; the tile variants: what their static arrays take)
+};
+
+template <bool AK, bool BNC>
+constexpr int x3_lds() { return 3 * (GxImg<AK>::BYTES + GxImg<!BNC>::BYTES); }
+
+inline int variant_lds(int v) {
+    if (v < 4) return TileLds<64, 64>::BYTES;
+    if (v < VAR_X3) return TileLds<128, 128>::BYTES;
+    switch ((v - VAR_X3) >> 1) {
+        case 0: return x3_lds<false, false>();
+        case 1: return x3_lds<false, true>();
+        case 2: return x3_lds<true, false>();
+        default: return x3_lds<true, true>();
+    }
+}
+
+struct GemmArgs {
+    int M, N, K, batch;
+    const float* A; long sAm, sAk, sAb;
+    const float* B; long sBk, sBn, sBb;
+    float* C; long sCm, sCn, sCb;
+    const float* bias; int bias_mode, bias_div, flags, splitk;
+    int part;                // != 0: jvae_gemm_launch_part - partial products stored sCsplit apart, splitk = the wanted number
+    long sCsplit;
+};
+
+// 0: *pl is a launch; 1: nothing to do (an empty product); < 0: invalid.  pl->p.splitk is the number of K slices made.
+int gemm_plan(const GemmArgs& a, GemmPlan* pl) {
+    if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return 1;
+    if (!a.A || !a.B || !a.C) return JVAE_EINVAL;
+    if (a.part ? a.K <= 0 : a.K < 0) return JVAE_EINVAL;
+    if (!a.part && a.bias_mode && !a.bias) return JVAE_EINVAL;
+    GemmP& p = pl->p;
+    p.A = a.A; p.sAm = a.sAm; p.sAk = a.sAk; p.sAb = a.sAb;
+    p.B = a.B; p.sBk = a.sBk; p.sBn = a.sBn; p.sBb = a.sBb;
+    p.C = a.C; p.sCm = a.sCm; p.sCn = a.sCn; p.sCb = a.sCb;
+    p.bias = a.part ? nullptr : a.bias;
+    p.bias_mode = a.part ? 0 : a.bias_mode;
+    p.bias_div = (!a.part && a.bias_div > 0) ? a.bias_div : 1;
+    p.M = a.M; p.N = a.N; p.K = a.K;
+    int splitk = a.splitk < 1 ? 1 : a.splitk;
+    const int ktiles = cdiv(a.K, BK);
+    if (splitk > ktiles) splitk = ktiles > 0 ? ktiles : 1;
+    p.kchunk = cdiv(ktiles, splitk) * BK;
+    splitk = a.K > 0 ? cdiv(a.K, p.kchunk) : 1;
+    p.splitk = splitk;
+    if (a.part) {
+        p.flags = 8;
+        p.sCsplit = a.sCsplit;
+    } else {
+        p.flags = a.flags & ~8;
+        p.sCsplit = 0;
+        if (splitk > 1) {
+            if (a.flags & 2) return JVAE_EINVAL;      // ReLU cannot follow a partial sum
+            p.flags |= 4;                             // caller pre-zeroes C (or wants accumulation)
+        }
+    }
+    // vector loads: contiguous direction has unit stride, everything else keeps 16-byte alignment
+    const bool ak = (a.sAk == 1), bnc = (a.sBn == 1);
+    p.vecA = aligned16(a.A) && (a.sAb % 4 == 0) && (ak ? (a.sAm % 4 == 0) : (a.sAm == 1 && a.sAk % 4 == 0));
+    p.vecB = aligned16(a.B) && (a.sBb % 4 == 0) && (bnc ? (a.sBk % 4 == 0) : (a.sBk == 1 && a.sBn % 4 == 0));
+    p.xcd = 0;
+    int bm = 64;
+    if (gemm_x3_on(a.K)) {
+        p.xcd = 1;                                                 // XCD-aware tile order
+        // deep prefetch: 16-byte loads on both operands, K range a multiple of 4 (kchunk is a multiple of 32)
+        const bool deep = p.vecA && p.vecB && p.K % 4 == 0 && (ak || p.M % 4 == 0) && (!bnc || p.N % 4 == 0);
+        pl->variant = VAR_X3 + 4 * ak + 2 * bnc + (deep ? 1 : 0);
+    } else {
+        const long tiles128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128) * a.batch * splitk;
+        if (!a.part && a.M > 64 && a.N > 64 && tiles128 >= 512) bm = 128;
+        pl->variant = (bm == 128 ? 4 : 0) + 2 * ak + (bnc ? 1 : 0);
+    }
+    pl->gx = cdiv(a.N, bm); pl->gy = cdiv(a.M, bm); pl->gz = (unsigned)a.batch * splitk;
+    pl->lds = variant_lds(pl->variant);
+    return 0;
+}
+
+template <typename F>
+int set_lds_once(F kernel, int lds, bool* done) {
+    if (!*done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return (int)e;
+        *done = true;
+    }
+    return 0;
+}
+
+template <int BM, bool AK, bool BNC>
+int launch_tile_variant(const GemmPlan& pl, hipStream_t st) {
+    hipLaunchKernelGGL((gemm_kernel<BM, BM, AK, BNC>), dim3(pl.gx, pl.gy, pl.gz), dim3(256), 0, st, pl.p);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+template <bool AK, bool BNC, int DEPTH>
+int launch_x3_variant(const GemmPlan& pl, hipStream_t st) {
+    static bool attr_set = false;
+    if (int rc = set_lds_once(&gemm_x3_kernel<AK, BNC, DEPTH>, x3_lds<AK, BNC>(), &attr_set)) return rc;
+    hipLaunchKernelGGL((gemm_x3_kernel<AK, BNC, DEPTH>), dim3(pl.gx, pl.gy, pl.gz), dim3(256), pl.lds, st, pl.p);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_plan(const GemmPlan& pl, hipStream_t st) {
+    switch (pl.variant) {
+        case 0: return launch_tile_variant<64, false, false>(pl, st);
+        case 1: return launch_tile_variant<64, false, true>(pl, st);
+        case 2: return launch_tile_variant<64, true, false>(pl, st);
+        case 3: return launch_tile_variant<64, true, true>(pl, st);
+        case 4: return launch_tile_variant<128, false, false>(pl, st);
+        case 5: return launch_tile_variant<128, false, true>(pl, st);
+        case 6: return launch_tile_variant<128, true, false>(pl, st);
+        case 7: return launch_tile_variant<128, true, true>(pl, st);
+        case 8: return launch_x3_variant<false, false, 1>(pl, st);
+        case 9: return launch_x3_variant<false, false, 3>(pl, st);
+        case 10: return launch_x3_variant<false, true, 1>(pl, st);
+        case 11: return launch_x3_variant<false, true, 3>(pl, st);
+        case 12: return launch_x3_variant<true, false, 1>(pl, st);
+        case 13: return launch_x3_variant<true, false, 3>(pl, st);
+        case 14: return launch_x3_variant<true, true, 1>(pl, st);
+        case 15: return launch_x3_variant<true, true, 3>(pl, st);
+    }
+    return JVAE_EINVAL;
+}
+
+// ---- grouped launch: up to JVAE_GEMM_GROUP_MAX independent products in ONE flat grid.  The records travel by value in the kernel
+// arguments (as PackTable does): nothing to upload, safe under graph capture.  A workgroup finds its record from blockIdx.x
+// (uniform over the workgroup) and runs that variant's body with the record's own virtual grid.  Every record starts at a
+// multiple of 8 workgroups, so that the XCD a workgroup runs on (flat id % 8) is the one xcd_tile() assumes for its tile; the
+// few workgroups of the padding return at once.
+// Which variants may share a launch: those with equal __launch_bounds__ - the eight gemm_kernel variants one launch
+// (gemm_group_tile_kernel), the eight gemm_x3_kernel variants another (gemm_group_x3_kernel).  A group that holds both kinds is
+// two launches.
+constexpr int GROUP_MAX = 8;
+struct GemmRec {
+    GemmP p;
+    int variant;
+    unsigned gx, gy, gz;
+    unsigned first;          // first flat workgroup of the record (a multiple of 8); 0xffffffff in unused records
+};
+struct GemmGroup {
+    GemmRec rec[GROUP_MAX];
+};
+
+struct GroupTile { unsigned r, bx, by, bz; bool live; };
+__device__ __forceinline__ GroupTile group_tile(const GemmGroup& g) {
+    unsigned r = 0;
+#pragma unroll
+    for (unsigned i = 1; i < GROUP_MAX; ++i)
+        if (blockIdx.x >= g.rec[i].first) r = i;
+    const GemmRec& rc = g.rec[r];
+    const unsigned local = blockIdx.x - rc.first;
+    GroupTile t;
+    t.r = r;
+    t.live = local < rc.gx * rc.gy * rc.gz;
+    t.bx = local % rc.gx; t.by = (local / rc.gx) % rc.gy; t.bz = local / (rc.gx * rc.gy);
+    return t;
+}
+
+// BIG: the 128 x 128 variants are compiled in.  They take 76-80 VGPRs + 64 AGPRs (occupancy 3) where the 64 x 64 variants take
+// 38-42 + 16 (occupancy 8), so a group of 64 x 64 tiles only has a kernel of its own.
+template <bool BIG>
+__global__ __launch_bounds__(256) void gemm_group_tile_kernel(GemmGroup g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char grp_lds[];
+    float* lds = reinterpret_cast<float*>(grp_lds);
+    const GroupTile t = group_tile(g);
+    if (!t.live) return;
+    const GemmRec& rc = g.rec[t.r];
+    switch (rc.variant) {
+        case 0: gemm_tile_body<64, 64, false, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+        case 1: gemm_tile_body<64, 64, false, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+        case 2: gemm_tile_body<64, 64, true, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+        case 3: gemm_tile_body<64, 64, true, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+    }
+    if constexpr (BIG) {
+        switch (rc.variant) {
+            case 4: gemm_tile_body<128, 128, false, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+            case 5: gemm_tile_body<128, 128, false, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+            case 6: gemm_tile_body<128, 128, true, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+            case 7: gemm_tile_body<128, 128, true, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
+        }
+    }
+}
+
+template <bool BIG>
+int launch_group_tile(const GemmGroup& g, unsigned total, int lds, hipStream_t st) {
+    static bool attr_set = false;
+    if (int rc = set_lds_once(&gemm_group_tile_kernel<BIG>, TileLds<BIG ? 128 : 64, BIG ? 128 : 64>::BYTES, &attr_set)) return rc;
+    hipLaunchKernelGGL(gemm_group_tile_kernel<BIG>, dim3(total), dim3(256), lds, st, g);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// MASK: bit (variant - 8) set = that variant's body is compiled in.  The union of all eight takes the registers of its largest
+// member (128 VGPRs, three of them spilled; occupancy 4 as every DEPTH = 3 variant has alone), so the variant sets the training
+// step uses have kernels of their own, which build to their members' counts: the two forward products of a pair of linear
+// layers (X3_FWD) and the dgrads and weight gradients of linear layers (X3_BWD).  Any other set takes the union.
+constexpr unsigned X3_FWD = 1u << (13 - VAR_X3), X3_BWD = (1u << (15 - VAR_X3)) | (1u << (11 - VAR_X3)), X3_ALL = 0xffu;
+
+template <unsigned MASK, int V, bool AK, bool BNC, int DEPTH>
+__device__ __forceinline__ void group_x3_case(const GemmRec& rc, unsigned char* lds, const GroupTile& t) {
+    if constexpr ((MASK >> (V - VAR_X3)) & 1u) {
+        if (rc.variant == V) gemm_x3_body<AK, BNC, DEPTH>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz);
+    }
+}
+
+template <unsigned MASK>
+__global__ __launch_bounds__(256, 4) void gemm_group_x3_kernel(GemmGroup g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char grp_lds[];
+    const GroupTile t = group_tile(g);
+    if (!t.live) return;
+    const GemmRec& rc = g.rec[t.r];
+    group_x3_case<MASK, 8, false, false, 1>(rc, grp_lds, t);
+    group_x3_case<MASK, 9, false, false, 3>(rc, grp_lds, t);
+    group_x3_case<MASK, 10, false, true, 1>(rc, grp_lds, t);
+    group_x3_case<MASK, 11, false, true, 3>(rc, grp_lds, t);
+    group_x3_case<MASK, 12, true, false, 1>(rc, grp_lds, t);
+    group_x3_case<MASK, 13, true, false, 3>(rc, grp_lds, t);
+    group_x3_case<MASK, 14, true, true, 1>(rc, grp_lds, t);
+    group_x3_case<MASK, 15, true, true, 3>(rc, grp_lds, t);
+}
+
+template <unsigned MASK>
+int launch_group_x3(const GemmGroup& g, unsigned total, int lds, hipStream_t st) {
+    static bool attr_set = false;
+    if (int rc = set_lds_once(&gemm_group_x3_kernel<MASK>, x3_lds<false, false>(), &attr_set)) return rc;
+    hipLaunchKernelGGL(gemm_group_x3_kernel<MASK>, dim3(total), dim3(256), lds, st, g);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// The plans of one kind (x3 or tile variants) as one launch; a single plan goes through the stand-alone kernel.
+int launch_group_kind(const GemmPlan* plans, int n, bool x3, hipStream_t st) {
+    GemmGroup g;
+    int cnt = 0, lds = 0, last = -1;
+    unsigned long total = 0;
+    for (int i = 0; i < n; ++i) {
+        if ((plans[i].variant >= VAR_X3) != x3) continue;
+        GemmRec& rc = g.rec[cnt++];
+        rc.p = plans[i].p; rc.variant = plans[i].variant;
+        rc.gx = plans[i].gx; rc.gy = plans[i].gy; rc.gz = plans[i].gz;
+        rc.first = (unsigned)total;
+        total += ((unsigned long)rc.gx * rc.gy * rc.gz + 7) & ~7ul;
+        if (total > 0x7fffffffUL) return JVAE_ENOTSUP;
+        if (plans[i].lds > lds) lds = plans[i].lds;
+        last = i;
+    }
+    if (cnt == 0) return 0;
+    if (cnt == 1) return launch_plan(plans[last], st);
+    for (int i = cnt; i < GROUP_MAX; ++i) { g.rec[i] = g.rec[0]; g.rec[i].first = 0xffffffffu; }
+    if (x3) {
+        unsigned mask = 0;
+        for (int i = 0; i < cnt; ++i) mask |= 1u << (g.rec[i].variant - VAR_X3);
+        if ((mask & ~X3_FWD) == 0) return launch_group_x3<X3_FWD>(g, (unsigned)total, lds, st);
+        if ((mask & ~X3_BWD) == 0) return launch_group_x3<X3_BWD>(g, (unsigned)total, lds, st);
+        return launch_group_x3<X3_ALL>(g, (unsigned)total, lds, st);
+    }
+    for (int i = 0; i < cnt; ++i)
+        if (g.rec[i].variant >= 4) return launch_group_tile<true>(g, (unsigned)total, lds, st);
+    return launch_group_tile<false>(g, (unsigned)total, lds, st);
+}
+
+int launch_group(const GemmPlan* plans, int n, hipStream_t st) {
+    if (int rc = launch_group_kind(plans, n, true, st)) return rc;
+    return launch_group_kind(plans, n, false, st);
+}
+
+// [lo, hi] byte range a plan's product may write (a hull: strided outputs that interleave count as overlapping)
+void plan_out_range(const GemmPlan& pl, uintptr_t* lo, uintptr_t* hi) {
+    const GemmP& p = pl.p;
+    const long batch = pl.gz / p.splitk;
+    long neg = 0, pos = 0;
+    auto span = [&](long stride, long count) {
+        const long d = stride * (count - 1);
+        if (d < 0) neg += d; else pos += d;
+    };
+    span(p.sCm, p.M); span(p.sCn, p.N); span(p.sCb, batch);
+    if (p.flags & 8) span(p.sCsplit, p.splitk);
+    *lo = reinterpret_cast<uintptr_t>(p.C + neg);
+    *hi = reinterpret_cast<uintptr_t>(p.C + pos) + sizeof(float) - 1;
+}
+
 
 }  // namespace
 
@@ -500,35 +774,12 @@ int jvae_gemm_launch_ex(int M, int N, int K, int batch,
                         const float* B, long sBk, long sBn, long sBb,
                         float* C, long sCm, long sCn, long sCb,
                         const float* bias, int bias_mode, int bias_div, int flags, int splitk, hipStream_t st) {
-    if (M <= 0 || N <= 0 || batch <= 0) return 0;
-    if (K < 0 || !A || !B || !C) return JVAE_EINVAL;
-    if (bias_mode && !bias) return JVAE_EINVAL;
-    GemmP p;
-    p.A = A; p.sAm = sAm; p.sAk = sAk; p.sAb = sAb;
-    p.B = B; p.sBk = sBk; p.sBn = sBn; p.sBb = sBb;
-    p.C = C; p.sCm = sCm; p.sCn = sCn; p.sCb = sCb;
-    p.bias = bias; p.bias_mode = bias_mode; p.bias_div = bias_div > 0 ? bias_div : 1;
-    p.M = M; p.N = N; p.K = K;
-    if (splitk < 1) splitk = 1;
-    int ktiles = cdiv(K, BK);
-    if (splitk > ktiles) splitk = ktiles > 0 ? ktiles : 1;
-    p.kchunk = cdiv(ktiles, splitk) * BK;
-    splitk = K > 0 ? cdiv(K, p.kchunk) : 1;
-    p.splitk = splitk;
-    p.flags = flags & ~8;
-    p.sCsplit = 0;
-    if (splitk > 1) {
-        if (flags & 2) return JVAE_EINVAL;        // ReLU cannot follow a partial sum
-        p.flags |= 4;                             // caller pre-zeroes C (or wants accumulation)
-    }
-    // vector loads: contiguous direction has unit stride, everything else keeps 16-byte alignment
-    const bool ak = (sAk == 1), bnc = (sBn == 1);
-    p.vecA = aligned16(A) && (sAb % 4 == 0) && (ak ? (sAm % 4 == 0) : (sAm == 1 && sAk % 4 == 0));
-    p.vecB = aligned16(B) && (sBb % 4 == 0) && (bnc ? (sBk % 4 == 0) : (sBk == 1 && sBn % 4 == 0));
-    if (gemm_x3_on(K)) return launch_x3(p, batch, st);
-    const long tiles128 = (long)cdiv(M, 128) * cdiv(N, 128) * batch * splitk;
-    if (M > 64 && N > 64 && tiles128 >= 512) return launch_tile<128, 128>(p, batch, st);
-    return launch_tile<64, 64>(p, batch, st);
+    const GemmArgs a = {M, N, K, batch, A, sAm, sAk, sAb, B, sBk, sBn, sBb, C, sCm, sCn, sCb,
+                        bias, bias_mode, bias_div, flags, splitk, 0, 0};
+    GemmPlan pl;
+    const int rc = gemm_plan(a, &pl);
+    if (rc) return rc < 0 ? rc : 0;
+    return launch_plan(pl, st);
 }
 
 // Deterministic split-K: K is cut into *splits pieces whose partial products are STORED side by side (part + s*sCsplit,
@@ -539,42 +790,91 @@ int jvae_gemm_launch_part(int M, int N, int K, int batch,
                           float* part, long sCm, long sCn, long sCb, long sCsplit, int want_splits, int* splits,
                           hipStream_t st) {
     if (splits) *splits = 0;
-    if (M <= 0 || N <= 0 || batch <= 0) return 0;
-    if (K <= 0 || !A || !B || !part || !splits) return JVAE_EINVAL;
-    GemmP p;
-    p.A = A; p.sAm = sAm; p.sAk = sAk; p.sAb = sAb;
-    p.B = B; p.sBk = sBk; p.sBn = sBn; p.sBb = sBb;
-    p.C = part; p.sCm = sCm; p.sCn = sCn; p.sCb = sCb;
-    p.bias = nullptr; p.bias_mode = 0; p.bias_div = 1;
-    p.M = M; p.N = N; p.K = K;
-    int splitk = want_splits < 1 ? 1 : want_splits;
-    const int ktiles = cdiv(K, BK);
-    if (splitk > ktiles) splitk = ktiles;
-    p.kchunk = cdiv(ktiles, splitk) * BK;
-    splitk = cdiv(K, p.kchunk);
-    p.splitk = splitk;
-    p.flags = 8;
-    p.sCsplit = sCsplit;
-    const bool ak = (sAk == 1), bnc = (sBn == 1);
-    p.vecA = aligned16(A) && (sAb % 4 == 0) && (ak ? (sAm % 4 == 0) : (sAm == 1 && sAk % 4 == 0));
-    p.vecB = aligned16(B) && (sBb % 4 == 0) && (bnc ? (sBk % 4 == 0) : (sBk == 1 && sBn % 4 == 0));
-    *splits = splitk;
-    if (gemm_x3_on(K)) return launch_x3(p, batch, st);
-    return launch_tile<64, 64>(p, batch, st);
+    const GemmArgs a = {M, N, K, batch, A, sAm, sAk, sAb, B, sBk, sBn, sBb, part, sCm, sCn, sCb,
+                        nullptr, 0, 1, 0, want_splits, 1, sCsplit};
+    GemmPlan pl;
+    const int rc = gemm_plan(a, &pl);
+    if (rc) return rc < 0 ? rc : 0;
+    if (!splits) return JVAE_EINVAL;
+    *splits = pl.p.splitk;
+    return launch_plan(pl, st);
+}
+
+// Plans for n <= 8 descriptors (jvae_hip.h: JvaeGemmDesc), checked as a whole before anything is launched: an invalid descriptor or
+// two outputs that overlap return JVAE_EINVAL, more than 8 JVAE_ENOTSUP.  Empty products are dropped.
+extern "C" int jvae_gemm_group_f32(const JvaeGemmDesc* descs, int n, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !descs) return JVAE_EINVAL;
+    if (n > GROUP_MAX) return JVAE_ENOTSUP;
+    GemmPlan plans[GROUP_MAX];
+    uintptr_t lo[GROUP_MAX], hi[GROUP_MAX];
+    int cnt = 0;
+    for (int i = 0; i < n; ++i) {
+        const JvaeGemmDesc& d = descs[i];
+        if (d.splits) *d.splits = 0;
+        const bool part = d.want_splits > 0;
+        const GemmArgs a = {d.M, d.N, d.K, d.batch, d.A, d.sAm, d.sAk, d.sAb, d.B, d.sBk, d.sBn, d.sBb, d.C, d.sCm, d.sCn, d.sCb,
+                            d.bias, d.bias_mode, 1, d.flags, part ? d.want_splits : d.splitk, part ? 1 : 0, d.sCsplit};
+        const int rc = gemm_plan(a, &plans[cnt]);
+        if (rc < 0) return rc;
+        if (rc) continue;
+        if (part && !d.splits) return JVAE_EINVAL;
+        plan_out_range(plans[cnt], &lo[cnt], &hi[cnt]);
+        for (int j = 0; j < cnt; ++j)
+            if (lo[cnt] <= hi[j] && lo[j] <= hi[cnt]) return JVAE_EINVAL;
+        ++cnt;
+    }
+    // (the numbers of slices are reported only once the whole group is known to be valid)
+    for (int i = 0, k = 0; i < n; ++i) {
+        const JvaeGemmDesc& d = descs[i];
+        if (d.M <= 0 || d.N <= 0 || d.batch <= 0) continue;
+        if (d.splits) *d.splits = plans[k].p.splitk;
+        ++k;
+    }
+    return launch_group(plans, cnt, (hipStream_t)stream);
 }
 
 // y[i] = [relu](bias[i % N] + sum_s part[s][i]) in a fixed order: the deterministic second half of a split-K product
-// whose S partial products were written side by side by a batched launch (batch = K slices).
-__global__ __launch_bounds__(256) void splitk_fold_kernel(const float* __restrict__ part, const float* __restrict__ bias,
-                                                          float* __restrict__ y, int S, long MN, int N, int relu,
-                                                          int accumulate, int bias_div) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < MN; i += (long)gridDim.x * blockDim.x) {
+// whose S partial products were written side by side by a batched launch (batch = K slices).  `block` of `blocks`: the
+// workgroup's place in the job's own grid (the hardware's in the stand-alone kernel, the record's in the grouped one).
+__device__ __forceinline__ void splitk_fold_body(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y,
+                                                 int S, long MN, int N, int relu, int accumulate, int bias_div, unsigned block,
+                                                 unsigned blocks) {
+    for (long i = (long)block * blockDim.x + threadIdx.x; i < MN; i += (long)blocks * blockDim.x) {
         float v = bias ? bias[(i / bias_div) % N] : 0.f;
         for (int s = 0; s < S; ++s) v += part[(long)s * MN + i];
         if (accumulate) v += y[i];
         y[i] = relu ? fmaxf(v, 0.f) : v;
     }
 }
+
+__global__ __launch_bounds__(256) void splitk_fold_kernel(const float* __restrict__ part, const float* __restrict__ bias,
+                                                          float* __restrict__ y, int S, long MN, int N, int relu,
+                                                          int accumulate, int bias_div) {
+    splitk_fold_body(part, bias, y, S, MN, N, relu, accumulate, bias_div, blockIdx.x, gridDim.x);
+}
+
+// Up to 8 such folds in one flat grid: the records by value in the kernel arguments, as GemmGroup.
+struct FoldRec {
+    const float* part; const float* bias; float* y;
+    long MN;
+    int S, N, relu, accumulate, bias_div;
+    unsigned first, blocks;      // first flat workgroup (0xffffffff: unused record) and the job's own grid
+};
+struct FoldGroup {
+    FoldRec rec[8];
+};
+
+__global__ __launch_bounds__(256) void splitk_fold_group_kernel(FoldGroup g) {
+    unsigned r = 0;
+#pragma unroll
+    for (unsigned i = 1; i < 8; ++i)
+        if (blockIdx.x >= g.rec[i].first) r = i;
+    const FoldRec& rc = g.rec[r];
+    splitk_fold_body(rc.part, rc.bias, rc.y, rc.S, rc.MN, rc.N, rc.relu, rc.accumulate, rc.bias_div, blockIdx.x - rc.first, rc.blocks);
+}
+
+inline int fold_blocks(long MN) { return (int)((MN + 255) / 256 > 4096 ? 4096 : (MN + 255) / 256); }
 
 // The same for partial products stored [slice][position q][image n][channel cs] - rows of cs: the product's lanes run along cs, so its
 // stores are 128-byte segments; in the OUTPUT's own layout [n][cs][q] they were 4-byte stores 4 * Ps bytes apart (26 MB of
@@ -605,7 +905,7 @@ int jvae_splitk_fold_qn(const float* part, const float* bias, float* y, int S, i
 int jvae_splitk_fold(const float* part, const float* bias, float* y, int S, long MN, int N, int relu, int accumulate,
                      hipStream_t st, int bias_div) {
     if (MN == 0) return 0;
-    const int blocks = (int)((MN + 255) / 256 > 4096 ? 4096 : (MN + 255) / 256);
+    const int blocks = fold_blocks(MN);
     hipLaunchKernelGGL(splitk_fold_kernel, dim3(blocks), dim3(256), 0, st, part, bias, y, S, MN, N, relu, accumulate,
                        bias_div > 0 ? bias_div : 1);
     JVAE_LAUNCH_CHECK();
@@ -616,6 +916,39 @@ extern "C" int jvae_splitk_fold_f32(const float* part, const float* bias, float*
                                     int accumulate, void* stream) {
     if (!part || !y || S < 1 || MN < 0 || N < 1) return JVAE_EINVAL;
     return jvae_splitk_fold(part, bias, y, S, MN, N, relu, accumulate, (hipStream_t)stream);
+}
+
+extern "C" int jvae_splitk_fold_group_f32(const JvaeFoldDesc* descs, int n, void* stream) {
+    if (n == 0) return 0;
+    if (n < 0 || !descs) return JVAE_EINVAL;
+    if (n > 8) return JVAE_ENOTSUP;
+    FoldGroup g;
+    int cnt = 0, last = -1;
+    unsigned total = 0;
+    for (int i = 0; i < n; ++i) {
+        const JvaeFoldDesc& d = descs[i];
+        if (!d.part || !d.y || d.S < 1 || d.MN < 0 || d.N < 1) return JVAE_EINVAL;
+        for (int j = 0; j < i; ++j) {            // outputs of one launch must not overlap
+            const JvaeFoldDesc& e = descs[j];
+            if (d.MN > 0 && e.MN > 0 && d.y < e.y + e.MN && e.y < d.y + d.MN) return JVAE_EINVAL;
+        }
+        if (d.MN == 0) continue;
+        FoldRec& rc = g.rec[cnt++];
+        rc.part = d.part; rc.bias = d.bias; rc.y = d.y; rc.MN = d.MN;
+        rc.S = d.S; rc.N = d.N; rc.relu = d.relu; rc.accumulate = d.accumulate; rc.bias_div = 1;
+        rc.first = total; rc.blocks = (unsigned)fold_blocks(d.MN);
+        total += rc.blocks;
+        last = i;
+    }
+    if (cnt == 0) return 0;
+    if (cnt == 1) {
+        const JvaeFoldDesc& d = descs[last];
+        return jvae_splitk_fold(d.part, d.bias, d.y, d.S, d.MN, d.N, d.relu, d.accumulate, (hipStream_t)stream);
+    }
+    for (int i = cnt; i < 8; ++i) { g.rec[i] = g.rec[0]; g.rec[i].first = 0xffffffffu; }
+    hipLaunchKernelGGL(splitk_fold_group_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
+    JVAE_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int jvae_gemm_f32(int M, int N, int K, int batch,

@@ -15,10 +15,30 @@ LIB_PATH = os.environ.get('JVAE_HIP_LIB') or os.path.join(_HERE, 'libjvae_hip.so
 _lib = None
 
 P = c_void_p
+
+
+class GemmDesc(ctypes.Structure):
+    """JvaeGemmDesc (include/jvae_hip.h): one product of jvae_gemm_group_f32."""
+    _fields_ = ([('M', c_int), ('N', c_int), ('K', c_int), ('batch', c_int)]
+                + [('A', P), ('sAm', c_long), ('sAk', c_long), ('sAb', c_long)]
+                + [('B', P), ('sBk', c_long), ('sBn', c_long), ('sBb', c_long)]
+                + [('C', P), ('sCm', c_long), ('sCn', c_long), ('sCb', c_long)]
+                + [('bias', P), ('bias_mode', c_int), ('flags', c_int), ('splitk', c_int)]
+                + [('want_splits', c_int), ('sCsplit', c_long), ('splits', POINTER(c_int))])
+
+
+class FoldDesc(ctypes.Structure):
+    """JvaeFoldDesc: one job of jvae_splitk_fold_group_f32."""
+    _fields_ = [('part', P), ('bias', P), ('y', P), ('S', c_int), ('MN', c_long), ('N', c_int), ('relu', c_int),
+                ('accumulate', c_int)]
+
+
 _SIGS = {
     'jvae_version': (c_char_p, []),
     'jvae_gemm_f32': (c_int, [c_int] * 4 + [P, c_long, c_long, c_long] * 3 + [P, c_int, c_int, c_int, P]),
     'jvae_splitk_fold_f32': (c_int, [P, P, P, c_int, c_long, c_int, c_int, c_int, P]),
+    'jvae_gemm_group_f32': (c_int, [POINTER(GemmDesc), c_int, P]),
+    'jvae_splitk_fold_group_f32': (c_int, [POINTER(FoldDesc), c_int, P]),
     'jvae_conv2d_workspace_bytes': (c_size_t, [c_int] * 11),
     'jvae_conv2d_set_split_bf16': (c_int, [c_int]),
     'jvae_conv2d_set_split_shape16': (c_int, [c_int]),

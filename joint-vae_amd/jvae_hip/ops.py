@@ -69,6 +69,50 @@ def gemm(M, N, K, A, sA, B, sB, C, sC, bias=None, bias_mode=0, flags=0, splitk=1
     L.check(rc, 'jvae_gemm_f32')
 
 
+def gemm_desc(M, N, K, A, sA, B, sB, C, sC, bias=None, bias_mode=0, flags=0, splitk=1, batch=1):
+    """The arguments of gemm() as one record of a grouped launch (gemm_group)."""
+    return (M, N, K, batch, A, sA, B, sB, C, sC, bias, bias_mode, flags, splitk)
+
+
+def gemm_group(descs):
+    """Independent products (gemm_desc records, at most 8, outputs that do not overlap) in ONE launch on the current stream.
+    Every product runs the kernel, tiles and K slices that gemm() gives it alone: the same bits."""
+    lib = L.load()
+    arr = (L.GemmDesc * max(len(descs), 1))()
+    for d, (M, N, K, batch, A, sA, B, sB, C, sC, bias, bias_mode, flags, splitk) in zip(arr, descs):
+        d.M, d.N, d.K, d.batch = M, N, K, batch
+        d.A, (d.sAm, d.sAk, d.sAb) = L.ptr(A), sA
+        d.B, (d.sBk, d.sBn, d.sBb) = L.ptr(B), sB
+        d.C, (d.sCm, d.sCn, d.sCb) = L.ptr(C), sC
+        d.bias, d.bias_mode, d.flags, d.splitk = L.ptr(bias), bias_mode, flags, splitk
+    L.check(lib.jvae_gemm_group_f32(arr, len(descs), L.stream_ptr()), 'jvae_gemm_group_f32')
+
+
+def splitk_fold_group(jobs):
+    """jobs: (part, bias, y, S, MN, N, relu, accumulate) as for jvae_splitk_fold_f32, at most 8, in ONE launch."""
+    lib = L.load()
+    arr = (L.FoldDesc * max(len(jobs), 1))()
+    for d, (part, bias, y, S, MN, N, relu, accumulate) in zip(arr, jobs):
+        d.part, d.bias, d.y = L.ptr(part), L.ptr(bias), L.ptr(y)
+        d.S, d.MN, d.N, d.relu, d.accumulate = S, MN, N, relu, accumulate
+    L.check(lib.jvae_splitk_fold_group_f32(arr, len(jobs), L.stream_ptr()), 'jvae_splitk_fold_group_f32')
+
+
+def _run_products(descs, folds):
+    """The products of one dependency level, then their folds: one launch each when there is more than one."""
+    if len(descs) == 1:
+        M, N, K, batch, A, sA, B, sB, C, sC, bias, bias_mode, flags, splitk = descs[0]
+        gemm(M, N, K, A, sA, B, sB, C, sC, bias=bias, bias_mode=bias_mode, flags=flags, splitk=splitk, batch=batch)
+    elif descs:
+        gemm_group(descs)
+    if len(folds) == 1:
+        part, bias, y, S, MN, N, relu, accumulate = folds[0]
+        L.check(L.load().jvae_splitk_fold_f32(L.ptr(part), L.ptr(bias), L.ptr(y), S, MN, N, relu, accumulate, L.stream_ptr()),
+                'jvae_splitk_fold_f32')
+    elif folds:
+        splitk_fold_group(folds)
+
+
 def channel_sum(t, N, C, P, out=None, accumulate=False):
     lib = L.load()
     if out is None:
@@ -132,36 +176,126 @@ class _Linear(torch.autograd.Function):
             g = torch.empty_like(gy)
             L.check(lib.jvae_act_bwd_f32(L.ptr(gy), L.ptr(y), L.ptr(g), gy.numel(), ctx.act, L.stream_ptr()), 'act_bwd')
             gy = g
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty((R, I), device=gy.device, dtype=torch.float32)
-            gemm(R, I, O, gy, (O, 1, 0), w, (I, 1, 0), gx, (I, 1, 0))
+        descs, folds = [], []
+        # the dgrad and the weight-gradient product share gy and nothing else: one launch when both are needed
+        gx, gw = _linear_bwd_products(gy, x2, w, ctx.w_ref, ctx.needs_input_grad[0], ctx.needs_input_grad[1], descs, folds)
+        _run_products(descs, folds)
+        if gx is not None:
             gx = gx.reshape(ctx.xshape)
-        if ctx.needs_input_grad[1]:
-            slot = _grad_slot(ctx.w_ref)
-            gw = slot if slot is not None else torch.zeros((O, I), device=gy.device, dtype=torch.float32)
-            S = _linear_split(O, I, R)
-            if S > 1:           # few (O, I) tiles: batch rows sliced over the launch's batch dimension, fixed-order fold
-                part = torch.empty((S, O, I), device=gy.device, dtype=torch.float32)
-                Rs = R // S
-                gemm(O, I, Rs, gy, (1, O, Rs * O), x2, (I, 1, Rs * I), part, (I, 1, O * I), batch=S)
-                L.check(lib.jvae_splitk_fold_f32(L.ptr(part), None, L.ptr(gw), S, O * I, I, 0, 1, L.stream_ptr()),
-                        'jvae_splitk_fold_f32')
-            else:
-                gemm(O, I, R, gy, (1, O, 0), x2, (I, 1, 0), gw, (I, 1, 0), flags=1)      # no atomics: deterministic
-            if slot is not None:
-                gw = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            slot = _grad_slot(ctx.b_ref)
-            if slot is not None:
-                channel_sum(gy, R, O, 1, out=slot, accumulate=True)
-            else:
-                gb = channel_sum(gy, R, O, 1)
+        gb = _linear_bias_grad(gy, ctx.b_ref) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return gx, gw, gb, None
+
+
+def _linear_fwd_products(x2, w, b, act, descs, folds):
+    """y = x2 W^T + b as records for _run_products: the product (K slices as the batch of the launch when the (R, O) output
+    alone gives too few tiles) and, for the sliced form, the fixed-order fold (+bias, ReLU).  Returns y."""
+    R, I = x2.shape
+    O = w.shape[0]
+    y = torch.empty((R, O), device=x2.device, dtype=torch.float32)
+    S = _linear_split(R, O, I)
+    if S > 1:
+        part = torch.empty((S, R, O), device=x2.device, dtype=torch.float32)
+        Ks = I // S
+        descs.append(gemm_desc(R, O, Ks, x2, (I, 1, Ks), w, (1, I, Ks), part, (O, 1, R * O), batch=S))
+        folds.append((part, b, y, S, R * O, O, int(act == RELU), 0))
+    else:
+        descs.append(gemm_desc(R, O, I, x2, (I, 1, 0), w, (1, I, 0), y, (O, 1, 0), bias=b, bias_mode=1 if b is not None else 0,
+                               flags=2 if act == RELU else 0))
+    return y
+
+
+def _linear_bwd_products(gy, x2, w, w_ref, need_x, need_w, descs, folds):
+    """The dgrad and weight-gradient products of one linear layer as records for _run_products.  Returns (gx, gw): gx (R, I) or
+    None; gw None when it was not asked for or goes straight into the parameter's gradient slot."""
+    R, I = x2.shape
+    O = w.shape[0]
+    gx = gw = None
+    if need_x:
+        gx = torch.empty((R, I), device=gy.device, dtype=torch.float32)
+        descs.append(gemm_desc(R, I, O, gy, (O, 1, 0), w, (I, 1, 0), gx, (I, 1, 0)))
+    if need_w:
+        slot = _grad_slot(w_ref)
+        gw = slot if slot is not None else torch.zeros((O, I), device=gy.device, dtype=torch.float32)
+        S = _linear_split(O, I, R)
+        if S > 1:           # few (O, I) tiles: batch rows sliced over the launch's batch dimension, fixed-order fold
+            part = torch.empty((S, O, I), device=gy.device, dtype=torch.float32)
+            Rs = R // S
+            descs.append(gemm_desc(O, I, Rs, gy, (1, O, Rs * O), x2, (I, 1, Rs * I), part, (I, 1, O * I), batch=S))
+            folds.append((part, None, gw, S, O * I, I, 0, 1))
+        else:
+            descs.append(gemm_desc(O, I, R, gy, (1, O, 0), x2, (I, 1, 0), gw, (I, 1, 0), flags=1))      # no atomics: deterministic
+        if slot is not None:
+            gw = None
+    return gx, gw
+
+
+def _linear_bias_grad(gy, b_ref):
+    R, O = gy.shape
+    slot = _grad_slot(b_ref)
+    if slot is not None:
+        channel_sum(gy, R, O, 1, out=slot, accumulate=True)
+        return None
+    return channel_sum(gy, R, O, 1)
 
 
 def linear(x, w, b=None, act=IDENT):
     return _Linear.apply(x, w, b, act)
+
+
+class _LinearPair(torch.autograd.Function):
+    """Two linear layers without activation on the same input (the latent heads): (x W0^T + b0, x W1^T + b1).  The two forward
+    products are one launch and their folds another; backward runs both dgrads and both weight-gradient products as one launch
+    and the two weight folds as another.  Every product and fold is the one _Linear issues: the same bits."""
+
+    @staticmethod
+    def forward(ctx, x, w0, b0, w1, b1):
+        x2 = _c(_f32(x, 'linear_pair').reshape(-1, x.shape[-1]))
+        ws = (_c(w0), _c(w1))
+        descs, folds = [], []
+        ys = [_linear_fwd_products(x2, w, b, IDENT, descs, folds) for w, b in zip(ws, (b0, b1))]
+        _run_products(descs, folds)
+        ctx.save_for_backward(x2, *ws)
+        ctx.xshape = x.shape
+        ctx.refs = ((w0, b0), (w1, b1))
+        ctx.set_materialize_grads(False)
+        return tuple(y.reshape(*x.shape[:-1], y.shape[1]) for y in ys)
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        x2, *ws = ctx.saved_tensors
+        R = x2.shape[0]
+        descs, folds = [], []
+        out = []
+        gxs = []
+        gys = []
+        for h, g in enumerate((g0, g1)):
+            if g is None:           # this head's output was not used: no gradient from it, as with two linear() calls
+                out += [None, None]
+                gys.append(None)
+                continue
+            gy = _c(g.reshape(R, ws[h].shape[0]))
+            gx, gw = _linear_bwd_products(gy, x2, ws[h], ctx.refs[h][0], ctx.needs_input_grad[0], ctx.needs_input_grad[1 + 2 * h],
+                                          descs, folds)
+            if gx is not None:
+                gxs.append(gx)
+            out += [gw, None]
+            gys.append(gy)
+        _run_products(descs, folds)
+        for h, gy in enumerate(gys):
+            b_ref = ctx.refs[h][1]
+            if gy is not None and b_ref is not None and ctx.needs_input_grad[2 + 2 * h]:
+                out[1 + 2 * h] = _linear_bias_grad(gy, b_ref)
+        gx = None
+        if gxs:
+            gx = (gxs[0] if len(gxs) == 1 else torch.add(gxs[0], gxs[1])).reshape(ctx.xshape)
+        return (gx, *out)
+
+
+def linear_pair(x, w0, b0, w1, b1):
+    """(linear(x, w0, b0), linear(x, w1, b1)) with the independent products of the two layers sharing their launches."""
+    if w0 is w1:            # one gradient slot for both heads: their weight-gradient folds would depend on each other
+        return linear(x, w0, b0), linear(x, w1, b1)
+    return _LinearPair.apply(x, w0, b0, w1, b1)
 
 
 # ------------------------------------------------------------------------------------------- conv

@@ -332,7 +332,11 @@ class Encoder(nn.Module):
         """Trunk + the two heads: (u, mu, raw log-variance) — raw = before the +-20 clip."""
         u = x if y is None else torch.cat((x, y), dim=-1)
         u = self.dense_projs(u)
-        return u, self.dense_mean(u), (None if self.forced_variance else self.dense_log_var(u))
+        if self.forced_variance:
+            return u, self.dense_mean(u), None
+        # the two heads share their input and nothing else: their products run in the same launches (ops.linear_pair)
+        mu, lv = ops.linear_pair(u, self.dense_mean.weight, self.dense_mean.bias, self.dense_log_var.weight, self.dense_log_var.bias)
+        return u, mu, lv
 
     def encode(self, x, y_onehot, labels, kl_var_weighting=1., epsilon=None):
         """Fused path used by the training step: heads, then ONE latent kernel for clip + samples + KL.

@@ -60,6 +60,26 @@ typedef struct JvaeGemmDesc {
 } JvaeGemmDesc;
 int jvae_gemm_group_f32(const JvaeGemmDesc* descs, int n, void* stream);
 
+/* Host-only query of the plan the dense entry points take for a descriptor (nothing is initialised on the device, nothing is
+ * launched; the operand pointers are looked at for their alignment only, *d->splits is not written).  want_splits > 0 means the
+ * stored-slices form, as in jvae_gemm_group_f32.  Reads the split-bf16 switch (jvae_conv2d_set_split_bf16) like every call.
+ * variant: 0 ... 7 the fp32 MFMA tile kernel, 8 ... 15 the split-bf16 kernel (name: jvae_gemm_variant_name); gx, gy, gz the
+ * grid (gz = batch * slices); slices the K slices made, kchunk the K elements of a slice (a multiple of 32; 0 when K = 0);
+ * vecA / vecB whether the operand is read with 16-byte loads; lds the LDS bytes of a workgroup.  Returns what the launch entries
+ * return for the descriptor: -1 for one they refuse; 0 with variant -1 (the other fields 0) for an empty product. */
+typedef struct JvaeGemmRoute {
+    int variant;
+    int gx, gy, gz;
+    int slices, kchunk;
+    int vecA, vecB;
+    int lds;
+} JvaeGemmRoute;
+int jvae_gemm_route(const JvaeGemmDesc* d, JvaeGemmRoute* out);
+/* "TILE64_AM_BK" ... "X3_AK_BN_D3" for a variant of jvae_gemm_route: TILE64 / TILE128 the block tile of the fp32 kernel, X3 the
+ * split-bf16 kernel with D1 / D3 K steps in flight; AK / AM: A is contiguous along k / treated as contiguous along m (sAk != 1),
+ * BN / BK: B contiguous along n / treated as contiguous along k (sBn != 1).  NULL outside 0 ... 15. */
+const char* jvae_gemm_variant_name(int variant);
+
 /* Up to 8 folds (the arguments of jvae_splitk_fold_f32 each) in one launch; every element is folded by the same expression in
  * the same slice order.  n == 0: nothing; n > 8: -2; a descriptor that jvae_splitk_fold_f32 refuses or overlapping outputs: -1. */
 typedef struct JvaeFoldDesc {

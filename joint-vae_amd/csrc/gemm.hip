@@ -1,6 +1,7 @@
 // fp32 MFMA GEMM for gfx950:  C[b](m,n) (+)= sum_k A[b](m,k) * B[b](k,n)  (+ bias, ReLU)
 //
-// v_mfma_f32_32x32x2_f32: exact fp32 (k-ordered fmaf chain), 64 FLOP/clk/SIMD.  256-thread workgroups
+// v_mfma_f32_32x32x2_f32: exact fp32 (k-ordered fmaf chain; a single product comes back as the correctly rounded fp64 product,
+// 0 ulp in tests/test_24_gemm_sweep_gpu.py::test_single_products_of_the_fp32_kernel), 64 FLOP/clk/SIMD.  256-thread workgroups
 // (4 waves as 2x2), block tile BMxBN, K step 16; operands are staged global -> registers -> LDS with the
 // next tile's global loads in flight under the current tile's MFMAs.  LDS images are k-major
 // (As[k][m], Bs[k][n]) so that every fragment read is 32 consecutive dwords per half-wave (conflict-free
@@ -467,6 +468,7 @@ inline bool gemm_x3_on(int K) {                               // jvae_conv2d_set
 // take it from gemm_plan() alone, so a product cannot get another kernel, tile or K slicing because it shares a launch.
 //   variant 0 ... 7   gemm_kernel<BM, BN, AK, BNC>:      (BM == 128 ? 4 : 0) + 2 * AK + BNC        __launch_bounds__(256)
 //   variant 8 ... 15  gemm_x3_kernel<AK, BNC, DEPTH>:    8 + 4 * AK + 2 * BNC + (DEPTH == 3)       __launch_bounds__(256, 4)
+// jvae_gemm_route() (at the end of the file) reports this plan without launching; jvae_gemm_variant_name() names the variants.
 constexpr int VAR_X3 = 8;
 struct GemmPlan {
     GemmP p;
@@ -756,6 +758,15 @@ void plan_out_range(const GemmPlan& pl, uintptr_t* lo, uintptr_t* hi) {
     *hi = reinterpret_cast<uintptr_t>(p.C + pos) + sizeof(float) - 1;
 }
 
+// The plan of one descriptor (jvae_hip.h: JvaeGemmDesc; want_splits > 0 = the stored-slices form, which has to report its count).
+int plan_desc(const JvaeGemmDesc& d, GemmPlan* pl) {
+    const bool part = d.want_splits > 0;
+    const GemmArgs a = {d.M, d.N, d.K, d.batch, d.A, d.sAm, d.sAk, d.sAb, d.B, d.sBk, d.sBn, d.sBb, d.C, d.sCm, d.sCn, d.sCb,
+                        d.bias, d.bias_mode, 1, d.flags, part ? d.want_splits : d.splitk, part ? 1 : 0, d.sCsplit};
+    const int rc = gemm_plan(a, pl);
+    if (rc == 0 && part && !d.splits) return JVAE_EINVAL;
+    return rc;
+}
 
 }  // namespace
 
@@ -812,13 +823,9 @@ extern "C" int jvae_gemm_group_f32(const JvaeGemmDesc* descs, int n, void* strea
     for (int i = 0; i < n; ++i) {
         const JvaeGemmDesc& d = descs[i];
         if (d.splits) *d.splits = 0;
-        const bool part = d.want_splits > 0;
-        const GemmArgs a = {d.M, d.N, d.K, d.batch, d.A, d.sAm, d.sAk, d.sAb, d.B, d.sBk, d.sBn, d.sBb, d.C, d.sCm, d.sCn, d.sCb,
-                            d.bias, d.bias_mode, 1, d.flags, part ? d.want_splits : d.splitk, part ? 1 : 0, d.sCsplit};
-        const int rc = gemm_plan(a, &plans[cnt]);
+        const int rc = plan_desc(d, &plans[cnt]);
         if (rc < 0) return rc;
         if (rc) continue;
-        if (part && !d.splits) return JVAE_EINVAL;
         plan_out_range(plans[cnt], &lo[cnt], &hi[cnt]);
         for (int j = 0; j < cnt; ++j)
             if (lo[cnt] <= hi[j] && lo[j] <= hi[cnt]) return JVAE_EINVAL;
@@ -958,4 +965,23 @@ extern "C" int jvae_gemm_f32(int M, int N, int K, int batch,
                              const float* bias, int bias_mode, int flags, int splitk, void* stream) {
     return jvae_gemm_launch(M, N, K, batch, A, sAm, sAk, sAb, B, sBk, sBn, sBb, C, sCm, sCn, sCb,
                             bias, bias_mode, flags, splitk, (hipStream_t)stream);
+}
+
+// Host-only: the plan the launch entries take for this descriptor.  Nothing is launched, the operands are not read.
+extern "C" int jvae_gemm_route(const JvaeGemmDesc* d, JvaeGemmRoute* out) {
+    if (!d || !out) return JVAE_EINVAL;
+    *out = JvaeGemmRoute{-1, 0, 0, 0, 0, 0, 0, 0, 0};
+    GemmPlan pl;
+    const int rc = plan_desc(*d, &pl);
+    if (rc) return rc < 0 ? rc : 0;
+    *out = JvaeGemmRoute{pl.variant, (int)pl.gx, (int)pl.gy, (int)pl.gz, pl.p.splitk, pl.p.kchunk, pl.p.vecA, pl.p.vecB, pl.lds};
+    return 0;
+}
+
+extern "C" const char* jvae_gemm_variant_name(int variant) {
+    static const char* const names[16] = {
+        "TILE64_AM_BK", "TILE64_AM_BN", "TILE64_AK_BK", "TILE64_AK_BN", "TILE128_AM_BK", "TILE128_AM_BN", "TILE128_AK_BK",
+        "TILE128_AK_BN", "X3_AM_BK_D1", "X3_AM_BK_D3", "X3_AM_BN_D1", "X3_AM_BN_D3", "X3_AK_BK_D1", "X3_AK_BK_D3", "X3_AK_BN_D1",
+        "X3_AK_BN_D3"};
+    return (variant >= 0 && variant < 16) ? names[variant] : nullptr;
 }

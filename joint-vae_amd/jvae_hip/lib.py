@@ -33,8 +33,15 @@ class FoldDesc(ctypes.Structure):
                 ('accumulate', c_int)]
 
 
+class GemmRoute(ctypes.Structure):
+    """JvaeGemmRoute: what jvae_gemm_route reports."""
+    _fields_ = [(n, c_int) for n in ('variant', 'gx', 'gy', 'gz', 'slices', 'kchunk', 'vecA', 'vecB', 'lds')]
+
+
 _SIGS = {
     'jvae_version': (c_char_p, []),
+    'jvae_gemm_route': (c_int, [POINTER(GemmDesc), POINTER(GemmRoute)]),
+    'jvae_gemm_variant_name': (c_char_p, [c_int]),
     'jvae_gemm_f32': (c_int, [c_int] * 4 + [P, c_long, c_long, c_long] * 3 + [P, c_int, c_int, c_int, P]),
     'jvae_splitk_fold_f32': (c_int, [P, P, P, c_int, c_long, c_int, c_int, c_int, P]),
     'jvae_gemm_group_f32': (c_int, [POINTER(GemmDesc), c_int, P]),

@@ -88,6 +88,32 @@ def gemm_group(descs):
     L.check(lib.jvae_gemm_group_f32(arr, len(descs), L.stream_ptr()), 'jvae_gemm_group_f32')
 
 
+GemmRoute = collections.namedtuple('GemmRoute', 'variant grid slices kchunk vecA vecB lds')
+
+
+def gemm_route(M, N, K, A, sA, B, sB, C, sC, bias=None, bias_mode=0, flags=0, splitk=1, batch=1, want_splits=0, sCsplit=0):
+    """The plan gemm() / a gemm_desc record of gemm_group takes for these arguments, asked from gemm_plan() through the host-only
+    query: GemmRoute(variant='X3_AK_BK_D3', grid=(gx, gy, gz), slices, kchunk, vecA, vecB, lds); variant None for an empty
+    product.  want_splits > 0: the stored-slices form of jvae_gemm_group_f32.  Nothing is launched and no operand is read: A, B,
+    C and bias may be tensors or plain addresses (only their alignment matters).  Not memoised: the plan follows the split-bf16
+    switch.  JvaeHipError for arguments the launch entries refuse."""
+    lib = L.load()
+    addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+    d, r, made = L.GemmDesc(), L.GemmRoute(), c_int(0)
+    d.M, d.N, d.K, d.batch = M, N, K, batch
+    d.A, (d.sAm, d.sAk, d.sAb) = addr(A), sA
+    d.B, (d.sBk, d.sBn, d.sBb) = addr(B), sB
+    d.C, (d.sCm, d.sCn, d.sCb) = addr(C), sC
+    d.bias, d.bias_mode, d.flags, d.splitk = addr(bias), bias_mode, flags, splitk
+    d.want_splits, d.sCsplit = want_splits, sCsplit
+    if want_splits > 0:
+        d.splits = ctypes.pointer(made)
+    L.check(lib.jvae_gemm_route(byref(d), byref(r)), 'jvae_gemm_route')
+    name = lib.jvae_gemm_variant_name(r.variant)
+    return GemmRoute(name.decode() if name is not None else None, (r.gx, r.gy, r.gz), r.slices, r.kchunk, bool(r.vecA), bool(r.vecB),
+                     r.lds)
+
+
 def splitk_fold_group(jobs):
     """jobs: (part, bias, y, S, MN, N, relu, accumulate) as for jvae_splitk_fold_f32, at most 8, in ONE launch."""
     lib = L.load()

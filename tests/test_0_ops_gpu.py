@@ -39,6 +39,9 @@ def test_gemm_layouts(M, N, K, layout):
     sA = (K, 1, 0) if layout[0] == 'n' else (1, M, 0)
     sB = (N, 1, 0) if layout[1] == 'n' else (1, K, 0)
     C = torch.empty(M, N, device=DEV)
+    # the variant that runs (tests/gemm_cases.py has the table): split-bf16 from K = 64, else the 64 x 64 fp32 tile
+    route = ops.gemm_route(M, N, K, Ad, sA, Bd, sB, C, (N, 1, 0), bias=bias.to(DEV), bias_mode=1)
+    assert route.variant.startswith(('X3_' if K >= 64 else 'TILE64_') + ('AK_' if sA[1] == 1 else 'AM_') + ('BN' if sB[1] == 1 else 'BK'))
     ops.gemm(M, N, K, Ad, sA, Bd, sB, C, (N, 1, 0), bias=bias.to(DEV), bias_mode=1)
     assert rel(C, ref) < 2e-5
     # split-K with atomics on a pre-zeroed C

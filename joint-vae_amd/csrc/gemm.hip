@@ -1,18 +1,25 @@
 // fp32 MFMA GEMM for gfx950:  C[b](m,n) (+)= sum_k A[b](m,k) * B[b](k,n)  (+ bias, ReLU)
 //
-// v_mfma_f32_32x32x2_f32: exact fp32 (k-ordered fmaf chain; a single product comes back as the correctly rounded fp64 product,
-// 0 ulp in tests/test_24_gemm_sweep_gpu.py::test_single_products_of_the_fp32_kernel), 64 FLOP/clk/SIMD.  256-thread workgroups
-// (4 waves as 2x2), block tile BMxBN, K step 16; operands are staged global -> registers -> LDS with the
-// next tile's global loads in flight under the current tile's MFMAs.  LDS images are k-major
-// (As[k][m], Bs[k][n]) so that every fragment read is 32 consecutive dwords per half-wave (conflict-free
-// ds_read_b32, MI355X_MICROARCH.md §LDS).  Arbitrary element strides on A, B and C let one kernel serve
-// NN / NT / TN products, per-image batched products (grid.z) and split-K with float-atomic accumulation.
+// Two bodies, gemm_tile_body and gemm_x3_body, of 256 threads (4 waves as 2 x 2) and K step BK = 32, sixteen variants of them
+// (VARIANTS: the table every launch, grouped kernel, LDS size and name is derived from).
+//   gemm_tile_body  v_mfma_f32_32x32x2_f32: exact fp32 (k-ordered fmaf chain; a single product comes back as the correctly rounded
+//                   fp64 product, 0 ulp in tests/test_24_gemm_sweep_gpu.py::test_single_products_of_the_fp32_kernel), 64
+//                   FLOP/clk/SIMD.  Block tile 64 x 64 or 128 x 128; LDS images are k-major (As[k][m], Bs[k][n]) so that every
+//                   fragment read is 32 consecutive dwords per half-wave (conflict-free ds_read_b32, MI355X_MICROARCH.md §LDS).
+//   gemm_x3_body    the same product on the bf16 matrix cores: every fp32 operand split exactly into three bf16 terms (below).
+// Both stage their operands global -> registers -> LDS with the next K step's global loads in flight under the current step's
+// MFMAs; which float4 group of an operand tile a thread stages is StageMap, for the load and for the store that consumes it.
+// Both take their block's operands and K slice from TileCtx and store through gemm_store().  Arbitrary element strides on A, B
+// and C let one kernel serve NN / NT / TN products, per-image batched products (grid.z) and split-K with float-atomic
+// accumulation or stored slices.
 //
 // Serves: Linear layers fwd/dgrad/wgrad (reference: nn.Linear in layers.py:283-296, cvae.py:291-326),
 // the 1x1 -> kxk first transposed conv of the upsampler, and the generic (im2col) convolution path.
 // Independent products that cannot fill the chip alone (the two latent heads, a linear layer's dgrad and weight gradient) share
 // ONE launch through jvae_gemm_group_f32: the same plan, bodies and bits per product as alone.
+#include <stdio.h>
 #include <stdlib.h>
+#include <utility>
 #include "common.h"
 #include "jvae_hip.h"
 #include "conv_x3.h"
@@ -21,8 +28,8 @@
 
 namespace {
 
-constexpr int BK = 32;          // 64 MFMAs (128x128 tile) between two barriers
-constexpr int KQ = BK / 4;      // float4 groups along k
+constexpr int BK = 32;          // K step of both bodies: 64 MFMAs (128x128 tile) between two barriers; keeps the split-bf16 images at
+                                // 32 KB -> four workgroups per CU (the products there are latency-bound: few tiles, short K slices)
 
 struct GemmP {
     const float* A; long sAm, sAk, sAb;
@@ -40,6 +47,32 @@ struct GemmP {
     int xcd;             // gemm_x3_kernel: XCD-aware tile order
 };
 
+// What block tile (bx, by, bz) of a BM x BN tiling works on: its rows and columns, its K slice, its batch's operands.  (A
+// constructor, and the members in this order: returned from a function, or with the bias slice `split == 0 && !(flags & 8)` as
+// a member, the kernels build to other instruction orders - profiles/NOTES.md.)
+struct TileCtx {
+    int m0, n0;
+    int batch, split, kbeg, kend;
+    const float* A; const float* B; float* C;     // C: of this slice where the slices are stored (flag 8)
+    __device__ __forceinline__ TileCtx(const GemmP& p, int BM, int BN, unsigned bx, unsigned by, unsigned bz)
+        : m0(by * BM), n0(bx * BN), batch(bz / p.splitk), split(bz % p.splitk), kbeg(split * p.kchunk),
+          kend(min(p.K, kbeg + p.kchunk)), A(p.A + (long)batch * p.sAb), B(p.B + (long)batch * p.sBb),
+          C(p.C + (long)batch * p.sCb + ((p.flags & 8) ? (long)split * p.sCsplit : 0L)) {}
+};
+
+// One element of the result (bias already added) into C, as the product's flags say.
+__device__ __forceinline__ void gemm_store(const GemmP& p, float* dst, float v) {
+    if (p.flags & 8) {
+        *dst = v;
+    } else if (p.flags & 4) {
+        atomicAdd(dst, v);
+    } else {
+        if (p.flags & 1) v += *dst;
+        if (p.flags & 2) v = fmaxf(v, 0.f);
+        *dst = v;
+    }
+}
+
 // 4 consecutive elements along the contiguous direction, zero-filled outside [0,lim).
 template <bool VEC>
 __device__ __forceinline__ f32x4 load4(const float* p, long stride, int i0, int lim, bool row_ok) {
@@ -54,6 +87,33 @@ __device__ __forceinline__ f32x4 load4(const float* p, long stride, int i0, int 
     return v;
 }
 
+// The staging map: the g-th float4 group that thread tid holds of a ROWS x BK operand tile.  KC: the operand is contiguous along k
+// in memory (A with AK, B without BNC), and the groups run along k; otherwise they run along the rows.  The contiguous direction
+// runs fastest over the threads.  A global load and the LDS store that consumes it both take their place from here.
+template <bool KC, int ROWS>
+struct StageMap {
+    static constexpr int Q = (KC ? BK : ROWS) / 4;      // groups along the contiguous direction
+    static constexpr int G = ROWS * BK / 4 / 256;       // groups per thread
+    int fq, sl;                                         // LDS slot: group along the contiguous direction, index along the other
+    __device__ __forceinline__ StageMap(int tid, int g) : fq(tid % Q), sl(tid / Q + g * (256 / Q)) {}
+    // first element of the group, for the tile at row r0 and the K step at k0
+    __device__ __forceinline__ int row(int r0) const { return KC ? r0 + sl : r0 + fq * 4; }
+    __device__ __forceinline__ int k(int k0) const { return KC ? k0 + fq * 4 : k0 + sl; }
+};
+
+// The group of the map, zero-filled outside the operand and the K slice: any strides, 16-byte loads where the plan allows them
+// (vec).  The operand: `rows` rows (M of A, N of B) sR elements apart, k sK apart.  KFIRST: k is the operand's first index (B[k][n];
+// A[m][k] has it second) - the order in which the two terms of the address are added.  It decides nothing but the compiler's
+// instruction order; so does passing the operand as a struct, which is why it comes as plain arguments (profiles/NOTES.md).
+template <bool KC, int ROWS, bool KFIRST>
+__device__ __forceinline__ f32x4 stage_load(const float* base, long sR, long sK, int rows, int vec, int tid, int g, int r0, int k0, int kend) {
+    const StageMap<KC, ROWS> s(tid, g);
+    const int row = s.row(r0), k = s.k(k0);
+    const float* src = KFIRST ? base + (long)k * sK + (long)row * sR : base + (long)row * sR + (long)k * sK;
+    if (KC) return vec ? load4<true>(src, sK, k, kend, row < rows) : load4<false>(src, sK, k, kend, row < rows);
+    return vec ? load4<true>(src, sR, row, rows, k < kend) : load4<false>(src, sR, row, rows, k < kend);
+}
+
 // AK: A is contiguous along k (row-major MxK); otherwise thread groups run along m.
 // BN_: B is contiguous along n (row-major KxN); otherwise along k.
 //
@@ -66,27 +126,34 @@ struct TileLds {
     static constexpr int BYTES = BK * (LDA + LDB) * (int)sizeof(float);
 };
 
+// A staged group into the k-major fp32 image img[BK][LD].
+template <bool KC, int ROWS, int LD>
+__device__ __forceinline__ void tile_lstore(float* img, int tid, int g, const f32x4& v) {
+    const StageMap<KC, ROWS> s(tid, g);
+    if (KC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) img[(s.fq * 4 + j) * LD + s.sl] = v[j];
+    } else {
+        *reinterpret_cast<f32x4*>(&img[s.sl * LD + s.fq * 4]) = v;
+    }
+}
+
 template <int BM, int BN, bool AK, bool BNC>
 __device__ __forceinline__ void gemm_tile_body(const GemmP& p, float* __restrict__ lds, unsigned bx, unsigned by, unsigned bz,
                                                unsigned gx, unsigned gy, unsigned gz) {
     constexpr int LDA = TileLds<BM, BN>::LDA, LDB = TileLds<BM, BN>::LDB;
     constexpr int WM = BM / 2, WN = BN / 2;          // wave tile
     constexpr int TM = WM / 32, TN = WN / 32;        // 32x32 MFMA tiles per wave
-    constexpr int GA = BM * BK / 4 / 256;            // float4 groups per thread (A)
-    constexpr int GB = BN * BK / 4 / 256;
+    constexpr int GA = StageMap<AK, BM>::G, GB = StageMap<!BNC, BN>::G;      // float4 groups per thread
     float* As = lds;                                 // [BK][LDA]
     float* Bs = lds + BK * LDA;                      // [BK][LDB]
     (void)gx; (void)gy; (void)gz;                    // (no tile remap in this kernel)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
-    const int m0 = by * BM, n0 = bx * BN;
-    const int batch = bz / p.splitk, split = bz % p.splitk;
-    const int kbeg = split * p.kchunk;
-    const int kend = min(p.K, kbeg + p.kchunk);
-    const float* A = p.A + (long)batch * p.sAb;
-    const float* B = p.B + (long)batch * p.sBb;
-    float* C = p.C + (long)batch * p.sCb + ((p.flags & 8) ? (long)split * p.sCsplit : 0L);
+    const TileCtx t(p, BM, BN, bx, by, bz);
+    const int m0 = t.m0, n0 = t.n0, kbeg = t.kbeg, kend = t.kend;
+    const float* A = t.A; const float* B = t.B; float* C = t.C;
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -100,61 +167,15 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, float* __restrict
 
     auto gload = [&](int k0) {
 #pragma unroll
-        for (int g = 0; g < GA; ++g) {
-            if (AK) {
-                const int kq = tid % KQ, row = tid / KQ + g * (256 / KQ);
-                const int m = m0 + row, k = k0 + kq * 4;
-                const float* src = A + (long)m * p.sAm + (long)k * p.sAk;
-                ra[g] = p.vecA ? load4<true>(src, p.sAk, k, kend, m < p.M) : load4<false>(src, p.sAk, k, kend, m < p.M);
-            } else {
-                constexpr int GPR = BM / 4;                 // groups per k-row
-                const int mq = tid % GPR, kr = tid / GPR + g * (256 / GPR);
-                const int m = m0 + mq * 4, k = k0 + kr;
-                const float* src = A + (long)m * p.sAm + (long)k * p.sAk;
-                ra[g] = p.vecA ? load4<true>(src, p.sAm, m, p.M, k < kend) : load4<false>(src, p.sAm, m, p.M, k < kend);
-            }
-        }
+        for (int g = 0; g < GA; ++g) ra[g] = stage_load<AK, BM, false>(A, p.sAm, p.sAk, p.M, p.vecA, tid, g, m0, k0, kend);
 #pragma unroll
-        for (int g = 0; g < GB; ++g) {
-            if (BNC) {
-                constexpr int GPR = BN / 4;
-                const int nq = tid % GPR, kr = tid / GPR + g * (256 / GPR);
-                const int n = n0 + nq * 4, k = k0 + kr;
-                const float* src = B + (long)k * p.sBk + (long)n * p.sBn;
-                rb[g] = p.vecB ? load4<true>(src, p.sBn, n, p.N, k < kend) : load4<false>(src, p.sBn, n, p.N, k < kend);
-            } else {
-                const int kq = tid % KQ, col = tid / KQ + g * (256 / KQ);
-                const int n = n0 + col, k = k0 + kq * 4;
-                const float* src = B + (long)k * p.sBk + (long)n * p.sBn;
-                rb[g] = p.vecB ? load4<true>(src, p.sBk, k, kend, n < p.N) : load4<false>(src, p.sBk, k, kend, n < p.N);
-            }
-        }
+        for (int g = 0; g < GB; ++g) rb[g] = stage_load<!BNC, BN, true>(B, p.sBn, p.sBk, p.N, p.vecB, tid, g, n0, k0, kend);
     };
     auto lstore = [&]() {
 #pragma unroll
-        for (int g = 0; g < GA; ++g) {
-            if (AK) {
-                const int kq = tid % KQ, row = tid / KQ + g * (256 / KQ);
+        for (int g = 0; g < GA; ++g) tile_lstore<AK, BM, LDA>(As, tid, g, ra[g]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) As[(kq * 4 + j) * LDA + row] = ra[g][j];
-            } else {
-                constexpr int GPR = BM / 4;
-                const int mq = tid % GPR, kr = tid / GPR + g * (256 / GPR);
-                *reinterpret_cast<f32x4*>(&As[kr * LDA + mq * 4]) = ra[g];
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < GB; ++g) {
-            if (BNC) {
-                constexpr int GPR = BN / 4;
-                const int nq = tid % GPR, kr = tid / GPR + g * (256 / GPR);
-                *reinterpret_cast<f32x4*>(&Bs[kr * LDB + nq * 4]) = rb[g];
-            } else {
-                const int kq = tid % KQ, col = tid / KQ + g * (256 / KQ);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) Bs[(kq * 4 + j) * LDB + col] = rb[g][j];
-            }
-        }
+        for (int g = 0; g < GB; ++g) tile_lstore<!BNC, BN, LDB>(Bs, tid, g, rb[g]);
     };
 
     const int half = lane >> 5, l31 = lane & 31;
@@ -180,7 +201,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, float* __restrict
     }
 
     // epilogue: D[i][j]: j = lane&31, i = (r&3) + 8*(r>>2) + 4*(lane>>5)
-    const bool lead = (split == 0) && !(p.flags & 8);
+    const bool lead = (t.split == 0) && !(p.flags & 8);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -194,16 +215,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, float* __restrict
                 if (m >= p.M) continue;
                 float v = acc[i][j][r] + bn;
                 if (p.bias_mode == 2 && lead) v += p.bias[m];
-                float* dst = C + (long)m * p.sCm + (long)n * p.sCn;
-                if (p.flags & 8) {
-                    *dst = v;
-                } else if (p.flags & 4) {
-                    atomicAdd(dst, v);
-                } else {
-                    if (p.flags & 1) v += *dst;
-                    if (p.flags & 2) v = fmaxf(v, 0.f);
-                    *dst = v;
-                }
+                gemm_store(p, C + (long)m * p.sCm + (long)n * p.sCn, v);
             }
         }
 }
@@ -218,8 +230,8 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 // ---- the same product on the bf16 matrix cores: every fp32 operand split exactly into three bf16 terms, six
 // v_mfma_f32_32x32x16_bf16 per fp32 product tile (the arithmetic of conv_x3.hip: dropped terms < 2^-24 of a product).
-// 64 x 64 block tile, K step 64, 4 waves as 2 x 2 (wave tile 32 x 32).  LDS images are bf16 planes:
-//   operand contiguous along k in memory   -> [row][k]  (pitch 144 B): a fragment = one ds_read_b128, conflict-free
+// 64 x 64 block tile, 4 waves as 2 x 2 (wave tile 32 x 32).  LDS images are bf16 planes:
+//   operand contiguous along k in memory   -> [row][k]  (pitch 80 B): a fragment = one ds_read_b128, conflict-free
 //   operand contiguous along m / n         -> [k][row]  (pitch 192 B): the fragment is read TRANSPOSED with two
 //                                             ds_read_b64_tr_b16 (4 k x 16 rows per 16 lanes, returned k-major per lane)
 // so that both memory layouts are staged with 16-byte global loads and 8-byte LDS stores, no shuffles.
@@ -228,9 +240,6 @@ typedef __bf16 gx_bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int gx_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int gx_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) gx_bf16x4 gx_lds_bf16x4;
-constexpr int BKX = 32;              // K step: 32 keeps the images at 32 KB -> four workgroups per CU (the products here are
-                                     // latency-bound: few tiles, short K slices)
-
 // (round 4: two values per conversion / residual instruction - x3_split2, conv_x3.h; the same bits as the scalar form)
 __device__ __forceinline__ void gx_split4(const f32x4& v, gx_u32x2 (&out)[3]) {
 #pragma unroll
@@ -243,8 +252,8 @@ __device__ __forceinline__ void gx_split4(const f32x4& v, gx_u32x2 (&out)[3]) {
 
 template <bool KC>           // KC: the operand is k-contiguous ([row][k] image), else [k][row]
 struct GxImg {
-    static constexpr int PITCH = KC ? (BKX * 2 + 16) : (64 * 2 + 64);
-    static constexpr int ROWS = KC ? 64 : BKX;            // 64 rows of the tile, or the k of one step
+    static constexpr int PITCH = KC ? (BK * 2 + 16) : (64 * 2 + 64);
+    static constexpr int ROWS = KC ? 64 : BK;            // 64 rows of the tile, or the k of one step
     static constexpr int BYTES = PITCH * ROWS;            // one plane
 };
 
@@ -261,8 +270,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
                                              unsigned gx, unsigned gy, unsigned gz) {
     using IA = GxImg<AK>;
     using IB = GxImg<!BNC>;
-    constexpr int BM = 64, BN = 64, G4 = BM * BKX / 4 / 256;   // float4 groups per thread and operand
-    constexpr int KQX = BKX / 4;                               // float4 groups along k
+    constexpr int BM = 64, BN = 64, G4 = StageMap<AK, BM>::G;   // float4 groups per thread and operand
     unsigned char* As = gx_lds;                                 // [3 planes][IA::BYTES]
     unsigned char* Bs = gx_lds + 3 * IA::BYTES;                 // [3 planes][IB::BYTES]
 
@@ -277,27 +285,26 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
         const unsigned lin = (unsigned)xcd_tile(bx + gx * (by + gy * bz), gx * gy * gz);
         bx = lin % gx; by = (lin / gx) % gy; bz = lin / (gx * gy);
     }
-    const int m0 = by * BM, n0 = bx * BN;
-    const int batch = bz / p.splitk, split = bz % p.splitk;
-    const int kbeg = split * p.kchunk;
-    const int kend = min(p.K, kbeg + p.kchunk);
-    const float* A = p.A + (long)batch * p.sAb;
-    const float* B = p.B + (long)batch * p.sBb;
-    float* C = p.C + (long)batch * p.sCb + ((p.flags & 8) ? (long)split * p.sCsplit : 0L);
+    const TileCtx t(p, BM, BN, bx, by, bz);
+    const int m0 = t.m0, n0 = t.n0, kbeg = t.kbeg, kend = t.kend;
+    const float* A = t.A; const float* B = t.B; float* C = t.C;
 
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     f32x4 ra[DEPTH][G4], rb[DEPTH][G4];
 
-    // (row, k) coordinates of this thread's float4 group g of a K step starting at k0; the contiguous direction runs fastest
+    // The deep form's (contiguous, other) coordinates of float4 group g of the K step at k0: StageMap's rule written out, with
+    // the map's constants.  Read through StageMap::row() / k() the DEPTH = 3 bodies (and only they) come out with another
+    // register allocation and other global-load counts, so this one copy stays (profiles/NOTES.md).
+    constexpr int QK = StageMap<true, 64>::Q, QR = StageMap<false, 64>::Q;
     auto coordA = [&](int g, int k0, int* fast, int* slow) {
-        if (AK) { *fast = k0 + (tid % KQX) * 4; *slow = m0 + tid / KQX + g * (256 / KQX); }       // (k, m)
-        else    { *fast = m0 + (tid % 16) * 4;  *slow = k0 + tid / 16 + g * 16; }                  // (m, k)
+        if (AK) { *fast = k0 + (tid % QK) * 4; *slow = m0 + tid / QK + g * (256 / QK); }          // (k, m)
+        else    { *fast = m0 + (tid % QR) * 4; *slow = k0 + tid / QR + g * (256 / QR); }          // (m, k)
     };
     auto coordB = [&](int g, int k0, int* fast, int* slow) {
-        if (BNC) { *fast = n0 + (tid % 16) * 4;  *slow = k0 + tid / 16 + g * 16; }                 // (n, k)
-        else     { *fast = k0 + (tid % KQX) * 4; *slow = n0 + tid / KQX + g * (256 / KQX); }       // (k, n)
+        if (BNC) { *fast = n0 + (tid % QR) * 4; *slow = k0 + tid / QR + g * (256 / QR); }         // (n, k)
+        else     { *fast = k0 + (tid % QK) * 4; *slow = n0 + tid / QK + g * (256 / QK); }         // (k, n)
     };
     auto okA = [&](int fast, int slow) { return AK ? (fast < kend && slow < p.M) : (fast + 3 < p.M && slow < kend); };
     auto okB = [&](int fast, int slow) { return BNC ? (fast + 3 < p.N && slow < kend) : (fast < kend && slow < p.N); };
@@ -315,36 +322,15 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
                 rb[st][g] = *reinterpret_cast<const f32x4*>(okB(f, sl) ? sb : B);
                 continue;
             }
-            if (AK) {
-                const int kq = tid % KQX, row = tid / KQX + g * (256 / KQX);
-                const int m = m0 + row, k = k0 + kq * 4;
-                const float* src = A + (long)m * p.sAm + (long)k * p.sAk;
-                ra[st][g] = p.vecA ? load4<true>(src, p.sAk, k, kend, m < p.M) : load4<false>(src, p.sAk, k, kend, m < p.M);
-            } else {
-                const int mq = tid % 16, kr = tid / 16 + g * 16;
-                const int m = m0 + mq * 4, k = k0 + kr;
-                const float* src = A + (long)m * p.sAm + (long)k * p.sAk;
-                ra[st][g] = p.vecA ? load4<true>(src, p.sAm, m, p.M, k < kend) : load4<false>(src, p.sAm, m, p.M, k < kend);
-            }
-            if (BNC) {
-                const int nq = tid % 16, kr = tid / 16 + g * 16;
-                const int n = n0 + nq * 4, k = k0 + kr;
-                const float* src = B + (long)k * p.sBk + (long)n * p.sBn;
-                rb[st][g] = p.vecB ? load4<true>(src, p.sBn, n, p.N, k < kend) : load4<false>(src, p.sBn, n, p.N, k < kend);
-            } else {
-                const int kq = tid % KQX, col = tid / KQX + g * (256 / KQX);
-                const int n = n0 + col, k = k0 + kq * 4;
-                const float* src = B + (long)k * p.sBk + (long)n * p.sBn;
-                rb[st][g] = p.vecB ? load4<true>(src, p.sBk, k, kend, n < p.N) : load4<false>(src, p.sBk, k, kend, n < p.N);
-            }
+            ra[st][g] = stage_load<AK, BM, false>(A, p.sAm, p.sAk, p.M, p.vecA, tid, g, m0, k0, kend);
+            rb[st][g] = stage_load<!BNC, BN, true>(B, p.sBn, p.sBk, p.N, p.vecB, tid, g, n0, k0, kend);
         }
     };
     auto lstore = [&](int st, int k0) {
 #pragma unroll
         for (int g = 0; g < G4; ++g) {
-            // the contiguous direction runs fastest over the threads, as in gload
-            const int fa = AK ? tid % KQX : tid % 16, sa_ = AK ? tid / KQX + g * (256 / KQX) : tid / 16 + g * 16;
-            const int fb = BNC ? tid % 16 : tid % KQX, sb_ = BNC ? tid / 16 + g * 16 : tid / KQX + g * (256 / KQX);
+            const StageMap<AK, BM> ma(tid, g);
+            const StageMap<!BNC, BN> mb(tid, g);
             f32x4 va = ra[st][g], vb = rb[st][g];
             if constexpr (DEPTH > 1) {               // stand-in loads of out-of-range groups: exact zeros
                 int f, sl;
@@ -358,8 +344,8 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
             gx_split4(vb, sb);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
-                *reinterpret_cast<gx_u32x2*>(As + pl * IA::BYTES + sa_ * IA::PITCH + fa * 8) = sa[pl];
-                *reinterpret_cast<gx_u32x2*>(Bs + pl * IB::BYTES + sb_ * IB::PITCH + fb * 8) = sb[pl];
+                *reinterpret_cast<gx_u32x2*>(As + pl * IA::BYTES + ma.sl * IA::PITCH + ma.fq * 8) = sa[pl];
+                *reinterpret_cast<gx_u32x2*>(Bs + pl * IB::BYTES + mb.sl * IB::PITCH + mb.fq * 8) = sb[pl];
             }
         }
     };
@@ -375,7 +361,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
 
     auto multiply = [&]() {
 #pragma unroll
-        for (int ks = 0; ks < BKX / 16; ++ks) {
+        for (int ks = 0; ks < BK / 16; ++ks) {
             gx_bf16x8 a[3], b[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
@@ -390,28 +376,28 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
     if constexpr (DEPTH > 1) {
         // prologue: DEPTH steps in flight (steps beyond kend load the stand-in address: harmless, never stored)
 #pragma unroll
-        for (int d = 0; d < DEPTH; ++d) gload(d, kbeg + d * BKX);
+        for (int d = 0; d < DEPTH; ++d) gload(d, kbeg + d * BK);
         // Round 4: the rounds of DEPTH full steps run in a loop WITHOUT branches, the 0 ... DEPTH-1 remaining steps behind it.  With
         // `if (kk < kend)` around every step the loop header was a join of paths with different numbers of loads in flight, and the
         // compiler put s_waitcnt vmcnt(0) in front of the first stage's LDS stores: every third K step waited for the loads that
         // had just been issued for three steps ahead - the deep prefetch was one step deep (tools/e4_probe.py: 37 us for the 7x7
         // head's product, MFMA busy 0.20, and nothing inside the step mattered).
-        const int nst = (kend - kbeg + BKX - 1) / BKX;
+        const int nst = (kend - kbeg + BK - 1) / BK;
         int k0 = kbeg;
-        for (int it = 0; it < nst / DEPTH; ++it, k0 += DEPTH * BKX) {
+        for (int it = 0; it < nst / DEPTH; ++it, k0 += DEPTH * BK) {
 #pragma unroll
             for (int d = 0; d < DEPTH; ++d) {
-                const int kk = k0 + d * BKX;
+                const int kk = k0 + d * BK;
                 __syncthreads();                         // previous tile's fragment reads are done
                 lstore(d, kk);
                 __syncthreads();
-                gload(d, kk + DEPTH * BKX);              // stage d is free again: three steps ahead, under the MFMAs below
+                gload(d, kk + DEPTH * BK);              // stage d is free again: three steps ahead, under the MFMAs below
                 multiply();
             }
         }
 #pragma unroll
         for (int d = 0; d < DEPTH - 1; ++d) {            // (the loads issued for steps beyond kend read the stand-in address)
-            const int kk = k0 + d * BKX;
+            const int kk = k0 + d * BK;
             if (kk < kend) {                             // block-uniform
                 __syncthreads();
                 lstore(d, kk);
@@ -421,17 +407,17 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
         }
     } else {
         if (kbeg < kend) gload(0, kbeg);
-        for (int k0 = kbeg; k0 < kend; k0 += BKX) {
+        for (int k0 = kbeg; k0 < kend; k0 += BK) {
             __syncthreads();                 // previous tile's fragment reads are done
             lstore(0, k0);
             __syncthreads();
-            if (k0 + BKX < kend) gload(0, k0 + BKX);   // in flight under the MFMAs below
+            if (k0 + BK < kend) gload(0, k0 + BK);   // in flight under the MFMAs below
             multiply();
         }
     }
 
     // epilogue (as gemm_kernel): D[i][j]: j = lane&31, i = (r&3) + 8*(r>>2) + 4*(lane>>5)
-    const bool lead = (split == 0) && !(p.flags & 8);
+    const bool lead = (t.split == 0) && !(p.flags & 8);
     const int n = n0 + wn0 + l31;
     if (n >= p.N) return;
     const float bn = (p.bias_mode == 1 && lead) ? p.bias[n / p.bias_div] : 0.f;
@@ -441,16 +427,7 @@ __device__ __forceinline__ void gemm_x3_body(const GemmP& p, unsigned char* __re
         if (m >= p.M) continue;
         float v = acc[r] + bn;
         if (p.bias_mode == 2 && lead) v += p.bias[m];
-        float* dst = C + (long)m * p.sCm + (long)n * p.sCn;
-        if (p.flags & 8) {
-            *dst = v;
-        } else if (p.flags & 4) {
-            atomicAdd(dst, v);
-        } else {
-            if (p.flags & 1) v += *dst;
-            if (p.flags & 2) v = fmaxf(v, 0.f);
-            *dst = v;
-        }
+        gemm_store(p, C + (long)m * p.sCm + (long)n * p.sCn, v);
     }
 }
 
@@ -464,64 +441,82 @@ inline bool gemm_x3_on(int K) {                               // jvae_conv2d_set
     return K >= 64 && jvae_conv5_x3_enabled();
 }
 
-// ---- plan: what one product runs - its GemmP, the kernel variant and the grid.  The single-product entries and the grouped entry
+// ---- the variants: what a product can run.  The index of a row is the variant number of jvae_gemm_route(); the plan, the LDS
+// sizes, the stand-alone launch, the bodies of the grouped kernels and jvae_gemm_variant_name() all read this table.
+//   x3 false: gemm_kernel<bm, bm, ak, bnc>            __launch_bounds__(256)
+//   x3 true:  gemm_x3_kernel<ak, bnc, depth>          __launch_bounds__(256, 4)
+struct Variant {
+    bool x3; int bm; bool ak, bnc; int depth;
+};
+constexpr int NVAR = 16, VAR_X3 = 8;          // VAR_X3: the first split-bf16 variant
+constexpr Variant VARIANTS[NVAR] = {
+    {false, 64, false, false, 1}, {false, 64, false, true, 1}, {false, 64, true, false, 1}, {false, 64, true, true, 1},
+    {false, 128, false, false, 1}, {false, 128, false, true, 1}, {false, 128, true, false, 1}, {false, 128, true, true, 1},
+    {true, 64, false, false, 1}, {true, 64, false, false, 3}, {true, 64, false, true, 1}, {true, 64, false, true, 3},
+    {true, 64, true, false, 1}, {true, 64, true, false, 3}, {true, 64, true, true, 1}, {true, 64, true, true, 3},
+};
+constexpr int variant_index(bool x3, int bm, bool ak, bool bnc, int depth) {
+    for (int v = 0; v < NVAR; ++v) {
+        const Variant& d = VARIANTS[v];
+        if (d.x3 == x3 && d.bm == bm && d.ak == ak && d.bnc == bnc && d.depth == depth) return v;
+    }
+    return -1;
+}
+// LDS bytes of a workgroup: dynamic for the x3 variants, what the static arrays take for the tile variants
+constexpr int variant_lds(int v) {
+    const Variant& d = VARIANTS[v];
+    if (!d.x3) return d.bm == 128 ? TileLds<128, 128>::BYTES : TileLds<64, 64>::BYTES;
+    return 3 * ((d.ak ? GxImg<true>::BYTES : GxImg<false>::BYTES) + (d.bnc ? GxImg<false>::BYTES : GxImg<true>::BYTES));
+}
+// the largest of the variants in `set` (bit v = variant v)
+constexpr int set_lds(unsigned set) {
+    int lds = 0;
+    for (int v = 0; v < NVAR; ++v)
+        if (((set >> v) & 1u) && variant_lds(v) > lds) lds = variant_lds(v);
+    return lds;
+}
+// f(std::integral_constant<int, V>{}) for the variant v (the idiom of jvae_with_aff, jvae_internal.h)
+template <class F, int... V>
+inline void with_variant_seq(int v, F&& f, std::integer_sequence<int, V...>) {
+    ((v == V ? (f(std::integral_constant<int, V>{}), 0) : 0), ...);
+}
+template <class F>
+inline void with_variant(int v, F&& f) { with_variant_seq(v, f, std::make_integer_sequence<int, NVAR>{}); }
+
+// ---- plan: what one product runs - its GemmP, the variant and the grid.  The single-product entries and the grouped entry
 // take it from gemm_plan() alone, so a product cannot get another kernel, tile or K slicing because it shares a launch.
-//   variant 0 ... 7   gemm_kernel<BM, BN, AK, BNC>:      (BM == 128 ? 4 : 0) + 2 * AK + BNC        __launch_bounds__(256)
-//   variant 8 ... 15  gemm_x3_kernel<AK, BNC, DEPTH>:    8 + 4 * AK + 2 * BNC + (DEPTH == 3)       __launch_bounds__(256, 4)
-// jvae_gemm_route() (at the end of the file) reports this plan without launching; jvae_gemm_variant_name() names the variants.
-constexpr int VAR_X3 = 8;
+// jvae_gemm_route() (at the end of the file) reports this plan without launching.
 struct GemmPlan {
     GemmP p;
     int variant;
     unsigned gx, gy, gz;     // the grid of the stand-alone launch = the virtual grid of the record in a group
-    int lds;                 // dynamic LDS bytes (the x3 variants; the tile variants: what their static arrays take)
+    int lds;                 // variant_lds(variant)
 };
 
-template <bool AK, bool BNC>
-constexpr int x3_lds() { return 3 * (GxImg<AK>::BYTES + GxImg<!BNC>::BYTES); }
-
-inline int variant_lds(int v) {
-    if (v < 4) return TileLds<64, 64>::BYTES;
-    if (v < VAR_X3) return TileLds<128, 128>::BYTES;
-    switch ((v - VAR_X3) >> 1) {
-        case 0: return x3_lds<false, false>();
-        case 1: return x3_lds<false, true>();
-        case 2: return x3_lds<true, false>();
-        default: return x3_lds<true, true>();
-    }
-}
-
-struct GemmArgs {
-    int M, N, K, batch;
-    const float* A; long sAm, sAk, sAb;
-    const float* B; long sBk, sBn, sBb;
-    float* C; long sCm, sCn, sCb;
-    const float* bias; int bias_mode, bias_div, flags, splitk;
-    int part;                // != 0: jvae_gemm_launch_part - partial products stored sCsplit apart, splitk = the wanted number
-    long sCsplit;
-};
-
+// The plan of one descriptor (jvae_hip.h: JvaeGemmDesc; want_splits > 0 = the stored-slices form: partial products sCsplit apart,
+// no bias, splitk = the wanted number, and it has to report its count) and the one argument that only the internal entry has.
 // 0: *pl is a launch; 1: nothing to do (an empty product); < 0: invalid.  pl->p.splitk is the number of K slices made.
-int gemm_plan(const GemmArgs& a, GemmPlan* pl) {
+int gemm_plan(const JvaeGemmDesc& a, int bias_div, GemmPlan* pl) {
+    const bool part = a.want_splits > 0;
     if (a.M <= 0 || a.N <= 0 || a.batch <= 0) return 1;
     if (!a.A || !a.B || !a.C) return JVAE_EINVAL;
-    if (a.part ? a.K <= 0 : a.K < 0) return JVAE_EINVAL;
-    if (!a.part && a.bias_mode && !a.bias) return JVAE_EINVAL;
+    if (part ? a.K <= 0 : a.K < 0) return JVAE_EINVAL;
+    if (!part && a.bias_mode && !a.bias) return JVAE_EINVAL;
     GemmP& p = pl->p;
     p.A = a.A; p.sAm = a.sAm; p.sAk = a.sAk; p.sAb = a.sAb;
     p.B = a.B; p.sBk = a.sBk; p.sBn = a.sBn; p.sBb = a.sBb;
     p.C = a.C; p.sCm = a.sCm; p.sCn = a.sCn; p.sCb = a.sCb;
-    p.bias = a.part ? nullptr : a.bias;
-    p.bias_mode = a.part ? 0 : a.bias_mode;
-    p.bias_div = (!a.part && a.bias_div > 0) ? a.bias_div : 1;
+    p.bias = part ? nullptr : a.bias;
+    p.bias_mode = part ? 0 : a.bias_mode;
+    p.bias_div = (!part && bias_div > 0) ? bias_div : 1;
     p.M = a.M; p.N = a.N; p.K = a.K;
-    int splitk = a.splitk < 1 ? 1 : a.splitk;
+    int splitk = part ? a.want_splits : (a.splitk < 1 ? 1 : a.splitk);
     const int ktiles = cdiv(a.K, BK);
     if (splitk > ktiles) splitk = ktiles > 0 ? ktiles : 1;
     p.kchunk = cdiv(ktiles, splitk) * BK;
     splitk = a.K > 0 ? cdiv(a.K, p.kchunk) : 1;
     p.splitk = splitk;
-    if (a.part) {
+    if (part) {
         p.flags = 8;
         p.sCsplit = a.sCsplit;
     } else {
@@ -542,15 +537,15 @@ int gemm_plan(const GemmArgs& a, GemmPlan* pl) {
         p.xcd = 1;                                                 // XCD-aware tile order
         // deep prefetch: 16-byte loads on both operands, K range a multiple of 4 (kchunk is a multiple of 32)
         const bool deep = p.vecA && p.vecB && p.K % 4 == 0 && (ak || p.M % 4 == 0) && (!bnc || p.N % 4 == 0);
-        pl->variant = VAR_X3 + 4 * ak + 2 * bnc + (deep ? 1 : 0);
+        pl->variant = variant_index(true, 64, ak, bnc, deep ? 3 : 1);
     } else {
         const long tiles128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128) * a.batch * splitk;
-        if (!a.part && a.M > 64 && a.N > 64 && tiles128 >= 512) bm = 128;
-        pl->variant = (bm == 128 ? 4 : 0) + 2 * ak + (bnc ? 1 : 0);
+        if (!part && a.M > 64 && a.N > 64 && tiles128 >= 512) bm = 128;
+        pl->variant = variant_index(false, bm, ak, bnc, 1);
     }
     pl->gx = cdiv(a.N, bm); pl->gy = cdiv(a.M, bm); pl->gz = (unsigned)a.batch * splitk;
     pl->lds = variant_lds(pl->variant);
-    return 0;
+    return part && !a.splits ? JVAE_EINVAL : 0;
 }
 
 template <typename F>
@@ -563,42 +558,24 @@ int set_lds_once(F kernel, int lds, bool* done) {
     return 0;
 }
 
-template <int BM, bool AK, bool BNC>
-int launch_tile_variant(const GemmPlan& pl, hipStream_t st) {
-    hipLaunchKernelGGL((gemm_kernel<BM, BM, AK, BNC>), dim3(pl.gx, pl.gy, pl.gz), dim3(256), 0, st, pl.p);
-    JVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-template <bool AK, bool BNC, int DEPTH>
-int launch_x3_variant(const GemmPlan& pl, hipStream_t st) {
-    static bool attr_set = false;
-    if (int rc = set_lds_once(&gemm_x3_kernel<AK, BNC, DEPTH>, x3_lds<AK, BNC>(), &attr_set)) return rc;
-    hipLaunchKernelGGL((gemm_x3_kernel<AK, BNC, DEPTH>), dim3(pl.gx, pl.gy, pl.gz), dim3(256), pl.lds, st, pl.p);
+template <int V>
+int launch_variant(const GemmPlan& pl, hipStream_t st) {
+    constexpr Variant d = VARIANTS[V];
+    if constexpr (d.x3) {
+        static bool attr_set = false;
+        if (int rc = set_lds_once(&gemm_x3_kernel<d.ak, d.bnc, d.depth>, variant_lds(V), &attr_set)) return rc;
+        hipLaunchKernelGGL((gemm_x3_kernel<d.ak, d.bnc, d.depth>), dim3(pl.gx, pl.gy, pl.gz), dim3(256), pl.lds, st, pl.p);
+    } else {
+        hipLaunchKernelGGL((gemm_kernel<d.bm, d.bm, d.ak, d.bnc>), dim3(pl.gx, pl.gy, pl.gz), dim3(256), 0, st, pl.p);
+    }
     JVAE_LAUNCH_CHECK();
     return 0;
 }
 
 int launch_plan(const GemmPlan& pl, hipStream_t st) {
-    switch (pl.variant) {
-        case 0: return launch_tile_variant<64, false, false>(pl, st);
-        case 1: return launch_tile_variant<64, false, true>(pl, st);
-        case 2: return launch_tile_variant<64, true, false>(pl, st);
-        case 3: return launch_tile_variant<64, true, true>(pl, st);
-        case 4: return launch_tile_variant<128, false, false>(pl, st);
-        case 5: return launch_tile_variant<128, false, true>(pl, st);
-        case 6: return launch_tile_variant<128, true, false>(pl, st);
-        case 7: return launch_tile_variant<128, true, true>(pl, st);
-        case 8: return launch_x3_variant<false, false, 1>(pl, st);
-        case 9: return launch_x3_variant<false, false, 3>(pl, st);
-        case 10: return launch_x3_variant<false, true, 1>(pl, st);
-        case 11: return launch_x3_variant<false, true, 3>(pl, st);
-        case 12: return launch_x3_variant<true, false, 1>(pl, st);
-        case 13: return launch_x3_variant<true, false, 3>(pl, st);
-        case 14: return launch_x3_variant<true, true, 1>(pl, st);
-        case 15: return launch_x3_variant<true, true, 3>(pl, st);
-    }
-    return JVAE_EINVAL;
+    int rc = JVAE_EINVAL;
+    with_variant(pl.variant, [&](auto V) { rc = launch_variant<decltype(V)::value>(pl, st); });
+    return rc;
 }
 
 // ---- grouped launch: up to JVAE_GEMM_GROUP_MAX independent products in ONE flat grid.  The records travel by value in the kernel
@@ -620,100 +597,110 @@ struct GemmGroup {
     GemmRec rec[GROUP_MAX];
 };
 
-struct GroupTile { unsigned r, bx, by, bz; bool live; };
-__device__ __forceinline__ GroupTile group_tile(const GemmGroup& g) {
+// The record of this flat workgroup and the workgroup's index within it (GemmGroup, FoldGroup: records with a `first`).
+template <class G>
+__device__ __forceinline__ unsigned group_record(const G& g, unsigned* local) {
     unsigned r = 0;
 #pragma unroll
     for (unsigned i = 1; i < GROUP_MAX; ++i)
         if (blockIdx.x >= g.rec[i].first) r = i;
-    const GemmRec& rc = g.rec[r];
-    const unsigned local = blockIdx.x - rc.first;
+    *local = blockIdx.x - g.rec[r].first;
+    return r;
+}
+// The unused records of a group with cnt >= 1 records: copies of record 0 that no workgroup reaches.
+template <class G>
+void pad_records(G* g, int cnt) {
+    for (int i = cnt; i < GROUP_MAX; ++i) { g->rec[i] = g->rec[0]; g->rec[i].first = 0xffffffffu; }
+}
+
+struct GroupTile { unsigned r, bx, by, bz; bool live; };
+__device__ __forceinline__ GroupTile group_tile(const GemmGroup& g) {
+    unsigned local;
     GroupTile t;
-    t.r = r;
+    t.r = group_record(g, &local);
+    const GemmRec& rc = g.rec[t.r];
     t.live = local < rc.gx * rc.gy * rc.gz;
     t.bx = local % rc.gx; t.by = (local / rc.gx) % rc.gy; t.bz = local / (rc.gx * rc.gy);
     return t;
 }
 
+// The body of variant V, when it is in SET (bit v = variant v is compiled in) and the record asks for it: true if it ran.  The
+// grouped kernels run these as consecutive tests: behind one `switch` the split-bf16 bodies spilled.  STOP: no test after the one
+// that ran.  The tile kernel stops (without, its 64 x 64 form takes 50 VGPRs and loses a wave per SIMD), the split-bf16 kernel
+// does not (with, it spills one to seven VGPRs more): profiles/NOTES.md.
+template <unsigned SET, int V>
+__device__ __forceinline__ bool group_case(const GemmRec& rc, unsigned char* lds, const GroupTile& t) {
+    constexpr Variant d = VARIANTS[V];
+    if constexpr ((SET >> V) & 1u) {
+        if (rc.variant == V) {
+            if constexpr (d.x3) gemm_x3_body<d.ak, d.bnc, d.depth>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz);
+            else gemm_tile_body<d.bm, d.bm, d.ak, d.bnc>(rc.p, reinterpret_cast<float*>(lds), t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz);
+            return true;
+        }
+    }
+    return false;
+}
+template <unsigned SET, bool STOP, int... V>
+__device__ __forceinline__ void group_cases(const GemmGroup& g, unsigned char* lds, std::integer_sequence<int, V...>) {
+    const GroupTile t = group_tile(g);
+    if (!t.live) return;
+    if constexpr (STOP) (void)(group_case<SET, V>(g.rec[t.r], lds, t) || ...);
+    else (group_case<SET, V>(g.rec[t.r], lds, t), ...);
+}
+
 // BIG: the 128 x 128 variants are compiled in.  They take 76-80 VGPRs + 64 AGPRs (occupancy 3) where the 64 x 64 variants take
 // 38-42 + 16 (occupancy 8), so a group of 64 x 64 tiles only has a kernel of its own.
+constexpr unsigned tile_set(bool big) {
+    unsigned set = 0;
+    for (int v = 0; v < VAR_X3; ++v)
+        if (big || VARIANTS[v].bm == 64) set |= 1u << v;
+    return set;
+}
 template <bool BIG>
 __global__ __launch_bounds__(256) void gemm_group_tile_kernel(GemmGroup g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char grp_lds[];
-    float* lds = reinterpret_cast<float*>(grp_lds);
-    const GroupTile t = group_tile(g);
-    if (!t.live) return;
-    const GemmRec& rc = g.rec[t.r];
-    switch (rc.variant) {
-        case 0: gemm_tile_body<64, 64, false, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-        case 1: gemm_tile_body<64, 64, false, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-        case 2: gemm_tile_body<64, 64, true, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-        case 3: gemm_tile_body<64, 64, true, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-    }
-    if constexpr (BIG) {
-        switch (rc.variant) {
-            case 4: gemm_tile_body<128, 128, false, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-            case 5: gemm_tile_body<128, 128, false, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-            case 6: gemm_tile_body<128, 128, true, false>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-            case 7: gemm_tile_body<128, 128, true, true>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz); return;
-        }
-    }
+    group_cases<tile_set(BIG), true>(g, grp_lds, std::make_integer_sequence<int, NVAR>{});
 }
 
-template <bool BIG>
-int launch_group_tile(const GemmGroup& g, unsigned total, int lds, hipStream_t st) {
-    static bool attr_set = false;
-    if (int rc = set_lds_once(&gemm_group_tile_kernel<BIG>, TileLds<BIG ? 128 : 64, BIG ? 128 : 64>::BYTES, &attr_set)) return rc;
-    hipLaunchKernelGGL(gemm_group_tile_kernel<BIG>, dim3(total), dim3(256), lds, st, g);
-    JVAE_LAUNCH_CHECK();
-    return 0;
-}
-
-// MASK: bit (variant - 8) set = that variant's body is compiled in.  The union of all eight takes the registers of its largest
+// MASK: bit (variant - VAR_X3) set = that variant's body is compiled in.  The union of all eight takes the registers of its largest
 // member (128 VGPRs, three of them spilled; occupancy 4 as every DEPTH = 3 variant has alone), so the variant sets the training
 // step uses have kernels of their own, which build to their members' counts: the two forward products of a pair of linear
 // layers (X3_FWD) and the dgrads and weight gradients of linear layers (X3_BWD).  Any other set takes the union.
-constexpr unsigned X3_FWD = 1u << (13 - VAR_X3), X3_BWD = (1u << (15 - VAR_X3)) | (1u << (11 - VAR_X3)), X3_ALL = 0xffu;
-
-template <unsigned MASK, int V, bool AK, bool BNC, int DEPTH>
-__device__ __forceinline__ void group_x3_case(const GemmRec& rc, unsigned char* lds, const GroupTile& t) {
-    if constexpr ((MASK >> (V - VAR_X3)) & 1u) {
-        if (rc.variant == V) gemm_x3_body<AK, BNC, DEPTH>(rc.p, lds, t.bx, t.by, t.bz, rc.gx, rc.gy, rc.gz);
-    }
-}
+constexpr unsigned x3_bit(bool ak, bool bnc, int depth) { return 1u << (variant_index(true, 64, ak, bnc, depth) - VAR_X3); }
+constexpr unsigned X3_FWD = x3_bit(true, false, 3), X3_BWD = x3_bit(true, true, 3) | x3_bit(false, true, 3), X3_ALL = 0xffu;
 
 template <unsigned MASK>
 __global__ __launch_bounds__(256, 4) void gemm_group_x3_kernel(GemmGroup g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char grp_lds[];
-    const GroupTile t = group_tile(g);
-    if (!t.live) return;
-    const GemmRec& rc = g.rec[t.r];
-    group_x3_case<MASK, 8, false, false, 1>(rc, grp_lds, t);
-    group_x3_case<MASK, 9, false, false, 3>(rc, grp_lds, t);
-    group_x3_case<MASK, 10, false, true, 1>(rc, grp_lds, t);
-    group_x3_case<MASK, 11, false, true, 3>(rc, grp_lds, t);
-    group_x3_case<MASK, 12, true, false, 1>(rc, grp_lds, t);
-    group_x3_case<MASK, 13, true, false, 3>(rc, grp_lds, t);
-    group_x3_case<MASK, 14, true, true, 1>(rc, grp_lds, t);
-    group_x3_case<MASK, 15, true, true, 3>(rc, grp_lds, t);
+    group_cases<(MASK << VAR_X3), false>(g, grp_lds, std::make_integer_sequence<int, NVAR>{});
 }
 
-template <unsigned MASK>
-int launch_group_x3(const GemmGroup& g, unsigned total, int lds, hipStream_t st) {
+// One grouped kernel, compiled for the variants in SET: its dynamic-LDS limit is that of the largest of them.
+template <unsigned SET, class K>
+int launch_group_set(K kernel, const GemmGroup& g, unsigned total, int lds, hipStream_t st) {
     static bool attr_set = false;
-    if (int rc = set_lds_once(&gemm_group_x3_kernel<MASK>, x3_lds<false, false>(), &attr_set)) return rc;
-    hipLaunchKernelGGL(gemm_group_x3_kernel<MASK>, dim3(total), dim3(256), lds, st, g);
+    if (int rc = set_lds_once(kernel, set_lds(SET), &attr_set)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(total), dim3(256), lds, st, g);
     JVAE_LAUNCH_CHECK();
     return 0;
+}
+template <bool BIG>
+int launch_group_tile(const GemmGroup& g, unsigned total, int lds, hipStream_t st) {
+    return launch_group_set<tile_set(BIG)>(&gemm_group_tile_kernel<BIG>, g, total, lds, st);
+}
+template <unsigned MASK>
+int launch_group_x3(const GemmGroup& g, unsigned total, int lds, hipStream_t st) {
+    return launch_group_set<(MASK << VAR_X3)>(&gemm_group_x3_kernel<MASK>, g, total, lds, st);
 }
 
 // The plans of one kind (x3 or tile variants) as one launch; a single plan goes through the stand-alone kernel.
 int launch_group_kind(const GemmPlan* plans, int n, bool x3, hipStream_t st) {
     GemmGroup g;
     int cnt = 0, lds = 0, last = -1;
+    unsigned set = 0;
     unsigned long total = 0;
     for (int i = 0; i < n; ++i) {
-        if ((plans[i].variant >= VAR_X3) != x3) continue;
+        if (VARIANTS[plans[i].variant].x3 != x3) continue;
         GemmRec& rc = g.rec[cnt++];
         rc.p = plans[i].p; rc.variant = plans[i].variant;
         rc.gx = plans[i].gx; rc.gy = plans[i].gy; rc.gz = plans[i].gz;
@@ -721,20 +708,19 @@ int launch_group_kind(const GemmPlan* plans, int n, bool x3, hipStream_t st) {
         total += ((unsigned long)rc.gx * rc.gy * rc.gz + 7) & ~7ul;
         if (total > 0x7fffffffUL) return JVAE_ENOTSUP;
         if (plans[i].lds > lds) lds = plans[i].lds;
+        set |= 1u << rc.variant;
         last = i;
     }
     if (cnt == 0) return 0;
     if (cnt == 1) return launch_plan(plans[last], st);
-    for (int i = cnt; i < GROUP_MAX; ++i) { g.rec[i] = g.rec[0]; g.rec[i].first = 0xffffffffu; }
+    pad_records(&g, cnt);
     if (x3) {
-        unsigned mask = 0;
-        for (int i = 0; i < cnt; ++i) mask |= 1u << (g.rec[i].variant - VAR_X3);
+        const unsigned mask = set >> VAR_X3;
         if ((mask & ~X3_FWD) == 0) return launch_group_x3<X3_FWD>(g, (unsigned)total, lds, st);
         if ((mask & ~X3_BWD) == 0) return launch_group_x3<X3_BWD>(g, (unsigned)total, lds, st);
         return launch_group_x3<X3_ALL>(g, (unsigned)total, lds, st);
     }
-    for (int i = 0; i < cnt; ++i)
-        if (g.rec[i].variant >= 4) return launch_group_tile<true>(g, (unsigned)total, lds, st);
+    if (set & ~tile_set(false)) return launch_group_tile<true>(g, (unsigned)total, lds, st);
     return launch_group_tile<false>(g, (unsigned)total, lds, st);
 }
 
@@ -758,14 +744,14 @@ void plan_out_range(const GemmPlan& pl, uintptr_t* lo, uintptr_t* hi) {
     *hi = reinterpret_cast<uintptr_t>(p.C + pos) + sizeof(float) - 1;
 }
 
-// The plan of one descriptor (jvae_hip.h: JvaeGemmDesc; want_splits > 0 = the stored-slices form, which has to report its count).
-int plan_desc(const JvaeGemmDesc& d, GemmPlan* pl) {
-    const bool part = d.want_splits > 0;
-    const GemmArgs a = {d.M, d.N, d.K, d.batch, d.A, d.sAm, d.sAk, d.sAb, d.B, d.sBk, d.sBn, d.sBb, d.C, d.sCm, d.sCn, d.sCb,
-                        d.bias, d.bias_mode, 1, d.flags, part ? d.want_splits : d.splitk, part ? 1 : 0, d.sCsplit};
-    const int rc = gemm_plan(a, pl);
-    if (rc == 0 && part && !d.splits) return JVAE_EINVAL;
-    return rc;
+// Plan, then launch: one product alone.  *d.splits (where the caller wants it) is the number of K slices made, 0 if none was.
+int plan_and_launch(const JvaeGemmDesc& d, int bias_div, hipStream_t st) {
+    if (d.splits) *d.splits = 0;
+    GemmPlan pl;
+    const int rc = gemm_plan(d, bias_div, &pl);
+    if (rc) return rc < 0 ? rc : 0;
+    if (d.splits) *d.splits = pl.p.splitk;
+    return launch_plan(pl, st);
 }
 
 }  // namespace
@@ -785,12 +771,13 @@ int jvae_gemm_launch_ex(int M, int N, int K, int batch,
                         const float* B, long sBk, long sBn, long sBb,
                         float* C, long sCm, long sCn, long sCb,
                         const float* bias, int bias_mode, int bias_div, int flags, int splitk, hipStream_t st) {
-    const GemmArgs a = {M, N, K, batch, A, sAm, sAk, sAb, B, sBk, sBn, sBb, C, sCm, sCn, sCb,
-                        bias, bias_mode, bias_div, flags, splitk, 0, 0};
-    GemmPlan pl;
-    const int rc = gemm_plan(a, &pl);
-    if (rc) return rc < 0 ? rc : 0;
-    return launch_plan(pl, st);
+    JvaeGemmDesc d = {};
+    d.M = M; d.N = N; d.K = K; d.batch = batch;
+    d.A = A; d.sAm = sAm; d.sAk = sAk; d.sAb = sAb;
+    d.B = B; d.sBk = sBk; d.sBn = sBn; d.sBb = sBb;
+    d.C = C; d.sCm = sCm; d.sCn = sCn; d.sCb = sCb;
+    d.bias = bias; d.bias_mode = bias_mode; d.flags = flags; d.splitk = splitk;
+    return plan_and_launch(d, bias_div, st);
 }
 
 // Deterministic split-K: K is cut into *splits pieces whose partial products are STORED side by side (part + s*sCsplit,
@@ -800,15 +787,13 @@ int jvae_gemm_launch_part(int M, int N, int K, int batch,
                           const float* B, long sBk, long sBn, long sBb,
                           float* part, long sCm, long sCn, long sCb, long sCsplit, int want_splits, int* splits,
                           hipStream_t st) {
-    if (splits) *splits = 0;
-    const GemmArgs a = {M, N, K, batch, A, sAm, sAk, sAb, B, sBk, sBn, sBb, part, sCm, sCn, sCb,
-                        nullptr, 0, 1, 0, want_splits, 1, sCsplit};
-    GemmPlan pl;
-    const int rc = gemm_plan(a, &pl);
-    if (rc) return rc < 0 ? rc : 0;
-    if (!splits) return JVAE_EINVAL;
-    *splits = pl.p.splitk;
-    return launch_plan(pl, st);
+    JvaeGemmDesc d = {};
+    d.M = M; d.N = N; d.K = K; d.batch = batch;
+    d.A = A; d.sAm = sAm; d.sAk = sAk; d.sAb = sAb;
+    d.B = B; d.sBk = sBk; d.sBn = sBn; d.sBb = sBb;
+    d.C = part; d.sCm = sCm; d.sCn = sCn; d.sCb = sCb;
+    d.want_splits = want_splits < 1 ? 1 : want_splits; d.sCsplit = sCsplit; d.splits = splits;
+    return plan_and_launch(d, 1, st);
 }
 
 // Plans for n <= 8 descriptors (jvae_hip.h: JvaeGemmDesc), checked as a whole before anything is launched: an invalid descriptor or
@@ -819,25 +804,22 @@ extern "C" int jvae_gemm_group_f32(const JvaeGemmDesc* descs, int n, void* strea
     if (n > GROUP_MAX) return JVAE_ENOTSUP;
     GemmPlan plans[GROUP_MAX];
     uintptr_t lo[GROUP_MAX], hi[GROUP_MAX];
+    int* splits[GROUP_MAX];
     int cnt = 0;
     for (int i = 0; i < n; ++i) {
         const JvaeGemmDesc& d = descs[i];
         if (d.splits) *d.splits = 0;
-        const int rc = plan_desc(d, &plans[cnt]);
+        const int rc = gemm_plan(d, 1, &plans[cnt]);
         if (rc < 0) return rc;
         if (rc) continue;
         plan_out_range(plans[cnt], &lo[cnt], &hi[cnt]);
         for (int j = 0; j < cnt; ++j)
             if (lo[cnt] <= hi[j] && lo[j] <= hi[cnt]) return JVAE_EINVAL;
-        ++cnt;
+        splits[cnt++] = d.splits;
     }
     // (the numbers of slices are reported only once the whole group is known to be valid)
-    for (int i = 0, k = 0; i < n; ++i) {
-        const JvaeGemmDesc& d = descs[i];
-        if (d.M <= 0 || d.N <= 0 || d.batch <= 0) continue;
-        if (d.splits) *d.splits = plans[k].p.splitk;
-        ++k;
-    }
+    for (int k = 0; k < cnt; ++k)
+        if (splits[k]) *splits[k] = plans[k].p.splitk;
     return launch_group(plans, cnt, (hipStream_t)stream);
 }
 
@@ -869,19 +851,17 @@ struct FoldRec {
     unsigned first, blocks;      // first flat workgroup (0xffffffff: unused record) and the job's own grid
 };
 struct FoldGroup {
-    FoldRec rec[8];
+    FoldRec rec[GROUP_MAX];
 };
 
 __global__ __launch_bounds__(256) void splitk_fold_group_kernel(FoldGroup g) {
-    unsigned r = 0;
-#pragma unroll
-    for (unsigned i = 1; i < 8; ++i)
-        if (blockIdx.x >= g.rec[i].first) r = i;
-    const FoldRec& rc = g.rec[r];
-    splitk_fold_body(rc.part, rc.bias, rc.y, rc.S, rc.MN, rc.N, rc.relu, rc.accumulate, rc.bias_div, blockIdx.x - rc.first, rc.blocks);
+    unsigned local;
+    const FoldRec& rc = g.rec[group_record(g, &local)];
+    splitk_fold_body(rc.part, rc.bias, rc.y, rc.S, rc.MN, rc.N, rc.relu, rc.accumulate, rc.bias_div, local, rc.blocks);
 }
 
-inline int fold_blocks(long MN) { return (int)((MN + 255) / 256 > 4096 ? 4096 : (MN + 255) / 256); }
+// the grid of a fold (and of the fold below) over `elems` elements
+inline int fold_blocks(long elems) { return (int)((elems + 255) / 256 > 4096 ? 4096 : (elems + 255) / 256); }
 
 // The same for partial products stored [slice][position q][image n][channel cs] - rows of cs: the product's lanes run along cs, so its
 // stores are 128-byte segments; in the OUTPUT's own layout [n][cs][q] they were 4-byte stores 4 * Ps bytes apart (26 MB of
@@ -903,8 +883,7 @@ __global__ __launch_bounds__(256) void splitk_fold_qn_kernel(const float* __rest
 int jvae_splitk_fold_qn(const float* part, const float* bias, float* y, int S, int N, int Cs, int Ps, hipStream_t st) {
     const long total = (long)Ps * N * Cs;
     if (total == 0) return 0;
-    const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(splitk_fold_qn_kernel, dim3(blocks), dim3(256), 0, st, part, bias, y, S, N, Cs, Ps);
+    hipLaunchKernelGGL(splitk_fold_qn_kernel, dim3(fold_blocks(total)), dim3(256), 0, st, part, bias, y, S, N, Cs, Ps);
     JVAE_LAUNCH_CHECK();
     return 0;
 }
@@ -912,8 +891,7 @@ int jvae_splitk_fold_qn(const float* part, const float* bias, float* y, int S, i
 int jvae_splitk_fold(const float* part, const float* bias, float* y, int S, long MN, int N, int relu, int accumulate,
                      hipStream_t st, int bias_div) {
     if (MN == 0) return 0;
-    const int blocks = fold_blocks(MN);
-    hipLaunchKernelGGL(splitk_fold_kernel, dim3(blocks), dim3(256), 0, st, part, bias, y, S, MN, N, relu, accumulate,
+    hipLaunchKernelGGL(splitk_fold_kernel, dim3(fold_blocks(MN)), dim3(256), 0, st, part, bias, y, S, MN, N, relu, accumulate,
                        bias_div > 0 ? bias_div : 1);
     JVAE_LAUNCH_CHECK();
     return 0;
@@ -928,7 +906,7 @@ extern "C" int jvae_splitk_fold_f32(const float* part, const float* bias, float*
 extern "C" int jvae_splitk_fold_group_f32(const JvaeFoldDesc* descs, int n, void* stream) {
     if (n == 0) return 0;
     if (n < 0 || !descs) return JVAE_EINVAL;
-    if (n > 8) return JVAE_ENOTSUP;
+    if (n > GROUP_MAX) return JVAE_ENOTSUP;
     FoldGroup g;
     int cnt = 0, last = -1;
     unsigned total = 0;
@@ -952,7 +930,7 @@ extern "C" int jvae_splitk_fold_group_f32(const JvaeFoldDesc* descs, int n, void
         const JvaeFoldDesc& d = descs[last];
         return jvae_splitk_fold(d.part, d.bias, d.y, d.S, d.MN, d.N, d.relu, d.accumulate, (hipStream_t)stream);
     }
-    for (int i = cnt; i < 8; ++i) { g.rec[i] = g.rec[0]; g.rec[i].first = 0xffffffffu; }
+    pad_records(&g, cnt);
     hipLaunchKernelGGL(splitk_fold_group_kernel, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
     JVAE_LAUNCH_CHECK();
     return 0;
@@ -972,16 +950,25 @@ extern "C" int jvae_gemm_route(const JvaeGemmDesc* d, JvaeGemmRoute* out) {
     if (!d || !out) return JVAE_EINVAL;
     *out = JvaeGemmRoute{-1, 0, 0, 0, 0, 0, 0, 0, 0};
     GemmPlan pl;
-    const int rc = plan_desc(*d, &pl);
+    const int rc = gemm_plan(*d, 1, &pl);
     if (rc) return rc < 0 ? rc : 0;
     *out = JvaeGemmRoute{pl.variant, (int)pl.gx, (int)pl.gy, (int)pl.gz, pl.p.splitk, pl.p.kchunk, pl.p.vecA, pl.p.vecB, pl.lds};
     return 0;
 }
 
+// "TILE64_AM_BK" ... "X3_AK_BN_D3" (jvae_hip.h), spelled from the table
 extern "C" const char* jvae_gemm_variant_name(int variant) {
-    static const char* const names[16] = {
-        "TILE64_AM_BK", "TILE64_AM_BN", "TILE64_AK_BK", "TILE64_AK_BN", "TILE128_AM_BK", "TILE128_AM_BN", "TILE128_AK_BK",
-        "TILE128_AK_BN", "X3_AM_BK_D1", "X3_AM_BK_D3", "X3_AM_BN_D1", "X3_AM_BN_D3", "X3_AK_BK_D1", "X3_AK_BK_D3", "X3_AK_BN_D1",
-        "X3_AK_BN_D3"};
-    return (variant >= 0 && variant < 16) ? names[variant] : nullptr;
+    struct Names {
+        char s[NVAR][16];
+        Names() {
+            for (int v = 0; v < NVAR; ++v) {
+                const Variant& d = VARIANTS[v];
+                const char *a = d.ak ? "AK" : "AM", *b = d.bnc ? "BN" : "BK";
+                if (d.x3) snprintf(s[v], sizeof s[v], "X3_%s_%s_D%d", a, b, d.depth);
+                else snprintf(s[v], sizeof s[v], "TILE%d_%s_%s", d.bm, a, b);
+            }
+        }
+    };
+    static const Names names;
+    return (variant >= 0 && variant < NVAR) ? names.s[variant] : nullptr;
 }

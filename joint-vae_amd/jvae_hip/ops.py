@@ -74,17 +74,23 @@ def gemm_desc(M, N, K, A, sA, B, sB, C, sC, bias=None, bias_mode=0, flags=0, spl
     return (M, N, K, batch, A, sA, B, sB, C, sC, bias, bias_mode, flags, splitk)
 
 
+def _fill_gemm_desc(d, rec, ptr):
+    """A gemm_desc record into the L.GemmDesc d; ptr turns an operand into its address."""
+    M, N, K, batch, A, sA, B, sB, C, sC, bias, bias_mode, flags, splitk = rec
+    d.M, d.N, d.K, d.batch = M, N, K, batch
+    d.A, (d.sAm, d.sAk, d.sAb) = ptr(A), sA
+    d.B, (d.sBk, d.sBn, d.sBb) = ptr(B), sB
+    d.C, (d.sCm, d.sCn, d.sCb) = ptr(C), sC
+    d.bias, d.bias_mode, d.flags, d.splitk = ptr(bias), bias_mode, flags, splitk
+
+
 def gemm_group(descs):
     """Independent products (gemm_desc records, at most 8, outputs that do not overlap) in ONE launch on the current stream.
     Every product runs the kernel, tiles and K slices that gemm() gives it alone: the same bits."""
     lib = L.load()
     arr = (L.GemmDesc * max(len(descs), 1))()
-    for d, (M, N, K, batch, A, sA, B, sB, C, sC, bias, bias_mode, flags, splitk) in zip(arr, descs):
-        d.M, d.N, d.K, d.batch = M, N, K, batch
-        d.A, (d.sAm, d.sAk, d.sAb) = L.ptr(A), sA
-        d.B, (d.sBk, d.sBn, d.sBb) = L.ptr(B), sB
-        d.C, (d.sCm, d.sCn, d.sCb) = L.ptr(C), sC
-        d.bias, d.bias_mode, d.flags, d.splitk = L.ptr(bias), bias_mode, flags, splitk
+    for d, rec in zip(arr, descs):
+        _fill_gemm_desc(d, rec, L.ptr)
     L.check(lib.jvae_gemm_group_f32(arr, len(descs), L.stream_ptr()), 'jvae_gemm_group_f32')
 
 
@@ -100,11 +106,7 @@ def gemm_route(M, N, K, A, sA, B, sB, C, sC, bias=None, bias_mode=0, flags=0, sp
     lib = L.load()
     addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
     d, r, made = L.GemmDesc(), L.GemmRoute(), c_int(0)
-    d.M, d.N, d.K, d.batch = M, N, K, batch
-    d.A, (d.sAm, d.sAk, d.sAb) = addr(A), sA
-    d.B, (d.sBk, d.sBn, d.sBb) = addr(B), sB
-    d.C, (d.sCm, d.sCn, d.sCb) = addr(C), sC
-    d.bias, d.bias_mode, d.flags, d.splitk = addr(bias), bias_mode, flags, splitk
+    _fill_gemm_desc(d, gemm_desc(M, N, K, A, sA, B, sB, C, sC, bias, bias_mode, flags, splitk, batch), addr)
     d.want_splits, d.sCsplit = want_splits, sCsplit
     if want_splits > 0:
         d.splits = ctypes.pointer(made)
@@ -168,20 +170,10 @@ class _Linear(torch.autograd.Function):
         x2 = _c(_f32(x, 'linear').reshape(-1, x.shape[-1]))
         w_in = w
         w = _c(w)
-        R, I = x2.shape
         O = w.shape[0]
-        y = torch.empty((R, O), device=x.device, dtype=torch.float32)
-        S = _linear_split(R, O, I)
-        if S > 1:
-            # few output tiles, long K: K slices as the batch of one launch, then a fixed-order fold (+bias, ReLU)
-            part = torch.empty((S, R, O), device=x.device, dtype=torch.float32)
-            Ks = I // S
-            gemm(R, O, Ks, x2, (I, 1, Ks), w, (1, I, Ks), part, (O, 1, R * O), batch=S)
-            L.check(L.load().jvae_splitk_fold_f32(L.ptr(part), L.ptr(b), L.ptr(y), S, R * O, O, int(act == RELU), 0,
-                                                  L.stream_ptr()), 'jvae_splitk_fold_f32')
-        else:
-            gemm(R, O, I, x2, (I, 1, 0), w, (1, I, 0), y, (O, 1, 0), bias=b, bias_mode=1 if b is not None else 0,
-                 flags=2 if act == RELU else 0)
+        descs, folds = [], []
+        y = _linear_fwd_products(x2, w, b, act, descs, folds)
+        _run_products(descs, folds)
         if act in (SIGMOID, LEAKY):           # (ReLU rides in the product's epilogue; these two are a pass of their own, in place)
             L.check(L.load().jvae_act_fwd_f32(L.ptr(y), L.ptr(y), y.numel(), act, L.stream_ptr()), 'act_fwd')
         ctx.save_for_backward(x2, w, y if act != IDENT else None)

@@ -99,6 +99,27 @@ def test_route_reports_the_plan_fields():
     assert (r.variant, r.slices, r.kchunk, r.grid) == ('TILE64_AK_BN', 1, 0, (1, 2, 1))
 
 
+def test_lds_bytes_of_every_variant():
+    """GemmRoute.lds per variant name, one row of the table each: the fp32 images BK * ((BM + 4) + (BN + 4)) * 4 of the tile
+    kernels and three bf16 planes per operand of the split-bf16 kernels - 64 rows of 80 bytes for an operand contiguous along k,
+    32 k of 192 bytes otherwise.  The figures are written out: they are what the kernels took before the variant table."""
+    want = {'TILE64': 17408, 'TILE128': 33792, 'X3_AM_BK': 33792, 'X3_AM_BN': 36864, 'X3_AK_BK': 30720, 'X3_AK_BN': 33792}
+    assert want['TILE64'] == 32 * 2 * 68 * 4 and want['TILE128'] == 32 * 2 * 132 * 4
+    kc, kr = 3 * 64 * 80, 3 * 32 * 192
+    assert [want['X3_' + n] for n in ('AM_BK', 'AM_BN', 'AK_BK', 'AK_BN')] == [kr + kc, kr + kr, kc + kc, kc + kr]
+    L, seen = lib.load(), {}
+    for c in gc.ROWS:
+        if c.expect not in seen:
+            L.jvae_conv2d_set_split_bf16(c.split)
+            r = c.route()
+            assert r.variant == c.expect, c.name
+            seen[c.expect] = r.lds
+    assert set(seen) == set(gc.VARIANTS)
+    for name, lds in seen.items():
+        key = name.split('_')[0] if name.startswith('TILE') else name[:-3]
+        assert lds == want[key], (name, lds)
+
+
 def test_route_return_codes_are_those_of_the_launch_entries():
     L = lib.load()
     base = dict(A=0x1000, sA=(8, 1, 0), B=0x2000, sB=(8, 1, 0), C=0x3000, sC=(8, 1, 0))

@@ -828,6 +828,46 @@ int jvae_nearest_centroid_f32(const float* mu, const float* centroids, long long
 int jvae_histogram_f32(const float* values, const double* edges, const int* group, long long* counts, long long* nonfinite, long n,
                        int B, int G, void* stream);
 
+/* ---- 2-D projections of recorded latents: exact t-SNE and PCA (csrc/embed.hip; reference ft/inspection.py::proj2d, there
+ * through scikit-learn) ------------------------------------------------------------------------------------------------
+ * None of the entry points allocates or synchronises.  No floating-point atomics: every sum is a fixed-order reduction whose
+ * order hangs on the sizes alone, the same bits run to run.  Pair arithmetic is fp64; tensors are fp32 unless stated.
+ * Distances: x (N, K) -> d (N, N), d_ij = fp32(sum_k (double(x_ik) - double(x_jk))^2), k ascending, each operation rounded on
+ * its own: d is exactly symmetric with an exactly zero diagonal.
+ * Affinities: d (N, N) -> beta (N,) fp64, S (N,) fp64 and P (N, N): per row scikit-learn's search for the precision beta_i at
+ * which the conditional distribution p_j|i = exp(-d_ij beta_i) / S_i (j != i) has the given perplexity (beta from 1, at most
+ * 100 steps, stop at |H - log perplexity| <= 1e-5f, S = 0 replaced by 1e-8f), then
+ *   P_ij = max((p_j|i + p_i|j) / max(sum P, eps), eps),  eps = 2^-52,
+ * formed in fp64 and rounded once.  The diagonal holds eps.  ws: jvae_tsne_affinities_workspace_bytes(N) bytes, 8-byte aligned.
+ * Gradient: P (N, N), y (N, 2) -> g (N, 2), with qn_ij = 1 / (1 + |y_i - y_j|^2) and Z = sum_{i != j} qn_ij
+ *   g_i = 4 (exaggeration sum_j P_ij qn_ij (y_i - y_j) - sum_j qn_ij^2 (y_i - y_j) / Z)      (j != i)
+ * rounded once to fp32; as in scikit-learn the distance in qn is taken on the widened y and the factor (y_i - y_j) is the fp32
+ * difference, widened.  P itself is never rescaled.  stats (2 fp64 device words, or NULL): a second pass leaves
+ *   stats[0] = sum_{i != j} f P_ij log(max(f P_ij, eps) / max(qn_ij / Z, eps)),  f = exaggeration;   stats[1] = |g|_2.
+ * ws: jvae_tsne_gradient_workspace_bytes(N) bytes, 8-byte aligned.
+ * Update: scikit-learn's gradient-descent step on the 2 N values, as numpy executes it in fp32 (each product and sum rounded):
+ *   gains = max(update * g < 0 ? gains + 0.2 : gains * 0.8, 0.01);  g *= gains;  update = momentum * update - lr * g;  y += update
+ * norm (one fp64 device word, or NULL) receives |g|_2 of the scaled g, which is what scikit-learn's stopping rule looks at.
+ * 2 <= N <= 16384 (a row of distances in LDS) and 1 <= K <= 1024 for the above, else -2 (JVAE_ENOTSUP); N < 2: -1.
+ * PCA moments: x (N, K) -> mean (K,) fp64 and cov (K, K) fp64 = (x - mean)^T (x - mean) / (N - 1), summed in fp64 over at most
+ * 8 slabs of rows that are folded in ascending order; cov is exactly symmetric.  2 <= N <= 2^24, K <= 1024.
+ * ws: jvae_pca_moments_workspace_bytes(N, K) bytes, 8-byte aligned (-3, JVAE_EWORKSPACE, when smaller).
+ * Projection: out (N, n_components) = fp32((x - mean) V^T), V (n_components, K) fp64, k ascending.  n_components <= 16.
+ * Any other malformed argument: -1 (JVAE_EINVAL).  A refused call launches nothing and writes nothing. */
+int jvae_pairwise_sqdist_f32(const float* x, float* d, int N, int K, void* stream);
+size_t jvae_tsne_affinities_workspace_bytes(int N);
+int jvae_tsne_affinities_f32(const float* d, float* P, double* beta, double* S, float perplexity, int N, void* ws, size_t ws_bytes,
+                             void* stream);
+size_t jvae_tsne_gradient_workspace_bytes(int N);
+int jvae_tsne_gradient_f32(const float* P, const float* y, float* g, float exaggeration, int N, double* stats, void* ws,
+                           size_t ws_bytes, void* stream);
+int jvae_tsne_update_f32(float* y, float* update, float* gains, float* g, float momentum, float lr, int N, double* norm,
+                         void* stream);
+size_t jvae_pca_moments_workspace_bytes(long N, int K);
+int jvae_pca_moments_f32(const float* x, double* mean, double* cov, long N, int K, void* ws, size_t ws_bytes, void* stream);
+int jvae_project_f32(const float* x, const double* mean, const double* V, float* out, long N, int K, int n_components,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,10 +10,17 @@ Three layers, kept apart so that the CPU tests can hold the text to the referenc
                        from numpy on the host: `bin_edges`), quantiles a `torch.sort` whose two neighbouring order statistics per
                        quantile come to the host and are interpolated there in fp64 (`quantiles`), nearest centroids
                        `ops.nearest_centroid`.
-  the reference's functions  `output_latent_distribution`, `losses_distribution_graphs`, `loss_comparisons`, `estimate_y`, `dmu`.
+  the reference's functions  `output_latent_distribution`, `losses_distribution_graphs`, `loss_comparisons`, `estimate_y`, `dmu`,
+                       `proj2d`, `plot2d`.
+
+`proj2d` draws the latent means of the recorded sets, the class centroids and the alternate prior in two dimensions.  The
+reference takes the projection from scikit-learn; here `PCA` and `TSNE` (the exact method, two components) are this module's
+own classes over the kernels of csrc/embed.hip - moments and projection for the PCA (the K x K eigen-decomposition is numpy's,
+on the host), squared distances, perplexity search, joint probabilities, gradient and update for the t-SNE - and scikit-learn
+is not needed.
 
 Outputs are file paths (the directory is made) and `sys.stdout`; a matplotlib `Axes` is served when matplotlib imports.
-`proj2d`, `plot2d`, `to_mat` (sklearn, pandas, scipy) and the command-line blocks stay in the reference.
+`to_mat` (scipy) and the command-line blocks stay in the reference.
 """
 import errno
 import logging
@@ -359,3 +366,250 @@ def loss_comparisons(net, root=os.path.join(DEFAULT_RESULTS_DIR, '%j', 'losses')
     n_pred = {s: torch.bincount(y_pred[s], minlength=net.num_labels).cpu().numpy() for s in y_pred}
     with open(os.path.join(root, 'predicted-classes-per-set.tab'), 'w') as f:
         f.write(predicted_classes_text(n_pred, net.num_labels))
+
+
+# ------------------------------------------------------------------- 2-D pictures of the latent means (ft/inspection.py:100-206)
+def _as_device_rows(X, device, what):
+    """A numpy array or a tensor (N, K) -> a dense fp32 tensor on the device (the kernels have no CPU path)."""
+    if not torch.is_tensor(X):
+        X = torch.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float32)))
+    if X.dim() != 2:
+        raise ValueError(f'{what}: a (N, K) array expected, got {tuple(X.shape)}')
+    if device is None:
+        device = X.device if X.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    return X.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def principal_axes(cov, n_components):
+    """The host part of the PCA, fp64: cov (K, K) symmetric -> (components (n_components, K), their eigenvalues), largest
+    eigenvalue first, the sign of each component such that its largest-magnitude entry is positive (scikit-learn's svd_flip on
+    the components)."""
+    w, v = np.linalg.eigh(np.asarray(cov, dtype=np.float64))
+    order = np.argsort(-w, kind='stable')[:n_components]
+    comp = v[:, order].T.copy()
+    big = np.abs(comp).argmax(axis=1)
+    comp *= np.where(comp[np.arange(len(comp)), big] < 0, -1., 1.)[:, None]
+    return comp, w[order]
+
+
+class PCA:
+    """sklearn.decomposition.PCA(n_components) as far as `proj2d` uses it: `fit_transform` and the attributes `mean_`,
+    `components_`, `explained_variance_`.  Means and the centred covariance are summed on the device in fp64
+    (`ops.pca_moments`), the K x K eigen-decomposition is numpy's on the host in fp64, the projection is `ops.project`."""
+    MAX_COMPONENTS = ops.EMBED_MAX_COMPONENTS
+
+    def __init__(self, n_components=2, device=None):
+        self.n_components = int(n_components)
+        self.device = device
+
+    def fit_transform(self, X):
+        x = _as_device_rows(X, self.device, 'PCA')
+        N, K = x.shape
+        if not 1 <= self.n_components <= min(N, K, self.MAX_COMPONENTS):
+            raise ValueError(f'PCA: n_components = {self.n_components} must be between 1 and min(N, K, {self.MAX_COMPONENTS}) = '
+                             f'{min(N, K, self.MAX_COMPONENTS)}')
+        mean, cov = ops.pca_moments(x)
+        self.mean_ = mean.cpu().numpy()
+        self.components_, self.explained_variance_ = principal_axes(cov.cpu().numpy(), self.n_components)
+        return self.transform(x)
+
+    def transform(self, X):
+        x = _as_device_rows(X, self.device, 'PCA')
+        dev = x.device
+        return ops.project(x, torch.from_numpy(self.mean_).to(dev), torch.from_numpy(self.components_).to(dev)).cpu().numpy()
+
+
+class TSNE:
+    """sklearn.manifold.TSNE(method='exact') in two dimensions, on the device: squared distances, the perplexity search and the
+    joint probabilities once (`ops.pairwise_sqdist`, `ops.tsne_affinities`), then scikit-learn's gradient descent - 250
+    iterations at momentum 0.5 with the early exaggeration, the rest at momentum 0.8, gains and update restarted in between -
+    with one gradient and one update launch group per iteration.  Every 50th iteration two fp64 words (the KL divergence, the
+    norm of the scaled gradient) are read back for scikit-learn's two stopping rules.  `kl_divergence_` is the KL kernel's
+    value AT `embedding_` (scikit-learn keeps the value one update earlier).  The reference's default, Barnes-Hut, is an
+    approximation of this method; it is not built.  N <= ops.EMBED_MAX_N points."""
+    _EXPLORATION_MAX_ITER = 250
+    _N_ITER_CHECK = 50
+
+    def __init__(self, n_components=2, *, perplexity=30., early_exaggeration=12., learning_rate='auto', max_iter=1000,
+                 n_iter_without_progress=300, min_grad_norm=1e-7, init='pca', random_state=None, device=None):
+        if n_components != 2:
+            raise NotImplementedError('TSNE: two components only')
+        self.n_components = 2
+        self.perplexity, self.early_exaggeration, self.learning_rate = perplexity, early_exaggeration, learning_rate
+        self.max_iter, self.n_iter_without_progress, self.min_grad_norm = max_iter, n_iter_without_progress, min_grad_norm
+        self.init, self.random_state, self.device = init, random_state, device
+
+    def _initial(self, x):
+        N = x.shape[0]
+        if isinstance(self.init, str) and self.init == 'pca':
+            y = PCA(2, device=x.device).fit_transform(x)
+            return (y / np.std(y[:, 0]) * 1e-4).astype(np.float32)
+        if isinstance(self.init, str) and self.init == 'random':
+            rs = self.random_state
+            rs = rs if isinstance(rs, np.random.RandomState) else (np.random.mtrand._rand if rs is None else np.random.RandomState(rs))
+            return 1e-4 * rs.standard_normal(size=(N, 2)).astype(np.float32)
+        if isinstance(self.init, str):
+            raise ValueError(f"TSNE: init must be 'pca', 'random' or an array, not {self.init!r}")
+        y = self.init.detach().cpu().numpy() if torch.is_tensor(self.init) else np.asarray(self.init)
+        if y.shape != (N, 2):
+            raise ValueError(f'TSNE: init of shape {(N, 2)} expected, got {y.shape}')
+        return y.astype(np.float32)
+
+    def _descend(self, P, state, it, max_iter, momentum, n_iter_without_progress, exaggeration):
+        y, update, gains, g, words = state
+        update.zero_()
+        gains.fill_(1.)
+        best_error, best_iter, i = np.finfo(float).max, it, it
+        for i in range(it, max_iter):
+            check = (i + 1) % self._N_ITER_CHECK == 0
+            ops.tsne_gradient(P, y, exaggeration, g=g, stats=words[:2] if check else None)
+            ops.tsne_update(y, update, gains, g, momentum, self.learning_rate_, norm=words[2:] if check else None)
+            if check:
+                error, _, grad_norm = words.tolist()          # the one read of this check: three fp64 words
+                if error < best_error:
+                    best_error, best_iter = error, i
+                elif i - best_iter > n_iter_without_progress:
+                    break
+                if grad_norm <= self.min_grad_norm:
+                    break
+        return i
+
+    def fit_transform(self, X):
+        x = _as_device_rows(X, self.device, 'TSNE')
+        N = x.shape[0]
+        if self.perplexity >= N:
+            raise ValueError(f'perplexity ({self.perplexity}) must be less than n_samples ({N})')
+        if self.learning_rate == 'auto':
+            self.learning_rate_ = max(N / self.early_exaggeration / 4, 50)
+        else:
+            self.learning_rate_ = float(self.learning_rate)
+        y0 = self._initial(x)
+        d = ops.pairwise_sqdist(x)
+        P = ops.tsne_affinities(d, self.perplexity)[0]
+        del d
+        y = torch.from_numpy(np.ascontiguousarray(y0)).to(x.device)
+        words = torch.zeros(3, dtype=torch.float64, device=x.device)
+        state = (y, torch.empty_like(y), torch.empty_like(y), torch.empty_like(y), words)
+        it = self._descend(P, state, 0, self._EXPLORATION_MAX_ITER, 0.5, self._EXPLORATION_MAX_ITER, self.early_exaggeration)
+        if it < self._EXPLORATION_MAX_ITER or self.max_iter - self._EXPLORATION_MAX_ITER > 0:
+            it = self._descend(P, state, it + 1, self.max_iter, 0.8, self.n_iter_without_progress, 1.)
+        self.n_iter_ = it
+        self.kl_divergence_ = self.kl_divergence(P, y)
+        self.embedding_ = y.cpu().numpy()
+        return self.embedding_
+
+    @staticmethod
+    def kl_divergence(P, y, exaggeration=1.):
+        """KL(exaggeration P || Q(y)) through the KL kernel: P (N, N) and y (N, 2) on the device -> a Python float."""
+        words = torch.zeros(2, dtype=torch.float64, device=y.device)
+        ops.tsne_gradient(P, y, exaggeration, stats=words)
+        return float(words[0])
+
+
+def _split_key(k):
+    """'<set>-<pre|ft>' -> (set, suffix), split at the LAST '-' (held-out names such as cifar10-3 keep theirs); a key without one
+    -> (k, None)."""
+    head, sep, tail = k.rpartition('-')
+    return (head, tail) if sep else (k, None)
+
+
+def proj2d_csv_text(mu_, y_, tset):
+    """The rows `x1,x2,y,set,dist,ft` of proj2d's csv file: set rows (set, 'ind' for the training set else 'ood', 'pre' | 'ft'),
+    centroids ('centroids', 'ind', 'both'), the alternate prior ('alt', 'ood', 'both')."""
+    rows = [','.join(['x1', 'x2', 'y', 'set', 'dist', 'ft']) + '\n']
+    for k in mu_:
+        if k == 'centroids':
+            dset, dist, ft = 'centroids', 'ind', 'both'
+        elif k == 'alternate':
+            dset, dist, ft = 'alt', 'ood', 'both'
+        else:
+            dset, ft = _split_key(k)
+            dist = 'ind' if dset == tset else 'ood'
+        for (x1, x2), y in zip(mu_[k], y_[k]):
+            rows.append('{x1},{x2},{y},{s},{d},{ft}\n'.format(x1=x1, x2=x2, y=y, s=dset, d=dist, ft=ft))
+    return ''.join(rows)
+
+
+def proj2d(sample_recorders_pre, sample_recorders_ft, tset, include_alternate=False, N=60, N_=10, Model=TSNE, csv_file=None):
+    """ft/inspection.py:100-179: ONE 2-D projection (`Model(2).fit_transform`) of the stack, over the recorders before and after
+    fine-tuning and over their sets in recorder order, of N_ copies of the class centroids (and of the alternate prior with
+    include_alternate) followed by the first N latent means of the sets whose name starts with `tset`, N // 10 of the others;
+    the result is cut apart with the same slices -> (mu_, y_): 'centroids' (the C centroids; the reference hard-codes 10),
+    'alternate', '<set>-pre', '<set>-ft' -> (n, 2) arrays and their labels, the class names for `tset` and the set name for the
+    others.  The class names come from the registry of `torch_load`: no data set is opened.  The reference's function cannot
+    run (a `np.zeros()` without a shape) and its csv block labels every set row `alt,ood,both`: this is the evident intent."""
+    from jvae_compat.torch_load import get_classes_by_name
+
+    def numpy(t):
+        return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+    centroids = numpy(sample_recorders_pre[tset]._aux['centroids'])
+    C = centroids.shape[0]
+    classes = list(get_classes_by_name(tset))
+    if len(classes) != C:
+        raise ValueError(f'proj2d: {C} centroids recorded for {tset}, which has {len(classes)} classes')
+    centroids_labels = np.expand_dims(np.array(classes, dtype=object), 1)
+    if include_alternate:
+        centroids = np.vstack([centroids, numpy(sample_recorders_pre[tset]._aux['alternate']).reshape(1, -1)])
+        centroids_labels = np.vstack([centroids_labels, np.array([['ood']], dtype=object)])
+
+    mu = np.ndarray((0, centroids.shape[-1]))
+    y = np.ndarray((0, 1), dtype=object)
+    for sample_recorders in (sample_recorders_pre, sample_recorders_ft):
+        for s in sample_recorders:
+            _N = N if s.startswith(tset) else N // 10
+            batch = numpy(sample_recorders[s]['mu'])[:_N]
+            mu = np.vstack([mu, *([centroids] * N_), batch])
+            if s == tset:
+                c_batch = np.expand_dims(centroids_labels.take(numpy(sample_recorders[s]['y'])[:_N]), 1)
+            else:
+                c_batch = np.zeros((len(batch), 1), object)
+                c_batch[:] = s
+            y = np.vstack([y, *([centroids_labels] * N_), c_batch])
+
+    logging.info('Mu of shape %s', mu.shape)
+    mu = Model(2).fit_transform(mu)
+
+    mu_, y_ = {}, {}
+    start = 0
+    for sample_recorders, suffix in zip((sample_recorders_pre, sample_recorders_ft), ('pre', 'ft')):
+        for s in sample_recorders:
+            _N = min(N if s.startswith(tset) else N // 10, len(numpy(sample_recorders[s]['mu'])))
+            mu_['centroids'] = mu[start:start + C]
+            y_['centroids'] = classes
+            if include_alternate:
+                mu_['alternate'] = mu[start + C:start + C + 1]
+                y_['alternate'] = ['ood']
+            start += N_ * len(centroids)
+            k = '{}-{}'.format(s, suffix)
+            mu_[k] = mu[start:start + _N]
+            y_[k] = y[start:start + _N].squeeze(1)
+            start += _N
+
+    if csv_file:
+        with open(csv_file, 'w') as f:
+            f.write(proj2d_csv_text(mu_, y_, tset))
+    return mu_, y_
+
+
+def plot2d(mu2d, dset, ax=None):
+    """ft/inspection.py:182-206: the scatter plot of proj2d's `mu_` - the sets of `dset` and the centroids in blue, the other
+    sets and the alternate prior in red, crosses for the centroids and the prior.  Served when matplotlib imports."""
+    if _axes_type() is None:
+        raise ImportError('plot2d needs matplotlib')
+    from matplotlib import pyplot as plt
+    marker = {k: ',' for k in mu2d}
+    marker['centroids'] = 'x'
+    color = {'centroids': 'b'}
+    for k in mu2d:
+        if k.startswith(dset):
+            color[k] = 'b'
+    if 'alternate' in marker:
+        marker['alternate'] = 'x'
+        color['alternate'] = 'r'
+    color.update({k: 'r' for k in mu2d if k not in color})
+    ax = ax or plt.gca()
+    for k in mu2d:
+        facecolor = color[k] if marker[k] == 'x' else 'none'
+        ax.scatter(mu2d[k][:, 0], mu2d[k][:, 1], marker=marker[k], edgecolors=color[k], facecolors=facecolor)
+    return ax

@@ -175,6 +175,15 @@ _SIGS = {
     'jvae_latent_moments_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
     'jvae_nearest_centroid_f32': (c_int, [P, P, P, P, c_long, c_int, c_int, P]),
     'jvae_histogram_f32': (c_int, [P, P, P, P, P, c_long, c_int, c_int, P]),
+    'jvae_pairwise_sqdist_f32': (c_int, [P, P, c_int, c_int, P]),
+    'jvae_tsne_affinities_workspace_bytes': (c_size_t, [c_int]),
+    'jvae_tsne_affinities_f32': (c_int, [P, P, P, P, c_float, c_int, P, c_size_t, P]),
+    'jvae_tsne_gradient_workspace_bytes': (c_size_t, [c_int]),
+    'jvae_tsne_gradient_f32': (c_int, [P, P, P, c_float, c_int, P, P, c_size_t, P]),
+    'jvae_tsne_update_f32': (c_int, [P, P, P, P, c_float, c_float, c_int, P, P]),
+    'jvae_pca_moments_workspace_bytes': (c_size_t, [c_long, c_int]),
+    'jvae_pca_moments_f32': (c_int, [P, P, P, c_long, c_int, P, c_size_t, P]),
+    'jvae_project_f32': (c_int, [P, P, P, P, c_long, c_int, c_int, P]),
 }
 
 

@@ -2161,6 +2161,124 @@ def histogram_check(device=None):
             raise ValueError(f'histogram: {bad} non-finite value(s) were met (they are in no bin)')
 
 
+# ------------------------------------------------------------ 2-D projections: exact t-SNE and PCA (csrc/embed.hip)
+EMBED_MAX_N = 16384         # points of a t-SNE: a row of fp32 distances in LDS
+EMBED_MAX_K = 1024          # dimensions of the points
+EMBED_MAX_COMPONENTS = 16
+
+
+def _embed_ws(nbytes, device, what):
+    if not nbytes:
+        raise L.JvaeHipError(f'{what}: sizes out of range (unsupported configuration)')
+    ws = L.workspace(nbytes + 8, device)
+    off = (-ws.data_ptr()) % 8
+    return ws.data_ptr() + off, ws.numel() - off
+
+
+def _embed_rows(x, what):
+    x = _c(_f32(x, what))
+    L.ptr(x)
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise L.JvaeHipError(f'{what}: (N, K) expected, got {tuple(x.shape)}')
+    return x
+
+
+def pairwise_sqdist(x):
+    """x (N, K) fp32 -> d (N, N) fp32, d_ij = fp32(sum_k (double(x_ik) - double(x_jk))^2) with k ascending: exactly symmetric,
+    the diagonal exactly 0.  2 <= N <= EMBED_MAX_N, K <= EMBED_MAX_K.  One launch, nothing synchronised."""
+    x = _embed_rows(x, 'pairwise_sqdist')
+    N, K = x.shape
+    d = torch.empty((N, N), dtype=torch.float32, device=x.device)
+    L.check(L.load().jvae_pairwise_sqdist_f32(L.ptr(x), L.ptr(d), N, K, L.stream_ptr()), 'jvae_pairwise_sqdist_f32')
+    return d
+
+
+def tsne_affinities(d, perplexity):
+    """d (N, N) fp32 squared distances -> (P (N, N) fp32, beta (N,) fp64, S (N,) fp64): scikit-learn's perplexity search per row
+    in fp64 (beta_i, and the sum S_i of exp(-d_ij beta_i) over j != i) and the joint probabilities
+    max((p_j|i + p_i|j) / sum, 2^-52) formed in fp64 and rounded once.  Three launches, nothing synchronised."""
+    d = _embed_rows(d, 'tsne_affinities')
+    N = d.shape[0]
+    if d.shape[1] != N:
+        raise L.JvaeHipError(f'tsne_affinities: a square (N, N) matrix expected, got {tuple(d.shape)}')
+    lib = L.load()
+    ws, nbytes = _embed_ws(lib.jvae_tsne_affinities_workspace_bytes(N), d.device, 'tsne_affinities')
+    P = torch.empty_like(d)
+    beta = torch.empty(N, dtype=torch.float64, device=d.device)
+    S = torch.empty(N, dtype=torch.float64, device=d.device)
+    L.check(lib.jvae_tsne_affinities_f32(L.ptr(d), L.ptr(P), L.ptr(beta), L.ptr(S), float(perplexity), N, ws, nbytes,
+                                         L.stream_ptr()), 'jvae_tsne_affinities_f32')
+    return P, beta, S
+
+
+def tsne_gradient(P, y, exaggeration=1., g=None, stats=None):
+    """P (N, N) fp32, y (N, 2) fp32 -> g (N, 2) fp32, the gradient of KL(exaggeration P || Q) in y: pair arithmetic and sums in
+    fp64, one rounding.  stats: a (2,) fp64 device tensor that receives the KL divergence and |g|_2 (a second pass), or None.
+    Nothing is synchronised."""
+    P, y = _embed_rows(P, 'tsne_gradient'), _embed_rows(y, 'tsne_gradient')
+    N = P.shape[0]
+    if P.shape[1] != N or tuple(y.shape) != (N, 2) or y.device != P.device:
+        raise L.JvaeHipError(f'tsne_gradient: P (N, N) and y (N, 2) on one device expected, got {tuple(P.shape)} and {tuple(y.shape)}')
+    if g is None:
+        g = torch.empty_like(y)
+    if g.dtype != torch.float32 or g.shape != y.shape or g.device != y.device or not g.is_contiguous():
+        raise L.JvaeHipError('tsne_gradient: g (N, 2) fp32, dense, on the device of y expected')
+    if stats is not None and (stats.dtype != torch.float64 or tuple(stats.shape) != (2,) or stats.device != y.device):
+        raise L.JvaeHipError('tsne_gradient: stats (2,) fp64 on the device of y expected')
+    lib = L.load()
+    ws, nbytes = _embed_ws(lib.jvae_tsne_gradient_workspace_bytes(N), P.device, 'tsne_gradient')
+    L.check(lib.jvae_tsne_gradient_f32(L.ptr(P), L.ptr(y), L.ptr(g), float(exaggeration), N, L.ptr(stats), ws, nbytes,
+                                       L.stream_ptr()), 'jvae_tsne_gradient_f32')
+    return g
+
+
+def tsne_update(y, update, gains, g, momentum, lr, norm=None):
+    """One step of scikit-learn's gradient descent, in place on y, update, gains and g (all (N, 2) fp32), as numpy executes it in
+    fp32: gains = max(gains + 0.2 where update * g < 0 else gains * 0.8, 0.01), g *= gains, update = momentum * update - lr * g,
+    y += update.  norm: a (1,) fp64 device tensor that receives |g|_2 of the scaled g, or None.  Nothing is synchronised."""
+    for t in (y, update, gains, g):
+        _f32(t, 'tsne_update')
+        L.ptr(t)
+        if t.dim() != 2 or t.shape[1] != 2 or t.shape != y.shape or t.device != y.device:
+            raise L.JvaeHipError('tsne_update: y, update, gains and g (N, 2) fp32 on one device expected')
+    if norm is not None and (norm.dtype != torch.float64 or norm.numel() != 1 or norm.device != y.device):
+        raise L.JvaeHipError('tsne_update: norm (1,) fp64 on the device of y expected')
+    L.check(L.load().jvae_tsne_update_f32(L.ptr(y), L.ptr(update), L.ptr(gains), L.ptr(g), float(momentum), float(lr), y.shape[0],
+                                          L.ptr(norm), L.stream_ptr()), 'jvae_tsne_update_f32')
+    return y
+
+
+def pca_moments(x):
+    """x (N, K) fp32 -> (mean (K,) fp64, cov (K, K) fp64): the column means and the centred covariance / (N - 1), summed in fp64
+    over slabs of rows folded in a fixed order.  N >= 2, K <= EMBED_MAX_K.  Four launches, nothing synchronised."""
+    x = _embed_rows(x, 'pca_moments')
+    N, K = x.shape
+    lib = L.load()
+    mean = torch.empty(K, dtype=torch.float64, device=x.device)
+    cov = torch.empty((K, K), dtype=torch.float64, device=x.device)
+    if N < 2:
+        raise L.JvaeHipError('pca_moments: at least two rows expected')
+    ws, nbytes = _embed_ws(lib.jvae_pca_moments_workspace_bytes(N, K), x.device, 'pca_moments')
+    L.check(lib.jvae_pca_moments_f32(L.ptr(x), L.ptr(mean), L.ptr(cov), N, K, ws, nbytes, L.stream_ptr()), 'jvae_pca_moments_f32')
+    return mean, cov
+
+
+def project(x, mean, V):
+    """fp32((x - mean) V^T): x (N, K) fp32, mean (K,) fp64, V (n_components, K) fp64 -> (N, n_components) fp32, accumulated in
+    fp64 with k ascending.  n_components <= EMBED_MAX_COMPONENTS.  One launch, nothing synchronised."""
+    x = _embed_rows(x, 'project')
+    N, K = x.shape
+    L.ptr(mean), L.ptr(V)
+    if mean.dtype != torch.float64 or V.dtype != torch.float64 or tuple(mean.shape) != (K,) or V.dim() != 2 or V.shape[1] != K \
+            or V.shape[0] < 1 or mean.device != x.device or V.device != x.device:
+        raise L.JvaeHipError('project: mean (K,) and V (n_components, K) fp64 on the device of x expected')
+    out = torch.empty((N, V.shape[0]), dtype=torch.float32, device=x.device)
+    if N:
+        L.check(L.load().jvae_project_f32(L.ptr(x), L.ptr(_c(mean)), L.ptr(_c(V)), L.ptr(out), N, K, V.shape[0], L.stream_ptr()),
+                'jvae_project_f32')
+    return out
+
+
 def misclass_split(scores, mask):
     """(M, N) fp32 score rows and an (N,) mask (non-zero / True = correctly classified) -> ins (M, n_correct), outs
     (M, N - n_correct), n_correct: both row sets compacted in their original order by ONE scan of the mask (two views of one

@@ -611,6 +611,30 @@ int jvae_roc_curve_f32(const float* ins, const float* outs, const double* kept_t
                        double* auc, double* kept_fpr, double* kept_tpr_out, double* thr_low, double* thr_up, int* status,
                        int M, long n_in, long n_out, int K, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Precision-recall figures of OOD scores: AUPR-in / -out, AUCPR, detection error (csrc/prc.hip) ------------------
+ * The companions of the ROC in the tables of the OOD literature, for M score rows in one call.  ins (M, n_in), outs
+ * (M, n_out): fp32 scores, higher = more in-distribution; modes: M int32 mode words on the device, those of
+ * jvae_roc_curve_f32.  figures (M, 5) fp64, defined by scikit-learn's functions on the scores widened exactly to fp64:
+ *   0  aupr_in    average_precision_score, in = positive: sum dR * P over the distinct in-scores v, with
+ *                 tp = #{ins >= v}, fp = #{outs >= v}, tp' = #{ins > v}, fp' = #{outs > v}, dR = (tp - tp') / n_in,
+ *                 P = tp / (tp + fp), P' = tp' / (tp' + fp') (1 when tp' + fp' = 0)
+ *   1  aupr_out   the same with out = positive and the score negated: the sweep over the distinct out-scores with the rows
+ *                 swapped and <= / <
+ *   2  aucpr_in   auc(recall, precision) of precision_recall_curve, the trapezoid: sum dR * (P + P') / 2
+ *   3  aucpr_out  its out-side twin
+ *   4  dete       the smallest detection error: min(0.5, min_v 0.5 * (n_in - tp) / n_in + 0.5 * fp / n_out)
+ * Mode 0: scores equal under IEEE comparison are one tie group (-0 = +0); infinities are ordinary values.  Mode 1: the score
+ * of a sample is -|s - c| in fp64, c the fp64 mean of the row's in-scores exactly as jvae_roc_curve_f32 forms it.  Mode 2
+ * (quantile rows) has no scalar score: five NaNs, status 0.  A malformed word: status bit 2, computed as a mode-0 row.
+ * status (M int32, cleared by the call): the bits of jvae_roc_curve_f32 (0 = NaN score, 1 = non-finite in-score of an
+ * around-mean row, 2 = malformed mode word); the figures of such a row are meaningless (never out of bounds).
+ * Sums in fp64 in a fixed order, no float atomics: the same bits run to run, and a row's figures do not depend on the other
+ * rows of the call.  Neither copies to the host nor synchronises.
+ * n_in, n_out in [1, 2^24]; M <= 65535; ws 8-byte aligned, jvae_pr_workspace_bytes(...) bytes (0 = sizes out of range). */
+size_t jvae_pr_workspace_bytes(int M, long n_in, long n_out);
+int jvae_pr_metrics_f32(const float* ins, const float* outs, const int* modes, double* figures, int* status,
+                        int M, long n_in, long n_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- SCOD: selective classification with OOD data, score rows and risk curves (csrc/scod.hip) ----------------------
  * Replaces tests/scod.py of the reference (scoring_r, scoring_g, scoring, scrisk and the figures of its command-line block).
  * Scores: M <= 32 variants of ONE recorded set of N samples in one launch, row m of out (row stride out_stride >= N) =

@@ -22,7 +22,7 @@
 // Rows are padded to a power of two (>= one tile) with the largest key, which sorts behind every real score.
 #include "common.h"
 #include "jvae_internal.h"
-#include "roc_sort.h"                  // ROC_TILE, roc_pad, roc_key / roc_unkey, the bitonic passes, roc_sort_rows, ROC_MAX_N
+#include "roc_sort.h"                  // ROC_TILE, roc_pad, roc_key / roc_unkey, the bitonic passes, roc_sort_rows, roc_mean_kernel, ROC_MAX_N
 
 namespace {
 
@@ -44,15 +44,6 @@ inline RocWs roc_ws(int M, long n_in, long n_out) {
     w.V = o;      o += roc_align(sizeof(int) * M);
     w.total = o;
     return w;
-}
-
-// Mode word of a row -> 0 one-sided, 1 around-mean, 2 strided quantiles with the factors f_low = bits 8-15 and f_up = bits
-// 16-23, each in [1, 255], of the word 2 | f_low << 8 | f_up << 16; -1: the word decodes to nothing.
-__device__ __forceinline__ int roc_decode(int w, int& f_low, int& f_up) {
-    f_low = (w >> 8) & 255;
-    f_up = (w >> 16) & 255;
-    if (w == 0 || w == 1) return w;
-    return ((w & 255) == 2 && (w >> 24) == 0 && f_low >= 1 && f_up >= 1) ? 2 : -1;
 }
 
 // keys of both row sets (z = 0: ins, 1: outs) + the status word (bit 0: NaN score, bit 1: non-finite in-score of an
@@ -77,23 +68,6 @@ __global__ __launch_bounds__(256) void roc_keys_kernel(const float* __restrict__
     if (z == 0 && i == 0 && roc_decode(modes[m], f_low, f_up) < 0) bad |= 4;
     (z ? kout : kin)[(size_t)m * P + i] = key;
     if (bad) atomicOr(&status[m], bad);
-}
-
-// c = mean(ins) in fp64 (roc_curves.py:69): strided partial sums, then a fixed tree
-__global__ __launch_bounds__(1024) void roc_mean_kernel(const float* __restrict__ ins, const int* __restrict__ modes,
-                                                        double* __restrict__ c, long n) {
-    const int m = blockIdx.x, t = threadIdx.x;
-    if (modes[m] != 1) return;
-    __shared__ double red[1024];
-    double s = 0.0;
-    for (long i = t; i < n; i += 1024) s += (double)ins[(size_t)m * n + i];
-    red[t] = s;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) c[m] = red[0] / (double)n;
 }
 
 // abs(ins - center) in fp64 (roc_curves.py:70) as sortable bits: non-negative doubles order as their bit patterns

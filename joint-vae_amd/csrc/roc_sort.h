@@ -1,5 +1,6 @@
-// The padded bitonic sort of score rows shared by the ROC (roc.hip) and the SCOD risk curves (scod.hip): the order-preserving
-// integer image of fp32 scores, the row padding, and the compare-exchange passes for 32- and 64-bit keys.
+// The padded bitonic sort of score rows shared by the ROC (roc.hip), the precision-recall figures (prc.hip) and the SCOD risk
+// curves (scod.hip): the order-preserving integer image of fp32 scores, the row padding, the compare-exchange passes for 32- and
+// 64-bit keys, and what roc.hip and prc.hip both need of a row's mode: its decoded mode word and the centre of an around-mean row.
 //
 // Rows are padded to a power of two (>= one tile) with the largest key, which sorts behind every real key.  Strides below the
 // 2048-key tile run in LDS, longer ones in HBM.  Everything lives in an unnamed namespace: each translation unit that includes
@@ -27,6 +28,33 @@ __device__ __forceinline__ uint32_t roc_key(float v) {
 }
 __device__ __forceinline__ float roc_unkey(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+// Mode word of a row -> 0 one-sided, 1 around-mean, 2 strided quantiles with the factors f_low = bits 8-15 and f_up = bits
+// 16-23, each in [1, 255], of the word 2 | f_low << 8 | f_up << 16; -1: the word decodes to nothing.
+__device__ __forceinline__ int roc_decode(int w, int& f_low, int& f_up) {
+    f_low = (w >> 8) & 255;
+    f_up = (w >> 16) & 255;
+    if (w == 0 || w == 1) return w;
+    return ((w & 255) == 2 && (w >> 24) == 0 && f_low >= 1 && f_up >= 1) ? 2 : -1;
+}
+
+// c = mean(ins) in fp64 of the around-mean rows (roc_curves.py:69): strided partial sums, then a fixed tree.  Shared by the ROC
+// and the precision-recall figures (prc.hip), whose around-mean scores are distances to the same centre, bit for bit.
+__global__ __launch_bounds__(1024) void roc_mean_kernel(const float* __restrict__ ins, const int* __restrict__ modes,
+                                                        double* __restrict__ c, long n) {
+    const int m = blockIdx.x, t = threadIdx.x;
+    if (modes[m] != 1) return;
+    __shared__ double red[1024];
+    double s = 0.0;
+    for (long i = t; i < n; i += 1024) s += (double)ins[(size_t)m * n + i];
+    red[t] = s;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) c[m] = red[0] / (double)n;
 }
 
 // Compare-exchange passes of the bitonic network that fit one tile.  k == 0: the whole local sort (k = 2 ... ROC_TILE);

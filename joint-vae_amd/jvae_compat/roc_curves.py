@@ -4,6 +4,9 @@
 precision in which the model produces its scores) and returns numpy values of the same shapes.  What the reference computes
 through a SciPy spline (`two_sided=(a, b)`), a validation split or reversed scores raises there; `roc_curve_quantile` is the
 tuple mode on the spline's noise-free values, under a name of its own because its numbers are not the reference's.
+
+Public names: `fpr_at_tpr`, `tpr_at_fpr`, `roc_curve`, `roc_curve_quantile` and `pr_metrics` - the precision-recall side the
+reference's scripts take from scikit-learn (AUPR-in / -out, AUCPR, detection error), computed by jvae_hip.ops.pr_metrics.
 """
 import numpy as np
 import torch
@@ -48,10 +51,28 @@ def roc_curve_quantile(ins, outs, *kept_tpr, factors=(1, 1), device=None):
     return _one_row(ins, outs, kept_tpr, ('quantile',) + tuple(factors), device)
 
 
-def _one_row(ins, outs, kept_tpr, mode, device):
+def pr_metrics(ins, outs, two_sided=False, device=None):
+    """-> {'aupr_in', 'aupr_out', 'aucpr_in', 'aucpr_out', 'dete'} as plain floats: scikit-learn's average_precision_score and
+    auc(recall, precision) with in, resp. out and the negated score, as the positive class, and the smallest detection error
+    0.5 (1 - tpr) + 0.5 fpr over all thresholds (jvae_hip.ops.pr_metrics, csrc/prc.hip).  two_sided: False or
+    'around-mean' (the score of a sample is then -|s - mean(ins)|).  ValueError on a NaN score, as for `roc_curve`."""
+    if isinstance(two_sided, tuple):
+        raise NotImplementedError('pr_metrics: quantile thresholds (two_sided=(a, b)) give no scalar score')
+    rows = _rows(ins, outs, device)
+    r = ops.pr_metrics(rows[0], rows[1], 'around-mean' if two_sided == 'around-mean' else False)
+    host = torch.cat([torch.stack([r[k] for k in ops.PR_FIGURES]), r['status'].double()[None]]).cpu().tolist()
+    ops.roc_check_status([int(host[-1])])
+    return dict(zip(ops.PR_FIGURES, host[:-1]))
+
+
+def _rows(ins, outs, device):
     device = device or ('cuda' if torch.cuda.is_available() else 'cpu')      # off the GPU the op raises JvaeHipError
-    rows = [torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(device=device, dtype=torch.float32).reshape(-1)
+    return [torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v).to(device=device, dtype=torch.float32).reshape(-1)
             for v in (ins, outs)]
+
+
+def _one_row(ins, outs, kept_tpr, mode, device):
+    rows = _rows(ins, outs, device)
     r = ops.roc_curve(rows[0], rows[1], sorted(kept_tpr), mode)
     ops.roc_check_status([int(r['status'].cpu())])
     host = {k: r[k].cpu().numpy() for k in ('auc', 'fpr', 'tpr', 'low', 'up')}

@@ -151,6 +151,8 @@ _SIGS = {
     'jvae_upsample_nearest_bwd_b8': (c_int, [P, P, c_long, c_int, c_int, c_int, P]),
     'jvae_roc_workspace_bytes': (c_size_t, [c_int, c_long, c_long]),
     'jvae_roc_curve_f32': (c_int, [P] * 10 + [c_int, c_long, c_long, c_int, P, c_size_t, P]),
+    'jvae_pr_workspace_bytes': (c_size_t, [c_int, c_long, c_long]),
+    'jvae_pr_metrics_f32': (c_int, [P] * 5 + [c_int, c_long, c_long, P, c_size_t, P]),
     'jvae_scod_scores_f32': (c_int, [P] * 8 + [c_long, c_int, c_int, c_long, P, P]),
     'jvae_scod_workspace_bytes': (c_size_t, [c_int, c_long]),
     'jvae_scod_curve_f32': (c_int, [P] * 6 + [c_int, c_long, c_long, P, c_size_t, P]),

@@ -1415,14 +1415,7 @@ def roc_curve(ins, outs, kept_tpr, two_sided=False):
         kept = _c(kept_tpr.to(device=dev, dtype=torch.float64))
     else:
         kept = torch.tensor(sorted(float(t) for t in kept_tpr), dtype=torch.float64, device=dev)
-    if torch.is_tensor(two_sided):
-        modes = _c(two_sided.to(device=dev, dtype=torch.int32))
-    else:
-        for_all = not isinstance(two_sided, (list, tuple)) or two_sided[:1] == ('quantile',)
-        rows = [two_sided] * M if for_all else list(two_sided)
-        modes = torch.tensor([roc_mode_word(t) for t in rows], dtype=torch.int32, device=dev)
-    if modes.numel() != M:
-        raise L.JvaeHipError(f'roc_curve: {modes.numel()} modes for {M} rows')
+    modes = _roc_modes(two_sided, M, dev, 'roc_curve')
     K = kept.numel()
     out = torch.empty((4, M, max(K, 1)), dtype=torch.float64, device=dev)
     auc = torch.empty(M, dtype=torch.float64, device=dev)
@@ -1439,6 +1432,19 @@ def roc_curve(ins, outs, kept_tpr, two_sided=False):
     return {k: v[0] for k, v in res.items()} if single else res
 
 
+def _roc_modes(two_sided, M, dev, what):
+    """The `two_sided` argument of `roc_curve` / `pr_metrics` -> (M,) int32 mode words on the device."""
+    if torch.is_tensor(two_sided):
+        modes = _c(two_sided.to(device=dev, dtype=torch.int32))
+    else:
+        for_all = not isinstance(two_sided, (list, tuple)) or two_sided[:1] == ('quantile',)
+        rows = [two_sided] * M if for_all else list(two_sided)
+        modes = torch.tensor([roc_mode_word(t) for t in rows], dtype=torch.int32, device=dev)
+    if modes.numel() != M:
+        raise L.JvaeHipError(f'{what}: {modes.numel()} modes for {M} rows')
+    return modes
+
+
 def roc_mode_word(t):
     """One row's `two_sided` value -> its int32 mode word (include/jvae_hip.h): 0 one-sided, 1 'around-mean',
     2 | f_low << 8 | f_up << 16 for ('quantile', f_low, f_up)."""
@@ -1449,6 +1455,39 @@ def roc_mode_word(t):
     if isinstance(t, tuple) or t not in (False, True, 0, 1, None, 'around-mean'):
         raise NotImplementedError(f'roc_curve: two_sided={t!r} (the spline thresholds of the reference are not built)')
     return 1 if t == 'around-mean' else 0
+
+
+PR_FIGURES = ('aupr_in', 'aupr_out', 'aucpr_in', 'aucpr_out', 'dete')
+
+
+def pr_metrics(ins, outs, two_sided=False):
+    """The precision-recall side of M score rows in one call (csrc/prc.hip): AUPR-in and AUPR-out (scikit-learn's
+    average_precision_score with in, resp. out and the negated score, as the positive class), the trapezoid AUCPR of both
+    (auc(recall, precision) of precision_recall_curve) and the smallest detection error over all thresholds,
+    min 0.5 (1 - tpr) + 0.5 fpr.  ins, outs and two_sided as for `roc_curve`; with 'around-mean' the score of a sample is
+    -|s - mean(ins)|; a ('quantile', f_low, f_up) row has no scalar score and gets NaN figures.
+    -> dict of DEVICE tensors: the five PR_FIGURES (M,) fp64 and 'status' (M,) int32 with the bits of `roc_curve`
+    (`roc_check_status` reads it).  (n,) inputs drop the M axis.  Nothing is synchronised or copied to the host."""
+    lib = L.load()
+    single = ins.dim() == 1
+    ins, outs = _c(_f32(ins, 'pr_metrics')), _c(_f32(outs, 'pr_metrics'))
+    L.ptr(ins), L.ptr(outs)                                    # off the GPU: JvaeHipError, before anything else is looked at
+    if single:
+        ins, outs = ins[None], outs[None]
+    if ins.dim() != 2 or outs.dim() != 2 or ins.shape[0] != outs.shape[0] or ins.shape[1] < 1 or outs.shape[1] < 1:
+        raise L.JvaeHipError(f'pr_metrics: (M, n_in) and (M, n_out) score rows expected, got {tuple(ins.shape)} and {tuple(outs.shape)}')
+    M, n_in, n_out, dev = ins.shape[0], ins.shape[1], outs.shape[1], ins.device
+    modes = _roc_modes(two_sided, M, dev, 'pr_metrics')
+    figures =torch.empty((M, len(PR_FIGURES)), dtype=torch.float64, device=dev)
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    nbytes = lib.jvae_pr_workspace_bytes(M, n_in, n_out)
+    if not nbytes:
+        raise L.JvaeHipError(f'pr_metrics: sizes out of range (M={M}, n_in={n_in}, n_out={n_out})')
+    ws = L.workspace(nbytes, dev)
+    L.check(lib.jvae_pr_metrics_f32(L.ptr(ins), L.ptr(outs), L.ptr(modes), L.ptr(figures), L.ptr(status), M, n_in, n_out,
+                                    L.ptr(ws), ws.numel(), L.stream_ptr()), 'jvae_pr_metrics_f32')
+    res = dict({k: figures[:, j] for j, k in enumerate(PR_FIGURES)}, status=status)
+    return {k: v[0] for k, v in res.items()} if single else res
 
 
 def roc_check_status(status):
@@ -2320,10 +2359,12 @@ def misclass_confusion(scores, mask, thr):
     return counts[0], counts[1]
 
 
-def misclass_rates(scores, correct_mask, kept_tpr):
+def misclass_rates(scores, correct_mask, kept_tpr, pr=False):
     """The device side of misclassification_detection_rates for M score rows of one prediction method: ONE split, ONE ROC
     (correct = in, missed = out, one-sided) and ONE confusion call.  -> dict of DEVICE tensors 'auc' (M,), 'fpr' / 'tpr' / 'low' /
     'up' (M, K) fp64, 'tp' / 'fp' (M, K) int32, 'status' (M,) int32 as `roc_curve` returns it, and 'n_correct' (Python int).
+    With `pr`, also 'pr' (M, 5) fp64: the PR_FIGURES of ONE `pr_metrics` call on the same two row sets (correct = positive, then
+    missed = positive with the score negated).
     ValueError when every sample - or none - is correct: there is no ROC of an empty set."""
     single = scores.dim() == 1
     scores = scores[None] if single else scores
@@ -2332,7 +2373,10 @@ def misclass_rates(scores, correct_mask, kept_tpr):
         raise ValueError(f'misclass_rates: {nc} of {scores.shape[1]} samples are correct, no ROC of an empty set')
     res = roc_curve(ins, outs, kept_tpr, False)
     res['tp'], res['fp'] = misclass_confusion(scores, correct_mask, res['low'])
-    res = {k: v[0] for k, v in res.items()} if single else res
+    if pr:
+        figures = pr_metrics(ins, outs, False)
+        res['pr'] = torch.stack([figures[k] for k in PR_FIGURES], 1)
+    res ={k: v[0] for k, v in res.items()} if single else res
     res['n_correct'] = nc
     return res
 

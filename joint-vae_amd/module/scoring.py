@@ -170,6 +170,13 @@ class ScoringMixin:
     # ('quantile', x, y)).  Off by default: the reference reads these thresholds off a spline whose rounding noise decides
     # its kept rates, so the numbers here are close to the reference's, not equal to them.
     OOD_QUANTILE_METHODS = False
+    # The precision-recall side of the detection rates (ops.pr_metrics, csrc/prc.hip).  Off by default:
+    # every dictionary and file is the reference's.  On: ood_detection_rates() adds 'aupr_in', 'aupr_out', 'aucpr_in',
+    # 'aucpr_out' and 'dete' to every per-method dictionary of an OOD set (not to the '-a-x-y' methods, which have no scalar
+    # score) and misclassification_detection_rates() adds 'aupr_correct', 'aupr_error', 'aucpr_correct', 'aucpr_error' and
+    # 'dete' to every entry.  Whether the reference's loaders accept the extra keys in ood.json / test.json is not claimed.
+    DETECTION_PR_METRICS = False
+    MISCLASS_PR_KEYS = ('aupr_correct', 'aupr_error', 'aucpr_correct', 'aucpr_error', 'dete')
 
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
@@ -336,7 +343,11 @@ class ScoringMixin:
         nearest class `y_nearest` of every evaluated batch appended (the keys the recorder holds; `_score_set`) and
         `samples-<set>.pth` written into every `sample_dirs` entry.  The OOD sets get `y` and `y_nearest` as well when their
         recorder holds them - the reference leaves zeros there (cvae.py:1793-1795 appends `mu` alone) and its ft/inspection.py
-        recomputes `y_nearest` from `mu`.  Empty or None: nothing changes, the same launches and the same results."""
+        recomputes `y_nearest` from `mu`.  Empty or None: nothing changes, the same launches and the same results.
+
+        With `DETECTION_PR_METRICS` every per-method dictionary of an OOD set also holds 'aupr_in', 'aupr_out', 'aucpr_in',
+        'aucpr_out' and 'dete' (ONE `ops.pr_metrics` call beside each ROC, its figures in the ROC's host copy); the '-a-x-y'
+        methods gain nothing."""
         if testset is None or isinstance(testset, str) or oodsets is None or any(isinstance(o, str) for o in oodsets):
             if self.DATA_ROOT is None:
                 raise NotImplementedError('named torchvision datasets are outside this build: pass torch.utils.data.Datasets')
@@ -395,13 +406,18 @@ class ScoringMixin:
 
         kept = torch.tensor(self.OOD_KEPT_TPR, dtype=torch.float64, device=ind.device)
         K = len(self.OOD_KEPT_TPR)
+        with_pr = bool(self.DETECTION_PR_METRICS)
         for oodset, name in zip(oodsets, names[1:]):
             last = {}
 
             def roc(scores):
                 """ONE device ROC for all methods, ONE copy of its (M, 4K + 4) results to the host."""
                 r = ops.roc_curve(ind, scores.contiguous(), kept, modes)
-                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['status'].double()[:, None],
+                # with DETECTION_PR_METRICS: ONE ops.pr_metrics call, its (M, 5) figures in the same copy (the status word of
+                # the ROC above flags the same rows)
+                pr = [torch.stack([p[k] for k in ops.PR_FIGURES], 1) for p in
+                      ([ops.pr_metrics(ind, scores.contiguous(), modes)] if with_pr else [])]
+                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['status'].double()[:, None], *pr,
                                   self._row_mean_std(scores)], 1).cpu().numpy()
                 ops.roc_check_status(host[:, 1 + 4 * K].astype(np.int64))
                 last['host'] = host
@@ -420,6 +436,8 @@ class ScoringMixin:
                 ood_results[name][m] = {'epochs': epoch, 'n': scores.shape[1], 'mean': float(h[-2]), 'std': float(h[-1]),
                                         'auc': float(h[0]), 'tpr': list(self.OOD_KEPT_TPR), 'fpr': [float(f) for f in fpr],
                                         'thresholds': [[float(a), float(b)] for a, b in zip(low, up)]}
+                if with_pr and '-a-' not in m:                # a quantile row has no scalar score: no figures
+                    ood_results[name][m].update(zip(ops.PR_FIGURES, (float(f) for f in h[2 + 4 * K:7 + 4 * K])))
                 if update_self_ood:
                     self.ood_results.setdefault(epoch, {}).setdefault(name, {})[m] = ood_results[name][m]
         if was_training:
@@ -470,7 +488,11 @@ class ScoringMixin:
         naming it.  The reference's "n already there" guard reads `self.testing[epoch][predict_methods][m]` - the ARGUMENT, a
         list or 'all', so it never finds anything (cvae.py:2064); here it looks under the prediction method being processed.
         The P / R / FPR at `shown_tpr` are logged at debug level (and sent to `outputs` with `print_result`); NaN when no kept slot
-        reaches `shown_tpr`.  Nothing stored depends on them."""
+        reaches `shown_tpr`.  Nothing stored depends on them.
+
+        With `DETECTION_PR_METRICS` every entry also holds `MISCLASS_PR_KEYS`: 'aupr_correct' / 'aucpr_correct' (correct =
+        positive), 'aupr_error' / 'aucpr_error' (missed = positive, score negated) and 'dete', from ONE `ops.pr_metrics` call on
+        the two row sets of the split, in the same host copy."""
         def nothing(why):
             logging.debug('misclassification_detection_rates: nothing to do (%s)', why)
 
@@ -518,6 +540,7 @@ class ScoringMixin:
         if skipped:
             logging.debug('misclassification_detection_rates: not in the recorder: %s', ', '.join(skipped))
         sampling = self._latent_samplings['eval']
+        with_pr = bool(self.DETECTION_PR_METRICS)
         results = {}
         if not methods:
             return results
@@ -532,14 +555,14 @@ class ScoringMixin:
             for pm in chosen['predict']:
                 correct = self.predict_after_evaluate(logits, tensors, method=pm) == y
                 try:
-                    r = ops.misclass_rates(scores, correct, kept)
+                    r = ops.misclass_rates(scores, correct, kept, pr=True) if with_pr else ops.misclass_rates(scores, correct, kept)
                 except ValueError as err:
                     logging.warning('misclassification_detection_rates: prediction method %s skipped: %s', pm, err)
                     continue
                 n_correct = r['n_correct']
                 acc = n_correct / n
                 host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['tp'].double(), r['fp'].double(),
-                                  r['status'].double()[:, None]], 1).cpu().numpy()
+                                  *([r['pr']] if with_pr else []), r['status'].double()[:, None]], 1).cpu().numpy()
                 logging.debug('Acc. for method %s: (%5.2f) ****', pm, 100 * acc)
                 results[pm] = {}
                 best = (None, 0.)
@@ -563,6 +586,8 @@ class ScoringMixin:
                         sink.write(line + '\n')
                     entry = {'n': n, 'epochs': epoch, 'sampling': sampling, 'tpr': [float(t) for t in tpr],
                              'fpr': [float(f) for f in fpr], 'auc': float(h[0]), 'precision': [float(p) for p in precision]}
+                    if with_pr:
+                        entry.update(zip(self.MISCLASS_PR_KEYS, (float(f) for f in h[1 + 6 * K:6 + 6 * K])))
                     results[pm][m] = entry
                     n_already = self.testing.get(epoch, {}).get(pm, {}).get(m, {'n': 0})['n']
                     if update_self_results and n >= n_already:

@@ -401,6 +401,27 @@ int jvae_latent_mixed_bwd_f32(const float* mu, const float* lv_raw, const float*
                               int C_a, int prior_a, int var_dim_a, float tau_a, float alpha_a,
                               int C_b, int prior_b, int var_dim_b, float tau_b, float alpha_b,
                               float w, int sampled, int has_forced, void* ws, size_t ws_bytes, void* stream);
+/* One iteration of the posterior refinement behind the likelihood regret (Xiao, Yan, Amit 2020) in ONE launch, one wavefront
+ * per sample, with the per-sample bodies of the latent kernels.  For sample n with class y[n], in this order:
+ *   1. gradient of J_n = mean_l(-log p(x_n | z_ln)) + KL(q_n || p(z | y_n)) with respect to (mu_n, lv_raw_n): `dz` (L+1,N,K)
+ *      is d(sum_n mean_l -log p)/dz at z = mu + exp(lv/2) eps_cur (row 0, the mean path, normally carries zeros), the KL part
+ *      is analytic with KL weight 1 and warm-up weight 1; the +-20 clip gates the log-variance gradient as in training;
+ *   2. torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, bias-corrected, no weight decay, no clipping) on mu_n and lv_raw_n IN
+ *      PLACE with the state m_mu, v_mu, m_lv, v_lv (N,K each), step number `step` >= 1 and learning rate `lr`; with a forced
+ *      variance only mu moves (lv_raw, m_lv, v_lv may be NULL);
+ *   3. the latent forward at the moved posterior with eps_next (L+1,N,K): lv (clipped, N,K), z_next (L+1,N,K), kl, zdist,
+ *      var_kl (N,).
+ * `lv` is in/out: the clipped log-variance of the posterior on entry (step 3 of the previous call), of the moved one on exit.
+ * flags: 1 skips 1 and 2 (the first draw of a loop: eps_cur, dz and the state may be NULL); 2 skips 3 (a last update: eps_next
+ * and the outputs of 3 may be NULL); 3 is refused.  All priors of the latent kernel.  No atomics, no workspace; LDS only for
+ * the full-variance prior (8 K floats per workgroup, -2 beyond 64 KiB); same inputs, same bits.  A label outside [0, C) is
+ * never an index: that sample does not move and its outputs of step 3 are NaN. */
+int jvae_latent_refine_f32(float* mu, float* lv_raw, float* lv, const float* eps_cur, const float* eps_next,
+                           const long long* y, const float* means, const float* T, const float* dz,
+                           float* m_mu, float* v_mu, float* m_lv, float* v_lv,
+                           float* z_next, float* kl, float* zdist, float* var_kl,
+                           int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha,
+                           int sampled, int has_forced, float forced_lv, float lr, long step, int flags, void* stream);
 
 /* ---- reconstruction term ---------------------------------------------------------------------------
  * wmse[l][n] = mean_D((x_reco[l+1][n] - x[n])^2) / sigma^2   (mse_loss, module/losses.py:8-27, called at

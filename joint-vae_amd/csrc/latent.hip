@@ -194,22 +194,32 @@ __global__ __launch_bounds__(256) void latent_mixed_fwd_kernel(LatentP a, PriorB
 // `valid` false: the wave shadows sample n (it only takes the barriers) and stores nothing.  `uni_first` (uniform prior):
 // which branch of the forward's max() was taken.  `block_full`: some wave of the workgroup has a full-variance prior, so
 // EVERY wave of it takes the two barriers of the LDS staging (block-uniform; the single-prior kernel passes `full` itself).
+//
+// Where the two gradients of element (n, k) go is the caller's `sink(row + k, g_mu, g_lv_raw)`, called once per element by
+// the lane that owns it, after that lane's last read of mu / lv of the element: StoreGrad writes them out (the backward
+// kernels); the refinement kernel applies its optimiser step to the element in place instead.  gk, gd_in, gv_in: the
+// upstream gradients of the sample's kl, zdist and var_kl.
+struct StoreGrad {
+    float* __restrict__ gmu;
+    float* __restrict__ glv_raw;
+    __device__ __forceinline__ void operator()(const long i, const float g_mu, const float g_lv) const {
+        gmu[i] = g_mu;
+        glv_raw[i] = g_lv;
+    }
+};
+
+template <class Sink>
 __device__ __forceinline__ void latent_bwd_sample(const LatentP& p, const int n, const bool valid, const long long cls,
                                                   const int lane, const int wv, const bool block_full, const bool uni_first,
-                                                  float* lds_dw, const float* __restrict__ lv,
-                                                  const float* __restrict__ gz, const float* __restrict__ g_kl,
-                                                  const float* __restrict__ g_zdist, const float* __restrict__ g_vkl,
-                                                  const float* __restrict__ gmu_direct,
-                                                  const float* __restrict__ glv_direct,
-                                                  float* __restrict__ gmu, float* __restrict__ glv_raw,
+                                                  float* lds_dw, const float* lv,
+                                                  const float* __restrict__ gz, const float gk, const float gd_in,
+                                                  const float gv_in, const float* __restrict__ gmu_direct,
+                                                  const float* __restrict__ glv_direct, const Sink& sink,
                                                   float* gd_scratch, float* gt_scratch, float* gpair) {
     const int K = p.K;
     const float w = p.w_dev ? p.w_dev[0] : p.w;
     const float* m = p.means + (long)cls * K;
     const long row = (long)n * K;
-    const float gk = g_kl ? g_kl[n] : 0.f;
-    const float gd_in = g_zdist ? g_zdist[n] : 0.f;
-    const float gv_in = g_vkl ? g_vkl[n] : 0.f;
 
     // gradient reaching `distance` and `var_kl` (gaussian) ...
     float g_dist = gd_in, g_var = gv_in;
@@ -302,10 +312,9 @@ __device__ __forceinline__ void latent_bwd_sample(const LatentP& p, const int n,
         }
         g_mu += g_d;
         if (gd_scratch) gd_scratch[row + k] = -g_d;          // summed per class in sample order by means_grad_kernel
-        gmu[row + k] = g_mu;
         const float raw = p.lv_raw ? p.lv_raw[row + k] : 0.f;
         const bool pass = p.has_forced ? false : (raw >= -20.f && raw <= 20.f);
-        glv_raw[row + k] = pass ? g_lv : 0.f;
+        sink(row + k, g_mu, pass ? g_lv : 0.f);
     }
 }
 
@@ -325,8 +334,9 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentP p, const float*
     const int n = valid ? n_raw : p.N - 1;     // out-of-range waves shadow the last sample and store nothing
     const bool uni_first = p.prior == PRIOR_UNIFORM ? kl_fwd_terms[2 * n] >= kl_fwd_terms[2 * n + 1] : true;
     const bool full = p.prior != PRIOR_UNIFORM && p.var_dim == VAR_FULL;
-    latent_bwd_sample(p, n, valid, p.y[n], lane, wv, full, uni_first, lds_dw, lv, gz, g_kl, g_zdist, g_vkl, gmu_direct,
-                      glv_direct, gmu, glv_raw, gd_scratch, gt_scratch, gpair);
+    latent_bwd_sample(p, n, valid, p.y[n], lane, wv, full, uni_first, lds_dw, lv, gz, g_kl ? g_kl[n] : 0.f,
+                      g_zdist ? g_zdist[n] : 0.f, g_vkl ? g_vkl[n] : 0.f, gmu_direct, glv_direct, StoreGrad{gmu, glv_raw},
+                      gd_scratch, gt_scratch, gpair);
 }
 
 // Full variance: gT[c][i][k] += sum over the samples n of class c, IN SAMPLE ORDER, of
@@ -471,10 +481,88 @@ __global__ __launch_bounds__(256) void latent_mixed_bwd_kernel(LatentP a, PriorB
         uniform_terms_sample(p, n, cls, lane, lv, first, second);
         uni_first = first >= second;
     }
-    latent_bwd_sample(p, n, in_range && good, cls, lane, wv, block_full != 0, uni_first, lds_dw, lv, gz, g_kl, g_zdist, g_vkl,
-                      gmu_direct, glv_direct, gmu, glv_raw, nullptr, nullptr, nullptr);
+    latent_bwd_sample(p, n, in_range && good, cls, lane, wv, block_full != 0, uni_first, lds_dw, lv, gz,
+                      g_kl ? g_kl[n] : 0.f, g_zdist ? g_zdist[n] : 0.f, g_vkl ? g_vkl[n] : 0.f, gmu_direct, glv_direct,
+                      StoreGrad{gmu, glv_raw}, nullptr, nullptr, nullptr);
     if (in_range && !good)
         for (int k = lane; k < p.K; k += 64) { gmu[(long)n * p.K + k] = NAN; glv_raw[(long)n * p.K + k] = NAN; }
+}
+
+// ---- posterior refinement (likelihood regret): gradient -> Adam -> forward of the next iteration, one launch ------------
+// The per-sample optimiser of the refinement loop: torch.optim.Adam(betas = (0.9, 0.999), eps = 1e-8, no weight decay) on the
+// element (n, k) of mu and of the raw log-variance, as latent_bwd_sample's sink.  The arithmetic is adam1's of csrc/adam.hip.
+struct RefineAdam {
+    float* mu; float* lv_raw;
+    float* m_mu; float* v_mu; float* m_lv; float* v_lv;
+    float lr_over_bc1, inv_sqrt_bc2;
+    bool move_lv;                              // false with a forced variance: only mu moves
+    static __device__ __forceinline__ float step1(const float p, const float g, float& m, float& v, const float lr_over_bc1,
+                                                  const float inv_sqrt_bc2) {
+        m = 0.9f * m + 0.1f * g;               // 1 - beta rounded from the exact difference, as torch hands it over
+        v = 0.999f * v + 0.001f * g * g;
+        const float denom = sqrtf(v) * inv_sqrt_bc2 + 1e-8f;
+        return p - lr_over_bc1 * (m / denom);
+    }
+    __device__ __forceinline__ void operator()(const long i, const float g_mu, const float g_lv) const {
+        float m = m_mu[i], v = v_mu[i];
+        mu[i] = step1(mu[i], g_mu, m, v, lr_over_bc1, inv_sqrt_bc2);
+        m_mu[i] = m; v_mu[i] = v;
+        if (move_lv) {
+            m = m_lv[i]; v = v_lv[i];
+            lv_raw[i] = step1(lv_raw[i], g_lv, m, v, lr_over_bc1, inv_sqrt_bc2);
+            m_lv[i] = m; v_lv[i] = v;
+        }
+    }
+};
+
+enum { REFINE_FORWARD_ONLY = 1, REFINE_NO_FORWARD = 2 };
+
+// One wave per sample n, class y[n]:
+//   1. d J_n / d (mu_n, lv_raw_n) of J_n = mean_l(-log p(x_n | z_ln)) + KL(q_n || p(z | y_n)) by latent_bwd_sample: `dz` is the
+//      reconstruction part at z = mu + exp(lv / 2) eps_cur (p.eps), the KL part is analytic with both weights 1;
+//   2. the Adam step of RefineAdam on the sample's own elements, in place (the sink of 1: no gradient array exists);
+//   3. latent_fwd_sample at the moved posterior with eps_next: clipped log-variance, z_next, kl, zdist, var_kl.
+// `lv` holds the clipped log-variance of the posterior on entry (what 3 of the previous launch wrote) and of the moved one on
+// exit.  Every element is read and written by the lane that owns it, except in 3 with a full-variance prior, where a lane
+// reads the whole moved mean of its sample: the workgroup fence between 2 and 3 orders those reads behind the wave's stores.
+// A label outside [0, C) is never an index: the sample does not move and its outputs are NaN.
+__global__ __launch_bounds__(256) void latent_refine_kernel(LatentP p, const float* __restrict__ eps_next,
+                                                            const float* __restrict__ dz, RefineAdam adam, int flags,
+                                                            float* lv, float* __restrict__ z_next, float* __restrict__ kl,
+                                                            float* __restrict__ zdist, float* __restrict__ var_kl) {
+    extern __shared__ float lds_dw[];          // full variance only: per wave d[K] then wd[K]
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_raw = blockIdx.x * (blockDim.x >> 6) + wv;
+    const bool in_range = n_raw < p.N;
+    const int n = in_range ? n_raw : p.N - 1;  // out-of-range waves shadow the last sample: they take the barriers, store nothing
+    const long long y = p.y[n];
+    const bool good = y >= 0 && y < (long long)p.C;
+    const long long cls = good ? y : 0;
+    if (!(flags & REFINE_FORWARD_ONLY)) {
+        bool uni_first = true;
+        if (p.prior == PRIOR_UNIFORM) {
+            float first, second;
+            uniform_terms_sample(p, n, cls, lane, lv, first, second);
+            uni_first = first >= second;
+        }
+        const bool full = p.prior != PRIOR_UNIFORM && p.var_dim == VAR_FULL;
+        latent_bwd_sample(p, n, in_range && good, cls, lane, wv, full, uni_first, lds_dw, lv, dz, 1.f, 0.f, 0.f, nullptr, nullptr,
+                          adam, nullptr, nullptr, nullptr);
+        __threadfence_block();
+    }
+    if (!in_range || (flags & REFINE_NO_FORWARD)) return;
+    if (!good) {
+        for (int k = lane; k < p.K; k += 64) {
+            lv[(long)n * p.K + k] = NAN;
+            for (int l = 0; l <= p.L; ++l) z_next[((long)l * p.N + n) * p.K + k] = NAN;
+        }
+        if (lane == 0) { kl[n] = NAN; zdist[n] = NAN; var_kl[n] = NAN; }
+        return;
+    }
+    LatentP q = p;
+    q.eps = eps_next;
+    latent_fwd_sample(q, n, cls, lane, lv, z_next, kl, zdist, var_kl, nullptr);
 }
 
 bool fill(LatentP* p, const float* mu, const float* lv_raw, const float* eps, const long long* y, const float* means,
@@ -645,6 +733,41 @@ int jvae_latent_mixed_bwd_f32(const float* mu, const float* lv_raw, const float*
     if (lds > 64 * 1024) return JVAE_ENOTSUP;
     hipLaunchKernelGGL(latent_mixed_bwd_kernel, dim3(cdiv(N, 4)), dim3(256), lds, (hipStream_t)stream, a, b, split, block_full,
                        lv, gz, g_kl, g_zdist, g_vkl, gmu_direct, glv_direct, gmu, glv_raw);
+    JVAE_LAUNCH_CHECK();
+    return 0;
+}
+
+// One iteration of the posterior refinement in one launch (latent_refine_kernel).  step >= 1 is the Adam step number.
+int jvae_latent_refine_f32(float* mu, float* lv_raw, float* lv, const float* eps_cur, const float* eps_next,
+                           const long long* y, const float* means, const float* T, const float* dz,
+                           float* m_mu, float* v_mu, float* m_lv, float* v_lv,
+                           float* z_next, float* kl, float* zdist, float* var_kl,
+                           int N, int K, int L, int C, int prior, int var_dim, float tau, float alpha,
+                           int sampled, int has_forced, float forced_lv, float lr, long step, int flags, void* stream) {
+    LatentP p;
+    if (!fill(&p, mu, lv_raw, eps_cur, y, means, T, nullptr, N, K, L, C, prior, var_dim, tau, alpha, 1.f, sampled, has_forced,
+              forced_lv))
+        return JVAE_EINVAL;
+    if (flags & ~(REFINE_FORWARD_ONLY | REFINE_NO_FORWARD)) return JVAE_EINVAL;
+    const bool update = !(flags & REFINE_FORWARD_ONLY), forward = !(flags & REFINE_NO_FORWARD);
+    if (!update && !forward) return JVAE_EINVAL;
+    if (!lv) return JVAE_EINVAL;
+    if (update && (!eps_cur || !dz || !m_mu || !v_mu || step < 1 || (!has_forced && (!m_lv || !v_lv)))) return JVAE_EINVAL;
+    if (forward && (!eps_next || !z_next || !kl || !zdist || !var_kl)) return JVAE_EINVAL;
+    if (N == 0) return 0;
+    RefineAdam adam;
+    adam.mu = mu; adam.lv_raw = lv_raw; adam.m_mu = m_mu; adam.v_mu = v_mu; adam.m_lv = m_lv; adam.v_lv = v_lv;
+    adam.move_lv = !has_forced;
+    adam.lr_over_bc1 = 0.f; adam.inv_sqrt_bc2 = 0.f;
+    if (update) {
+        const double bc1 = 1.0 - pow(0.9, (double)step), bc2 = 1.0 - pow(0.999, (double)step);
+        adam.lr_over_bc1 = (float)((double)lr / bc1);
+        adam.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    const size_t lds = (update && prior != PRIOR_UNIFORM && var_dim == VAR_FULL) ? sizeof(float) * 4 * 2 * (size_t)K : 0;
+    if (lds > 64 * 1024) return JVAE_ENOTSUP;
+    hipLaunchKernelGGL(latent_refine_kernel, dim3(cdiv(N, 4)), dim3(256), lds, (hipStream_t)stream, p, eps_next, dz, adam, flags,
+                       lv, z_next, kl, zdist, var_kl);
     JVAE_LAUNCH_CHECK();
     return 0;
 }

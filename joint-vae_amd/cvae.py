@@ -42,7 +42,7 @@ from module.optimizers import Optimizer
 from module.losses import x_loss, mse_loss, categorical_loss  # noqa: F401  (import surface of the reference)
 from module.vae_layers import Encoder, Classifier, Sigma, build_de_conv_layers, find_input_shape
 from module.vae_layers import onehot_encoding, activation_layers
-from module.vae_layers.layers import HipLinear, HipDropout, DenseStack
+from module.vae_layers.layers import HipLinear, HipDropout, DenseStack, draw_epsilon
 
 DEFAULT_ACTIVATION = 'relu'
 DEFAULT_OUTPUT_ACTIVATION = 'linear'
@@ -1010,6 +1010,138 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             if was_training:
                 self.train()
         return dict(zip(self._odin_names(), scores))
+
+    # ------------------------------------------------------------------------------------ likelihood regret
+    def _regret_objective(self, z, kl, x, s, s_kind, want_grad):
+        """J (N,) = cross_x + kl, the `total` of evaluate(..., with_beta=False), at the draws z (L+1, N, K) of a posterior whose
+        KL terms are `kl`, and with `want_grad` the decoder's part of its gradient, d(sum_n cross_x_n)/dz (L+1, N, K): rows are
+        independent in eval mode, so that is each sample's own.  Samples go through the decoder in slabs of `_eval_slab_rows()`
+        rows ((L+1) rows per sample); nothing asks for a weight gradient (the caller froze the parameters)."""
+        Lp1, N, K = z.shape
+        D = int(np.prod(self.input_shape))
+        per = max(self._eval_slab_rows() // Lp1, 1)
+        J = dz = None
+        for n0 in range(0, N, per):
+            n1 = min(N, n0 + per)
+            whole = n0 == 0 and n1 == N
+            zs = z if whole else z[:, n0:n1].contiguous()
+            sig = s[n0:n1] if s_kind == ops.SIGMA_CODED else s
+            with torch.enable_grad() if want_grad else torch.no_grad():
+                if want_grad:
+                    zs = zs.detach().requires_grad_(True)
+                x_reco = self._decode_rows(zs).view(Lp1, n1 - n0, *self._reco_shape())
+                wmse_s = ops.recon_wmse(x_reco, x[n0:n1], sig, s_kind)
+                _, cross_x, total = ops.elbo(wmse_s, kl[n0:n1], None, sig, s_kind, D, 1., 0.)
+                g = torch.autograd.grad(cross_x, zs, grad_outputs=torch.ones_like(cross_x))[0] if want_grad else None
+            if whole:
+                J, dz = total.detach(), None if g is None else g.contiguous()
+                break
+            if J is None:
+                J = torch.empty(N, dtype=torch.float32, device=z.device)
+                dz = torch.empty_like(z) if want_grad else None
+            J[n0:n1] = total.detach()
+            if want_grad:
+                dz[:, n0:n1] = g
+        return J, dz
+
+    def likelihood_regret(self, x, y=None, steps=5, lr=0.05, epsilon=None, trajectory=None, evaluated=None):
+        """The likelihood regret of a batch (Xiao, Yan, Amit, NeurIPS 2020): how much a sample's ELBO improves when its own
+        posterior is optimised for `steps` Adam steps of learning rate `lr` with every weight frozen, in evaluation mode
+        -> (regret (N,), mu (N, K), log_var (N, K)): the refined posterior with it.  Larger regret = more out of distribution
+        (the `regret-*` score rows record MINUS this value).
+
+            (mu_0, lv_0) = the encoder's posterior, bit for bit latent_posterior()'s
+            for t < steps:  z_t = mu_t + exp(lv_t / 2) eps_t;  J_t = mean_l(-log p(x | z_tl)) + KL(q_t || p(z | y))
+                            (mu, lv)_{t+1} = Adam step t + 1 on d J_t / d (mu_t, lv_t)      [per sample: Adam is elementwise]
+            regret = J(mu_0, lv_0; eps_T) - J(mu_T, lv_T; eps_T)
+
+        J is `total` as evaluate(x, y, with_beta=False) reports it, the scale of the `elbo` score.  Deliberately not the
+        paper's: only the posterior's parameters move, not the encoder's weights, and both ELBOs of the difference share
+        their noise eps_T (common random numbers), so that zero steps give exactly zero.
+
+        y: the class of each sample under a class-conditional prior; without it the prediction (first predict method) of one
+        label-free evaluate(x), or of `evaluated` = (logits, losses) when the caller already has that pass.  `epsilon`
+        (steps + 1, L, N, K) injects the noise, L = the evaluation `latent_sampling`; slot 0 also serves the label-free pass.
+        `trajectory`: a list that receives (mu_t, log_var_t, J_t) copies for t = 0 .. steps (J_steps under eps_T).
+
+        Underneath, one iteration is the decoder forward, `ops.recon_wmse`, `ops.elbo`, their input-gradient passes back to z
+        (eval-mode BatchNorm backward, no weight-gradient kernel: every .grad stays as it was) and ONE `ops.latent_refine`
+        launch for gradient, Adam step and the next draw; the call is one span of constant weights and brings nothing to the
+        host.  Types cvae, vae and xvae with a gaussian decoder and a fixed, decayed, learned or coded sigma, fp32 only."""
+        if getattr(self, 'compute_dtype', 'fp32') != 'fp32':
+            raise NotImplementedError('the likelihood regret is built for the fp32 compute mode (set_compute_dtype("fp32"))')
+        if self.type not in self.REGRET_TYPES or self.y_is_coded:
+            raise NotImplementedError(f'the likelihood regret needs a decoder and a model without coded labels (types '
+                                      f'{", ".join(self.REGRET_TYPES)}), not type {self.type}')
+        if self.output_distribution != 'gaussian':
+            raise NotImplementedError(f'the likelihood regret is built for the gaussian decoder, not {self.output_distribution}')
+        if self.sigma.is_rmse:
+            raise NotImplementedError('the likelihood regret with a sigma that follows the rmse (is_rmse) is not built: that '
+                                      'sigma is no constant of the refinement')
+        enc = self.encoder
+        pr = enc.prior
+        if enc.mixed_prior is not None:
+            raise NotImplementedError('the likelihood regret under a mixed prior is not built')
+        steps = int(steps)
+        if steps < 0 or not lr > 0:
+            raise ValueError(f'steps {steps} >= 0 and lr {lr} > 0 expected')
+        x = x.detach().reshape(-1, *self.input_shape)
+        dev, N, K = x.device, x.shape[0], self.latent_dim
+        was_training = self.training
+        self.eval()
+        L = self.latent_sampling
+        if epsilon is not None and tuple(epsilon.shape) != (steps + 1, L, N, K):
+            raise ValueError(f'epsilon: (steps + 1, L, N, K) = {(steps + 1, L, N, K)} expected, got {tuple(epsilon.shape)}')
+        frozen = [p for p in self.parameters() if p.requires_grad]
+        for p in frozen:                      # input gradients only: no node of a gradient pass asks for a weight gradient
+            p.requires_grad_(False)
+        _lib.span_hold += 1
+        try:
+            with torch.no_grad(), self._constant_weights(x):
+                if epsilon is None:
+                    eps = draw_epsilon(L, (steps + 1, N, K), dev, enc.sampling.distribution).transpose(0, 1).contiguous()
+                else:
+                    eps = torch.cat((torch.zeros((steps + 1, 1, N, K), dtype=torch.float32, device=dev),
+                                     epsilon.to(dev, torch.float32)), 1)
+                feats = self._features_of(x).reshape(N, -1)
+                u, mu0, raw0 = enc.heads(feats, None)
+                if self.sigma.coded:          # taken once from the encoder pass; the Sigma parameter is not touched
+                    s, s_kind = enc.sigma(u).reshape(N).contiguous(), ops.SIGMA_CODED
+                else:
+                    s, s_kind = self.sigma.detach(), (ops.SIGMA_LOG if self.sigma.is_log else ops.SIGMA_VALUE)
+                if pr.conditional:
+                    if y is None:
+                        if evaluated is None:
+                            evaluated = self.evaluate(x, epsilon=None if epsilon is None else eps[0])[1:3]
+                        y = self.predict_after_evaluate(*evaluated)
+                    y = y.reshape(-1).to(dev, torch.int64)
+                lab, means, T = pr._kernel_operands(y if pr.conditional else None, N, dev)
+                forced = math.log(enc.forced_variance) if enc.forced_variance else None
+                kw = dict(prior=pr.distribution, var_dim=pr.var_dim, tau=pr._tau, alpha=pr._alpha_k,
+                          sampled=bool(enc.sampling.is_sampled), forced_lv=forced)
+                mu0, raw0 = mu0.contiguous(), None if raw0 is None else raw0.contiguous()
+                mu, raw, lv = mu0.clone(), None if raw0 is None else raw0.clone(), torch.empty_like(mu0)
+                z, kl = ops.latent_refine(mu, raw, lv, lab, means, T, eps_next=eps[0], **kw)[:2]
+                state = ops.latent_refine_state(mu, forced is not None)
+                for t in range(steps):
+                    J, dz = self._regret_objective(z, kl, x, s, s_kind, True)
+                    if trajectory is not None:
+                        trajectory.append((mu.clone(), lv.clone(), J))
+                    z, kl = ops.latent_refine(mu, raw, lv, lab, means, T, eps_cur=eps[t], dz=dz, state=state, step=t + 1, lr=lr,
+                                              eps_next=eps[t + 1], **kw)[:2]
+                J_end = self._regret_objective(z, kl, x, s, s_kind, False)[0]
+                if trajectory is not None:
+                    trajectory.append((mu.clone(), lv.clone(), J_end))
+                # the encoder's posterior under the same last noise: a forward-only launch leaves mu0 / raw0 as they are
+                z, kl = ops.latent_refine(mu0, raw0, torch.empty_like(mu0), lab, means, T, eps_next=eps[steps], **kw)[:2]
+                regret = self._regret_objective(z, kl, x, s, s_kind, False)[0] - J_end
+        finally:
+            _lib.span_hold -= 1
+            for p in frozen:
+                p.requires_grad_(True)
+            if was_training:
+                self.train()
+        return regret, mu, lv
 
     def latent_posterior(self, x, y=None):
         """The encoder's posterior of a batch and nothing else -> (mu, log_var), each (N, K): the feature stack, the two heads of

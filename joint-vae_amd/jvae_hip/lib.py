@@ -113,7 +113,8 @@ _SIGS = {
                                   + [c_float, c_int, c_int, c_float, P]),
     'jvae_latent_mixed_bwd_f32': (c_int, [P] * 19 + [c_int] * 4 + ([c_int] * 3 + [c_float] * 2) * 2
                                   + [c_float, c_int, c_int, P, c_size_t, P]),
-    'jvae_recon_fwd_f32': (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, P]),
+    'jvae_latent_refine_f32': (c_int, [P] * 17 + [c_int] * 6 + [c_float] * 2 + [c_int, c_int, c_float, c_float, c_long, c_int, P]),
+    'jvae_recon_fwd_f32':(c_int, [P, P, P, c_int, P, c_int, c_int, c_int, P]),
     'jvae_recon_bwd_f32': (c_int, [P, P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     'jvae_mse_rows_fwd_f32': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'jvae_mse_rows_bwd_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, P]),

@@ -1120,8 +1120,95 @@ def latent_mixed(mu, lv_raw, eps, y, prior_a, prior_b, split, *, w=1., sampled=T
     return _LatentMixed.apply(mu, lv_raw, eps, y, prior_a['means'], prior_a['T'], prior_b['means'], prior_b['T'], cfg)
 
 
+def _refine_operand(t, shape, what):
+    """A tensor the refinement kernel reads or writes IN PLACE: fp32, on the GPU, contiguous (no copy can stand in), no graph."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.requires_grad \
+            or tuple(t.shape) != tuple(shape):
+        raise L.JvaeHipError(f'latent_refine: {what} must be a contiguous fp32 GPU tensor of shape {tuple(shape)} without '
+                             'gradient (the kernel works in place)')
+    return t
+
+
+def latent_refine_state(mu, forced=False):
+    """Zero Adam state of `latent_refine` for the posterior `mu` (N, K): (m_mu, v_mu, m_lv, v_lv); no lv pair when forced."""
+    z = torch.zeros((4 - 2 * bool(forced),) + tuple(mu.shape), device=mu.device, dtype=torch.float32)
+    return tuple(z) + (None, None) * bool(forced)
+
+
+def latent_refine(mu, lv_raw, lv, y, means, T, *, eps_cur=None, dz=None, state=None, step=0, lr=0., eps_next=None,
+                  prior='gaussian', var_dim='scalar', tau=0., alpha=0., sampled=True, forced_lv=None):
+    """One iteration of the posterior refinement of the likelihood regret in ONE launch (csrc/latent.hip, latent_refine_kernel):
+
+        dz given:        g = d[mean_l(-log p(x|z_l)) + KL(q || p(z|y))] / d(mu, lv_raw), `dz` (L+1, N, K) being the decoder's
+                         part at z = mu + exp(lv/2) eps_cur; then one torch.optim.Adam step (betas (0.9, 0.999), eps 1e-8) of
+                         number `step` >= 1 and learning rate `lr` on mu and lv_raw IN PLACE with `state` = (m_mu, v_mu, m_lv,
+                         v_lv), updated in place as well (`latent_refine_state`); with forced_lv only mu moves;
+        eps_next given:  the latent forward at the (moved) posterior -> (z_next (L+1, N, K), kl, zdist, var_kl (N,)); `lv` (N, K)
+                         receives the clipped log-variance.  Without it: the update alone, returns None.
+
+    `lv` must hold the clipped log-variance of the posterior on entry when dz is given (the previous call wrote it).  Labels
+    given on the HOST are checked against [0, C) here; labels on the device are checked by the kernel, which never indexes with
+    a bad one (that sample does not move, its outputs are NaN).  No autograd: the kernel IS the backward."""
+    update, forward = dz is not None, eps_next is not None
+    if not (update or forward):
+        raise L.JvaeHipError('latent_refine: neither dz (an update) nor eps_next (a forward) was given')
+    if not torch.is_tensor(mu) or mu.dim() != 2:
+        raise L.JvaeHipError('latent_refine: mu must be (N, K)')
+    N, K = mu.shape
+    forced = forced_lv is not None
+    _refine_operand(mu, (N, K), 'mu')
+    _refine_operand(lv, (N, K), 'lv')
+    if not forced:
+        _refine_operand(lv_raw, (N, K), 'lv_raw')
+    means, T = _c(means.detach()), _c(T.detach())
+    if means.dim() != 2 or means.shape[1] != K or not means.is_cuda or means.dtype != torch.float32 or T.dtype != torch.float32:
+        raise L.JvaeHipError(f'latent_refine: means must be (C, {K}) fp32 on the GPU')
+    C = means.shape[0]
+    if PRIOR_KIND[prior] != PRIOR_KIND['gaussian'] and var_dim != 'scalar':
+        raise L.JvaeHipError('latent_refine: the tilted and uniform priors have a scalar variance')
+    t_numel = {'scalar': C, 'diag': C * K, 'full': C * K * K}[var_dim]
+    if T.numel() != t_numel:
+        raise L.JvaeHipError(f'latent_refine: T has {T.numel()} elements, var_dim {var_dim!r} wants {t_numel}')
+    if y.dtype != torch.int64 or tuple(y.shape) != (N,):
+        raise L.JvaeHipError(f'latent_refine: class labels must be int64 of shape ({N},)')
+    if not y.is_cuda:
+        if bool(((y < 0) | (y >= C)).any()):
+            L.check(-1, 'latent_refine: a label outside the classes of the prior')
+        y = y.to(mu.device)
+    y = _c(y)
+    noise = eps_next if forward else eps_cur
+    if not torch.is_tensor(noise) or noise.dim() != 3:
+        raise L.JvaeHipError('latent_refine: the noise must be (L+1, N, K); an update needs eps_cur')
+    Ls = noise.shape[0] - 1
+    m_mu = v_mu = m_lv = v_lv = None
+    if update:
+        _refine_operand(eps_cur, (Ls + 1, N, K), 'eps_cur')
+        _refine_operand(dz, (Ls + 1, N, K), 'dz')
+        if state is None or len(state) != 4:
+            raise L.JvaeHipError('latent_refine: an update needs state = (m_mu, v_mu, m_lv, v_lv)')
+        m_mu, v_mu = (_refine_operand(t, (N, K), 'Adam state') for t in state[:2])
+        if not forced:
+            m_lv, v_lv = (_refine_operand(t, (N, K), 'Adam state') for t in state[2:])
+        if int(step) < 1 or not math.isfinite(float(lr)):
+            raise L.JvaeHipError(f'latent_refine: step {step} must be >= 1 and lr {lr} finite')
+    out = None
+    if forward:
+        _refine_operand(eps_next, (Ls + 1, N, K), 'eps_next')
+        z = torch.empty((Ls + 1, N, K), device=mu.device, dtype=torch.float32)
+        out = (z,) + tuple(torch.empty((3, N), device=mu.device, dtype=torch.float32))
+    o = out or (None,) * 4
+    rc = L.load().jvae_latent_refine_f32(
+        L.ptr(mu), L.ptr(None if forced else lv_raw), L.ptr(lv), L.ptr(eps_cur if update else None), L.ptr(eps_next),
+        L.ptr(y), L.ptr(means), L.ptr(T), L.ptr(dz), L.ptr(m_mu), L.ptr(v_mu), L.ptr(m_lv), L.ptr(v_lv),
+        L.ptr(o[0]), L.ptr(o[1]), L.ptr(o[2]), L.ptr(o[3]), N, K, Ls, C, PRIOR_KIND[prior], VAR_KIND[var_dim], float(tau),
+        float(alpha), int(bool(sampled)), int(forced), float(forced_lv or 0.), float(lr), int(step) if update else 0,
+        (0 if update else 1) | (0 if forward else 2), L.stream_ptr())
+    L.check(rc, 'jvae_latent_refine_f32')
+    return out
+
+
 # ------------------------------------------------------------------------------------------- losses
-SIGMA_VALUE, SIGMA_LOG, SIGMA_CODED, SIGMA_RMSE = 0, 1, 2, 3      # kinds of sigma the loss kernels know (csrc/loss.hip)
+SIGMA_VALUE,SIGMA_LOG, SIGMA_CODED, SIGMA_RMSE = 0, 1, 2, 3      # kinds of sigma the loss kernels know (csrc/loss.hip)
 
 
 def _check_sigma(sigma, mode, N):

@@ -178,6 +178,30 @@ class ScoringMixin:
     DETECTION_PR_METRICS = False
     MISCLASS_PR_KEYS = ('aupr_correct', 'aupr_error', 'aucpr_correct', 'aucpr_error', 'dete')
 
+    # The likelihood-regret rows `regret-<steps>-<lr>` (Xiao, Yan, Amit 2020; cvae.likelihood_regret): T
+    # decoder forward and input-gradient passes per batch and pair of `REGRET_PARAMS`.  Off by default: every name raises, 'all'
+    # is the reference's table.  On (class or instance): 'all' and 'regret*' expand to the pairs on the types of REGRET_TYPES.
+    OOD_REGRET_METHODS = False
+    REGRET_TYPES = ('cvae', 'vae', 'xvae')
+    REGRET_PARAMS = [(5, 0.05), (20, 0.02)]                                   # (steps, lr): a starting point nobody has tuned
+
+    def _regret_names(self):
+        """The `regret-<steps>-<lr:.4f>` method names of this instance's `REGRET_PARAMS`, in their order."""
+        return ['regret-{:d}-{:.4f}'.format(int(s), float(lr)) for s, lr in self.REGRET_PARAMS]
+
+    def regret_scores(self, x, y=None, logits=None, losses=None, epsilon=None):
+        """The likelihood-regret rows of a batch for every (steps, lr) pair of `REGRET_PARAMS`: {'regret-<steps>-<lr>': (N,) fp32
+        device tensor}, higher = more in-distribution (the row is MINUS the regret).  `logits`, `losses`: what a label-free
+        evaluate(x) of the batch returned, if the caller has it (the class is predicted from them instead of from a pass of its
+        own).  `epsilon`: {name: (steps + 1, L, N, K)} noise per row.  One `likelihood_regret` call per pair."""
+        seen = None if losses is None else (logits, losses)
+        out = {}
+        for name, (steps, lr) in zip(self._regret_names(), self.REGRET_PARAMS):
+            regret = self.likelihood_regret(x, y, steps=int(steps), lr=float(lr), evaluated=seen,
+                                            epsilon=None if epsilon is None else epsilon[name])[0]
+            out[name] = -regret
+        return out
+
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
         return ['odin-{:.0f}-{:.4f}'.format(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
@@ -189,27 +213,33 @@ class ScoringMixin:
         `odin-T-eps` names are accepted; on every other type an ODIN name raises, and so do the spline-threshold ('-a-x-y')
         methods unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
         has_odin = 'odin*' in self.ood_methods
+        has_regret = bool(self.OOD_REGRET_METHODS) and self.type in self.REGRET_TYPES
 
         def unbuilt(m):
             return ('-a-' in m and not self.OOD_QUANTILE_METHODS) or (m.startswith('odin') and not has_odin)
 
         def expand(names):
-            plain = [m for m in names if m != 'odin*']
-            return plain + (self._odin_names() if len(plain) < len(names) else [])
+            plain = [m for m in names if m not in ('odin*', 'regret*')]
+            return plain + (self._odin_names() if 'odin*' in names else []) + (self._regret_names() if 'regret*' in names else [])
         if method == 'all':
             skipped = [m for m in self.ood_methods if unbuilt(m)]
             if skipped:
                 logging.warning('ood_detection_rates: methods outside this build are left out: %s', ', '.join(skipped))
-            return expand([m for m in self.ood_methods if not unbuilt(m)])
+            return expand([m for m in self.ood_methods if not unbuilt(m)] + ['regret*'] * has_regret)
         methods = [method] if isinstance(method, str) else list(method)
         for m in methods:
             if unbuilt(m):
                 raise NotImplementedError(f'{m}: spline-threshold (-a-x-y) and ODIN OOD methods are outside this build')
+            if m.startswith('regret') and not has_regret:
+                raise NotImplementedError(f'{m}: the likelihood-regret rows are an opt-in (OOD_REGRET_METHODS) of the types '
+                                          + ', '.join(self.REGRET_TYPES))
         methods = expand(methods)
         grid = set(self._odin_names())
         for m in methods:
             if m.startswith('odin') and m not in grid:
                 raise ValueError(f'{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)')
+            if m.startswith('regret') and m not in self._regret_names():
+                raise ValueError(f'{m}: not among the (steps, lr) pairs of this model (REGRET_PARAMS)')
             if '-a-' in m:
                 score_rows.roc_mode(m)
         return methods
@@ -240,11 +270,12 @@ class ScoringMixin:
         buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
         filled, sums, measures = 0, {}, None
         odin = any(m.startswith('odin') for m in methods)
+        regret = any(m.startswith('regret-') for m in methods)
         records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
         with torch.no_grad():
             for i in range(num_batch):
                 if recorded:
-                    keys = [k for k in recorder.keys() if k in self.loss_components or k.startswith('odin')]     # cvae.py:1665-1667
+                    keys = [k for k in recorder.keys() if k in self.loss_components or k.startswith(('odin', 'regret-'))]     # cvae.py:1665-1667
                     losses = recorder.get_batch(i, *keys, force_dict=True)
                     logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
                 else:
@@ -259,13 +290,16 @@ class ScoringMixin:
                     if odin:
                         # cvae.py:1645-1663: the whole grid per batch (it is what the recorder holds), on the device
                         losses = dict(losses, **self.odin_scores(x))
+                    if regret:
+                        # every pair of REGRET_PARAMS per batch, as for ODIN; the class comes from the pass above
+                        losses = dict(losses, **self.regret_scores(x, logits=logits, losses=losses))
                     if recording:
                         extra = {} if logits is None else {'logits': logits.T}
                         recorder.append_batch(**losses, y_true=y, **extra)
                 n = score_rows.write_rows(records, range(len(records)), logits, losses, buf, filled, self.SCORE_SET_TORCH_ROWS,
                                           self._wim_status_word)[0].shape[0]
-                if odin:
-                    losses = {k: v for k, v in losses.items() if not k.startswith('odin')}     # test_losses: the loss components
+                if odin or regret:
+                    losses = {k: v for k, v in losses.items() if not k.startswith(('odin', 'regret-'))}     # test_losses: the loss components
                 filled += n
                 if keep_test:
                     for k, v in losses.items():                                      # cvae.py:1671, summed on the device

@@ -913,6 +913,29 @@ int jvae_pca_moments_f32(const float* x, double* mean, double* cov, long N, int 
 int jvae_project_f32(const float* x, const double* mean, const double* V, float* out, long N, int K, int n_components,
                      void* stream);
 
+/* ---- k nearest neighbours of query rows among the rows of a bank (csrc/knn.hip; the deep-nearest-neighbour OOD score of Sun,
+ * Ming, Zhu and Li 2022 over the posterior means of a training set; no counterpart in the reference) ------------------------
+ * None of the entry points allocates or synchronises.  No floating-point atomics: same inputs, same bits, run to run and
+ * whatever `splits` is.
+ * Norms: x (M, K) fp32 -> sq (M,) fp32, sq_m = fmaf chain over k ascending of x_mk^2.  Computed once per bank.
+ * Neighbours: q (N, K), q_sq (N,), bank (M, K), bank_sq (M,) -> d2_out (N, k) fp32, the k smallest squared distances of each
+ * query row, ascending, and idx_out (N, k) int32, their bank rows.  The dot product of a pair is one fmaf chain over k ascending
+ * (the fp32 matrix instruction), then
+ *   normalized = 0:  d2 = max(fmaf(-2, q.b, |q|^2 + |b|^2), 0)
+ *   normalized = 1:  d2 = max(fmaf(-2, q.b / (max(sqrt|q|^2, 1e-12) * max(sqrt|b|^2, 1e-12)), 2), 0)
+ * the squared distance of the F.normalize()d rows, of which no copy is made.  Equal distances are ordered by ascending bank row.
+ * With M < k the unused slots hold +inf and -1.  A bank row whose distance is not finite is never selected and sets bit 0 of the
+ * device word *status; a query row with a non-finite element (or norm) gets NaN and -1 in all k slots and sets bit 1.  The word
+ * is only ever OR-ed into: the caller owns and clears it.
+ * splits: the number of bank partitions that are selected independently and merged by a second, fixed-order launch; 0: chosen
+ * here.  ws: device scratch of jvae_knn_workspace_bytes(N, M, K, k, splits) bytes, 4-byte aligned (-3, JVAE_EWORKSPACE, when
+ * smaller).  1 <= k <= 64, 1 <= K <= 4096, M < 2^31, N < 2^31, else -2 (JVAE_ENOTSUP) and a workspace size of 0; splits outside
+ * 0 .. 1024, a negative size or a missing pointer: -1 (JVAE_EINVAL).  N = 0 launches nothing. */
+int jvae_knn_sqnorms_f32(const float* x, float* sq, long M, int K, void* stream);
+size_t jvae_knn_workspace_bytes(long N, long M, int K, int k, int splits);
+int jvae_knn_f32(const float* q, const float* q_sq, const float* bank, const float* bank_sq, float* d2_out, int* idx_out, long N,
+                 long M, int K, int k, int normalized, int splits, int* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2287,6 +2287,99 @@ def histogram_check(device=None):
             raise ValueError(f'histogram: {bad} non-finite value(s) were met (they are in no bin)')
 
 
+# ------------------------------------------------------------ k nearest neighbours over a latent bank (csrc/knn.hip)
+KNN_MAX_K = 64              # neighbours: one list slot per lane
+KNN_MAX_DIM = 4096          # columns of the rows
+KNN_MAX_SPLITS = 1024
+KNN_STATUS_BANK = 1         # a bank row with a distance that is not finite was met (it is in no list)
+KNN_STATUS_QUERY = 2        # a query row with a non-finite element was met (its slots are NaN / -1)
+_knn_status = {}
+
+
+def knn_status(device):
+    """The per-device status word of `knn` calls made without one of their own (created cleared, on first use)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _knn_status:
+        _knn_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _knn_status[idx]
+
+
+def _knn_sqnorms(x):
+    sq = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    if x.shape[0]:
+        L.check(L.load().jvae_knn_sqnorms_f32(L.ptr(x), L.ptr(sq), x.shape[0], x.shape[1], L.stream_ptr()), 'jvae_knn_sqnorms_f32')
+    return sq
+
+
+def knn_bank(x):
+    """x (M, K) -> (bank, sq): the rows as contiguous fp32 (x itself when it already is; a bf16 / fp16 x is widened) and their
+    squared norms (M,) fp32, summed over k ascending in a fixed order - what `knn` wants of a bank, computed once.
+    1 <= K <= KNN_MAX_DIM.  One launch."""
+    if not x.is_floating_point():
+        raise L.JvaeHipError(f'knn_bank: floating-point rows expected, got {x.dtype}')
+    bank = _c(x.float())
+    L.ptr(bank)
+    if bank.dim() != 2 or not 1 <= bank.shape[1] <= KNN_MAX_DIM:
+        raise L.JvaeHipError(f'knn_bank: (M, K) with 1 <= K <= {KNN_MAX_DIM} expected, got {tuple(bank.shape)}')
+    return bank, _knn_sqnorms(bank)
+
+
+def knn(q, bank, sq, k, normalized=True, splits=0, status=None):
+    """The k nearest rows of `bank` (M, K) to each row of q (N, K), all fp32 on one device; sq (M,): the bank's norms from
+    `knn_bank` -> (d2 (N, k) fp32, the squared distances ascending, idx (N, k) int32, their bank rows).  normalized: the
+    distance between the F.normalize()d rows, 2 - 2 cos (no normalised copy is made), else |q|^2 + |b|^2 - 2 q.b; both clamped
+    at 0.  The products are exact-fp32 matrix instructions fused with the selection (csrc/knn.hip): no (N, M) matrix exists.
+    Ties go to the lower bank row; with M < k the unused slots hold +inf / -1.  splits: bank partitions selected independently
+    and merged in a fixed order (0: the library's choice); the result's bits do not depend on it.  status: an int32 device word
+    that takes bit KNN_STATUS_BANK when a bank row's distance is not finite (the row is never selected) and KNN_STATUS_QUERY
+    when a query row is not finite (its slots are NaN / -1); default `knn_status(device)`; `knn_check_status` raises on them.
+    1 <= k <= KNN_MAX_K, 1 <= K <= KNN_MAX_DIM.  N = 0 returns empties.  Three launches, nothing synchronised."""
+    q, bank, sq = _c(_f32(q, 'knn')), _c(_f32(bank, 'knn')), _c(_f32(sq, 'knn'))
+    L.ptr(q), L.ptr(bank), L.ptr(sq)
+    if q.dim() != 2 or bank.dim() != 2 or bank.shape[1] != q.shape[1] or tuple(sq.shape) != (bank.shape[0],) \
+            or bank.device != q.device or sq.device != q.device:
+        raise L.JvaeHipError(f'knn: q (N, K), bank (M, K) and sq (M,) on one device expected, got {tuple(q.shape)}, '
+                             f'{tuple(bank.shape)} and {tuple(sq.shape)}')
+    k, splits = int(k), int(splits)
+    (N, K), M = q.shape, bank.shape[0]
+    if not 1 <= k <= KNN_MAX_K or not 1 <= K <= KNN_MAX_DIM or not 0 <= splits <= KNN_MAX_SPLITS:
+        raise L.JvaeHipError(f'knn: 1 <= k <= {KNN_MAX_K}, 1 <= K <= {KNN_MAX_DIM} and 0 <= splits <= {KNN_MAX_SPLITS} expected, '
+                             f'got k={k}, K={K}, splits={splits} (unsupported configuration)')
+    dev = q.device
+    d2 = torch.empty((N, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((N, k), dtype=torch.int32, device=dev)
+    if not N:
+        return d2, idx
+    if status is None:
+        status = knn_status(dev)
+    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise L.JvaeHipError('knn: an int32 status word on the device of the rows expected')
+    lib = L.load()
+    nbytes = lib.jvae_knn_workspace_bytes(N, M, K, k, splits)
+    if not nbytes:
+        raise L.JvaeHipError(f'knn: sizes out of range (N={N}, M={M}, K={K}, k={k})')
+    ws = L.workspace(nbytes + 4, dev)
+    off = (-ws.data_ptr()) % 4
+    L.check(lib.jvae_knn_f32(L.ptr(q), L.ptr(_knn_sqnorms(q)), L.ptr(bank), L.ptr(sq), L.ptr(d2), L.ptr(idx), N, M, K, k,
+                             1 if normalized else 0, splits, L.ptr(status), ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()),
+            'jvae_knn_f32')
+    return d2, idx
+
+
+def knn_check_status(status=None):
+    """Raise ValueError for what `knn` flagged.  status: the word given to the op (a device tensor: read here - this is the
+    synchronisation - and cleared), a host value, or None for the per-device default words."""
+    words = list(_knn_status.values()) if status is None else [status]
+    for w in words:
+        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
+        if torch.is_tensor(w) and v:
+            w.zero_()
+        if v & KNN_STATUS_QUERY:
+            raise ValueError('knn: a query row with a non-finite element was met (its distances are NaN, its indices -1)')
+        if v & KNN_STATUS_BANK:
+            raise ValueError('knn: a bank row at a non-finite distance was met (it is in no list)')
+
+
 # ------------------------------------------------------------ 2-D projections: exact t-SNE and PCA (csrc/embed.hip)
 EMBED_MAX_N = 16384         # points of a t-SNE: a row of fp32 distances in LDS
 EMBED_MAX_K = 1024          # dimensions of the points

@@ -13,9 +13,10 @@ import torch
 from jvae_hip import ops
 
 # what the form of a row depends on besides its name
-# (OOD_REGRET_METHODS: the model's opt-in switch of the recorded `regret-*` rows; off where a caller does not say)
-Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is_jvae num_labels OOD_REGRET_METHODS',
-                    defaults=(False,))
+# (OOD_REGRET_METHODS, OOD_KNN_METHODS: the model's opt-in switches of the recorded `regret-*` / `knn-*` rows; off where a caller
+# does not say)
+Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is_jvae num_labels OOD_REGRET_METHODS OOD_KNN_METHODS',
+                    defaults=(False, False))
 
 
 def traits_of(model):
@@ -52,6 +53,8 @@ def _plain_entry(m, t):
         return m, None, None                                   # cvae.py:1076-1078: recorded by odin_scores()
     if m.startswith('regret-'):                                # recorded by regret_scores(), an opt-in
         return (m, None, None) if t.OOD_REGRET_METHODS else None
+    if m.startswith('knn-') and m[4:].isdigit():               # recorded by knn_scores(), an opt-in
+        return (m, None, None) if t.OOD_KNN_METHODS else None
     if m == 'elbo':
         return ('total', 'max-', 1.) if per_class else ('total', 'neg', 0.)
     if m == 'iws':                                             # cvae.py:1013-1019: log C unless is_jvae
@@ -85,7 +88,8 @@ def _wim_entry(m):
 @dataclass(frozen=True)
 class Row:
     """One score row.  base: the name without the '-2s' / '-a-x-y' suffix, which only names the thresholding done downstream
-    (`roc_mode`); source: the key of the losses the row reads, `logits`, or the name itself for a recorded `odin-*` / `regret-*` row; kind,
+    (`roc_mode`); source: the key of the losses the row reads, `logits`, or the name itself for a recorded `odin-*` / `regret-*` /
+    `knn-*` row; kind,
     const: its row of ops.misclass_scores (temperature or additive constant) or of ops.wim_scores (the family's factor), kind
     None where there is no kernel row."""
     name: str

@@ -202,6 +202,99 @@ class ScoringMixin:
             out[name] = -regret
         return out
 
+    # The nearest-neighbour rows `knn-<k>` (Sun, Ming, Zhu, Li 2022): minus the distance from a sample's
+    # posterior mean to its k-th nearest neighbour among the means of a training set, the bank of `fit_latent_bank`.  Off by
+    # default: every name raises, 'all' is the reference's table.  On (class or instance): 'all' and 'knn*' expand to `KNN_K`.
+    # A set scored against a bank fitted on itself meets itself: `knn-1` is then about 0 (there is no leave-one-out).
+    OOD_KNN_METHODS = False
+    KNN_K = (1, 10, 50)
+    KNN_NORMALIZE = True                                                      # distances between the F.normalize()d means
+    latent_bank = None                                                        # {'bank' (M, K), 'sq' (M,), 'labels' (M,), 'set'}
+    LATENT_BANK_FILE = 'latent-bank.pth'
+
+    def _knn_names(self):
+        """The `knn-<k>` method names of this instance's `KNN_K`, in their order."""
+        return ['knn-{:d}'.format(int(k)) for k in self.KNN_K]
+
+    def fit_latent_bank(self, dataset, batch_size=100, ratio=1.0, seed=0):
+        """Fill `latent_bank` with the posterior means of `dataset` (any map-style dataset of (x, label)): one latent_posterior()
+        pass in eval mode, each batch's `mu` written straight into a preallocated (M, K) fp32 device tensor, the labels beside
+        it, then the rows' norms (ops.knn_bank).  ratio < 1: a seeded random subset of round(ratio * len) samples (a
+        torch.Generator permutation on the host, chosen before the pass; only the kept rows are stored, in the order of the
+        set).  -> the bank's dictionary.  Models with coded labels are refused, as latent_posterior(x) refuses them."""
+        if self.y_is_coded:
+            raise NotImplementedError('fit_latent_bank: latent_posterior(x) without labels is not possible for models with coded '
+                                      'labels (their encoder reads y)')
+        n = len(dataset)
+        if not 0 < ratio <= 1:
+            raise ValueError(f'fit_latent_bank: a ratio in (0, 1] expected, got {ratio}')
+        keep = None
+        if ratio < 1:
+            perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
+            keep = torch.zeros(n, dtype=torch.bool)
+            keep[perm[:max(1, int(round(ratio * n)))]] = True
+        M = n if keep is None else int(keep.sum())
+        device = self.device
+        was_training = self.training
+        self.eval()
+        bank, labels, seen, pos = None, torch.empty(M, dtype=torch.int64, device=device), 0, 0
+        with torch.no_grad():
+            for batch in self._batch_source(dataset, batch_size, False):
+                x, y = batch[:2]
+                sel = None if keep is None else keep[seen:seen + x.shape[0]]
+                seen += x.shape[0]
+                if sel is not None and not bool(sel.any()):
+                    continue
+                mu = self.latent_posterior(self._device_batch(x.to(device)))[0]
+                y = y.to(device)
+                if sel is not None and not bool(sel.all()):       # the whole batch is encoded: the rows are those of a full pass
+                    rows = sel.nonzero()[:, 0].to(device)
+                    mu, y = mu[rows], y[rows]
+                if bank is None:
+                    bank = torch.empty((M, mu.shape[1]), dtype=torch.float32, device=device)
+                bank[pos:pos + mu.shape[0]] = mu
+                labels[pos:pos + mu.shape[0]] = y
+                pos += mu.shape[0]
+        if was_training:
+            self.train()
+        if bank is None or pos != M:
+            raise ValueError(f'fit_latent_bank: the set yielded {pos} of the {M} rows expected')
+        bank, sq = ops.knn_bank(bank)
+        self.latent_bank = {'bank': bank, 'sq': sq, 'labels': labels, 'set': getattr(dataset, 'name', 'set')}
+        return self.latent_bank
+
+    def save_latent_bank(self, dir_name):
+        """Write the fitted bank as `latent-bank.pth` into `dir_name` (a file of its own: save() / load() do not know it)."""
+        if self.latent_bank is None:
+            raise ValueError('save_latent_bank: no bank is fitted (fit_latent_bank)')
+        os.makedirs(dir_name, exist_ok=True)
+        path = os.path.join(dir_name, self.LATENT_BANK_FILE)
+        torch.save({k: v.cpu() if torch.is_tensor(v) else v for k, v in self.latent_bank.items()}, path)
+        return path
+
+    def load_latent_bank(self, dir_name):
+        """Read `latent-bank.pth` of `dir_name` onto the model's device -> the bank's dictionary, bit for bit what was saved."""
+        d = torch.load(os.path.join(dir_name, self.LATENT_BANK_FILE), map_location='cpu')
+        if set(d) != {'bank', 'sq', 'labels', 'set'} or d['bank'].dtype != torch.float32 or d['bank'].dim() != 2 \
+                or tuple(d['sq'].shape) != (d['bank'].shape[0],) or tuple(d['labels'].shape) != (d['bank'].shape[0],):
+            raise ValueError(f'load_latent_bank: {dir_name} does not hold a latent bank')
+        self.latent_bank = {k: v.to(self.device).contiguous() if torch.is_tensor(v) else v for k, v in d.items()}
+        return self.latent_bank
+
+    def knn_scores(self, mu):
+        """The nearest-neighbour rows of a batch of posterior means mu (N, K) for every k of `KNN_K`: {'knn-<k>': (N,) fp32 device
+        tensor} = -sqrt(d2 to the k-th nearest row of the bank), higher = more in-distribution.  ONE `ops.knn` call with
+        k = max(KNN_K); `KNN_NORMALIZE`: distances between the normalised rows.  ValueError without a bank, or with a bank of
+        fewer rows than max(KNN_K).  A non-finite row sets the device's `ops.knn_status` word (`ops.knn_check_status`)."""
+        ks = [int(k) for k in self.KNN_K]
+        if self.latent_bank is None:
+            raise ValueError('knn_scores: no latent bank is fitted (fit_latent_bank or load_latent_bank)')
+        bank = self.latent_bank
+        if not ks or min(ks) < 1 or bank['bank'].shape[0] < max(ks):
+            raise ValueError(f"knn_scores: the bank holds {bank['bank'].shape[0]} rows, KNN_K = {tuple(ks)} needs 1 <= k <= rows")
+        d2, _ = ops.knn(mu.float(), bank['bank'], bank['sq'], max(ks), normalized=bool(self.KNN_NORMALIZE))
+        return {name: -d2[:, k - 1].sqrt() for name, k in zip(self._knn_names(), ks)}
+
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
         return ['odin-{:.0f}-{:.4f}'.format(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
@@ -211,21 +304,25 @@ class ScoringMixin:
         line), a name or a list of names.  On a type whose table lists `odin*` (vib), 'all' and 'odin*' expand to the ODIN grid
         (the plain names first, the expansion behind them, as the reference's develop_starred_methods orders them) and single
         `odin-T-eps` names are accepted; on every other type an ODIN name raises, and so do the spline-threshold ('-a-x-y')
-        methods unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
+        methods unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others.  The `regret*` and `knn*` rows are
+        opt-ins (`OOD_REGRET_METHODS`, `OOD_KNN_METHODS`): off, their names raise and 'all' does not hold them; on, 'all' and the
+        starred name expand to `_regret_names()` / `_knn_names()`, behind everything else."""
         has_odin = 'odin*' in self.ood_methods
         has_regret = bool(self.OOD_REGRET_METHODS) and self.type in self.REGRET_TYPES
+        has_knn = bool(self.OOD_KNN_METHODS)
 
         def unbuilt(m):
             return ('-a-' in m and not self.OOD_QUANTILE_METHODS) or (m.startswith('odin') and not has_odin)
 
         def expand(names):
-            plain = [m for m in names if m not in ('odin*', 'regret*')]
-            return plain + (self._odin_names() if 'odin*' in names else []) + (self._regret_names() if 'regret*' in names else [])
+            plain = [m for m in names if m not in ('odin*', 'regret*', 'knn*')]
+            return plain + (self._odin_names() if 'odin*' in names else []) + (self._regret_names() if 'regret*' in names else []) \
+                + (self._knn_names() if 'knn*' in names else [])
         if method == 'all':
             skipped = [m for m in self.ood_methods if unbuilt(m)]
             if skipped:
                 logging.warning('ood_detection_rates: methods outside this build are left out: %s', ', '.join(skipped))
-            return expand([m for m in self.ood_methods if not unbuilt(m)] + ['regret*'] * has_regret)
+            return expand([m for m in self.ood_methods if not unbuilt(m)] + ['regret*'] * has_regret + ['knn*'] * has_knn)
         methods = [method] if isinstance(method, str) else list(method)
         for m in methods:
             if unbuilt(m):
@@ -233,6 +330,8 @@ class ScoringMixin:
             if m.startswith('regret') and not has_regret:
                 raise NotImplementedError(f'{m}: the likelihood-regret rows are an opt-in (OOD_REGRET_METHODS) of the types '
                                           + ', '.join(self.REGRET_TYPES))
+            if m.startswith('knn') and not has_knn:
+                raise NotImplementedError(f'{m}: the nearest-neighbour rows are an opt-in (OOD_KNN_METHODS)')
         methods = expand(methods)
         grid = set(self._odin_names())
         for m in methods:
@@ -240,6 +339,8 @@ class ScoringMixin:
                 raise ValueError(f'{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)')
             if m.startswith('regret') and m not in self._regret_names():
                 raise ValueError(f'{m}: not among the (steps, lr) pairs of this model (REGRET_PARAMS)')
+            if m.startswith('knn') and m not in self._knn_names():
+                raise ValueError(f'{m}: not among the neighbour counts of this model (KNN_K)')
             if '-a-' in m:
                 score_rows.roc_mode(m)
         return methods
@@ -271,16 +372,17 @@ class ScoringMixin:
         filled, sums, measures = 0, {}, None
         odin = any(m.startswith('odin') for m in methods)
         regret = any(m.startswith('regret-') for m in methods)
+        knn = any(m.startswith('knn-') for m in methods)
         records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
         with torch.no_grad():
             for i in range(num_batch):
                 if recorded:
-                    keys = [k for k in recorder.keys() if k in self.loss_components or k.startswith(('odin', 'regret-'))]     # cvae.py:1665-1667
+                    keys = [k for k in recorder.keys() if k in self.loss_components or k.startswith(('odin', 'regret-', 'knn-'))]     # cvae.py:1665-1667
                     losses = recorder.get_batch(i, *keys, force_dict=True)
                     logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
                 else:
                     x, y = next(loader)[:2]
-                    if sample_recorder is None:
+                    if sample_recorder is None and not knn:
                         x, logits, losses, measures = self._evaluate_for_scores(x, i, measures)
                     else:
                         x, logits, losses, measures, mu = self._evaluate_for_scores(x, i, measures, with_mu=True)
@@ -293,13 +395,16 @@ class ScoringMixin:
                     if regret:
                         # every pair of REGRET_PARAMS per batch, as for ODIN; the class comes from the pass above
                         losses = dict(losses, **self.regret_scores(x, logits=logits, losses=losses))
+                    if knn:
+                        # every k of KNN_K from one call, on the posterior means of the pass above
+                        losses = dict(losses, **self.knn_scores(mu))
                     if recording:
                         extra = {} if logits is None else {'logits': logits.T}
                         recorder.append_batch(**losses, y_true=y, **extra)
                 n = score_rows.write_rows(records, range(len(records)), logits, losses, buf, filled, self.SCORE_SET_TORCH_ROWS,
                                           self._wim_status_word)[0].shape[0]
-                if odin or regret:
-                    losses = {k: v for k, v in losses.items() if not k.startswith(('odin', 'regret-'))}     # test_losses: the loss components
+                if odin or regret or knn:
+                    losses = {k: v for k, v in losses.items() if not k.startswith(('odin', 'regret-', 'knn-'))}     # test_losses: the loss components
                 filled += n
                 if keep_test:
                     for k, v in losses.items():                                      # cvae.py:1671, summed on the device

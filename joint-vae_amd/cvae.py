@@ -39,6 +39,7 @@ from torch import nn
 
 from jvae_hip import ops
 from jvae_hip import lib as _lib
+from module import score_rows
 from module.scoring import ScoringMixin
 from module.optimizers import Optimizer
 from module.losses import x_loss, mse_loss, categorical_loss  # noqa: F401  (import surface of the reference)
@@ -173,12 +174,12 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
     # instance may override the two lists (its `odin*` rows then follow its own lists)
     ODIN_TEMPS = [m * 10 ** i for i in (0, 1, 2) for m in (1, 2, 5)] + [1000]
     ODIN_EPS = [k / 20 * 0.004 for k in range(21)]
-    methods_params = {'softkl': [], 'softzdist': [], 'baseline': [], 'odin': []}
+    methods_params = {'softkl': [], 'softzdist': [], 'baseline': [], score_rows.ODIN.prefix: []}
     for _T in ODIN_TEMPS:
         for _k in ('softkl', 'softzdist', 'baseline'):
             methods_params[_k].append('{}-{:.0f}'.format(_k, _T))
         for _e in ODIN_EPS:
-            methods_params['odin'].append('odin-{:.0f}-{:.4f}'.format(_T, _e))
+            methods_params[score_rows.ODIN.prefix].append(score_rows.odin_name(_T, _e))
     del _T, _k, _e
 
     # train_model(): run every full-size batch of the train phase as a replay of ONE captured HIP graph (zero_grad ... Adam,

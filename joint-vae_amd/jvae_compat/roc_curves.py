@@ -60,9 +60,9 @@ def pr_metrics(ins, outs, two_sided=False, device=None):
         raise NotImplementedError('pr_metrics: quantile thresholds (two_sided=(a, b)) give no scalar score')
     rows = _rows(ins, outs, device)
     r = ops.pr_metrics(rows[0], rows[1], 'around-mean' if two_sided == 'around-mean' else False)
-    host = torch.cat([torch.stack([r[k] for k in ops.PR_FIGURES]), r['status'].double()[None]]).cpu().tolist()
-    ops.roc_check_status([int(host[-1])])
-    return dict(zip(ops.PR_FIGURES, host[:-1]))
+    host = ops.read_back(r)
+    ops.roc_check_status([int(host['status'])])
+    return {k: float(host[k]) for k in ops.PR_FIGURES}
 
 
 def _rows(ins, outs, device):
@@ -74,6 +74,6 @@ def _rows(ins, outs, device):
 def _one_row(ins, outs, kept_tpr, mode, device):
     rows = _rows(ins, outs, device)
     r = ops.roc_curve(rows[0], rows[1], sorted(kept_tpr), mode)
-    ops.roc_check_status([int(r['status'].cpu())])
-    host = {k: r[k].cpu().numpy() for k in ('auc', 'fpr', 'tpr', 'low', 'up')}
+    host = ops.read_back(r)
+    ops.roc_check_status([int(host['status'])])
     return float(host['auc']), host['fpr'], host['tpr'], {'low': host['low'], 'up': host['up']}

@@ -16,6 +16,7 @@ import torch
 
 from jvae_hip import ops
 from jvae_hip import lib as _lib
+from module.score_rows import ODIN
 
 default_scores = {'wim': {'r': 'zdist', 'g': 'elbo'},
                   'vib': {'r': 'odin-1-0.0040', 'g': 'none'}}
@@ -35,7 +36,7 @@ def _r_spec(losses, score, mtype, cache=None):
     if score is None:
         score = default_scores[mtype]['r']
     logging.debug('r score is %s', score)
-    if score and score.startswith('odin'):
+    if score and score.startswith(ODIN.prefix):
         return 'odin', losses[score], None
     if score == 'predist':
         return 'half_y', losses['pre-zdist'], None
@@ -197,13 +198,12 @@ def scod_rates(recorders, dset, mtype=None, r=None, g=None, weight=1., curves=Fa
         ops.scod_scores(specs, losses['y_est_already'], max(_classes(sp) for sp in specs), k, out=scores, col=col, status=word)
         col += k
     res = ops.scod_curve(scores, y_true.to(torch.int64), y_est.to(torch.int64), curves=curves, figures=True, n_in=n_in)
-    host = torch.cat((res['figures'].reshape(-1), res['status'].double(), word.double())).tolist()     # the one read-back
-    F = len(ops.SCOD_FIGURES)
-    ops.wim_check_status(int(host[-1]))
-    ops.scod_check_status([int(v) for v in host[M * F:M * F + M]])
+    host = ops.read_back({'figures': res['figures'], 'status': res['status'], 'word': word})     # the one read-back
+    ops.wim_check_status(int(host['word'][0]))
+    ops.scod_check_status([int(v) for v in host['status']])
     out = {}
     for m, v in enumerate(variants):
-        out[v] = dict(zip(ops.SCOD_FIGURES, host[m * F:(m + 1) * F]))
+        out[v] = dict(zip(ops.SCOD_FIGURES, host['figures'][m].tolist()))
         if curves:
             out[v].update({k: res[k][m] for k in ('tpr', 'selective_risk', 'fpr')})
     return out if any(as_lists) else out[variants[0]]

@@ -1589,6 +1589,15 @@ def roc_check_status(status):
             raise ValueError(f'roc_curve: non-finite in-distribution score in around-mean row {m}')
 
 
+def read_back(fields):
+    """{name: device tensor} -> {name: fp64 numpy array of that tensor's shape}, in ONE copy to the host: every field is widened
+    to fp64 (exact for fp64 and fp32 values and for the int32 status words and counts), flattened and concatenated on the device,
+    and the host copy is cut by numel() and reshaped."""
+    host = torch.cat([v.double().reshape(-1) for v in fields.values()]).cpu().numpy()
+    ends = np.cumsum([v.numel() for v in fields.values()]).tolist()
+    return {k: host[end - v.numel():end].reshape(tuple(v.shape)) for (k, v), end in zip(fields.items(), ends)}
+
+
 # ------------------------------------------------------------------------------------------- SCOD risk curves (csrc/scod.hip)
 SCOD_R_KINDS = {None: -1, 'zero': 0, 'half_y': 1, 'logmsp': 2, 'odin': 3}
 SCOD_G_KINDS = {None: -1, 'zero': 0, 'half': 1, 'neg': 2, 'plain': 3}

@@ -19,6 +19,46 @@ Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is
                     defaults=(False, False))
 
 
+# One family of RECORDED score rows: a model method computes them once per batch, the pass records them with the losses, reads
+# them back from a full recorder and copies them into the score buffer as they are.  prefix: a name that starts with it is the
+# family's (`_ood_methods` refuses it unless the model lists it); is_row: name without its thresholding suffix -> whether it is a
+# well-formed row (`parse` accepts nothing else); starred: the name that expands to the model's list; on, trait: whether the family
+# is switched on, from a model and from a Traits value; names, scores: the NAMES of the model methods (looked up at each call) that
+# list the rows and compute {row: (N,) scores} from the keywords `args` - `x`, `logits`, `losses` (the batch and its label-free
+# evaluation), `mu` (its posterior means); off, unlisted: the refusals where the family is off / the model does not list the name
+Family = namedtuple('Family', 'prefix is_row starred on trait names scores args off unlisted')
+
+# in the order in which 'all' and the starred names expand and the per-batch calls run
+FAMILIES = (
+    Family('odin', lambda m: m.startswith('odin'), 'odin*',                  # cvae.py:1076-1078, 1645-1663
+           lambda model: 'odin*' in model.ood_methods, lambda t: True, '_odin_names', 'odin_scores', ('x',),
+           '{m}: spline-threshold (-a-x-y) and ODIN OOD methods are outside this build',
+           '{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)'),
+    Family('regret', lambda m: m.startswith('regret-'), 'regret*',
+           lambda model: bool(model.OOD_REGRET_METHODS) and model.type in model.REGRET_TYPES, lambda t: t.OOD_REGRET_METHODS,
+           '_regret_names', 'regret_scores', ('x', 'logits', 'losses'),
+           '{m}: the likelihood-regret rows are an opt-in (OOD_REGRET_METHODS) of the types {types}',
+           '{m}: not among the (steps, lr) pairs of this model (REGRET_PARAMS)'),
+    Family('knn', lambda m: m.startswith('knn-') and m[4:].isdigit(), 'knn*',
+           lambda model: bool(model.OOD_KNN_METHODS), lambda t: t.OOD_KNN_METHODS, '_knn_names', 'knn_scores', ('mu',),
+           '{m}: the nearest-neighbour rows are an opt-in (OOD_KNN_METHODS)',
+           '{m}: not among the neighbour counts of this model (KNN_K)'))
+ODIN = FAMILIES[0]
+odin_name = (ODIN.prefix + '-{:.0f}-{:.4f}').format            # (T, eps) -> `odin-T-eps` as the reference formats it (cvae.py:124-127)
+
+
+def claimed_by(name):
+    """The family whose prefix claims `name`, or None."""
+    return next((f for f in FAMILIES if name.startswith(f.prefix)), None)
+
+
+def recorded_by(name):
+    """The family `name` (no thresholding suffix) is a well-formed row of, or None."""
+    for f in FAMILIES:
+        if f.is_row(name):
+            return f
+
+
 def traits_of(model):
     opt = Traits._field_defaults
     return Traits(*(getattr(model, f, opt[f]) if f in opt else getattr(model, f) for f in Traits._fields))
@@ -49,12 +89,9 @@ def roc_mode(name):
 def _plain_entry(m, t):
     """(source, kind, const) of the score `m` (no thresholding suffix) on a model with the traits `t`; None: no such score."""
     per_class = t.losses_might_be_computed_for_each_class
-    if m.startswith('odin'):
-        return m, None, None                                   # cvae.py:1076-1078: recorded by odin_scores()
-    if m.startswith('regret-'):                                # recorded by regret_scores(), an opt-in (DESIGN.md section 7o)
-        return (m, None, None) if t.OOD_REGRET_METHODS else None
-    if m.startswith('knn-') and m[4:].isdigit():               # recorded by knn_scores(), an opt-in (DESIGN.md section 7p)
-        return (m, None, None) if t.OOD_KNN_METHODS else None
+    family = recorded_by(m)
+    if family is not None:                                     # recorded by the family's method; off: no such score
+        return (m, None, None) if family.trait(t) else None
     if m == 'elbo':
         return ('total', 'max-', 1.) if per_class else ('total', 'neg', 0.)
     if m == 'iws':                                             # cvae.py:1013-1019: log C unless is_jvae

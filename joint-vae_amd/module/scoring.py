@@ -2,6 +2,7 @@
 ClassificationVariationalNetwork: per-sample OOD scores, accuracy, OOD and misclassification detection rates.  What a method name
 means, and the one writer of score rows, are in module/score_rows.py; the model itself (evaluate, predict_after_evaluate,
 odin_scores, the tables of method names) is in cvae.py."""
+import contextlib
 import logging
 import os
 import time
@@ -19,7 +20,7 @@ class ScoringMixin:
     # existing ROC checks hold their thresholds to the bits of exactly these expressions, and a softmax or log-sum-exp summed in
     # another order moves a last bit (measured on the MI355X: up to 2 fp32 ulp between the kernel's softmax rows and torch's).
     SCORE_SET_TORCH_ROWS = ('iws', 'elbo', 'soft', 'baseline', 'hyz')
-    MISCLASS_TORCH_ROWS = ('iws', 'odin')     # what misclassification_detection_rates leaves on torch: `iws`, the recorded `odin-*`
+    MISCLASS_TORCH_ROWS = ('iws', score_rows.ODIN.prefix)     # misclassification_detection_rates: `iws`, the recorded `odin-*`
     _wim_status_word = None                   # jvae_compat.wim.WIMJob: (name, device) -> the status word of its `~` / `@` rows
 
     def batch_dist_measures(self, logits, losses, methods, to_cpu=False, out=None, rows=None, col=0):
@@ -82,6 +83,32 @@ class ScoringMixin:
             return batches
         return torch.utils.data.DataLoader(dset, batch_size=batch_size, num_workers=0, shuffle=shuffle)
 
+    @contextlib.contextmanager
+    def _recorded_pass(self, dset, name, batch_size, num_batch, shuffle, recorder, sample_dirs):
+        """One pass over `dset` with a `LossRecorder` (or None), around the caller's loop: -> (recorded, recording, num_batch,
+        batch_size, iterator over the batches).  recorded: the recorder holds the batches already, their number and size are its
+        own and nothing is loaded (iterator None); recording: it is reset, the caller appends every batch and `record-<name>.pth`
+        is written into `sample_dirs` afterwards.  The loader is made and read between init_seed_for_dataloader() and
+        restore_seed(): every pass with the recorder sees the same samples in the same order."""
+        recorded = recorder is not None and len(recorder) >= num_batch
+        recording = recorder is not None and not recorded
+        if recorded:
+            num_batch, batch_size = len(recorder), recorder.batch_size
+        if recording:
+            recorder.reset()
+            recorder.num_batch = num_batch
+        if recorder is not None:
+            recorder.init_seed_for_dataloader()
+        try:
+            yield recorded, recording, num_batch, batch_size, None if recorded else iter(self._batch_source(dset, batch_size, shuffle))
+        finally:
+            if recorder is not None:
+                recorder.restore_seed()
+        if recording:
+            for d in sample_dirs:
+                os.makedirs(d, exist_ok=True)
+                recorder.save(os.path.join(d, 'record-{}.pth'.format(name)))
+
     def accuracy(self, testset=None, batch_size=100, num_batch='all', method='all', print_result=False,
                  update_self_testing=True, outputs=None, sample_dirs=[], recorder=None, epoch='last', from_where='all',
                  epoch_tolerance=0, log=True):
@@ -105,22 +132,13 @@ class ScoringMixin:
         num_batch = full if not shuffle else int(num_batch)
         if epoch == 'last':
             epoch = self.trained
-        recorded = recorder is not None and len(recorder) >= num_batch
-        recording = recorder is not None and not recorded
-        if recorded:
-            num_batch, batch_size = len(recorder), recorder.batch_size
-        if recording:
-            recorder.reset()
-            recorder.num_batch = num_batch
-        if recorder is not None:
-            recorder.init_seed_for_dataloader()
         device = self.device
         was_training = self.training
         self.eval()
-        loader = iter(self._batch_source(testset, batch_size, shuffle))
         errors = torch.zeros(len(methods), device=device)
         sums, n, measures, t0 = {}, 0, None, time.time()
-        with torch.no_grad():
+        with torch.no_grad(), self._recorded_pass(testset, name, batch_size, num_batch, shuffle, recorder, sample_dirs) as (
+                recorded, recording, num_batch, batch_size, loader):
             for i in range(num_batch):
                 if recorded:
                     keys = [k for k in recorder.keys() if k in self.loss_components]
@@ -149,12 +167,6 @@ class ScoringMixin:
         self.test_losses = {k: float(v) / max(num_batch, 1) for k, v in sums.items()}
         if measures:
             self.test_measures = dict(measures)
-        if recorder is not None:
-            recorder.restore_seed()
-        if recording:
-            for d in sample_dirs:
-                os.makedirs(d, exist_ok=True)
-                recorder.save(os.path.join(d, 'record-{}.pth'.format(name)))
         if update_self_testing:
             for m in methods:
                 if n > self.testing.get(epoch, {}).get(m, {'n': 0})['n']:
@@ -297,50 +309,42 @@ class ScoringMixin:
 
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
-        return ['odin-{:.0f}-{:.4f}'.format(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
+        return [score_rows.odin_name(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
 
     def _ood_methods(self, method):
         """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
-        line), a name or a list of names.  On a type whose table lists `odin*` (vib), 'all' and 'odin*' expand to the ODIN grid
-        (the plain names first, the expansion behind them, as the reference's develop_starred_methods orders them) and single
-        `odin-T-eps` names are accepted; on every other type an ODIN name raises, and so do the spline-threshold ('-a-x-y')
-        methods unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others.  The `regret*` and `knn*` rows are
-        opt-ins (`OOD_REGRET_METHODS`, `OOD_KNN_METHODS`): off, their names raise and 'all' does not hold them; on, 'all' and the
-        starred name expand to `_regret_names()` / `_knn_names()`, behind everything else."""
-        has_odin = 'odin*' in self.ood_methods
-        has_regret = bool(self.OOD_REGRET_METHODS) and self.type in self.REGRET_TYPES
-        has_knn = bool(self.OOD_KNN_METHODS)
+        line), a name or a list of names.  The recorded families (score_rows.FAMILIES: `odin*` on a type whose table lists it,
+        i.e. vib; the opt-ins `regret*` and `knn*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
+        name expand to the model's own list (the plain names first, the expansions behind them in the table's order, as the
+        reference's develop_starred_methods orders them) and a single name has to be on that list.  The spline-threshold
+        ('-a-x-y') methods raise unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
+        families = score_rows.FAMILIES
+        on = {f: f.on(self) for f in families}
 
-        def unbuilt(m):
-            return ('-a-' in m and not self.OOD_QUANTILE_METHODS) or (m.startswith('odin') and not has_odin)
+        def refusal(m):                                         # why m is outside this build, or None
+            spline = '-a-' in m and not self.OOD_QUANTILE_METHODS      # the spline thresholds share ODIN's sentence
+            f = score_rows.ODIN if spline else score_rows.claimed_by(m)
+            return f.off.format(m=m, types=', '.join(self.REGRET_TYPES)) if spline or not on.get(f, True) else None
 
         def expand(names):
-            plain = [m for m in names if m not in ('odin*', 'regret*', 'knn*')]
-            return plain + (self._odin_names() if 'odin*' in names else []) + (self._regret_names() if 'regret*' in names else []) \
-                + (self._knn_names() if 'knn*' in names else [])
+            plain = [m for m in names if m not in [f.starred for f in families]]
+            return plain + [e for f in families if f.starred in names for e in getattr(self, f.names)()]
         if method == 'all':
-            skipped = [m for m in self.ood_methods if unbuilt(m)]
+            skipped = [m for m in self.ood_methods if refusal(m)]
             if skipped:
                 logging.warning('ood_detection_rates: methods outside this build are left out: %s', ', '.join(skipped))
-            return expand([m for m in self.ood_methods if not unbuilt(m)] + ['regret*'] * has_regret + ['knn*'] * has_knn)
+            built = [m for m in self.ood_methods if not refusal(m)]
+            return expand(built + [f.starred for f in families if on[f] and f.starred not in built])
         methods = [method] if isinstance(method, str) else list(method)
         for m in methods:
-            if unbuilt(m):
-                raise NotImplementedError(f'{m}: spline-threshold (-a-x-y) and ODIN OOD methods are outside this build')
-            if m.startswith('regret') and not has_regret:
-                raise NotImplementedError(f'{m}: the likelihood-regret rows are an opt-in (OOD_REGRET_METHODS) of the types '
-                                          + ', '.join(self.REGRET_TYPES))
-            if m.startswith('knn') and not has_knn:
-                raise NotImplementedError(f'{m}: the nearest-neighbour rows are an opt-in (OOD_KNN_METHODS)')
+            if refusal(m):
+                raise NotImplementedError(refusal(m))
         methods = expand(methods)
-        grid = set(self._odin_names())
+        listed = {f: getattr(self, f.names)() for f in families if on[f]}
         for m in methods:
-            if m.startswith('odin') and m not in grid:
-                raise ValueError(f'{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)')
-            if m.startswith('regret') and m not in self._regret_names():
-                raise ValueError(f'{m}: not among the (steps, lr) pairs of this model (REGRET_PARAMS)')
-            if m.startswith('knn') and m not in self._knn_names():
-                raise ValueError(f'{m}: not among the neighbour counts of this model (KNN_K)')
+            f = score_rows.claimed_by(m)
+            if f is not None and m not in listed[f]:
+                raise ValueError(f.unlisted.format(m=m))
             if '-a-' in m:
                 score_rows.roc_mode(m)
         return methods
@@ -358,53 +362,35 @@ class ScoringMixin:
         It is saved as samples-<set>.pth beside the loss record."""
         device = self.device
         name = getattr(dset, 'name', 'set')
-        recorded = recorder is not None and len(recorder) >= num_batch
-        recording = recorder is not None and not recorded
-        if recorded:
-            num_batch, batch_size = len(recorder), recorder.batch_size
-        if recording:
-            recorder.reset()
-            recorder.num_batch = num_batch
-        if recorder is not None:
-            recorder.init_seed_for_dataloader()
-        loader = None if recorded else iter(self._batch_source(dset, batch_size, shuffle))
-        buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
-        filled, sums, measures = 0, {}, None
-        odin = any(m.startswith('odin') for m in methods)
-        regret = any(m.startswith('regret-') for m in methods)
-        knn = any(m.startswith('knn-') for m in methods)
         records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
-        with torch.no_grad():
+        families = [f for f in score_rows.FAMILIES if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
+        with_mu = sample_recorder is not None or any('mu' in f.args for f in families)
+        filled, sums, measures = 0, {}, None
+        with torch.no_grad(), self._recorded_pass(dset, name, batch_size, num_batch, shuffle, recorder, sample_dirs) as (
+                recorded, recording, num_batch, batch_size, loader):
+            buf = torch.empty((len(methods), num_batch * batch_size), dtype=torch.float32, device=device)
             for i in range(num_batch):
                 if recorded:
-                    keys = [k for k in recorder.keys() if k in self.loss_components or k.startswith(('odin', 'regret-', 'knn-'))]     # cvae.py:1665-1667
+                    keys = [k for k in recorder.keys() if k in self.loss_components or score_rows.recorded_by(k)]     # cvae.py:1665-1667
                     losses = recorder.get_batch(i, *keys, force_dict=True)
                     logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
                 else:
                     x, y = next(loader)[:2]
-                    if sample_recorder is None and not knn:
-                        x, logits, losses, measures = self._evaluate_for_scores(x, i, measures)
-                    else:
-                        x, logits, losses, measures, mu = self._evaluate_for_scores(x, i, measures, with_mu=True)
+                    x, logits, losses, measures, *mu = self._evaluate_for_scores(x, i, measures, with_mu=with_mu)
                     y = y.to(device)
                     if sample_recorder is not None:
-                        sample_recorder.append_batch(**self._sample_record(sample_recorder, mu, y, losses))
-                    if odin:
-                        # cvae.py:1645-1663: the whole grid per batch (it is what the recorder holds), on the device
-                        losses = dict(losses, **self.odin_scores(x))
-                    if regret:
-                        # every pair of REGRET_PARAMS per batch, as for ODIN; the class comes from the pass above
-                        losses = dict(losses, **self.regret_scores(x, logits=logits, losses=losses))
-                    if knn:
-                        # every k of KNN_K from one call, on the posterior means of the pass above
-                        losses = dict(losses, **self.knn_scores(mu))
+                        sample_recorder.append_batch(**self._sample_record(sample_recorder, mu[0], y, losses))
+                    for f in families:
+                        # all rows of the family per batch (it is what the recorder holds), from the pass above, on the device
+                        have = {'x': x, 'logits': logits, 'losses': losses, 'mu': mu[0] if mu else None}
+                        losses = dict(losses, **getattr(self, f.scores)(**{a: have[a] for a in f.args}))
                     if recording:
                         extra = {} if logits is None else {'logits': logits.T}
                         recorder.append_batch(**losses, y_true=y, **extra)
                 n = score_rows.write_rows(records, range(len(records)), logits, losses, buf, filled, self.SCORE_SET_TORCH_ROWS,
                                           self._wim_status_word)[0].shape[0]
-                if odin or regret or knn:
-                    losses = {k: v for k, v in losses.items() if not k.startswith(('odin', 'regret-', 'knn-'))}     # test_losses: the loss components
+                if families:
+                    losses = {k: v for k, v in losses.items() if not score_rows.recorded_by(k)}     # test_losses: the loss components
                 filled += n
                 if keep_test:
                     for k, v in losses.items():                                      # cvae.py:1671, summed on the device
@@ -416,12 +402,6 @@ class ScoringMixin:
                                 zip(sums, torch.stack(list(sums.values())).tolist())} if sums else {}
             if measures:
                 self.test_measures = dict(measures)
-        if recorder is not None:
-            recorder.restore_seed()
-        if recording:
-            for d in sample_dirs:
-                os.makedirs(d, exist_ok=True)
-                recorder.save(os.path.join(d, 'record-{}.pth'.format(name)))
         if sample_recorder is not None:
             for d in sample_dirs:
                 os.makedirs(d, exist_ok=True)
@@ -544,39 +524,35 @@ class ScoringMixin:
                 entry[m] = {'n': ind.shape[1], 'epochs': epoch, 'mean': mean, 'std:': std}
 
         kept = torch.tensor(self.OOD_KEPT_TPR, dtype=torch.float64, device=ind.device)
-        K = len(self.OOD_KEPT_TPR)
         with_pr = bool(self.DETECTION_PR_METRICS)
         for oodset, name in zip(oodsets, names[1:]):
             last = {}
 
             def roc(scores):
-                """ONE device ROC for all methods, ONE copy of its (M, 4K + 4) results to the host."""
-                r = ops.roc_curve(ind, scores.contiguous(), kept, modes)
-                # with DETECTION_PR_METRICS: ONE ops.pr_metrics call, its (M, 5) figures in the same copy (the status word of
-                # the ROC above flags the same rows)
-                pr = [torch.stack([p[k] for k in ops.PR_FIGURES], 1) for p in
-                      ([ops.pr_metrics(ind, scores.contiguous(), modes)] if with_pr else [])]
-                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['status'].double()[:, None], *pr,
-                                  self._row_mean_std(scores)], 1).cpu().numpy()
-                ops.roc_check_status(host[:, 1 + 4 * K].astype(np.int64))
-                last['host'] = host
-                return host[:, -2].tolist()
+                """ONE device ROC for all methods, ONE copy of its results to the host."""
+                fields = dict(ops.roc_curve(ind, scores.contiguous(), kept, modes), mean_std=self._row_mean_std(scores))
+                if with_pr:        # ONE ops.pr_metrics call, its (M, 5) figures in the same copy (the ROC's status word flags the same rows)
+                    p = ops.pr_metrics(ind, scores.contiguous(), modes)
+                    fields['pr'] = torch.stack([p[k] for k in ops.PR_FIGURES], 1)
+                host = last['host'] = ops.read_back(fields)
+                ops.roc_check_status(host['status'].astype(np.int64))
+                return host['mean_std'][:, 0].tolist()
 
             def fpr95():
-                return {m: float(h[1 + 5]) for m, h in zip(methods, last['host'])}      # fpr_at_tpr(..., 0.95): slot 5 of the kept TPRs
+                return {m: float(f[5]) for m, f in zip(methods, last['host']['fpr'])}      # fpr_at_tpr(..., 0.95): slot 5 of the kept TPRs
 
             nb, shuffle = plan(oodset)
             scores = self._score_set(oodset, methods, batch_size, nb, shuffle, recorders.get(name), sample_dirs,
                                      sample_recorder=sample_recorders.get(name), on_batch=progress_line(name, roc, fpr95))
             if sink is None:                                  # with a sink the last batch's progress ROC is the final one
                 roc(scores)
-            for m, h in zip(methods, last['host']):
-                fpr, low, up = h[1:1 + K], h[1 + 2 * K:1 + 3 * K], h[1 + 3 * K:1 + 4 * K]
-                ood_results[name][m] = {'epochs': epoch, 'n': scores.shape[1], 'mean': float(h[-2]), 'std': float(h[-1]),
-                                        'auc': float(h[0]), 'tpr': list(self.OOD_KEPT_TPR), 'fpr': [float(f) for f in fpr],
+            keys = ('auc', 'fpr', 'low', 'up', 'mean_std') + ('pr',) * with_pr
+            for m, auc, fpr, low, up, (mean, std), *pr in zip(methods, *(last['host'][k] for k in keys)):
+                ood_results[name][m] = {'epochs': epoch, 'n': scores.shape[1], 'mean': float(mean), 'std': float(std),
+                                        'auc': float(auc), 'tpr': list(self.OOD_KEPT_TPR), 'fpr': [float(f) for f in fpr],
                                         'thresholds': [[float(a), float(b)] for a, b in zip(low, up)]}
                 if with_pr and '-a-' not in m:                # a quantile row has no scalar score: no figures
-                    ood_results[name][m].update(zip(ops.PR_FIGURES, (float(f) for f in h[2 + 4 * K:7 + 4 * K])))
+                    ood_results[name][m].update(zip(ops.PR_FIGURES, (float(f) for f in pr[0])))
                 if update_self_ood:
                     self.ood_results.setdefault(epoch, {}).setdefault(name, {})[m] = ood_results[name][m]
         if was_training:
@@ -587,7 +563,7 @@ class ScoringMixin:
     def _starred(self, names):
         """develop_starred_methods (utils/save_load/dictify.py:198-212) on a copy: the plain names in their order, then what
         each starred name expands to; a starred name without an entry in `methods_params` (softiws*) expands to nothing."""
-        grids = dict(self.methods_params, odin=self._odin_names())
+        grids = dict(self.methods_params, **{score_rows.ODIN.prefix: self._odin_names()})
         plain = [m for m in names if not m.endswith('*')]
         return plain + [e for m in names if m.endswith('*') for e in grids.get(m[:-1], [])]
 
@@ -672,7 +648,7 @@ class ScoringMixin:
         logits_cn, y = tensors.pop('logits', None), tensors.pop('y_true')
         logits = None if logits_cn is None else logits_cn.T
         sources = dict(tensors, logits=logits)
-        n, K = y.shape[0], len(self.OOD_KEPT_TPR)
+        n = y.shape[0]
         rows_of = {m: score_rows.parse(m, score_rows.traits_of(self), misclass=True) for m in chosen['miss']}
         methods = [m for m in chosen['miss'] if sources.get(rows_of[m].source) is not None]
         skipped = [m for m in chosen['miss'] if m not in methods]
@@ -700,17 +676,14 @@ class ScoringMixin:
                     continue
                 n_correct = r['n_correct']
                 acc = n_correct / n
-                host = torch.cat([r['auc'][:, None], r['fpr'], r['tpr'], r['low'], r['up'], r['tp'].double(), r['fp'].double(),
-                                  *([r['pr']] if with_pr else []), r['status'].double()[:, None]], 1).cpu().numpy()
+                host = ops.read_back({k: r[k] for k in ('auc', 'fpr', 'tpr', 'tp', 'fp', 'status') + ('pr',) * with_pr})
                 logging.debug('Acc. for method %s: (%5.2f) ****', pm, 100 * acc)
                 results[pm] = {}
                 best = (None, 0.)
-                for m, h in zip(methods, host):
-                    if int(h[-1]):
+                for m, auc, fpr, tpr, tp, fp, status, *pr in zip(methods, *host.values()):
+                    if int(status):
                         logging.warning('misclassification_detection_rates: %s-%s skipped: NaN score', pm, m)
                         continue
-                    fpr, tpr = h[1:1 + K], h[1 + K:1 + 2 * K]
-                    tp, fp = h[1 + 4 * K:1 + 5 * K], h[1 + 5 * K:1 + 6 * K]
                     with np.errstate(invalid='ignore', divide='ignore'):
                         precision = tp / (tp + fp)                          # 0 / 0 = NaN, as numpy gives the reference
                     at = np.where(tpr >= shown_tpr)[0]                      # fpr_at_tpr (utils/roc_curves.py:8-27)
@@ -724,9 +697,9 @@ class ScoringMixin:
                     if sink is not None:
                         sink.write(line + '\n')
                     entry = {'n': n, 'epochs': epoch, 'sampling': sampling, 'tpr': [float(t) for t in tpr],
-                             'fpr': [float(f) for f in fpr], 'auc': float(h[0]), 'precision': [float(p) for p in precision]}
+                             'fpr': [float(f) for f in fpr], 'auc': float(auc), 'precision': [float(p) for p in precision]}
                     if with_pr:
-                        entry.update(zip(self.MISCLASS_PR_KEYS, (float(f) for f in h[1 + 6 * K:6 + 6 * K])))
+                        entry.update(zip(self.MISCLASS_PR_KEYS, (float(f) for f in pr[0])))
                     results[pm][m] = entry
                     n_already = self.testing.get(epoch, {}).get(pm, {}).get(m, {'n': 0})['n']
                     if update_self_results and n >= n_already:

@@ -329,6 +329,42 @@ def test_rates(monkeypatch):
         del net.OOD_KNN_METHODS
 
 
+def test_two_families_in_one_pass(monkeypatch):
+    """`regret*` and `knn*` together: each family's rows are those of a pass with that family alone, the per-batch calls run in
+    the order evaluate, regret_scores, knn_scores, and a full recorder is read back without any of them."""
+    net, train, bank = fitted()
+    sets = [synth(40, 'ind', 1), synth(40, 'ood', 2, .3)]
+    call = dict(oodsets=sets[1:], testset=sets[0], batch_size=16, update_self_ood=False)
+    net.KNN_K, net.REGRET_PARAMS, net.OOD_KNN_METHODS, net.OOD_REGRET_METHODS = (1, 3), [(2, 0.05)], True, True
+    try:
+        knn, regret = net._knn_names(), net._regret_names()
+        assert knn == ['knn-1', 'knn-3'] and regret == ['regret-2-0.0500']
+        def rates(method, recorders):
+            np.random.seed(28)                     # a new recorder takes its seed, and with it the noise of its pass, from numpy
+            return net.ood_detection_rates(method=method, recorders=recorders, **call)
+        alone = {m: rates(['elbo', m], {}) for m in ('knn*', 'regret*')}
+        calls = []
+        for name in ('evaluate', 'regret_scores', 'knn_scores'):
+            real = getattr(net, name)
+            monkeypatch.setattr(net, name, lambda *a, _real=real, _tag=name[0], **k: calls.append(_tag) or _real(*a, **k))
+        recorders = {}
+        both = rates(['elbo', 'regret*', 'knn*'], recorders)
+        assert list(both['ood']) == ['elbo'] + regret + knn
+        for m in knn:
+            assert both['ood'][m] == alone['knn*']['ood'][m], m
+        for m in regret:
+            assert both['ood'][m] == alone['regret*']['ood'][m], m
+        print('calls of the pass', ''.join(calls))
+        assert calls == ['e', 'r', 'k'] * 6                                             # 3 batches of 2 sets, once each, in order
+        assert all(m in recorders[s.name].keys() for s in sets for m in regret + knn)
+        assert net.test_losses and not any(k.startswith(('knn', 'regret')) for k in net.test_losses)
+        del calls[:]
+        again = net.ood_detection_rates(method=['elbo', 'regret*', 'knn*'], recorders=recorders, **call)
+        assert not calls and again == both                                              # full recorders: nothing is evaluated
+    finally:
+        del net.KNN_K, net.REGRET_PARAMS, net.OOD_KNN_METHODS, net.OOD_REGRET_METHODS
+
+
 def test_bank_file_round_trip(tmp_path):
     net, train, bank = fitted()
     path = net.save_latent_bank(str(tmp_path))

@@ -936,6 +936,32 @@ size_t jvae_knn_workspace_bytes(long N, long M, int K, int k, int splits);
 int jvae_knn_f32(const float* q, const float* q_sq, const float* bank, const float* bank_sq, float* d2_out, int* idx_out, long N,
                  long M, int K, int k, int normalized, int splits, int* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Mahalanobis scores against Gaussians fitted on a bank (csrc/maha.hip; Lee et al. 2018, the relative form of Ren et al. 2021;
+ * no counterpart in the reference) -------------------------------------------------------------------------------------------
+ * None of the entry points allocates or synchronises.  No floating-point atomics: same inputs, same bits, run to run.
+ * Moments: bank (M, K) fp32, labels (M,) int64 -> counts (C,) int64, means (C, K), mean0 (K,), Sw (K, K) and St (K, K) fp64:
+ * the class sizes and means, the overall mean, and the scatter of the rows about the mean of their class (Sw) and about mean0
+ * (St), each divided by the number of rows summed.  All sums are fp64 in a fixed order that hangs on M alone; Sw and St are
+ * symmetric to the bit.  A row whose label is outside [0, C) sets bit 0 of *status, a row with a non-finite element bit 1; such
+ * a row is in no sum and in no count.  An empty class has a mean of zeros.  ws: device scratch of
+ * jvae_maha_moments_workspace_bytes(M, K, C) bytes, 8-byte aligned (-3 when smaller).  1 <= K <= 256, 1 <= C <= 128,
+ * 1 <= M < 2^31, else -2 (a size below 1, a missing pointer: -1) and a workspace size of 0.
+ * Scores: q (N, K) fp32; mu0 (K,) fp32; W (2K, K) fp32, the whitening matrix of Sw stacked on that of St; m (Cn, K) fp32, the
+ * whitened, mu0-centred means of the Cn non-empty classes in ascending label order; m0 (K,) fp32, the overall mean treated the
+ * same way (the whitened rounding error of mu0); cmap (Cn,) int32, the classes' labels in [0, C).
+ * With x = q - mu0, y = W x (each y_k one fmaf chain over j ascending: the fp32 matrix instruction), d_c = sum_k (y_k - m_ck)^2
+ * for k < K and d0 = sum_k (y_(K + k) - m0_k)^2 (fmaf chains over k ascending):
+ *   d (N,) = min_c d_c, cls (N,) int32 = the label of the first class that attains it, rel (N,) = d - d0,
+ *   per_class (N, C) or NULL: d_c in the column of its label, +inf in the column of an empty class.
+ * A query row with a non-finite element gets NaN, -1, NaN (and NaN in all of per_class) and sets bit 2 of *status.  The word is
+ * only ever OR-ed into: the caller owns and clears it.  ONE launch; neither y nor the (N, Cn) distances reach memory unless
+ * per_class is given.  1 <= K <= 256, 1 <= Cn <= C <= 128, N < 2^31.  N = 0 launches nothing. */
+size_t jvae_maha_moments_workspace_bytes(long M, int K, int C);
+int jvae_maha_moments_f32(const float* bank, const long long* labels, long M, int K, int C, long long* counts, double* means,
+                          double* mean0, double* Sw, double* St, int* status, void* ws, size_t ws_bytes, void* stream);
+int jvae_maha_scores_f32(const float* q, const float* mu0, const float* W, const float* m, const float* m0, const int* cmap,
+                         float* d, int* cls, float* rel, float* per_class, long N, int K, int Cn, int C, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

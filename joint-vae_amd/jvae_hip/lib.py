@@ -190,6 +190,9 @@ _SIGS = {
     'jvae_knn_sqnorms_f32': (c_int, [P, P, c_long, c_int, P]),
     'jvae_knn_workspace_bytes': (c_size_t, [c_long, c_long, c_int, c_int, c_int]),
     'jvae_knn_f32': (c_int, [P] * 6 + [c_long, c_long, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
+    'jvae_maha_moments_workspace_bytes': (c_size_t, [c_long, c_int, c_int]),
+    'jvae_maha_moments_f32': (c_int, [P, P, c_long, c_int, c_int] + [P] * 6 + [P, c_size_t, P]),
+    'jvae_maha_scores_f32': (c_int, [P] * 10 + [c_long, c_int, c_int, c_int, P, P]),
 }
 
 

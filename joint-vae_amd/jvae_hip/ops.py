@@ -2389,6 +2389,198 @@ def knn_check_status(status=None):
             raise ValueError('knn: a bank row at a non-finite distance was met (it is in no list)')
 
 
+# ------------------------------------------------------------ Mahalanobis scores over a latent bank (csrc/maha.hip)
+MAHA_MAX_DIM = 256          # columns of the rows
+MAHA_STATUS_LABEL = 1       # a bank row with a label outside [0, C) was met (it is in no sum)
+MAHA_STATUS_BANK = 2        # a bank row with a non-finite element was met (it is in no sum)
+MAHA_STATUS_QUERY = 4       # a query row with a non-finite element was met (its scores are NaN, its class -1)
+MAHA_FIT_KEYS = ('counts', 'means', 'mean0', 'W', 'W0', 'mu0_32', 'W32', 'm32', 'm0_32', 'cmap', 'shrinkage')
+_maha_status = {}
+
+
+def maha_status(device):
+    """The per-device status word of `maha_moments` / `maha_scores` calls made without one of their own (created cleared)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _maha_status:
+        _maha_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _maha_status[idx]
+
+
+def _maha_word(status, dev, what):
+    if status is None:
+        status = maha_status(dev)
+    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise L.JvaeHipError(f'{what}: an int32 status word on the device of the rows expected')
+    return status
+
+
+def maha_moments(bank, labels, num_classes, status=None):
+    """bank (M, K) fp32 and labels (M,) int64 on one device -> {'counts' (C,) int64, 'means' (C, K), 'mean0' (K,), 'Sw' (K, K),
+    'St' (K, K) fp64}: the class sizes and means, the overall mean, Sw = sum_i (b_i - means[y_i]) (b_i - means[y_i])^T / M and St,
+    the same about mean0.  Every sum is fp64 in a fixed order that hangs on M alone, without floating-point atomics: a second call
+    returns the same bits; Sw and St are symmetric to the bit.  A row with a label outside [0, C) sets MAHA_STATUS_LABEL in the
+    device word `status` (default `maha_status(device)`), a row with a non-finite element MAHA_STATUS_BANK; such a row is in no
+    sum and in no count, and the divisor M is the number of rows kept.  An empty class has a mean of zeros.
+    1 <= K <= MAHA_MAX_DIM, 1 <= C <= MISCLASS_MAX_CLASSES, 1 <= M < 2^31, refused here before any launch.  Nothing is
+    synchronised (csrc/maha.hip)."""
+    if not torch.is_tensor(bank) or not torch.is_tensor(labels) or bank.dim() != 2 or tuple(labels.shape) != (bank.shape[0],):
+        raise L.JvaeHipError('maha_moments: bank (M, K) and labels (M,) expected')
+    if labels.dtype != torch.int64:
+        raise L.JvaeHipError(f'maha_moments: int64 labels expected, got {labels.dtype}')
+    bank = _c(_f32(bank, 'maha_moments'))
+    (M, K), C = bank.shape, int(num_classes)
+    if not 1 <= K <= MAHA_MAX_DIM or not 1 <= C <= MISCLASS_MAX_CLASSES or not 1 <= M < 1 << 31:
+        raise L.JvaeHipError(f'maha_moments: 1 <= K <= {MAHA_MAX_DIM}, 1 <= C <= {MISCLASS_MAX_CLASSES} and 1 <= M < 2^31 expected, '
+                             f'got K={K}, C={C}, M={M} (unsupported configuration)')
+    L.ptr(bank), L.ptr(labels)
+    dev = bank.device
+    if labels.device != dev:
+        raise L.JvaeHipError('maha_moments: bank and labels on one device expected')
+    status = _maha_word(status, dev, 'maha_moments')
+    out = {'counts': torch.empty(C, dtype=torch.int64, device=dev), 'means': torch.empty((C, K), dtype=torch.float64, device=dev),
+           'mean0': torch.empty(K, dtype=torch.float64, device=dev), 'Sw': torch.empty((K, K), dtype=torch.float64, device=dev),
+           'St': torch.empty((K, K), dtype=torch.float64, device=dev)}
+    lib = L.load()
+    nbytes = lib.jvae_maha_moments_workspace_bytes(M, K, C)
+    ws = L.workspace(nbytes + 8, dev)
+    off = (-ws.data_ptr()) % 8
+    L.check(lib.jvae_maha_moments_f32(L.ptr(bank), L.ptr(_c(labels)), M, K, C, *(L.ptr(out[k]) for k in out), L.ptr(status),
+                                      ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()), 'jvae_maha_moments_f32')
+    return out
+
+
+def _maha_whitener(S, shrinkage, what):
+    """fp64 numpy: L^-1 (lower triangular) of the Cholesky factor L of S + shrinkage * (trace S / K) * I."""
+    import numpy as np
+    K = S.shape[0]
+    A = S + shrinkage * (np.trace(S) / K) * np.eye(K)
+    refusal = (f'maha_fit: {what} is not positive definite (fewer independent rows than dimensions, or a constant dimension): '
+               f'a larger `shrinkage` is needed (now {shrinkage})')
+    if not np.all(np.isfinite(A)):
+        raise ValueError(refusal)
+    try:
+        chol = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        raise ValueError(refusal) from None
+    # a pivot at the rounding level of the matrix: positive by accident
+    if np.min(np.diag(chol)) ** 2 <= K * 2. ** -52 * np.max(np.diag(A)):
+        raise ValueError(refusal)
+    return np.tril(np.linalg.inv(chol))
+
+
+def maha_fit(moments, shrinkage=0., device=None):
+    """The Gaussians of `maha_moments`' result (device or host tensors, or numpy arrays), factored on the host in numpy fp64 -
+    once per fit, as the eigenvectors of `pca_moments`' covariance are: for Sw and for St, S + shrinkage * (trace S / K) * I =
+    L L^T and W = L^-1 (`W`, `W0`, lower triangular).  -> the fit of `maha_scores`, on `device` (default: the moments' own):
+    'counts' int64, 'means', 'mean0', 'W', 'W0' fp64, and the operands rounded ONCE to fp32: 'mu0_32' = fp32(mean0), 'W32' (2K, K)
+    = W stacked on W0, 'm32' (Cn, K) = fp32(W (means[c] - mu0_32)) for the Cn non-empty classes in ascending label order, 'm0_32'
+    (K,) = fp32(W0 (mean0 - mu0_32)), the whitened rounding error of mu0_32, 'cmap' (Cn,) int32 the classes' labels; 'shrinkage'.  ValueError, naming `shrinkage`, for a matrix that is not positive definite."""
+    import numpy as np
+    if device is None:
+        device = next((v.device for v in moments.values() if torch.is_tensor(v)), torch.device('cpu'))
+    tensors = {k: torch.as_tensor(moments[k]) for k in ('counts', 'means', 'mean0', 'Sw', 'St')}
+    if tensors['means'].dim() != 2 or any(tensors[k].dtype != torch.float64 for k in ('means', 'mean0', 'Sw', 'St')) \
+            or tensors['counts'].dtype != torch.int64:
+        raise L.JvaeHipError('maha_fit: the result of maha_moments expected (counts int64; means, mean0, Sw, St fp64)')
+    C, K = tensors['means'].shape
+    if tuple(tensors['counts'].shape) != (C,) or tuple(tensors['mean0'].shape) != (K,) \
+            or any(tuple(tensors[k].shape) != (K, K) for k in ('Sw', 'St')):
+        raise L.JvaeHipError('maha_fit: counts (C,), means (C, K), mean0 (K,), Sw and St (K, K) expected')
+    shrinkage = float(shrinkage)
+    if not shrinkage >= 0.:
+        raise ValueError(f'maha_fit: a shrinkage >= 0 expected, got {shrinkage}')
+    host = read_back(tensors)                                       # ONE copy; the counts are exact in fp64
+    counts = host['counts'].astype(np.int64)
+    kept = np.flatnonzero(counts > 0)
+    if not kept.size:
+        raise ValueError('maha_fit: no row was kept, every class is empty')
+    W = _maha_whitener(host['Sw'], shrinkage, 'the within-class scatter Sw')
+    W0 = _maha_whitener(host['St'], shrinkage, 'the total scatter St')
+    mu0_32 = host['mean0'].astype(np.float32)
+    m = (host['means'][kept] - mu0_32.astype(np.float64)) @ W.T
+    m0 = W0 @ (host['mean0'] - mu0_32.astype(np.float64))
+
+    def put(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return {'counts': put(counts), 'means': put(host['means']), 'mean0': put(host['mean0']), 'W': put(W), 'W0': put(W0),
+            'mu0_32': put(mu0_32), 'W32': put(np.concatenate([W, W0]).astype(np.float32)), 'm32': put(m.astype(np.float32)),
+            'm0_32': put(m0.astype(np.float32)), 'cmap': put(kept.astype(np.int32)), 'shrinkage': shrinkage}
+
+
+def maha_check_fit(fit, what='maha_scores'):
+    """Keys, dtypes and shapes of a fit of `maha_fit` -> (K, Cn, C); ValueError otherwise."""
+    def bad(why):
+        return ValueError(f'{what}: not a fit of maha_fit ({why})')
+    if not isinstance(fit, dict) or not set(MAHA_FIT_KEYS) <= set(fit):
+        raise bad('keys ' + ', '.join(MAHA_FIT_KEYS) + ' expected')
+    dtypes = {'counts': torch.int64, 'means': torch.float64, 'mean0': torch.float64, 'W': torch.float64, 'W0': torch.float64,
+              'mu0_32': torch.float32, 'W32': torch.float32, 'm32': torch.float32, 'm0_32': torch.float32, 'cmap': torch.int32}
+    for k, dt in dtypes.items():
+        if not torch.is_tensor(fit[k]) or fit[k].dtype != dt:
+            raise bad(f'{k}: a {dt} tensor expected')
+    if fit['means'].dim() != 2 or fit['m32'].dim() != 2:
+        raise bad('means (C, K) and m32 (Cn, K) expected')
+    (C, K), Cn = fit['means'].shape, fit['m32'].shape[0]
+    shapes = {'counts': (C,), 'mean0': (K,), 'W': (K, K), 'W0': (K, K), 'mu0_32': (K,), 'W32': (2 * K, K), 'm32': (Cn, K), 'm0_32': (K,),
+              'cmap': (Cn,)}
+    for k, shape in shapes.items():
+        if tuple(fit[k].shape) != shape:
+            raise bad(f'{k}: {shape} expected, got {tuple(fit[k].shape)}')
+    if not 1 <= K <= MAHA_MAX_DIM or not 1 <= Cn <= C <= MISCLASS_MAX_CLASSES:
+        raise bad(f'1 <= K <= {MAHA_MAX_DIM} and 1 <= non-empty classes <= C <= {MISCLASS_MAX_CLASSES} expected')
+    if not isinstance(fit['shrinkage'], float):
+        raise bad('shrinkage: a float expected')
+    return K, Cn, C
+
+
+def maha_scores(q, fit, per_class=False, status=None):
+    """q (N, K) fp32 against the fit of `maha_fit` -> (d (N,) fp32, cls (N,) int32, rel (N,) fp32[, per_class (N, C) fp32]):
+    with x = q - mu0_32 and y = W32 x (ONE product against the stacked matrix on the fp32 matrix cores, every y_k the fmaf chain
+    over j ascending), d_c = sum_k (y_k - m_ck)^2 and d0 = sum_k (y0_k - m0_k)^2 as fmaf chains over k ascending; d = min_c d_c over the
+    non-empty classes, cls the label that attains it (the lower one of a tie), rel = min_c (d_c - d0) - the relative distance of
+    Ren et al. 2021.  per_class: also d_c for every label, +inf in the column of an empty class.  A query row with a non-finite
+    element gets NaN / -1 and sets MAHA_STATUS_QUERY in `status` (default `maha_status(device)`; `maha_check_status`).
+    N = 0 returns empties without a launch.  ONE launch; neither y nor the (N, C) distances are written to memory unless
+    `per_class` asks for them.  Nothing is synchronised."""
+    K, Cn, C = maha_check_fit(fit)
+    if not torch.is_tensor(q) or q.dim() != 2 or q.shape[1] != K:
+        raise L.JvaeHipError(f'maha_scores: q (N, {K}) expected, got {tuple(q.shape) if torch.is_tensor(q) else type(q)}')
+    q = _c(_f32(q, 'maha_scores'))
+    N = q.shape[0]
+    if N >= 1 << 31:
+        raise L.JvaeHipError(f'maha_scores: N < 2^31 expected, got {N} (unsupported configuration)')
+    L.ptr(q)
+    dev = q.device
+    ops_ = [fit[k] for k in ('mu0_32', 'W32', 'm32', 'm0_32', 'cmap')]
+    if any(t.device != dev for t in ops_):
+        raise L.JvaeHipError('maha_scores: the fit on the device of the rows expected')
+    d = torch.empty(N, dtype=torch.float32, device=dev)
+    cls = torch.empty(N, dtype=torch.int32, device=dev)
+    rel = torch.empty(N, dtype=torch.float32, device=dev)
+    pc = torch.empty((N, C), dtype=torch.float32, device=dev) if per_class else None
+    if N:
+        status = _maha_word(status, dev, 'maha_scores')
+        L.check(L.load().jvae_maha_scores_f32(L.ptr(q), *(L.ptr(_c(t)) for t in ops_), L.ptr(d), L.ptr(cls), L.ptr(rel), L.ptr(pc),
+                                              N, K, Cn, C, L.ptr(status), L.stream_ptr()), 'jvae_maha_scores_f32')
+    return (d, cls, rel, pc) if per_class else (d, cls, rel)
+
+
+def maha_check_status(status=None):
+    """Raise ValueError for what `maha_moments` / `maha_scores` flagged.  status: the word given to the op (a device tensor: read
+    here - this is the synchronisation - and cleared), a host value, or None for the per-device default words."""
+    words = list(_maha_status.values()) if status is None else [status]
+    for w in words:
+        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
+        if torch.is_tensor(w) and v:
+            w.zero_()
+        if v & MAHA_STATUS_QUERY:
+            raise ValueError('maha: a query row with a non-finite element was met (its scores are NaN, its class -1)')
+        if v & MAHA_STATUS_LABEL:
+            raise ValueError('maha: a bank row with a label outside [0, num_classes) was met (it is in no sum)')
+        if v & MAHA_STATUS_BANK:
+            raise ValueError('maha: a bank row with a non-finite element was met (it is in no sum)')
+
+
 # ------------------------------------------------------------ 2-D projections: exact t-SNE and PCA (csrc/embed.hip)
 EMBED_MAX_N = 16384         # points of a t-SNE: a row of fp32 distances in LDS
 EMBED_MAX_K = 1024          # dimensions of the points

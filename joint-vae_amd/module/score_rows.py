@@ -13,10 +13,10 @@ import torch
 from jvae_hip import ops
 
 # what the form of a row depends on besides its name
-# (OOD_REGRET_METHODS, OOD_KNN_METHODS: the model's opt-in switches of the recorded `regret-*` / `knn-*` rows; off where a caller
-# does not say)
-Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is_jvae num_labels OOD_REGRET_METHODS OOD_KNN_METHODS',
-                    defaults=(False, False))
+# (OOD_REGRET_METHODS, OOD_KNN_METHODS, OOD_MAHA_METHODS: the model's opt-in switches of the recorded `regret-*` / `knn-*` / `maha*`
+# rows; off where a caller does not say)
+Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is_jvae num_labels OOD_REGRET_METHODS OOD_KNN_METHODS '
+                    'OOD_MAHA_METHODS', defaults=(False, False, False))
 
 
 # One family of RECORDED score rows: a model method computes them once per batch, the pass records them with the losses, reads
@@ -42,7 +42,11 @@ FAMILIES = (
     Family('knn', lambda m: m.startswith('knn-') and m[4:].isdigit(), 'knn*',
            lambda model: bool(model.OOD_KNN_METHODS), lambda t: t.OOD_KNN_METHODS, '_knn_names', 'knn_scores', ('mu',),
            '{m}: the nearest-neighbour rows are an opt-in (OOD_KNN_METHODS)',
-           '{m}: not among the neighbour counts of this model (KNN_K)'))
+           '{m}: not among the neighbour counts of this model (KNN_K)'),
+    Family('maha', lambda m: m in ('maha', 'maha-rel'), 'maha*',
+           lambda model: bool(model.OOD_MAHA_METHODS), lambda t: t.OOD_MAHA_METHODS, '_maha_names', 'maha_scores', ('mu',),
+           '{m}: the Mahalanobis rows are an opt-in (OOD_MAHA_METHODS)',
+           '{m}: not among the Mahalanobis rows of this model (`maha`; `maha-rel` with more than one fitted class)'))
 ODIN = FAMILIES[0]
 odin_name = (ODIN.prefix + '-{:.0f}-{:.4f}').format            # (T, eps) -> `odin-T-eps` as the reference formats it (cvae.py:124-127)
 
@@ -126,7 +130,7 @@ def _wim_entry(m):
 class Row:
     """One score row.  base: the name without the '-2s' / '-a-x-y' suffix, which only names the thresholding done downstream
     (`roc_mode`); source: the key of the losses the row reads, `logits`, or the name itself for a recorded `odin-*` / `regret-*` /
-    `knn-*` row; kind,
+    `knn-*` / `maha*` row; kind,
     const: its row of ops.misclass_scores (temperature or additive constant) or of ops.wim_scores (the family's factor), kind
     None where there is no kernel row."""
     name: str

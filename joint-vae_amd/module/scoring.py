@@ -307,6 +307,67 @@ class ScoringMixin:
         d2, _ = ops.knn(mu.float(), bank['bank'], bank['sq'], max(ks), normalized=bool(self.KNN_NORMALIZE))
         return {name: -d2[:, k - 1].sqrt() for name, k in zip(self._knn_names(), ks)}
 
+    # The Mahalanobis rows `maha` and `maha-rel` (Lee et al. 2018; Ren et al. 2021): minus the squared
+    # Mahalanobis distance from a sample's posterior mean to the nearest of the class Gaussians - one per class of the bank, with
+    # one shared covariance - that `fit_latent_gaussians` fits on the latent bank, and the same minus the distance under ONE
+    # Gaussian for the whole bank.  `zdist` is the distance to the centroids the prior learned; this is the distance to the
+    # Gaussians the encoder produces on the training set.  Off by default: every name raises, 'all' is the reference's table.
+    # On (class or instance): 'all' and 'maha*' expand to `_maha_names()`.  Fitting is the caller's job.
+    OOD_MAHA_METHODS = False
+    latent_gaussians = None                                                   # ops.maha_fit's dictionary and 'set'
+    LATENT_GAUSSIANS_FILE = 'latent-gaussians.pth'
+
+    def _maha_names(self):
+        """`maha` and `maha-rel`; `maha` alone once Gaussians with a single non-empty class are fitted (`maha-rel` is then 0)."""
+        g = self.latent_gaussians
+        return ['maha'] if g is not None and g['cmap'].shape[0] < 2 else ['maha', 'maha-rel']
+
+    def fit_latent_gaussians(self, shrinkage=0.0):
+        """Fit `latent_gaussians` on `latent_bank`: the moments of the bank by class on the device in fp64 (ops.maha_moments),
+        then the two factorisations on the host (ops.maha_fit; `shrinkage` * the mean variance is added to both diagonals,
+        ValueError naming it when a matrix is not positive definite).  -> the dictionary: ops.maha_fit's - counts, means, mean0,
+        the fp64 factors W and W0, the fp32 operands, the class map, the shrinkage - and 'set', the bank's set name.  ValueError
+        without a bank, with a bank of fewer than two rows, and for a bank row with a label outside the model's classes or a
+        non-finite element.  This call synchronises; scoring does not."""
+        bank = self.latent_bank
+        if bank is None:
+            raise ValueError('fit_latent_gaussians: no latent bank is fitted (fit_latent_bank or load_latent_bank)')
+        if bank['bank'].shape[0] < 2:
+            raise ValueError(f"fit_latent_gaussians: the bank holds {bank['bank'].shape[0]} rows, at least two are needed")
+        status = torch.zeros(1, dtype=torch.int32, device=bank['bank'].device)
+        moments = ops.maha_moments(bank['bank'], bank['labels'], self.num_labels, status=status)
+        ops.maha_check_status(status)
+        self.latent_gaussians = dict(ops.maha_fit(moments, shrinkage), set=bank['set'])
+        return self.latent_gaussians
+
+    def save_latent_gaussians(self, dir_name):
+        """Write the fitted Gaussians as `latent-gaussians.pth` into `dir_name` (a file of its own: save() / load() do not know it)."""
+        if self.latent_gaussians is None:
+            raise ValueError('save_latent_gaussians: no Gaussians are fitted (fit_latent_gaussians)')
+        os.makedirs(dir_name, exist_ok=True)
+        path = os.path.join(dir_name, self.LATENT_GAUSSIANS_FILE)
+        torch.save({k: v.cpu() if torch.is_tensor(v) else v for k, v in self.latent_gaussians.items()}, path)
+        return path
+
+    def load_latent_gaussians(self, dir_name):
+        """Read `latent-gaussians.pth` of `dir_name` onto the model's device -> the dictionary, bit for bit what was saved."""
+        d = torch.load(os.path.join(dir_name, self.LATENT_GAUSSIANS_FILE), map_location='cpu')
+        if not isinstance(d, dict) or set(d) != set(ops.MAHA_FIT_KEYS) | {'set'}:
+            raise ValueError(f'load_latent_gaussians: {dir_name} does not hold latent Gaussians')
+        ops.maha_check_fit(d, 'load_latent_gaussians')
+        self.latent_gaussians = {k: v.to(self.device).contiguous() if torch.is_tensor(v) else v for k, v in d.items()}
+        return self.latent_gaussians
+
+    def maha_scores(self, mu):
+        """The Mahalanobis rows of a batch of posterior means mu (N, K): {'maha': -d, 'maha-rel': -rel}, (N,) fp32 device tensors,
+        higher = more in-distribution, from ONE `ops.maha_scores` call (d: the squared distance to the nearest class Gaussian,
+        rel: d minus the squared distance under the Gaussian of the whole bank); `maha` alone when a single class is fitted.
+        ValueError without fitted Gaussians.  A non-finite row sets the device's `ops.maha_status` word (`ops.maha_check_status`)."""
+        if self.latent_gaussians is None:
+            raise ValueError('maha_scores: no latent Gaussians are fitted (fit_latent_gaussians or load_latent_gaussians)')
+        d, _, rel = ops.maha_scores(mu.float(), self.latent_gaussians)
+        return {name: -v for name, v in zip(self._maha_names(), (d, rel))}
+
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
         return [score_rows.odin_name(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
@@ -314,7 +375,7 @@ class ScoringMixin:
     def _ood_methods(self, method):
         """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
         line), a name or a list of names.  The recorded families (score_rows.FAMILIES: `odin*` on a type whose table lists it,
-        i.e. vib; the opt-ins `regret*` and `knn*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
+        i.e. vib; the opt-ins `regret*`, `knn*` and `maha*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
         name expand to the model's own list (the plain names first, the expansions behind them in the table's order, as the
         reference's develop_starred_methods orders them) and a single name has to be on that list.  The spline-threshold
         ('-a-x-y') methods raise unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""

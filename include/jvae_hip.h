@@ -962,6 +962,25 @@ int jvae_maha_moments_f32(const float* bank, const long long* labels, long M, in
 int jvae_maha_scores_f32(const float* q, const float* mu0, const float* W, const float* m, const float* m0, const int* cmap,
                          float* d, int* cls, float* rel, float* per_class, long N, int K, int Cn, int C, int* status, void* stream);
 
+/* ---- Input complexity: the length of a lossless image code (csrc/ic.hip; Serra et al. 2020; no counterpart in the reference) ----
+ * x (N, C, H, W) fp32 -> bits (N,) fp64, bits32 (N,) fp32 = (float)bits, choice (N,) int32.  Nothing is encoded: the exact
+ * length of an achievable code is computed, in ONE launch, one workgroup per image; nothing is allocated or synchronised.
+ * q = clamp(rint(255 x), 0, 255).  Planes: the channels; at C == 3 a second colour space (G, (R - G) mod 256, (B - G) mod 256).
+ * Modes of a plane, over a = left, b = up, c = up-left (0 outside the image), residual (v - pred) mod 256:
+ *   0: 0, 1: a, 2: b, 3: (a + b) >> 1, 4: PNG's Paeth, 5: the LOCO-I median edge detector, 6: stored at 8 n bits, n = H W.
+ * A residual plane with histogram n_s over k used symbols costs, with table[m] = log2(m!) in fp64 for m = 0 .. table_len - 1,
+ *   ((((8 + ((table[256] - table[k]) - table[256 - k])) + table[n + k - 1]) - table[k - 1]) - sum_s table[n_s]),
+ * the sum over s ascending from 0 in fp64.  bits = min over the colour spaces of the sum over its planes, in their order, of
+ * (3 + min over the modes), + 1 at C == 3; a tie goes to the lower index.  The counts are integers and every sum has one order:
+ * the same bits on every call, no floating-point atomics.
+ * choice = space | (mode of plane p + 1) << (4 + 3 p) for the planes of the chosen space.
+ * A pixel with |255 x - q| > 1/64 sets bit 0 of *status (the length is that of the quantised image); a non-finite pixel sets
+ * bit 1, and its image gets NaN, NaN, -1 while the other images are untouched.  The word is only ever OR-ed into: the caller
+ * owns and clears it.  1 <= C <= 4, 1 <= H, W, H W <= 2^20, N < 2^31, else -2; N < 0, table_len < n + 257 or a missing pointer:
+ * -1.  N = 0 launches nothing. */
+int jvae_image_code_length_f32(const float* x, long N, int C, int H, int W, const double* table, long table_len, double* bits,
+                               float* bits32, int* choice, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2581,6 +2581,111 @@ def maha_check_status(status=None):
             raise ValueError('maha: a bank row with a non-finite element was met (it is in no sum)')
 
 
+# ------------------------------------------------------------ input complexity: a lossless image code length (csrc/ic.hip)
+IC_MAX_CHANNELS = 4
+IC_MAX_PIXELS = 1 << 20     # H W of an image: the 32-bit counters of a histogram hold it
+IC_MODES = ('none', 'sub', 'up', 'average', 'paeth', 'med', 'stored')
+IC_STATUS_INEXACT = 1       # a pixel further than 1/64 from its 8-bit level was met (the length is the quantised image's)
+IC_STATUS_NONFINITE = 2     # an image with a non-finite pixel was met (its bits are NaN, its choice -1)
+_ic_status = {}
+_ic_tables = {}             # n = H W -> the host table log2(m!), m = 0 .. n + 256; (n, device) -> its upload
+
+
+def ic_status(device):
+    """The per-device status word of `image_code_length` calls made without one of their own (created cleared)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _ic_status:
+        _ic_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _ic_status[idx]
+
+
+def ic_table(n, device=None):
+    """T[m] = log2(m!) for m = 0 .. n + 256 in fp64, math.lgamma(m + 1) / math.log(2) entry by entry, built once per n on the
+    host and kept; with `device` the (cached) upload of it."""
+    n = int(n)
+    if n not in _ic_tables:
+        ln2 = math.log(2)
+        _ic_tables[n] = torch.tensor([math.lgamma(m + 1) / ln2 for m in range(n + 257)], dtype=torch.float64)
+    if device is None:
+        return _ic_tables[n]
+    key = (n, str(device))
+    if key not in _ic_tables:
+        _ic_tables[key] = _ic_tables[n].to(device)
+    return _ic_tables[key]
+
+
+def image_code_length(x, status=None):
+    """x (N, C, H, W) fp32 -> (bits (N,) fp64, bits32 (N,) fp32, choice (N,) int32): the length in bits of every image under a
+    lossless coder - the exact length of an achievable code, nothing is encoded (csrc/ic.hip, ONE launch, one workgroup per
+    image).  q = clamp(rint(255 x), 0, 255); per plane the best of six predictors (`IC_MODES`: none, left, up, their mean, Paeth,
+    the LOCO-I median) and the stored mode, a residual plane at 8 + log2 C(256, k) + log2[(n + k - 1)! / ((k - 1)! prod n_s!)]
+    bits for its histogram n_s over k used symbols, 3 bits per plane for the mode; at C == 3 the better of (R, G, B) and
+    (G, R - G, B - G), and 1 bit for it.  Integer histograms and one fixed-order fp64 sum per histogram over the table
+    `ic_table(H W)`: the bits are those of the numpy restatement (tests/test_ic_restatement.py) and the same on every call.
+    bits32 = fp32(bits); `ic_choice` decodes `choice`.  status: an int32 device word that takes IC_STATUS_INEXACT when a pixel is
+    further than 1/64 from its 8-bit level and IC_STATUS_NONFINITE when one is not finite (that image: NaN, NaN, -1; the others
+    are untouched); default `ic_status(device)`; `ic_check_status` raises on the second.  1 <= C <= IC_MAX_CHANNELS,
+    H W <= IC_MAX_PIXELS.  N = 0 returns empties without a launch.  Nothing is synchronised."""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise L.JvaeHipError(f'image_code_length: x (N, C, H, W) expected, got {tuple(x.shape) if torch.is_tensor(x) else type(x)}')
+    x = _c(_f32(x, 'image_code_length'))
+    N, C, H, W = x.shape
+    if not 1 <= C <= IC_MAX_CHANNELS or H < 1 or W < 1 or H * W > IC_MAX_PIXELS or N >= 1 << 31:
+        raise L.JvaeHipError(f'image_code_length: 1 <= C <= {IC_MAX_CHANNELS}, 1 <= H, W, H W <= 2^20 and N < 2^31 expected, got '
+                             f'{tuple(x.shape)} (unsupported configuration)')
+    L.ptr(x)
+    dev = x.device
+    bits = torch.empty(N, dtype=torch.float64, device=dev)
+    bits32 = torch.empty(N, dtype=torch.float32, device=dev)
+    choice = torch.empty(N, dtype=torch.int32, device=dev)
+    if N:
+        if status is None:
+            status = ic_status(dev)
+        if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+            raise L.JvaeHipError('image_code_length: an int32 status word on the device of the images expected')
+        table = ic_table(H * W, dev)
+        L.check(L.load().jvae_image_code_length_f32(L.ptr(x), N, C, H, W, L.ptr(table), table.numel(), L.ptr(bits), L.ptr(bits32),
+                                                    L.ptr(choice), L.ptr(status), L.stream_ptr()), 'jvae_image_code_length_f32')
+    return bits, bits32, choice
+
+
+def ic_check_status(status=None):
+    """Read and clear what `image_code_length` flagged and raise ValueError for a non-finite pixel; pixels off the 8-bit grid
+    (IC_STATUS_INEXACT) are not an error.  status: the word given to the op (a device tensor: read here - this is the
+    synchronisation - and cleared), a host value, or None for the per-device default words.  -> the OR of the words read."""
+    words = list(_ic_status.values()) if status is None else [status]
+    seen = 0
+    for w in words:
+        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
+        if torch.is_tensor(w) and v:
+            w.zero_()
+        seen |= v
+    if seen & IC_STATUS_NONFINITE:
+        raise ValueError('image_code_length: an image with a non-finite pixel was met (its bits are NaN, its choice -1)')
+    return seen
+
+
+def ic_choice(word):
+    """The `choice` word of an image -> (space, [mode per plane of that space]): space 0 = the planes as they are, 1 =
+    (G, R - G, B - G); modes index `IC_MODES`.  -1 (a refused image) -> (-1, [])."""
+    word = int(word)
+    if word < 0:
+        return -1, []
+    modes, rest = [], word >> 4
+    while rest & 7:
+        modes.append((rest & 7) - 1)
+        rest >>= 3
+    return word & 15, modes
+
+
+def ic_choice_word(space, modes):
+    """The inverse of `ic_choice`."""
+    word = int(space)
+    for p, m in enumerate(modes):
+        word |= (int(m) + 1) << (4 + 3 * p)
+    return word
+
+
 # ------------------------------------------------------------ 2-D projections: exact t-SNE and PCA (csrc/embed.hip)
 EMBED_MAX_N = 16384         # points of a t-SNE: a row of fp32 distances in LDS
 EMBED_MAX_K = 1024          # dimensions of the points

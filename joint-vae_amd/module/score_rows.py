@@ -13,10 +13,10 @@ import torch
 from jvae_hip import ops
 
 # what the form of a row depends on besides its name
-# (OOD_REGRET_METHODS, OOD_KNN_METHODS, OOD_MAHA_METHODS: the model's opt-in switches of the recorded `regret-*` / `knn-*` / `maha*`
-# rows; off where a caller does not say)
+# (OOD_REGRET_METHODS, OOD_KNN_METHODS, OOD_MAHA_METHODS, OOD_IC_METHODS: the model's opt-in switches of the recorded `regret-*` /
+# `knn-*` / `maha*` / `ic-*` rows; off where a caller does not say.  The switches are read by name, their order means nothing.)
 Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is_jvae num_labels OOD_REGRET_METHODS OOD_KNN_METHODS '
-                    'OOD_MAHA_METHODS', defaults=(False, False, False))
+                    'OOD_IC_METHODS OOD_MAHA_METHODS', defaults=(False, False, False, False))
 
 
 # One family of RECORDED score rows: a model method computes them once per batch, the pass records them with the losses, reads
@@ -47,18 +47,31 @@ FAMILIES = (
            lambda model: bool(model.OOD_MAHA_METHODS), lambda t: t.OOD_MAHA_METHODS, '_maha_names', 'maha_scores', ('mu',),
            '{m}: the Mahalanobis rows are an opt-in (OOD_MAHA_METHODS)',
            '{m}: not among the Mahalanobis rows of this model (`maha`; `maha-rel` with more than one fitted class)'))
+# ... and behind them the families that score the IMAGE and correct the model's own rows with it, in a table of their own: FAMILIES
+# holds the families that score a sample through the model, and its four entries are pinned as such
+IMAGE_FAMILIES = (
+    Family('ic-', lambda m: m in ('ic-bits', 'ic-elbo', 'ic-iws'), 'ic*',
+           lambda model: bool(model.OOD_IC_METHODS) and model.type in model.IC_TYPES, lambda t: t.OOD_IC_METHODS,
+           '_ic_names', 'ic_scores', ('x', 'losses'),
+           '{m}: the input-complexity rows are an opt-in (OOD_IC_METHODS) of the types with a decoder (IC_TYPES)',
+           '{m}: not among the input-complexity rows of this model (`ic-bits`, `ic-elbo`, `ic-iws`)'),)
 ODIN = FAMILIES[0]
 odin_name = (ODIN.prefix + '-{:.0f}-{:.4f}').format            # (T, eps) -> `odin-T-eps` as the reference formats it (cvae.py:124-127)
 
 
+def families():
+    """Every family of recorded rows, in the order of expansion: both tables as they are at the call."""
+    return tuple(FAMILIES) + tuple(IMAGE_FAMILIES)
+
+
 def claimed_by(name):
-    """The family whose prefix claims `name`, or None."""
-    return next((f for f in FAMILIES if name.startswith(f.prefix)), None)
+    """The family whose prefix claims `name` (or whose starred name it is), or None."""
+    return next((f for f in families() if name.startswith(f.prefix) or name == f.starred), None)
 
 
 def recorded_by(name):
     """The family `name` (no thresholding suffix) is a well-formed row of, or None."""
-    for f in FAMILIES:
+    for f in families():
         if f.is_row(name):
             return f
 
@@ -130,7 +143,7 @@ def _wim_entry(m):
 class Row:
     """One score row.  base: the name without the '-2s' / '-a-x-y' suffix, which only names the thresholding done downstream
     (`roc_mode`); source: the key of the losses the row reads, `logits`, or the name itself for a recorded `odin-*` / `regret-*` /
-    `knn-*` / `maha*` row; kind,
+    `knn-*` / `maha*` / `ic-*` row; kind,
     const: its row of ops.misclass_scores (temperature or additive constant) or of ops.wim_scores (the family's factor), kind
     None where there is no kernel row."""
     name: str

@@ -4,6 +4,7 @@ means, and the one writer of score rows, are in module/score_rows.py; the model 
 odin_scores, the tables of method names) is in cvae.py."""
 import contextlib
 import logging
+import math
 import os
 import time
 
@@ -368,18 +369,62 @@ class ScoringMixin:
         d, _, rel = ops.maha_scores(mu.float(), self.latent_gaussians)
         return {name: -v for name, v in zip(self._maha_names(), (d, rel))}
 
+    # The input-complexity rows `ic-bits`, `ic-elbo` and `ic-iws` (Serra et al. 2020): a VAE's likelihood is
+    # high on a simple image whatever set it comes from, and S(x) = -log2 p(x) - L(x) takes the length L(x) of the image under a
+    # lossless coder out of it.  `ic-bits` is -L alone, `ic-elbo` / `ic-iws` are log2 of the model's `elbo` / `iws` row as the
+    # probability of the pixel's 8-bit bin, plus L: higher = more in-distribution, as every row here.  L comes from ONE launch
+    # of csrc/ic.hip per batch (ops.image_code_length).  Off by default: every name raises, 'all' is the reference's table.
+    # On (class or instance): 'all' and 'ic*' expand to `_ic_names()` on the types of IC_TYPES (`vib` has no decoder).
+    OOD_IC_METHODS = False
+    IC_TYPES = ('cvae', 'vae', 'xvae')
+
+    def _ic_names(self):
+        """`ic-bits`, `ic-elbo`, `ic-iws`."""
+        return ['ic-bits', 'ic-elbo', 'ic-iws']
+
+    def input_complexity(self, x):
+        """The code length of a batch of images x (N, *input_shape) fp32 on the device, values in [0, 1]: {'bits': (N,) fp64, the
+        length L(x) in bits of the image quantised to 8 bits, 'bits_per_dim': bits / (C H W), 'choice': (N,) int32, the coder's
+        colour space and modes (`ops.ic_choice`)}.  ONE `ops.image_code_length` call; nothing is synchronised.  A pixel off the
+        8-bit grid or a non-finite one sets the device's `ops.ic_status` word (`ops.ic_check_status`)."""
+        shape = tuple(self.input_shape)
+        if len(shape) != 3:
+            raise NotImplementedError(f'input_complexity: images (C, H, W) expected, the model reads {shape}')
+        bits, _, choice = ops.image_code_length(x.reshape(-1, *shape))
+        return {'bits': bits, 'bits_per_dim': bits / float(np.prod(shape)), 'choice': choice}
+
+    def ic_scores(self, x, losses):
+        """The input-complexity rows of a batch: x as `input_complexity` takes it, `losses` what a label-free evaluate(x) of the
+        batch returned -> {'ic-bits': -L, 'ic-elbo': e / ln 2 - D log2 255 + L, 'ic-iws': the same on the `iws` row}, (N,) fp32
+        device tensors computed in fp64 and rounded once.  e: the model's own `elbo` row (score_rows.parse('elbo'): the max over
+        the classes for a cvae), in nats; D = C H W; D log2 255 turns the density of x = q / 255 into the probability of its bin
+        and is left out for output_distribution='categorical', whose likelihood is discrete already.  Models of another type
+        than IC_TYPES or with coded labels are refused, as latent_posterior(x) refuses the latter."""
+        if self.type not in self.IC_TYPES or self.y_is_coded:
+            raise NotImplementedError(f'ic_scores: built for models without coded labels of the types {", ".join(self.IC_TYPES)}, '
+                                      f'not type {self.type}' + (' with coded labels' if self.y_is_coded else ''))
+        L = self.input_complexity(x)['bits']
+        D = float(np.prod(tuple(self.input_shape)))
+        traits = score_rows.traits_of(self)
+        # both rows through one chain of elementwise launches: the same operations in the same order as row by row
+        log2p = torch.stack([score_rows.parse(base, traits).torch_row(losses) for base in ('elbo', 'iws')]).double() / math.log(2)
+        if self.output_distribution != 'categorical':
+            log2p = log2p - D * math.log2(255)
+        elbo, iws = (log2p + L).float()
+        return {'ic-bits': (-L).float(), 'ic-elbo': elbo, 'ic-iws': iws}
+
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
         return [score_rows.odin_name(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
 
     def _ood_methods(self, method):
         """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
-        line), a name or a list of names.  The recorded families (score_rows.FAMILIES: `odin*` on a type whose table lists it,
-        i.e. vib; the opt-ins `regret*`, `knn*` and `maha*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
+        line), a name or a list of names.  The recorded families (score_rows.families(): `odin*` on a type whose table lists it,
+        i.e. vib; the opt-ins `regret*`, `knn*`, `maha*` and `ic*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
         name expand to the model's own list (the plain names first, the expansions behind them in the table's order, as the
         reference's develop_starred_methods orders them) and a single name has to be on that list.  The spline-threshold
         ('-a-x-y') methods raise unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
-        families = score_rows.FAMILIES
+        families = score_rows.families()
         on = {f: f.on(self) for f in families}
 
         def refusal(m):                                         # why m is outside this build, or None
@@ -424,7 +469,7 @@ class ScoringMixin:
         device = self.device
         name = getattr(dset, 'name', 'set')
         records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
-        families = [f for f in score_rows.FAMILIES if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
+        families = [f for f in score_rows.families() if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
         with_mu = sample_recorder is not None or any('mu' in f.args for f in families)
         filled, sums, measures = 0, {}, None
         with torch.no_grad(), self._recorded_pass(dset, name, batch_size, num_batch, shuffle, recorder, sample_dirs) as (

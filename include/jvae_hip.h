@@ -981,6 +981,38 @@ int jvae_maha_scores_f32(const float* q, const float* mu0, const float* W, const
 int jvae_image_code_length_f32(const float* x, long N, int C, int H, int W, const double* table, long table_len, double* bits,
                                float* bits32, int* choice, int* status, void* stream);
 
+/* ---- Density-of-states scores: a Gaussian kernel density estimate over a score bank (csrc/dose.hip; Morningstar et al. 2021,
+ * Nalisnick et al. 2019; no counterpart in the reference) ------------------------------------------------------------------------
+ * None of the entry points allocates or synchronises.  No floating-point atomics: same inputs, same bits, run to run.
+ * Fit: bank (S, M) fp32, row s = statistic s of M samples.  factors: a HOST pointer to three doubles, read by the call itself:
+ * bandwidth, scott1 = M^(-1/5), scottS = M^(-1/(S + 4)).  -> centre (S,), sigma (S,) (ddof = 1), h1 = bandwidth * sigma * scott1,
+ * hS = bandwidth * sigma * scottS, lognorm (S + 1,): log(M h1_s) + log(2 pi) / 2 for s < S, then log M + sum_s log hS_s +
+ * (S / 2) log(2 pi); all fp64, every sum in a fixed order that hangs on M alone.  z (S, M) fp32 = ((double)bank - centre) / h1,
+ * rounded once.  A non-finite element of row s sets bit s of *status, a row whose sigma is not a positive finite number bit
+ * 8 + s.  ws: device scratch of jvae_kde_fit_workspace_bytes(M, S) bytes, 8-byte aligned (-3 when smaller).  1 <= S <= 8,
+ * 2 <= M <= 2^24, else -2 and a workspace size of 0; M < 2, S < 1, a factor that is not positive, a missing pointer: -1.
+ * Scores: stats (S, N) fp32, raw -> out (2 S + 2, N) fp32.  With t = fp32(((double)stats - centre) / h1):
+ *   rows 0 .. S - 1   the marginal log-densities logsumexp_m(-((t_s - z_sm)^2) / 2) - lognorm[s];
+ *   row S             their sum over s ascending, in fp64, rounded once;
+ *   row S + 1         the product-kernel log-density logsumexp_m(-(*ratio2 / 2) sum_s (t_s - z_sm)^2) - lognorm[S];
+ *   rows S + 2 ..     the typicality -|stats_s - centre_s| / sigma_s.
+ * ratio2: a HOST pointer to one double, (h1 / hS)^2, the same for every row.  Differences, squares and exponentials are fp32.
+ * Every sum is shifted by its largest exponent, piece by piece of jvae_kde_partition() bank values - a partition that depends on
+ * neither N nor the grid, so a query's bits do not depend on the batch it is in.  A query element that is +-inf gives -inf in the
+ * rows that read it (its marginal and typicality row, rows S and S + 1); so does a finite element so far from the bank that a
+ * square overflows fp32 (|t - z| above 2^63; its typicality row stays finite; where only the SUM of the squares overflows, row
+ * S + 1 alone); a NaN gives NaN there.  All of them set bit 16 of *status and leave the other columns untouched.  The word is
+ * only ever OR-ed into: the caller owns and clears it.  ONE scoring launch and one merge launch.  ws: device scratch of
+ * jvae_kde_workspace_bytes(N, M, S) bytes, 8-byte aligned.  N = 0 launches nothing; N < 2^31. */
+int jvae_kde_partition(void);
+size_t jvae_kde_fit_workspace_bytes(long M, int S);
+int jvae_kde_fit_f32(const float* bank, long M, int S, const double* factors, float* z, double* centre, double* sigma, double* h1,
+                     double* hS, double* lognorm, int* status, void* ws, size_t ws_bytes, void* stream);
+size_t jvae_kde_workspace_bytes(long N, long M, int S);
+int jvae_kde_logdensity_f32(const float* stats, const float* z, const double* centre, const double* sigma, const double* h1,
+                            const double* lognorm, float* out, long N, long M, int S, const double* ratio2, int* status, void* ws,
+                            size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

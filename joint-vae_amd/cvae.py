@@ -22,6 +22,8 @@ fit_latent_bank() keeps the posterior means of a training set on the device and 
 OOD_KNN_METHODS; module/scoring.py, csrc/knn.hip) score a sample by its distance to them: no counterpart in the reference (section 7p).
 fit_latent_gaussians() fits class Gaussians with one shared covariance on that bank and maha_scores() / the `maha`, `maha-rel` OOD
 rows (an opt-in, OOD_MAHA_METHODS; module/scoring.py, csrc/maha.hip) are the Mahalanobis distances to them (section 7q).
+fit_score_bank() keeps the statistics DOSE_STATS of a training set and dose_scores() / the `dose*` OOD rows (an opt-in,
+OOD_DOSE_METHODS; module/scoring.py, csrc/dose.hip) are their kernel density estimates: how TYPICAL a sample's scores are (section 7s).
 input_complexity() is the length of a batch's images under a lossless coder, one launch of csrc/ic.hip, and the `ic-bits`, `ic-elbo`,
 `ic-iws` OOD rows (an opt-in, OOD_IC_METHODS; module/scoring.py) take it out of the likelihood (Serra et al. 2020; section 7r).
 Named data sets ('cifar10-3', 'mnist32r', 'svhn', ...: jvae_compat/torch_load.py, device-resident sets whose batches are one

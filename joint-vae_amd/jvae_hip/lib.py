@@ -194,6 +194,11 @@ _SIGS = {
     'jvae_maha_moments_f32': (c_int, [P, P, c_long, c_int, c_int] + [P] * 6 + [P, c_size_t, P]),
     'jvae_maha_scores_f32': (c_int, [P] * 10 + [c_long, c_int, c_int, c_int, P, P]),
     'jvae_image_code_length_f32': (c_int, [P, c_long, c_int, c_int, c_int, P, c_long, P, P, P, P, P]),
+    'jvae_kde_partition': (c_int, []),
+    'jvae_kde_fit_workspace_bytes': (c_size_t, [c_long, c_int]),
+    'jvae_kde_fit_f32': (c_int, [P, c_long, c_int, P] + [P] * 7 + [P, c_size_t, P]),
+    'jvae_kde_workspace_bytes': (c_size_t, [c_long, c_long, c_int]),
+    'jvae_kde_logdensity_f32': (c_int, [P] * 7 + [c_long, c_long, c_int, P, P, P, c_size_t, P]),
 }
 
 

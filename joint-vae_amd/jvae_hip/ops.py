@@ -2686,6 +2686,162 @@ def ic_choice_word(space, modes):
     return word
 
 
+# ------------------------------------------------------------ density of states: a KDE over a score bank (csrc/dose.hip)
+DOSE_MAX_STATS = 8
+DOSE_MAX_BANK = 1 << 24     # values of a bank row
+DOSE_STATUS_QUERY = 1 << 16        # a query with a non-finite (or fp32-overflowing) element was met (-inf / NaN in its rows)
+DOSE_FIT_KEYS = ('z', 'centre', 'sigma', 'h1', 'hS', 'lognorm', 'M', 'S', 'bandwidth')
+_dose_status = {}
+
+
+def kde_status(device):
+    """The per-device status word of `kde_logdensity` calls made without one of their own (created cleared)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _dose_status:
+        _dose_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _dose_status[idx]
+
+
+def kde_partition():
+    """Bank values of a piece of the kernel's fixed bank partition (a property of the build)."""
+    return int(L.load().jvae_kde_partition())
+
+
+def kde_scott(M, d):
+    """Scott's factor M^(-1 / (d + 4)) as `kde_fit` computes it (host fp64)."""
+    return float(M) ** (-1. / (d + 4))
+
+
+def kde_fit(bank, bandwidth=1.0):
+    """bank (S, M) fp32 on the device, row s = statistic s of M samples -> the fit of `kde_logdensity`: {'z' (S, M) fp32, the bank
+    centred and scaled in fp64, (B - centre) / h1, and rounded once; 'centre', 'sigma' (ddof = 1), 'h1' = bandwidth * sigma *
+    M^(-1/5) (Scott's factor: scipy.stats.gaussian_kde's default), 'hS' = bandwidth * sigma * M^(-1/(S+4)) (S,) fp64; 'lognorm'
+    (S + 1,) fp64, log(M h1_s sqrt(2 pi)) and, last, log M + sum_s log hS_s + (S / 2) log(2 pi); 'M', 'S', 'bandwidth'}.  The
+    moments are fp64 sums on the device in a fixed order that hangs on M alone (csrc/dose.hip): a second call returns the same
+    bits.  ValueError, naming the row, for a row without spread (sigma = 0), for a non-finite element and for M < 2: the device
+    sets a status word that is read HERE - this call synchronises, scoring does not.  1 <= S <= DOSE_MAX_STATS,
+    M <= DOSE_MAX_BANK, bandwidth > 0."""
+    if not torch.is_tensor(bank) or bank.dim() != 2:
+        raise L.JvaeHipError(f'kde_fit: bank (S, M) expected, got {tuple(bank.shape) if torch.is_tensor(bank) else type(bank)}')
+    bank = _c(_f32(bank, 'kde_fit'))
+    S, M = bank.shape
+    bandwidth = float(bandwidth)
+    if not 1 <= S <= DOSE_MAX_STATS or M > DOSE_MAX_BANK:
+        raise L.JvaeHipError(f'kde_fit: 1 <= S <= {DOSE_MAX_STATS} and M <= 2^24 expected, got S={S}, M={M} (unsupported '
+                             'configuration)')
+    if M < 2:
+        raise ValueError(f'kde_fit: a bank of at least two samples expected, got M={M}')
+    if not 0 < bandwidth < math.inf:
+        raise ValueError(f'kde_fit: a bandwidth > 0 expected, got {bandwidth}')
+    L.ptr(bank)
+    dev = bank.device
+
+    def f64(n):
+        return torch.empty(n, dtype=torch.float64, device=dev)
+    fit = {'z': torch.empty((S, M), dtype=torch.float32, device=dev), 'centre': f64(S), 'sigma': f64(S), 'h1': f64(S), 'hS': f64(S),
+           'lognorm': f64(S + 1)}
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib = L.load()
+    ws = L.workspace(lib.jvae_kde_fit_workspace_bytes(M, S) + 8, dev)
+    off = (-ws.data_ptr()) % 8
+    factors = (ctypes.c_double * 3)(bandwidth, kde_scott(M, 1), kde_scott(M, S))       # a host array, read by the call
+    L.check(lib.jvae_kde_fit_f32(L.ptr(bank), M, S, factors, *(L.ptr(fit[k]) for k in fit),
+                                 L.ptr(status), ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()), 'jvae_kde_fit_f32')
+    word = int(status[0])                                           # the synchronisation
+    for s in range(S):
+        if word >> s & 1:
+            raise ValueError(f'kde_fit: row {s} of the bank holds a non-finite element')
+    for s in range(S):
+        if word >> (8 + s) & 1:
+            raise ValueError(f'kde_fit: row {s} of the bank has no spread (sigma = 0): no bandwidth can be set for it')
+    return dict(fit, M=M, S=S, bandwidth=bandwidth)
+
+
+def kde_check_fit(fit, who='kde_logdensity'):
+    """Keys, dtypes and shapes of a fit of `kde_fit` -> (S, M); ValueError otherwise."""
+    def bad(why):
+        return ValueError(f'{who}: not a fit of kde_fit ({why})')
+    if not isinstance(fit, dict) or not set(DOSE_FIT_KEYS) <= set(fit):
+        raise bad('keys ' + ', '.join(DOSE_FIT_KEYS) + ' expected')
+    for k in ('M', 'S'):
+        if not isinstance(fit[k], int) or isinstance(fit[k], bool):
+            raise bad(f'{k}: an int expected')
+    S, M = fit['S'], fit['M']
+    if not 1 <= S <= DOSE_MAX_STATS or not 2 <= M <= DOSE_MAX_BANK:
+        raise bad(f'1 <= S <= {DOSE_MAX_STATS} and 2 <= M <= 2^24 expected, got S={S}, M={M}')
+    if not isinstance(fit['bandwidth'], float) or not 0 < fit['bandwidth'] < math.inf:
+        raise bad('bandwidth: a float > 0 expected')
+    shapes = {'z': (S, M), 'centre': (S,), 'sigma': (S,), 'h1': (S,), 'hS': (S,), 'lognorm': (S + 1,)}
+    for k, shape in shapes.items():
+        dt = torch.float32 if k == 'z' else torch.float64
+        if not torch.is_tensor(fit[k]) or fit[k].dtype != dt:
+            raise bad(f'{k}: a {dt} tensor expected')
+        if tuple(fit[k].shape) != shape:
+            raise bad(f'{k}: {shape} expected, got {tuple(fit[k].shape)}')
+    return S, M
+
+
+def kde_logdensity(stats, fit, status=None):
+    """stats (S, N) fp32 on the device, raw (not standardised), against the fit of `kde_fit` -> (2 S + 2, N) fp32: rows 0 .. S - 1
+    the marginal log-densities logq_s = logsumexp_m(-((T_s - B_sm) / h1_s)^2 / 2) - log(M h1_s sqrt(2 pi)); row S their sum over s
+    ascending (`dose`); row S + 1 the log-density under the product kernel with the bandwidths hS (`dose-joint`); rows S + 2 ..
+    2 S + 1 the typicality -|T_s - centre_s| / sigma_s.  Higher = more typical of the bank.  The query is centred and scaled in
+    fp64 and rounded once; differences, squares and exponentials are fp32; every sum is shifted by its largest exponent, so a
+    query far from every bank value gets a finite, correctly ordered score.  The bank is partitioned in pieces of
+    `kde_partition()` values whatever N is: a sample's bits do not depend on its batch, and a second call returns the same bits
+    (no floating-point atomics).  A +-inf element gives -inf in the rows that read it (its marginal and typicality row, `dose`,
+    `dose-joint`; the typicality row by its own arithmetic), and so does a finite one more than about 2^63 bandwidths from the
+    bank, whose square overflows fp32 (its typicality row stays finite); a NaN gives NaN; all set DOSE_STATUS_QUERY in `status` (default `kde_status(device)`; `kde_check_status`)
+    and leave the other columns untouched.  N = 0 returns an empty result without a launch.  ONE scoring launch and one merge
+    launch; nothing is read back (csrc/dose.hip)."""
+    S, M = kde_check_fit(fit)
+    if not torch.is_tensor(stats) or stats.dim() != 2 or stats.shape[0] != S:
+        raise L.JvaeHipError(f'kde_logdensity: stats ({S}, N) expected, got {tuple(stats.shape) if torch.is_tensor(stats) else type(stats)}')
+    if stats.dtype != torch.float32:
+        raise L.JvaeHipError(f'kde_logdensity: fp32 stats expected, got {stats.dtype}')
+    stats = _c(stats)
+    N = stats.shape[1]
+    if N >= 1 << 31:
+        raise L.JvaeHipError(f'kde_logdensity: N < 2^31 expected, got {N} (unsupported configuration)')
+    L.ptr(stats)
+    dev = stats.device
+    ops_ = [fit[k] for k in ('z', 'centre', 'sigma', 'h1', 'lognorm')]
+    if any(t.device != dev for t in ops_):
+        raise L.JvaeHipError('kde_logdensity: the fit on the device of the statistics expected')
+    out = torch.empty((2 * S + 2, N), dtype=torch.float32, device=dev)
+    if not N:
+        return out
+    if status is None:
+        status = kde_status(dev)
+    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+        raise L.JvaeHipError('kde_logdensity: an int32 status word on the device of the statistics expected')
+    lib = L.load()
+    nbytes = lib.jvae_kde_workspace_bytes(N, M, S)
+    if not nbytes:
+        raise L.JvaeHipError(f'kde_logdensity: sizes out of range (N={N}, M={M}, S={S})')
+    ws = L.workspace(nbytes + 8, dev)
+    off = (-ws.data_ptr()) % 8
+    ratio2 = ctypes.c_double((kde_scott(M, 1) / kde_scott(M, S)) ** 2)     # (h1 / hS)^2: the same for every row; read by the call
+    L.check(lib.jvae_kde_logdensity_f32(L.ptr(stats), *(L.ptr(_c(t)) for t in ops_), L.ptr(out), N, M, S, ctypes.byref(ratio2), L.ptr(status),
+                                        ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()), 'jvae_kde_logdensity_f32')
+    return out
+
+
+def kde_check_status(status=None):
+    """Raise JvaeHipError for what `kde_logdensity` flagged.  status: the word given to the op (a device tensor: read here - this
+    is the synchronisation - and cleared), a host value, or None for the per-device default words."""
+    words = list(_dose_status.values()) if status is None else [status]
+    seen = 0
+    for w in words:                                                 # every word is read and cleared before anything is raised
+        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
+        if torch.is_tensor(w) and v:
+            w.zero_()
+        seen |= v
+    if seen & DOSE_STATUS_QUERY:
+        raise L.JvaeHipError('kde_logdensity: a query with a non-finite statistic, or one so far from the bank that its square '
+                             'overflows fp32, was met (its rows hold -inf / NaN)')
+
+
 # ------------------------------------------------------------ 2-D projections: exact t-SNE and PCA (csrc/embed.hip)
 EMBED_MAX_N = 16384         # points of a t-SNE: a row of fp32 distances in LDS
 EMBED_MAX_K = 1024          # dimensions of the points

@@ -13,10 +13,11 @@ import torch
 from jvae_hip import ops
 
 # what the form of a row depends on besides its name
-# (OOD_REGRET_METHODS, OOD_KNN_METHODS, OOD_MAHA_METHODS, OOD_IC_METHODS: the model's opt-in switches of the recorded `regret-*` /
-# `knn-*` / `maha*` / `ic-*` rows; off where a caller does not say.  The switches are read by name, their order means nothing.)
+# (OOD_REGRET_METHODS, OOD_KNN_METHODS, OOD_IC_METHODS, OOD_DOSE_METHODS, OOD_MAHA_METHODS: the model's opt-in switches of the
+# recorded `regret-*` / `knn-*` / `ic-*` / `dose*` / `maha*` rows; off where a caller does not say.  The switches are read by name,
+# their order means nothing.)
 Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is_jvae num_labels OOD_REGRET_METHODS OOD_KNN_METHODS '
-                    'OOD_IC_METHODS OOD_MAHA_METHODS', defaults=(False, False, False, False))
+                    'OOD_IC_METHODS OOD_DOSE_METHODS OOD_MAHA_METHODS', defaults=(False, False, False, False, False))
 
 
 # One family of RECORDED score rows: a model method computes them once per batch, the pass records them with the losses, reads
@@ -28,7 +29,8 @@ Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is
 # evaluation), `mu` (its posterior means); off, unlisted: the refusals where the family is off / the model does not list the name
 Family = namedtuple('Family', 'prefix is_row starred on trait names scores args off unlisted')
 
-# in the order in which 'all' and the starred names expand and the per-batch calls run
+# in the order in which 'all' and the starred names expand and the per-batch calls run: FAMILIES, then IMAGE_FAMILIES, then
+# STAT_FAMILIES (`all_families()`)
 FAMILIES = (
     Family('odin', lambda m: m.startswith('odin'), 'odin*',                  # cvae.py:1076-1078, 1645-1663
            lambda model: 'odin*' in model.ood_methods, lambda t: True, '_odin_names', 'odin_scores', ('x',),
@@ -55,23 +57,38 @@ IMAGE_FAMILIES = (
            '_ic_names', 'ic_scores', ('x', 'losses'),
            '{m}: the input-complexity rows are an opt-in (OOD_IC_METHODS) of the types with a decoder (IC_TYPES)',
            '{m}: not among the input-complexity rows of this model (`ic-bits`, `ic-elbo`, `ic-iws`)'),)
+# ... and last the families that score a sample by how typical its STATISTICS - other rows of this catalogue - are of a training
+# set: they read the evaluation of the batch, not the image.  A third table: the two above are pinned as they are
+STAT_FAMILIES = (
+    Family('dose', lambda m: m == 'dose' or m.startswith('dose-'), 'dose*',
+           lambda model: bool(model.OOD_DOSE_METHODS) and model.type in model.DOSE_TYPES, lambda t: t.OOD_DOSE_METHODS,
+           '_dose_names', 'dose_scores', ('logits', 'losses'),
+           '{m}: the density-of-states rows are an opt-in (OOD_DOSE_METHODS) of the types of DOSE_TYPES',
+           '{m}: not among the density-of-states rows of this model (`dose`, `dose-joint`, `dose-<stat>` and `dose-typ-<stat>` for '
+           'the statistics of DOSE_STATS)'),)
 ODIN = FAMILIES[0]
 odin_name = (ODIN.prefix + '-{:.0f}-{:.4f}').format            # (T, eps) -> `odin-T-eps` as the reference formats it (cvae.py:124-127)
 
 
 def families():
-    """Every family of recorded rows, in the order of expansion: both tables as they are at the call."""
+    """The families that score a sample through the model or its image, in the order of expansion: the first two tables as they
+    are at the call."""
     return tuple(FAMILIES) + tuple(IMAGE_FAMILIES)
+
+
+def all_families():
+    """Every family of recorded rows, in the order of expansion: the three tables as they are at the call."""
+    return families() + tuple(STAT_FAMILIES)
 
 
 def claimed_by(name):
     """The family whose prefix claims `name` (or whose starred name it is), or None."""
-    return next((f for f in families() if name.startswith(f.prefix) or name == f.starred), None)
+    return next((f for f in all_families() if name.startswith(f.prefix) or name == f.starred), None)
 
 
 def recorded_by(name):
     """The family `name` (no thresholding suffix) is a well-formed row of, or None."""
-    for f in families():
+    for f in all_families():
         if f.is_row(name):
             return f
 
@@ -143,7 +160,7 @@ def _wim_entry(m):
 class Row:
     """One score row.  base: the name without the '-2s' / '-a-x-y' suffix, which only names the thresholding done downstream
     (`roc_mode`); source: the key of the losses the row reads, `logits`, or the name itself for a recorded `odin-*` / `regret-*` /
-    `knn-*` / `maha*` / `ic-*` row; kind,
+    `knn-*` / `maha*` / `ic-*` / `dose*` row; kind,
     const: its row of ops.misclass_scores (temperature or additive constant) or of ops.wim_scores (the family's factor), kind
     None where there is no kernel row."""
     name: str

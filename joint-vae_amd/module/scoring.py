@@ -413,18 +413,178 @@ class ScoringMixin:
         elbo, iws = (log2p + L).float()
         return {'ic-bits': (-L).float(), 'ic-elbo': elbo, 'ic-iws': iws}
 
+    # The density-of-states rows (Morningstar et al. 2021; for one statistic the typicality test of Nalisnick et al. 2019;
+    # DESIGN.md section 7s).  Every other row is monotone in a statistic, and a VAE's known failure is the sample whose statistic
+    # is TOO good; these rows ask how typical a sample's statistics `DOSE_STATS` are of a training set, the score bank of
+    # `fit_score_bank`: `dose-<stat>` is the log-density of the statistic under a Gaussian kernel density estimate of the bank's
+    # (bandwidth DOSE_BANDWIDTH x Scott's), `dose` their sum (the paper's score), `dose-joint` the log-density of all of them
+    # under a product kernel, `dose-typ-<stat>` minus the distance to the bank's mean in its standard deviations.  Higher = more
+    # in-distribution, as every row here.  ONE `ops.kde_logdensity` call per batch (csrc/dose.hip).  Off by default: every name
+    # raises, 'all' is the reference's table.  On (class or instance): 'all' and 'dose*' expand to `_dose_names()` on the types
+    # of DOSE_TYPES.  Fitting is the caller's job.  A set scored against a bank fitted on itself meets itself: each of its
+    # samples is one of the kernels it is scored under (there is no leave-one-out).
+    OOD_DOSE_METHODS = False
+    DOSE_BANDWIDTH = 1.0
+    DOSE_TYPES = ('cvae', 'vae', 'xvae', 'vib')
+    _DOSE_STATS = {'vib': ('kl', 'zdist', 'logits')}
+    score_bank = None                                                         # ops.kde_fit's dictionary, 'stats' and 'set'
+    SCORE_BANK_FILE = 'score-bank.pth'
+
+    @property
+    def DOSE_STATS(self):
+        """The statistics of the density-of-states rows: an instance's own tuple once it sets one, else its type's default."""
+        own = self.__dict__.get('_dose_stats')
+        return own if own is not None else self._DOSE_STATS.get(self.type, ('elbo', 'iws', 'kl', 'zdist', 'mse'))
+
+    @DOSE_STATS.setter
+    def DOSE_STATS(self, names):
+        self.__dict__['_dose_stats'] = None if names is None else tuple(names)
+
+    def _dose_stat_rows(self):
+        """DOSE_STATS -> their Rows.  ValueError for an entry that is not a plain score name of this model: a name with a `-`,
+        a row of a recorded family, `joint` or `typ`, or a name score_rows.parse does not accept."""
+        stats = tuple(self.DOSE_STATS)
+        traits = score_rows.traits_of(self)
+        if not traits.losses_might_be_computed_for_each_class:
+            # a vib's `kl` and `zdist` have no class axis, as a vae's: the statistic is minus the loss (the reference's rows
+            # take a maximum over the first axis for every type but vae, cvae.py:1035-1039 - over the SAMPLES here)
+            traits = traits._replace(is_vae=True)
+        rows = []
+        for name in stats:
+            bad = None
+            if not isinstance(name, str) or not name or '-' in name or name[-1] in '~@' or name in ('joint', 'typ'):
+                bad = 'a plain score name expected'
+            elif score_rows.claimed_by(name) is not None or score_rows.recorded_by(name) is not None:
+                bad = 'a row of a recorded family'
+            else:
+                try:
+                    rows.append(score_rows.parse(name, traits))
+                except NotImplementedError:
+                    bad = f'not a score of a {self.type}'
+            if bad:
+                raise ValueError(f'DOSE_STATS: {name!r}: {bad}')
+        if not 1 <= len(stats) <= ops.DOSE_MAX_STATS or len(set(stats)) != len(stats):
+            raise ValueError(f'DOSE_STATS: 1 to {ops.DOSE_MAX_STATS} different statistics expected, got {stats}')
+        return rows
+
+    def _dose_names(self):
+        """`dose`, `dose-joint` (not for a single statistic: it is `dose` then), `dose-<stat>` and `dose-typ-<stat>` for the
+        statistics of `DOSE_STATS`, in their order."""
+        stats = tuple(self.DOSE_STATS)
+        return (['dose'] + ['dose-joint'] * (len(stats) > 1) + ['dose-' + s for s in stats] + ['dose-typ-' + s for s in stats])
+
+    def _dose_refuse(self, who):
+        if self.type not in self.DOSE_TYPES or self.y_is_coded:
+            raise NotImplementedError(f'{who}: built for models without coded labels of the types {", ".join(self.DOSE_TYPES)}, '
+                                      f'not type {self.type}' + (' with coded labels' if self.y_is_coded else ''))
+
+    def _dose_stat_values(self, rows, logits, losses, out=None, col=0):
+        """The statistics of a batch by their torch expressions, stacked: (S, N) fp32 (into out[:, col:col + N] with `out`)."""
+        got = score_rows.write_rows(rows, range(len(rows)), logits, losses, out, col, torch_rows=('',))
+        return torch.stack([v.float() for v in got]) if out is None else out[:, col:col + got[0].shape[0]]
+
+    def fit_score_bank(self, dataset, batch_size=100, ratio=1.0, seed=0):
+        """Fill `score_bank` with the statistics `DOSE_STATS` of `dataset` (any map-style dataset of (x, label)): ONE label-free
+        evaluation pass in eval mode, the rows of each batch written through score_rows.write_rows (their torch expressions)
+        straight into a preallocated (S, M) fp32 device buffer, then `ops.kde_fit` (bandwidth DOSE_BANDWIDTH).  ratio < 1: a
+        seeded random subset of round(ratio * len) samples, by the rule of `fit_latent_bank`; every batch is evaluated whole,
+        also one that keeps no sample, so under one seed of the latent noise the kept columns are those of a full pass.  -> the bank's dictionary: ops.kde_fit's, 'stats' (the names) and 'set'.
+        ValueError for a `DOSE_STATS` entry that is not a plain score name of the model, for a statistic that is constant or not
+        finite on the set and for fewer than two samples.  Models of another type than DOSE_TYPES or with coded labels are
+        refused, as the other families refuse the latter.  This call synchronises."""
+        self._dose_refuse('fit_score_bank')
+        rows = self._dose_stat_rows()
+        n = len(dataset)
+        if not 0 < ratio <= 1:
+            raise ValueError(f'fit_score_bank: a ratio in (0, 1] expected, got {ratio}')
+        keep = None
+        if ratio < 1:
+            perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
+            keep = torch.zeros(n, dtype=torch.bool)
+            keep[perm[:max(1, int(round(ratio * n)))]] = True
+        M = n if keep is None else int(keep.sum())
+        device = self.device
+        was_training = self.training
+        self.eval()
+        bank, seen, pos, measures = torch.empty((len(rows), M), dtype=torch.float32, device=device), 0, 0, None
+        with torch.no_grad():
+            for i, batch in enumerate(self._batch_source(dataset, batch_size, False)):
+                x = batch[0]
+                sel = None if keep is None else keep[seen:seen + x.shape[0]]
+                seen += x.shape[0]
+                # EVERY batch is evaluated, one without a kept sample too: the statistics draw latent noise, and a batch left
+                # out would shift the draws of every batch behind it (the posterior means of fit_latent_bank draw none)
+                _, logits, losses, measures = self._evaluate_for_scores(x, i, measures)[:4]
+                if sel is not None and not bool(sel.any()):
+                    continue
+                if sel is None or bool(sel.all()):
+                    pos += self._dose_stat_values(rows, logits, losses, bank, pos).shape[1]
+                else:
+                    cols = sel.nonzero()[:, 0].to(device)
+                    bank[:, pos:pos + cols.shape[0]] = self._dose_stat_values(rows, logits, losses)[:, cols]
+                    pos += cols.shape[0]
+        if was_training:
+            self.train()
+        if pos != M:
+            raise ValueError(f'fit_score_bank: the set yielded {pos} of the {M} samples expected')
+        fit = ops.kde_fit(bank, float(self.DOSE_BANDWIDTH))
+        self.score_bank = dict(fit, stats=tuple(self.DOSE_STATS), set=getattr(dataset, 'name', 'set'))
+        return self.score_bank
+
+    def save_score_bank(self, dir_name):
+        """Write the fitted bank as `score-bank.pth` into `dir_name` (a file of its own: save() / load() do not know it)."""
+        if self.score_bank is None:
+            raise ValueError('save_score_bank: no bank is fitted (fit_score_bank)')
+        os.makedirs(dir_name, exist_ok=True)
+        path = os.path.join(dir_name, self.SCORE_BANK_FILE)
+        torch.save({k: v.cpu() if torch.is_tensor(v) else v for k, v in self.score_bank.items()}, path)
+        return path
+
+    def load_score_bank(self, dir_name):
+        """Read `score-bank.pth` of `dir_name` onto the model's device -> the bank's dictionary, bit for bit what was saved.
+        ValueError for a file that does not hold a score bank, and for one whose 'stats' are not this model's `DOSE_STATS`."""
+        d = torch.load(os.path.join(dir_name, self.SCORE_BANK_FILE), map_location='cpu')
+        if not isinstance(d, dict) or set(d) != set(ops.DOSE_FIT_KEYS) | {'stats', 'set'} or not isinstance(d['stats'], tuple):
+            raise ValueError(f'load_score_bank: {dir_name} does not hold a score bank')
+        ops.kde_check_fit(d, 'load_score_bank')
+        if len(d['stats']) != d['S']:
+            raise ValueError(f'load_score_bank: {dir_name} does not hold a score bank')
+        if d['stats'] != tuple(self.DOSE_STATS):
+            raise ValueError(f"load_score_bank: the bank was fitted on the statistics {d['stats']}, this model's DOSE_STATS are "
+                             f'{tuple(self.DOSE_STATS)}')
+        self.score_bank = {k: v.to(self.device).contiguous() if torch.is_tensor(v) else v for k, v in d.items()}
+        return self.score_bank
+
+    def dose_scores(self, logits, losses):
+        """The density-of-states rows of a batch, `logits` and `losses` what a label-free evaluate(x) of it returned:
+        {name: (N,) fp32 device tensor} for the names of `_dose_names()`, higher = more in-distribution.  The statistics come by
+        their torch expressions, stacked (S, N), and go through ONE `ops.kde_logdensity` call.  ValueError without a bank, or
+        with a bank of other statistics than `DOSE_STATS`.  A non-finite statistic sets the device's `ops.kde_status` word
+        (`ops.kde_check_status`)."""
+        self._dose_refuse('dose_scores')
+        if self.score_bank is None:
+            raise ValueError('dose_scores: no score bank is fitted (fit_score_bank or load_score_bank)')
+        if tuple(self.score_bank['stats']) != tuple(self.DOSE_STATS):
+            raise ValueError(f"dose_scores: the bank was fitted on the statistics {self.score_bank['stats']}, this model's "
+                             f'DOSE_STATS are {tuple(self.DOSE_STATS)}')
+        rows = self._dose_stat_rows()
+        out = ops.kde_logdensity(self._dose_stat_values(rows, logits, losses).contiguous(), self.score_bank)
+        by_name = dict(zip(['dose-' + s for s in self.DOSE_STATS] + ['dose', 'dose-joint']
+                           + ['dose-typ-' + s for s in self.DOSE_STATS], out))
+        return {name: by_name[name] for name in self._dose_names()}
+
     def _odin_names(self):
         """The `odin-T-eps` method names of this instance's grid, temperature-major (cvae.py:124-127)."""
         return [score_rows.odin_name(T, e) for T in self.ODIN_TEMPS for e in self.ODIN_EPS]
 
     def _ood_methods(self, method):
         """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
-        line), a name or a list of names.  The recorded families (score_rows.families(): `odin*` on a type whose table lists it,
-        i.e. vib; the opt-ins `regret*`, `knn*`, `maha*` and `ic*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
+        line), a name or a list of names.  The recorded families (score_rows.all_families(): `odin*` on a type whose table lists
+        it, i.e. vib; the opt-ins `regret*`, `knn*`, `maha*`, `ic*` and `dose*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
         name expand to the model's own list (the plain names first, the expansions behind them in the table's order, as the
         reference's develop_starred_methods orders them) and a single name has to be on that list.  The spline-threshold
         ('-a-x-y') methods raise unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
-        families = score_rows.families()
+        families = score_rows.all_families()
         on = {f: f.on(self) for f in families}
 
         def refusal(m):                                         # why m is outside this build, or None
@@ -469,7 +629,7 @@ class ScoringMixin:
         device = self.device
         name = getattr(dset, 'name', 'set')
         records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
-        families = [f for f in score_rows.families() if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
+        families = [f for f in score_rows.all_families() if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
         with_mu = sample_recorder is not None or any('mu' in f.args for f in families)
         filled, sums, measures = 0, {}, None
         with torch.no_grad(), self._recorded_pass(dset, name, batch_size, num_batch, shuffle, recorder, sample_dirs) as (

@@ -1013,6 +1013,28 @@ int jvae_kde_logdensity_f32(const float* stats, const float* z, const double* ce
                             const double* lognorm, float* out, long N, long M, int S, const double* ratio2, int* status, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- SSIM of images against their reconstructions (csrc/ssim.hip; Wang et al. 2004, Bergmann et al. 2018; no counterpart in the
+ * reference) ----
+ * x (N, C, H, W) fp32, y (R, N, C, H, W) fp32 -> ssim (R, N) fp32, cs (R, N) fp32 and, where map is not NULL, map (R, N, H - 10,
+ * W - 10) fp32.  ONE launch; nothing is allocated or synchronised.  g: the 11 taps exp(-k^2 / 4.5), k = -5 .. 5, over their sum
+ * (formed in fp64, rounded to fp32), applied separably over the valid region.  Per plane, with a = fp32(the fp64 mean of the
+ * plane of x), x' = x - a and y' = y - a:
+ *   mx = g*x', my = g*y', vx = g*x'^2 - mx^2, vy = g*y'^2 - my^2, cxy = g*x'y' - mx my   (products rounded, then fmaf chains),
+ *   cs = ((cxy + cxy) + C2) / ((vx + vy) + C2), fx = a + mx, fy = a + my,
+ *   l = ((fx fy + fx fy) + C1) / ((fx fx + fy fy) + C1), C1 = 1e-4, C2 = 9e-4 (data range 1),
+ * every operation fp32, rounded as written.  ssim[r, n] = the mean of l cs over channels and valid pixels, cs[r, n] that of cs
+ * (fp64 sums in a fixed order, one division, rounded once); map[r, n] = the channel mean of l cs (fp32, channels ascending).
+ * This is scikit-image's structural_similarity(gaussian_weights=True, use_sample_covariance=False, data_range=1) on its
+ * interior.  A draw equal to its image scores exactly 1.  No output bit depends on N, R, the place of a sample or draw in the
+ * batch, or on whether map is given.  A non-finite pixel in x[n] sets bit 0 of *status and makes ssim, cs (and map) of every
+ * [r, n] NaN; one in y[r, n] sets bit 1 and makes that entry NaN.  The word is only ever OR-ed into: the caller owns and clears
+ * it.  C >= 1, 11 <= H <= 32768, 11 <= W <= 128 (a strip of rows is staged at full width), N, R < 2^31, else -2; N < 0, R < 0 or
+ * a missing pointer (map may be NULL): -1.  N = 0 or R = 0 launches nothing.
+ * jvae_ssim_strip_rows: the output rows of one staged strip at this shape (0 for a refused shape): host only. */
+int jvae_ssim_f32(const float* x, const float* y, long N, long R, int C, int H, int W, float* ssim, float* cs, float* map,
+                  int* status, void* stream);
+int jvae_ssim_strip_rows(int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ fit_score_bank() keeps the statistics DOSE_STATS of a training set and dose_scor
 OOD_DOSE_METHODS; module/scoring.py, csrc/dose.hip) are their kernel density estimates: how TYPICAL a sample's scores are (section 7s).
 input_complexity() is the length of a batch's images under a lossless coder, one launch of csrc/ic.hip, and the `ic-bits`, `ic-elbo`,
 `ic-iws` OOD rows (an opt-in, OOD_IC_METHODS; module/scoring.py) take it out of the likelihood (Serra et al. 2020; section 7r).
+ssim_scores() / ssim_map() and the `ssim`, `ssim-mu`, `ssim-cs` OOD rows (an opt-in, OOD_SSIM_METHODS; module/scoring.py) are the
+structural similarity of a batch to its reconstructions, one launch of csrc/ssim.hip on the x_reco of the scoring pass (section 7t).
 Named data sets ('cifar10-3', 'mnist32r', 'svhn', ...: jvae_compat/torch_load.py, device-resident sets whose batches are one
 launch of csrc/imageset.hip) are an opt-in, `DATA_ROOT` (class attribute, settable per instance: the torchvision-style directory
 of the raw files); None, the default, keeps every refusal of a name as it was.
@@ -1181,13 +1183,14 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                                  forced_lv=forced)[0]
         return mu, log_var
 
-    def _evaluate_for_scores(self, x, batch, measures, with_mu=False):
-        """One batch of the scoring pass: `x` as the data loader yields it -> (x on the device, logits, losses, measures[, mu]).
-        `with_mu`: the posterior means of the same pass, for the sample recorders.  A subclass whose items carry more than the
-        image (jvae_compat/wim.py: (x, y_est) pairs) overrides this."""
+    def _evaluate_for_scores(self, x, batch, measures, with_mu=False, with_reco=False):
+        """One batch of the scoring pass: `x` as the data loader yields it -> (x on the device, logits, losses, measures[, mu]
+        [, x_reco]).  `with_mu`: the posterior means of the same pass, for the sample recorders.  `with_reco`: the reconstructions
+        (L + 1, N, ...) of the same pass as the LAST item, for the families that score them (no second decode).  A subclass
+        whose items carry more than the image (jvae_compat/wim.py: (x, y_est) pairs) overrides this."""
         x = self._device_batch(x.to(self.device))
         out = self.evaluate(x, batch=batch, current_measures=measures, z_output=with_mu)
-        return (x,) + tuple(out[1:4]) + ((out[4],) if with_mu else ())
+        return (x,) + tuple(out[1:4]) + ((out[4],) if with_mu else ()) + ((out[0],) if with_reco else ())
 
     def _early_reduce_hook(self, grad):
         self.optimizer.reduce_early_bucket()

@@ -254,16 +254,17 @@ class WIMJob(ClassificationVariationalNetwork):
             self._wim_status = torch.zeros(1, dtype=torch.int32, device=device)
         return self._wim_status
 
-    def _evaluate_for_scores(self, x, batch, measures, with_mu=False):
+    def _evaluate_for_scores(self, x, batch, measures, with_mu=False, with_reco=False):
         """Scoring pass of ood_detection_rates: with estimated labels on, the loader's item is the pair (x, y_est) and the
-        evaluation runs under both priors.  `with_mu`: the posterior means of that same pass come back as a fifth item."""
+        evaluation runs under both priors.  `with_mu`: the posterior means of that same pass come back as a fifth item;
+        `with_reco`: its reconstructions as the last one."""
         if not self._with_estimated_labels:
-            return super()._evaluate_for_scores(x, batch, measures, with_mu=with_mu)
+            return super()._evaluate_for_scores(x, batch, measures, with_mu=with_mu, with_reco=with_reco)
         x, y_est = x
         x = self._device_batch(x.to(self.device))
         with self.evaluate_on_both_priors():
             out = self.evaluate((x, y_est.to(self.device)), batch=batch, current_measures=measures, z_output=with_mu)
-        return (x,) + tuple(out[1:4]) + ((out[4],) if with_mu else ())
+        return (x,) + tuple(out[1:4]) + ((out[4],) if with_mu else ()) + ((out[0],) if with_reco else ())
 
     def ood_detection_rates(self, *a, **kw):
         """The base class's method over `((x, y_est), y)` items; a label outside [0, C) met by the score kernel raises here,

@@ -199,6 +199,8 @@ _SIGS = {
     'jvae_kde_fit_f32': (c_int, [P, c_long, c_int, P] + [P] * 7 + [P, c_size_t, P]),
     'jvae_kde_workspace_bytes': (c_size_t, [c_long, c_long, c_int]),
     'jvae_kde_logdensity_f32': (c_int, [P] * 7 + [c_long, c_long, c_int, P, P, P, c_size_t, P]),
+    'jvae_ssim_f32': (c_int, [P, P, c_long, c_long, c_int, c_int, c_int, P, P, P, P, P]),
+    'jvae_ssim_strip_rows': (c_int, [c_int, c_int]),
 }
 
 

@@ -2686,6 +2686,83 @@ def ic_choice_word(space, modes):
     return word
 
 
+# ------------------------------------------------------------ SSIM of images against their reconstructions (csrc/ssim.hip)
+SSIM_WINDOW = 11            # taps of the Gaussian window (sigma 1.5); min(H, W) of an image
+SSIM_MAX_W = 128            # a strip of rows is staged at full width
+SSIM_MAX_H = 32768
+SSIM_STATUS_X = 1           # an image x[n] with a non-finite pixel was met (every [r, n] is NaN)
+SSIM_STATUS_Y = 2           # a draw y[r, n] with a non-finite pixel was met (that entry is NaN)
+_ssim_status = {}
+
+
+def ssim_status(device):
+    """The per-device status word of `ssim` calls made without one of their own (created cleared)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _ssim_status:
+        _ssim_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
+    return _ssim_status[idx]
+
+
+def ssim_strip_rows(H, W):
+    """The output rows of one staged strip of csrc/ssim.hip at this image size (a property of the build; 0: a refused size)."""
+    return int(L.load().jvae_ssim_strip_rows(int(H), int(W)))
+
+
+def ssim(x, x_reco, maps=False, status=None):
+    """x (N, C, H, W) fp32, x_reco (R, N, C, H, W) fp32 -> (ssim (R, N), cs (R, N)) fp32, with `maps` also map (R, N, H - 10,
+    W - 10): the structural similarity (Wang et al. 2004) of every image to each of its R reconstructions under the 11-tap
+    Gaussian window of sigma 1.5 over the valid region, data range 1 - scikit-image's structural_similarity(gaussian_weights=
+    True, use_sample_covariance=False, data_range=1) on its interior.  ssim: the mean over channels and valid pixels of
+    l * cs; cs: the same mean of the contrast-structure term alone; map: the channel mean of l * cs per pixel.  ONE launch
+    (csrc/ssim.hip): x is staged and its local moments are formed once per sample and chunk of draws; the second moments are
+    those of x - a and y - a, a the plane mean of x.  A draw equal to its image scores exactly 1; no bit depends on the batch
+    or on `maps`.  status: an int32 device word that takes SSIM_STATUS_X for a non-finite pixel in x[n] (every [r, n] NaN)
+    and SSIM_STATUS_Y for one in x_reco[r, n] (that entry NaN); default `ssim_status(device)`; `ssim_check_status` raises on
+    either.  SSIM_WINDOW <= H <= SSIM_MAX_H, SSIM_WINDOW <= W <= SSIM_MAX_W, C >= 1.  N = 0 or R = 0 returns empties without a
+    launch.  Nothing is synchronised."""
+    if not torch.is_tensor(x) or not torch.is_tensor(x_reco) or x.dim() != 4 or x_reco.dim() != 5 \
+            or tuple(x_reco.shape[1:]) != tuple(x.shape):
+        raise L.JvaeHipError('ssim: x (N, C, H, W) and x_reco (R, N, C, H, W) expected, got '
+                             + ' and '.join(str(tuple(t.shape)) if torch.is_tensor(t) else str(type(t)) for t in (x, x_reco)))
+    x, y = _c(_f32(x, 'ssim')), _c(_f32(x_reco, 'ssim'))
+    N, C, H, W = x.shape
+    R = y.shape[0]
+    if C < 1 or not SSIM_WINDOW <= H <= SSIM_MAX_H or not SSIM_WINDOW <= W <= SSIM_MAX_W or N >= 1 << 31 or R >= 1 << 31:
+        raise L.JvaeHipError(f'ssim: C >= 1, {SSIM_WINDOW} <= H <= {SSIM_MAX_H}, {SSIM_WINDOW} <= W <= {SSIM_MAX_W} and N, R < 2^31 '
+                             f'expected, got {tuple(y.shape)} (unsupported configuration)')
+    L.ptr(x)
+    dev = x.device
+    if y.device != dev:
+        raise L.JvaeHipError('ssim: x and x_reco on one device expected')
+    out = torch.empty((2, R, N), dtype=torch.float32, device=dev)
+    pix = torch.empty((R, N, H - 10, W - 10), dtype=torch.float32, device=dev) if maps else None
+    if N and R:
+        if status is None:
+            status = ssim_status(dev)
+        if not torch.is_tensor(status) or status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
+            raise L.JvaeHipError('ssim: an int32 status word on the device of the images expected')
+        L.check(L.load().jvae_ssim_f32(L.ptr(x), L.ptr(y), N, R, C, H, W, L.ptr(out[0]), L.ptr(out[1]), L.ptr(pix), L.ptr(status),
+                                       L.stream_ptr()), 'jvae_ssim_f32')
+    return (out[0], out[1], pix) if maps else (out[0], out[1])
+
+
+def ssim_check_status(status=None):
+    """Read and clear what `ssim` flagged and raise ValueError for a non-finite pixel.  status: the word given to the op (a device
+    tensor: read here - this is the synchronisation - and cleared), a host value, or None for the per-device default words."""
+    words = list(_ssim_status.values()) if status is None else [status]
+    seen = 0
+    for w in words:
+        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
+        if torch.is_tensor(w) and v:
+            w.zero_()
+        seen |= v
+    if seen & SSIM_STATUS_X:
+        raise ValueError('ssim: an image with a non-finite pixel was met (the scores of all its draws are NaN)')
+    if seen & SSIM_STATUS_Y:
+        raise ValueError('ssim: a reconstruction with a non-finite pixel was met (its scores are NaN)')
+    return seen
+
+
 # ------------------------------------------------------------ density of states: a KDE over a score bank (csrc/dose.hip)
 DOSE_MAX_STATS = 8
 DOSE_MAX_BANK = 1 << 24     # values of a bank row

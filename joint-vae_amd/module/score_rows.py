@@ -13,11 +13,12 @@ import torch
 from jvae_hip import ops
 
 # what the form of a row depends on besides its name
-# (OOD_REGRET_METHODS, OOD_KNN_METHODS, OOD_IC_METHODS, OOD_DOSE_METHODS, OOD_MAHA_METHODS: the model's opt-in switches of the
-# recorded `regret-*` / `knn-*` / `ic-*` / `dose*` / `maha*` rows; off where a caller does not say.  The switches are read by name,
-# their order means nothing.)
+# (OOD_REGRET_METHODS, OOD_KNN_METHODS, OOD_IC_METHODS, OOD_SSIM_METHODS, OOD_DOSE_METHODS, OOD_MAHA_METHODS: the model's opt-in
+# switches of the recorded `regret-*` / `knn-*` / `ic-*` / `ssim*` / `dose*` / `maha*` rows; off where a caller does not say.  The
+# switches are read by name, their order means nothing.)
 Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is_jvae num_labels OOD_REGRET_METHODS OOD_KNN_METHODS '
-                    'OOD_IC_METHODS OOD_DOSE_METHODS OOD_MAHA_METHODS', defaults=(False, False, False, False, False))
+                    'OOD_IC_METHODS OOD_SSIM_METHODS OOD_DOSE_METHODS OOD_MAHA_METHODS',
+                    defaults=(False, False, False, False, False, False))
 
 
 # One family of RECORDED score rows: a model method computes them once per batch, the pass records them with the losses, reads
@@ -30,7 +31,7 @@ Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is
 Family = namedtuple('Family', 'prefix is_row starred on trait names scores args off unlisted')
 
 # in the order in which 'all' and the starred names expand and the per-batch calls run: FAMILIES, then IMAGE_FAMILIES, then
-# STAT_FAMILIES (`all_families()`)
+# STAT_FAMILIES (`all_families()`), then RECO_FAMILIES (`every_family()`)
 FAMILIES = (
     Family('odin', lambda m: m.startswith('odin'), 'odin*',                  # cvae.py:1076-1078, 1645-1663
            lambda model: 'odin*' in model.ood_methods, lambda t: True, '_odin_names', 'odin_scores', ('x',),
@@ -66,6 +67,14 @@ STAT_FAMILIES = (
            '{m}: the density-of-states rows are an opt-in (OOD_DOSE_METHODS) of the types of DOSE_TYPES',
            '{m}: not among the density-of-states rows of this model (`dose`, `dose-joint`, `dose-<stat>` and `dose-typ-<stat>` for '
            'the statistics of DOSE_STATS)'),)
+# ... and the families that score the RECONSTRUCTION as an image, against the image it was decoded from.  A fourth table: the
+# three above and `all_families()` are pinned as they are
+RECO_FAMILIES = (
+    Family('ssim', lambda m: m in ('ssim', 'ssim-mu', 'ssim-cs'), 'ssim*',
+           lambda model: bool(model.OOD_SSIM_METHODS) and model.type in model.SSIM_TYPES, lambda t: t.OOD_SSIM_METHODS,
+           '_ssim_names', 'ssim_scores', ('x', 'x_reco'),
+           '{m}: the SSIM rows are an opt-in (OOD_SSIM_METHODS) of the types with a decoder (SSIM_TYPES)',
+           '{m}: not among the SSIM rows of this model (`ssim`, `ssim-mu`, `ssim-cs`)'),)
 ODIN = FAMILIES[0]
 odin_name = (ODIN.prefix + '-{:.0f}-{:.4f}').format            # (T, eps) -> `odin-T-eps` as the reference formats it (cvae.py:124-127)
 
@@ -81,14 +90,19 @@ def all_families():
     return families() + tuple(STAT_FAMILIES)
 
 
+def every_family():
+    """Every family of recorded rows, the ones that score the reconstruction last: the four tables as they are at the call."""
+    return all_families() + tuple(RECO_FAMILIES)
+
+
 def claimed_by(name):
     """The family whose prefix claims `name` (or whose starred name it is), or None."""
-    return next((f for f in all_families() if name.startswith(f.prefix) or name == f.starred), None)
+    return next((f for f in every_family() if name.startswith(f.prefix) or name == f.starred), None)
 
 
 def recorded_by(name):
     """The family `name` (no thresholding suffix) is a well-formed row of, or None."""
-    for f in all_families():
+    for f in every_family():
         if f.is_row(name):
             return f
 
@@ -160,7 +174,7 @@ def _wim_entry(m):
 class Row:
     """One score row.  base: the name without the '-2s' / '-a-x-y' suffix, which only names the thresholding done downstream
     (`roc_mode`); source: the key of the losses the row reads, `logits`, or the name itself for a recorded `odin-*` / `regret-*` /
-    `knn-*` / `maha*` / `ic-*` / `dose*` row; kind,
+    `knn-*` / `maha*` / `ic-*` / `dose*` / `ssim*` row; kind,
     const: its row of ops.misclass_scores (temperature or additive constant) or of ops.wim_scores (the family's factor), kind
     None where there is no kernel row."""
     name: str

@@ -413,6 +413,67 @@ class ScoringMixin:
         elbo, iws = (log2p + L).float()
         return {'ic-bits': (-L).float(), 'ic-elbo': elbo, 'ic-iws': iws}
 
+    # The SSIM rows `ssim`, `ssim-mu` and `ssim-cs` (Wang et al. 2004; Bergmann et al. 2018): every other row
+    # judges a reconstruction by its squared error, which a blurred reconstruction of the right brightness keeps small whatever
+    # it lost of edges and texture.  These rows score the reconstruction as an image: the structural similarity of x to x_reco
+    # under an 11-tap Gaussian window - local means, variances and the covariance.  `ssim` is the mean over the sampled draws
+    # (rows 1 .. L of x_reco, the rows `mse` averages), `ssim-mu` the row decoded from the posterior mean (row 0: no noise, the
+    # same bits under any seed), `ssim-cs` the mean over the draws of the contrast-structure term alone (the luminance term
+    # taken out).  Higher = more in-distribution.  ONE launch of csrc/ssim.hip per batch (ops.ssim), on the x_reco the label-free
+    # evaluation of the batch has made anyway.  Off by default: every name raises, 'all' is the reference's table.  On (class or
+    # instance): 'all' and 'ssim*' expand to `_ssim_names()` on the types of SSIM_TYPES (`vib` has no decoder).
+    OOD_SSIM_METHODS = False
+    SSIM_TYPES = ('cvae', 'vae', 'xvae')
+
+    def _ssim_names(self):
+        """`ssim`, `ssim-mu`, `ssim-cs`."""
+        return ['ssim', 'ssim-mu', 'ssim-cs']
+
+    def _ssim_refuse(self, who):
+        shape = tuple(self.input_shape)
+        why = None
+        if self.type not in self.SSIM_TYPES or self.y_is_coded:
+            why = f'not type {self.type}' + (' with coded labels' if self.y_is_coded else '')
+        elif self.output_distribution == 'categorical':
+            why = "not output_distribution='categorical' (its x_reco holds 256 levels per pixel)"
+        elif len(shape) != 3 or min(shape[1:]) < ops.SSIM_WINDOW:
+            why = f'the model reads {shape}'
+        if why:
+            raise NotImplementedError(f'{who}: built for models without coded labels of the types {", ".join(self.SSIM_TYPES)} that '
+                                      f'decode images (C, H, W) with min(H, W) >= {ops.SSIM_WINDOW}, {why}')
+
+    def ssim_scores(self, x, x_reco):
+        """The SSIM rows of a batch: x (N, *input_shape) and x_reco (L + 1, N, *input_shape), what a label-free evaluate(x)
+        returned first -> {'ssim': the mean over rows 1 .. L of ssim[r, n], 'ssim-mu': ssim[0, n], 'ssim-cs': the mean over rows
+        1 .. L of cs[r, n]}, (N,) fp32 device tensors from ONE `ops.ssim` call, the means taken in fp64 and rounded once.
+        Refused (NotImplementedError) for another type than SSIM_TYPES, coded labels, a categorical decoder and inputs that are
+        not images with min(H, W) >= 11.  A non-finite pixel sets the device's `ops.ssim_status` word (`ops.ssim_check_status`)."""
+        self._ssim_refuse('ssim_scores')
+        shape = tuple(self.input_shape)
+        x = x.reshape(-1, *shape)
+        s, cs = ops.ssim(x, x_reco.reshape(-1, x.shape[0], *shape))
+        if s.shape[0] < 2:
+            raise ValueError('ssim_scores: x_reco with the mean row and at least one sampled draw expected')
+        mean, mean_cs = torch.stack([s[1:], cs[1:]]).double().mean(1).float()
+        return {'ssim': mean, 'ssim-mu': s[0], 'ssim-cs': mean_cs}
+
+    def ssim_map(self, x):
+        """The per-pixel similarity map of a batch x (N, *input_shape) against its reconstruction from the posterior mean:
+        (N, H - 10, W - 10) fp32, the channel mean of l * cs, for localisation.  One label-free evaluate in eval mode under
+        no_grad and ONE `ops.ssim(maps=True)` call; the training flag is restored."""
+        self._ssim_refuse('ssim_map')
+        shape = tuple(self.input_shape)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                x = x.reshape(-1, *shape)
+                x_reco = self.evaluate(x)[0]
+                return ops.ssim(x, x_reco.reshape(-1, x.shape[0], *shape), maps=True)[2][0]
+        finally:
+            if was_training:
+                self.train()
+
     # The density-of-states rows (Morningstar et al. 2021; for one statistic the typicality test of Nalisnick et al. 2019;
     # DESIGN.md section 7s).  Every other row is monotone in a statistic, and a VAE's known failure is the sample whose statistic
     # is TOO good; these rows ask how typical a sample's statistics `DOSE_STATS` are of a training set, the score bank of
@@ -579,12 +640,12 @@ class ScoringMixin:
 
     def _ood_methods(self, method):
         """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
-        line), a name or a list of names.  The recorded families (score_rows.all_families(): `odin*` on a type whose table lists
-        it, i.e. vib; the opt-ins `regret*`, `knn*`, `maha*`, `ic*` and `dose*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
+        line), a name or a list of names.  The recorded families (score_rows.every_family(): `odin*` on a type whose table lists
+        it, i.e. vib; the opt-ins `regret*`, `knn*`, `maha*`, `ic*`, `dose*` and `ssim*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
         name expand to the model's own list (the plain names first, the expansions behind them in the table's order, as the
         reference's develop_starred_methods orders them) and a single name has to be on that list.  The spline-threshold
         ('-a-x-y') methods raise unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
-        families = score_rows.all_families()
+        families = score_rows.every_family()
         on = {f: f.on(self) for f in families}
 
         def refusal(m):                                         # why m is outside this build, or None
@@ -629,8 +690,9 @@ class ScoringMixin:
         device = self.device
         name = getattr(dset, 'name', 'set')
         records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
-        families = [f for f in score_rows.all_families() if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
+        families = [f for f in score_rows.every_family() if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
         with_mu = sample_recorder is not None or any('mu' in f.args for f in families)
+        with_reco = any('x_reco' in f.args for f in families)   # the reconstructions of the same pass: no second decode
         filled, sums, measures = 0, {}, None
         with torch.no_grad(), self._recorded_pass(dset, name, batch_size, num_batch, shuffle, recorder, sample_dirs) as (
                 recorded, recording, num_batch, batch_size, loader):
@@ -642,13 +704,15 @@ class ScoringMixin:
                     logits = recorder.get_batch(i, 'logits').T if 'logits' in recorder.keys() else None
                 else:
                     x, y = next(loader)[:2]
-                    x, logits, losses, measures, *mu = self._evaluate_for_scores(x, i, measures, with_mu=with_mu)
+                    more = {'with_reco': True} if with_reco else {}           # no family reads x_reco: the call as it always was
+                    x, logits, losses, measures, *mu = self._evaluate_for_scores(x, i, measures, with_mu=with_mu, **more)
+                    x_reco = mu.pop() if with_reco else None
                     y = y.to(device)
                     if sample_recorder is not None:
                         sample_recorder.append_batch(**self._sample_record(sample_recorder, mu[0], y, losses))
                     for f in families:
                         # all rows of the family per batch (it is what the recorder holds), from the pass above, on the device
-                        have = {'x': x, 'logits': logits, 'losses': losses, 'mu': mu[0] if mu else None}
+                        have = {'x': x, 'logits': logits, 'losses': losses, 'mu': mu[0] if mu else None, 'x_reco': x_reco}
                         losses = dict(losses, **getattr(self, f.scores)(**{a: have[a] for a in f.args}))
                     if recording:
                         extra = {} if logits is None else {'logits': logits.T}

@@ -185,6 +185,26 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return red[16];
 }
 
+// The fp64 sums of the fixed-order reductions (dose.hip, maha.hip, embed.hip): the butterfly over the 64 lanes of a wave ...
+__device__ __forceinline__ double wave_sum64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ... and over a workgroup (a multiple of 64 threads, at most 1024): the butterfly inside each wave, then the waves in sequence;
+// valid in every thread.  red: 16 doubles of LDS.  Contains barriers: call from uniform control flow.
+__device__ __forceinline__ double block_sum64(double v, double* red) {
+    v = wave_sum64(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double r = red[0];
+    for (int i = 1; i < nw; ++i) r += red[i];
+    return r;
+}
+
 // Activation kinds of the `relu` / `in_relu` arguments of the C ABI (include/jvae_hip.h): 0 = none, 1 = ReLU, 2 = leaky ReLU with
 // PyTorch's default negative slope - the reference's activation='leaky' is nn.LeakyReLU() (module/vae_layers/misc.py:24-27).
 // max(x, slope * x) is x for x > 0 and slope * x otherwise: the same product and the same bits as torch's select.

@@ -40,12 +40,6 @@
 #define DOSE_STATUS_QUERY 0x10000
 #define DOSE_K (-0.72134752044448170368)      // -log2(e) / 2
 
-__device__ __forceinline__ double dose_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // part[(s, slab)] = the sum over the slab of b (centre == nullptr) or of (b - centre[s])^2
 __global__ __launch_bounds__(DOSE_BLOCK) void dose_rowsum_kernel(const float* __restrict__ bank, const double* __restrict__ centre,
                                                                  double* __restrict__ part, long M, int* status) {
@@ -63,7 +57,7 @@ __global__ __launch_bounds__(DOSE_BLOCK) void dose_rowsum_kernel(const float* __
         acc = centre ? fma(d, d, acc) : acc + d;
     }
     if (!finite && !centre) atomicOr(status, 1 << s);
-    acc = dose_wave_sum(acc);
+    acc = wave_sum64(acc);
     if (lane == 0) red[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -45,25 +45,6 @@ constexpr int EMB_PCA_MAX_SLABS = 8;
 
 inline size_t emb_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-__device__ __forceinline__ double emb_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// fixed-order sum over a workgroup (a multiple of 64 threads, at most 1024): butterfly inside each wave, then the waves in
-// sequence; valid in every thread.  red: 16 doubles of LDS.  Contains barriers.
-__device__ __forceinline__ double emb_block_sum(double v, double* red) {
-    v = emb_wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int i = 1; i < nw; ++i) r += red[i];
-    return r;
-}
-
 // ------------------------------------------------------------------------------------------------- pairwise distances
 constexpr int PD_TILE = 16, PD_KC = 64;
 __global__ __launch_bounds__(PD_TILE* PD_TILE) void emb_sqdist_kernel(const float* __restrict__ x, float* __restrict__ d, int N,
@@ -112,8 +93,8 @@ __global__ __launch_bounds__(EMB_BLOCK) void emb_search_kernel(const float* __re
             s += p;
             sd += (double)dist * p;
         }
-        s = emb_wave_sum(s);
-        sd = emb_wave_sum(sd);
+        s = wave_sum64(s);
+        sd = wave_sum64(sd);
         __syncthreads();
         if (lane == 0) { red[0][w] = s; red[1][w] = sd; }
         __syncthreads();
@@ -134,7 +115,7 @@ __global__ __launch_bounds__(EMB_BLOCK) void emb_search_kernel(const float* __re
     double rs = 0.;
     for (int j = t; j < N; j += EMB_BLOCK)
         if (j != i) rs += exp((double)(-emb_row[j]) * used) / S;
-    rs = emb_wave_sum(rs);
+    rs = wave_sum64(rs);
     __syncthreads();
     if (lane == 0) red[0][w] = rs;
     __syncthreads();
@@ -151,7 +132,7 @@ __global__ __launch_bounds__(1024) void emb_total_kernel(const double* __restric
     __shared__ double red[16];
     double s = 0.;
     for (int i = threadIdx.x; i < n; i += 1024) s += v[(size_t)i * stride];
-    s = emb_block_sum(s, red);
+    s = block_sum64(s, red);
     if (threadIdx.x == 0) out[0] = scale * s;
 }
 
@@ -209,12 +190,12 @@ __global__ __launch_bounds__(EMB_BLOCK) void emb_pairs_kernel(const float* __res
             }
         }
     }
-    a0 = emb_wave_sum(a0);
+    a0 = wave_sum64(a0);
     if (KL) {
         if (valid && lane == 0) rows[i] = a0;
         return;
     }
-    a1 = emb_wave_sum(a1); b0 = emb_wave_sum(b0); b1 = emb_wave_sum(b1); z = emb_wave_sum(z);
+    a1 = wave_sum64(a1); b0 = wave_sum64(b0); b1 = wave_sum64(b1); z = wave_sum64(z);
     if (valid && lane == 0) {
         double* r = rows + 5 * (size_t)i;
         r[0] = a0; r[1] = a1; r[2] = b0; r[3] = b1; r[4] = z;
@@ -227,7 +208,7 @@ __global__ __launch_bounds__(1024) void emb_grad_fold_kernel(const double* __res
     __shared__ double red[16];
     double s = 0.;
     for (int i = threadIdx.x; i < N; i += 1024) s += rows[5 * (size_t)i + 4];
-    const double Z = emb_block_sum(s, red);
+    const double Z = block_sum64(s, red);
     if (threadIdx.x == 0) zsum[0] = Z;
     for (int i = threadIdx.x; i < N; i += 1024) {
         const double* r = rows + 5 * (size_t)i;
@@ -244,7 +225,7 @@ __global__ __launch_bounds__(1024) void emb_stats_kernel(const double* __restric
     if (stat_kl) {
         double s = 0.;
         for (int i = threadIdx.x; i < N; i += 1024) s += kl[i];
-        s = emb_block_sum(s, red);
+        s = block_sum64(s, red);
         if (threadIdx.x == 0) stat_kl[0] = s;
     }
     double q = 0.;
@@ -252,7 +233,7 @@ __global__ __launch_bounds__(1024) void emb_stats_kernel(const double* __restric
         const double v = (double)g[i];
         q += v * v;
     }
-    q = emb_block_sum(q, red);
+    q = block_sum64(q, red);
     if (threadIdx.x == 0) stat_norm[0] = sqrt(q);
 }
 

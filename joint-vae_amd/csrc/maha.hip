@@ -52,12 +52,6 @@ __device__ __forceinline__ MahaRange maha_range(long M, int slabs, int s) {
     return r;
 }
 
-__device__ __forceinline__ double maha_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(MAHA_BLOCK) void maha_rows_kernel(const float* __restrict__ bank, const long long* __restrict__ labels,
                                                                int* __restrict__ rowcls, long M, int K, int C, int* status) {
     const long r = (long)blockIdx.x * MAHA_BLOCK + threadIdx.x;
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(MAHA_BLOCK) void maha_colsum_kernel(const float* __
         ++n;
     }
 #pragma unroll
-    for (int j = 0; j < MAHA_CT; ++j) acc[j] = maha_wave_sum(acc[j]);
+    for (int j = 0; j < MAHA_CT; ++j) acc[j] = wave_sum64(acc[j]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
     if (lane == 0) {
@@ -161,7 +155,7 @@ __global__ __launch_bounds__(MAHA_BLOCK) void maha_scatter_kernel(const float* _
     for (int a = 0; a < MAHA_T; ++a)
 #pragma unroll
         for (int b = 0; b < MAHA_T; ++b) {
-            const double t = maha_wave_sum(acc[a][b]);
+            const double t = wave_sum64(acc[a][b]);
             if (lane == 0) red[wave][a * MAHA_T + b] = t;
         }
     __syncthreads();

@@ -1598,6 +1598,50 @@ def read_back(fields):
     return {k: host[end - v.numel():end].reshape(tuple(v.shape)) for (k, v), end in zip(fields.items(), ends)}
 
 
+# ------------------------------------------------------------------------------------------- status words, aligned workspace
+# ONE mechanism for the device status words of the flagging ops: a family ('wim', 'knn', 'maha', 'ic', 'ssim', 'kde') has one
+# default word per device for the calls made without a word of their own; an op takes its word through `_status_word`, a
+# family's `X_check_status` reads through `_read_status` and raises for its own bits.
+_status = {}                 # (family, device index) -> the int32 default word, created cleared on first use
+
+
+def _status_word(family, device, status=None, what=None, noun=None):
+    """The word an op hands to its kernel: the family's default word on `device`, or the caller's `status` - an int32 tensor with
+    at least one element on that device, else JvaeHipError in the name of the op `what`, whose inputs are the `noun`."""
+    if status is None:
+        key = family, device.index if device.index is not None else torch.cuda.current_device()
+        if key not in _status:
+            _status[key] = torch.zeros(1, dtype=torch.int32, device=device)
+        return _status[key]
+    if not torch.is_tensor(status) or status.dtype != torch.int32 or status.numel() < 1 or status.device != device:
+        raise L.JvaeHipError(f'{what}: an int32 status word on the device of the {noun} expected')
+    return status
+
+
+def _read_status(family, status=None):
+    """status: the word given to an op (a tensor: read here - this is the synchronisation - and cleared when it was not zero), a
+    host value, or None for every default word of the family -> the OR of what was read.  Every word is read and cleared before
+    the caller raises anything."""
+    words = [w for (f, _), w in _status.items() if f == family] if status is None else [status]
+    seen = 0
+    for w in words:
+        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
+        if torch.is_tensor(w) and v:
+            w.zero_()
+        seen |= v
+    return seen
+
+
+def _aligned_ws(nbytes, device, align=8, what=None):
+    """(pointer, bytes) of at least `nbytes` of the stream's workspace from an `align`-byte boundary on.  With `what`, the name
+    of an op whose library call answers 0 bytes for sizes out of range, that answer is refused here."""
+    if what and not nbytes:
+        raise L.JvaeHipError(f'{what}: sizes out of range (unsupported configuration)')
+    ws = L.workspace(nbytes + align, device)
+    off = (-ws.data_ptr()) % align
+    return ws.data_ptr() + off, ws.numel() - off
+
+
 # ------------------------------------------------------------------------------------------- SCOD risk curves (csrc/scod.hip)
 SCOD_R_KINDS = {None: -1, 'zero': 0, 'half_y': 1, 'logmsp': 2, 'odin': 3}
 SCOD_G_KINDS = {None: -1, 'zero': 0, 'half': 1, 'neg': 2, 'plain': 3}
@@ -1658,10 +1702,7 @@ def scod_scores(specs, y_est, C, N, out=None, col=0, status=None):
             or not out.is_contiguous() or out.device != dev:
         raise L.JvaeHipError(f'scod_scores: a dense (>= {M}, >= {col} + {N}) fp32 buffer on {dev} expected')
     L.ptr(out)
-    if status is None:
-        status = wim_status(dev)
-    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-        raise L.JvaeHipError('scod_scores: an int32 status word on the device of the sources expected')
+    status = _status_word('wim', dev, status, 'scod_scores', 'sources')
     lib = L.load()
     for m0 in range(0, M, SCOD_MAX_ROWS):
         part = rows[m0:m0 + SCOD_MAX_ROWS]
@@ -1805,15 +1846,11 @@ def misclass_scores(src, specs, out=None, rows=None, col=0):
 # ------------------------------------------------------------------------------------------- WIM score rows (csrc/wim.hip)
 WIM_KINDS = {'Y': 0, 'SOFT_Y': 1, 'LSE_AT': 2, 'Y_AT': 3}
 WIM_MAX_SOURCES = 4
-_wim_status = {}             # device index -> the int32 status word `wim_scores` uses when the caller passes none
 
 
 def wim_status(device):
     """The per-device status word of `wim_scores` calls made without one of their own (created cleared, on first use)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _wim_status:
-        _wim_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _wim_status[idx]
+    return _status_word('wim', device)
 
 
 def wim_scores(sources, y_est, specs, out=None, rows=None, col=0, status=None):
@@ -1847,10 +1884,7 @@ def wim_scores(sources, y_est, specs, out=None, rows=None, col=0, status=None):
         if kind not in WIM_KINDS or not 0 <= int(s) < S or (kind in ('LSE_AT', 'Y_AT') and alts[int(s)] is None):
             raise L.JvaeHipError(f'wim_scores: unknown row ({s!r}, {kind!r}) or no alternate loss for it')
         flat += [int(s), WIM_KINDS[kind], r]
-    if status is None:
-        status = wim_status(dev)
-    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-        raise L.JvaeHipError('wim_scores: an int32 status word on the device of the sources expected')
+    status = _status_word('wim', dev, status, 'wim_scores', 'sources')
     src_p = (ctypes.c_void_p * S)(*[s.data_ptr() for s in srcs])
     alt_p = (ctypes.c_void_p * S)(*[None if a is None else a.data_ptr() for a in alts])
     fac = (ctypes.c_float * S)(*[float(f) for _, f, _ in sources])
@@ -1864,17 +1898,9 @@ def wim_check_status(status=None):
     """Raise JvaeHipError when a launch that takes a status word (`wim_scores`, `prior_sample`, `aggregate_scores` on votes) met
     a label outside [0, C).  status: the word given to the op (a device tensor: read here - this is the synchronisation - and
     cleared), a host value, or None for the per-device default words."""
-    if status is None:
-        words = list(_wim_status.values())
-    else:
-        words = [status]
-    for w in words:
-        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
-        if torch.is_tensor(w) and v:
-            w.zero_()
-        if v & 1:
-            raise L.JvaeHipError('a label outside [0, C) was met by wim_scores, prior_sample or aggregate_scores (the rows of '
-                                 'that sample are NaN)')
+    if _read_status('wim', status) & 1:
+        raise L.JvaeHipError('a label outside [0, C) was met by wim_scores, prior_sample or aggregate_scores (the rows of '
+                             'that sample are NaN)')
 
 
 def group_tally(values, group, sums, counts):
@@ -1933,10 +1959,7 @@ def prior_sample(eps, y, means, T, mode='unit', temperature=1., out=None, status
         out = torch.empty_like(eps)
     elif out.dtype != torch.float32 or out.shape != eps.shape or not out.is_contiguous() or out.device != dev:
         raise L.JvaeHipError(f'prior_sample: a dense fp32 output of shape {tuple(eps.shape)} on {dev} expected')
-    if status is None:
-        status = wim_status(dev)
-    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-        raise L.JvaeHipError('prior_sample: an int32 status word on the device of the noise expected')
+    status = _status_word('wim', dev, status, 'prior_sample', 'noise')
     L.check(L.load().jvae_prior_sample_f32(L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T), L.ptr(out), L.ptr(status), R, K, C,
                                            float(temperature), SAMPLE_MODES[mode], L.stream_ptr()), 'jvae_prior_sample_f32')
     return out
@@ -2119,10 +2142,7 @@ def aggregate_scores(sources, mode, factors=None, temps=(), post=True, a=False, 
     if not -1 <= int(slot) < nT or not (post or a or amax or argmax) or (mode == 'mean_soft' and (a or ((amax or argmax) and slot < 0))):
         raise L.JvaeHipError(f'aggregate_scores: nothing to write, slot {slot} outside the {nT} temperatures, or the aggregated '
                              'row of mode mean_soft (it has none) asked for')
-    if status is None:
-        status = wim_status(dev)
-    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-        raise L.JvaeHipError('aggregate_scores: an int32 status word on the device of the sources expected')
+    status = _status_word('wim', dev, status, 'aggregate_scores', 'sources')
     o_post = torch.empty((nT, C, N), dtype=torch.float32, device=dev) if post else None
     o_a = torch.empty((C, N), dtype=torch.float32, device=dev) if a else None
     o_max = torch.empty((N,), dtype=torch.float32, device=dev) if amax else None
@@ -2214,11 +2234,9 @@ def latent_moments(mu, log_var, group, sums, counts):
     if N == 0:
         return sums, counts
     lib = L.load()
-    nbytes = lib.jvae_latent_moments_workspace_bytes(N, K, G)
-    ws = L.workspace(nbytes + 8, mu.device)
-    off = (-ws.data_ptr()) % 8
+    ws = _aligned_ws(lib.jvae_latent_moments_workspace_bytes(N, K, G), mu.device)
     L.check(lib.jvae_latent_moments_f32(L.ptr(mu), L.ptr(log_var), None if group is None else L.ptr(_c(group)), L.ptr(sums),
-                                        L.ptr(counts), N, K, G, ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()),
+                                        L.ptr(counts), N, K, G, *ws, L.stream_ptr()),
             'jvae_latent_moments_f32')
     return sums, counts
 
@@ -2302,15 +2320,11 @@ KNN_MAX_DIM = 4096          # columns of the rows
 KNN_MAX_SPLITS = 1024
 KNN_STATUS_BANK = 1         # a bank row with a distance that is not finite was met (it is in no list)
 KNN_STATUS_QUERY = 2        # a query row with a non-finite element was met (its slots are NaN / -1)
-_knn_status = {}
 
 
 def knn_status(device):
     """The per-device status word of `knn` calls made without one of their own (created cleared, on first use)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _knn_status:
-        _knn_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _knn_status[idx]
+    return _status_word('knn', device)
 
 
 def _knn_sqnorms(x):
@@ -2359,18 +2373,13 @@ def knn(q, bank, sq, k, normalized=True, splits=0, status=None):
     idx = torch.empty((N, k), dtype=torch.int32, device=dev)
     if not N:
         return d2, idx
-    if status is None:
-        status = knn_status(dev)
-    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-        raise L.JvaeHipError('knn: an int32 status word on the device of the rows expected')
+    status = _status_word('knn', dev, status, 'knn', 'rows')
     lib = L.load()
     nbytes = lib.jvae_knn_workspace_bytes(N, M, K, k, splits)
     if not nbytes:
         raise L.JvaeHipError(f'knn: sizes out of range (N={N}, M={M}, K={K}, k={k})')
-    ws = L.workspace(nbytes + 4, dev)
-    off = (-ws.data_ptr()) % 4
     L.check(lib.jvae_knn_f32(L.ptr(q), L.ptr(_knn_sqnorms(q)), L.ptr(bank), L.ptr(sq), L.ptr(d2), L.ptr(idx), N, M, K, k,
-                             1 if normalized else 0, splits, L.ptr(status), ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()),
+                             1 if normalized else 0, splits, L.ptr(status), *_aligned_ws(nbytes, dev, 4), L.stream_ptr()),
             'jvae_knn_f32')
     return d2, idx
 
@@ -2378,15 +2387,11 @@ def knn(q, bank, sq, k, normalized=True, splits=0, status=None):
 def knn_check_status(status=None):
     """Raise ValueError for what `knn` flagged.  status: the word given to the op (a device tensor: read here - this is the
     synchronisation - and cleared), a host value, or None for the per-device default words."""
-    words = list(_knn_status.values()) if status is None else [status]
-    for w in words:
-        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
-        if torch.is_tensor(w) and v:
-            w.zero_()
-        if v & KNN_STATUS_QUERY:
-            raise ValueError('knn: a query row with a non-finite element was met (its distances are NaN, its indices -1)')
-        if v & KNN_STATUS_BANK:
-            raise ValueError('knn: a bank row at a non-finite distance was met (it is in no list)')
+    word = _read_status('knn', status)
+    if word & KNN_STATUS_QUERY:
+        raise ValueError('knn: a query row with a non-finite element was met (its distances are NaN, its indices -1)')
+    if word & KNN_STATUS_BANK:
+        raise ValueError('knn: a bank row at a non-finite distance was met (it is in no list)')
 
 
 # ------------------------------------------------------------ Mahalanobis scores over a latent bank (csrc/maha.hip)
@@ -2395,23 +2400,11 @@ MAHA_STATUS_LABEL = 1       # a bank row with a label outside [0, C) was met (it
 MAHA_STATUS_BANK = 2        # a bank row with a non-finite element was met (it is in no sum)
 MAHA_STATUS_QUERY = 4       # a query row with a non-finite element was met (its scores are NaN, its class -1)
 MAHA_FIT_KEYS = ('counts', 'means', 'mean0', 'W', 'W0', 'mu0_32', 'W32', 'm32', 'm0_32', 'cmap', 'shrinkage')
-_maha_status = {}
 
 
 def maha_status(device):
     """The per-device status word of `maha_moments` / `maha_scores` calls made without one of their own (created cleared)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _maha_status:
-        _maha_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _maha_status[idx]
-
-
-def _maha_word(status, dev, what):
-    if status is None:
-        status = maha_status(dev)
-    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-        raise L.JvaeHipError(f'{what}: an int32 status word on the device of the rows expected')
-    return status
+    return _status_word('maha', device)
 
 
 def maha_moments(bank, labels, num_classes, status=None):
@@ -2436,16 +2429,14 @@ def maha_moments(bank, labels, num_classes, status=None):
     dev = bank.device
     if labels.device != dev:
         raise L.JvaeHipError('maha_moments: bank and labels on one device expected')
-    status = _maha_word(status, dev, 'maha_moments')
+    status = _status_word('maha', dev, status, 'maha_moments', 'rows')
     out = {'counts': torch.empty(C, dtype=torch.int64, device=dev), 'means': torch.empty((C, K), dtype=torch.float64, device=dev),
            'mean0': torch.empty(K, dtype=torch.float64, device=dev), 'Sw': torch.empty((K, K), dtype=torch.float64, device=dev),
            'St': torch.empty((K, K), dtype=torch.float64, device=dev)}
     lib = L.load()
-    nbytes = lib.jvae_maha_moments_workspace_bytes(M, K, C)
-    ws = L.workspace(nbytes + 8, dev)
-    off = (-ws.data_ptr()) % 8
     L.check(lib.jvae_maha_moments_f32(L.ptr(bank), L.ptr(_c(labels)), M, K, C, *(L.ptr(out[k]) for k in out), L.ptr(status),
-                                      ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()), 'jvae_maha_moments_f32')
+                                      *_aligned_ws(lib.jvae_maha_moments_workspace_bytes(M, K, C), dev), L.stream_ptr()),
+            'jvae_maha_moments_f32')
     return out
 
 
@@ -2559,7 +2550,7 @@ def maha_scores(q, fit, per_class=False, status=None):
     rel = torch.empty(N, dtype=torch.float32, device=dev)
     pc = torch.empty((N, C), dtype=torch.float32, device=dev) if per_class else None
     if N:
-        status = _maha_word(status, dev, 'maha_scores')
+        status = _status_word('maha', dev, status, 'maha_scores', 'rows')
         L.check(L.load().jvae_maha_scores_f32(L.ptr(q), *(L.ptr(_c(t)) for t in ops_), L.ptr(d), L.ptr(cls), L.ptr(rel), L.ptr(pc),
                                               N, K, Cn, C, L.ptr(status), L.stream_ptr()), 'jvae_maha_scores_f32')
     return (d, cls, rel, pc) if per_class else (d, cls, rel)
@@ -2568,17 +2559,13 @@ def maha_scores(q, fit, per_class=False, status=None):
 def maha_check_status(status=None):
     """Raise ValueError for what `maha_moments` / `maha_scores` flagged.  status: the word given to the op (a device tensor: read
     here - this is the synchronisation - and cleared), a host value, or None for the per-device default words."""
-    words = list(_maha_status.values()) if status is None else [status]
-    for w in words:
-        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
-        if torch.is_tensor(w) and v:
-            w.zero_()
-        if v & MAHA_STATUS_QUERY:
-            raise ValueError('maha: a query row with a non-finite element was met (its scores are NaN, its class -1)')
-        if v & MAHA_STATUS_LABEL:
-            raise ValueError('maha: a bank row with a label outside [0, num_classes) was met (it is in no sum)')
-        if v & MAHA_STATUS_BANK:
-            raise ValueError('maha: a bank row with a non-finite element was met (it is in no sum)')
+    word = _read_status('maha', status)
+    if word & MAHA_STATUS_QUERY:
+        raise ValueError('maha: a query row with a non-finite element was met (its scores are NaN, its class -1)')
+    if word & MAHA_STATUS_LABEL:
+        raise ValueError('maha: a bank row with a label outside [0, num_classes) was met (it is in no sum)')
+    if word & MAHA_STATUS_BANK:
+        raise ValueError('maha: a bank row with a non-finite element was met (it is in no sum)')
 
 
 # ------------------------------------------------------------ input complexity: a lossless image code length (csrc/ic.hip)
@@ -2587,16 +2574,12 @@ IC_MAX_PIXELS = 1 << 20     # H W of an image: the 32-bit counters of a histogra
 IC_MODES = ('none', 'sub', 'up', 'average', 'paeth', 'med', 'stored')
 IC_STATUS_INEXACT = 1       # a pixel further than 1/64 from its 8-bit level was met (the length is the quantised image's)
 IC_STATUS_NONFINITE = 2     # an image with a non-finite pixel was met (its bits are NaN, its choice -1)
-_ic_status = {}
 _ic_tables = {}             # n = H W -> the host table log2(m!), m = 0 .. n + 256; (n, device) -> its upload
 
 
 def ic_status(device):
     """The per-device status word of `image_code_length` calls made without one of their own (created cleared)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _ic_status:
-        _ic_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _ic_status[idx]
+    return _status_word('ic', device)
 
 
 def ic_table(n, device=None):
@@ -2639,10 +2622,7 @@ def image_code_length(x, status=None):
     bits32 = torch.empty(N, dtype=torch.float32, device=dev)
     choice = torch.empty(N, dtype=torch.int32, device=dev)
     if N:
-        if status is None:
-            status = ic_status(dev)
-        if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-            raise L.JvaeHipError('image_code_length: an int32 status word on the device of the images expected')
+        status = _status_word('ic', dev, status, 'image_code_length', 'images')
         table = ic_table(H * W, dev)
         L.check(L.load().jvae_image_code_length_f32(L.ptr(x), N, C, H, W, L.ptr(table), table.numel(), L.ptr(bits), L.ptr(bits32),
                                                     L.ptr(choice), L.ptr(status), L.stream_ptr()), 'jvae_image_code_length_f32')
@@ -2653,13 +2633,7 @@ def ic_check_status(status=None):
     """Read and clear what `image_code_length` flagged and raise ValueError for a non-finite pixel; pixels off the 8-bit grid
     (IC_STATUS_INEXACT) are not an error.  status: the word given to the op (a device tensor: read here - this is the
     synchronisation - and cleared), a host value, or None for the per-device default words.  -> the OR of the words read."""
-    words = list(_ic_status.values()) if status is None else [status]
-    seen = 0
-    for w in words:
-        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
-        if torch.is_tensor(w) and v:
-            w.zero_()
-        seen |= v
+    seen = _read_status('ic', status)
     if seen & IC_STATUS_NONFINITE:
         raise ValueError('image_code_length: an image with a non-finite pixel was met (its bits are NaN, its choice -1)')
     return seen
@@ -2692,15 +2666,11 @@ SSIM_MAX_W = 128            # a strip of rows is staged at full width
 SSIM_MAX_H = 32768
 SSIM_STATUS_X = 1           # an image x[n] with a non-finite pixel was met (every [r, n] is NaN)
 SSIM_STATUS_Y = 2           # a draw y[r, n] with a non-finite pixel was met (that entry is NaN)
-_ssim_status = {}
 
 
 def ssim_status(device):
     """The per-device status word of `ssim` calls made without one of their own (created cleared)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _ssim_status:
-        _ssim_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _ssim_status[idx]
+    return _status_word('ssim', device)
 
 
 def ssim_strip_rows(H, W):
@@ -2737,10 +2707,7 @@ def ssim(x, x_reco, maps=False, status=None):
     out = torch.empty((2, R, N), dtype=torch.float32, device=dev)
     pix = torch.empty((R, N, H - 10, W - 10), dtype=torch.float32, device=dev) if maps else None
     if N and R:
-        if status is None:
-            status = ssim_status(dev)
-        if not torch.is_tensor(status) or status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-            raise L.JvaeHipError('ssim: an int32 status word on the device of the images expected')
+        status = _status_word('ssim', dev, status, 'ssim', 'images')
         L.check(L.load().jvae_ssim_f32(L.ptr(x), L.ptr(y), N, R, C, H, W, L.ptr(out[0]), L.ptr(out[1]), L.ptr(pix), L.ptr(status),
                                        L.stream_ptr()), 'jvae_ssim_f32')
     return (out[0], out[1], pix) if maps else (out[0], out[1])
@@ -2749,13 +2716,7 @@ def ssim(x, x_reco, maps=False, status=None):
 def ssim_check_status(status=None):
     """Read and clear what `ssim` flagged and raise ValueError for a non-finite pixel.  status: the word given to the op (a device
     tensor: read here - this is the synchronisation - and cleared), a host value, or None for the per-device default words."""
-    words = list(_ssim_status.values()) if status is None else [status]
-    seen = 0
-    for w in words:
-        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
-        if torch.is_tensor(w) and v:
-            w.zero_()
-        seen |= v
+    seen = _read_status('ssim', status)
     if seen & SSIM_STATUS_X:
         raise ValueError('ssim: an image with a non-finite pixel was met (the scores of all its draws are NaN)')
     if seen & SSIM_STATUS_Y:
@@ -2768,15 +2729,11 @@ DOSE_MAX_STATS = 8
 DOSE_MAX_BANK = 1 << 24     # values of a bank row
 DOSE_STATUS_QUERY = 1 << 16        # a query with a non-finite (or fp32-overflowing) element was met (-inf / NaN in its rows)
 DOSE_FIT_KEYS = ('z', 'centre', 'sigma', 'h1', 'hS', 'lognorm', 'M', 'S', 'bandwidth')
-_dose_status = {}
 
 
 def kde_status(device):
     """The per-device status word of `kde_logdensity` calls made without one of their own (created cleared)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _dose_status:
-        _dose_status[idx] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _dose_status[idx]
+    return _status_word('kde', device)
 
 
 def kde_partition():
@@ -2819,11 +2776,9 @@ def kde_fit(bank, bandwidth=1.0):
            'lognorm': f64(S + 1)}
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     lib = L.load()
-    ws = L.workspace(lib.jvae_kde_fit_workspace_bytes(M, S) + 8, dev)
-    off = (-ws.data_ptr()) % 8
     factors = (ctypes.c_double * 3)(bandwidth, kde_scott(M, 1), kde_scott(M, S))       # a host array, read by the call
-    L.check(lib.jvae_kde_fit_f32(L.ptr(bank), M, S, factors, *(L.ptr(fit[k]) for k in fit),
-                                 L.ptr(status), ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()), 'jvae_kde_fit_f32')
+    L.check(lib.jvae_kde_fit_f32(L.ptr(bank), M, S, factors, *(L.ptr(fit[k]) for k in fit), L.ptr(status),
+                                 *_aligned_ws(lib.jvae_kde_fit_workspace_bytes(M, S), dev), L.stream_ptr()), 'jvae_kde_fit_f32')
     word = int(status[0])                                           # the synchronisation
     for s in range(S):
         if word >> s & 1:
@@ -2888,33 +2843,21 @@ def kde_logdensity(stats, fit, status=None):
     out = torch.empty((2 * S + 2, N), dtype=torch.float32, device=dev)
     if not N:
         return out
-    if status is None:
-        status = kde_status(dev)
-    if status.dtype != torch.int32 or status.numel() < 1 or status.device != dev:
-        raise L.JvaeHipError('kde_logdensity: an int32 status word on the device of the statistics expected')
+    status = _status_word('kde', dev, status, 'kde_logdensity', 'statistics')
     lib = L.load()
     nbytes = lib.jvae_kde_workspace_bytes(N, M, S)
     if not nbytes:
         raise L.JvaeHipError(f'kde_logdensity: sizes out of range (N={N}, M={M}, S={S})')
-    ws = L.workspace(nbytes + 8, dev)
-    off = (-ws.data_ptr()) % 8
     ratio2 = ctypes.c_double((kde_scott(M, 1) / kde_scott(M, S)) ** 2)     # (h1 / hS)^2: the same for every row; read by the call
     L.check(lib.jvae_kde_logdensity_f32(L.ptr(stats), *(L.ptr(_c(t)) for t in ops_), L.ptr(out), N, M, S, ctypes.byref(ratio2), L.ptr(status),
-                                        ws.data_ptr() + off, ws.numel() - off, L.stream_ptr()), 'jvae_kde_logdensity_f32')
+                                        *_aligned_ws(nbytes, dev), L.stream_ptr()), 'jvae_kde_logdensity_f32')
     return out
 
 
 def kde_check_status(status=None):
     """Raise JvaeHipError for what `kde_logdensity` flagged.  status: the word given to the op (a device tensor: read here - this
     is the synchronisation - and cleared), a host value, or None for the per-device default words."""
-    words = list(_dose_status.values()) if status is None else [status]
-    seen = 0
-    for w in words:                                                 # every word is read and cleared before anything is raised
-        v = int(w.reshape(-1)[0]) if torch.is_tensor(w) else int(w)
-        if torch.is_tensor(w) and v:
-            w.zero_()
-        seen |= v
-    if seen & DOSE_STATUS_QUERY:
+    if _read_status('kde', status) & DOSE_STATUS_QUERY:
         raise L.JvaeHipError('kde_logdensity: a query with a non-finite statistic, or one so far from the bank that its square '
                              'overflows fp32, was met (its rows hold -inf / NaN)')
 
@@ -2923,14 +2866,6 @@ def kde_check_status(status=None):
 EMBED_MAX_N = 16384         # points of a t-SNE: a row of fp32 distances in LDS
 EMBED_MAX_K = 1024          # dimensions of the points
 EMBED_MAX_COMPONENTS = 16
-
-
-def _embed_ws(nbytes, device, what):
-    if not nbytes:
-        raise L.JvaeHipError(f'{what}: sizes out of range (unsupported configuration)')
-    ws = L.workspace(nbytes + 8, device)
-    off = (-ws.data_ptr()) % 8
-    return ws.data_ptr() + off, ws.numel() - off
 
 
 def _embed_rows(x, what):
@@ -2960,7 +2895,7 @@ def tsne_affinities(d, perplexity):
     if d.shape[1] != N:
         raise L.JvaeHipError(f'tsne_affinities: a square (N, N) matrix expected, got {tuple(d.shape)}')
     lib = L.load()
-    ws, nbytes = _embed_ws(lib.jvae_tsne_affinities_workspace_bytes(N), d.device, 'tsne_affinities')
+    ws, nbytes = _aligned_ws(lib.jvae_tsne_affinities_workspace_bytes(N), d.device, what='tsne_affinities')
     P = torch.empty_like(d)
     beta = torch.empty(N, dtype=torch.float64, device=d.device)
     S = torch.empty(N, dtype=torch.float64, device=d.device)
@@ -2984,7 +2919,7 @@ def tsne_gradient(P, y, exaggeration=1., g=None, stats=None):
     if stats is not None and (stats.dtype != torch.float64 or tuple(stats.shape) != (2,) or stats.device != y.device):
         raise L.JvaeHipError('tsne_gradient: stats (2,) fp64 on the device of y expected')
     lib = L.load()
-    ws, nbytes = _embed_ws(lib.jvae_tsne_gradient_workspace_bytes(N), P.device, 'tsne_gradient')
+    ws, nbytes = _aligned_ws(lib.jvae_tsne_gradient_workspace_bytes(N), P.device, what='tsne_gradient')
     L.check(lib.jvae_tsne_gradient_f32(L.ptr(P), L.ptr(y), L.ptr(g), float(exaggeration), N, L.ptr(stats), ws, nbytes,
                                        L.stream_ptr()), 'jvae_tsne_gradient_f32')
     return g
@@ -3016,7 +2951,7 @@ def pca_moments(x):
     cov = torch.empty((K, K), dtype=torch.float64, device=x.device)
     if N < 2:
         raise L.JvaeHipError('pca_moments: at least two rows expected')
-    ws, nbytes = _embed_ws(lib.jvae_pca_moments_workspace_bytes(N, K), x.device, 'pca_moments')
+    ws, nbytes = _aligned_ws(lib.jvae_pca_moments_workspace_bytes(N, K), x.device, what='pca_moments')
     L.check(lib.jvae_pca_moments_f32(L.ptr(x), L.ptr(mean), L.ptr(cov), N, K, ws, nbytes, L.stream_ptr()), 'jvae_pca_moments_f32')
     return mean, cov
 

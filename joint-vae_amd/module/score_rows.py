@@ -24,85 +24,69 @@ Traits = namedtuple('Traits', 'losses_might_be_computed_for_each_class is_vae is
 # One family of RECORDED score rows: a model method computes them once per batch, the pass records them with the losses, reads
 # them back from a full recorder and copies them into the score buffer as they are.  prefix: a name that starts with it is the
 # family's (`_ood_methods` refuses it unless the model lists it); is_row: name without its thresholding suffix -> whether it is a
-# well-formed row (`parse` accepts nothing else); starred: the name that expands to the model's list; on, trait: whether the family
-# is switched on, from a model and from a Traits value; names, scores: the NAMES of the model methods (looked up at each call) that
-# list the rows and compute {row: (N,) scores} from the keywords `args` - `x`, `logits`, `losses` (the batch and its label-free
-# evaluation), `mu` (its posterior means); off, unlisted: the refusals where the family is off / the model does not list the name
-Family = namedtuple('Family', 'prefix is_row starred on trait names scores args off unlisted')
+# well-formed row (`parse` accepts nothing else); starred: the name that expands to the model's list; switch, types: the NAMES of
+# the model's opt-in switch and, if only some model types have the rows, of its tuple of those types - `on(model)` and
+# `trait(traits)` say whether the family is switched on, from a model and from a Traits value (no switch: `odin*`, on where the
+# type's own table lists it); names, scores: the NAMES of the model methods (looked up at each call) that list the rows and compute
+# {row: (N,) scores} from the keywords `args` - `x`, `logits`, `losses` (the batch and its label-free evaluation), `mu` (its
+# posterior means), `x_reco` (its reconstructions); off, unlisted: the refusals where the family is off / the model does not list
+# the name
+class Family(namedtuple('Family', 'prefix is_row starred switch types names scores args off unlisted')):
+    __slots__ = ()
 
-# in the order in which 'all' and the starred names expand and the per-batch calls run: FAMILIES, then IMAGE_FAMILIES, then
-# STAT_FAMILIES (`all_families()`), then RECO_FAMILIES (`every_family()`)
+    def on(self, model):
+        if self.switch is None:
+            return self.starred in model.ood_methods
+        return bool(getattr(model, self.switch)) and (self.types is None or model.type in getattr(model, self.types))
+
+    def trait(self, t):
+        return self.switch is None or getattr(t, self.switch)
+
+
+# in the order in which 'all' and the starred names expand and the per-batch calls run.  Callers read `score_rows.FAMILIES` at the
+# call: a test takes a family out by replacing the attribute
 FAMILIES = (
-    Family('odin', lambda m: m.startswith('odin'), 'odin*',                  # cvae.py:1076-1078, 1645-1663
-           lambda model: 'odin*' in model.ood_methods, lambda t: True, '_odin_names', 'odin_scores', ('x',),
+    Family('odin', lambda m: m.startswith('odin'), 'odin*', None, None,      # cvae.py:1076-1078, 1645-1663
+           '_odin_names', 'odin_scores', ('x',),
            '{m}: spline-threshold (-a-x-y) and ODIN OOD methods are outside this build',
            '{m}: not on the ODIN grid of this model (ODIN_TEMPS x ODIN_EPS)'),
-    Family('regret', lambda m: m.startswith('regret-'), 'regret*',
-           lambda model: bool(model.OOD_REGRET_METHODS) and model.type in model.REGRET_TYPES, lambda t: t.OOD_REGRET_METHODS,
+    Family('regret', lambda m: m.startswith('regret-'), 'regret*', 'OOD_REGRET_METHODS', 'REGRET_TYPES',
            '_regret_names', 'regret_scores', ('x', 'logits', 'losses'),
            '{m}: the likelihood-regret rows are an opt-in (OOD_REGRET_METHODS) of the types {types}',
            '{m}: not among the (steps, lr) pairs of this model (REGRET_PARAMS)'),
-    Family('knn', lambda m: m.startswith('knn-') and m[4:].isdigit(), 'knn*',
-           lambda model: bool(model.OOD_KNN_METHODS), lambda t: t.OOD_KNN_METHODS, '_knn_names', 'knn_scores', ('mu',),
+    Family('knn', lambda m: m.startswith('knn-') and m[4:].isdigit(), 'knn*', 'OOD_KNN_METHODS', None,
+           '_knn_names', 'knn_scores', ('mu',),
            '{m}: the nearest-neighbour rows are an opt-in (OOD_KNN_METHODS)',
            '{m}: not among the neighbour counts of this model (KNN_K)'),
-    Family('maha', lambda m: m in ('maha', 'maha-rel'), 'maha*',
-           lambda model: bool(model.OOD_MAHA_METHODS), lambda t: t.OOD_MAHA_METHODS, '_maha_names', 'maha_scores', ('mu',),
+    Family('maha', lambda m: m in ('maha', 'maha-rel'), 'maha*', 'OOD_MAHA_METHODS', None,
+           '_maha_names', 'maha_scores', ('mu',),
            '{m}: the Mahalanobis rows are an opt-in (OOD_MAHA_METHODS)',
-           '{m}: not among the Mahalanobis rows of this model (`maha`; `maha-rel` with more than one fitted class)'))
-# ... and behind them the families that score the IMAGE and correct the model's own rows with it, in a table of their own: FAMILIES
-# holds the families that score a sample through the model, and its four entries are pinned as such
-IMAGE_FAMILIES = (
-    Family('ic-', lambda m: m in ('ic-bits', 'ic-elbo', 'ic-iws'), 'ic*',
-           lambda model: bool(model.OOD_IC_METHODS) and model.type in model.IC_TYPES, lambda t: t.OOD_IC_METHODS,
+           '{m}: not among the Mahalanobis rows of this model (`maha`; `maha-rel` with more than one fitted class)'),
+    Family('ic-', lambda m: m in ('ic-bits', 'ic-elbo', 'ic-iws'), 'ic*', 'OOD_IC_METHODS', 'IC_TYPES',
            '_ic_names', 'ic_scores', ('x', 'losses'),
            '{m}: the input-complexity rows are an opt-in (OOD_IC_METHODS) of the types with a decoder (IC_TYPES)',
-           '{m}: not among the input-complexity rows of this model (`ic-bits`, `ic-elbo`, `ic-iws`)'),)
-# ... and last the families that score a sample by how typical its STATISTICS - other rows of this catalogue - are of a training
-# set: they read the evaluation of the batch, not the image.  A third table: the two above are pinned as they are
-STAT_FAMILIES = (
-    Family('dose', lambda m: m == 'dose' or m.startswith('dose-'), 'dose*',
-           lambda model: bool(model.OOD_DOSE_METHODS) and model.type in model.DOSE_TYPES, lambda t: t.OOD_DOSE_METHODS,
+           '{m}: not among the input-complexity rows of this model (`ic-bits`, `ic-elbo`, `ic-iws`)'),
+    Family('dose', lambda m: m == 'dose' or m.startswith('dose-'), 'dose*', 'OOD_DOSE_METHODS', 'DOSE_TYPES',
            '_dose_names', 'dose_scores', ('logits', 'losses'),
            '{m}: the density-of-states rows are an opt-in (OOD_DOSE_METHODS) of the types of DOSE_TYPES',
            '{m}: not among the density-of-states rows of this model (`dose`, `dose-joint`, `dose-<stat>` and `dose-typ-<stat>` for '
-           'the statistics of DOSE_STATS)'),)
-# ... and the families that score the RECONSTRUCTION as an image, against the image it was decoded from.  A fourth table: the
-# three above and `all_families()` are pinned as they are
-RECO_FAMILIES = (
-    Family('ssim', lambda m: m in ('ssim', 'ssim-mu', 'ssim-cs'), 'ssim*',
-           lambda model: bool(model.OOD_SSIM_METHODS) and model.type in model.SSIM_TYPES, lambda t: t.OOD_SSIM_METHODS,
+           'the statistics of DOSE_STATS)'),
+    Family('ssim', lambda m: m in ('ssim', 'ssim-mu', 'ssim-cs'), 'ssim*', 'OOD_SSIM_METHODS', 'SSIM_TYPES',
            '_ssim_names', 'ssim_scores', ('x', 'x_reco'),
            '{m}: the SSIM rows are an opt-in (OOD_SSIM_METHODS) of the types with a decoder (SSIM_TYPES)',
-           '{m}: not among the SSIM rows of this model (`ssim`, `ssim-mu`, `ssim-cs`)'),)
+           '{m}: not among the SSIM rows of this model (`ssim`, `ssim-mu`, `ssim-cs`)'))
 ODIN = FAMILIES[0]
 odin_name = (ODIN.prefix + '-{:.0f}-{:.4f}').format            # (T, eps) -> `odin-T-eps` as the reference formats it (cvae.py:124-127)
 
 
-def families():
-    """The families that score a sample through the model or its image, in the order of expansion: the first two tables as they
-    are at the call."""
-    return tuple(FAMILIES) + tuple(IMAGE_FAMILIES)
-
-
-def all_families():
-    """Every family of recorded rows, in the order of expansion: the three tables as they are at the call."""
-    return families() + tuple(STAT_FAMILIES)
-
-
-def every_family():
-    """Every family of recorded rows, the ones that score the reconstruction last: the four tables as they are at the call."""
-    return all_families() + tuple(RECO_FAMILIES)
-
-
 def claimed_by(name):
     """The family whose prefix claims `name` (or whose starred name it is), or None."""
-    return next((f for f in every_family() if name.startswith(f.prefix) or name == f.starred), None)
+    return next((f for f in FAMILIES if name.startswith(f.prefix) or name == f.starred), None)
 
 
 def recorded_by(name):
     """The family `name` (no thresholding suffix) is a well-formed row of, or None."""
-    for f in every_family():
+    for f in FAMILIES:
         if f.is_row(name):
             return f
 

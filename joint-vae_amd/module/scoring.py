@@ -229,6 +229,43 @@ class ScoringMixin:
         """The `knn-<k>` method names of this instance's `KNN_K`, in their order."""
         return ['knn-{:d}'.format(int(k)) for k in self.KNN_K]
 
+    @staticmethod
+    def _seeded_subset(n, ratio, seed, who):
+        """The seeded random subset of the fitted stores -> (keep, M): a host bool mask of n samples with round(ratio * n) (at
+        least one) set, from a torch.Generator permutation, or None for ratio = 1 (all n); M: how many are kept."""
+        if not 0 < ratio <= 1:
+            raise ValueError(f'{who}: a ratio in (0, 1] expected, got {ratio}')
+        if ratio == 1:
+            return None, n
+        keep = torch.zeros(n, dtype=torch.bool)
+        keep[torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))[:max(1, int(round(ratio * n)))]] = True
+        return keep, int(keep.sum())
+
+    def _save_store(self, attr, file_name, dir_name, nothing):
+        """Write the fitted store `attr` as `file_name` into `dir_name`, its tensors on the host -> the path."""
+        store = getattr(self, attr)
+        if store is None:
+            raise ValueError(nothing)
+        os.makedirs(dir_name, exist_ok=True)
+        path = os.path.join(dir_name, file_name)
+        torch.save({k: v.cpu() if torch.is_tensor(v) else v for k, v in store.items()}, path)
+        return path
+
+    def _load_store(self, attr, file_name, dir_name, check):
+        """Read `file_name` of `dir_name` on the host, have `check(d)` raise for what is not this store, and set `attr` to it with
+        its tensors on the model's device -> the store."""
+        d = torch.load(os.path.join(dir_name, file_name), map_location='cpu')
+        check(d)
+        setattr(self, attr, {k: v.to(self.device).contiguous() if torch.is_tensor(v) else v for k, v in d.items()})
+        return getattr(self, attr)
+
+    def _refuse_types(self, who, types, more='', why=None):
+        """NotImplementedError for a model of another type than `types` or with coded labels, or for the caller's own reason `why`."""
+        if self.type not in types or self.y_is_coded:
+            why = f'not type {self.type}' + (' with coded labels' if self.y_is_coded else '')
+        if why:
+            raise NotImplementedError(f'{who}: built for models without coded labels of the types {", ".join(types)}{more}, {why}')
+
     def fit_latent_bank(self, dataset, batch_size=100, ratio=1.0, seed=0):
         """Fill `latent_bank` with the posterior means of `dataset` (any map-style dataset of (x, label)): one latent_posterior()
         pass in eval mode, each batch's `mu` written straight into a preallocated (M, K) fp32 device tensor, the labels beside
@@ -238,15 +275,7 @@ class ScoringMixin:
         if self.y_is_coded:
             raise NotImplementedError('fit_latent_bank: latent_posterior(x) without labels is not possible for models with coded '
                                       'labels (their encoder reads y)')
-        n = len(dataset)
-        if not 0 < ratio <= 1:
-            raise ValueError(f'fit_latent_bank: a ratio in (0, 1] expected, got {ratio}')
-        keep = None
-        if ratio < 1:
-            perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
-            keep = torch.zeros(n, dtype=torch.bool)
-            keep[perm[:max(1, int(round(ratio * n)))]] = True
-        M = n if keep is None else int(keep.sum())
+        keep, M = self._seeded_subset(len(dataset), ratio, seed, 'fit_latent_bank')
         device = self.device
         was_training = self.training
         self.eval()
@@ -278,21 +307,15 @@ class ScoringMixin:
 
     def save_latent_bank(self, dir_name):
         """Write the fitted bank as `latent-bank.pth` into `dir_name` (a file of its own: save() / load() do not know it)."""
-        if self.latent_bank is None:
-            raise ValueError('save_latent_bank: no bank is fitted (fit_latent_bank)')
-        os.makedirs(dir_name, exist_ok=True)
-        path = os.path.join(dir_name, self.LATENT_BANK_FILE)
-        torch.save({k: v.cpu() if torch.is_tensor(v) else v for k, v in self.latent_bank.items()}, path)
-        return path
+        return self._save_store('latent_bank', self.LATENT_BANK_FILE, dir_name, 'save_latent_bank: no bank is fitted (fit_latent_bank)')
 
     def load_latent_bank(self, dir_name):
         """Read `latent-bank.pth` of `dir_name` onto the model's device -> the bank's dictionary, bit for bit what was saved."""
-        d = torch.load(os.path.join(dir_name, self.LATENT_BANK_FILE), map_location='cpu')
-        if set(d) != {'bank', 'sq', 'labels', 'set'} or d['bank'].dtype != torch.float32 or d['bank'].dim() != 2 \
-                or tuple(d['sq'].shape) != (d['bank'].shape[0],) or tuple(d['labels'].shape) != (d['bank'].shape[0],):
-            raise ValueError(f'load_latent_bank: {dir_name} does not hold a latent bank')
-        self.latent_bank = {k: v.to(self.device).contiguous() if torch.is_tensor(v) else v for k, v in d.items()}
-        return self.latent_bank
+        def check(d):
+            if set(d) != {'bank', 'sq', 'labels', 'set'} or d['bank'].dtype != torch.float32 or d['bank'].dim() != 2 \
+                    or tuple(d['sq'].shape) != (d['bank'].shape[0],) or tuple(d['labels'].shape) != (d['bank'].shape[0],):
+                raise ValueError(f'load_latent_bank: {dir_name} does not hold a latent bank')
+        return self._load_store('latent_bank', self.LATENT_BANK_FILE, dir_name, check)
 
     def knn_scores(self, mu):
         """The nearest-neighbour rows of a batch of posterior means mu (N, K) for every k of `KNN_K`: {'knn-<k>': (N,) fp32 device
@@ -343,21 +366,16 @@ class ScoringMixin:
 
     def save_latent_gaussians(self, dir_name):
         """Write the fitted Gaussians as `latent-gaussians.pth` into `dir_name` (a file of its own: save() / load() do not know it)."""
-        if self.latent_gaussians is None:
-            raise ValueError('save_latent_gaussians: no Gaussians are fitted (fit_latent_gaussians)')
-        os.makedirs(dir_name, exist_ok=True)
-        path = os.path.join(dir_name, self.LATENT_GAUSSIANS_FILE)
-        torch.save({k: v.cpu() if torch.is_tensor(v) else v for k, v in self.latent_gaussians.items()}, path)
-        return path
+        return self._save_store('latent_gaussians', self.LATENT_GAUSSIANS_FILE, dir_name,
+                                'save_latent_gaussians: no Gaussians are fitted (fit_latent_gaussians)')
 
     def load_latent_gaussians(self, dir_name):
         """Read `latent-gaussians.pth` of `dir_name` onto the model's device -> the dictionary, bit for bit what was saved."""
-        d = torch.load(os.path.join(dir_name, self.LATENT_GAUSSIANS_FILE), map_location='cpu')
-        if not isinstance(d, dict) or set(d) != set(ops.MAHA_FIT_KEYS) | {'set'}:
-            raise ValueError(f'load_latent_gaussians: {dir_name} does not hold latent Gaussians')
-        ops.maha_check_fit(d, 'load_latent_gaussians')
-        self.latent_gaussians = {k: v.to(self.device).contiguous() if torch.is_tensor(v) else v for k, v in d.items()}
-        return self.latent_gaussians
+        def check(d):
+            if not isinstance(d, dict) or set(d) != set(ops.MAHA_FIT_KEYS) | {'set'}:
+                raise ValueError(f'load_latent_gaussians: {dir_name} does not hold latent Gaussians')
+            ops.maha_check_fit(d, 'load_latent_gaussians')
+        return self._load_store('latent_gaussians', self.LATENT_GAUSSIANS_FILE, dir_name, check)
 
     def maha_scores(self, mu):
         """The Mahalanobis rows of a batch of posterior means mu (N, K): {'maha': -d, 'maha-rel': -rel}, (N,) fp32 device tensors,
@@ -400,9 +418,7 @@ class ScoringMixin:
         the classes for a cvae), in nats; D = C H W; D log2 255 turns the density of x = q / 255 into the probability of its bin
         and is left out for output_distribution='categorical', whose likelihood is discrete already.  Models of another type
         than IC_TYPES or with coded labels are refused, as latent_posterior(x) refuses the latter."""
-        if self.type not in self.IC_TYPES or self.y_is_coded:
-            raise NotImplementedError(f'ic_scores: built for models without coded labels of the types {", ".join(self.IC_TYPES)}, '
-                                      f'not type {self.type}' + (' with coded labels' if self.y_is_coded else ''))
+        self._refuse_types('ic_scores', self.IC_TYPES)
         L = self.input_complexity(x)['bits']
         D = float(np.prod(tuple(self.input_shape)))
         traits = score_rows.traits_of(self)
@@ -432,15 +448,11 @@ class ScoringMixin:
     def _ssim_refuse(self, who):
         shape = tuple(self.input_shape)
         why = None
-        if self.type not in self.SSIM_TYPES or self.y_is_coded:
-            why = f'not type {self.type}' + (' with coded labels' if self.y_is_coded else '')
-        elif self.output_distribution == 'categorical':
+        if self.output_distribution == 'categorical':
             why = "not output_distribution='categorical' (its x_reco holds 256 levels per pixel)"
         elif len(shape) != 3 or min(shape[1:]) < ops.SSIM_WINDOW:
             why = f'the model reads {shape}'
-        if why:
-            raise NotImplementedError(f'{who}: built for models without coded labels of the types {", ".join(self.SSIM_TYPES)} that '
-                                      f'decode images (C, H, W) with min(H, W) >= {ops.SSIM_WINDOW}, {why}')
+        self._refuse_types(who, self.SSIM_TYPES, f' that decode images (C, H, W) with min(H, W) >= {ops.SSIM_WINDOW}', why)
 
     def ssim_scores(self, x, x_reco):
         """The SSIM rows of a batch: x (N, *input_shape) and x_reco (L + 1, N, *input_shape), what a label-free evaluate(x)
@@ -535,9 +547,7 @@ class ScoringMixin:
         return (['dose'] + ['dose-joint'] * (len(stats) > 1) + ['dose-' + s for s in stats] + ['dose-typ-' + s for s in stats])
 
     def _dose_refuse(self, who):
-        if self.type not in self.DOSE_TYPES or self.y_is_coded:
-            raise NotImplementedError(f'{who}: built for models without coded labels of the types {", ".join(self.DOSE_TYPES)}, '
-                                      f'not type {self.type}' + (' with coded labels' if self.y_is_coded else ''))
+        self._refuse_types(who, self.DOSE_TYPES)
 
     def _dose_stat_values(self, rows, logits, losses, out=None, col=0):
         """The statistics of a batch by their torch expressions, stacked: (S, N) fp32 (into out[:, col:col + N] with `out`)."""
@@ -555,15 +565,7 @@ class ScoringMixin:
         refused, as the other families refuse the latter.  This call synchronises."""
         self._dose_refuse('fit_score_bank')
         rows = self._dose_stat_rows()
-        n = len(dataset)
-        if not 0 < ratio <= 1:
-            raise ValueError(f'fit_score_bank: a ratio in (0, 1] expected, got {ratio}')
-        keep = None
-        if ratio < 1:
-            perm = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
-            keep = torch.zeros(n, dtype=torch.bool)
-            keep[perm[:max(1, int(round(ratio * n)))]] = True
-        M = n if keep is None else int(keep.sum())
+        keep, M = self._seeded_subset(len(dataset), ratio, seed, 'fit_score_bank')
         device = self.device
         was_training = self.training
         self.eval()
@@ -594,27 +596,21 @@ class ScoringMixin:
 
     def save_score_bank(self, dir_name):
         """Write the fitted bank as `score-bank.pth` into `dir_name` (a file of its own: save() / load() do not know it)."""
-        if self.score_bank is None:
-            raise ValueError('save_score_bank: no bank is fitted (fit_score_bank)')
-        os.makedirs(dir_name, exist_ok=True)
-        path = os.path.join(dir_name, self.SCORE_BANK_FILE)
-        torch.save({k: v.cpu() if torch.is_tensor(v) else v for k, v in self.score_bank.items()}, path)
-        return path
+        return self._save_store('score_bank', self.SCORE_BANK_FILE, dir_name, 'save_score_bank: no bank is fitted (fit_score_bank)')
 
     def load_score_bank(self, dir_name):
         """Read `score-bank.pth` of `dir_name` onto the model's device -> the bank's dictionary, bit for bit what was saved.
         ValueError for a file that does not hold a score bank, and for one whose 'stats' are not this model's `DOSE_STATS`."""
-        d = torch.load(os.path.join(dir_name, self.SCORE_BANK_FILE), map_location='cpu')
-        if not isinstance(d, dict) or set(d) != set(ops.DOSE_FIT_KEYS) | {'stats', 'set'} or not isinstance(d['stats'], tuple):
-            raise ValueError(f'load_score_bank: {dir_name} does not hold a score bank')
-        ops.kde_check_fit(d, 'load_score_bank')
-        if len(d['stats']) != d['S']:
-            raise ValueError(f'load_score_bank: {dir_name} does not hold a score bank')
-        if d['stats'] != tuple(self.DOSE_STATS):
-            raise ValueError(f"load_score_bank: the bank was fitted on the statistics {d['stats']}, this model's DOSE_STATS are "
-                             f'{tuple(self.DOSE_STATS)}')
-        self.score_bank = {k: v.to(self.device).contiguous() if torch.is_tensor(v) else v for k, v in d.items()}
-        return self.score_bank
+        def check(d):
+            if not isinstance(d, dict) or set(d) != set(ops.DOSE_FIT_KEYS) | {'stats', 'set'} or not isinstance(d['stats'], tuple):
+                raise ValueError(f'load_score_bank: {dir_name} does not hold a score bank')
+            ops.kde_check_fit(d, 'load_score_bank')
+            if len(d['stats']) != d['S']:
+                raise ValueError(f'load_score_bank: {dir_name} does not hold a score bank')
+            if d['stats'] != tuple(self.DOSE_STATS):
+                raise ValueError(f"load_score_bank: the bank was fitted on the statistics {d['stats']}, this model's DOSE_STATS are "
+                                 f'{tuple(self.DOSE_STATS)}')
+        return self._load_store('score_bank', self.SCORE_BANK_FILE, dir_name, check)
 
     def dose_scores(self, logits, losses):
         """The density-of-states rows of a batch, `logits` and `losses` what a label-free evaluate(x) of it returned:
@@ -640,12 +636,12 @@ class ScoringMixin:
 
     def _ood_methods(self, method):
         """The score rows of ood_detection_rates: `method` = 'all' (this type's table minus what is not built, said in ONE log
-        line), a name or a list of names.  The recorded families (score_rows.every_family(): `odin*` on a type whose table lists
+        line), a name or a list of names.  The recorded families (score_rows.FAMILIES: `odin*` on a type whose table lists
         it, i.e. vib; the opt-ins `regret*`, `knn*`, `maha*`, `ic*`, `dose*` and `ssim*`): off, their names raise and 'all' does not hold them; on, 'all' and the starred
         name expand to the model's own list (the plain names first, the expansions behind them in the table's order, as the
         reference's develop_starred_methods orders them) and a single name has to be on that list.  The spline-threshold
         ('-a-x-y') methods raise unless `OOD_QUANTILE_METHODS` is set, with which they are rows like the others."""
-        families = score_rows.every_family()
+        families = score_rows.FAMILIES
         on = {f: f.on(self) for f in families}
 
         def refusal(m):                                         # why m is outside this build, or None
@@ -690,7 +686,7 @@ class ScoringMixin:
         device = self.device
         name = getattr(dset, 'name', 'set')
         records = [score_rows.parse(m, score_rows.traits_of(self)) for m in methods]
-        families = [f for f in score_rows.every_family() if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
+        families = [f for f in score_rows.FAMILIES if any(f.is_row(r.base) for r in records)]      # what this pass computes per batch
         with_mu = sample_recorder is not None or any('mu' in f.args for f in families)
         with_reco = any('x_reco' in f.args for f in families)   # the reconstructions of the same pass: no second decode
         filled, sums, measures = 0, {}, None
@@ -710,10 +706,10 @@ class ScoringMixin:
                     y = y.to(device)
                     if sample_recorder is not None:
                         sample_recorder.append_batch(**self._sample_record(sample_recorder, mu[0], y, losses))
+                    have = {'x': x, 'logits': logits, 'losses': losses, 'mu': mu[0] if mu else None, 'x_reco': x_reco}
                     for f in families:
                         # all rows of the family per batch (it is what the recorder holds), from the pass above, on the device
-                        have = {'x': x, 'logits': logits, 'losses': losses, 'mu': mu[0] if mu else None, 'x_reco': x_reco}
-                        losses = dict(losses, **getattr(self, f.scores)(**{a: have[a] for a in f.args}))
+                        have['losses'] = losses = dict(losses, **getattr(self, f.scores)(**{a: have[a] for a in f.args}))
                     if recording:
                         extra = {} if logits is None else {'logits': logits.T}
                         recorder.append_batch(**losses, y_true=y, **extra)

@@ -245,7 +245,7 @@ def test_rates(monkeypatch):
     torch.manual_seed(11)
     off_all = net.ood_detection_rates(method='all', **call)
     families = score_rows.FAMILIES
-    monkeypatch.setattr(score_rows, 'FAMILIES', families[:3])                          # the table as it was without the family
+    monkeypatch.setattr(score_rows, 'FAMILIES', tuple(f for f in families if f.prefix != 'maha'))      # the table without the family
     torch.manual_seed(11)
     assert net.ood_detection_rates(method='all', **call) == off_all                    # off: 'all' is bit for bit what it was
     monkeypatch.setattr(score_rows, 'FAMILIES', families)

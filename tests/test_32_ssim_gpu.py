@@ -234,11 +234,11 @@ def test_rates(monkeypatch, tmp_path):
     plain = net.ood_detection_rates(method=['elbo', 'mse'], **call)
     torch.manual_seed(11)
     off_all = net.ood_detection_rates(method='all', **call)
-    families = score_rows.RECO_FAMILIES
-    monkeypatch.setattr(score_rows, 'RECO_FAMILIES', ())                               # the tables as they were without the family
+    families = score_rows.FAMILIES
+    monkeypatch.setattr(score_rows, 'FAMILIES', tuple(f for f in families if f.prefix != 'ssim'))      # the table without the family
     torch.manual_seed(11)
     assert net.ood_detection_rates(method='all', **call) == off_all                    # off: 'all' is bit for bit what it was
-    monkeypatch.setattr(score_rows, 'RECO_FAMILIES', families)
+    monkeypatch.setattr(score_rows, 'FAMILIES', families)
     assert not any(m.startswith('ssim') for m in off_all['ood'])
 
     def record_keys(where, method=('elbo', 'mse')):
@@ -246,9 +246,9 @@ def test_rates(monkeypatch, tmp_path):
         net.ood_detection_rates(method=list(method), recorders={}, sample_dirs=[str(tmp_path / where)], **call)
         return {s.name: sorted(torch.load(tmp_path / where / f'record-{s.name}.pth', map_location='cpu',
                                                weights_only=False)['_tensors']) for s in sets}
-    monkeypatch.setattr(score_rows, 'RECO_FAMILIES', ())
+    monkeypatch.setattr(score_rows, 'FAMILIES', tuple(f for f in families if f.prefix != 'ssim'))
     without = record_keys('without')                                                   # a pass without the family
-    monkeypatch.setattr(score_rows, 'RECO_FAMILIES', families)
+    monkeypatch.setattr(score_rows, 'FAMILIES', families)
     assert record_keys('off') == without and not any(k.startswith('ssim') for k in without['ind'])
     net.OOD_SSIM_METHODS = True
     try:

@@ -41,35 +41,33 @@ def test_the_switch_is_off_by_default():
             net._ood_methods(m)
 
 
-def test_all_families_against_families():
+def test_the_family_in_the_table():
     from module import score_rows
-    assert [f.prefix for f in score_rows.families()] == ['odin', 'regret', 'knn', 'maha', 'ic-']
-    assert [f.prefix for f in score_rows.all_families()] == ['odin', 'regret', 'knn', 'maha', 'ic-', 'dose']
-    assert score_rows.all_families()[:5] == score_rows.families() and score_rows.all_families()[5:] == score_rows.STAT_FAMILIES
-    dose = score_rows.STAT_FAMILIES[0]
+    assert [f.prefix for f in score_rows.FAMILIES] == ['odin', 'regret', 'knn', 'maha', 'ic-', 'dose', 'ssim']
+    dose = score_rows.FAMILIES[5]
     assert (dose.starred, dose.names, dose.scores, dose.args) == ('dose*', '_dose_names', 'dose_scores', ('logits', 'losses'))
     assert dose.is_row('dose') and dose.is_row('dose-joint') and dose.is_row('dose-typ-kl') and not dose.is_row('dosed')
     assert score_rows.claimed_by('dose*') is dose and score_rows.claimed_by('dose-kl') is dose
     assert score_rows.recorded_by('dose-kl') is dose and score_rows.recorded_by('elbo') is None
-    # the tables are read at the call
-    tables = score_rows.STAT_FAMILIES
+    # the table is read at the call
+    table = score_rows.FAMILIES
     try:
-        score_rows.STAT_FAMILIES = ()
-        assert score_rows.all_families() == score_rows.families() and score_rows.claimed_by('dose') is None
+        score_rows.FAMILIES = tuple(f for f in table if f is not dose)
+        assert score_rows.FAMILIES == table[:5] + table[6:] and score_rows.claimed_by('dose') is None
     finally:
-        score_rows.STAT_FAMILIES = tables
+        score_rows.FAMILIES = table
 
 
 def test_all_with_the_switch_off_is_the_table_without_the_family():
     from module import score_rows
     net = make_net()
     with_family = net._ood_methods('all')
-    tables = score_rows.STAT_FAMILIES
+    table = score_rows.FAMILIES
     try:
-        score_rows.STAT_FAMILIES = ()
+        score_rows.FAMILIES = tuple(f for f in table if f.prefix != 'dose')
         assert net._ood_methods('all') == with_family
     finally:
-        score_rows.STAT_FAMILIES = tables
+        score_rows.FAMILIES = table
 
 
 def test_the_switch_on_expands_the_names_behind_the_other_families():

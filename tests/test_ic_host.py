@@ -28,19 +28,18 @@ def test_the_switch_is_off_by_default():
 def test_all_with_the_switch_off_is_the_table_without_the_family():
     from module import score_rows
     net = make_net()
-    assert [f.prefix for f in score_rows.families()] == ['odin', 'regret', 'knn', 'maha', 'ic-']
-    assert [f.prefix for f in score_rows.IMAGE_FAMILIES] == ['ic-'] and score_rows.families()[:4] == tuple(score_rows.FAMILIES)
-    ic = score_rows.families()[4]
+    assert [f.prefix for f in score_rows.FAMILIES] == ['odin', 'regret', 'knn', 'maha', 'ic-', 'dose', 'ssim']
+    ic = score_rows.FAMILIES[4]
     assert (ic.starred, ic.names, ic.scores, ic.args) == ('ic*', '_ic_names', 'ic_scores', ('x', 'losses'))
     assert all(ic.is_row(m) for m in NAMES) and not ic.is_row('ic-') and not ic.is_row('ic*') and not ic.is_row('ic-bits-2s')
     assert score_rows.claimed_by('ic-elbo') is ic and score_rows.claimed_by('ic*') is ic and score_rows.claimed_by('iws') is None
     with_family = net._ood_methods('all')
-    families = score_rows.IMAGE_FAMILIES
+    families = score_rows.FAMILIES
     try:
-        score_rows.IMAGE_FAMILIES = ()                       # the tables as they were before the family existed
+        score_rows.FAMILIES = tuple(f for f in families if f is not ic)      # the table as it was before the family existed
         assert net._ood_methods('all') == with_family
     finally:
-        score_rows.IMAGE_FAMILIES = families
+        score_rows.FAMILIES = families
     net.OOD_MAHA_METHODS = True
     assert net._ood_methods('all') == with_family + net._maha_names()
 

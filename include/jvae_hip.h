@@ -172,7 +172,8 @@ int jvae_channel_sum_f32(const float* t, float* out, int N, int C, int P, int ac
  * `relu` (here and as `in_relu` of the convolutions below) names the activation that follows the BatchNorm in the reference's stacks
  * (conv.py:214-220, misc.py:24-27), fused into these kernels: 0 none, 1 nn.ReLU, 2 nn.LeakyReLU() - negative slope 0.01, the
  * reference's activation='leaky' (round 5); any other non-zero value means ReLU.  Backward recomputes the mask from x.  The bf16
- * ("b8") entry points know 0 and 1 only. */
+ * ("b8") entry points know 0 and 1 only and refuse 2 with JVAE_ENOTSUP (-2) before they launch anything, as the bf16 convolutions
+ * refuse a leaky in_relu: nothing is written. */
 size_t jvae_bn_workspace_bytes(int C);
 /* Host-only (no GPU work): launch plan of the BatchNorm kernels - nsplit image parts for the reduction kernels, nchunk for the
  * apply kernels - and the image range [nb, ne) of part j out of `parts` (trailing parts may be EMPTY, nb == ne, never

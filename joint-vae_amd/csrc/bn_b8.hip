@@ -335,6 +335,7 @@ int jvae_bn_fwd_b8(const void* x, const float* gamma, const float* beta,
                    const float* ext_stats, int ext_nsplit, const float* ext_pivot,
                    void* ws, size_t ws_bytes, void* stream) {
     if (!x || !y || N < 0 || C <= 0 || HW <= 0) return JVAE_EINVAL;
+    if (relu == JVAE_ACT_LEAKY) return JVAE_ENOTSUP;          // these kernels know ReLU only: refused, never computed as ReLU
     hipStream_t st = (hipStream_t)stream;
     const int CB = (C + 7) / 8;
     float* coef = ws ? (float*)ws + (size_t)2 * CB * 8 * MAX_SPLIT_B8 : nullptr;      // no workspace: bn8_finalize refuses
@@ -366,6 +367,7 @@ int jvae_bn_bwd_b8(const void* dy, const void* x, const float* gamma, const floa
                    void* dx, float* dgamma, float* dbeta, int accumulate,
                    int N, int C, long HW, int relu, void* ws, size_t ws_bytes, void* stream) {
     if (!dy || !x || !save_mean || !save_invstd || !dx || N < 0 || C <= 0 || HW <= 0) return JVAE_EINVAL;
+    if (relu == JVAE_ACT_LEAKY) return JVAE_ENOTSUP;
     if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
     if (N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
@@ -414,6 +416,7 @@ int jvae_bn_fwd_sync_b8(const void* x, const float* gamma, const float* beta,
                         void* ws, size_t ws_bytes, void* stream) {
     if (!x || !y || !global_sums || !pivot || !save_mean || !save_invstd || world < 1 || N <= 0 || C <= 0 || HW <= 0)
         return JVAE_EINVAL;
+    if (relu == JVAE_ACT_LEAKY) return JVAE_ENOTSUP;
     if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int CB = (C + 7) / 8;
@@ -435,6 +438,7 @@ int jvae_bn_bwd_sums_b8(const void* dy, const void* x, const float* gamma, const
                         const float* save_mean, const float* save_invstd, float* local_sums,
                         int N, int C, long HW, int relu, void* ws, size_t ws_bytes, void* stream) {
     if (!dy || !x || !save_mean || !save_invstd || !local_sums || N <= 0 || C <= 0 || HW <= 0) return JVAE_EINVAL;
+    if (relu == JVAE_ACT_LEAKY) return JVAE_ENOTSUP;
     if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int CB = (C + 7) / 8;
@@ -456,6 +460,7 @@ int jvae_bn_bwd_sync_b8(const void* dy, const void* x, const float* gamma, const
                         int N, int C, long HW, int relu, void* ws, size_t ws_bytes, void* stream) {
     if (!dy || !x || !save_mean || !save_invstd || !local_sums || !global_sums || !dx || world < 1 || N <= 0 || C <= 0 || HW <= 0)
         return JVAE_EINVAL;
+    if (relu == JVAE_ACT_LEAKY) return JVAE_ENOTSUP;
     if (ws_bytes < jvae_bn_workspace_bytes_b8(C) || !ws) return JVAE_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int CB = (C + 7) / 8;

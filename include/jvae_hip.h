@@ -432,7 +432,8 @@ int jvae_latent_refine_f32(float* mu, float* lv_raw, float* lv, const float* eps
  *      (cvae.py:631-634)                                             (the ELBO kernels normalise, cvae.py:662-666)
  * Backward fills ALL L+1 rows of g_x_reco (row 0 with zeros); gsigma (may be NULL): 1 float (modes 0/1) or N floats (2).
  * sigma_fwd (mode 0, may be NULL): the value sigma had in the forward pass - the reference's decay rule changes the
- * parameter in place between forward and backward and its backward divides by sigma_fwd * sigma_now (layers.py:168). */
+ * parameter in place between forward and backward and its backward divides by sigma_fwd * sigma_now (layers.py:168).
+ * x_reco, x and g_x_reco 16-byte aligned when D % 4 == 0 (the float4 path; JVAE_EINVAL before any launch otherwise). */
 int jvae_recon_fwd_f32(const float* x_reco, const float* x, const float* sigma, int sigma_is_log,
                        float* wmse, int L, int N, int D, void* stream);
 int jvae_recon_bwd_f32(const float* x_reco, const float* x, const float* sigma, int sigma_is_log, const float* sigma_fwd,

@@ -156,8 +156,9 @@ int jvae_sqnorm_accum_f32(const float* g, long n, float* acc, int reset, void* w
 }
 
 int jvae_clip_scale_f32(float* g, long n, const float* sqnorm, float max_norm, void* stream) {
-    if (!g || !sqnorm || n < 0 || !(max_norm > 0.f)) return JVAE_EINVAL;
-    if (n == 0) return 0;
+    if (!sqnorm || n < 0 || !(max_norm > 0.f)) return JVAE_EINVAL;
+    if (n == 0) return 0;                    // an empty buffer has no address: as jvae_sqnorm_accum_f32 and the step entry points
+    if (!g) return JVAE_EINVAL;
     hipLaunchKernelGGL(clip_scale_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, g, n, sqnorm, max_norm);
     JVAE_LAUNCH_CHECK();
     return 0;

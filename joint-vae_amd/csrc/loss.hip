@@ -416,6 +416,7 @@ extern "C" {
 int jvae_recon_fwd_f32(const float* x_reco, const float* x, const float* sigma, int sigma_is_log,
                        float* wmse, int L, int N, int D, void* stream) {
     if (!x_reco || !x || !sigma || !wmse || L < 0 || N < 0 || D <= 0 || sigma_is_log < 0 || sigma_is_log > 3) return JVAE_EINVAL;
+    if ((D & 3) == 0 && (((uintptr_t)x_reco | (uintptr_t)x) & 15)) return JVAE_EINVAL;   // 16-byte loads, as jvae_mse_rows_*
     if (N == 0 || L == 0) return 0;
     hipLaunchKernelGGL(recon_fwd_kernel, dim3(N, L), dim3(256), 0, (hipStream_t)stream, x_reco, x, sigma, sigma_is_log,
                        wmse, L, N, D, 1);
@@ -454,6 +455,7 @@ int jvae_recon_bwd_f32(const float* x_reco, const float* x, const float* sigma, 
                        int L, int N, int D, void* ws, size_t ws_bytes, void* stream) {
     if (!x_reco || !x || !sigma || !g_wmse || !wmse || !g_x_reco || L < 0 || N < 0 || D <= 0) return JVAE_EINVAL;
     if (sigma_is_log < 0 || sigma_is_log > 3 || (sigma_is_log == SIG_RMSE && gsigma)) return JVAE_EINVAL;
+    if ((D & 3) == 0 && (((uintptr_t)x_reco | (uintptr_t)x | (uintptr_t)g_x_reco) & 15)) return JVAE_EINVAL;
     if (gsigma && (!ws || ws_bytes < sizeof(float) * (size_t)L * N)) return JVAE_EWORKSPACE;
     if (N == 0) return 0;
     hipStream_t st = (hipStream_t)stream;

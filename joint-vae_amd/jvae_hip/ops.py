@@ -1230,6 +1230,9 @@ class _Recon(torch.autograd.Function):
         Lp1, N = x_reco.shape[0], x_reco.shape[1]
         _check_sigma(sigma, mode, N)
         D = x.numel() // max(N, 1)
+        if D % 4 == 0:                                   # 16-byte loads: an odd view offset gets a copy (as _MseRows)
+            x_reco = x_reco if x_reco.data_ptr() % 16 == 0 else x_reco.clone()
+            x = x if x.data_ptr() % 16 == 0 else x.clone()
         wmse = torch.empty((Lp1 - 1, N), device=x.device, dtype=torch.float32)
         rc = L.load().jvae_recon_fwd_f32(L.ptr(x_reco), L.ptr(x), L.ptr(sigma), mode, L.ptr(wmse),
                                          Lp1 - 1, N, D, L.stream_ptr())

@@ -1037,6 +1037,36 @@ int jvae_ssim_f32(const float* x, const float* y, long N, long R, int C, int H, 
                   int* status, void* stream);
 int jvae_ssim_strip_rows(int H, int W);
 
+/* ---- log-density of the aggregate posterior of a bank of diagonal Gaussians (csrc/aggpost.hip; Hoffman & Johnson 2016, Chen et
+ * al. 2018; no counterpart in the reference) ----
+ * Bank: mu, log_var (N, K) fp32 and, for the conditional form, group (N,) int32 >= 0.  Prepare (once per bank): with Np =
+ * jvae_aggpost_padded_rows(N) (N rounded up to the row tile; 0 for N out of range; host only), muT, wT, lvT (K, Np) fp32 = mu,
+ * fp32(exp(-(double)log_var)) and log_var k-major (padding rows 0) and c (Np,) fp32 = fp32(sum_k (double)log_var), k ascending.
+ * Scores: z (M, K) fp32, zgroup (M,) int32 ->
+ *   logq (M,) fp32 = log 1/|S_m| sum_{n in S_m} N(z_m; mu_n, diag exp(log_var_n)), S_m all rows or, with conditional != 0, the rows
+ *   with group == zgroup[m] (zgroup and group may be NULL otherwise);
+ *   logq_dims (M, K) fp32 where not NULL: the same over S_m for each coordinate alone.
+ * A pair's exponent is -Q / 2 with Q = c_n + sum_k (z - mu)^2 w, the fmaf chain acc = fmaf(d * d, w, acc) from acc = c_n on, k
+ * ascending, d and d * d rounded on their own (a coordinate's: fmaf(d * d, w, log_var)).  Every sum is shifted by its smallest Q,
+ * the difference taken before the scaling: its largest term is exactly 1 and every output is finite for every finite query whose
+ * Q does not overflow fp32.  The bank is cut into pieces of jvae_aggpost_partition() rows whatever M is and every sum has a fixed
+ * order: bits hang on (N, K, the piece size) alone, a subset of the queries gives the bits of its rows, there are no
+ * floating-point atomics.  The end is fp64: -min Q / 2 + ln sum - ln |S_m| - (K / 2) ln 2 pi (K = 1 for a coordinate), rounded once.
+ * *status takes an integer OR: bit 0 a non-finite stored operand (mu, exp(-log_var) or c), bit 1 a query with a non-finite
+ * element (NaN -> NaN, +-inf -> -inf) or a finite one so far away that every Q overflows fp32 (-inf), bit 2 a query whose group
+ * has no bank row (-inf).  The caller owns and clears the word.  Two launches for logq, two more for logq_dims.
+ * ws: device scratch of jvae_aggpost_workspace_bytes(M, N, K, dims) = pieces M (8 + 4) + (dims ? pieces M K 8 : 0) bytes, pieces =
+ * ceil(N / partition), 8-byte aligned (-3 when smaller).  1 <= K <= 1024, 1 <= N <= 2^24 (at most 16384 pieces), M < 2^31, else
+ * -2 and a workspace size of 0; N < 1, K < 1, M < 0 or a missing pointer: -1.  M = 0 launches nothing. */
+int jvae_aggpost_partition(void);
+long jvae_aggpost_padded_rows(long N);
+int jvae_aggpost_prepare_f32(const float* mu, const float* log_var, float* muT, float* wT, float* lvT, float* c, long N, int K,
+                             void* stream);
+size_t jvae_aggpost_workspace_bytes(long M, long N, int K, int dims);
+int jvae_aggpost_logdensity_f32(const float* z, const int* zgroup, const float* muT, const float* wT, const float* lvT,
+                                const float* c, const int* group, float* logq, float* logq_dims, long M, long N, int K,
+                                int conditional, int* status, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

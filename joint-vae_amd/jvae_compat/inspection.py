@@ -80,6 +80,24 @@ def predicted_classes_text(n_pred, num_labels):
     return ''.join(rows)
 
 
+def elbo_decomposition_text(result):
+    """The table of `net.elbo_decomposition()`: one row per figure it gave (a figure that is None is left out), then one row per
+    class with queries (conditional priors) and one per coordinate (where the prior factorises)."""
+    names = ('kl', 'kl_mc', 'mi', 'mi_unconditional', 'mi_bound', 'kl_marginal', 'tc', 'dwkl')
+    rows = ['{:20} {:>14}\n'.format('which', 'nats')]
+    rows += [f'{k:20} {result[k]:-14.7e}\n' for k in names if result.get(k) is not None]
+    rows.append('{:20} {:14d}\n{:20} {:14d}\n'.format('n', int(result['n']), 'm', int(result['m'])))
+    per_class = result.get('per_class')
+    if per_class is not None:
+        rows.append('{:>6} {:>8} {:>14} {:>14}\n'.format('class', 'count', 'mi', 'kl_marginal'))
+        rows += [f'{c:6d} {int(n):8d} {per_class["mi"][c]:-14.7e} {per_class["kl_marginal"][c]:-14.7e}\n'
+                 for c, n in enumerate(per_class['count']) if n]
+    if result.get('dwkl_per_dim') is not None:
+        rows.append('{:>6} {:>14}\n'.format('dim', 'dwkl'))
+        rows += [f'{k:6d} {v:-14.7e}\n' for k, v in enumerate(result['dwkl_per_dim'])]
+    return ''.join(rows)
+
+
 def per_dim_statistics(sums, count):
     """sums (4, K) fp64 = the sums over `count` samples of mu, mu^2, v, v^2 (one group of `ops.latent_moments`) -> the columns
     of `mu_z_var_z.dat` in the reference's order: mean of mu^2, mean variance, their sum, mean of mu, unbiased std of the

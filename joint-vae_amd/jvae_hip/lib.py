@@ -201,6 +201,11 @@ _SIGS = {
     'jvae_kde_logdensity_f32': (c_int, [P] * 7 + [c_long, c_long, c_int, P, P, P, c_size_t, P]),
     'jvae_ssim_f32': (c_int, [P, P, c_long, c_long, c_int, c_int, c_int, P, P, P, P, P]),
     'jvae_ssim_strip_rows': (c_int, [c_int, c_int]),
+    'jvae_aggpost_partition': (c_int, []),
+    'jvae_aggpost_padded_rows': (c_long, [c_long]),
+    'jvae_aggpost_prepare_f32': (c_int, [P] * 6 + [c_long, c_int, P]),
+    'jvae_aggpost_workspace_bytes': (c_size_t, [c_long, c_long, c_int, c_int]),
+    'jvae_aggpost_logdensity_f32': (c_int, [P] * 9 + [c_long, c_long, c_int, c_int, P, P, c_size_t, P]),
 }
 
 

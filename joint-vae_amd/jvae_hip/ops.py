@@ -1602,7 +1602,7 @@ def read_back(fields):
 
 
 # ------------------------------------------------------------------------------------------- status words, aligned workspace
-# ONE mechanism for the device status words of the flagging ops: a family ('wim', 'knn', 'maha', 'ic', 'ssim', 'kde') has one
+# ONE mechanism for the device status words of the flagging ops: a family ('wim', 'knn', 'maha', 'ic', 'ssim', 'kde', 'aggpost') has one
 # default word per device for the calls made without a word of their own; an op takes its word through `_status_word`, a
 # family's `X_check_status` reads through `_read_status` and raises for its own bits.
 _status = {}                 # (family, device index) -> the int32 default word, created cleared on first use
@@ -2863,6 +2863,157 @@ def kde_check_status(status=None):
     if _read_status('kde', status) & DOSE_STATUS_QUERY:
         raise L.JvaeHipError('kde_logdensity: a query with a non-finite statistic, or one so far from the bank that its square '
                              'overflows fp32, was met (its rows hold -inf / NaN)')
+
+
+# ------------------------------------------------------------ the aggregate posterior of a bank of posteriors (csrc/aggpost.hip)
+AGGPOST_MAX_K = 1024
+AGGPOST_MAX_BANK = 1 << 24         # rows of a bank
+AGGPOST_MAX_PIECES = 1 << 14       # AGGPOST_MAX_BANK / aggpost_partition()
+AGGPOST_STATUS_BANK = 1            # a non-finite stored operand (mu, exp(-log_var) or the sum of a row's log_var)
+AGGPOST_STATUS_QUERY = 2           # a query with a non-finite element, or so far away that every exponent overflows fp32
+AGGPOST_STATUS_EMPTY = 4           # a query whose group has no bank row (-inf)
+AGGPOST_BANK_KEYS = ('mu', 'log_var', 'group', 'muT', 'wT', 'lvT', 'c')
+AGGPOST_WS_BYTES = 1 << 28         # queries are scored in runs whose workspace stays below this (bits do not hang on the run)
+
+
+def aggpost_status(device):
+    """The per-device status word of `aggpost_logdensity` calls made without one of their own (created cleared)."""
+    return _status_word('aggpost', device)
+
+
+def aggpost_partition():
+    """Bank rows of a piece of the kernel's fixed bank partition (a property of the build)."""
+    return int(L.load().jvae_aggpost_partition())
+
+
+def aggpost_bank(mu, log_var, group=None):
+    """The stored operands of a bank of N diagonal Gaussian posteriors N(mu_n, diag exp(log_var_n)): mu, log_var (N, K) fp32 on the
+    device, group (N,) int32 / int64 >= 0 or None (one group) -> {'mu', 'log_var' as given, 'group' (N,) int32, 'muT', 'wT', 'lvT'
+    (K, Np) fp32: mu, fp32(exp(-log_var)) (formed in fp64) and log_var k-major with the rows padded to the kernel's tile, 'c' (Np,)
+    fp32: the fp64 sum of a row's log_var, k ascending, rounded once}.  1 <= K <= AGGPOST_MAX_K, 1 <= N <= AGGPOST_MAX_BANK.  A
+    negative group is a ValueError (read here: this call synchronises when groups are given); non-finite elements are flagged by
+    the scoring call."""
+    for name, t in (('mu', mu), ('log_var', log_var)):
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise L.JvaeHipError(f'aggpost_bank: {name} (N, K) expected, got {tuple(t.shape) if torch.is_tensor(t) else type(t)}')
+        _f32(t, f'aggpost_bank: {name}')
+    if mu.shape != log_var.shape:
+        raise L.JvaeHipError(f'aggpost_bank: mu and log_var of one shape expected, got {tuple(mu.shape)} and {tuple(log_var.shape)}')
+    N, K = mu.shape
+    if not 1 <= K <= AGGPOST_MAX_K or not 1 <= N <= AGGPOST_MAX_BANK:
+        raise L.JvaeHipError(f'aggpost_bank: 1 <= K <= {AGGPOST_MAX_K} and 1 <= N <= 2^24 expected, got N={N}, K={K} (unsupported '
+                             'configuration)')
+    if group is not None:
+        if not torch.is_tensor(group) or group.dtype not in (torch.int32, torch.int64) or tuple(group.shape) != (N,):
+            raise L.JvaeHipError(f'aggpost_bank: group ({N},) int32 or int64 expected')
+    dev = mu.device
+    if log_var.device != dev or (group is not None and group.device != dev):
+        raise L.JvaeHipError('aggpost_bank: mu, log_var and group on one device expected')
+    mu, log_var = _c(mu), _c(log_var)
+    L.ptr(mu)
+    if group is None:
+        group = torch.zeros(N, dtype=torch.int32, device=dev)
+    else:
+        if int(group.min()) < 0:
+            raise ValueError('aggpost_bank: groups >= 0 expected')
+        group = _c(group.to(torch.int32))
+    lib = L.load()
+    Np = int(lib.jvae_aggpost_padded_rows(N))
+    muT, wT, lvT = (torch.empty((K, Np), dtype=torch.float32, device=dev) for _ in range(3))
+    c = torch.empty(Np, dtype=torch.float32, device=dev)
+    L.check(lib.jvae_aggpost_prepare_f32(L.ptr(mu), L.ptr(log_var), L.ptr(muT), L.ptr(wT), L.ptr(lvT), L.ptr(c), N, K, L.stream_ptr()),
+            'jvae_aggpost_prepare_f32')
+    return {'mu': mu, 'log_var': log_var, 'group': group, 'muT': muT, 'wT': wT, 'lvT': lvT, 'c': c}
+
+
+def aggpost_check_bank(bank, who='aggpost_logdensity'):
+    """Keys, dtypes, shapes and the one device of a bank of `aggpost_bank` -> (N, K); ValueError otherwise."""
+    def bad(why):
+        return ValueError(f'{who}: not a bank of aggpost_bank ({why})')
+    if not isinstance(bank, dict) or not set(AGGPOST_BANK_KEYS) <= set(bank):
+        raise bad('keys ' + ', '.join(AGGPOST_BANK_KEYS) + ' expected')
+    mu = bank['mu']
+    if not torch.is_tensor(mu) or mu.dtype != torch.float32 or mu.dim() != 2:
+        raise bad('mu: a (N, K) fp32 tensor expected')
+    N, K = mu.shape
+    if not 1 <= K <= AGGPOST_MAX_K or not 1 <= N <= AGGPOST_MAX_BANK:
+        raise bad(f'1 <= K <= {AGGPOST_MAX_K} and 1 <= N <= 2^24 expected, got N={N}, K={K}')
+    Np = int(L.load().jvae_aggpost_padded_rows(N))           # host only: N rounded up to the kernel's row tile
+    shapes = {'log_var': (N, K), 'group': (N,), 'muT': (K, Np), 'wT': (K, Np), 'lvT': (K, Np), 'c': (Np,)}
+    for k, shape in shapes.items():
+        dt = torch.int32 if k == 'group' else torch.float32
+        if not torch.is_tensor(bank[k]) or bank[k].dtype != dt:
+            raise bad(f'{k}: a {dt} tensor expected')
+        if tuple(bank[k].shape) != shape:
+            raise bad(f'{k}: {shape} expected, got {tuple(bank[k].shape)}')
+        if bank[k].device != mu.device:
+            raise bad(f'{k}: on the device of mu expected')
+    return N, K
+
+
+def aggpost_logdensity(z, bank, zgroup=None, conditional=False, dims=False, status=None):
+    """z (M, K) fp32 on the device against a bank of `aggpost_bank` -> (logq (M,) fp32, logq_dims (M, K) fp32 or None): logq =
+    log 1/|S_m| sum_{n in S_m} N(z_m; mu_n, diag exp(log_var_n)) with S_m the whole bank, or with `conditional` the rows whose
+    group is zgroup[m] ((M,) int32 / int64); with `dims` the same for each coordinate alone.  A pair's exponent is the direct form
+    -1/2 (sum_k log_var + sum_k (z - mu)^2 exp(-log_var)), an fp32 fmaf chain over k ascending; every sum is shifted by its
+    largest exponent (the difference taken before the scaling), so a query far from every bank row gets a finite value.  The bank
+    is partitioned in pieces of `aggpost_partition()` rows whatever M is: a query's bits do not depend on its batch, and a second
+    call returns the same bits (no floating-point atomics).  No (M, N) array exists: the workspace is O(M pieces), times K with
+    `dims`, and the queries are scored in runs that keep it below AGGPOST_WS_BYTES.  `status` (default `aggpost_status(device)`;
+    `aggpost_check_status`) takes AGGPOST_STATUS_BANK for a non-finite stored operand, AGGPOST_STATUS_QUERY for a query with a
+    non-finite element (NaN -> NaN, +-inf -> -inf) or one whose every exponent overflows fp32 (-inf), AGGPOST_STATUS_EMPTY for a
+    query whose group has no bank row (-inf).  M = 0 returns empty results without a launch; nothing is read back."""
+    N, K = aggpost_check_bank(bank)
+    if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] != K:
+        raise L.JvaeHipError(f'aggpost_logdensity: z (M, {K}) expected, got {tuple(z.shape) if torch.is_tensor(z) else type(z)}')
+    _f32(z, 'aggpost_logdensity: z')
+    M = z.shape[0]
+    if M >= 1 << 31:
+        raise L.JvaeHipError(f'aggpost_logdensity: M < 2^31 expected, got {M} (unsupported configuration)')
+    conditional = bool(conditional)
+    if conditional:
+        if not torch.is_tensor(zgroup) or zgroup.dtype not in (torch.int32, torch.int64) or tuple(zgroup.shape) != (M,):
+            raise L.JvaeHipError(f'aggpost_logdensity: the conditional form needs zgroup ({M},) int32 or int64')
+        if zgroup.device != z.device:
+            raise L.JvaeHipError('aggpost_logdensity: zgroup on the device of z expected')
+    elif zgroup is not None:
+        raise L.JvaeHipError('aggpost_logdensity: zgroup is read by the conditional form only (conditional=True)')
+    dev = z.device
+    if bank['mu'].device != dev:
+        raise L.JvaeHipError('aggpost_logdensity: the bank on the device of z expected')
+    z = _c(z)
+    L.ptr(z)
+    zg = _c(zgroup.to(torch.int32)) if conditional else None
+    logq = torch.empty(M, dtype=torch.float32, device=dev)
+    logq_dims = torch.empty((M, K), dtype=torch.float32, device=dev) if dims else None
+    if not M:
+        return logq, logq_dims
+    status = _status_word('aggpost', dev, status, 'aggpost_logdensity', 'queries')
+    lib = L.load()
+    run = max(64, AGGPOST_WS_BYTES // lib.jvae_aggpost_workspace_bytes(1, N, K, int(bool(dims))) // 64 * 64)
+    operands = [L.ptr(bank[k]) for k in ('muT', 'wT', 'lvT', 'c')]
+    for a in range(0, M, run):
+        b = min(M, a + run)
+        nbytes = lib.jvae_aggpost_workspace_bytes(b - a, N, K, int(bool(dims)))
+        L.check(lib.jvae_aggpost_logdensity_f32(L.ptr(z[a:b]), L.ptr(zg[a:b]) if conditional else None, *operands,
+                                                L.ptr(bank['group']) if conditional else None, L.ptr(logq[a:b]),
+                                                L.ptr(logq_dims[a:b]) if dims else None, b - a, N, K, int(conditional),
+                                                L.ptr(status), *_aligned_ws(nbytes, dev, what='aggpost_logdensity'), L.stream_ptr()),
+                'jvae_aggpost_logdensity_f32')
+    return logq, logq_dims
+
+
+def aggpost_check_status(status=None):
+    """Raise JvaeHipError for what `aggpost_logdensity` flagged.  status: the word given to the op (a device tensor: read here -
+    this is the synchronisation - and cleared), a host value, or None for the per-device default words."""
+    word = _read_status('aggpost', status)
+    if word & AGGPOST_STATUS_BANK:
+        raise L.JvaeHipError('aggpost_logdensity: the bank holds a non-finite operand (mu, exp(-log_var) or a row\'s sum of log_var)')
+    if word & AGGPOST_STATUS_QUERY:
+        raise L.JvaeHipError('aggpost_logdensity: a query with a non-finite element, or one so far from the bank that every '
+                             'exponent overflows fp32, was met (its outputs hold -inf / NaN)')
+    if word & AGGPOST_STATUS_EMPTY:
+        raise L.JvaeHipError('aggpost_logdensity: a query whose group has no bank row was met (its outputs hold -inf)')
 
 
 # ------------------------------------------------------------ 2-D projections: exact t-SNE and PCA (csrc/embed.hip)

@@ -266,20 +266,20 @@ class ScoringMixin:
         if why:
             raise NotImplementedError(f'{who}: built for models without coded labels of the types {", ".join(types)}{more}, {why}')
 
-    def fit_latent_bank(self, dataset, batch_size=100, ratio=1.0, seed=0):
-        """Fill `latent_bank` with the posterior means of `dataset` (any map-style dataset of (x, label)): one latent_posterior()
-        pass in eval mode, each batch's `mu` written straight into a preallocated (M, K) fp32 device tensor, the labels beside
-        it, then the rows' norms (ops.knn_bank).  ratio < 1: a seeded random subset of round(ratio * len) samples (a
-        torch.Generator permutation on the host, chosen before the pass; only the kept rows are stored, in the order of the
-        set).  -> the bank's dictionary.  Models with coded labels are refused, as latent_posterior(x) refuses them."""
+    def _posterior_rows(self, dataset, batch_size, ratio, seed, who):
+        """The pass of the fitted latent stores: one latent_posterior() pass over `dataset` in eval mode, each batch's mu and
+        log sigma^2 written straight into preallocated (M, K) fp32 device tensors, the labels beside them -> (mu, log_var,
+        labels).  ratio < 1: a seeded random subset of round(ratio * len) samples (a torch.Generator permutation on the host,
+        chosen before the pass; only the kept rows are stored, in the order of the set; a batch that keeps any row is encoded
+        whole).  Models with coded labels are refused, as latent_posterior(x) refuses them."""
         if self.y_is_coded:
-            raise NotImplementedError('fit_latent_bank: latent_posterior(x) without labels is not possible for models with coded '
+            raise NotImplementedError(f'{who}: latent_posterior(x) without labels is not possible for models with coded '
                                       'labels (their encoder reads y)')
-        keep, M = self._seeded_subset(len(dataset), ratio, seed, 'fit_latent_bank')
+        keep, M = self._seeded_subset(len(dataset), ratio, seed, who)
         device = self.device
         was_training = self.training
         self.eval()
-        bank, labels, seen, pos = None, torch.empty(M, dtype=torch.int64, device=device), 0, 0
+        mus, lvs, labels, seen, pos = None, None, torch.empty(M, dtype=torch.int64, device=device), 0, 0
         with torch.no_grad():
             for batch in self._batch_source(dataset, batch_size, False):
                 x, y = batch[:2]
@@ -287,21 +287,31 @@ class ScoringMixin:
                 seen += x.shape[0]
                 if sel is not None and not bool(sel.any()):
                     continue
-                mu = self.latent_posterior(self._device_batch(x.to(device)))[0]
+                mu, lv = self.latent_posterior(self._device_batch(x.to(device)))
                 y = y.to(device)
                 if sel is not None and not bool(sel.all()):       # the whole batch is encoded: the rows are those of a full pass
                     rows = sel.nonzero()[:, 0].to(device)
-                    mu, y = mu[rows], y[rows]
-                if bank is None:
-                    bank = torch.empty((M, mu.shape[1]), dtype=torch.float32, device=device)
-                bank[pos:pos + mu.shape[0]] = mu
+                    mu, lv, y = mu[rows], lv[rows], y[rows]
+                if mus is None:
+                    mus, lvs = (torch.empty((M, mu.shape[1]), dtype=torch.float32, device=device) for _ in range(2))
+                mus[pos:pos + mu.shape[0]] = mu
+                lvs[pos:pos + mu.shape[0]] = lv
                 labels[pos:pos + mu.shape[0]] = y
                 pos += mu.shape[0]
         if was_training:
             self.train()
-        if bank is None or pos != M:
-            raise ValueError(f'fit_latent_bank: the set yielded {pos} of the {M} rows expected')
-        bank, sq = ops.knn_bank(bank)
+        if mus is None or pos != M:
+            raise ValueError(f'{who}: the set yielded {pos} of the {M} rows expected')
+        return mus, lvs, labels
+
+    def fit_latent_bank(self, dataset, batch_size=100, ratio=1.0, seed=0):
+        """Fill `latent_bank` with the posterior means of `dataset` (any map-style dataset of (x, label)): one latent_posterior()
+        pass in eval mode, each batch's `mu` written straight into a preallocated (M, K) fp32 device tensor, the labels beside
+        it, then the rows' norms (ops.knn_bank).  ratio < 1: a seeded random subset of round(ratio * len) samples (a
+        torch.Generator permutation on the host, chosen before the pass; only the kept rows are stored, in the order of the
+        set).  -> the bank's dictionary.  Models with coded labels are refused, as latent_posterior(x) refuses them."""
+        mu, _, labels = self._posterior_rows(dataset, batch_size, ratio, seed, 'fit_latent_bank')
+        bank, sq = ops.knn_bank(mu)
         self.latent_bank = {'bank': bank, 'sq': sq, 'labels': labels, 'set': getattr(dataset, 'name', 'set')}
         return self.latent_bank
 
@@ -330,6 +340,131 @@ class ScoringMixin:
             raise ValueError(f"knn_scores: the bank holds {bank['bank'].shape[0]} rows, KNN_K = {tuple(ks)} needs 1 <= k <= rows")
         d2, _ = ops.knn(mu.float(), bank['bank'], bank['sq'], max(ks), normalized=bool(self.KNN_NORMALIZE))
         return {name: -d2[:, k - 1].sqrt() for name, k in zip(self._knn_names(), ks)}
+
+    # The aggregate posterior q(z) = 1/N sum_n q(z | x_n) of a set and the decomposition of the KL term it gives (Hoffman & Johnson
+    # 2016; Chen et al. 2018): the bank of `fit_posterior_bank` holds the posteriors (mu, log sigma^2) of a
+    # training set, `aggregate_logdensity` evaluates log q(z) (log q(z | y) given classes) of any codes under it in HIP
+    # (ops.aggpost_logdensity), `elbo_decomposition` splits the mean KL(q(z|x) || p(z|y)) into mutual information, the KL of the
+    # aggregate posterior to the prior, total correlation and dimension-wise KL.  No OOD row family: nothing here is a score row.
+    posterior_bank = None                     # {'mu', 'log_var' (N, K), 'labels' (N,), 'set'} and the operands of ops.aggpost_bank
+    POSTERIOR_BANK_FILE = 'posterior-bank.pth'
+    ELBO_TYPES = ('cvae', 'xvae', 'vae', 'vib', 'jvae')
+
+    def fit_posterior_bank(self, dataset, batch_size=100, ratio=1.0, seed=0):
+        """Fill `posterior_bank` with the posteriors of `dataset` (any map-style dataset of (x, label)): the pass of
+        `fit_latent_bank` (one latent_posterior() pass in eval mode into preallocated device tensors, its seeded subset and
+        whole-batch rule) keeping mu AND log sigma^2, then the stored operands of the density kernel (ops.aggpost_bank; the labels
+        are its groups).  -> the bank's dictionary.  Models with coded labels are refused, as latent_posterior(x) refuses them."""
+        mu, lv, labels = self._posterior_rows(dataset, batch_size, ratio, seed, 'fit_posterior_bank')
+        self.posterior_bank = dict(ops.aggpost_bank(mu, lv, labels), labels=labels, set=getattr(dataset, 'name', 'set'))
+        return self.posterior_bank
+
+    def save_posterior_bank(self, dir_name):
+        """Write the fitted bank as `posterior-bank.pth` into `dir_name` (a file of its own: save() / load() do not know it)."""
+        return self._save_store('posterior_bank', self.POSTERIOR_BANK_FILE, dir_name,
+                                'save_posterior_bank: no bank is fitted (fit_posterior_bank)')
+
+    def load_posterior_bank(self, dir_name):
+        """Read `posterior-bank.pth` of `dir_name` onto the model's device -> the bank's dictionary, bit for bit what was saved."""
+        def check(d):
+            try:
+                ok = isinstance(d, dict) and set(d) == set(ops.AGGPOST_BANK_KEYS) | {'labels', 'set'}
+                N, _ = ops.aggpost_check_bank(d, 'load_posterior_bank') if ok else (0, 0)
+                ok = ok and torch.is_tensor(d['labels']) and d['labels'].dtype == torch.int64 and tuple(d['labels'].shape) == (N,)
+            except ValueError:
+                ok = False
+            if not ok:
+                raise ValueError(f'load_posterior_bank: {dir_name} does not hold a posterior bank')
+        return self._load_store('posterior_bank', self.POSTERIOR_BANK_FILE, dir_name, check)
+
+    def _posterior_bank_for(self, who):
+        self._refuse_types(who, self.ELBO_TYPES)
+        if self.posterior_bank is None:
+            raise ValueError(f'{who}: no posterior bank is fitted (fit_posterior_bank or load_posterior_bank)')
+        return self.posterior_bank
+
+    def aggregate_logdensity(self, z, y=None, dims=False):
+        """log q(z) of codes z (M, K) under the aggregate posterior of the bank -> (logq (M,), logq_dims (M, K) or None), fp32
+        device tensors; with y (M,) labels: log q(z | y), the mixture of the bank rows of that class.  dims: the same for every
+        coordinate alone.  ValueError without a bank.  What the kernel flags (a class without bank rows, a non-finite code) is in
+        `ops.aggpost_status(device)` (`ops.aggpost_check_status`)."""
+        bank = self._posterior_bank_for('aggregate_logdensity')
+        z = z.to(device=bank['mu'].device, dtype=torch.float32)
+        if y is not None:
+            y = y.reshape(-1).to(z.device)
+        return ops.aggpost_logdensity(z, bank, zgroup=y, conditional=y is not None, dims=dims)
+
+    def elbo_decomposition(self, samples=None, seed=0, epsilon=None, dims=True):
+        """The mean KL term of the bank's set taken apart, from ONE draw z_m = mu_m + sigma_m eps_m of `samples` rows of the bank
+        (None: all of them in their order; else the first `samples` of a seeded host permutation); eps: `epsilon` (M, K) or a
+        seeded draw on the device.  Per query: log q(z|x) = -1/2 sum_k (eps^2 + log sigma^2 + log 2 pi) in fp64, log q(z) and the
+        per-coordinate log q(z_k) from the density kernel over the WHOLE bank, log p from the prior's log_density.  -> a dictionary
+        of host values (means in fp64 on the device, one read-back):
+          'kl' the mean analytic KL of the queried rows (the prior's kl()), 'kl_mc' mean[log q(z|x) - log p], 'mi' mean[log q(z|x) -
+          log q(z)], 'kl_marginal' mean[log q(z) - log p], 'tc' mean[log q(z) - sum_k log q(z_k)], 'dwkl' mean[sum_k log q(z_k) -
+          log p] and 'dwkl_per_dim' (K,) (None unless the prior is Gaussian with scalar or diagonal variance; tc and both None
+          without `dims`), 'mi_bound' log N, 'n', 'm'; kl_mc = mi + kl_marginal and kl_marginal = tc + dwkl by construction.
+        With a conditional prior (cvae, xvae) q(z) is q(z | y) of the row's class and p is p(z | y): mi is I(x; z | y), kl_marginal
+        the mean KL(q(z|y) || p(z|y)); 'per_class' holds (C,) 'mi', 'kl_marginal' and 'count' (NaN where a class has no query) and
+        'mi_unconditional' comes from a second launch against the bank as a whole.  'rows' (the queried rows, None for all) and 'z'
+        (M, K, on the device) are the queries themselves.  ValueError without a bank; coded labels are refused."""
+        bank = self._posterior_bank_for('elbo_decomposition')
+        prior = self.encoder.prior
+        N, K = bank['mu'].shape
+        dev = bank['mu'].device
+        if samples is None:
+            rows, mu, lv, y = None, bank['mu'], bank['log_var'], bank['labels']
+        else:
+            if not 1 <= int(samples) <= N:
+                raise ValueError(f'elbo_decomposition: 1 <= samples <= {N} (the rows of the bank) expected, got {samples}')
+            rows = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:int(samples)]
+            at = rows.to(dev)
+            mu, lv, y = bank['mu'][at], bank['log_var'][at], bank['labels'][at]
+        M = mu.shape[0]
+        if epsilon is None:
+            epsilon = torch.randn((M, K), generator=torch.Generator(device=dev).manual_seed(int(seed)), device=dev)
+        elif not torch.is_tensor(epsilon) or tuple(epsilon.shape) != (M, K):
+            raise ValueError(f'elbo_decomposition: epsilon ({M}, {K}) expected')
+        eps = epsilon.to(device=dev, dtype=torch.float32)
+        cond = bool(prior.conditional)
+        with torch.no_grad():
+            z = (mu + (0.5 * lv).exp() * eps).contiguous()
+            lqzx = -0.5 * (eps.double().square() + lv.double() + math.log(2 * math.pi)).sum(1)
+            logq, logq_dims = ops.aggpost_logdensity(z, bank, zgroup=y if cond else None, conditional=cond, dims=bool(dims))
+            logq = logq.double()
+            logp = prior.log_density(z, y if cond else None).double()
+            fields = {'kl': prior.kl(mu, lv, y if cond else None, output_dict=False).double().mean(), 'kl_mc': (lqzx - logp).mean(),
+                      'mi': (lqzx - logq).mean(), 'kl_marginal': (logq - logp).mean()}
+            factorised = prior.distribution == 'gaussian' and prior.var_dim in ('scalar', 'diag')
+            if dims:
+                qsum = logq_dims.double().sum(1)
+                fields['tc'] = (logq - qsum).mean()
+                if factorised:
+                    t = prior.inv_trans.detach().double()
+                    t = (t.reshape(-1, 1) if prior.var_dim == 'scalar' else t.reshape(-1, K)).expand(prior.num_priors if cond else 1, K)
+                    means = prior.mean.detach().double().reshape(-1, K)
+                    at = y if cond else torch.zeros(M, dtype=torch.int64, device=dev)
+                    logp_k = -0.5 * math.log(2 * math.pi) - 0.5 * ((z.double() - means[at]) * t[at]).square() + t[at].abs().log()
+                    fields['dwkl'] = (qsum - logp).mean()
+                    fields['dwkl_per_dim'] = (logq_dims.double() - logp_k).mean(0)
+            if cond:
+                C = prior.num_priors
+                count = torch.bincount(y, minlength=C).double()
+                fields['count'] = count
+                for name, v in (('mi_c', lqzx - logq), ('kl_marginal_c', logq - logp)):
+                    fields[name] = torch.zeros(C, dtype=torch.float64, device=dev).index_add_(0, y, v) / count
+                fields['mi_unconditional'] = (lqzx - ops.aggpost_logdensity(z, bank)[0].double()).mean()
+            host = ops.read_back(fields)
+        out = {k: float(host[k]) for k in ('kl', 'kl_mc', 'mi', 'kl_marginal')}
+        out['tc'] = float(host['tc']) if dims else None
+        out['dwkl'] = float(host['dwkl']) if 'dwkl' in host else None
+        out['dwkl_per_dim'] = host.get('dwkl_per_dim')
+        out.update(mi_bound=math.log(N), n=N, m=M)
+        if cond:
+            out['per_class'] = {'mi': host['mi_c'], 'kl_marginal': host['kl_marginal_c'], 'count': host['count'].astype(np.int64)}
+            out['mi_unconditional'] = float(host['mi_unconditional'])
+        out.update(rows=rows, z=z)
+        return out
 
     # The Mahalanobis rows `maha` and `maha-rel` (Lee et al. 2018; Ren et al. 2021; DESIGN.md section 7q): minus the squared
     # Mahalanobis distance from a sample's posterior mean to the nearest of the class Gaussians - one per class of the bank, with

@@ -1067,6 +1067,39 @@ int jvae_aggpost_logdensity_f32(const float* z, const int* zgroup, const float* 
                                 const float* c, const int* group, float* logq, float* logq_dims, long M, long N, int K,
                                 int conditional, int* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- importance-weighted bound of the training step, forward and backward (csrc/iwae.hip; Burda et al. 2016; no counterpart in
+ * the reference, whose `iws` (jvae_iws_f32) is an evaluation score without gradient) ----
+ * For sample n of class y[n] and the draws l = 1..L (row 0 of z, the mean latent, takes no part):
+ *   log w_l = -D/2 (wmse_s[l,n] + 2 log sigma + log 2pi) + beta (-1/2 |T_y (z_l - m_y)|^2 + sum_k log|t_yk| + 1/2 sum_k (eps_lk^2 + lv_k))
+ *   bound[n] = logsumexp_l(log w_l) - log L,   wt[l,n] = softmax_l(log w_l),   ess[n] = 1 / sum_l wt^2
+ * wmse_s (L, N), z (L+1, N, K), lv (N, K) the clipped log-variance, eps (L, N, K), y (N,) int64, means (C, K), T (C,) for var_dim 0
+ * and (C, K) for var_dim 1 (the whitening factor of GaussianPrior), sigma as jvae_elbo_fwd_f32 takes it (kinds 0 value, 1 log, 2
+ * coded).  log w is formed in fp64 (fixed-order sums) from these fp32 operands and never stored; what the fold reads is
+ * fp32(log w - max).  (wmse_s itself is an fp32 row, magnified by D/2: a weight is as good as that row, not better.)  Forward: ONE
+ * launch; the sum over l is shifted by its maximum, so every output is finite for finite inputs, and a draw that leads the others
+ * beyond the fp32 exponent range gives a wt that is exactly one-hot and ess exactly 1.  state (may be NULL): (4, N) fp64 = (max,
+ * shifted sum, shifted sum of squares, draws so far) of earlier slabs of draws, all zeros at the start; the slab is merged in
+ * exactly (one of the two scale factors is exp(0) = 1) and bound / ess are those of all draws so far (wt stays the slab's own
+ * softmax).
+ * Backward: g_bound (N,) (NULL: zeros) and the forward's wt -> the DIRECT partial derivatives g_wmse_s (L, N) = -g wt D/2, g_z
+ * (L+1, N, K) = -g wt beta T^T T (z - m) (row 0 zero), g_lv (N, K) = g beta/2 and, where not NULL, g_means (C, K), g_T (C, K; var_dim
+ * 1 only, else -1) and g_sigma (1 value for kinds 0 / 1, N for kind 2), all overwritten.  The class sums run in sample order over a
+ * fixed partition of 16 contiguous sample chunks and the sigma sum in a fixed order: no floating-point atomics, the same bits
+ * from run to run (each product chain and each sum in fp64, rounded once).  ws: jvae_iw_bound_bwd_workspace_bytes(N, K) bytes,
+ * 8-byte aligned, when any of the three is asked for (-3 when smaller).
+ * A label outside [0, C) is never an index: NaN in every output of that sample, nothing added to any class.
+ * prior != 0 (tilted, uniform), var_dim 2 (full) and sigma kind 3 (rmse): -2 before any launch.  L < 1, K < 1, C < 1, D < 1,
+ * N < 0, an unknown kind or a missing pointer: -1.  N = 0 launches nothing in the forward. */
+int jvae_iw_bound_fwd_f32(const float* wmse_s, const float* z, const float* lv, const float* eps, const long long* y,
+                          const float* means, const float* T, const float* sigma, int sigma_is_log, int prior, int var_dim,
+                          float beta, int L, int N, int K, int C, int D, float* bound, float* wt, float* ess, double* state,
+                          void* stream);
+size_t jvae_iw_bound_bwd_workspace_bytes(int N, int K);
+int jvae_iw_bound_bwd_f32(const float* g_bound, const float* wt, const float* z, const long long* y, const float* means,
+                          const float* T, const float* sigma, int sigma_is_log, int prior, int var_dim, float beta,
+                          int L, int N, int K, int C, int D, float* g_wmse_s, float* g_z, float* g_lv, float* g_means,
+                          float* g_T, float* g_sigma, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

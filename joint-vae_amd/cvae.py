@@ -31,6 +31,11 @@ structural similarity of a batch to its reconstructions, one launch of csrc/ssim
 Named data sets ('cifar10-3', 'mnist32r', 'svhn', ...: jvae_compat/torch_load.py, device-resident sets whose batches are one
 launch of csrc/imageset.hip) are an opt-in, `DATA_ROOT` (class attribute, settable per instance: the torchvision-style directory
 of the raw files); None, the default, keeps every refusal of a name as it was.
+TRAIN_OBJECTIVE = 'iwae' (class attribute, settable per instance; default 'elbo') trains on the importance-weighted bound of Burda et
+al. instead of the ELBO: the labelled training-mode evaluate() forms total = -bound from the draws, reconstruction rows and prior it
+already holds (ops.iw_bound, csrc/iwae.hip: weights, bound, effective sample size and every direct gradient fused), reports `iwae` and
+`ess` beside the usual losses, and refuses by name what it does not cover; iw_bound(x, y, samples) is the matching evaluation entry,
+the proper log (1/L) sum_l w_l over slabs of draws - not the reference's `iws`.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -194,6 +199,10 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
     # the epoch's loss sums and running measures included) instead of the eager train_step().  Opt-in; an instance may set
     # it.  What stays eager, and the late NaN exit: INTEGRATION.md ("The captured training loop").
     TRAIN_CAPTURED = False
+    # the objective of the labelled training-mode evaluate(): 'elbo' (the reference's, with the analytic KL) or 'iwae' (the
+    # importance-weighted bound over the step's L draws, ops.iw_bound).  Opt-in; an instance may set it.  Evaluation mode is
+    # never affected.  What 'iwae' refuses: _check_iwae_objective().
+    TRAIN_OBJECTIVE = 'elbo'
     # train_model(): run the reference's OOD phase (ood_detection_rates on `oodsets` every `ood_detection_every` epochs and once
     # after the loop, cvae.py:2309-2336,2513-2526).  Opt-in; an instance may set it.  Off: one warning, the phase is skipped.
     TRAIN_OOD_PHASE = False
@@ -669,6 +678,8 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
 
     def _evaluate(self, x, y=None, batch=0, current_measures=None, with_beta=False, kl_var_weighting=1.,
                   gamma_weighting=1, z_output=False, epsilon=None, **kw):
+        # the labelled training-mode evaluation alone follows TRAIN_OBJECTIVE (refusals are raised here, before any work)
+        iwae = self.training and y is not None and self._check_iwae_objective(kl_var_weighting, kw)
         if y is None or self.is_vib:
             if self.is_vib:
                 return self._evaluate_vib(x, y, batch, current_measures, with_beta, kl_var_weighting, gamma_weighting,
@@ -729,12 +740,28 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             total = cross_x + (self.beta if with_beta else 1.) * terms['kl']
             if cross_y_weight:
                 total = total + cw * ce
+        elif iwae:
+            # TRAIN_OBJECTIVE = 'iwae': total = -bound over the L draws of this very step (ops.iw_bound: weights, bound, ess and
+            # the direct gradients in csrc/iwae.hip; autograd carries z and log_var on through the unchanged latent / decoder
+            # ops).  wmse, cross_x and mse are reported as the ELBO reports them, outside the loss.
+            wmse_s = ops.recon_wmse(x_reco, x, s, s_kind, snapshot=bool(self.sigma.decay))                      # (L, N)
+            pr = self.encoder.prior
+            lab, means, T = pr._kernel_operands(y if pr.conditional else None, N, x.device)
+            bound, ess = ops.iw_bound(wmse_s, z, log_var, eps, lab, means, T, s, s_kind, D,
+                                      beta=self.beta if with_beta else 1., var_dim=pr.var_dim)
+            with torch.no_grad():
+                wmse, cross_x, _, mse = ops.elbo(wmse_s, terms['kl'], None, s, s_kind, D, 1., 0., with_mse=True)
+            total = -bound
+            if cross_y_weight:
+                total = total + cw * ce
         else:
             wmse_s = ops.recon_wmse(x_reco, x, s, s_kind, snapshot=bool(self.training and self.sigma.decay))     # (L, N)
             wmse, cross_x, total, mse = ops.elbo(wmse_s, terms['kl'], ce if cross_y_weight else None, s, s_kind, D,
                                                  self.beta if with_beta else 1.,
                                                  cw if torch.is_tensor(cw) else float(cross_y_weight or 0.), with_mse=True)
         losses = {'kl': terms['kl'], 'zdist': terms['distance'], 'var_kl': terms['var_kl']}
+        if iwae:
+            losses['iwae'], losses['ess'] = bound, ess
         dictionary = self.encoder.prior.mean if self.encoder.prior.conditional else None
         if dictionary is not None:
             losses['dzdist'] = terms['dzdist']
@@ -764,6 +791,126 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         if z_output:
             out += (mu, log_var, z)
         return out
+
+    # ------------------------------------------------------------------------------------ importance-weighted objective
+    def _check_iwae_objective(self, kl_var_weighting, kw):
+        """Is this training-mode evaluate() on the importance-weighted bound?  TRAIN_OBJECTIVE 'elbo': False.  'iwae': True, or
+        NotImplementedError naming what the bound is not built for (DESIGN.md section 7v says why for each)."""
+        objective = self.TRAIN_OBJECTIVE
+        if objective == 'elbo':
+            return False
+        if objective != 'iwae':
+            raise ValueError("TRAIN_OBJECTIVE is 'elbo' or 'iwae', got {!r}".format(objective))
+
+        def refuse(what):
+            raise NotImplementedError("TRAIN_OBJECTIVE = 'iwae': " + what)
+        self._iw_model_refusals(refuse)
+        if self.encoder.mixed_prior is not None:
+            refuse('a mixed (two-prior) encode is not built')
+        if not self.encoder.sampling.is_sampled:
+            refuse('the encoder does not sample (latent_sampling <= 1 and beta = 0): there are no draws to weigh')
+        if torch.is_tensor(kl_var_weighting) or kl_var_weighting != 1:
+            refuse('kl_var_weighting != 1 (a warm-up on the variance part of the KL) has no meaning for sampled densities')
+        if getattr(self.optimizer, '_world', 1) > 1:
+            refuse('data-parallel training (optimizer._world > 1) is not built')
+        if (self.TRAIN_CAPTURED or kw.get('_raw_measures') or kw.get('_dev_weights') is not None
+                or kw.get('_dev_state') is not None or getattr(self, '_graph_capture', False)
+                or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())):
+            refuse('graph_train_step / capture_train_step / TRAIN_CAPTURED are not built: the captured steps train on the ELBO')
+        return True
+
+    def _iw_model_refusals(self, refuse):
+        """What the importance-weighted bound is not built for ABOUT THE MODEL, the same for the training objective and for
+        iw_bound(): `refuse(what)` raises with the caller's own prefix."""
+        pr = self.encoder.prior
+        if not (self.is_cvae or self.is_vae or self.is_xvae):
+            refuse("built for the types 'cvae', 'vae' and 'xvae', not '{}'".format(self.type))
+        if self.y_is_coded:
+            refuse('coded labels (y_is_coded) are not built')
+        if self.output_distribution == 'categorical':
+            refuse('the categorical decoder is not built')
+        if self.sigma.is_rmse:
+            refuse('the rmse sigma (is_rmse) is not built: sigma would depend on all draws of the sample')
+        if pr.distribution != 'gaussian':
+            refuse("the '{}' prior is not built: Gaussian priors only".format(pr.distribution))
+        if pr.var_dim == 'full':
+            refuse("the full-variance prior (var_dim='full') is not built: 'scalar' and 'diag' only")
+        if getattr(self, 'compute_dtype', 'fp32') != 'fp32':
+            refuse('the bf16 compute mode is not built (set_compute_dtype("fp32"))')
+
+    def _refuse_captured_iwae(self, who):
+        """The captured steps train on the ELBO: asked for with another objective they refuse before anything is captured."""
+        if self.TRAIN_OBJECTIVE != 'elbo':
+            raise NotImplementedError("TRAIN_OBJECTIVE = {!r}: {} is not built for it (graph_train_step / capture_train_step / "
+                                      "TRAIN_CAPTURED train on the ELBO)".format(self.TRAIN_OBJECTIVE, who))
+
+    def iw_bound(self, x, y=None, samples=None, epsilon=None):
+        """log p(x | y) estimated with `samples` importance draws from the encoder -> (bound (N,), ess (N,)), fp32 on the device:
+
+            bound_n = log (1/L) sum_l w_l,    w_l = p(x | z_l) p(z_l | y) / q(z_l | x),    ess_n = (sum_l w_l)^2 / sum_l w_l^2
+
+        the importance-weighted bound of Burda et al. with beta = 1, a lower bound of log p(x | y) in expectation that tightens
+        with L.  This is the PROPER estimate: not `losses['iws']` of evaluate(x), which reproduces the reference as written (the
+        mean of exp(l_i - m) plus m, not its logarithm: csrc/loss.hip marks the sic) and bounds nothing.
+
+        y (N,) is required for a class-conditional prior and must be None for type 'vae'.  samples: default latent_sampling of the
+        evaluation mode.  epsilon (samples + 1, N, K) injects the noise (row 0 is not used).  Runs in eval mode under no_grad (the
+        training flag is restored).  The draws are cut into slabs so that no decoder activation passes EVAL_SLAB_ELEMENTS - 5000
+        draws of 100 images never exist as one (L, N, D) tensor - and the slabs are folded on the device by an exact merge of
+        (max, shifted sum) pairs inside the kernel (ops.iw_bound with a state).  Refuses what TRAIN_OBJECTIVE = 'iwae' refuses
+        about the model (type, coded labels, categorical decoder, rmse sigma, non-Gaussian or full-variance priors, bf16).
+        The reconstruction rows wmse_s reach the kernel as fp32 (ops.recon_wmse): a weight is as good as those rows times D / 2."""
+        was_training = self.training
+        self.eval()
+        try:
+            pr = self.encoder.prior
+
+            def refuse(what):
+                raise NotImplementedError('iw_bound: ' + what)
+            self._iw_model_refusals(refuse)
+            if pr.conditional and y is None:
+                raise ValueError('iw_bound: a class-conditional prior needs the labels y')
+            if not pr.conditional and y is not None:
+                raise ValueError('iw_bound: y must be None for a model with a single prior')
+            if x.dim() != self.input_dim + 1:
+                x = x.reshape(-1, *self.input_shape)
+            y = None if y is None else y.reshape(-1)
+            N, K = x.shape[0], self.latent_dim
+            D = int(np.prod(self.input_shape))
+            L = int(samples if samples is not None else (epsilon.shape[0] - 1 if epsilon is not None else self.latent_sampling))
+            if L < 1:
+                raise ValueError('iw_bound: at least one draw')
+            if epsilon is not None and tuple(epsilon.shape) != (L + 1, N, K):
+                raise ValueError('iw_bound: epsilon must be ({}, {}, {}), got {}'.format(L + 1, N, K, tuple(epsilon.shape)))
+            per_slab = max(self._eval_slab_rows() // max(N, 1) - 1, 1)          # draws per slab; each slab decodes one more row
+            enc = self.encoder
+            with torch.no_grad(), self._constant_weights(x):
+                feats = self._features_of(x).reshape(N, -1)
+                u, mu, lv_raw = enc.heads(feats, None)
+                lab, means, T = pr._kernel_operands(y if pr.conditional else None, N, x.device)
+                forced = math.log(enc.forced_variance) if enc.forced_variance else None
+                s, s_kind, _ = self._sigma_operand(enc.sigma(u) if enc.sigma_output_dim else None, N, store=False)
+                s = s.detach().contiguous()
+                state = torch.zeros((4, N), device=x.device, dtype=torch.float64)
+                bound = ess = None
+                for l0 in range(0, L, per_slab):
+                    Ls = min(per_slab, L - l0)
+                    e = torch.empty((Ls + 1, N, K), device=x.device, dtype=torch.float32)
+                    e[0] = 0
+                    if epsilon is None:
+                        e[1:].normal_()
+                    else:
+                        e[1:].copy_(epsilon[1 + l0:1 + l0 + Ls])
+                    log_var, z = ops.latent(mu, mu if lv_raw is None else lv_raw, e, lab, means, T, prior=pr.distribution,
+                                            var_dim=pr.var_dim, sampled=True, forced_lv=forced)[:2]
+                    x_reco = self._decode_rows(z.reshape(-1, K)).view(Ls + 1, N, *self._reco_shape())
+                    wmse_s = ops.recon_wmse(x_reco, x, s, s_kind)
+                    bound, ess = ops.iw_bound(wmse_s, z, log_var, e[1:], lab, means.detach(), T.detach(), s, s_kind, D,
+                                              beta=1., var_dim=pr.var_dim, state=state)
+            return bound, ess
+        finally:
+            if was_training:
+                self.train()
 
     # ------------------------------------------------------------------------------------ type 'vib'
     def _evaluate_vib(self, x, y, batch, current_measures, with_beta, kl_var_weighting, gamma_weighting, z_output, epsilon,
@@ -1203,7 +1350,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             t[i] = float(current.get(k, 0.))
         return t.to(device, non_blocking=True)
 
-    def _sigma_operand(self, sigma_coded, N):
+    def _sigma_operand(self, sigma_coded, N, store=True):
         """What the loss kernels get as `sigma` (cvae.py:626-646): (tensor, kind, rms) - rms is the device scalar reported
         as the `sigma` measure for the coded / rmse kinds (the parameter's value BEFORE this batch updates it: cvae.py:624),
         None otherwise (the measures kernel derives it from the parameter).  A coded sigma is also stored into the
@@ -1217,7 +1364,8 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         if sg.is_rmse:
             return sg, ops.SIGMA_RMSE, rms
         per_sample = sigma_coded.reshape(-1, *sg.output_dim)
-        sg.update(v=per_sample.detach())
+        if store:                                # store=False (net.iw_bound): a scoring call leaves the parameter alone
+            sg.update(v=per_sample.detach())
         return per_sample.reshape(N), ops.SIGMA_CODED, rms
 
     def _pack_measures(self, x, wmse, terms, dictionary, prev, batch, mse=None, sigma_rms=None, sigma_t=None, dev_state=None):
@@ -1286,6 +1434,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         two captured halves with the gradient all-reduce between them.  Drop every reference to the outputs of earlier EAGER
         steps (losses, measures) before calling this: a live eager autograd graph keeps its gradient-accumulation nodes bound
         to the default stream, which a capture must not touch."""
+        self._refuse_captured_iwae('graph_train_step()')
         world = getattr(self.optimizer, '_world', 1)
         dev = x.device
         self.optimizer.enable_device_hyper(True)
@@ -1414,6 +1563,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         * the step's last launch adds the mean of every loss row to the running sums (ops.loss_sums).
         * `step.epsilon`: the (L, N, K) noise of the replay that has just run; `step.losses`: the graph's loss rows.
         step(x, y) copies the batch in, replays and returns `step.losses`.  Single process only."""
+        self._refuse_captured_iwae('capture_train_step()')
         if getattr(self.optimizer, '_world', 1) > 1:
             raise NotImplementedError('capture_train_step() is single-process: data-parallel models use graph_train_step()')
         if self.optimizer.kind != 'adam':
@@ -1724,6 +1874,8 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             warmup_gamma[_] = max(warmup_gamma[_], warmup_gamma_[_])
         self.training_parameters['warmup'] = warmup
         self.training_parameters['warmup_gamma'] = warmup_gamma
+        if self.TRAIN_OBJECTIVE != 'elbo':         # a default run writes the job directory it always wrote
+            self.training_parameters['objective'] = self.TRAIN_OBJECTIVE
 
         from jvae_compat.recorders import LossRecorder
         sets = [set_name] + (['validation'] if validation else [])

@@ -206,6 +206,9 @@ _SIGS = {
     'jvae_aggpost_prepare_f32': (c_int, [P] * 6 + [c_long, c_int, P]),
     'jvae_aggpost_workspace_bytes': (c_size_t, [c_long, c_long, c_int, c_int]),
     'jvae_aggpost_logdensity_f32': (c_int, [P] * 9 + [c_long, c_long, c_int, c_int, P, P, c_size_t, P]),
+    'jvae_iw_bound_fwd_f32': (c_int, [P] * 8 + [c_int] * 3 + [c_float] + [c_int] * 5 + [P] * 5),
+    'jvae_iw_bound_bwd_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'jvae_iw_bound_bwd_f32': (c_int, [P] * 7 + [c_int] * 3 + [c_float] + [c_int] * 5 + [P] * 7 + [c_size_t, P]),
 }
 
 

@@ -1370,6 +1370,88 @@ def iws(wmse_s, eps, log_var, log_pz, sigma, sigma_is_log, D):
     return out if conditional else out[0]
 
 
+def _iw_operand(t, shape, what, dtype=torch.float32):
+    """An operand of the importance-weighted bound as the kernels read it: this dtype and shape (lib.ptr then refuses a tensor
+    that is off the device or not contiguous when its address is taken)."""
+    if t.dtype != dtype:
+        raise L.JvaeHipError(f'iw_bound: {what} must be {dtype}, got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise L.JvaeHipError(f'iw_bound: {what} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+    return t
+
+
+class _IwBound(torch.autograd.Function):
+    """wmse_s (L,N), z (L+1,N,K), lv (N,K), eps (L,N,K), y, means, T, sigma -> (bound (N,), ess (N,)): csrc/iwae.hip."""
+
+    @staticmethod
+    def forward(ctx, wmse_s, z, lv, eps, y, means, T, sigma, cfg, state):
+        mode, D, beta, var_dim = cfg
+        Ls, N, K = eps.shape
+        C = means.shape[0]
+        _iw_operand(wmse_s, (Ls, N), 'wmse_s')
+        _iw_operand(z, (Ls + 1, N, K), 'z')
+        _iw_operand(lv, (N, K), 'lv')
+        _iw_operand(eps, (Ls, N, K), 'eps')
+        _iw_operand(y, (N,), 'y', torch.int64)
+        _iw_operand(means, (C, K), 'means')
+        _iw_operand(T, (C, K) if var_dim == VAR_KIND['diag'] else ((C, K, K) if var_dim == VAR_KIND['full'] else (C,)), 'T')
+        _check_sigma(sigma, mode, N)
+        _iw_operand(sigma, sigma.shape, 'sigma')
+        dev = eps.device
+        if state is not None:
+            _iw_operand(state, (4, N), 'state', torch.float64)
+        bound, ess = (torch.empty(N, device=dev, dtype=torch.float32) for _ in range(2))
+        wt = torch.empty((Ls, N), device=dev, dtype=torch.float32)
+        rc = L.load().jvae_iw_bound_fwd_f32(L.ptr(wmse_s), L.ptr(z), L.ptr(lv), L.ptr(eps), L.ptr(y), L.ptr(means), L.ptr(T),
+                                            L.ptr(sigma), mode, PRIOR_KIND['gaussian'], var_dim, beta, Ls, N, K, C, D,
+                                            L.ptr(bound), L.ptr(wt), L.ptr(ess), L.ptr(state), L.stream_ptr())
+        L.check(rc, 'jvae_iw_bound_fwd_f32')
+        ctx.save_for_backward(wt, z, y, means, T, sigma)
+        ctx.cfg = (mode, D, beta, var_dim, Ls, N, K, C)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(ess)
+        return bound, ess
+
+    @staticmethod
+    def backward(ctx, g_bound, _g_ess):
+        wt, z, y, means, T, sigma = ctx.saved_tensors
+        mode, D, beta, var_dim, Ls, N, K, C = ctx.cfg
+        dev = wt.device
+        lib = L.load()
+        g_ws = torch.empty((Ls, N), device=dev, dtype=torch.float32)
+        g_z = torch.empty((Ls + 1, N, K), device=dev, dtype=torch.float32)
+        g_lv = torch.empty((N, K), device=dev, dtype=torch.float32)
+        g_means = torch.empty_like(means) if ctx.needs_input_grad[5] else None
+        g_T = torch.empty_like(T) if (ctx.needs_input_grad[6] and var_dim == VAR_KIND['diag']) else None
+        g_sigma = torch.empty_like(sigma) if ctx.needs_input_grad[7] else None
+        ws = L.workspace(lib.jvae_iw_bound_bwd_workspace_bytes(N, K), dev)
+        g = None if g_bound is None else _c(g_bound)
+        rc = lib.jvae_iw_bound_bwd_f32(L.ptr(g), L.ptr(wt), L.ptr(z), L.ptr(y), L.ptr(means), L.ptr(T), L.ptr(sigma), mode,
+                                       PRIOR_KIND['gaussian'], var_dim, beta, Ls, N, K, C, D, L.ptr(g_ws), L.ptr(g_z), L.ptr(g_lv),
+                                       L.ptr(g_means), L.ptr(g_T), L.ptr(g_sigma), L.ptr(ws), ws.numel(), L.stream_ptr())
+        L.check(rc, 'jvae_iw_bound_bwd_f32')
+        return g_ws, g_z, g_lv, None, None, g_means, g_T, g_sigma, None, None
+
+
+def iw_bound(wmse_s, z, lv, eps, y, means, T, sigma, sigma_is_log, D, beta=1., var_dim='scalar', state=None):
+    """The importance-weighted bound of Burda et al. and its effective sample size -> (bound (N,), ess (N,)), csrc/iwae.hip:
+
+        log w_l = log p(x | z_l) + beta (log p(z_l | y) - log q(z_l | x)),  bound = logsumexp_l(log w_l) - log L,  ess = 1 / sum_l wt_l^2
+
+    wmse_s (L, N) of recon_wmse, z (L+1, N, K) and lv (N, K) of latent (row 0 of z takes no part), eps (L, N, K) the noise of the
+    draws, y (N,) int64, means (C, K) and T ((C,) 'scalar' / (C, K) 'diag') of the Gaussian prior, sigma and its kind as elbo takes
+    them.  Differentiable in wmse_s, z, lv, means, T ('diag') and sigma with the DIRECT partial derivatives; autograd carries z and lv
+    on through latent's backward.  ess carries no gradient.  Operands must be fp32 (y int64), contiguous and on the device.
+    var_dim 'full', the rmse sigma kind: refused by the library (unsupported configuration); the tilted and uniform priors have
+    no entry here at all.  log w is formed in fp64 inside the kernels.  state (4, N) fp64, zeros at first: the bound over slabs of draws - each call merges its slab in and
+    returns bound / ess of all draws so far; no gradient flows through a call with a state."""
+    if var_dim not in VAR_KIND:
+        raise L.JvaeHipError(f'iw_bound: var_dim {var_dim!r} unknown')
+    if state is not None and torch.is_grad_enabled() and any(t.requires_grad for t in (wmse_s, z, lv, means, T, sigma)):
+        raise L.JvaeHipError('iw_bound: a call with a state carries no gradient: run it under no_grad')
+    return _IwBound.apply(wmse_s, z, lv, eps, y, means, T, sigma, (int(sigma_is_log), int(D), float(beta), VAR_KIND[var_dim]), state)
+
+
 def measures(x, wmse, zdist, var_kl, sigma, sigma_is_log, means, flag, scratch, prev=None, batch=0, run=None, counter=None):
     """-> device tensor of 16 floats (layout in csrc/loss.hip measures_kernel); `scratch`: 1-float device tensor;
     `prev`: the tensor returned for the previous batch (running means are continued on the device).

@@ -90,20 +90,40 @@ for _n in ('__getitem__', 'get', '__contains__', '__iter__', '__len__', 'keys', 
     setattr(_LazyDict, _n, _lazy(_n))
 
 
+# The 16-float block ops.measures writes (csrc/loss.hip): name -> index, the ONLY Python copy of that layout.  A captured
+# loop keeps the block at the head of a 40-float state block that one copy reads back (_capture_buffers).
+MEASURE_INDEX = {'sigma': 0, 'xpow': 10, 'mse': 11, 'rmse': 12, 'dB': 13, 'zdist': 14, 'var_kl': 15}
+DICTIONARY_MEASURE_INDEX = {'ld-norm': 6, 'imut-zy': 7, 'd-mind': 8}     # conditional priors only
+MEASURES_NONFINITE = 9                          # non-zero: the optimiser's flag was up when the block was written
+MEASURES_LEN, STATE_LEN = 16, 40
+STATE_RUN, STATE_SUMS = slice(0, 16), slice(16, 32)     # the measures; the epoch sums of the batch-mean losses
+STATE_FLAG = 32                                 # the optimiser's non-finite flag itself (an int32 in place)
+
+
+def decode_measures(h, has_dictionary, only=None):
+    """The measures dict of a block read back as a list of floats; `only`: the names to keep."""
+    m = {k: h[i] for k, i in MEASURE_INDEX.items()}
+    if has_dictionary:
+        m.update((k, h[i]) for k, i in DICTIONARY_MEASURE_INDEX.items())
+    return m if only is None else {k: v for k, v in m.items() if k in only}
+
+
+def measures_nonfinite(h):
+    """Did a parameter become NaN / Inf?  `h`: a measures block or a captured loop's whole state block, read back."""
+    return h[MEASURES_NONFINITE] != 0 or (len(h) > STATE_FLAG and h[STATE_FLAG] != 0)
+
+
 class Measures(_LazyDict):
     """`total_measures` of evaluate(): a dict of Python floats (rmse, dB, sigma, ...) exactly as in the reference, but
     materialised LAZILY: the 16 scalars sit in one device buffer (running means included, continued on the device from
     batch to batch) that is copied to pinned host memory asynchronously; the first time any entry is read the dict
     waits for that copy.  A training loop that only threads `measures` into the next evaluate() never synchronises."""
 
-    _KEYS = ('sigma', 'xpow', 'mse', 'rmse', 'dB', 'zdist', 'var_kl')
-
     def __init__(self, dev, has_dictionary, on_nan, from_main=False, only=None):
         super().__init__()
         self._only = only                                # type 'vib': ('sigma', 'zdist', 'var_kl') - nothing is reconstructed
-        from jvae_hip import lib as _lib
         self._dev = dev
-        self._host = torch.empty(16, dtype=torch.float32, pin_memory=True)
+        self._host = torch.empty(MEASURES_LEN, dtype=torch.float32, pin_memory=True)
         side = _lib.side_stream(dev.device)          # `dev` was produced on the side stream (logging is off the critical path)
         if from_main:                                # ... or by a graph replay on the current stream
             side.wait_stream(torch.cuda.current_stream(dev.device))
@@ -121,15 +141,9 @@ class Measures(_LazyDict):
         self._ready = True
         self._event.synchronize()
         h = self._host.tolist()
-        if h[9] != 0:
+        if measures_nonfinite(h):
             self._on_nan()
-        dict.update(self, {'sigma': h[0], 'xpow': h[10], 'mse': h[11], 'rmse': h[12], 'dB': h[13], 'zdist': h[14],
-                           'var_kl': h[15]})
-        if self._has_dictionary:
-            dict.update(self, {'ld-norm': h[6], 'imut-zy': h[7], 'd-mind': h[8]})
-        if self._only is not None:
-            for k in [k for k in dict.keys(self) if k not in self._only]:
-                dict.__delitem__(self, k)
+        dict.update(self, decode_measures(h, self._has_dictionary, self._only))
 
 
 class _LazySigmaParams(_LazyDict):
@@ -155,6 +169,50 @@ def _grad_nan_exit():
     print('GRAD NAN')              # cvae.py:2454-2457; detected by the Adam kernel: train_step() checks the flag of the previous update
                                    # before every backward (as the reference's scan does), lazily-read measures check it as well
     sys.exit(1)
+
+
+class CapturedStep:
+    """A training step captured into HIP graphs: what graph_train_step() and capture_train_step() return.  `step(x, y)` copies
+    the batch into the static buffers `x` / `y`, replays `graphs` in order - with `between()` in front of every graph after
+    the first (data parallel: the eager gradient all-reduce) - and notes the optimiser step on the host.  A graph is any
+    object with `.replay()`; `graph` is the graph, or the tuple of them when there is more than one.  `losses`: the graphs'
+    own loss rows, overwritten by the next replay.  `constants`: what the graphs read that nothing else is bound to keep.
+    `measures`: the 16-float device block the graphs write, which a call wraps into a fresh Measures and returns beside the
+    losses (graph_train_step); None: a call returns the losses alone and the measures continue on the device, in `buffers`
+    (capture_train_step, which also fills in `epsilon` and `key`; see there)."""
+
+    def __init__(self, net, x, y, graphs, between=None, losses=None, measures=None, has_dictionary=False, buffers=None,
+                 constants=()):
+        self.net, self.x, self.y, self.graphs, self.between = net, x, y, list(graphs), between
+        self.graph = self.graphs[0] if len(self.graphs) == 1 else tuple(self.graphs)
+        self.losses, self.keys, self.measures, self.has_dictionary = losses, list(losses or ()), measures, has_dictionary
+        self.buffers, self.constants, self.epsilon, self.key = buffers, constants, None, None
+
+    def __call__(self, xb, yb):
+        self.x.copy_(xb, non_blocking=True)
+        self.y.copy_(yb, non_blocking=True)
+        self.graphs[0].replay()
+        for g in self.graphs[1:]:
+            self.between()
+            g.replay()
+        self.net.optimizer.note_replayed_step()
+        if self.measures is None:
+            return self.losses
+        return self.losses, Measures(self.measures, self.has_dictionary, _grad_nan_exit, from_main=True)
+
+    def set_weights(self, kl_w, gamma_w):
+        """The two warm-up weights the captured kernels read from the device: kl_var_weighting and the cross_y weight."""
+        cw = gamma_w * self.net.gamma if self.net.y_is_decoded else 0.
+        self.buffers['weights'].copy_(torch.tensor([float(kl_w), float(cw or 0.)], dtype=torch.float32))
+
+    def seed_measures(self, prev, batch):
+        """Continue after `batch` eager batches whose last measures buffer (16 device floats) is `prev`."""
+        self.buffers['run'].copy_(prev)
+        self.buffers['counter'].fill_(int(batch))
+
+    def reset_epoch(self):
+        self.buffers['counter'].zero_()
+        self.buffers['sums'].zero_()
 
 
 class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
@@ -715,7 +773,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             self._dump_after_encoder_error(err, x, y)
             raise
         self._last_epsilon = eps
-        if self.training and self.optimizer._world > 1 and z.requires_grad and not getattr(self, '_graph_capture', False) \
+        if self.training and self.optimizer._world > 1 and z.requires_grad \
                 and not getattr(self.optimizer, '_external_reduce', False):
             # data-parallel: the decoder's gradients are final once d(loss)/dz exists -> start their all-reduce there
             z.register_hook(self._early_reduce_hook)
@@ -771,13 +829,11 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             losses['cross_y'] = ce
         losses['total'] = total
 
-        prev = current_measures._dev if isinstance(current_measures, Measures) else self._upload_measures(
-            current_measures, x.device) if (current_measures and batch) else None
+        prev = self._prev_measures(current_measures, batch, x.device)
         packed = self._pack_measures(x, wmse, terms, dictionary, prev, batch, mse=mse, sigma_rms=sigma_rms, sigma_t=s,
                                      dev_state=dev_state)
         if self.training:
             if self.sigma.decay and not self.sigma.learned:                  # the decay rule computes with the rmse now
-                from jvae_hip import lib as _lib
                 torch.cuda.current_stream(x.device).wait_stream(_lib.side_stream(x.device))
             self.sigma.update(rmse=packed[3])                                # device scalar, as in the reference
         if kw.get('_raw_measures'):
@@ -814,7 +870,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         if getattr(self.optimizer, '_world', 1) > 1:
             refuse('data-parallel training (optimizer._world > 1) is not built')
         if (self.TRAIN_CAPTURED or kw.get('_raw_measures') or kw.get('_dev_weights') is not None
-                or kw.get('_dev_state') is not None or getattr(self, '_graph_capture', False)
+                or kw.get('_dev_state') is not None or getattr(self.optimizer, '_external_reduce', False)
                 or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())):
             refuse('graph_train_step / capture_train_step / TRAIN_CAPTURED are not built: the captured steps train on the ELBO')
         return True
@@ -947,8 +1003,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                 total = total.unsqueeze(0).expand_as(ce)
             losses['total'] = total
             losses['cross_y'] = ce
-        prev = current_measures._dev if isinstance(current_measures, Measures) else self._upload_measures(
-            current_measures, x.device) if (current_measures and batch) else None
+        prev = self._prev_measures(current_measures, batch, x.device)
         with torch.no_grad():
             packed = self._pack_measures_raw(x, torch.zeros(N, device=x.device), terms, None, prev, batch, self.sigma.detach(),
                                              int(self.sigma.is_log), dev_state=dev_state)
@@ -1054,7 +1109,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             losses['iws'] = ops.iws(fwd['wmse_s'], fwd['eps'], log_var, log_pz, s, s_kind, D)
             if not with_measures:
                 return losses, None
-            prev = current_measures._dev if isinstance(current_measures, Measures) else None
+            prev = self._prev_measures(current_measures, batch, x.device, upload=False)
             packed = self._pack_measures(x, fwd['wmse'], terms, dictionary, prev, batch, mse=fwd['mse'],
                                          sigma_rms=fwd['sigma_rms'], sigma_t=fwd['s_report'])
         return losses, Measures(packed, dictionary is not None, _grad_nan_exit)
@@ -1345,10 +1400,18 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
 
     def _upload_measures(self, current, device):
         """Running means handed in as plain floats (first batch of a resumed loop, a caller's own dict)."""
-        t = torch.zeros(16)
-        for i, k in ((10, 'xpow'), (11, 'mse'), (14, 'zdist'), (15, 'var_kl')):
-            t[i] = float(current.get(k, 0.))
+        t = torch.zeros(MEASURES_LEN)
+        for k in ('xpow', 'mse', 'zdist', 'var_kl'):
+            t[MEASURE_INDEX[k]] = float(current.get(k, 0.))
         return t.to(device, non_blocking=True)
+
+    def _prev_measures(self, current_measures, batch, device, upload=True):
+        """The device block the running means continue from: a Measures' own, or (`upload`) a plain dict's values sent up."""
+        if isinstance(current_measures, Measures):
+            return current_measures._dev
+        if upload and current_measures and batch:
+            return self._upload_measures(current_measures, device)
+        return None
 
     def _sigma_operand(self, sigma_coded, N, store=True):
         """What the loss kernels get as `sigma` (cvae.py:626-646): (tensor, kind, rms) - rms is the device scalar reported
@@ -1381,7 +1444,6 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                                        int(self.sigma.is_log), dev_state=dev_state)
 
     def _pack_measures_raw(self, x, wmse, terms, dictionary, prev, batch, sigma_t, sigma_kind, dev_state=None):
-        from jvae_hip import lib as _lib
         with torch.no_grad():
             if getattr(self, '_scratch', None) is None or self._scratch.device != x.device:
                 self._scratch = torch.zeros(1, device=x.device, dtype=torch.float32)
@@ -1414,8 +1476,6 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                                                    kl_var_weighting=kl_var_weighting,
                                                    gamma_weighting=gamma_weighting,
                                                    current_measures=current_measures, epsilon=epsilon)
-        # total.mean().backward() without the two reduction kernels of the mean nobody reads and the expand of its
-        # backward: d(mean)/d(total_i) = 1/N, handed to autograd as a cached constant (same fp32 value as torch's own)
         if self.optimizer.check_nonfinite():     # cvae.py:2454-2457: a NaN / Inf parameter ends the run BEFORE backward
             _grad_nan_exit()
         self._mean_backward(losses['total'])
@@ -1439,91 +1499,76 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         dev = x.device
         self.optimizer.enable_device_hyper(True)
         sx, sy = x.clone(), y.clone()
-        from jvae_hip import lib as _lib
-
-        def fwd_bwd():
-            self.optimizer.zero_grad()
-            _, _, losses, raw = self.evaluate(sx, sy, batch=0, with_beta=True, kl_var_weighting=kl_var_weighting,
-                                              gamma_weighting=gamma_weighting, _raw_measures=True)
-            self._mean_backward(losses['total'])    # (the constant is created by the eager warm-up passes, not captured)
-            return losses, raw
-
-        def update():
-            self.optimizer.clip(self.parameters())
-            self.optimizer.step()
-
-        def body():
-            out = fwd_bwd()
-            update()
-            return out
-
+        forward_backward, update = self._captured_body(sx, sy, kl_var_weighting, gamma_weighting)
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(s):                      # eager warm-up on a side stream (allocations, lazy initialisations)
             for _ in range(max(int(warmup), 1)):
-                body()
+                update(forward_backward())
         torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
         if world > 1:
             # Data parallel: the step is captured in TWO graphs - [zero_grad, forward, backward] and [clip, Adam] - with the
             # gradient exchange (ONE all-reduce of the flat buffer, any backend) issued eagerly between them: three host
             # calls per step.  The early-bucket overlap of the eager path is given up (the exchange is ~0.1 ms of a ~4 ms step).
-            self._graph_capture = True                  # evaluate() must not launch the early-bucket hook while capturing
-            self.optimizer._external_reduce = True
-            try:
-                ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with torch.cuda.graph(ga):
-                    losses, (packed, has_dict) = fwd_bwd()
-                    _lib.join_side_stream()             # weight gradients of the side stream: inside the captured half
-                with torch.cuda.graph(gb, pool=ga.pool()):
-                    update()
-            finally:
-                # both flags exist only while the two halves are being captured: a later EAGER train_step() / train_model()
-                # on this model must again join the side stream and exchange its gradients inside reduce_gradients()
-                self._graph_capture = False
-                self.optimizer._external_reduce = False
-            for g in self.optimizer._groups:
-                g.step -= 1
+            def first_half():
+                out = forward_backward()
+                _lib.join_side_stream()                 # weight gradients of the side stream: inside the captured half
+                return out
 
-            def step(xb, yb):
-                sx.copy_(xb, non_blocking=True)
-                sy.copy_(yb, non_blocking=True)
-                ga.replay()
-                self.optimizer.all_reduce_flat()
-                gb.replay()
-                self.optimizer.note_replayed_step()
-                return losses, Measures(packed, has_dict, _grad_nan_exit, from_main=True)
+            with self.optimizer.external_reduce():      # evaluate() must not launch the early-bucket hook while capturing
+                graphs, ((losses, (packed, has_dict)), _) = self._capture((first_half, update), dev)
+        else:
+            graphs, ((losses, (packed, has_dict)),) = self._capture((lambda: update(forward_backward()),), dev)
+        return CapturedStep(self, sx, sy, graphs, self.optimizer.all_reduce_flat if world > 1 else None, losses=losses,
+                            measures=packed, has_dictionary=has_dict,
+                            constants=(self._mean_grad,))       # the graphs read it: alive as long as the step is
 
-            step.graph = (ga, gb)
-            step.constants = (self._mean_grad,)         # the captured graphs read it: alive as long as the step is
-            return step
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            losses, (packed, has_dict) = body()
-        for g in self.optimizer._groups:                # the capture pass advanced the host counter without executing
-            g.step -= 1
+    def _captured_body(self, sx, sy, kl_w, gamma_w, bufs=None):
+        """THE training step as the captures record it, on the static batch (sx, sy): -> (forward_backward, update), the whole
+        step being update(forward_backward()); the two-graph data-parallel form records each half into a graph of its own.
+        Without `bufs` (graph_train_step) the weights are host constants and the measures those of batch 0; with `bufs`
+        (_capture_buffers; capture_train_step) they are device words, and the last launch adds the loss means to the epoch sums."""
+        opt = self.optimizer
+        on_device = {} if bufs is None else {'_dev_weights': bufs['weights'], '_dev_state': (bufs['run'], bufs['counter'])}
 
-        def step(xb, yb):
-            sx.copy_(xb, non_blocking=True)
-            sy.copy_(yb, non_blocking=True)
-            graph.replay()
-            self.optimizer.note_replayed_step()
-            return losses, Measures(packed, has_dict, _grad_nan_exit, from_main=True)
+        def forward_backward():
+            opt.zero_grad()
+            _, _, losses, raw = self.evaluate(sx, sy, batch=0, with_beta=True, kl_var_weighting=kl_w, gamma_weighting=gamma_w,
+                                              _raw_measures=True, **on_device)
+            self._mean_backward(losses['total'])        # (its constant was created by the eager warm-up, not captured)
+            return losses, raw
 
-        step.graph = graph
-        step.constants = (self._mean_grad,)             # the captured graph reads it: alive as long as the step is
-        return step
+        def update(out=None):
+            opt.clip(self.parameters())
+            opt.step()
+            if bufs is not None:
+                ops.loss_sums(list(out[0].values()), bufs['sums'])      # the step's last launch
+            return out
+
+        return forward_backward, update
+
+    def _capture(self, parts, device):
+        """Record each callable of `parts` into a HIP graph of its own, all in the first one's memory pool: -> (graphs, what
+        the callables returned).  Nothing executes, so the host step count the recorded step() advanced is taken back."""
+        torch.cuda.synchronize(device)
+        graphs, results = [], []
+        for part in parts:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, pool=graphs[0].pool() if graphs else None):
+                results.append(part())
+            graphs.append(graph)
+        self.optimizer.forget_captured_step()
+        return graphs, results
 
     # ---- the captured step of train_model() (TRAIN_CAPTURED) ----------------------------------------------------------
     def _capture_buffers(self, device):
-        """The device words a captured step shares with the loop, in ONE 40-float block so that one copy reads them all back:
-        [0:16] the measures (running means included), [16:32] the epoch sums of the batch-mean losses, [32] the optimiser's
-        non-finite flag (an int32 in place); next to it the batch counter (int32) and the two warm-up weights."""
+        """The device words a captured step shares with the loop: ONE 40-float block that one copy reads back (STATE_RUN,
+        STATE_SUMS, STATE_FLAG: the optimiser's non-finite flag moves into it), the batch counter and the two warm-up weights."""
         b = getattr(self, '_capt_bufs', None)
         if b is None or b['state'].device != device:
-            state = torch.zeros(40, device=device, dtype=torch.float32)
-            b = self._capt_bufs = {'state': state, 'run': state[0:16], 'sums': state[16:32],
-                                   'flag': state.view(torch.int32)[32:33],
+            state = torch.zeros(STATE_LEN, device=device, dtype=torch.float32)
+            b = self._capt_bufs = {'state': state, 'run': state[STATE_RUN], 'sums': state[STATE_SUMS],
+                                   'flag': state.view(torch.int32)[STATE_FLAG:STATE_FLAG + 1],
                                    'counter': torch.zeros(1, device=device, dtype=torch.int32),
                                    'weights': torch.ones(2, device=device, dtype=torch.float32)}
         opt = self.optimizer
@@ -1573,62 +1618,21 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             raise RuntimeError('capture_train_step(): run the eager warm-up steps with optimizer.enable_device_hyper(True) first')
         dev = x.device
         bufs = self._capture_buffers(dev)
-        net, opt = self, self.optimizer
+        opt = self.optimizer
         sx, sy = x.clone(), y.clone()
-        keys = []
-
-        def body():
-            opt.zero_grad()
-            _, _, losses, _ = net.evaluate(sx, sy, batch=0, with_beta=True, kl_var_weighting=kl_var_weighting,
-                                           gamma_weighting=gamma_weighting, _raw_measures=True,
-                                           _dev_weights=bufs['weights'], _dev_state=(bufs['run'], bufs['counter']))
-            net._mean_backward(losses['total'])         # (its constant was created by the eager warm-up, not captured)
-            opt.clip(net.parameters())
-            opt.step()
-            keys.extend(losses)
-            ops.loss_sums([losses[k] for k in keys], bufs['sums'])      # the step's last launch
-            return losses
-
+        forward_backward, update = self._captured_body(sx, sy, kl_var_weighting, gamma_weighting, bufs)
         was_training = self.training
         self.train()
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(graph):
-                losses = body()
+            graphs, ((losses, _),) = self._capture((lambda: update(forward_backward()),), dev)
         finally:
             self.train(was_training)
-        for g in opt._groups:                           # the capture pass advanced the host counter without executing
-            g.step -= 1
         self._captures_built = self._captures_built + 1
-
-        def step(xb, yb):
-            sx.copy_(xb, non_blocking=True)
-            sy.copy_(yb, non_blocking=True)
-            graph.replay()
-            opt.note_replayed_step()
-            return losses
-
-        def set_weights(kl_w, gamma_w):
-            cw = gamma_w * net.gamma if net.y_is_decoded else 0.
-            bufs['weights'].copy_(torch.tensor([float(kl_w), float(cw or 0.)], dtype=torch.float32))
-
-        def seed_measures(prev, batch):
-            """Continue after `batch` eager batches whose last measures buffer (16 device floats) is `prev`."""
-            bufs['run'].copy_(prev)
-            bufs['counter'].fill_(int(batch))
-
-        def reset_epoch():
-            bufs['counter'].zero_()
-            bufs['sums'].zero_()
-
-        set_weights(kl_var_weighting, gamma_weighting)
-        step.graph, step.losses, step.keys, step.epsilon = graph, losses, keys, self._last_epsilon
-        step.buffers, step.x, step.y = bufs, sx, sy
-        step.set_weights, step.seed_measures, step.reset_epoch = set_weights, seed_measures, reset_epoch
-        step.has_dictionary = self.encoder.prior.conditional
-        # what the graph reads besides the model: alive as long as the step is
-        step.constants = (self._mean_grad, [g.hyper for g in opt._groups], opt._sqnorm, getattr(self, '_scratch', None))
+        step = CapturedStep(self, sx, sy, graphs, losses=losses, has_dictionary=self.encoder.prior.conditional, buffers=bufs,
+                            constants=(self._mean_grad, [g.hyper for g in opt._groups], opt._sqnorm,
+                                       getattr(self, '_scratch', None)))    # what the graph reads besides the model
+        step.set_weights(kl_var_weighting, gamma_weighting)
+        step.epsilon = self._last_epsilon
         step.key = self._capture_key(x, y, self._cross_y_on(gamma_weighting))
         return step
 
@@ -1636,17 +1640,27 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         """THE read-back of the captured loop: measures, loss sums and the non-finite flag in one copy (it synchronises).
         A NaN / Inf parameter ends the run here, as _grad_nan_exit() does on the eager path."""
         h = bufs['state'].tolist()
-        if h[32] != 0 or h[9] != 0:
+        if measures_nonfinite(h):
             _grad_nan_exit()
         return h
 
     def _measures_from_host(self, h, has_dictionary):
-        m = {'sigma': h[0], 'xpow': h[10], 'mse': h[11], 'rmse': h[12], 'dB': h[13], 'zdist': h[14], 'var_kl': h[15]}
-        if has_dictionary:
-            m.update({'ld-norm': h[6], 'imut-zy': h[7], 'd-mind': h[8]})
-        if self.is_vib:
-            m = {k: m[k] for k in ('sigma', 'zdist', 'var_kl')}
-        return m
+        return decode_measures(h, has_dictionary, only=('sigma', 'zdist', 'var_kl') if self.is_vib else None)
+
+    def _report_batch(self, outputs, i, per_epoch, epoch, epochs, batch_size, t0, report_every, shown, read, unheard=False):
+        """The end of train batch `i`, both loops: the progress line of `outputs`.  Every `report_every` batches and at the
+        epoch's last one `read() -> (mean losses, measures)`, the loop's read-back, refreshes `shown` - for a listening
+        `outputs`, or (`unheard`) whether anybody listens; the batches between show the losses last read and NaN measures."""
+        listening = outputs is not None and hasattr(outputs, 'results')
+        fresh = i % report_every == 0 or i + 1 == per_epoch
+        if fresh and (listening or unheard):
+            shown['losses'], shown['metrics'] = read()
+        if listening:
+            outputs.results(i, per_epoch, epoch + 1, epochs, preambule='train',
+                            losses={k: shown['losses'].get(k, float('nan')) for k in self.loss_components},
+                            metrics={k: shown['metrics'][k] if fresh else float('nan') for k in self.metrics},
+                            accuracy={k: np.nan for k in self.predict_methods},
+                            time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, end_of_epoch='\n')
 
     def _train_epoch_eager(self, batches, epoch, epochs, batch_size, w_kl, w_gamma, outputs, report_every):
         """The train phase of one epoch, one train_step() per batch (cvae.py:2424-2501): -> (mean_loss, measures dict)."""
@@ -1655,7 +1669,11 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         t0 = time.time()
         measures, nb = None, 0
         keys, acc = None, None          # running sums of the batch means of every loss: ONE device vector
-        shown = {}
+        shown = {'losses': {}, 'metrics': {}}
+
+        def read():                     # the only read-back of the loop: every k batches, for a listening `outputs`
+            return dict(zip(keys, (acc / nb).tolist())), {k: measures[k] for k in self.metrics}
+
         for i, (x, y) in enumerate(batches):
             losses, measures = self.train_step(x, y, batch=i, current_measures=measures,
                                                kl_var_weighting=w_kl, gamma_weighting=w_gamma)
@@ -1667,16 +1685,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             # one small kernel per batch (stack of means) instead of the reference's .item() per loss (cvae.py:2463-2469)
             acc += torch.stack([losses[k].detach().mean() for k in keys])
             nb = i + 1
-            if outputs is not None and hasattr(outputs, 'results'):
-                if i % report_every == 0 or i + 1 == per_epoch:
-                    host = (acc / nb).tolist()                    # the only read-back of the loop: every k batches
-                    shown = dict(zip(keys, host))
-                outputs.results(i, per_epoch, epoch + 1, epochs, preambule='train',
-                                losses={k: shown.get(k, float('nan')) for k in self.loss_components},
-                                metrics={k: measures[k] for k in self.metrics} if (i % report_every == 0 or i + 1 == per_epoch)
-                                else {k: float('nan') for k in self.metrics},
-                                accuracy={k: np.nan for k in self.predict_methods},
-                                time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, end_of_epoch='\n')
+            self._report_batch(outputs, i, per_epoch, epoch, epochs, batch_size, t0, report_every, shown, read)
         mean_loss = dict(zip(keys or [], (acc / max(nb, 1)).tolist() if acc is not None else []))
         return mean_loss, dict(measures or {})
 
@@ -1691,10 +1700,14 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         if not getattr(opt, '_device_hyper', False):
             opt.enable_device_hyper(True)
         step = getattr(self, '_captured_step', None)
-        bufs, keys, t0 = None, None, time.time()
-        shown, metrics_host, warm, h, checked = {}, {}, 0, None, False
+        bufs, keys, measures, t0 = None, None, None, time.time()
+        shown, warm, checked, nb = {'losses': {}, 'metrics': {}}, 0, False, 0
         has_dict = self.encoder.prior.conditional
-        measures = None
+
+        def read():
+            h = self._read_captured_state(bufs)
+            return {k: v / nb for k, v in zip(keys, h[STATE_SUMS])}, self._measures_from_host(h, has_dict)
+
         for i, (x, y) in enumerate(batches):
             if bufs is None:
                 bufs = self._capture_buffers(x.device)
@@ -1734,22 +1747,12 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                 hook(epoch, i, x, y, eps, losses)
             del losses
             nb = i + 1
-            if i % report_every == 0 or nb == per_epoch:
-                h = self._read_captured_state(bufs)
-                shown = {k: v / nb for k, v in zip(keys, h[16:])}
-                metrics_host = self._measures_from_host(h, has_dict)
-            if outputs is not None and hasattr(outputs, 'results'):
-                fresh = i % report_every == 0 or nb == per_epoch
-                outputs.results(i, per_epoch, epoch + 1, epochs, preambule='train',
-                                losses={k: shown.get(k, float('nan')) for k in self.loss_components},
-                                metrics={k: metrics_host[k] if fresh else float('nan') for k in self.metrics},
-                                accuracy={k: np.nan for k in self.predict_methods},
-                                time_per_i=(time.time() - t0) / (i + 1), batch_size=batch_size, end_of_epoch='\n')
-        if h is None:
+            self._report_batch(outputs, i, per_epoch, epoch, epochs, batch_size, t0, report_every, shown, read, unheard=True)
+        if not shown['metrics']:
             return {}, {}
         if not self.is_vib:
-            self.training_parameters['sigma'] = self.sigma.host_params(h[0])
-        return dict(shown), dict(metrics_host)
+            self.training_parameters['sigma'] = self.sigma.host_params(shown['metrics']['sigma'])
+        return dict(shown['losses']), dict(shown['metrics'])
 
     def train_model(self, trainset=None, transformer=None, data_augmentation=None, optimizer=None, epochs=50,
                     batch_size=100, test_batch_size=100, validation=4096, device=None, testset=None, oodsets=None,

@@ -15,6 +15,7 @@ Parameters that never receive gradient (e.g. the classifier when gamma = 0, the 
 left untouched exactly as torch.optim.Adam skips `grad is None` parameters; they join (as a new group with
 its own step count) the first time a gradient shows up.
 """
+import contextlib
 import logging
 
 import torch
@@ -440,6 +441,23 @@ class Optimizer:
         """Host bookkeeping for one optimiser step that ran inside a replayed HIP graph."""
         for g in self._groups:
             g.step += 1
+
+    def forget_captured_step(self):
+        """A graph capture went through step() without executing it: the host step count goes back by one."""
+        for g in self._groups:
+            g.step -= 1
+
+    @contextlib.contextmanager
+    def external_reduce(self):
+        """While the block runs, the gradient exchange happens OUTSIDE clip() / step(): reduce_gradients() neither joins the
+        side stream nor all-reduces, and the model starts no early-bucket exchange (the two captured halves of a data-parallel
+        graph_train_step(), with all_reduce_flat() between their replays).  Cleared on the way out, also when the block
+        raises: a later eager step on the same model must exchange its gradients inside reduce_gradients() again."""
+        self._external_reduce = True
+        try:
+            yield self
+        finally:
+            self._external_reduce = False
 
     def _sync_device_lr(self):
         for g in self._groups:

@@ -1,9 +1,13 @@
 """CPU: the host side of train_model()'s captured step - the header, the library and the ctypes table agree on the new
 entry points, their launchers refuse bad arguments before touching a device, and the capture key changes exactly when a
-captured step stops being valid."""
+captured step stops being valid; the one decode of the measures block, CapturedStep driven by fakes, and the optimiser's
+external-reduce flag."""
 import ctypes
+import gc
 import os
 import re
+import types
+import weakref
 
 import pytest
 import torch
@@ -125,3 +129,119 @@ def test_capture_key_follows_shape_and_trainable_set_only():
     assert net._cross_y_on(1.) is False
     g = Net(**dict(kw, gamma=2.0, classifier=[20]))
     assert g._cross_y_on(0.5) is True and g._cross_y_on(0.) is False
+
+
+# ---- the 16-float measures block: the indices are written out here on purpose, as the second copy that guards the table
+H = [100. + i for i in range(16)]
+
+
+def test_decode_measures_without_dictionary():
+    from cvae import decode_measures
+    assert decode_measures(H, False) == {'sigma': 100., 'xpow': 110., 'mse': 111., 'rmse': 112., 'dB': 113., 'zdist': 114.,
+                                         'var_kl': 115.}
+
+
+def test_decode_measures_with_dictionary():
+    from cvae import decode_measures
+    assert decode_measures(H, True) == {'sigma': 100., 'ld-norm': 106., 'imut-zy': 107., 'd-mind': 108., 'xpow': 110.,
+                                        'mse': 111., 'rmse': 112., 'dB': 113., 'zdist': 114., 'var_kl': 115.}
+
+
+@pytest.mark.parametrize('has_dictionary', (False, True))
+def test_decode_measures_only(has_dictionary):
+    from cvae import decode_measures
+    assert decode_measures(H, has_dictionary, only=('sigma', 'zdist', 'var_kl')) == {'sigma': 100., 'zdist': 114., 'var_kl': 115.}
+
+
+def test_nonfinite_word_of_both_blocks():
+    from cvae import measures_nonfinite
+    for n in (16, 40):
+        h = [0.] * n
+        assert not measures_nonfinite(h)
+        h[9] = 1.
+        assert measures_nonfinite(h)
+    h = [0.] * 40
+    h[32] = 1e-45                       # the optimiser's int32 flag read as a float: a denormal, not zero
+    assert measures_nonfinite(h)
+    h = [1.] * 40                       # every other word is free to be anything
+    h[9] = h[32] = 0.
+    assert not measures_nonfinite(h)
+
+
+# ---- CapturedStep driven by fakes: graphs that log their replay, an optimiser that logs its note, CPU buffers
+class FakeGraph:
+    def __init__(self, log, name):
+        self.log, self.name = log, name
+
+    def replay(self):
+        self.log.append(self.name)
+
+
+def fake_net(log):
+    optimizer = types.SimpleNamespace(note_replayed_step=lambda: log.append('noted'))
+    return types.SimpleNamespace(optimizer=optimizer)
+
+
+def test_two_graphs_replay_around_the_exchange():
+    from cvae import CapturedStep
+    log = []
+    sx, sy = torch.zeros(2, 3), torch.zeros(2, dtype=torch.int64)
+    graphs = [FakeGraph(log, 'replay0'), FakeGraph(log, 'replay1')]
+    losses = {'total': torch.ones(2)}
+    step = CapturedStep(fake_net(log), sx, sy, graphs, lambda: log.append('between'), losses=losses)
+    xb, yb = torch.arange(6.).reshape(2, 3), torch.tensor([4, 7])
+    out = step(xb, yb)
+    assert log == ['replay0', 'between', 'replay1', 'noted']
+    assert torch.equal(sx, xb) and torch.equal(sy, yb) and step.x is sx and step.y is sy
+    assert out is losses and step.losses is losses and step.keys == ['total']
+    assert isinstance(step.graph, tuple) and len(step.graph) == 2
+    assert step.graph[0] is graphs[0] and step.graph[1] is graphs[1]
+
+
+def test_one_graph_needs_no_exchange():
+    from cvae import CapturedStep
+    log = []
+    sx, sy = torch.zeros(2, 3), torch.zeros(2, dtype=torch.int64)
+    graph = FakeGraph(log, 'replay0')
+    step = CapturedStep(fake_net(log), sx, sy, [graph])
+    xb, yb = torch.full((2, 3), 5.), torch.tensor([1, 0])
+    step(xb, yb)
+    assert log == ['replay0', 'noted']
+    assert torch.equal(sx, xb) and torch.equal(sy, yb)
+    assert step.graph is graph
+
+
+def test_constants_live_as_long_as_the_step():
+    from cvae import CapturedStep
+    log = []
+    constant = torch.ones(3)
+    alive = weakref.ref(constant)
+    step = CapturedStep(fake_net(log), torch.zeros(2, 3), torch.zeros(2), [FakeGraph(log, 'replay0')],
+                        constants=(constant, [torch.zeros(1)]))
+    del constant
+    gc.collect()
+    assert alive() is not None and step.constants[0] is alive()
+    assert torch.equal(step.constants[0], torch.ones(3))
+    del step
+    gc.collect()
+    assert alive() is None
+
+
+# ---- the one flag for "the gradient exchange happens outside" (Optimizer.external_reduce)
+def test_external_reduce_is_set_inside_and_cleared_after():
+    from module.optimizers import Optimizer
+    opt = Optimizer([])
+    assert not getattr(opt, '_external_reduce', False)
+    with opt.external_reduce():
+        assert opt._external_reduce is True
+    assert opt._external_reduce is False
+
+
+def test_external_reduce_is_cleared_when_the_body_raises():
+    from module.optimizers import Optimizer
+    opt = Optimizer([])
+    with pytest.raises(RuntimeError, match='in the body'):
+        with opt.external_reduce():
+            assert opt._external_reduce is True
+            raise RuntimeError('in the body')
+    assert opt._external_reduce is False

@@ -1100,6 +1100,41 @@ int jvae_iw_bound_bwd_f32(const float* g_bound, const float* wt, const float* z,
                           int L, int N, int K, int C, int D, float* g_wmse_s, float* g_z, float* g_lv, float* g_means,
                           float* g_T, float* g_sigma, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- beta-TCVAE split of the training step, forward and backward (csrc/tcvae.hip; Chen et al. 2018; no counterpart in the
+ * reference) ----
+ * For sample i of class y[i], its draws l = 1..L (row 0 of z takes no part) and S_i = the rows j of the batch with y[j] = y[i]:
+ *   l_ijk = -1/2 (lv_jk + (z_lik - mu_jk)^2 e^(-lv_jk) + log 2pi),    c_i = log |S_i| + log n_i
+ *   A = -1/2 sum_k (eps_lik^2 + lv_ik) - K/2 log 2pi,   J = logsumexp_{j in S_i} sum_k l_ijk - c_i,
+ *   P = sum_k [logsumexp_{j in S_i} l_ijk - c_i],       Bp = log p(z_li | y_i) of the Gaussian prior (means, T as jvae_iw_bound_fwd_f32)
+ *   mi = mean_l (A - J),  tc = mean_l (J - P),  dwkl = mean_l (P - Bp),  reg = alpha mi + beta_tc tc + gamma dwkl        each (N,)
+ * z (L+1, N, K), mu, lv (N, K), eps (L, N, K), y (N,) int64, log_n (C,) fp64 = log of the training samples behind each class (NULL:
+ * n_i = |S_i|).  The two logsumexp are the aggregate posterior of jvae_aggpost_logdensity_f32 with the batch as the bank and the
+ * labels as the groups: the same kernels, the same bits for the same pair; every logarithm ends in fp64 and every output is
+ * rounded once.  keep: jvae_tc_keep_bytes(L, N, K) bytes, 16-byte aligned, written by the forward and read by the backward (every
+ * joint exponent Q_ij, the merged (min, 1 / sum) pairs, e^(-lv)); ws: jvae_tc_fwd_workspace_bytes(L, N, K) bytes of scratch, 16-byte
+ * aligned.  Both queries answer 0 for a shape the file does not compute.
+ * Backward: g_reg (N,) (NULL: zeros) -> the DIRECT partial derivatives g_z (L+1, N, K; row 0 zero), g_mu, g_lv (N, K) and, where not
+ * NULL, g_means (C, K) and g_T (C, K; var_dim 1 only, else -1), all overwritten; ws: jvae_tc_bwd_workspace_bytes(N, K) bytes, 8-byte
+ * aligned, when a class gradient is asked for.  Every sum has a fixed order (row pass: j ascending; column pass: i ascending, then l
+ * ascending; class sums as jvae_iw_bound_bwd_f32) and runs in fp64: no floating-point atomics, the same bits from run to run.  With
+ * alpha = beta_tc = gamma the mixture cancels and its weights are exactly 0.
+ * A label outside [0, C) is never an index: NaN in every output of that sample, it is in nobody's set and adds to no class.
+ * jvae_tc_joint_partition(): the rows of a piece of the joint sum (the error bound of the tests counts one merge step per piece).
+ * K > 1024, N > 8192, L N^2 > 2^26 (256 MB of kept exponents), var_dim 2: -2 before any launch.  L < 1, K < 1, C < 1, N < 0, a NaN
+ * weight or a missing pointer: -1; a short keep or ws: -3.  N = 0 launches nothing in the forward. */
+int jvae_tc_joint_partition(void);
+size_t jvae_tc_keep_bytes(int L, int N, int K);
+size_t jvae_tc_fwd_workspace_bytes(int L, int N, int K);
+size_t jvae_tc_bwd_workspace_bytes(int N, int K);
+int jvae_tc_objective_fwd_f32(const float* z, const float* mu, const float* lv, const float* eps, const long long* y,
+                              const float* means, const float* T, const double* log_n, int var_dim, float alpha, float beta_tc,
+                              float gamma, int L, int N, int K, int C, float* reg, float* mi, float* tc, float* dwkl, void* keep,
+                              size_t keep_bytes, void* ws, size_t ws_bytes, void* stream);
+int jvae_tc_objective_bwd_f32(const float* g_reg, const float* z, const float* mu, const float* lv, const long long* y,
+                              const float* means, const float* T, int var_dim, float alpha, float beta_tc, float gamma, int L,
+                              int N, int K, int C, const void* keep, size_t keep_bytes, float* g_z, float* g_mu, float* g_lv,
+                              float* g_means, float* g_T, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

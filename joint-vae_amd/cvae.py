@@ -36,6 +36,10 @@ al. instead of the ELBO: the labelled training-mode evaluate() forms total = -bo
 already holds (ops.iw_bound, csrc/iwae.hip: weights, bound, effective sample size and every direct gradient fused), reports `iwae` and
 `ess` beside the usual losses, and refuses by name what it does not cover; iw_bound(x, y, samples) is the matching evaluation entry,
 the proper log (1/L) sum_l w_l over slabs of draws - not the reference's `iws`.
+TRAIN_OBJECTIVE = 'tcvae' trains on the beta-TCVAE split of Chen et al.: total = cross_x + b (alpha mi + beta_tc tc + gamma dwkl), the
+three terms elbo_decomposition() measures, here estimated over the batch's own posteriors with their gradients (ops.tc_objective,
+csrc/tcvae.hip); TC_WEIGHTS = (alpha, beta_tc, gamma), default (1, 6, 1), TC_DATASET_SIZE the training samples behind the batch
+(train_model() fills it); `mi`, `tc` and `dwkl` are reported beside the usual losses.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -165,6 +169,25 @@ def _mean_over_draws(logits):
     return logits[1] if logits.shape[0] == 2 else logits[1:].mean(0)
 
 
+def _restores_tc_dataset_size(train_model):
+    """train_model() fills TC_DATASET_SIZE from the set it trains on when the attribute is None: whatever way the call ends, the
+    instance gets back what it had (an instance value, or none of its own)."""
+    import functools
+
+    @functools.wraps(train_model)
+    def wrapper(self, *a, **kw):
+        own = 'TC_DATASET_SIZE' in self.__dict__
+        before = self.__dict__.get('TC_DATASET_SIZE')
+        try:
+            return train_model(self, *a, **kw)
+        finally:
+            if own:
+                self.TC_DATASET_SIZE = before
+            else:
+                self.__dict__.pop('TC_DATASET_SIZE', None)
+    return wrapper
+
+
 def _grad_nan_exit():
     print('GRAD NAN')              # cvae.py:2454-2457; detected by the Adam kernel: train_step() checks the flag of the previous update
                                    # before every backward (as the reference's scan does), lazily-read measures check it as well
@@ -261,6 +284,13 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
     # importance-weighted bound over the step's L draws, ops.iw_bound).  Opt-in; an instance may set it.  Evaluation mode is
     # never affected.  What 'iwae' refuses: _check_iwae_objective().
     TRAIN_OBJECTIVE = 'elbo'
+    # 'tcvae' (Chen et al. 2018): the KL of the loss is replaced by alpha mi + beta_tc tc + gamma dwkl, the three terms of
+    # elbo_decomposition() estimated over the batch's own posteriors (ops.tc_objective).  TC_WEIGHTS = (alpha, beta_tc, gamma).
+    # TC_DATASET_SIZE: the training samples behind the batch's sets - None: the batch is the set (train_model() fills it from
+    # the set it trains on and restores it), an int for a single prior, C class counts for a conditional one.  It moves the
+    # three reported terms by constants and enters no gradient.  What 'tcvae' refuses: _check_tc_objective().
+    TC_WEIGHTS = (1., 6., 1.)
+    TC_DATASET_SIZE = None
     # train_model(): run the reference's OOD phase (ood_detection_rates on `oodsets` every `ood_detection_every` epochs and once
     # after the loop, cvae.py:2309-2336,2513-2526).  Opt-in; an instance may set it.  Off: one warning, the phase is skipped.
     TRAIN_OOD_PHASE = False
@@ -738,6 +768,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                   gamma_weighting=1, z_output=False, epsilon=None, **kw):
         # the labelled training-mode evaluation alone follows TRAIN_OBJECTIVE (refusals are raised here, before any work)
         iwae = self.training and y is not None and self._check_iwae_objective(kl_var_weighting, kw)
+        tcvae = self.training and y is not None and self._check_tc_objective(kl_var_weighting, kw)
         if y is None or self.is_vib:
             if self.is_vib:
                 return self._evaluate_vib(x, y, batch, current_measures, with_beta, kl_var_weighting, gamma_weighting,
@@ -812,6 +843,20 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             total = -bound
             if cross_y_weight:
                 total = total + cw * ce
+        elif tcvae:
+            # TRAIN_OBJECTIVE = 'tcvae': total = cross_x + b (alpha mi + beta_tc tc + gamma dwkl) (+ cw cross_y).  The
+            # reconstruction term keeps the ELBO's own path (ops.elbo with a zero KL operand); the regulariser and its direct
+            # gradients are ops.tc_objective (csrc/tcvae.hip), autograd carries z and log_var on through the unchanged latent op.
+            # kl, zdist and var_kl are reported as before, outside the loss.
+            wmse_s = ops.recon_wmse(x_reco, x, s, s_kind, snapshot=bool(self.sigma.decay))                      # (L, N)
+            b = self.beta if with_beta else 1.
+            wmse, cross_x, total, mse = ops.elbo(wmse_s, torch.zeros_like(terms['kl']), ce if cross_y_weight else None, s, s_kind,
+                                                 D, b, float(cross_y_weight or 0.), with_mse=True)
+            pr = self.encoder.prior
+            lab, means, T = pr._kernel_operands(y if pr.conditional else None, N, x.device)
+            reg, tc_mi, tc_tc, tc_dwkl = ops.tc_objective(z, mu.contiguous(), log_var, eps, lab, means, T, self.TC_WEIGHTS,
+                                                          self._tc_log_n(means.shape[0], x.device), var_dim=pr.var_dim)
+            total = total + b * reg
         else:
             wmse_s = ops.recon_wmse(x_reco, x, s, s_kind, snapshot=bool(self.training and self.sigma.decay))     # (L, N)
             wmse, cross_x, total, mse = ops.elbo(wmse_s, terms['kl'], ce if cross_y_weight else None, s, s_kind, D,
@@ -820,6 +865,8 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         losses = {'kl': terms['kl'], 'zdist': terms['distance'], 'var_kl': terms['var_kl']}
         if iwae:
             losses['iwae'], losses['ess'] = bound, ess
+        if tcvae:
+            losses['mi'], losses['tc'], losses['dwkl'] = tc_mi, tc_tc, tc_dwkl
         dictionary = self.encoder.prior.mean if self.encoder.prior.conditional else None
         if dictionary is not None:
             losses['dzdist'] = terms['dzdist']
@@ -855,8 +902,10 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         objective = self.TRAIN_OBJECTIVE
         if objective == 'elbo':
             return False
+        if objective == 'tcvae':                   # _check_tc_objective() decides that branch and makes its own refusals
+            return False
         if objective != 'iwae':
-            raise ValueError("TRAIN_OBJECTIVE is 'elbo' or 'iwae', got {!r}".format(objective))
+            raise ValueError("TRAIN_OBJECTIVE is 'elbo' or 'iwae' or 'tcvae', got {!r}".format(objective))
 
         def refuse(what):
             raise NotImplementedError("TRAIN_OBJECTIVE = 'iwae': " + what)
@@ -893,6 +942,80 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             refuse("the full-variance prior (var_dim='full') is not built: 'scalar' and 'diag' only")
         if getattr(self, 'compute_dtype', 'fp32') != 'fp32':
             refuse('the bf16 compute mode is not built (set_compute_dtype("fp32"))')
+
+    # ------------------------------------------------------------------------------------ beta-TCVAE objective
+    def _check_tc_objective(self, kl_var_weighting, kw):
+        """Is this training-mode evaluate() on the beta-TCVAE split?  True for TRAIN_OBJECTIVE 'tcvae', or NotImplementedError
+        naming what the split is not built for; False for every other value (_check_iwae_objective(),
+        called first, has already refused an unknown one)."""
+        if self.TRAIN_OBJECTIVE != 'tcvae':
+            return False
+
+        def refuse(what):
+            raise NotImplementedError("TRAIN_OBJECTIVE = 'tcvae': " + what)
+        self._iw_model_refusals(refuse)
+        if self.encoder.mixed_prior is not None:
+            refuse('a mixed (two-prior) encode is not built')
+        if not self.encoder.sampling.is_sampled:
+            refuse('the encoder does not sample (latent_sampling <= 1 and beta = 0): there are no draws to place in the mixture')
+        if torch.is_tensor(kl_var_weighting) or kl_var_weighting != 1:
+            refuse('kl_var_weighting != 1 (a warm-up on the variance part of the KL) has no meaning for sampled densities')
+        if getattr(self.optimizer, '_world', 1) > 1:
+            refuse('data-parallel training (optimizer._world > 1) is not built: the mixture spans the whole batch and a rank '
+                   'sees only its shard')
+        if (self.TRAIN_CAPTURED or kw.get('_raw_measures') or kw.get('_dev_weights') is not None
+                or kw.get('_dev_state') is not None or getattr(self.optimizer, '_external_reduce', False)
+                or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())):
+            refuse('graph_train_step / capture_train_step / TRAIN_CAPTURED are not built: the captured steps train on the ELBO')
+        weights = self.TC_WEIGHTS
+        if len(weights) != 3 or not all(np.isfinite(float(w)) for w in weights):
+            raise ValueError('TC_WEIGHTS is (alpha, beta_tc, gamma), three finite numbers, got {!r}'.format(weights))
+        return True
+
+    def _tc_log_n(self, C, device):
+        """TC_DATASET_SIZE as the operand of ops.tc_objective: None, or (C,) fp64 on the device, log of the training samples behind
+        each class (kept until the attribute or the device changes)."""
+        size = self.TC_DATASET_SIZE
+        if size is None:
+            return None
+        counts = (int(size),) if np.ndim(size) == 0 else tuple(int(v) for v in size)
+        if len(counts) != C:
+            raise ValueError('TC_DATASET_SIZE: {} expected, got {!r}'.format(
+                'an int (a single prior)' if C == 1 else 'the {} class counts of the conditional prior'.format(C), size))
+        if min(counts) < 1:
+            raise ValueError('TC_DATASET_SIZE: counts >= 1 expected, got {!r}'.format(size))
+        key = (counts, str(device))
+        if getattr(self, '_tc_log_n_cache', (None,))[0] != key:
+            self._tc_log_n_cache = (key, torch.tensor(counts, dtype=torch.float64).log().to(device))
+        return self._tc_log_n_cache[1]
+
+    @staticmethod
+    def _tc_dataset_size_of(trainset, C):
+        """What train_model() fills TC_DATASET_SIZE with: len(trainset) for a single prior (C == 1), else one bincount of its labels
+        (`.targets` / `.labels` of the dataset behind random_split's Subsets where it carries them, else the samples' own)."""
+        if C == 1:
+            return len(trainset)
+        base, indices = trainset, None
+        while isinstance(base, torch.utils.data.Subset):
+            idx = torch.as_tensor(base.indices, dtype=torch.int64)
+            indices = idx if indices is None else idx[indices]
+            base = base.dataset
+        labels = getattr(base, 'targets', None)
+        if labels is None:
+            labels = getattr(base, 'labels', None)
+        transform = getattr(base, 'target_transform', None)
+        lut = getattr(base, 'lut', None)
+        if labels is None or lut is not None:
+            labels = [int(trainset[i][1]) for i in range(len(trainset))]
+        else:
+            labels = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels).to('cpu', torch.int64)
+            labels = (labels if indices is None else labels[indices]).tolist()
+            if transform is not None:
+                labels = [int(transform(int(v))) for v in labels]
+        labels = torch.as_tensor(labels, dtype=torch.int64)
+        labels = labels[(labels >= 0) & (labels < C)]             # a label out of range is in nobody's set: not counted
+        counts = torch.bincount(labels, minlength=C)
+        return tuple(max(int(v), 1) for v in counts.tolist())          # a class without a sample is in no set: any count serves
 
     def _refuse_captured_iwae(self, who):
         """The captured steps train on the ELBO: asked for with another objective they refuse before anything is captured."""
@@ -1754,6 +1877,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             self.training_parameters['sigma'] = self.sigma.host_params(shown['metrics']['sigma'])
         return dict(shown['losses']), dict(shown['metrics'])
 
+    @_restores_tc_dataset_size
     def train_model(self, trainset=None, transformer=None, data_augmentation=None, optimizer=None, epochs=50,
                     batch_size=100, test_batch_size=100, validation=4096, device=None, testset=None, oodsets=None,
                     acc_methods=None, fine_tuning=False, warmup=[0, 0], warmup_gamma=[0, 0], latent_sampling=None,
@@ -1879,6 +2003,13 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         self.training_parameters['warmup_gamma'] = warmup_gamma
         if self.TRAIN_OBJECTIVE != 'elbo':         # a default run writes the job directory it always wrote
             self.training_parameters['objective'] = self.TRAIN_OBJECTIVE
+        if self.TRAIN_OBJECTIVE == 'tcvae':
+            if self.TC_DATASET_SIZE is None:       # the set this call trains on (after the validation split); restored on return
+                prior = self.encoder.prior
+                self.TC_DATASET_SIZE = self._tc_dataset_size_of(trainset, prior.mean.shape[0] if prior.conditional else 1)
+            size = self.TC_DATASET_SIZE
+            self.training_parameters['tc_weights'] = [float(w) for w in self.TC_WEIGHTS]
+            self.training_parameters['tc_dataset_size'] = int(size) if np.ndim(size) == 0 else [int(v) for v in size]
 
         from jvae_compat.recorders import LossRecorder
         sets = [set_name] + (['validation'] if validation else [])

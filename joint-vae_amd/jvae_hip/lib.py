@@ -209,6 +209,12 @@ _SIGS = {
     'jvae_iw_bound_fwd_f32': (c_int, [P] * 8 + [c_int] * 3 + [c_float] + [c_int] * 5 + [P] * 5),
     'jvae_iw_bound_bwd_workspace_bytes': (c_size_t, [c_int, c_int]),
     'jvae_iw_bound_bwd_f32': (c_int, [P] * 7 + [c_int] * 3 + [c_float] + [c_int] * 5 + [P] * 7 + [c_size_t, P]),
+    'jvae_tc_joint_partition': (c_int, []),
+    'jvae_tc_keep_bytes': (c_size_t, [c_int] * 3),
+    'jvae_tc_fwd_workspace_bytes': (c_size_t, [c_int] * 3),
+    'jvae_tc_bwd_workspace_bytes': (c_size_t, [c_int] * 2),
+    'jvae_tc_objective_fwd_f32': (c_int, [P] * 8 + [c_int] + [c_float] * 3 + [c_int] * 4 + [P] * 5 + [c_size_t, P, c_size_t, P]),
+    'jvae_tc_objective_bwd_f32': (c_int, [P] * 7 + [c_int] + [c_float] * 3 + [c_int] * 4 + [P, c_size_t] + [P] * 6 + [c_size_t, P]),
 }
 
 

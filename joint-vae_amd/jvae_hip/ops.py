@@ -1452,6 +1452,107 @@ def iw_bound(wmse_s, z, lv, eps, y, means, T, sigma, sigma_is_log, D, beta=1., v
     return _IwBound.apply(wmse_s, z, lv, eps, y, means, T, sigma, (int(sigma_is_log), int(D), float(beta), VAR_KIND[var_dim]), state)
 
 
+TC_MAX_K, TC_MAX_N, TC_MAX_Q = 1024, 8192, 1 << 26       # the limits of csrc/tcvae.hip (L N^2 <= 2^26: 256 MB of kept exponents)
+
+
+def tc_joint_partition():
+    """Rows of a piece of tc_objective's joint sum (host only): the pieces are merged one after the other."""
+    return int(L.load().jvae_tc_joint_partition())
+
+
+def _tc_operand(t, shape, what, dtype=torch.float32):
+    if t.dtype != dtype:
+        raise L.JvaeHipError(f'tc_objective: {what} must be {dtype}, got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise L.JvaeHipError(f'tc_objective: {what} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+    return t
+
+
+class _TcObjective(torch.autograd.Function):
+    """z (L+1,N,K), mu (N,K), lv (N,K), eps (L,N,K), y, means, T -> (reg, mi, tc, dwkl), each (N,): csrc/tcvae.hip."""
+
+    @staticmethod
+    def forward(ctx, z, mu, lv, eps, y, means, T, log_n, cfg):
+        alpha, beta_tc, gamma, var_dim = cfg
+        Ls, N, K = eps.shape
+        C = means.shape[0]
+        _tc_operand(z, (Ls + 1, N, K), 'z')
+        _tc_operand(mu, (N, K), 'mu')
+        _tc_operand(lv, (N, K), 'log_var')
+        _tc_operand(eps, (Ls, N, K), 'eps')
+        _tc_operand(y, (N,), 'y', torch.int64)
+        _tc_operand(means, (C, K), 'means')
+        _tc_operand(T, (C, K) if var_dim == VAR_KIND['diag'] else ((C, K, K) if var_dim == VAR_KIND['full'] else (C,)), 'T')
+        if log_n is not None:
+            _tc_operand(log_n, (C,), 'log_n', torch.float64)
+        if Ls < 1 or K < 1:
+            raise L.JvaeHipError(f'tc_objective: at least one draw and one coordinate expected, got L={Ls}, K={K}')
+        if K > TC_MAX_K or N > TC_MAX_N:
+            raise L.JvaeHipError(f'tc_objective: K <= {TC_MAX_K} and N <= {TC_MAX_N} expected, got N={N}, K={K} (unsupported configuration)')
+        if Ls * N * N > TC_MAX_Q:
+            raise L.JvaeHipError(f'tc_objective: the kept exponents (L, N, N) would take more than 256 MB (L N^2 = {Ls * N * N} > 2^26): '
+                                 'unsupported configuration, use a smaller batch or fewer draws')
+        operands = [L.ptr(t) for t in (z, mu, lv, eps, y, means, T, log_n)]      # on the device and contiguous, before anything is allocated
+        dev = eps.device
+        lib = L.load()
+        reg, mi, tc, dwkl = (torch.empty(N, device=dev, dtype=torch.float32) for _ in range(4))
+        keep = None
+        if N:
+            keep = torch.empty(lib.jvae_tc_keep_bytes(Ls, N, K), device=dev, dtype=torch.uint8)
+            nbytes = lib.jvae_tc_fwd_workspace_bytes(Ls, N, K)
+            ws = _aligned_ws(nbytes, dev, align=16, what='tc_objective')
+        else:
+            ws = (None, 0)
+        rc = lib.jvae_tc_objective_fwd_f32(*operands, var_dim, alpha, beta_tc, gamma, Ls, N, K, C, L.ptr(reg), L.ptr(mi), L.ptr(tc), L.ptr(dwkl),
+                                           L.ptr(keep), keep.numel() if N else 0, *ws, L.stream_ptr())
+        L.check(rc, 'jvae_tc_objective_fwd_f32')
+        ctx.save_for_backward(z, mu, lv, y, means, T, keep)
+        ctx.cfg = (alpha, beta_tc, gamma, var_dim, Ls, N, K, C)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(mi, tc, dwkl)
+        return reg, mi, tc, dwkl
+
+    @staticmethod
+    def backward(ctx, g_reg, _g_mi, _g_tc, _g_dwkl):
+        z, mu, lv, y, means, T, keep = ctx.saved_tensors
+        alpha, beta_tc, gamma, var_dim, Ls, N, K, C = ctx.cfg
+        dev = z.device
+        lib = L.load()
+        g_z = torch.empty((Ls + 1, N, K), device=dev, dtype=torch.float32)
+        g_mu = torch.empty((N, K), device=dev, dtype=torch.float32)
+        g_lv = torch.empty((N, K), device=dev, dtype=torch.float32)
+        g_means = torch.empty_like(means) if ctx.needs_input_grad[5] else None
+        g_T = torch.empty_like(T) if (ctx.needs_input_grad[6] and var_dim == VAR_KIND['diag']) else None
+        ws = L.workspace(lib.jvae_tc_bwd_workspace_bytes(N, K), dev)
+        g = None if g_reg is None else _c(g_reg)
+        rc = lib.jvae_tc_objective_bwd_f32(L.ptr(g), L.ptr(z), L.ptr(mu), L.ptr(lv), L.ptr(y), L.ptr(means), L.ptr(T), var_dim, alpha,
+                                           beta_tc, gamma, Ls, N, K, C, L.ptr(keep), keep.numel() if N else 0, L.ptr(g_z),
+                                           L.ptr(g_mu), L.ptr(g_lv), L.ptr(g_means), L.ptr(g_T), L.ptr(ws), ws.numel(), L.stream_ptr())
+        L.check(rc, 'jvae_tc_objective_bwd_f32')
+        return g_z, g_mu, g_lv, None, None, g_means, g_T, None, None
+
+
+def tc_objective(z, mu, log_var, eps, y, means, T, weights=(1., 6., 1.), log_n=None, var_dim='scalar'):
+    """The beta-TCVAE split of the KL over the batch's own posteriors (Chen et al. 2018) -> (reg, mi, tc, dwkl), each (N,),
+    csrc/tcvae.hip:
+
+        mi = A - J,  tc = J - P,  dwkl = P - Bp  (means over the L draws),   reg = alpha mi + beta_tc tc + gamma dwkl
+        A = log q(z_l | x),  J = logsumexp_{j in S} sum_k l_jk - c,  P = sum_k [logsumexp_{j in S} l_jk - c],  Bp = log p(z_l | y)
+
+    with S the rows of the batch that carry the sample's label (one class: the whole batch) and c = log |S| + log n.  z (L+1, N, K)
+    and log_var (N, K) of latent (row 0 of z takes no part), mu (N, K), eps (L, N, K) the noise of the draws, y (N,) int64, means
+    (C, K) and T ((C,) 'scalar' / (C, K) 'diag') of the Gaussian prior, weights = (alpha, beta_tc, gamma), log_n (C,) fp64 on the
+    device = log of the number of training samples behind each class (None: n = |S|, the plain minibatch estimator; it moves the
+    three terms by constants and enters no gradient).  Differentiable in z, mu, log_var, means and T ('diag') with the DIRECT
+    partial derivatives; autograd carries z and log_var on through latent's backward.  mi, tc and dwkl carry no gradient.  Operands
+    must be fp32 (y int64), contiguous and on the device.  K <= 1024, N <= 8192 and L N^2 <= 2^26; var_dim 'full' is refused by the
+    library.  A label outside [0, C): NaN in every output of that sample, which is in nobody's set."""
+    if var_dim not in VAR_KIND:
+        raise L.JvaeHipError(f'tc_objective: var_dim {var_dim!r} unknown')
+    a, b, g = (float(w) for w in weights)
+    return _TcObjective.apply(z, mu, log_var, eps, y, means, T, log_n, (a, b, g, VAR_KIND[var_dim]))
+
+
 def measures(x, wmse, zdist, var_kl, sigma, sigma_is_log, means, flag, scratch, prev=None, batch=0, run=None, counter=None):
     """-> device tensor of 16 floats (layout in csrc/loss.hip measures_kernel); `scratch`: 1-float device tensor;
     `prev`: the tensor returned for the previous batch (running means are continued on the device).

@@ -1135,6 +1135,35 @@ int jvae_tc_objective_bwd_f32(const float* g_reg, const float* z, const float* m
                               int N, int K, int C, const void* keep, size_t keep_bytes, float* g_z, float* g_mu, float* g_lv,
                               float* g_means, float* g_T, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- class-marginal KL of the unlabelled rows of a training batch, forward and backward (csrc/semisup.hip; the bound of Hershey &
+ * Olsen 2007; no counterpart in the reference) ----
+ * mu, lv (N, K) (lv: the clipped log-variance), y (N,) int64, means (C, K), T ((C,) var_dim 0 / (C, K) var_dim 1) as
+ * jvae_latent_fwd_f32 takes them, log_pi (C,) fp64 = the logarithms of the class weights (NULL: uniform), w the weight of var_kl.
+ * A row with y >= 0 is labelled: kl / zdist / var_kl are its kl_in / zdist_in / var_kl_in bit for bit, its row of r is one-hot on
+ * y (all zero for y >= C, which is never an index).  A row with y < 0 has no label:
+ *   d_c = sum_k t_ck^2 (mu_k - m_ck)^2,   v_c = sum_k (e^lv_k t_ck^2 - lv_k - log t_ck^2 - 1),   KL_c = 1/2 (d_c + w v_c)
+ *   kl = U = -log sum_c pi_c exp(-KL_c),   r_c = pi_c exp(-KL_c) / sum_c' pi_c' exp(-KL_c'),
+ *   zdist = sum_c r_c d_c,   var_kl = sum_c r_c v_c
+ * U is an upper bound of KL(q || sum_c pi_c p_c).  ONE launch; fp64 from the fp32 operands to the one rounding of each output; the
+ * sum is shifted by min_c (KL_c - log pi_c).  r (N, C) fp32, jvae_semi_keep_bytes(N, C) bytes: returned, and read by the backward.
+ * ws: jvae_semi_fwd_workspace_bytes(N, C) bytes of scratch, 8-byte aligned.  Both queries answer 0 for a shape the file does not
+ * compute.
+ * Backward: g_kl (N,) (NULL: zeros) -> g_kl_in (N,) (g_kl of a labelled row, 0 of an unlabelled one), g_mu, g_lv (N, K) (zero rows
+ * for labelled samples) and, where not NULL, g_means (C, K) and g_T (C, K; var_dim 1 only, else -1), all overwritten.  Two launches
+ * (one when no class gradient is asked for), fp64 sums of fp32 operands in fixed orders (rows: c ascending; classes: 16 contiguous
+ * chunks of rows in row order, folded in chunk order), no atomics: the same bits from run to run.  zdist and var_kl carry no gradient.
+ * -1 before any launch: a missing or misaligned pointer (4 bytes; y, log_pi and ws 8), var_dim other than 0 or 1, a non-finite w,
+ * K < 1, K > 1024, C < 1, C > 1024, N < 0, N > 2^20; -3: a short r or ws.  N = 0 launches nothing in the forward. */
+size_t jvae_semi_keep_bytes(int N, int C);
+size_t jvae_semi_fwd_workspace_bytes(int N, int C);
+int jvae_semi_class_marginal_fwd_f32(const float* mu, const float* lv, const long long* y, const float* means, const float* T,
+                                     const double* log_pi, int var_dim, float w, int N, int K, int C, const float* kl_in,
+                                     const float* zdist_in, const float* var_kl_in, float* kl, float* zdist, float* var_kl, float* r,
+                                     size_t r_bytes, void* ws, size_t ws_bytes, void* stream);
+int jvae_semi_class_marginal_bwd_f32(const float* g_kl, const float* mu, const float* lv, const long long* y, const float* means,
+                                     const float* T, int var_dim, float w, int N, int K, int C, const float* r, size_t r_bytes,
+                                     float* g_kl_in, float* g_mu, float* g_lv, float* g_means, float* g_T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

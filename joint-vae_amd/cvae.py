@@ -40,6 +40,10 @@ TRAIN_OBJECTIVE = 'tcvae' trains on the beta-TCVAE split of Chen et al.: total =
 three terms elbo_decomposition() measures, here estimated over the batch's own posteriors with their gradients (ops.tc_objective,
 csrc/tcvae.hip); TC_WEIGHTS = (alpha, beta_tc, gamma), default (1, 6, 1), TC_DATASET_SIZE the training samples behind the batch
 (train_model() fills it); `mi`, `tc` and `dwkl` are reported beside the usual losses.
+SEMI_SUPERVISED = True (class attribute, settable per instance; default False) lets a training batch carry unlabelled rows: a
+negative label gives that row the class-marginal KL U = -log sum_c pi_c exp(-KL_c) (ops.class_marginal_kl, csrc/semisup.hip),
+labelled rows are untouched; UNLABELLED_CLASS_WEIGHTS sets pi, class_marginal(x) returns (U, q(y|x)) in evaluation, and what
+is not covered is refused by name.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -291,6 +295,12 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
     # three reported terms by constants and enters no gradient.  What 'tcvae' refuses: _check_tc_objective().
     TC_WEIGHTS = (1., 6., 1.)
     TC_DATASET_SIZE = None
+    # semi-supervised training: a NEGATIVE label of the labelled training-mode evaluate() means "no label".  Such a row's KL is
+    # the class-marginal bound U = -log sum_c pi_c exp(-KL_c) (ops.class_marginal_kl) instead of the KL to
+    # ONE class; labelled rows are untouched.  Opt-in; an instance may set it.  UNLABELLED_CLASS_WEIGHTS: None (uniform pi) or C
+    # positive numbers, normalised once.  What it refuses: _check_semi_supervised().
+    SEMI_SUPERVISED = False
+    UNLABELLED_CLASS_WEIGHTS = None
     # train_model(): run the reference's OOD phase (ood_detection_rates on `oodsets` every `ood_detection_every` epochs and once
     # after the loop, cvae.py:2309-2336,2513-2526).  Opt-in; an instance may set it.  Off: one warning, the phase is skipped.
     TRAIN_OOD_PHASE = False
@@ -766,7 +776,9 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
 
     def _evaluate(self, x, y=None, batch=0, current_measures=None, with_beta=False, kl_var_weighting=1.,
                   gamma_weighting=1, z_output=False, epsilon=None, **kw):
-        # the labelled training-mode evaluation alone follows TRAIN_OBJECTIVE (refusals are raised here, before any work)
+        # the labelled training-mode evaluation alone follows SEMI_SUPERVISED and TRAIN_OBJECTIVE (refusals are raised here, before
+        # any work)
+        semi = self.training and y is not None and self._check_semi_supervised(kl_var_weighting, kw)
         iwae = self.training and y is not None and self._check_iwae_objective(kl_var_weighting, kw)
         tcvae = self.training and y is not None and self._check_tc_objective(kl_var_weighting, kw)
         if y is None or self.is_vib:
@@ -796,6 +808,12 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             kl_var_weighting = dev_weights[0:1]
             cw = dev_weights[1:2] if cross_y_weight else cross_y_weight
 
+        y_given = y
+        if semi:
+            # the draws and the labelled rows are what they are without the switch.  An unlabelled row is measured against class
+            # 0 by the latent op and that kl is then discarded: its backward meets g = 0 there.  0 x inf is not reachable: with
+            # the log-variance clipped to +-20 and fp32 means the class-0 terms stay far below the fp32 range.
+            y = y.clamp_min(0)
         feats = self._features_of(x).reshape(N, -1)
         y1h = onehot_encoding(y, self.num_labels).float() if self.y_is_coded else None
         try:
@@ -804,6 +822,16 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             self._dump_after_encoder_error(err, x, y)
             raise
         self._last_epsilon = eps
+        if semi:
+            # SEMI_SUPERVISED: the rows with a negative label take the class-marginal bound, its zdist and var_kl (ops.class_marginal_kl,
+            # csrc/semisup.hip); the others pass through with their bits.  The op runs on every such step: the host never asks
+            # whether a batch holds an unlabelled row.
+            pr = self.encoder.prior
+            s_kl, s_zd, s_vkl, _ = ops.class_marginal_kl(
+                mu.reshape(N, -1).contiguous(), log_var.reshape(N, -1), y_given, pr.mean, pr._var_parameter, terms['kl'],
+                terms['distance'], terms['var_kl'], log_pi=self._semi_log_pi(pr.mean.shape[0], x.device),
+                w=float(kl_var_weighting), var_dim=pr.var_dim)
+            terms = dict(terms, kl=s_kl, distance=s_zd, var_kl=s_vkl)
         if self.training and self.optimizer._world > 1 and z.requires_grad \
                 and not getattr(self.optimizer, '_external_reduce', False):
             # data-parallel: the decoder's gradients are final once d(loss)/dz exists -> start their all-reduce there
@@ -815,6 +843,8 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         ce = None
         if self.y_is_decoded:
             ce = x_loss(y, logits, batch_mean=False)                         # all L+1 rows, as cvae.py:738 does
+            if semi:
+                ce = ce * (y_given >= 0).to(ce.dtype)                        # no label: no cross_y, in value and in gradient
         if self.output_distribution == 'categorical':
             # cvae.py:654-660,752-753: -log p(x|z) is the 256-level cross entropy of every pixel, summed over the image (the
             # only term with a gradient); `wmse` is the plain mean-square error of the arg-max image (reported, sigma not
@@ -1016,6 +1046,93 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         labels = labels[(labels >= 0) & (labels < C)]             # a label out of range is in nobody's set: not counted
         counts = torch.bincount(labels, minlength=C)
         return tuple(max(int(v), 1) for v in counts.tolist())          # a class without a sample is in no set: any count serves
+
+    # ------------------------------------------------------------------------------------ semi-supervised training
+    def _check_semi_supervised(self, kl_var_weighting, kw):
+        """Does this training-mode evaluate() read negative labels as "no label"?  False while SEMI_SUPERVISED is off; True, or
+        NotImplementedError naming what the class-marginal KL is not built for (DESIGN.md section 7x says why for each)."""
+        if not self.SEMI_SUPERVISED:
+            return False
+
+        def refuse(what):
+            raise NotImplementedError('SEMI_SUPERVISED: ' + what)
+        self._iw_model_refusals(refuse)
+        if not self.encoder.prior.conditional:
+            refuse('a non-conditional prior has no classes to marginalise over')
+        if self.encoder.mixed_prior is not None:
+            refuse('a mixed (two-prior) encode is not built')
+        if self.TRAIN_OBJECTIVE != 'elbo':
+            refuse("TRAIN_OBJECTIVE = {!r} is not built: the class-marginal KL enters the ELBO only".format(self.TRAIN_OBJECTIVE))
+        if torch.is_tensor(kl_var_weighting):
+            refuse('kl_var_weighting as a device scalar is not built: the kernel takes the weight from the host')
+        if getattr(self.optimizer, '_world', 1) > 1:
+            refuse('data-parallel training (optimizer._world > 1) is not built')
+        if (self.TRAIN_CAPTURED or kw.get('_raw_measures') or kw.get('_dev_weights') is not None
+                or kw.get('_dev_state') is not None or getattr(self.optimizer, '_external_reduce', False)
+                or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())):
+            refuse('graph_train_step / capture_train_step / TRAIN_CAPTURED are not built: the captured steps take a label on every row')
+        self._semi_class_weights(self.encoder.prior.mean.shape[0])
+        return True
+
+    def _semi_class_weights(self, C):
+        """UNLABELLED_CLASS_WEIGHTS as a tuple of C floats, or None for uniform weights; ValueError for anything else."""
+        weights = self.UNLABELLED_CLASS_WEIGHTS
+        if weights is None:
+            return None
+        weights = tuple(float(v) for v in (weights.tolist() if hasattr(weights, 'tolist') else weights))
+        if len(weights) != C or not all(np.isfinite(v) and v > 0 for v in weights):
+            raise ValueError('UNLABELLED_CLASS_WEIGHTS is None or {} positive finite numbers, got {!r}'.format(
+                C, self.UNLABELLED_CLASS_WEIGHTS))
+        return weights
+
+    def _semi_log_pi(self, C, device):
+        """UNLABELLED_CLASS_WEIGHTS as the operand of ops.class_marginal_kl: None, or (C,) fp64 on the device, the logarithms of the
+        normalised weights (kept until the attribute or the device changes)."""
+        weights = self._semi_class_weights(C)
+        if weights is None:
+            return None
+        key = (weights, str(device))
+        if getattr(self, '_semi_log_pi_cache', (None,))[0] != key:
+            w = torch.tensor(weights, dtype=torch.float64)
+            self._semi_log_pi_cache = (key, (w / w.sum()).log().to(device))
+        return self._semi_log_pi_cache[1]
+
+    def class_marginal(self, x):
+        """q(y | x) under the class-marginal bound and the bound itself -> (U (N,), r (N, C)), fp32 on the device:
+
+            U = -log sum_c pi_c exp(-KL_c),    r_c = pi_c exp(-KL_c) / sum_c' pi_c' exp(-KL_c'),    KL_c = KL(q(z | x) || p(z | c))
+
+        U is the KL part of the ELBO of the class-marginal model (an upper bound of KL(q || sum_c pi_c p_c)), r the rule predict()
+        applies, with the weights of UNLABELLED_CLASS_WEIGHTS.  The encode-only pass (latent_posterior) and ONE launch of
+        ops.class_marginal_kl with every label -1: no (C, N, K) operand exists.  Runs in eval mode under no_grad (the training flag
+        is restored); SEMI_SUPERVISED need not be set.  Refuses what SEMI_SUPERVISED refuses about the model."""
+        def refuse(what):
+            raise NotImplementedError('class_marginal: ' + what)
+        self._iw_model_refusals(refuse)
+        pr = self.encoder.prior
+        if not pr.conditional:
+            refuse('a non-conditional prior has no classes to marginalise over')
+        was_training = self.training
+        self.eval()
+        try:
+            mu, log_var = self.latent_posterior(x)
+            N = mu.shape[0]
+            with torch.no_grad():
+                none = torch.full((N,), -1, dtype=torch.int64, device=mu.device)
+                zero = torch.zeros(N, dtype=torch.float32, device=mu.device)
+                U, _, _, r = ops.class_marginal_kl(mu.contiguous(), log_var.contiguous(), none, pr.mean.detach(),
+                                                   pr._var_parameter.detach(), zero, zero, zero,
+                                                   log_pi=self._semi_log_pi(pr.mean.shape[0], mu.device), w=1., var_dim=pr.var_dim)
+            return U, r
+        finally:
+            if was_training:
+                self.train()
+
+    def _refuse_captured_semi(self, who):
+        """The captured steps take a label on every row: asked for under SEMI_SUPERVISED they refuse before anything is captured."""
+        if self.SEMI_SUPERVISED:
+            raise NotImplementedError('SEMI_SUPERVISED: {} is not built for it (graph_train_step / capture_train_step / '
+                                      'TRAIN_CAPTURED take a label on every row)'.format(who))
 
     def _refuse_captured_iwae(self, who):
         """The captured steps train on the ELBO: asked for with another objective they refuse before anything is captured."""
@@ -1618,6 +1735,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         steps (losses, measures) before calling this: a live eager autograd graph keeps its gradient-accumulation nodes bound
         to the default stream, which a capture must not touch."""
         self._refuse_captured_iwae('graph_train_step()')
+        self._refuse_captured_semi('graph_train_step()')
         world = getattr(self.optimizer, '_world', 1)
         dev = x.device
         self.optimizer.enable_device_hyper(True)
@@ -1732,6 +1850,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         * `step.epsilon`: the (L, N, K) noise of the replay that has just run; `step.losses`: the graph's loss rows.
         step(x, y) copies the batch in, replays and returns `step.losses`.  Single process only."""
         self._refuse_captured_iwae('capture_train_step()')
+        self._refuse_captured_semi('capture_train_step()')
         if getattr(self.optimizer, '_world', 1) > 1:
             raise NotImplementedError('capture_train_step() is single-process: data-parallel models use graph_train_step()')
         if self.optimizer.kind != 'adam':
@@ -2003,6 +2122,8 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         self.training_parameters['warmup_gamma'] = warmup_gamma
         if self.TRAIN_OBJECTIVE != 'elbo':         # a default run writes the job directory it always wrote
             self.training_parameters['objective'] = self.TRAIN_OBJECTIVE
+        if self.SEMI_SUPERVISED:
+            self.training_parameters['semi_supervised'] = True
         if self.TRAIN_OBJECTIVE == 'tcvae':
             if self.TC_DATASET_SIZE is None:       # the set this call trains on (after the validation split); restored on return
                 prior = self.encoder.prior
@@ -2168,6 +2289,15 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                 for item in self.loader:
                     yield self.convert(item)
         from jvae_compat import torch_load
+        from jvae_compat.semi import HiddenLabels
+        wrapped = trainset                       # train_model() hands over the Subset its seeded random_split returned
+        while isinstance(wrapped, torch.utils.data.Subset):
+            wrapped = wrapped.dataset
+        if isinstance(wrapped, HiddenLabels) and torch_load.device_loader(wrapped.dataset, batch_size, False) is not None:
+            # the resident loader gathers labels (through the set's look-up table) inside its batch launch and hands no sample index
+            # back: hiding labels behind it is not built, and -1 must never reach that table
+            raise NotImplementedError('HiddenLabels over a device-resident image set is not built: wrap the host dataset, or hide the '
+                                      'labels of the device batches yourself')
         resident = torch_load.device_loader(trainset, batch_size, True, data_augmentation,
                                             getattr(self, 'augmentation_generator', None))
         if resident is not None:                 # a device-resident set: gathered, transformed and augmented in one launch

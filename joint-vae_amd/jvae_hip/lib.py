@@ -215,6 +215,10 @@ _SIGS = {
     'jvae_tc_bwd_workspace_bytes': (c_size_t, [c_int] * 2),
     'jvae_tc_objective_fwd_f32': (c_int, [P] * 8 + [c_int] + [c_float] * 3 + [c_int] * 4 + [P] * 5 + [c_size_t, P, c_size_t, P]),
     'jvae_tc_objective_bwd_f32': (c_int, [P] * 7 + [c_int] + [c_float] * 3 + [c_int] * 4 + [P, c_size_t] + [P] * 6 + [c_size_t, P]),
+    'jvae_semi_keep_bytes': (c_size_t, [c_int] * 2),
+    'jvae_semi_fwd_workspace_bytes': (c_size_t, [c_int] * 2),
+    'jvae_semi_class_marginal_fwd_f32': (c_int, [P] * 6 + [c_int, c_float] + [c_int] * 3 + [P] * 7 + [c_size_t, P, c_size_t, P]),
+    'jvae_semi_class_marginal_bwd_f32': (c_int, [P] * 6 + [c_int, c_float] + [c_int] * 3 + [P, c_size_t] + [P] * 6),
 }
 
 

@@ -1553,6 +1553,99 @@ def tc_objective(z, mu, log_var, eps, y, means, T, weights=(1., 6., 1.), log_n=N
     return _TcObjective.apply(z, mu, log_var, eps, y, means, T, log_n, (a, b, g, VAR_KIND[var_dim]))
 
 
+SEMI_MAX_K, SEMI_MAX_C, SEMI_MAX_N = 1024, 1024, 1 << 20       # the limits of csrc/semisup.hip
+
+
+def _semi_operand(t, shape, what, dtype=torch.float32):
+    if t.dtype != dtype:
+        raise L.JvaeHipError(f'class_marginal_kl: {what} must be {dtype}, got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise L.JvaeHipError(f'class_marginal_kl: {what} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+    return t
+
+
+class _ClassMarginalKl(torch.autograd.Function):
+    """mu, lv (N,K), y, means, T, log_pi, the labelled rows' (kl, zdist, var_kl) -> merged (kl, zdist, var_kl), r (N,C): csrc/semisup.hip."""
+
+    @staticmethod
+    def forward(ctx, mu, lv, y, means, T, log_pi, kl_in, zd_in, vkl_in, cfg):
+        w, var_dim = cfg
+        if mu.dim() != 2 or means.dim() != 2:
+            raise L.JvaeHipError(f'class_marginal_kl: mu (N, K) and means (C, K) expected, got {tuple(mu.shape)} and {tuple(means.shape)}')
+        N, K = mu.shape
+        C = means.shape[0]
+        _semi_operand(mu, (N, K), 'mu')
+        _semi_operand(lv, (N, K), 'log_var')
+        _semi_operand(y, (N,), 'y', torch.int64)
+        _semi_operand(means, (C, K), 'means')
+        _semi_operand(T, (C, K) if var_dim == VAR_KIND['diag'] else (C,), 'T')
+        if log_pi is not None:
+            _semi_operand(log_pi, (C,), 'log_pi', torch.float64)
+        for t, what in ((kl_in, 'kl'), (zd_in, 'zdist'), (vkl_in, 'var_kl')):
+            _semi_operand(t, (N,), what)
+        if not math.isfinite(w):
+            raise L.JvaeHipError(f'class_marginal_kl: a finite w expected, got {w}')
+        if K < 1 or C < 1:
+            raise L.JvaeHipError(f'class_marginal_kl: at least one coordinate and one class expected, got K={K}, C={C}')
+        if K > SEMI_MAX_K or C > SEMI_MAX_C or N > SEMI_MAX_N:
+            raise L.JvaeHipError(f'class_marginal_kl: K <= {SEMI_MAX_K}, C <= {SEMI_MAX_C} and N <= {SEMI_MAX_N} expected, got N={N}, K={K}, '
+                                 f'C={C} (unsupported configuration)')
+        operands = [L.ptr(t) for t in (mu, lv, y, means, T, log_pi)]       # on the device and contiguous, before anything is allocated
+        rows = [L.ptr(t) for t in (kl_in, zd_in, vkl_in)]
+        dev = mu.device
+        lib = L.load()
+        kl, zd, vkl = (torch.empty(N, device=dev, dtype=torch.float32) for _ in range(3))
+        r = torch.empty((N, C), device=dev, dtype=torch.float32)
+        ws = _aligned_ws(lib.jvae_semi_fwd_workspace_bytes(N, C), dev, what='class_marginal_kl') if N else (None, 0)
+        rc = lib.jvae_semi_class_marginal_fwd_f32(*operands, var_dim, w, N, K, C, *rows, L.ptr(kl), L.ptr(zd), L.ptr(vkl), L.ptr(r),
+                                                  4 * N * C, *ws, L.stream_ptr())
+        L.check(rc, 'jvae_semi_class_marginal_fwd_f32')
+        ctx.save_for_backward(mu, lv, y, means, T, r)
+        ctx.cfg = (w, var_dim, N, K, C)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(zd, vkl, r)
+        return kl, zd, vkl, r
+
+    @staticmethod
+    def backward(ctx, g_kl, _g_zd, _g_vkl, _g_r):
+        mu, lv, y, means, T, r = ctx.saved_tensors
+        w, var_dim, N, K, C = ctx.cfg
+        dev = mu.device
+        lib = L.load()
+        g_in = torch.empty(N, device=dev, dtype=torch.float32)
+        g_mu = torch.empty((N, K), device=dev, dtype=torch.float32)
+        g_lv = torch.empty((N, K), device=dev, dtype=torch.float32)
+        g_means = torch.empty_like(means) if ctx.needs_input_grad[3] else None
+        g_T = torch.empty_like(T) if (ctx.needs_input_grad[4] and var_dim == VAR_KIND['diag']) else None
+        g = None if g_kl is None else _c(g_kl)
+        rc = lib.jvae_semi_class_marginal_bwd_f32(L.ptr(g), L.ptr(mu), L.ptr(lv), L.ptr(y), L.ptr(means), L.ptr(T), var_dim, w, N, K, C,
+                                                  L.ptr(r), 4 * N * C, L.ptr(g_in), L.ptr(g_mu), L.ptr(g_lv), L.ptr(g_means), L.ptr(g_T),
+                                                  L.stream_ptr())
+        L.check(rc, 'jvae_semi_class_marginal_bwd_f32')
+        return g_mu, g_lv, None, g_means, g_T, None, g_in, None, None, None
+
+
+def class_marginal_kl(mu, log_var, y, means, T, kl, zdist, var_kl, log_pi=None, w=1., var_dim='scalar'):
+    """The KL of a batch in which a NEGATIVE label means "no label" -> (kl, zdist, var_kl (N,), r (N, C)), csrc/semisup.hip.
+
+    A row with y >= 0 keeps the kl, zdist and var_kl given (those of ops.latent), bit for bit; its row of r is one-hot on y.  A row
+    with y < 0 is measured against every class of the Gaussian prior at once:
+
+        KL_c = 1/2 (d_c + w v_c)        d_c, v_c: GaussianPrior.kl's distance and var_kl against class c
+        kl = U = -log sum_c pi_c exp(-KL_c),   r_c = pi_c exp(-KL_c) / sum_c' pi_c' exp(-KL_c'),   zdist = r . d,   var_kl = r . v
+
+    U is an upper bound of KL(q || sum_c pi_c p_c) (Hershey & Olsen 2007), r the optimal q(y | x).  mu, log_var (N, K) (the CLIPPED
+    log-variance), y (N,) int64, means (C, K), T ((C,) 'scalar' / (C, K) 'diag'), log_pi (C,) fp64 on the device (None: uniform
+    weights), w a finite float.  Differentiable in kl only - through mu, log_var, means, T ('diag') for the unlabelled rows and
+    through the incoming kl for the labelled ones; zdist, var_kl and r carry no gradient.  No (N, C, K) tensor exists.  Operands must
+    be fp32 (y int64, log_pi fp64), contiguous and on the device.  K <= 1024, C <= 1024, N <= 2^20; var_dim 'full' has no entry."""
+    if var_dim not in ('scalar', 'diag'):
+        raise L.JvaeHipError(f"class_marginal_kl: var_dim 'scalar' or 'diag' expected, got {var_dim!r}")
+    if torch.is_tensor(w):
+        raise L.JvaeHipError('class_marginal_kl: w is a host float here, not a tensor')
+    return _ClassMarginalKl.apply(mu, log_var, y, means, T, log_pi, kl, zdist, var_kl, (float(w), VAR_KIND[var_dim]))
+
+
 def measures(x, wmse, zdist, var_kl, sigma, sigma_is_log, means, flag, scratch, prev=None, batch=0, run=None, counter=None):
     """-> device tensor of 16 floats (layout in csrc/loss.hip measures_kernel); `scratch`: 1-float device tensor;
     `prev`: the tensor returned for the previous batch (running means are continued on the device).

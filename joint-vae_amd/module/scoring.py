@@ -153,11 +153,27 @@ class ScoringMixin:
                 preds = [self.predict_after_evaluate(logits, losses, method=m) for m in methods]
                 if recording:
                     recorder.append_batch(**losses, y_true=y, logits=logits.T)
-                errors += torch.stack([(p != y).sum() for p in preds]).float()
-                for k, v in losses.items():                     # loss of the TRUE class where a loss is per class (C, N)
-                    v = v.gather(0, y.unsqueeze(0))[0] if v.dim() == 2 else v
-                    sums[k] = sums.get(k, 0.) + v.float().mean()
-                n += y.numel()
+                if getattr(self, 'SEMI_SUPERVISED', False):
+                    # a set with unlabelled samples (validation cut out of a HiddenLabels set, train_accuracy): a negative label
+                    # is no class - such a row counts neither as a prediction nor as an error, it is never an index of the
+                    # gather, and the losses that are per class are averaged over the labelled rows (losses without a class
+                    # axis over all rows, as ever).  n = the labelled rows.
+                    lab = y >= 0
+                    n_lab = int(lab.sum())
+                    errors += torch.stack([((p != y) & lab).sum() for p in preds]).float()
+                    for k, v in losses.items():
+                        if v.dim() == 2:
+                            v = (v.gather(0, y.clamp_min(0).unsqueeze(0))[0].float() * lab).sum() / max(n_lab, 1)
+                        else:
+                            v = v.float().mean()
+                        sums[k] = sums.get(k, 0.) + v
+                    n += n_lab
+                else:
+                    errors += torch.stack([(p != y).sum() for p in preds]).float()
+                    for k, v in losses.items():                     # loss of the TRUE class where a loss is per class (C, N)
+                        v = v.gather(0, y.unsqueeze(0))[0] if v.dim() == 2 else v
+                        sums[k] = sums.get(k, 0.) + v.float().mean()
+                    n += y.numel()
                 if print_result and outputs is not None and hasattr(outputs, 'results'):
                     acc_now = (1 - errors / n).tolist()
                     outputs.results(i, num_batch, 0, 0, losses={k: float(sums[k]) / (i + 1) for k in self.loss_components if k in sums},

@@ -19,7 +19,7 @@
 // five NaNs.  Sums: fp64, an LDS tree per workgroup, then the partials in index order by one thread - no float atomics.
 #include "common.h"
 #include "jvae_internal.h"
-#include "roc_sort.h"                  // roc_pad, roc_key, roc_decode, roc_mean_kernel, roc_sort_rows, ROC_MAX_N
+#include "roc_sort.h"                  // roc_pad, roc_key_canonical, roc_decode, roc_mean_kernel, roc_sort_rows, ROC_MAX_N
 
 namespace {
 
@@ -62,8 +62,7 @@ __global__ __launch_bounds__(256) void prc_keys_kernel(const float* __restrict__
             key = (uint64_t)__double_as_longlong(fabs((double)v - c[m]));
             if (z == 0 && !isfinite(v)) bad |= 2;
         } else {
-            const uint32_t b = __float_as_uint(v);
-            key = (uint64_t)roc_key((b & 0x7FFFFFFFu) ? v : 0.0f);      // -0 and +0: one key
+            key = (uint64_t)roc_key_canonical(v);                      // -0 and +0: one key
         }
         if (v != v) bad |= 1;
     }

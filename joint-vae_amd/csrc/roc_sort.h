@@ -29,6 +29,12 @@ __device__ __forceinline__ uint32_t roc_key(float v) {
 __device__ __forceinline__ float roc_unkey(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
+// roc_key with -0 canonicalised to +0: IEEE-equal scores are ONE key, as they are one value to numpy.  For every caller that
+// compares KEYS (tie groups in prc.hip) or breaks ties by a payload packed behind the key (positions in scod.hip); a caller
+// that compares the decoded floats (roc.hip) keeps roc_key, whose image roc_unkey inverts bit for bit.
+__device__ __forceinline__ uint32_t roc_key_canonical(float v) {
+    return roc_key((__float_as_uint(v) & 0x7FFFFFFFu) ? v : 0.0f);
+}
 
 // Mode word of a row -> 0 one-sided, 1 around-mean, 2 strided quantiles with the factors f_low = bits 8-15 and f_up = bits
 // 16-23, each in [1, 255], of the word 2 | f_low << 8 | f_up << 16; -1: the word decodes to nothing.

@@ -15,8 +15,9 @@
 // [0, C) is never used as an index: its sample gets NaN and the status word is set to 1.
 //
 // Curves (scrisk, scod.py:17-57, and the figures of scod.py:231-235): per row, 64-bit keys - the sortable score bits in the high
-// word, (position << 2) | {0 correct, 1 wrong, 2 ood} in the low word - go through the padded bitonic network of roc_sort.h:
-// the order is the stable one, and the payload travels with the key.  One packed inclusive scan in sort order then gives the
+// word (roc_key_canonical: -0 and +0 are one score), (position << 2) | {0 correct, 1 wrong, 2 ood} in the low word - go through
+// the padded bitonic network of roc_sort.h: the order is the stable one, IEEE-equal scores by position, and the payload
+// travels with the key.  One packed inclusive scan in sort order then gives the
 // wrong and the in-distribution counts (both below 2^24: a 32-bit half each); the OOD count of position i is i + 1 minus the
 // in count.  tpr = in / n_in, fpr = ood / n_ood, selective_risk = wrong / in (0 / 0 -> 0): correctly rounded fp32 divisions of
 // integers below 2^24, which fp32 holds exactly.  The scan is tile totals, one exclusive scan of the totals per row, tile scan.
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256) void scod_keys_kernel(const float* __restrict_
         const float v = scores[(size_t)m * n + i];
         const long long yt = y_true[i];
         const unsigned code = yt < 0 ? 2u : (yt != y_est[i] ? 1u : 0u);
-        key = ((u64)roc_key(v) << 32) | (u64)(((unsigned)i << 2) | code);
+        key = ((u64)roc_key_canonical(v) << 32) | (u64)(((unsigned)i << 2) | code);    // -0 and +0: equal, so by position
         if (v != v) atomicOr(&status[m], 1);       // an integer flag: the result does not depend on the order
     }
     keys[(size_t)m * P + i] = key;

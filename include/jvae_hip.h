@@ -1164,6 +1164,38 @@ int jvae_semi_class_marginal_bwd_f32(const float* g_kl, const float* mu, const f
                                      const float* T, int var_dim, float w, int N, int K, int C, const float* r, size_t r_bytes,
                                      float* g_kl_in, float* g_mu, float* g_lv, float* g_means, float* g_T, void* stream);
 
+/* ---- MMD-regularised bound of the training step, forward and backward (csrc/mmd.hip; InfoVAE, Zhao et al. 2019; WAE-MMD,
+ * Tolstikhin et al. 2018; no counterpart in the reference) ----
+ * For sample i of class y[i], its draws l = 1..L (row 0 of z takes no part) and S_i = the rows j of the batch with y[j] = y[i]
+ * (joint = 0: the whole batch):
+ *   p_li = means[y_i] + eps_p_li / T[y_i(, k)]     (the 'scalar' / 'diag' expression of jvae_prior_sample_f32, bit for bit)
+ *   m_i  = mean_l [ 1/(N-1) sum_{j in S_i, j != i} k(z_li, z_lj) + 1/(N-1) sum_{j in S_i, j != i} k(p_li, p_lj)
+ *                 - 2/N sum_{j in S_i} k(z_li, p_lj) ]                                (N = 1: the two within sums are 0)
+ *   kind 0 (imq): k(a, b) = sum_s scales[s] / (scales[s] + |a - b|^2);  kind 1 (rbf): sum_s exp(-|a - b|^2 / (2 scales[s]))
+ * mean_i m_i is the unbiased U-statistic of MMD^2 between q(z, y) and pi_hat(y) p(z | y).  z (L+1, N, K), eps_p (L, N, K), y (N,)
+ * int64, means (C, K), T ((C,) var_dim 0 / (C, K) var_dim 1) on the device; scales: n_scales (1..8) positive finite floats in
+ * HOST memory, read before the call returns.  Squared distances are direct fp32 chains over k (never |a|^2 + |b|^2 - 2ab); kernel
+ * values are fp32; every sum over pairs is an fp64 chain in a fixed order, each output is rounded once.  m (N,).
+ * Backward: g_m (N,) (NULL: zeros) -> the DIRECT partial derivatives g_z (L+1, N, K; row 0 zero) and, where not NULL, g_means
+ * (C, K) and g_T ((C,) var_dim 0 / (C, K) var_dim 1) through p, all overwritten.  Kernel values are formed again: nothing is kept
+ * between the two calls and there is no limit on L N^2.  The class sums run as those of jvae_iw_bound_bwd_f32.  No floating-point
+ * atomics: the same bits from run to run.  Coincident points add exactly 0; with g_m all zero every gradient is exactly 0.
+ * ws: jvae_mmd_fwd_workspace_bytes / jvae_mmd_bwd_workspace_bytes(L, N, K) bytes of scratch, 16-byte aligned; both queries answer
+ * 0 for a shape the file does not compute.  jvae_mmd_tile: the rows of a workgroup's tile (host only).
+ * A label outside [0, C) is never an index: NaN in every output of that sample, it is in nobody's set and adds to no class.
+ * K > 1024, N > 8192, L > 65535, var_dim 2: -2 before any launch.  L < 1, K < 1, C < 1, N < 0, an unknown kind, joint other than
+ * 0 / 1, n_scales outside 1..8, a scale that is not positive and finite or a missing pointer: -1; a short ws: -3.  N = 0 launches
+ * nothing in the forward and writes zeros to the class gradients in the backward. */
+int jvae_mmd_tile(void);
+size_t jvae_mmd_fwd_workspace_bytes(int L, int N, int K);
+size_t jvae_mmd_bwd_workspace_bytes(int L, int N, int K);
+int jvae_mmd_objective_fwd_f32(const float* z, const float* eps_p, const long long* y, const float* means, const float* T,
+                               int var_dim, int kind, const float* scales, int n_scales, int joint, int L, int N, int K, int C,
+                               float* m, void* ws, size_t ws_bytes, void* stream);
+int jvae_mmd_objective_bwd_f32(const float* g_m, const float* z, const float* eps_p, const long long* y, const float* means,
+                               const float* T, int var_dim, int kind, const float* scales, int n_scales, int joint, int L, int N,
+                               int K, int C, float* g_z, float* g_means, float* g_T, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

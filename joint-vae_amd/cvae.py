@@ -44,6 +44,10 @@ SEMI_SUPERVISED = True (class attribute, settable per instance; default False) l
 negative label gives that row the class-marginal KL U = -log sum_c pi_c exp(-KL_c) (ops.class_marginal_kl, csrc/semisup.hip),
 labelled rows are untouched; UNLABELLED_CLASS_WEIGHTS sets pi, class_marginal(x) returns (U, q(y|x)) in evaluation, and what
 is not covered is refused by name.
+TRAIN_OBJECTIVE = 'mmd' trains on an MMD-regularised bound (InfoVAE, Zhao et al.; WAE-MMD, Tolstikhin et al.): total = cross_x +
+b kl_weight kl + mmd_weight m, m the per-row terms of the unbiased MMD^2 between the step's draws and draws of the sample's own
+class prior (ops.mmd_objective, csrc/mmd.hip); MMD_WEIGHTS = (kl_weight, mmd_weight), default (1, 1000), MMD_KERNEL = (kind,
+scales), MMD_JOINT; `mmd` is reported beside the usual losses and prior_mmd(codes, y) is the evaluation entry.
 There is no CPU path: calling forward/evaluate with CPU tensors raises.
 """
 import contextlib
@@ -295,6 +299,15 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
     # three reported terms by constants and enters no gradient.  What 'tcvae' refuses: _check_tc_objective().
     TC_WEIGHTS = (1., 6., 1.)
     TC_DATASET_SIZE = None
+    # 'mmd' (InfoVAE / WAE-MMD): total = cross_x + b kl_weight kl + mmd_weight m (+ cw cross_y), m the per-row terms of the unbiased
+    # MMD^2 between the step's draws and as many draws of each sample's own class prior (ops.mmd_objective).  MMD_WEIGHTS =
+    # (kl_weight, mmd_weight): (1, 1000) is InfoVAE's alpha = 0, lambda = 1000 (not tuned on this model), (0, lambda) is WAE-MMD.
+    # MMD_KERNEL = (kind, scales): 'imq' or 'rbf', scales a tuple of at most 8 positive floats or None (2 K s for WAE's seven s).
+    # MMD_JOINT: pairs are counted inside a class only (the MMD of the joint laws of (z, y)); False matches the two mixtures.
+    # What 'mmd' refuses: _check_mmd_objective().
+    MMD_WEIGHTS = (1., 1000.)
+    MMD_KERNEL = ('imq', None)
+    MMD_JOINT = True
     # semi-supervised training: a NEGATIVE label of the labelled training-mode evaluate() means "no label".  Such a row's KL is
     # the class-marginal bound U = -log sum_c pi_c exp(-KL_c) (ops.class_marginal_kl) instead of the KL to
     # ONE class; labelled rows are untouched.  Opt-in; an instance may set it.  UNLABELLED_CLASS_WEIGHTS: None (uniform pi) or C
@@ -778,6 +791,7 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
                   gamma_weighting=1, z_output=False, epsilon=None, **kw):
         # the labelled training-mode evaluation alone follows SEMI_SUPERVISED and TRAIN_OBJECTIVE (refusals are raised here, before
         # any work)
+        mmd = self.training and y is not None and self._check_mmd_objective(kl_var_weighting, kw)      # first: it names SEMI_SUPERVISED
         semi = self.training and y is not None and self._check_semi_supervised(kl_var_weighting, kw)
         iwae = self.training and y is not None and self._check_iwae_objective(kl_var_weighting, kw)
         tcvae = self.training and y is not None and self._check_tc_objective(kl_var_weighting, kw)
@@ -887,6 +901,26 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             reg, tc_mi, tc_tc, tc_dwkl = ops.tc_objective(z, mu.contiguous(), log_var, eps, lab, means, T, self.TC_WEIGHTS,
                                                           self._tc_log_n(means.shape[0], x.device), var_dim=pr.var_dim)
             total = total + b * reg
+        elif mmd:
+            # TRAIN_OBJECTIVE = 'mmd': total = cross_x + b kl_weight kl + mmd_weight m (+ cw cross_y).  The ELBO keeps its own path
+            # (ops.elbo with the KL operand scaled by kl_weight); m and its direct gradients are ops.mmd_objective (csrc/mmd.hip) on
+            # the step's own z and a second noise tensor, drawn here - after the encoder's draw and under this objective only, so
+            # that every other run keeps its random stream.  kl, zdist and var_kl are reported as before.
+            wmse_s = ops.recon_wmse(x_reco, x, s, s_kind, snapshot=bool(self.sigma.decay))                      # (L, N)
+            kl_weight, mmd_weight = (float(w) for w in self.MMD_WEIGHTS)
+            wmse, cross_x, total, mse = ops.elbo(wmse_s, terms['kl'] if kl_weight == 1. else terms['kl'] * kl_weight,
+                                                 ce if cross_y_weight else None, s, s_kind, D, self.beta if with_beta else 1.,
+                                                 float(cross_y_weight or 0.), with_mse=True)
+            pr = self.encoder.prior
+            lab, means, T = pr._kernel_operands(y if pr.conditional else None, N, x.device)
+            eps_p = kw.get('prior_epsilon')
+            if eps_p is None:
+                eps_p = torch.randn(eps.shape, device=x.device, dtype=torch.float32)
+            elif tuple(eps_p.shape) != tuple(eps.shape):
+                raise ValueError('prior_epsilon must be {}, got {}'.format(tuple(eps.shape), tuple(eps_p.shape)))
+            self._last_prior_epsilon = eps_p
+            mmd_rows = ops.mmd_objective(z, eps_p, lab, means, T, kernel=self.MMD_KERNEL, joint=self.MMD_JOINT, var_dim=pr.var_dim)
+            total = total + mmd_weight * mmd_rows
         else:
             wmse_s = ops.recon_wmse(x_reco, x, s, s_kind, snapshot=bool(self.training and self.sigma.decay))     # (L, N)
             wmse, cross_x, total, mse = ops.elbo(wmse_s, terms['kl'], ce if cross_y_weight else None, s, s_kind, D,
@@ -897,6 +931,8 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             losses['iwae'], losses['ess'] = bound, ess
         if tcvae:
             losses['mi'], losses['tc'], losses['dwkl'] = tc_mi, tc_tc, tc_dwkl
+        if mmd:
+            losses['mmd'] = mmd_rows
         dictionary = self.encoder.prior.mean if self.encoder.prior.conditional else None
         if dictionary is not None:
             losses['dzdist'] = terms['dzdist']
@@ -932,10 +968,10 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         objective = self.TRAIN_OBJECTIVE
         if objective == 'elbo':
             return False
-        if objective == 'tcvae':                   # _check_tc_objective() decides that branch and makes its own refusals
-            return False
+        if objective in ('tcvae', 'mmd'):          # _check_tc_objective() / _check_mmd_objective() decide those branches and make
+            return False                           # their own refusals
         if objective != 'iwae':
-            raise ValueError("TRAIN_OBJECTIVE is 'elbo' or 'iwae' or 'tcvae', got {!r}".format(objective))
+            raise ValueError("TRAIN_OBJECTIVE is 'elbo' or 'iwae' or 'tcvae' or 'mmd', got {!r}".format(objective))
 
         def refuse(what):
             raise NotImplementedError("TRAIN_OBJECTIVE = 'iwae': " + what)
@@ -1046,6 +1082,80 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
         labels = labels[(labels >= 0) & (labels < C)]             # a label out of range is in nobody's set: not counted
         counts = torch.bincount(labels, minlength=C)
         return tuple(max(int(v), 1) for v in counts.tolist())          # a class without a sample is in no set: any count serves
+
+    # ------------------------------------------------------------------------------------ MMD-regularised objective
+    def _check_mmd_objective(self, kl_var_weighting, kw):
+        """Is this training-mode evaluate() on the MMD-regularised bound?  True for TRAIN_OBJECTIVE 'mmd', or NotImplementedError
+        naming what it is not built for; False for every other value (_check_iwae_objective() refuses an
+        unknown one).  kl_var_weighting is free here, a device scalar included: the KL keeps its own path."""
+        if self.TRAIN_OBJECTIVE != 'mmd':
+            return False
+
+        def refuse(what):
+            raise NotImplementedError("TRAIN_OBJECTIVE = 'mmd': " + what)
+        self._iw_model_refusals(refuse)
+        if self.encoder.mixed_prior is not None:
+            refuse('a mixed (two-prior) encode is not built')
+        if not self.encoder.sampling.is_sampled:
+            refuse('the encoder does not sample (latent_sampling <= 1 and beta = 0): there are no draws to compare with the prior')
+        if self.SEMI_SUPERVISED:
+            refuse('SEMI_SUPERVISED is not built: a row without a label has no class prior to draw from')
+        if getattr(self.optimizer, '_world', 1) > 1:
+            refuse('data-parallel training (optimizer._world > 1) is not built: the pairs span the whole batch and a rank '
+                   'sees only its shard')
+        if (self.TRAIN_CAPTURED or kw.get('_raw_measures') or kw.get('_dev_weights') is not None
+                or kw.get('_dev_state') is not None or getattr(self.optimizer, '_external_reduce', False)
+                or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())):
+            refuse('graph_train_step / capture_train_step / TRAIN_CAPTURED are not built: the captured steps train on the ELBO')
+        self._mmd_settings()
+        return True
+
+    def _mmd_settings(self):
+        """(kl_weight, mmd_weight, kind, scales) of MMD_WEIGHTS and MMD_KERNEL, or ValueError naming the malformed attribute."""
+        weights = self.MMD_WEIGHTS
+        try:
+            ok = len(weights) == 2 and all(np.isfinite(float(w)) for w in weights)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('MMD_WEIGHTS is (kl_weight, mmd_weight), two finite numbers, got {!r}'.format(weights))
+        try:
+            kind, scales = ops.mmd_scales(self.MMD_KERNEL, self.latent_dim)
+        except _lib.JvaeHipError as err:
+            raise ValueError("MMD_KERNEL is (kind, scales): 'imq' or 'rbf', and at most 8 positive finite scales or None, "
+                             'got {!r} ({})'.format(self.MMD_KERNEL, err)) from None
+        return float(weights[0]), float(weights[1]), kind, scales
+
+    def prior_mmd(self, codes, y=None, epsilon=None):
+        """How far a set of latent codes is from the prior, with no density estimate -> (mmd2, rows): the unbiased U-statistic of
+        MMD^2 between codes (M, K) and as many draws of the prior, and its per-row terms (M,), fp32 on the device; the op of
+        TRAIN_OBJECTIVE = 'mmd' (ops.mmd_objective with one draw) under no_grad, with MMD_KERNEL and MMD_JOINT.  y (M,): the
+        labels of the codes, required for a class-conditional prior (each code is compared with draws of its own class) and
+        None for a single prior.  epsilon (M, K): the noise of the prior draws (default: drawn here).  M up to the op's limit
+        (8192).  Refuses what the objective refuses about the model."""
+        def refuse(what):
+            raise NotImplementedError('prior_mmd: ' + what)
+        self._iw_model_refusals(refuse)
+        pr = self.encoder.prior
+        if pr.conditional and y is None:
+            raise ValueError('prior_mmd: a class-conditional prior needs the labels y')
+        if not pr.conditional and y is not None:
+            raise ValueError('prior_mmd: y must be None for a model with a single prior')
+        if codes.dim() != 2 or codes.shape[1] != self.latent_dim:
+            raise ValueError('prior_mmd: codes must be (M, {}), got {}'.format(self.latent_dim, tuple(codes.shape)))
+        M, K = codes.shape
+        if epsilon is not None and tuple(epsilon.shape) != (M, K):
+            raise ValueError('prior_mmd: epsilon must be ({}, {}), got {}'.format(M, K, tuple(epsilon.shape)))
+        self._mmd_settings()
+        with torch.no_grad():
+            codes = codes.detach().to(torch.float32)
+            z = torch.stack([codes, codes])                                       # row 0 takes no part
+            e = (torch.randn((1, M, K), device=codes.device, dtype=torch.float32) if epsilon is None
+                 else epsilon.detach().to(torch.float32).reshape(1, M, K).contiguous())
+            lab, means, T = pr._kernel_operands(None if y is None else y.reshape(-1), M, codes.device)
+            rows = ops.mmd_objective(z, e, lab, means.detach(), T.detach(), kernel=self.MMD_KERNEL, joint=self.MMD_JOINT,
+                                     var_dim=pr.var_dim)
+            return rows.mean(), rows
 
     # ------------------------------------------------------------------------------------ semi-supervised training
     def _check_semi_supervised(self, kl_var_weighting, kw):
@@ -1709,13 +1819,16 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             self._mean_grad_key = key
         torch.autograd.backward(tot, grad_tensors=self._mean_grad)
 
-    def train_step(self, x, y, batch=0, current_measures=None, kl_var_weighting=1., gamma_weighting=1., epsilon=None):
-        """One iteration of the reference's hot loop (cvae.py:2429-2461): zero_grad, evaluate, backward, clip, step."""
+    def train_step(self, x, y, batch=0, current_measures=None, kl_var_weighting=1., gamma_weighting=1., epsilon=None,
+                   prior_epsilon=None):
+        """One iteration of the reference's hot loop (cvae.py:2429-2461): zero_grad, evaluate, backward, clip, step.
+        prior_epsilon: the noise of the prior draws of TRAIN_OBJECTIVE = 'mmd' (no other objective reads it)."""
         self.optimizer.zero_grad()
+        extra = {} if prior_epsilon is None else {'prior_epsilon': prior_epsilon}
         _, y_est, losses, measures = self.evaluate(x, y, batch=batch, with_beta=True,
                                                    kl_var_weighting=kl_var_weighting,
                                                    gamma_weighting=gamma_weighting,
-                                                   current_measures=current_measures, epsilon=epsilon)
+                                                   current_measures=current_measures, epsilon=epsilon, **extra)
         if self.optimizer.check_nonfinite():     # cvae.py:2454-2457: a NaN / Inf parameter ends the run BEFORE backward
             _grad_nan_exit()
         self._mean_backward(losses['total'])
@@ -2131,6 +2244,10 @@ class ClassificationVariationalNetwork(ScoringMixin, nn.Module):
             size = self.TC_DATASET_SIZE
             self.training_parameters['tc_weights'] = [float(w) for w in self.TC_WEIGHTS]
             self.training_parameters['tc_dataset_size'] = int(size) if np.ndim(size) == 0 else [int(v) for v in size]
+        if self.TRAIN_OBJECTIVE == 'mmd':
+            kl_weight, mmd_weight, kind, scales = self._mmd_settings()
+            self.training_parameters['mmd_weights'] = [kl_weight, mmd_weight]
+            self.training_parameters['mmd_kernel'] = {'kind': kind, 'scales': list(scales), 'joint': bool(self.MMD_JOINT)}
 
         from jvae_compat.recorders import LossRecorder
         sets = [set_name] + (['validation'] if validation else [])

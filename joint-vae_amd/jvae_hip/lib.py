@@ -219,6 +219,11 @@ _SIGS = {
     'jvae_semi_fwd_workspace_bytes': (c_size_t, [c_int] * 2),
     'jvae_semi_class_marginal_fwd_f32': (c_int, [P] * 6 + [c_int, c_float] + [c_int] * 3 + [P] * 7 + [c_size_t, P, c_size_t, P]),
     'jvae_semi_class_marginal_bwd_f32': (c_int, [P] * 6 + [c_int, c_float] + [c_int] * 3 + [P, c_size_t] + [P] * 6),
+    'jvae_mmd_tile': (c_int, []),
+    'jvae_mmd_fwd_workspace_bytes': (c_size_t, [c_int] * 3),
+    'jvae_mmd_bwd_workspace_bytes': (c_size_t, [c_int] * 3),
+    'jvae_mmd_objective_fwd_f32': (c_int, [P] * 5 + [c_int] * 2 + [P] + [c_int] * 6 + [P, P, c_size_t, P]),
+    'jvae_mmd_objective_bwd_f32': (c_int, [P] * 6 + [c_int] * 2 + [P] + [c_int] * 6 + [P] * 4 + [c_size_t, P]),
 }
 
 

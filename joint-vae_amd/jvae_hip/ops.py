@@ -1553,6 +1553,124 @@ def tc_objective(z, mu, log_var, eps, y, means, T, weights=(1., 6., 1.), log_n=N
     return _TcObjective.apply(z, mu, log_var, eps, y, means, T, log_n, (a, b, g, VAR_KIND[var_dim]))
 
 
+MMD_MAX_K, MMD_MAX_N, MMD_MAX_L, MMD_MAX_SCALES = 1024, 8192, 65535, 8       # the limits of csrc/mmd.hip
+MMD_KINDS = {'imq': 0, 'rbf': 1}
+MMD_WAE_SCALES = (.1, .2, .5, 1., 2., 5., 10.)       # WAE's seven scales, times 2 K for a unit-variance prior
+
+
+def mmd_tile():
+    """Rows of a workgroup's tile of mmd_objective's pair sums (host only)."""
+    return int(L.load().jvae_mmd_tile())
+
+
+def mmd_scales(kernel, K):
+    """(kind, scales) of a kernel = (kind, scales | None) as the library takes them: kind 'imq' | 'rbf', scales a tuple of 1..8
+    positive finite floats read as absolute C_s / h_s, None: 2 K s for WAE's seven s.  Plain numbers: they carry no gradient."""
+    try:
+        kind, scales = kernel
+    except (TypeError, ValueError):
+        raise L.JvaeHipError(f'mmd_objective: kernel is (kind, scales), got {kernel!r}') from None
+    if kind not in MMD_KINDS:
+        raise L.JvaeHipError(f'mmd_objective: kernel kind {kind!r} unknown (one of {sorted(MMD_KINDS)})')
+    if scales is None:
+        scales = tuple(2. * K * s for s in MMD_WAE_SCALES)
+    try:
+        scales = tuple(float(s) for s in scales)
+    except (TypeError, ValueError):
+        raise L.JvaeHipError(f'mmd_objective: scales is a tuple of numbers or None, got {scales!r}') from None
+    # positive and finite as the fp32 values the kernels read
+    if not 1 <= len(scales) <= MMD_MAX_SCALES or not all(0. < ctypes.c_float(s).value < float('inf') for s in scales):
+        raise L.JvaeHipError(f'mmd_objective: 1 to {MMD_MAX_SCALES} positive finite scales expected, got {scales!r}')
+    return kind, scales
+
+
+def _mmd_operand(t, shape, what, dtype=torch.float32):
+    if t.dtype != dtype:
+        raise L.JvaeHipError(f'mmd_objective: {what} must be {dtype}, got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise L.JvaeHipError(f'mmd_objective: {what} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+    return t
+
+
+class _MmdObjective(torch.autograd.Function):
+    """z (L+1,N,K), eps_p (L,N,K), y, means, T -> m (N,): csrc/mmd.hip."""
+
+    @staticmethod
+    def forward(ctx, z, eps_p, y, means, T, cfg):
+        kind, scales, joint, var_dim = cfg
+        if eps_p.dim() != 3:
+            raise L.JvaeHipError(f'mmd_objective: eps_p must have the shape (L, N, K), got {tuple(eps_p.shape)}')
+        Ls, N, K = eps_p.shape
+        C = means.shape[0] if means.dim() else 0
+        _mmd_operand(z, (Ls + 1, N, K), 'z')
+        _mmd_operand(eps_p, (Ls, N, K), 'eps_p')
+        _mmd_operand(y, (N,), 'y', torch.int64)
+        _mmd_operand(means, (C, K), 'means')
+        _mmd_operand(T, (C, K) if var_dim == VAR_KIND['diag'] else ((C, K, K) if var_dim == VAR_KIND['full'] else (C,)), 'T')
+        if Ls < 1 or K < 1 or C < 1:
+            raise L.JvaeHipError(f'mmd_objective: at least one draw, one coordinate and one class expected, got L={Ls}, K={K}, C={C}')
+        if K > MMD_MAX_K or N > MMD_MAX_N or Ls > MMD_MAX_L:
+            raise L.JvaeHipError(f'mmd_objective: K <= {MMD_MAX_K}, N <= {MMD_MAX_N} and L <= {MMD_MAX_L} expected, got N={N}, K={K}, '
+                                 f'L={Ls} (unsupported configuration)')
+        operands = [L.ptr(t) for t in (z, eps_p, y, means, T)]      # on the device and contiguous, before anything is allocated
+        dev = eps_p.device
+        lib = L.load()
+        sc = (ctypes.c_float * len(scales))(*scales)
+        m = torch.empty(N, device=dev, dtype=torch.float32)
+        ws = _aligned_ws(lib.jvae_mmd_fwd_workspace_bytes(Ls, N, K), dev, align=16, what='mmd_objective') if N else (None, 0)
+        rc = lib.jvae_mmd_objective_fwd_f32(*operands, var_dim, MMD_KINDS[kind], sc, len(scales), int(joint), Ls, N, K, C, L.ptr(m),
+                                            *ws, L.stream_ptr())
+        L.check(rc, 'jvae_mmd_objective_fwd_f32')
+        ctx.save_for_backward(z, eps_p, y, means, T)
+        ctx.cfg = (kind, scales, joint, var_dim, Ls, N, K, C)
+        ctx.set_materialize_grads(False)
+        return m
+
+    @staticmethod
+    def backward(ctx, g_m):
+        z, eps_p, y, means, T = ctx.saved_tensors
+        kind, scales, joint, var_dim, Ls, N, K, C = ctx.cfg
+        dev = z.device
+        lib = L.load()
+        g_z = torch.empty((Ls + 1, N, K), device=dev, dtype=torch.float32)
+        g_means = torch.empty_like(means) if ctx.needs_input_grad[3] else None
+        g_T = torch.empty_like(T) if ctx.needs_input_grad[4] else None
+        sc = (ctypes.c_float * len(scales))(*scales)
+        nbytes = lib.jvae_mmd_bwd_workspace_bytes(Ls, N, K) if N else 16
+        ws = _aligned_ws(nbytes, dev, align=16, what='mmd_objective')
+        g = None if g_m is None else _c(g_m)
+        rc = lib.jvae_mmd_objective_bwd_f32(L.ptr(g), L.ptr(z), L.ptr(eps_p), L.ptr(y), L.ptr(means), L.ptr(T), var_dim, MMD_KINDS[kind],
+                                            sc, len(scales), int(joint), Ls, N, K, C, L.ptr(g_z), L.ptr(g_means), L.ptr(g_T), *ws,
+                                            L.stream_ptr())
+        L.check(rc, 'jvae_mmd_objective_bwd_f32')
+        return g_z, None, None, g_means, g_T, None
+
+
+def mmd_objective(z, eps_p, y, means, T, kernel=('imq', None), joint=True, var_dim='scalar'):
+    """The per-row terms of the unbiased U-statistic of MMD^2 between the step's draws and draws of the class-conditional Gaussian
+    prior (InfoVAE, Zhao et al. 2019; WAE-MMD, Tolstikhin et al. 2018) -> m (N,), csrc/mmd.hip:
+
+        p_li = means[y_i] + eps_p_li / T[y_i]                    (prior_sample's 'scalar' / 'diag' expression, bit for bit)
+        m_i = mean_l [ 1/(N-1) sum_{j in S_i, j != i} k(z_li, z_lj) + 1/(N-1) sum_{j in S_i, j != i} k(p_li, p_lj)
+                       - 2/N sum_{j in S_i} k(z_li, p_lj) ]
+
+    with S_i the rows of the batch that carry the sample's label (joint=False or one class: the whole batch), so that mean_i m_i
+    estimates the MMD between the joint laws q(z, y) and pi_hat(y) p(z | y).  z (L+1, N, K) of latent (row 0 takes no part: its
+    gradient is 0), eps_p (L, N, K) the noise of the prior draws, y (N,) int64, means (C, K) and T ((C,) 'scalar' / (C, K) 'diag')
+    of the Gaussian prior.  kernel = (kind, scales): 'imq' sum_s C_s / (C_s + d^2) or 'rbf' sum_s exp(-d^2 / (2 h_s)), scales a
+    tuple of at most 8 positive floats or None (2 K s for WAE's seven s); d^2 is the direct sum of squared differences.
+    Differentiable in z, means and T with the DIRECT partial derivatives (kernel values are formed again in the backward, nothing
+    of size (L, N, N) is kept); autograd carries z on through latent's backward.  Operands must be fp32 (y int64), contiguous and
+    on the device.  K <= 1024, N <= 8192; var_dim 'full' is refused by the library.  A label outside [0, C): NaN in every output
+    of that sample, which is in nobody's set."""
+    if var_dim not in VAR_KIND:
+        raise L.JvaeHipError(f'mmd_objective: var_dim {var_dim!r} unknown')
+    if eps_p.dim() != 3:
+        raise L.JvaeHipError(f'mmd_objective: eps_p must have the shape (L, N, K), got {tuple(eps_p.shape)}')
+    kind, scales = mmd_scales(kernel, eps_p.shape[-1])
+    return _MmdObjective.apply(z, eps_p, y, means, T, (kind, scales, bool(joint), VAR_KIND[var_dim]))
+
+
 SEMI_MAX_K, SEMI_MAX_C, SEMI_MAX_N = 1024, 1024, 1 << 20       # the limits of csrc/semisup.hip
 
 
